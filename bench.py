@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py - throughput of the Frenet candidate hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 Workload at N = 1 (BASELINE.json configs[2], the configuration the metric is quoted on): a batch of 2048 synthetic ego
 problems, 9x9x7 (d, v, T) lattice = 567 candidates per ego, 50 dynamic rectangle obstacles with a 5 s / 50-step pose
@@ -18,13 +18,24 @@ The synthetic scenes come from SURVEY.md section 8(d)'s generator verbatim (`--l
 region cycles through `--rotate` (default 4) DISTINCT batches of that generator, so no launch ever sees the batch the
 feedback-directed launch order was learnt on.
 
+A plain run does only what the headline needs: set up, wake the device and warm up, time exactly K steps, write the
+outputs (--dump-outputs), print the line.  `--full` adds everything else, after the timed region: the cold-start timing,
+the oracle parity gates, the CPU baselines, the plan-cycle latency and materialise legs and the other single-GPU legs.
+
 Prints ONE compact JSON line (rank 0; < 4 KB, the last and only thing on stdout) with the driver's contract fields plus
-`roofline`, `cpu_baseline`, a short `parity` and `legs` (ms per step + parity verdict of the other single-GPU legs).  The
-full record of the run - the other configurations (`config2`, `config4`), the index-order and single-batch variants of
-the headline workload, the builder's `lanes` obstacle layout, the device-resident closed loop (`closed_loop`), the
-PCIe-inclusive host-buffer entry (`host_buffers`), every leg's complete `parity` object - goes to `bench_extras.json`
-next to this file ($BENCH_EXTRAS_FILE overrides the path).  EVERY leg that reports a number was compared with the CPU
-oracle in this run (index / Stats exact, cost <= 1e-6) and a mismatch aborts before anything is printed.
+`roofline` and, with --full, `cpu_baseline`, a short `parity` and `legs` (ms per step + parity verdict of the other
+single-GPU legs).  The full record of the run - with --full the other configurations (`config2`, `config4`), the
+index-order and single-batch variants of the headline workload, the builder's `lanes` obstacle layout, the
+device-resident closed loop (`closed_loop`), the PCIe-inclusive host-buffer entry (`host_buffers`), every leg's complete
+`parity` object - goes to `bench_extras.json` next to this file ($BENCH_EXTRAS_FILE overrides the path).  With --full,
+EVERY leg that reports a number was compared with the CPU oracle in this run (index / Stats exact, cost <= 1e-6) and a
+mismatch aborts before anything is printed.
+
+--dump-outputs DIR writes what the last timed step computed - the arrays a caller of the timed path receives (best index /
+cost, Stats, winner flag words and series; FISS+: best (i, j, k), refined, end state) - as DIR/<name>.npy in float64,
+with the values the ABI marks as absent (NaN: no winner, series padding) written as 0, at most DUMP_LIMIT bytes in all (a fixed, seeded sample of egos when the outputs are larger; `sample_rows.npy` names
+them).  The inputs are fixed by the generator's seeds, so two builds given the same arguments can be compared output
+for output.  At N > 1 every rank writes its own shard, the file names suffixed `_rank<r>`.
 """
 from __future__ import annotations
 
@@ -178,6 +189,62 @@ def emit(full: dict) -> None:
     print(text, flush=True)
 
 
+# ---- --dump-outputs: what the timed path computed in its last step, for output-by-output comparison of two builds
+DUMP_LIMIT = 60_000_000  # bytes of .npy data per run, all ranks together (the ceiling is 64 MB; the .npy headers ride on top)
+DUMP_SEED = 8161         # the fixed sample of egos taken when the outputs are larger
+
+
+def absent_to_zero(out: dict, fiss: bool) -> dict:
+    """The ABI marks values that do not exist with NaN (include/frenet_gpu.h): best_cost (and FISS+ end_state) of an ego without a
+    result, the whole series block of such an ego, and a series row's elements past its length - N for the Frenet rows 0-8, M for
+    x / y / yaw, M-1 for ds / c, M-2 for c_d, M-3 for c_dd.  Exactly those become 0 (best_idx = -1 / best_ijk = -1 with refined = 0,
+    and best_flags, say which values are absent); any other non-finite value is left as it is."""
+    out = dict(out)
+    none = ((out["best_ijk"][:, 0] < 0) & (out["refined"] == 0)) if fiss else out["best_idx"] < 0
+    zero = lambda a, absent: np.where(absent & np.isnan(a), 0.0, a)  # noqa: E731
+    out["best_cost"] = zero(out["best_cost"], none)
+    if fiss:
+        out["end_state"] = zero(out["end_state"], none[:, None])
+    fl = out["best_flags"].astype(np.int64)
+    N, M = (fl >> 8) & 0xFFF, fl >> 20
+    row_len = np.stack([N] * 9 + [M] * 3 + [M - 1] * 2 + [M - 2, M - 3], axis=1)                        # [B, 16]
+    col = np.arange(out["best_traj"].shape[2])
+    present = (fl != 0)[:, None, None] & (col[None, None, :] < row_len[:, :, None])                    # [B, 16, stride]
+    out["best_traj"] = zero(out["best_traj"], ~present)
+    return out
+
+
+def workload_outputs(wl) -> dict:
+    """The arrays a caller of the timed path receives from `wl`'s last step, per ego along the first axis, with the values the ABI
+    marks as absent set to 0 (absent_to_zero: every array written is finite unless a result itself is not)."""
+    out = {"best_cost": wl.h_cost.numpy(), ("refined" if wl.fiss else "best_idx"): wl.h_idx.numpy(), "stats": wl.stats.cpu().numpy(),
+           "best_flags": wl.best_flags.cpu().numpy().view(np.uint32), "best_traj": wl.best_traj.cpu().numpy()}
+    if wl.fiss:
+        out["best_ijk"], out["end_state"] = wl.ijk.cpu().numpy(), wl.end_state.cpu().numpy()
+    if wl.tables:
+        out["cost_tbl"], out["flag_tbl"] = wl.cost_tbl.cpu().numpy(), wl.flag_tbl.cpu().numpy().view(np.uint32)
+    return absent_to_zero(out, wl.fiss)
+
+
+def write_outputs(path: str, arrays: dict, limit: int = DUMP_LIMIT, suffix: str = "") -> int:
+    """arrays (name -> per-ego array) as path/<name><suffix>.npy in float64 (exact for the int32 / uint32 outputs).  Over `limit`
+    bytes: the same seeded sample of egos from every array, and `sample_rows` names them.  Returns the bytes written."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    B = {a.shape[0] for a in arrays.values()}
+    assert len(B) == 1, "every output is per ego"
+    B = B.pop()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > limit:
+        k = max(1, int(limit // (total / B + 8)))
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(B, k, replace=False))
+        arrays = {n: a[rows] for n, a in arrays.items()}
+        arrays["sample_rows"] = rows.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for n, a in arrays.items():
+        np.save(os.path.join(path, f"{n}{suffix}.npy"), a)
+    return sum(a.nbytes for a in arrays.values())
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -193,7 +260,15 @@ def parse():
     ap.add_argument("--tables", action="store_true", help="also write the dense cost/flag tables (materialised mode)")
     ap.add_argument("--no-latency", action="store_true", help="skip the single-ego plan-cycle latency leg (configs[0]) and the materialise leg")
     ap.add_argument("--no-extras", action="store_true", help="skip the extra single-GPU workloads (config2, config4, index order, rotating batches, survey layout)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline after the timed region: cold-start timing, oracle parity gates, CPU baselines, "
+                         "plan-cycle latency, materialise mode and the other single-GPU legs (--cpu-seconds, --no-latency, --no-extras shape it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float64, a seeded sample of egos beyond 60 MB)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def spawn_ranks(args) -> None:
@@ -266,9 +341,10 @@ class Workload:
         self.flag_tbl = torch.empty((B, C), dtype=torch.int32, device=dev) if tables else None
         self.best_flags = torch.zeros(B, dtype=torch.int32, device=dev)
         # winner epilogue output, stays in HBM.  Compact layout of the ABI (fp_result.traj_stride / traj_sparse): rows of
-        # ceil(max T / tick) columns, only the elements that exist are written - the bytes written ARE the algorithmic bytes
+        # ceil(max T / tick) columns, only the elements that exist are written - the bytes written ARE the algorithmic bytes.  NaN
+        # elsewhere, as the host entry points hand it over (every step of a workload plans the same batch, so writes the same elements)
         self.traj_stride = (int(np.ceil(batch.t_samples.max() / batch.tick_t)) + 15) // 16 * 16   # whole 128-byte lines per row
-        self.best_traj = torch.empty((B, 16, self.traj_stride), dtype=torch.float64, device=dev)
+        self.best_traj = torch.full((B, 16, self.traj_stride), float("nan"), dtype=torch.float64, device=dev)
         self.h_packed = torch.empty(12 * B, dtype=torch.uint8).pin_memory()
         self.h_cost = self.h_packed[:8 * B].view(torch.float64)
         self.h_idx = self.h_packed[8 * B:].view(torch.int32)
@@ -792,6 +868,12 @@ def main():
         raise SystemExit(f"bench.py: --gpus {args.gpus} but the launcher started WORLD_SIZE={world} ranks")
     config = args.config or (3 if world == 1 else 5)
     os.environ.setdefault("OMP_WAIT_POLICY", "PASSIVE")
+    if world > 1:
+        # the gloo backend's native side writes its connection messages ("[Gloo] Rank 1 is connected to 7 peer ranks ...") to fd 1,
+        # interleaved between the ranks mid-line: native writes of a rank go to stderr, Python's stdout keeps the real one for the line
+        out_fd = os.dup(1)
+        os.dup2(2, 1)
+        sys.stdout = os.fdopen(out_fd, "w")
     import torch
 
     if not torch.cuda.is_available():
@@ -842,7 +924,7 @@ def main():
     # exactly K timed ones.  BENCH_PREWARM_S=0 turns it off.
     prewarm_s = float(os.environ.get("BENCH_PREWARM_S", "0.25"))
     cold = None
-    if prewarm_s > 0:  # the same W + K steps WITHOUT the wake-up first, reported beside the headline (`cold_start`)
+    if prewarm_s > 0 and args.full:  # the same W + K steps WITHOUT the wake-up first, reported beside the headline (`cold_start`)
         el_c, _ = timed_run(torch, wls, args.steps, args.warmup, stream, barrier)
         cold = {"ms_per_step": el_c / args.steps * 1e3, "value": float(np.mean([w.candidates for w in wls])) * args.steps / el_c * world,
                 "what": "the W warm-up + K timed steps of this invocation run first, in the fresh process, before any wake-up: the GPU is on its clock ramp (rank 0's time)"}
@@ -860,13 +942,16 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     kern_ms = float(np.mean(kern_list))
-    solo = rank == 0 and world == 1
+    if args.dump_outputs:  # the workload of the last timed step; its outputs are complete (timed_run ends in a synchronize)
+        write_outputs(args.dump_outputs, workload_outputs(wls[(args.warmup + args.steps - 1) % n_rot]), DUMP_LIMIT // world,
+                      f"_rank{rank}" if world > 1 else "")
+    solo = rank == 0 and world == 1 and args.full  # the legs below beyond the headline run with --full only
     threads_all = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
     gate_threads = min(threads_all, 64)
 
-    # ---- parity gates + CPU baseline (rank 0, N=1 only), AFTER the timed region (libgomp workers spin after a parallel region
+    # ---- parity gates + CPU baseline (rank 0, N=1, --full only), AFTER the timed region (libgomp workers spin after a parallel region
     # and would steal the launch thread's core); any mismatch aborts before anything is printed.
-    for w in wls:  # every batch of the rotation leaves the results of its last step behind
+    for w in wls:  # every batch of the rotation leaves the results of its last step behind (the line's byte count and feasible share)
         w.step(); w.fetch()
     torch.cuda.synchronize(dev)
     cpu = {}

@@ -121,3 +121,62 @@ def test_line_from_the_current_rounds_full_record():
     assert built == printed
     assert printed["legs"]["overlap"]["parity_ok"] is True and printed["legs"]["config4"]["ms_per_step"] < 0.21
     assert printed["roofline"]["traffic"] < 1.2 * printed["roofline"]["algorithmic_bytes_per_launch"]
+
+
+def test_dump_outputs_are_float64_and_a_fixed_sample_beyond_the_limit(tmp_path):
+    """--dump-outputs: every output as <name>.npy in float64 (exact for int32 / uint32 words); over the limit the same seeded sample
+    of egos from every array, named by sample_rows.npy, and the same sample on every run."""
+    import numpy as np
+
+    rng = np.random.default_rng(1)
+    arrays = {"best_idx": rng.integers(-1, 567, 1000).astype(np.int32), "best_flags": rng.integers(0, 2**32, 1000, dtype=np.uint64).astype(np.uint32),
+              "best_traj": rng.standard_normal((1000, 16, 8))}
+    assert bench.write_outputs(str(tmp_path / "all"), arrays) == 1000 * (8 + 8 + 16 * 8 * 8)
+    for k, v in arrays.items():
+        got = np.load(tmp_path / "all" / f"{k}.npy")
+        assert got.dtype == np.float64 and np.array_equal(got, v.astype(np.float64))
+    assert not (tmp_path / "all" / "sample_rows.npy").exists()
+    limit = 100_000
+    n = bench.write_outputs(str(tmp_path / "a"), arrays, limit, "_rank1")
+    assert n <= limit
+    rows = np.load(tmp_path / "a" / "sample_rows_rank1.npy").astype(np.int64)
+    assert 0 < len(rows) < 1000 and np.array_equal(rows, np.unique(rows))
+    for k, v in arrays.items():
+        assert np.array_equal(np.load(tmp_path / "a" / f"{k}_rank1.npy"), v[rows].astype(np.float64))
+    bench.write_outputs(str(tmp_path / "b"), arrays, limit, "_rank1")
+    assert np.array_equal(np.load(tmp_path / "b" / "sample_rows_rank1.npy"), rows)
+
+
+def test_dump_zeroes_exactly_what_the_abi_marks_absent(oracle):
+    """absent_to_zero: NaN where include/frenet_gpu.h says a value does not exist becomes 0 - the series past each row's length (the
+    region is the oracle's own non-NaN pattern of the winner's series, exactly), everything of an ego without a result (FOP: best_idx
+    -1; FISS+: best_ijk -1 and not refined) - and any other non-finite value stays, so a defect still shows."""
+    import numpy as np
+
+    from fiss_plus_planner_amd import synth
+
+    b = synth.make_config(3, B=48)
+    probs = oracle.problems_from_batch(b, list(range(b.B)))
+    idx, _ = oracle.fop_plan_batch(probs, threads=4)
+    winners = np.nonzero(idx >= 0)[0][:16]
+    assert len(winners) >= 8
+    for e in winners:
+        bi = int(idx[e])
+        t = probs[e].eval_traj(b.d_samples[bi // (b.nv * b.nt)], b.v_samples[e, bi % b.nv], b.t_samples[(bi // b.nv) % b.nt], dump=True, stride=112)
+        fl = np.array([t.N << 8 | t.M << 20], dtype=np.uint32)
+        out = bench.absent_to_zero({"best_idx": np.array([bi]), "best_cost": np.array([np.nan]), "best_flags": fl,
+                                    "best_traj": np.full((1, 16, 112), np.nan)}, fiss=False)
+        assert np.array_equal(np.isnan(out["best_traj"][0]), ~np.isnan(t.arrays)), (e, t.N, t.M)
+        assert np.isnan(out["best_cost"][0])  # a winner's cost is never zeroed
+    none = bench.absent_to_zero({"best_idx": np.array([-1]), "best_cost": np.array([np.nan]), "best_flags": np.zeros(1, np.uint32),
+                                 "best_traj": np.full((1, 16, 112), np.nan)}, fiss=False)
+    assert none["best_cost"][0] == 0 and (none["best_traj"] == 0).all()
+    inf = bench.absent_to_zero({"best_idx": np.array([-1]), "best_cost": np.array([np.inf]), "best_flags": np.zeros(1, np.uint32),
+                                "best_traj": np.full((1, 16, 112), np.inf)}, fiss=False)
+    assert np.isinf(inf["best_cost"][0]) and np.isinf(inf["best_traj"]).all()
+    # FISS+: none = best_ijk -1 and refined 0; a refined result has best_ijk -1 too, and keeps its values
+    f = bench.absent_to_zero({"best_ijk": np.array([[-1, -1, -1], [-1, -1, -1], [2, 3, 4]]), "refined": np.array([0, 1, 0]),
+                              "best_cost": np.array([np.nan, np.nan, np.nan]), "end_state": np.full((3, 3), np.nan),
+                              "best_flags": np.zeros(3, np.uint32), "best_traj": np.full((3, 16, 16), np.nan)}, fiss=True)
+    assert f["best_cost"][0] == 0 and (f["end_state"][0] == 0).all()
+    assert np.isnan(f["best_cost"][1:]).all() and np.isnan(f["end_state"][1:]).all()

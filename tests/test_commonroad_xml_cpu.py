@@ -1,15 +1,28 @@
 """CPU: the CommonRoad XML reader against (a) the committed Flensburg fixture arrays and (b) all five demo files.
-Needs the reference's data files, which exist in the build container only: skipped elsewhere."""
+The five demo scenarios are stored xz-compressed under tests/golden/demo/ and unpacked into a temporary directory, so the
+reader parses ordinary .xml files as a caller would hand them over."""
 import glob
+import lzma
 import os
+import shutil
 
 import numpy as np
 import pytest
 
-from conftest import load_golden
+from conftest import GOLDEN, load_golden
 
-DEMO = "/root/reference/data/demo"
-pytestmark = pytest.mark.skipif(not os.path.isdir(DEMO), reason="reference data files are not present on this machine")
+DEMO = None  # the unpacked scenarios (set by _demo_dir)
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _demo_dir(tmp_path_factory):
+    global DEMO
+    DEMO = str(tmp_path_factory.mktemp("demo"))
+    for src in sorted(glob.glob(os.path.join(GOLDEN, "demo", "*.xml.xz"))):
+        with lzma.open(src) as f, open(os.path.join(DEMO, os.path.basename(src)[:-3]), "wb") as g:
+            shutil.copyfileobj(f, g)
+    yield
+    shutil.rmtree(DEMO, ignore_errors=True)
 
 
 def test_flensburg_matches_fixture():

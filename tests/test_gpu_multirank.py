@@ -30,8 +30,8 @@ def _run_bench(extra, env_extra=None, timeout=900, tmp_path=None):
     env = dict(os.environ, BENCH_EXTRAS_FILE=extras_file, **(env_extra or {}))
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + extra, env=env, capture_output=True, text=True, timeout=timeout, cwd=ROOT)
     assert out.returncode == 0, (out.stdout[-2000:], out.stderr[-4000:])
-    # (the gloo test hook chats on stdout - "[Gloo] Rank 1 is connected to 7 peer ranks ...", interleaved between ranks; RCCL prints nothing)
-    lines = [l for l in out.stdout.splitlines() if l.strip() and "Gloo" not in l and "peer ranks" not in l]
+    # (the ranks' native output - gloo's "[Gloo] Rank 1 is connected to 7 peer ranks ..." - goes to stderr: stdout is the line alone)
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1 and lines[0].startswith("{"), out.stdout[-2000:]   # nothing before, nothing after the line
     assert out.stdout.rstrip("\n").splitlines()[-1] == lines[0]               # ... and it is the LAST line
     assert len(lines[0].encode()) < bench_mod.LINE_LIMIT
@@ -44,9 +44,11 @@ def _run_bench(extra, env_extra=None, timeout=900, tmp_path=None):
 
 
 def test_bench_gpus_2_spawns_two_ranks(tmp_path):
-    line, _ = _run_bench(["--gpus", "2", "--steps", "6", "--warmup", "2", "--egos", "512"],
+    line, _ = _run_bench(["--gpus", "2", "--steps", "6", "--warmup", "2", "--egos", "512", "--dump-outputs", str(tmp_path / "out")],
                          {"BENCH_DIST_BACKEND": "gloo", "BENCH_ALL_ON_DEVICE0": "1"}, tmp_path=tmp_path)
     assert line["n_gpus"] == 2 and line["steps"] == 6 and line["warmup"] == 2
+    for r in (0, 1):  # every rank writes its own shard
+        assert np.load(tmp_path / "out" / f"best_idx_rank{r}.npy").shape == (512,)
     assert line["scaling"] == "weak" and line["unit"] == "candidates/s"
     assert "configs[4]" in line["config"]["workload"]
     # whole-job aggregate: both ranks' candidates over the max-over-ranks time
@@ -76,7 +78,7 @@ def test_bench_gpus_8_on_one_device(tmp_path):
 
 
 def test_bench_single_gpu_line_has_every_configuration(tmp_path):
-    cline, line = _run_bench(["--steps", "8", "--warmup", "2", "--cpu-seconds", "2", "--no-latency"], tmp_path=tmp_path)
+    cline, line = _run_bench(["--full", "--steps", "8", "--warmup", "2", "--cpu-seconds", "2", "--no-latency"], tmp_path=tmp_path)
     # the compact line: the contract's numbers, and one ms + verdict per leg
     assert cline["n_gpus"] == 1 and "configs[2]" in cline["config"]["workload"] and cline["parity"]["index_exact"] is True
     assert cline["roofline"]["bound"] == "hbm" and 0 < cline["roofline"]["frac"] < 1 and cline["roofline"]["kernel_ms"] > 0
@@ -116,6 +118,45 @@ def test_bench_single_gpu_line_has_every_configuration(tmp_path):
     assert line["host_buffers"]["value"] > 0 and line["host_buffers"]["parity"]["index_exact"]
     assert line["cpu_baseline"]["kind"] == "port" and line["cpu_baseline_1thread"]["cores"] == 1
     assert line["cpu_baseline"]["cores"] >= 1 and "thread_sweep" in line["cpu_baseline"] and "host" in line["cpu_baseline"]
+
+
+def test_bench_plain_run_is_the_headline_and_dumps_its_last_step(oracle, tmp_path):
+    """Without --full: exactly K timed steps, the headline's figures and nothing of the other legs; --dump-outputs holds what the
+    LAST timed step computed (batch (W + K - 1) mod 4 of the rotation), in float64, and it agrees with the oracle."""
+    egos, steps, warmup = 256, 6, 2
+    line, full = _run_bench(["--steps", str(steps), "--warmup", str(warmup), "--egos", str(egos), "--dump-outputs", str(tmp_path / "out")],
+                            tmp_path=tmp_path)
+    assert line["n_gpus"] == 1 and line["steps"] == steps and line["warmup"] == warmup and line["ms_per_step"] > 0
+    assert abs(line["value"] - egos * 567 * steps / (line["ms_per_step"] * steps * 1e-3)) / line["value"] < 1e-5
+    assert line["roofline"]["kernel_ms"] > 0 and line["higher_is_better"] is True and line["dtype"] == "f64"
+    assert line["cpu_baseline"] is None and line["parity"] is None and line["legs"] is None and line["value_cold"] is None
+    assert "config2" not in full and "closed_loop" not in full
+    files = sorted(p.name for p in (tmp_path / "out").iterdir())
+    assert files == ["best_cost.npy", "best_flags.npy", "best_idx.npy", "best_traj.npy", "stats.npy"]
+    out = {f[:-4]: np.load(tmp_path / "out" / f) for f in files}
+    assert all(a.dtype == np.float64 and a.shape[0] == egos for a in out.values())
+    assert sum(a.nbytes for a in out.values()) <= 64e6
+    k = (warmup + steps - 1) % 4
+    batch = synth.make_config(3, B=egos, ego_offset=k * egos)
+    assert batch.digest()[:16] == full["config"]["input_digests"][k]
+    sample = np.arange(0, egos, 8)
+    idx, cost = oracle.fop_plan_batch(oracle.problems_from_batch(batch, sample), threads=len(os.sched_getaffinity(0)))
+    np.testing.assert_array_equal(out["best_idx"][sample], idx)
+    good = idx >= 0
+    np.testing.assert_allclose(out["best_cost"][sample][good], cost[good], rtol=0, atol=COST_TOL)
+    # every value is finite: what the ABI marks as absent (NaN) is 0 - the cost and the whole series of an ego without a winner, a
+    # winner's series past each row's length; a winner's rows 0-10 are the oracle's, within the parity gate's 1e-8
+    assert all(np.isfinite(a).all() for a in out.values())
+    none = out["best_idx"] < 0
+    assert np.array_equal(out["best_flags"] != 0, ~none)
+    assert (out["best_cost"][none] == 0).all() and (out["best_traj"][none] == 0).all()
+    for e in sample[good][:8]:
+        bi = int(out["best_idx"][e])
+        iv, it, i_d = bi % batch.nv, (bi // batch.nv) % batch.nt, bi // (batch.nv * batch.nt)
+        t = oracle.problems_from_batch(batch, [e])[0].eval_traj(batch.d_samples[i_d], batch.v_samples[e, iv], batch.t_samples[it], dump=True,
+                                                                 stride=out["best_traj"].shape[2])
+        want = np.nan_to_num(t.arrays, nan=0.0)
+        assert np.abs(out["best_traj"][e][:11] - want[:11]).max() <= 1e-8, e
 
 
 def test_config5_full_batch_equals_its_eight_shards(oracle, engine):
