@@ -1704,6 +1704,9 @@ int plan_fiss_impl(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, 
         if (!trace_doubles) fa.io.trace = nullptr;
     } else {
         FP_TRY(check_batch_host(params, batch));
+        for (size_t i = 0; R > 0 && i < B; ++i)  // (a refinement probe beyond FP_MAX_POINTS would come back as NaN cost: a silently different walk)
+            if (ceil(io->samp_max[3 * i + 2] / params->tick_t) > FP_MAX_POINTS)
+                return fail(FP_ELIMIT, "samp_max[%zu].T=%g needs more than FP_MAX_POINTS points (FISS+ refinement)", i, io->samp_max[3 * i + 2]);
         fa.ka.p.points_max = host_points_max(params, batch, R > 0 ? io->samp_max + 2 : nullptr, R > 0 ? B : 0, 3);  // (refined trajectories reach T = samp_max)
         if (io->best_traj) {
             for (size_t i = 0; i < B; ++i)  // refined trajectories reach T = samp_max of their ego

@@ -96,72 +96,64 @@ __device__ __forceinline__ void quartic_eval(const Quartic& q, double t, double&
 
 // ---------------------------------------------------------------------------
 // Cost sums in closed form.  Every summand of CostFunction.cost_total (cost_function.py:29-50) is the square of a
-// polynomial in t, so  sum_i p(t_i)^2 = sum_k (p * p)_k S_k  with the power sums S_k = sum_{i<N} t_i^k, k = 0..10.
+// polynomial in t, so  sum_i p(t_i)^2 = sum_k (p * p)_k S_k  with power sums S_k.  The sums are taken about the centre of the samples,
+// c = (N - 1) tick / 2: p is re-expanded in u = t - c (Taylor shift) and S_k = sum_{i<N} (t_i - c)^k, which vanish for odd k.  In the
+// monomial basis of t itself the lateral quintic's squared coefficients cancel (|d_d| ~ 3, |d_dd| ~ 2 and T = 25.6 s: terms of ~1e8 for
+// a sum of ~1e3, relative errors up to 1e-11 at N = 256 and 1e-12 at N = 100); about the centre the terms do not cancel.
 //   lon[3] = sum (s_d - v_target)^2, sum s_dd^2, sum s_ddd^2      lat[3] = sum d_dd^2, sum d_ddd^2, sum d^2
 // Even in the lateral boundary data: mirrored candidates give bit-identical sums.
 // ---------------------------------------------------------------------------
+
+// p(t) = sum_k a_k t^k  ->  sum_k b_k (t - c)^k, b_k = p^(k)(c) / k!  (repeated synthetic division)
+template <int D>
+__device__ __forceinline__ void taylor_shift(double* a, double c)
+{
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+#pragma unroll
+        for (int j = D - 1; j >= i; --j) a[j] = fma(a[j + 1], c, a[j]);
+    }
+}
+
+// sum_k (e * e)_k S_k over the even k (the centred odd sums are 0); e has D + 1 coefficients
+template <int D>
+__device__ __forceinline__ double centred_square_sum(const double* e, const double* S)
+{
+    double s = 0.0;
+#pragma unroll
+    for (int kk = 0; kk <= 2 * D; kk += 2) {
+        double ck = 0.0;
+#pragma unroll
+        for (int a2 = 0; a2 <= D; ++a2) {
+            const int b2 = kk - a2;
+            if (b2 >= 0 && b2 <= D) ck = fma(e[a2], e[b2], ck);
+        }
+        s = fma(ck, S[kk], s);
+    }
+    return s;
+}
+
 __device__ __forceinline__ void lon_cost_sums(const Quartic& q, double target_speed, const double* S, double* lon)
 {
-    const double e0 = q.a1 - target_speed, e1 = 2.0 * q.a2, e2 = 3.0 * q.a3, e3 = 4.0 * q.a4;
-    const double g0 = 2.0 * q.a2, g1 = 6.0 * q.a3, g2 = 12.0 * q.a4;
-    const double h0 = 6.0 * q.a3, h1 = 24.0 * q.a4;
-    double sv = e0 * e0 * S[0];
-    sv = fma(2.0 * e0 * e1, S[1], sv);
-    sv = fma(fma(2.0 * e0, e2, e1 * e1), S[2], sv);
-    sv = fma(2.0 * fma(e0, e3, e1 * e2), S[3], sv);
-    sv = fma(fma(2.0 * e1, e3, e2 * e2), S[4], sv);
-    sv = fma(2.0 * e2 * e3, S[5], sv);
-    sv = fma(e3 * e3, S[6], sv);
-    double sa = g0 * g0 * S[0];
-    sa = fma(2.0 * g0 * g1, S[1], sa);
-    sa = fma(fma(2.0 * g0, g2, g1 * g1), S[2], sa);
-    sa = fma(2.0 * g1 * g2, S[3], sa);
-    sa = fma(g2 * g2, S[4], sa);
-    double sj = h0 * h0 * S[0];
-    sj = fma(2.0 * h0 * h1, S[1], sj);
-    sj = fma(h1 * h1, S[2], sj);
-    lon[0] = sv; lon[1] = sa; lon[2] = sj;
+    double b[5] = {q.a0, q.a1, q.a2, q.a3, q.a4};
+    taylor_shift<4>(b, S[1]);
+    const double e[4] = {b[1] - target_speed, 2.0 * b[2], 3.0 * b[3], 4.0 * b[4]};  // s_d - v_target
+    const double g[3] = {2.0 * b[2], 6.0 * b[3], 12.0 * b[4]};                     // s_dd
+    const double h[2] = {6.0 * b[3], 24.0 * b[4]};                                 // s_ddd
+    lon[0] = centred_square_sum<3>(e, S);
+    lon[1] = centred_square_sum<2>(g, S);
+    lon[2] = centred_square_sum<1>(h, S);
 }
 
 __device__ __forceinline__ void lat_cost_sums(const Quintic& q, const double* S, double* lat)
 {
-    const double c[6] = {q.a0, q.a1, q.a2, q.a3, q.a4, q.a5};
-    double sd = 0.0;
-#pragma unroll
-    for (int kk = 0; kk <= 10; ++kk) {
-        double ck = 0.0;
-#pragma unroll
-        for (int a2 = 0; a2 <= 5; ++a2) {
-            const int b2 = kk - a2;
-            if (b2 >= 0 && b2 <= 5) ck = fma(c[a2], c[b2], ck);
-        }
-        sd = fma(ck, S[kk], sd);
-    }
-    const double g[4] = {2.0 * q.a2, 6.0 * q.a3, 12.0 * q.a4, 20.0 * q.a5};  // d_dd
-    double sa = 0.0;
-#pragma unroll
-    for (int kk = 0; kk <= 6; ++kk) {
-        double ck = 0.0;
-#pragma unroll
-        for (int a2 = 0; a2 <= 3; ++a2) {
-            const int b2 = kk - a2;
-            if (b2 >= 0 && b2 <= 3) ck = fma(g[a2], g[b2], ck);
-        }
-        sa = fma(ck, S[kk], sa);
-    }
-    const double h[3] = {6.0 * q.a3, 24.0 * q.a4, 60.0 * q.a5};  // d_ddd
-    double sj = 0.0;
-#pragma unroll
-    for (int kk = 0; kk <= 4; ++kk) {
-        double ck = 0.0;
-#pragma unroll
-        for (int a2 = 0; a2 <= 2; ++a2) {
-            const int b2 = kk - a2;
-            if (b2 >= 0 && b2 <= 2) ck = fma(h[a2], h[b2], ck);
-        }
-        sj = fma(ck, S[kk], sj);
-    }
-    lat[0] = sa; lat[1] = sj; lat[2] = sd;
+    double c[6] = {q.a0, q.a1, q.a2, q.a3, q.a4, q.a5};
+    taylor_shift<5>(c, S[1]);
+    const double g[4] = {2.0 * c[2], 6.0 * c[3], 12.0 * c[4], 20.0 * c[5]};  // d_dd
+    const double h[3] = {6.0 * c[3], 24.0 * c[4], 60.0 * c[5]};              // d_ddd
+    lat[0] = centred_square_sum<3>(g, S);
+    lat[1] = centred_square_sum<2>(h, S);
+    lat[2] = centred_square_sum<5>(c, S);
 }
 
 // cost_total with the reference's grouping (cost_function.py:41-50)
@@ -182,25 +174,27 @@ __device__ __forceinline__ int arange_len(double T, double tick)
     return n > 0.0 ? (int)n : 0;
 }
 
-// S_k = sum_{i<N} (i*tick)^k = tick^k P_k(N), k = 0..10, with Faulhaber's polynomials P_k(N) = sum_{i<N} i^k
-// = 1/(k+1) sum_j C(k+1, j) B_j N^(k+1-j) (Bernoulli numbers, B_1 = -1/2; coefficients generated with exact rationals and
-// checked against the sums).  One lane per slice, ~90 instructions, instead of a wavefront per slice reducing 11 sums by DPP
-// trees; N <= 128 keeps the Horner evaluation at full double accuracy (leading term dominates: N^(k+1)/(k+1) vs N^k/2).
+// The power sums of lon_cost_sums / lat_cost_sums for t_i = i tick, i < N, about c = (N - 1) tick / 2:
+//   out[0] = N, out[1] = c (the odd centred sums are 0: their slot carries the centre), out[2j] = sum_i (t_i - c)^(2j), j = 1..5
+// in closed form: sum_{i<N} (i - (N - 1) / 2)^(2j) = N (N^2 - 1) R_j(N^2) / D_j with small integer polynomials R_j (derived with exact
+// rationals and checked against the sums).  One lane per slice, ~40 instructions, instead of a wavefront per slice reducing sums by DPP
+// trees.  Accuracy, measured against exact rational sums for every N <= FP_MAX_POINTS = 256 at tick 0.1 and 0.05: within 2e-15 relative
+// (every factor is positive for N >= 3, nothing cancels).  The costs built on them: within 1e-13 relative of CostFunction.cost_total
+// evaluated exactly (tests/exact_cost.py) in a host model of this arithmetic (fma rounded once) for N = 1 .. 256, lateral start speeds of 3 m/s
+// and accelerations of 2 m/s^2 included (the uncentred monomial sums: 1e-12 at N = 100, 7e-12 at N = 256); tests/test_gpu_edges.py holds
+// every kernel to 1e-12 relative.
 __device__ __forceinline__ void power_sums_closed(int N, double tick, double* out)
 {
-    const double x = (double)N;
-    double tk = 1.0;
-    out[0] = (1) * x * tk; tk *= tick;
-    out[1] = (fma(0.5, x, -0.5)) * x * tk; tk *= tick;
-    out[2] = (fma(fma(0.33333333333333331, x, -0.5), x, 0.16666666666666666)) * x * tk; tk *= tick;
-    out[3] = ((fma(fma(0.25, x, -0.5), x, 0.25)) * x) * x * tk; tk *= tick;
-    out[4] = (fma((fma(fma(0.20000000000000001, x, -0.5), x, 0.33333333333333331)) * x, x, -0.033333333333333333)) * x * tk; tk *= tick;
-    out[5] = ((fma((fma(fma(0.16666666666666666, x, -0.5), x, 0.41666666666666669)) * x, x, -0.083333333333333329)) * x) * x * tk; tk *= tick;
-    out[6] = (fma((fma((fma(fma(0.14285714285714285, x, -0.5), x, 0.5)) * x, x, -0.16666666666666666)) * x, x, 0.023809523809523808)) * x * tk; tk *= tick;
-    out[7] = ((fma((fma((fma(fma(0.125, x, -0.5), x, 0.58333333333333337)) * x, x, -0.29166666666666669)) * x, x, 0.083333333333333329)) * x) * x * tk; tk *= tick;
-    out[8] = (fma((fma((fma((fma(fma(0.1111111111111111, x, -0.5), x, 0.66666666666666663)) * x, x, -0.46666666666666667)) * x, x, 0.22222222222222221)) * x, x, -0.033333333333333333)) * x * tk; tk *= tick;
-    out[9] = ((fma((fma((fma((fma(fma(0.10000000000000001, x, -0.5), x, 0.75)) * x, x, -0.69999999999999996)) * x, x, 0.5)) * x, x, -0.14999999999999999)) * x) * x * tk; tk *= tick;
-    out[10] = (fma((fma((fma((fma((fma(fma(0.090909090909090912, x, -0.5), x, 0.83333333333333337)) * x, x, -1)) * x, x, 1)) * x, x, -0.5)) * x, x, 0.07575757575757576)) * x * tk; tk *= tick;
+    const double x = (double)N, y = x * x, base = x * (y - 1.0), t2 = tick * tick;
+    out[0] = x;
+    out[1] = 0.5 * (x - 1.0) * tick;
+    double tk = t2;
+    out[2] = base * (1.0 / 12.0) * tk; tk *= t2;
+    out[4] = base * fma(3.0, y, -7.0) * (1.0 / 240.0) * tk; tk *= t2;
+    out[6] = base * fma(fma(3.0, y, -18.0), y, 31.0) * (1.0 / 1344.0) * tk; tk *= t2;
+    out[8] = base * fma(fma(fma(5.0, y, -55.0), y, 239.0), y, -381.0) * (1.0 / 11520.0) * tk; tk *= t2;
+    out[10] = base * (y - 5.0) * fma(fma(fma(3.0, y, -37.0), y, 225.0), y, -511.0) * (1.0 / 33792.0) * tk;
+    out[3] = out[5] = out[7] = out[9] = 0.0;
 }
 
 

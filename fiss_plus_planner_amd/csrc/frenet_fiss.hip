@@ -455,7 +455,7 @@ __global__ __launch_bounds__(W * kWave) void fiss_search_kernel(FissArgs fa, int
 
 // ---------------------------------------------------------------------------
 // FISS+ refinement (fiss_plus_planner.py:207-326), one workgroup of kRefineWaves wavefronts per ego.
-//   * costs in closed form: the power sums S_k(N) = sum_{i<N} t_i^k of a horizon come from Faulhaber's polynomials, so the cost of ANY
+//   * costs in closed form: the power sums S_k(N) = sum_{i<N} (t_i - c)^k of a horizon come from closed-form polynomials in N, so the cost of ANY
 //     end state is O(1) (lon_cost_sums / lat_cost_sums): per round lanes 0..5 price the six probes clip(x -/+ res_dim e_dim)
 //     (:213-232), the finite-difference gradient and the decayed step are wave-uniform arithmetic on shuffled lane values
 //     (:262-271), lane 0 prices the trajectory at the new x.  The coarse winner is priced by the same function, so a probe clipped
@@ -500,7 +500,7 @@ __device__ __forceinline__ double analytic_cost(const fp_params& p, const double
     const Quintic lat = quintic_bvp(eg[3], eg[4], eg[5], x[0], 0.0, 0.0, T);
     double S[11], ls[3], ds[3];
     (void)Stab;
-    power_sums_closed(N, p.tick_t, S);  // S_k(N) = sum_{i<N} t_i^k in closed form (Faulhaber): no table
+    power_sums_closed(N, p.tick_t, S);  // S_k(N) = sum_{i<N} (t_i - c)^k in closed form: no table
     lon_cost_sums(lon, target_speed, S, ls);
     lat_cost_sums(lat, S, ds);
     return combine_cost(p, N, ls, ds);

@@ -11,7 +11,7 @@
 // Once per ego (phase A0): one lane per lon profile solves the boundary-value problem and tries to PROVE the profile clean from
 // the extrema of its polynomials (speed / acceleration limits, inside the spline's range); only slices with an unproven profile
 // run the reference's point-by-point scan (lane per (profile, point), LDS atomics).  The cost sums of every profile follow in
-// closed form from the per-slice power sums (Faulhaber) - no per-point work.
+// closed form from the per-slice power sums (centred, power_sums_closed) - no per-point work.
 // Once per ego, collision stage G: for every checked pose row the arclength range of the reference points of ALL lon profiles of
 // ALL slices (a polynomial evaluation each) becomes a circle - centre on the line at the middle of the range, radius = half the
 // range x an upper bound of the spline's parametric speed + ego reach + a closed-form bound of the lateral offsets - and one lane
@@ -218,7 +218,7 @@ __host__ __device__ inline Layout make_layout(int nx_max, int n_obs, int rows, i
     L.qlat = o;     o = align16(o + 24 * (kWalk ? nt : gs) * nd);   // a3, a4, a5 of the lat profiles (walk: of every slice; else of the CURRENT slices)
     L.box = o;      if (!slim) o = align16(o + 16 * (rows > 0 ? rows : 1));  // per checked pose row: bounding box of the slice's reference points (ordered-uint fp32)
     L.coll = o;     o = align16(o + (kWalk ? 8 * nt * nv : nd * nv * nt));  // walk: one bit per lateral sample, a 64-bit word per lon profile; else a byte per candidate
-    // per-wave hit queues; before the slice loop the same bytes hold the power sums S_k(N) = sum_i (i*tick)^k, k = 0..10, per slice
+    // per-wave hit queues; before the slice loop the same bytes hold the power sums S_k(N) = sum_i (i*tick - c)^k, k = 0..10, per slice
     L.queue = o;    L.pows = o;
     {
         const int q = kWalk ? (slim ? 2 : 4) * 64 * nwaves : 4 * kHitCap;
@@ -780,7 +780,7 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
     // (1) lane per (lon profile, time point): speed / acceleration masks by LDS atomic OR, the truncation index M (first point
     //     off the spline, a pure range test) by LDS atomic MIN - the same brute force over every point as the reference, with
     //     every lane busy (a wavefront per profile would idle a third of its lanes and all of its second half);
-    //     one lane per slice: the power sums S_k = sum_{i<N} t_i^k (k = 0..10) in closed form (Faulhaber, power_sums_closed).
+    //     one lane per slice: the power sums S_k = sum_{i<N} (t_i - c)^k (k = 0..10) about the samples' centre in closed form (power_sums_closed).
     // (2) lane per profile: the six cost sums in closed form.  Each summand is the square of a polynomial in t
     //     (s_d - v_target: cubic, s_dd: quadratic, s_ddd: linear, d: quintic, d_dd: cubic, d_ddd: quadratic), so
     //     sum_i p(t_i)^2 = sum_k c_k S_k with c = p (*) p (coefficient convolution) - no per-point work and no reductions.

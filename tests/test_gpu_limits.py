@@ -62,7 +62,7 @@ def test_more_lateral_samples_than_lanes_falls_back(oracle, engine):
 
 
 def test_largest_lattice(oracle, engine):
-    batch = synth.make_batch(1, 16, 16, 16, 12, 50, True, 73)  # C = 4096 = FP_MAX_CAND
+    batch = synth.make_batch(1, 16, 16, 16, 12, 50, True, 73)  # C = 4096 = FP_MAX_CAND_SEARCH (FP_MAX_CAND = 16384: tests/test_gpu_edges.py)
     _check_vs_oracle(oracle, engine, batch)
 
 
