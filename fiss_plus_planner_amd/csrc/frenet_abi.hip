@@ -789,18 +789,6 @@ int32_t* epi_flags_for(fp_ctx* ctx, size_t B, hipStream_t stream)
     return (int32_t*)ctx->epi_flags.base;
 }
 
-// Who writes the winner's series of a dense call that does not write them inside the lattice workgroups: with "lattice_winner" = 0
-// (auto) the epilogue workgroups appended to the lattice grid (launch_lattice_fused takes them when the launch is a three-per-CU one;
-// otherwise it reports winner_done = false and winner_traj_kernel follows).
-void offer_epilogue(fp_ctx* ctx, const fp::KernelArgs& ka, fp::KernelArgs* kl, size_t B, hipStream_t stream)
-{
-    if (ctx->lattice_winner != 0 || !ctx->appended_ok || !ka.r.best_traj || !ka.idx_shadow) return;
-    int32_t* flags = epi_flags_for(ctx, B, stream);
-    if (!flags) return;
-    kl->r.best_traj = ka.r.best_traj;
-    kl->epi_flag = flags;
-}
-
 // A hand-over of an earlier launch on this ctx timed out (fp_ctx::hand_err): the flags are reset in stream order, appended workgroups
 // are not offered again on this ctx (winner_traj_kernel / the search kernel take over), and the caller learns that the outputs of that
 // earlier call were incomplete.  FP_OK when nothing happened.
@@ -825,18 +813,34 @@ int handover_recover(fp_ctx* ctx, hipStream_t stream)
 }
 int handover_check(fp_ctx* ctx, hipStream_t stream) { return handover_failed(ctx) ? handover_recover(ctx, stream) : FP_OK; }
 
-// Optional curvature checks: the fused lattice kernel reads them from a [B][C] byte table that launch_lattice fills first.
-int lattice_curv_scratch(fp_ctx* ctx, const fp_params* p, const fp_batch* b, hipStream_t stream, const uint8_t** out)
+// The ctx's launch hints and hand-over error word, in the KernelArgs of a call that launches the lattice kernel.
+void ctx_lattice_args(const fp_ctx* ctx, fp::KernelArgs* ka)
 {
-    *out = nullptr;
-    if (!p->curvature_mask) return FP_OK;
-    const size_t need = (size_t)b->B * p->nd * p->nv * p->nt + kAlign;
-    if (need > ctx->curv_buf.cap) {
-        HIP_TRY(hipStreamSynchronize(stream));  // the buffer is reallocated: drain its users
-        FP_TRY(ctx->curv_buf.reserve(need));
+    ka->err_word = ctx->hand_err;
+    ka->occ_cap = ctx->lattice_occupancy; ka->resident2 = ctx->resident_groups; ka->lds_cu_kb = ctx->lds_cu_kb; ka->handover_timeout_us = ctx->handover_timeout_us;
+}
+
+// The lattice pass of a call: curvature table, split, launch order, the launch of kl and the order's feedback.  kl carries the
+// offers of the KernelArgs (the series inside, epilogue workgroups, the loop hand-over); inl / ft offer inline inputs and the
+// appended FISS+ search (either may be nullptr); *res says what the launch took.
+int lattice_step(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, fp::KernelArgs kl, hipStream_t stream, int which, const int* hint,
+                 const fp::InlineIn* inl, const fp::FissTail* ft, fp::LatticeResult* res)
+{
+    if (params->curvature_mask) {  // optional curvature checks: the fused lattice kernel reads them from a [B][C] byte table it fills first
+        const size_t need = (size_t)batch->B * params->nd * params->nv * params->nt + kAlign;
+        if (need > ctx->curv_buf.cap) {
+            HIP_TRY(hipStreamSynchronize(stream));  // the buffer is reallocated: drain its users
+            FP_TRY(ctx->curv_buf.reserve(need));
+        }
+        kl.curv_tbl = (const uint8_t*)ctx->curv_buf.base;
     }
-    *out = (const uint8_t*)ctx->curv_buf.base;
-    return FP_OK;
+    fp::LatticeRequest rq;
+    FP_TRY(lattice_split_for(ctx, params, batch, stream, &rq.nsplit, &rq.part_scratch, &rq.group, &rq.tail));
+    LaunchOrder* oslot = nullptr;
+    FP_TRY(launch_order_before(ctx, ctx->order_lattice, ctx->resident_groups, batch, rq.nsplit, stream, &rq.perm, &rq.dur, hint, &oslot));
+    rq.inl = inl; rq.ft = ft;
+    LAUNCH_TRY(fp::launch_lattice(kl, stream, which, rq, res), "lattice kernel");
+    return launch_order_after(oslot, batch, rq.dur, stream);
 }
 
 // Where the winner's series is written: by the lattice kernel's own workgroup (no second launch: what a single plan() call wants)
@@ -1461,96 +1465,72 @@ static int plan_dense_impl(fp_ctx* ctx, const fp_params* params, const fp_batch*
     if (result->audit && result->fopplus) return fail(FP_EINVAL, "result.audit settles FrenetOptimalPlanner's argmin: not together with result.fopplus");
     if (batch->B == 0) return FP_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    FP_TRY(handover_check(ctx, mem == FP_MEM_DEVICE ? (hipStream_t)stream : ctx->stream));
+    const hipStream_t st = mem == FP_MEM_DEVICE ? (hipStream_t)stream : ctx->stream;
+    FP_TRY(handover_check(ctx, st));
     const size_t C = (size_t)params->nd * params->nv * params->nt, B = (size_t)batch->B;
     int stride;
     FP_TRY(traj_stride_of(result->traj_stride, &stride));
     fp::KernelArgs ka;
     ka.p = *params;
-    ka.err_word = ctx->hand_err;
-    ka.occ_cap = ctx->lattice_occupancy; ka.resident2 = ctx->resident_groups; ka.lds_cu_kb = ctx->lds_cu_kb; ka.handover_timeout_us = ctx->handover_timeout_us;
+    ctx_lattice_args(ctx, &ka);
+    int32_t* fopplus = result->fopplus;
+    uint32_t* audit = result->audit;
+    HostStage hs(ctx);
+    fp::InlineIn inl;
     if (mem == FP_MEM_DEVICE) {
         ka.b = *batch;
         if (!(batch->S > 0 && batch->n_obs > 0)) ka.b.n_obs = 0;
         ka.r = *result;
-        if ((result->fopplus || result->audit) && (!ka.r.cost_tbl || !ka.r.flag_tbl)) FP_TRY(fopplus_tables(ctx, B, C, &ka.r, (hipStream_t)stream));
-        FP_TRY(lattice_curv_scratch(ctx, params, batch, (hipStream_t)stream, &ka.curv_tbl));
-        int nsplit, group, tail; void* parts;
-        FP_TRY(lattice_split_for(ctx, params, batch, (hipStream_t)stream, &nsplit, &parts, &group, &tail));
-        bool winner_done = false;
-        const int* perm; int* dur;
-        LaunchOrder* oslot = nullptr;
-        FP_TRY(launch_order_before(ctx, ctx->order_lattice, ctx->resident_groups, batch, nsplit, (hipStream_t)stream, &perm, &dur, batch->launch_order, &oslot));
-        // (the audit pass may move the winner: the series are written after it, by their own launch)
-        const bool inside = winner_inside_lattice(ctx, batch) && !result->audit && !big_points(ka.p);
-        if (result->best_traj && !inside) ka.idx_shadow = idx_shadow_for(ctx, B, (hipStream_t)stream);
-        fp::KernelArgs kl = ka;
-        if (!inside) kl.r.best_traj = nullptr;
-        if (!inside && !result->audit && !big_points(ka.p)) offer_epilogue(ctx, ka, &kl, B, (hipStream_t)stream);
-        LAUNCH_TRY(fp::launch_lattice(kl, (hipStream_t)stream, ctx->lattice_kernel, parts, nsplit, &winner_done, perm, dur, group, nullptr, tail), "lattice kernel");
-        FP_TRY(launch_order_after(oslot, batch, dur, (hipStream_t)stream));
-        if (result->audit) LAUNCH_TRY(fp::launch_audit(ka, result->audit, (hipStream_t)stream), "audit kernel");
-        if (result->best_traj && !winner_done) LAUNCH_TRY(fp::launch_winner_traj(ka, nullptr, (hipStream_t)stream), "winner epilogue");
-        if (result->fopplus)
-            LAUNCH_TRY(fp::launch_fopplus_count((int)B, (int)C, ka.r.cost_tbl, ka.r.flag_tbl, ka.r.best_idx, ka.r.best_cost, result->fopplus, ka.r.stats,
-                                                ka.b.skip, (hipStream_t)stream), "FOP+ count kernel");
-        return FP_OK;
+    } else {  // host buffers: checked, staged into device buffers, fetched below
+        FP_TRY(check_batch_host(params, batch));
+        if (result->best_traj) FP_TRY(check_stride_host(params, batch, stride));
+        ka.p.points_max = host_points_max(params, batch, nullptr, 0, 0);
+        const size_t traj_doubles = result->best_traj ? B * FP_ARR_COUNT * (size_t)stride : 0;
+        FP_TRY(hs.reserve(batch_need(params, batch) + HostStage::need<int32_t>(B * 4) + 2 * HostStage::need<double>(B) + HostStage::need<int32_t>(B) +
+                          HostStage::need<double>(B * C) + HostStage::need<uint32_t>(B * C) + HostStage::need<uint32_t>(B) +
+                          HostStage::need<double>(traj_doubles) + HostStage::need<int32_t>(B * 2) + HostStage::need<uint32_t>(B),
+                          /*zero_copy_out=*/B <= 8));
+        // (inline inputs need the fused kernel with the winner's series inside it: no other kernel of this call may read the batch)
+        const bool try_inline = ctx->inline_inputs && B <= 8 && !params->curvature_mask && ctx->lattice_kernel != 1 && !big_points(ka.p) &&
+                                (!result->best_traj || winner_inside_lattice(ctx, batch)) && !result->audit && fp::lattice_group_fit(*params, *batch) >= 1;
+        FP_TRY(stage_batch(hs, params, batch, &ka.b, try_inline ? &inl : nullptr));
+        FP_TRY(hs.flush_in());
+        ka.r.best_idx = hs.out(result->best_idx, B);
+        ka.r.best_cost = hs.out(result->best_cost, B);
+        ka.r.stats = hs.out(result->stats, B * 4);
+        ka.r.cost_tbl = hs.out(result->cost_tbl, B * C);
+        ka.r.flag_tbl = hs.out(result->flag_tbl, B * C);
+        ka.r.best_flags = hs.out(result->best_flags, B);
+        ka.r.best_traj = hs.out(result->best_traj, traj_doubles);
+        ka.r.traj_stride = result->traj_stride;
+        ka.r.traj_sparse = result->traj_sparse;
+        fopplus = hs.out(result->fopplus, B * 2);
+        audit = hs.out(result->audit, B);
+        // sparse rows are only partly written by the kernels: the host block comes back with the caller's own bytes elsewhere
+        if (result->traj_sparse && ka.r.best_traj) HIP_TRY(hipMemcpyAsync(ka.r.best_traj, result->best_traj, traj_doubles * sizeof(double), hipMemcpyDefault, st));
     }
-    FP_TRY(check_batch_host(params, batch));
-    if (result->best_traj) FP_TRY(check_stride_host(params, batch, stride));
-    ka.p.points_max = host_points_max(params, batch, nullptr, 0, 0);
+    if ((result->fopplus || result->audit) && (!ka.r.cost_tbl || !ka.r.flag_tbl)) FP_TRY(fopplus_tables(ctx, B, C, &ka.r, st));
+    // the series: inside the lattice workgroups, else by the epilogue workgroups appended to the launch or by winner_traj_kernel behind
+    // it (the audit pass may move the winner: its series are written after it, by their own launch)
     const bool big = big_points(ka.p);
-    const size_t traj_doubles = result->best_traj ? B * FP_ARR_COUNT * (size_t)stride : 0;
-    HostStage hs(ctx);
-    FP_TRY(hs.reserve(batch_need(params, batch) + HostStage::need<int32_t>(B * 4) + 2 * HostStage::need<double>(B) + HostStage::need<int32_t>(B) +
-                      HostStage::need<double>(B * C) + HostStage::need<uint32_t>(B * C) + HostStage::need<uint32_t>(B) +
-                      HostStage::need<double>(traj_doubles) + HostStage::need<int32_t>(B * 2) + HostStage::need<uint32_t>(B),
-                      /*zero_copy_out=*/B <= 8));
-    // (inline inputs need the fused kernel with the winner's series inside it: no other kernel of this call may read the batch)
-    fp::InlineIn inl;
-    const bool try_inline = ctx->inline_inputs && B <= 8 && !params->curvature_mask && ctx->lattice_kernel != 1 && !big &&
-                            (!result->best_traj || winner_inside_lattice(ctx, batch)) && !result->audit && fp::lattice_group_fit(*params, *batch) >= 1;
-    FP_TRY(stage_batch(hs, params, batch, &ka.b, try_inline ? &inl : nullptr));
-    FP_TRY(hs.flush_in());
-    ka.r.best_idx = hs.out(result->best_idx, B);
-    ka.r.best_cost = hs.out(result->best_cost, B);
-    ka.r.stats = hs.out(result->stats, B * 4);
-    ka.r.cost_tbl = hs.out(result->cost_tbl, B * C);
-    ka.r.flag_tbl = hs.out(result->flag_tbl, B * C);
-    ka.r.best_flags = hs.out(result->best_flags, B);
-    ka.r.best_traj = hs.out(result->best_traj, traj_doubles);
-    ka.r.traj_stride = result->traj_stride;
-    ka.r.traj_sparse = result->traj_sparse;
-    int32_t* d_fopplus = hs.out(result->fopplus, B * 2);
-    uint32_t* d_audit = hs.out(result->audit, B);
-    if ((result->fopplus || result->audit) && (!ka.r.cost_tbl || !ka.r.flag_tbl)) FP_TRY(fopplus_tables(ctx, B, C, &ka.r, ctx->stream));
-    // sparse rows are only partly written by the kernels: the host block comes back with the caller's own bytes elsewhere
-    if (result->traj_sparse && ka.r.best_traj) HIP_TRY(hipMemcpyAsync(ka.r.best_traj, result->best_traj, traj_doubles * sizeof(double), hipMemcpyDefault, ctx->stream));
-    FP_TRY(lattice_curv_scratch(ctx, params, batch, ctx->stream, &ka.curv_tbl));
-    int nsplit, group, tail; void* parts;
-    FP_TRY(lattice_split_for(ctx, params, batch, ctx->stream, &nsplit, &parts, &group, &tail));
-    bool winner_done = false;
-    const int* perm; int* dur;
-    LaunchOrder* oslot = nullptr;
-    FP_TRY(launch_order_before(ctx, ctx->order_lattice, ctx->resident_groups, batch, nsplit, ctx->stream, &perm, &dur, nullptr, &oslot));
+    const bool inside = winner_inside_lattice(ctx, batch) && !result->audit && !big;
+    if (result->best_traj && !inside) ka.idx_shadow = idx_shadow_for(ctx, B, st);
     fp::KernelArgs kl = ka;
-    if (!winner_inside_lattice(ctx, batch) || result->audit || big) {
-        kl.r.best_traj = nullptr;
-        if (result->best_traj && !result->audit && !inl.on) {
-            ka.idx_shadow = kl.idx_shadow = idx_shadow_for(ctx, B, ctx->stream);
-            if (!big) offer_epilogue(ctx, ka, &kl, B, ctx->stream);
-        }
+    if (!inside) kl.r.best_traj = nullptr;
+    if (!inside && !result->audit && !big && ctx->lattice_winner == 0 && ctx->appended_ok && ka.r.best_traj && ka.idx_shadow) {  // ("lattice_winner" 0: auto)
+        if (int32_t* flags = epi_flags_for(ctx, B, st)) { kl.r.best_traj = ka.r.best_traj; kl.epi_flag = flags; }  // (taken by three-per-CU launches)
     }
-    LAUNCH_TRY(fp::launch_lattice(kl, ctx->stream, ctx->lattice_kernel, parts, nsplit, &winner_done, perm, dur, group, inl.on ? &inl : nullptr, tail), "lattice kernel");
-    FP_TRY(launch_order_after(oslot, batch, dur, ctx->stream));
-    if (d_audit) LAUNCH_TRY(fp::launch_audit(ka, d_audit, ctx->stream), "audit kernel");
-    if (result->best_traj && !winner_done) {
+    fp::LatticeResult lr;
+    FP_TRY(lattice_step(ctx, params, batch, kl, st, ctx->lattice_kernel, mem == FP_MEM_DEVICE ? batch->launch_order : nullptr, inl.on ? &inl : nullptr, nullptr, &lr));
+    if (audit) LAUNCH_TRY(fp::launch_audit(ka, audit, st), "audit kernel");
+    if (result->best_traj && !lr.winner_done) {
         if (inl.on) return fail(FP_EHIP, "internal: inline inputs without the series inside the lattice kernel");
-        LAUNCH_TRY(fp::launch_winner_traj(ka, nullptr, ctx->stream), "winner epilogue");
+        LAUNCH_TRY(fp::launch_winner_traj(ka, nullptr, st), "winner epilogue");
     }
-    if (d_fopplus)
-        LAUNCH_TRY(fp::launch_fopplus_count((int)B, (int)C, ka.r.cost_tbl, ka.r.flag_tbl, ka.r.best_idx, ka.r.best_cost, d_fopplus, ka.r.stats, ka.b.skip, ctx->stream),
+    if (fopplus)
+        LAUNCH_TRY(fp::launch_fopplus_count((int)B, (int)C, ka.r.cost_tbl, ka.r.flag_tbl, ka.r.best_idx, ka.r.best_cost, fopplus, ka.r.stats, ka.b.skip, st),
                    "FOP+ count kernel");
+    if (mem == FP_MEM_DEVICE) return FP_OK;
     FP_TRY(hs.fetch_out());
     if (handover_failed(ctx)) {  // (the call has synchronised: a timed-out hand-over of ITS launch is known now - run it again without appended workgroups)
         (void)handover_recover(ctx, ctx->stream);
@@ -1675,8 +1655,7 @@ int plan_fiss_impl(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, 
     char* sp = ctx->scratch.base;
     fp::FissArgs fa;
     fa.ka.p = *params;
-    fa.ka.err_word = ctx->hand_err;
-    fa.ka.occ_cap = ctx->lattice_occupancy; fa.ka.resident2 = ctx->resident_groups; fa.ka.lds_cu_kb = ctx->lds_cu_kb; fa.ka.handover_timeout_us = ctx->handover_timeout_us;
+    ctx_lattice_args(ctx, &fa.ka);
     fa.opts = *opts;
     fa.opts.max_refine_iters = R;
     fa.ka.r = no_result();
@@ -1745,30 +1724,20 @@ int plan_fiss_impl(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, 
         fa.io.best_traj = hs.out(io->best_traj, traj_doubles);
         if (io->traj_sparse && fa.io.best_traj) HIP_TRY(hipMemcpyAsync(fa.io.best_traj, io->best_traj, traj_doubles * sizeof(double), hipMemcpyDefault, ctx->stream));
     }
-    FP_TRY(lattice_curv_scratch(ctx, params, batch, stream, &fa.ka.curv_tbl));
-    int nsplit, group, tail; void* parts;
-    FP_TRY(lattice_split_for(ctx, params, batch, stream, &nsplit, &parts, &group, &tail));
-    const int* perm; int* dur;
-    LaunchOrder* oslot = nullptr;
-    FP_TRY(launch_order_before(ctx, ctx->order_lattice, ctx->resident_groups, batch, nsplit, stream, &perm, &dur, mem == FP_MEM_DEVICE ? batch->launch_order : nullptr, &oslot));
-    bool search_done = false;
-    if (inl.on) {
-        fp::KernelArgs kl = fa.ka;
-        kl.b = lat_b;
-        LAUNCH_TRY(fp::launch_lattice(kl, stream, 2, parts, nsplit, nullptr, perm, dur, group, &inl, tail), "lattice kernel");
-    } else {
-        // the FISS+ search as workgroups appended to the lattice launch (launch_lattice_fused takes the offer for three-per-CU launches;
-        // "fiss_fused" 0, the stage-timing diagnostic and every other shape: the search kernel follows in its own launch)
-        fp::FissTail ft;
-        ft.opts = fa.opts; ft.io = fa.io; ft.walk_jump = ctx->fiss_jump;
-        ft.flag = (ctx->fiss_fused && ctx->appended_ok && ctx->fiss_stages >= 3 && opts->kind == FP_FISS_PLUS) ? epi_flags_for(ctx, B, stream) : nullptr;
-        LAUNCH_TRY(fp::launch_lattice(fa.ka, stream, ctx->lattice_kernel, parts, nsplit, nullptr, perm, dur, group, nullptr, tail, ft.flag ? &ft : nullptr, &search_done),
-                   "lattice kernel");
-    }
-    FP_TRY(launch_order_after(oslot, batch, dur, stream));
+    // inline inputs: the lattice kernel reads the batch from its argument block (lat_b) - the fused kernel or nothing.  Else the FISS+
+    // search is offered as workgroups appended to the lattice launch (taken by three-per-CU launches; "fiss_fused" 0, the stage-timing
+    // diagnostic and every other shape: the search kernel follows in its own launch)
+    fp::KernelArgs kl = fa.ka;
+    if (inl.on) kl.b = lat_b;
+    fp::FissTail ft;
+    ft.opts = fa.opts; ft.io = fa.io; ft.walk_jump = ctx->fiss_jump;
+    ft.flag = (!inl.on && ctx->fiss_fused && ctx->appended_ok && ctx->fiss_stages >= 3 && opts->kind == FP_FISS_PLUS) ? epi_flags_for(ctx, B, stream) : nullptr;
+    fp::LatticeResult lr;
+    FP_TRY(lattice_step(ctx, params, batch, kl, stream, inl.on ? 2 : ctx->lattice_kernel, mem == FP_MEM_DEVICE ? batch->launch_order : nullptr,
+                        inl.on ? &inl : nullptr, ft.flag ? &ft : nullptr, &lr));
     if (ctx->fiss_stages < 2) return mem == FP_MEM_HOST ? hs.fetch_out() : FP_OK;  // timing diagnostic: outputs are not produced
     fa.walk_jump = ctx->fiss_jump;
-    if (!search_done) LAUNCH_TRY(fp::launch_fiss_search(fa, stream), "search kernel");
+    if (!lr.search_done) LAUNCH_TRY(fp::launch_fiss_search(fa, stream), "search kernel");
     bool handed_over = false;
     if (R > 0 && ctx->fiss_stages >= 3) {
         // three refinement workgroups per CU are resident at once (fiss_refine_kernel: 168 VGPRs, ~52 KB LDS)
@@ -1902,45 +1871,22 @@ int fp_plan_step(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, co
     const size_t B = (size_t)batch->B;
     fp::KernelArgs ka;
     ka.p = *params;
-    ka.err_word = ctx->hand_err;
-    ka.occ_cap = ctx->lattice_occupancy; ka.resident2 = ctx->resident_groups; ka.lds_cu_kb = ctx->lds_cu_kb; ka.handover_timeout_us = ctx->handover_timeout_us;
+    ctx_lattice_args(ctx, &ka);
     ka.b = *batch;
     ka.b.skip = io->done;
     if (!(batch->S > 0 && batch->n_obs > 0)) ka.b.n_obs = 0;
     ka.r = *result;
-    FP_TRY(lattice_curv_scratch(ctx, params, batch, (hipStream_t)stream, &ka.curv_tbl));
-    int nsplit, group, tail; void* parts;
-    FP_TRY(lattice_split_for(ctx, params, batch, (hipStream_t)stream, &nsplit, &parts, &group, &tail));
-    const int* perm; int* dur;
-    LaunchOrder* oslot = nullptr;
-    FP_TRY(launch_order_before(ctx, ctx->order_lattice, ctx->resident_groups, batch, nsplit, (hipStream_t)stream, &perm, &dur, batch->launch_order, &oslot));
-    // the hand-over rides in the lattice launch unless that launch cannot write the series it is asked for itself (the standalone
-    // epilogue reads the ego's state, so it has to run BEFORE the state moves on) or the lane-per-candidate kernel is asked for
+    // the hand-over is offered to the lattice launch unless that launch cannot write the series it is asked for itself (the standalone
+    // epilogue reads the ego's state, so it has to run BEFORE the state moves on)
     const bool series_elsewhere = result->best_traj && (!winner_inside_lattice(ctx, batch) || big_points(ka.p));
-    bool try_fused = !series_elsewhere && ctx->lattice_kernel != 1, launched = false, fused = false;
-    bool winner_done = false;
-    if (try_fused) {
-        fp::KernelArgs kl = ka;
-        kl.loop = *io;
-        kl.has_loop = 1;
-        hipError_t e = fp::launch_lattice_fused(kl, (hipStream_t)stream, parts, nsplit, &winner_done, perm, dur, group, nullptr, tail, &fused);
-        if (e == hipErrorInvalidValue) {  // the problem does not fit the fused kernel
-            (void)hipGetLastError();
-        } else if (e != hipSuccess) {
-            return fail(FP_EHIP, "lattice kernel: %s", hipGetErrorString(e));
-        } else {
-            launched = true;  // (fused: the instance handed the egos over itself; else advance_kernel follows below)
-        }
-    }
-    if (!launched) {
-        if (series_elsewhere) ka.idx_shadow = idx_shadow_for(ctx, B, (hipStream_t)stream);
-        fp::KernelArgs kl = ka;
-        if (series_elsewhere) kl.r.best_traj = nullptr;
-        LAUNCH_TRY(fp::launch_lattice(kl, (hipStream_t)stream, ctx->lattice_kernel, parts, nsplit, &winner_done, perm, dur, group, nullptr, tail), "lattice kernel");
-    }
-    FP_TRY(launch_order_after(oslot, batch, dur, (hipStream_t)stream));
-    if (result->best_traj && !winner_done) LAUNCH_TRY(fp::launch_winner_traj(ka, nullptr, (hipStream_t)stream), "winner epilogue");
-    if (!fused) LAUNCH_TRY(fp::launch_advance(ka, ka.r.best_idx, nullptr, *io, (hipStream_t)stream), "advance kernel");
+    if (series_elsewhere) ka.idx_shadow = idx_shadow_for(ctx, B, (hipStream_t)stream);
+    fp::KernelArgs kl = ka;
+    if (series_elsewhere) kl.r.best_traj = nullptr;
+    else { kl.loop = *io; kl.has_loop = 1; }
+    fp::LatticeResult lr;
+    FP_TRY(lattice_step(ctx, params, batch, kl, (hipStream_t)stream, ctx->lattice_kernel, batch->launch_order, nullptr, nullptr, &lr));
+    if (result->best_traj && !lr.winner_done) LAUNCH_TRY(fp::launch_winner_traj(ka, nullptr, (hipStream_t)stream), "winner epilogue");
+    if (!lr.step_done) LAUNCH_TRY(fp::launch_advance(ka, ka.r.best_idx, nullptr, *io, (hipStream_t)stream), "advance kernel");
     return FP_OK;
 }
 

@@ -89,8 +89,6 @@ struct InlineIn {
     unsigned char bytes[kInlineMax];
 };
 
-// Production dense-lattice kernel (profile sharing + compacted collision).  Returns hipErrorInvalidValue when the
-// problem does not fit it (LDS budget / index widths); launch_lattice then uses the lane-per-candidate kernel.
 // Arguments of the FISS / FISS+ batch kernels: the lattice arguments plus the dense tables and the fp_fiss_io arrays.
 struct FissArgs {
     KernelArgs ka;
@@ -118,27 +116,29 @@ hipError_t launch_fiss_search(const FissArgs& fa, hipStream_t stream);
 hipError_t launch_fissplus_search(const FissArgs& fa, hipStream_t stream);
 // One workgroup per ego: FISS+ refinement rounds + cost-ordered validation of the refined trajectories.  table_kb = LDS budget
 // of the per-ego fp32 pose-obstacle pair table (0: no table, pairs are read from the scene table).
-// perm / dur: launch order and duration feedback, like launch_lattice_fused.
+// perm / dur: launch order and duration feedback, like LatticeRequest.
 hipError_t launch_fiss_refine(const FissArgs& fa, hipStream_t stream, int table_kb, const int* perm = nullptr, int* dur = nullptr);
 
 // part_scratch: device buffer of kTicketBytes (ticket counters, int per ego, ZERO before the first launch; the kernel leaves
 // them zero) + B * nsplit * 16 bytes (partial argmins), or nullptr; nsplit > 1 = latency mode (B <= kTicketBytes / 4).
 constexpr size_t kTicketBytes = 64 * 1024;
-// *winner_done (optional): the kernel also wrote ka.r.best_traj / best_flags (asked for, and not in latency mode).
-// perm (optional, nsplit == 1): workgroup i works on ego perm[i] (a permutation of [0, B): the launch order); dur (optional): every
-// workgroup leaves its ego's duration there (10 ns ticks).
-// group: time-horizon slices per barrier interval of the collision stages (<= 1: one at a time; n: up to n, as far as
-// lattice_group_fit allows - for small lattices whose slices are latency bound).
-// tail (needs part_scratch, nsplit == 1): the last `tail` dispatch slots of a multi-round launch are cut in two workgroups each (the
-// launch's tail drains faster); < 0: auto for a device of -tail compute units (a quarter of a round of resident workgroups, only when the
-// launch has more egos than stay resident); 0: off.
-// *step_done (optional, ka.has_loop set): the launched instance hands the egos over to their next states itself (fp_plan_step); false:
-// the caller launches advance_kernel behind it.
-// ft / search_done (optional): the FISS+ search of every ego in workgroups appended to the launch (three-per-CU launches of lattices up
-// to 1024 samples whose tables ka.r.cost_tbl / flag_tbl are written); *search_done = false: the caller launches the search kernel.
-hipError_t launch_lattice_fused(const KernelArgs& ka, hipStream_t stream, void* part_scratch, int nsplit, bool* winner_done = nullptr,
-                                const int* perm = nullptr, int* dur = nullptr, int group = 1, const InlineIn* inl = nullptr, int tail = 0,
-                                bool* step_done = nullptr, const FissTail* ft = nullptr, bool* search_done = nullptr);
+// What a caller asks of a lattice launch beside the offers its KernelArgs carry (series inside: r.best_traj; epilogue workgroups:
+// epi_flag + idx_shadow; loop hand-over: has_loop + loop).  plan_lattice (frenet_lattice_plan.h) takes what fits.
+struct LatticeRequest {
+    void* part_scratch = nullptr;  // see kTicketBytes
+    int nsplit = 1;
+    const int* perm = nullptr;     // (nsplit == 1) workgroup i works on ego perm[i]: the launch order
+    int* dur = nullptr;            // every workgroup leaves its ego's duration there (10 ns ticks)
+    int group = 1;                 // time-horizon slices per barrier interval, as far as lattice_group_fit allows (<= 1: one)
+    int tail = 0;                  // (needs part_scratch) cut the last `tail` slots of a multi-round launch in two; < 0: auto for -tail CUs
+    const InlineIn* inl = nullptr;  // inline inputs: the fused kernel or nothing
+    const FissTail* ft = nullptr;   // the FISS+ search in workgroups appended to the launch (three- / four-per-CU launches)
+};
+// What the launch did: wrote the winner's series (else winner_traj_kernel follows), handed the egos over (else advance_kernel),
+// ran the FISS+ search (else the search kernel).
+struct LatticeResult {
+    bool winner_done = false, step_done = false, search_done = false;
+};
 int lattice_group_fit(const fp_params& p, const fp_batch& b);
 // launches of the fused lattice kernel by workgroups per CU ([0] two, [1] three, [2] four) since the library was loaded: process-wide
 // counters behind fp_ctx_get_option("lattice_launches_2 / _3 / _4") - what the tests use to know which instance family they ran
@@ -146,11 +146,10 @@ long lattice_launches_per_cu(int which);
 hipError_t launch_lattice_percand(const KernelArgs& ka, hipStream_t stream);
 // Curvature flags of every lattice candidate -> out [B][C] (one workgroup per ego, one lane per candidate, spline in LDS).
 hipError_t launch_curvature_flags(const KernelArgs& ka, uint8_t* out, hipStream_t stream);
-// Dispatcher used by the ABI.  which: 0 = auto (fused, else per-candidate), 1 = per-candidate, 2 = fused only.
-// inl (optional, see InlineIn): only with which == 2 semantics guaranteed by the caller (the problem fits the fused kernel).
-hipError_t launch_lattice(const KernelArgs& ka, hipStream_t stream, int which, void* part_scratch, int nsplit, bool* winner_done = nullptr,
-                          const int* perm = nullptr, int* dur = nullptr, int group = 1, const InlineIn* inl = nullptr, int tail = 0,
-                          const FissTail* ft = nullptr, bool* search_done = nullptr);
+// The lattice pass of a dense, FISS or closed-loop call.  which: 0 = auto (the fused kernel when the problem fits it, else the
+// lane-per-candidate kernel), 1 = lane-per-candidate, 2 = fused only (hipErrorInvalidValue when it does not fit; so do inline inputs).
+// Every other error is the runtime's.
+hipError_t launch_lattice(const KernelArgs& ka, hipStream_t stream, int which, const LatticeRequest& rq, LatticeResult* res);
 // Winner epilogue: recompute the full series of trajectory best_idx[b] for every ego (one lane per time point).
 // end_states = nullptr: series of lattice candidate ka.r.best_idx[b]; else [B][3] explicit (d, v, T) end states (NaN = none).
 hipError_t launch_winner_traj(const KernelArgs& ka, const double* end_states, hipStream_t stream);

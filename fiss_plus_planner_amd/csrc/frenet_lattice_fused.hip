@@ -36,12 +36,14 @@
 //   argmin              planners/frenet_optimal_planner.py:263-268
 #include <atomic>
 #include <type_traits>
+#include <utility>
 
 #include "frenet_device.h"
 #include "frenet_kernels.h"
 #include "frenet_winner.h"
 #include "frenet_advance.h"
 #include "frenet_fissplus.h"
+#include "frenet_lattice_plan.h"
 
 namespace fp {
 
@@ -117,18 +119,6 @@ __device__ __forceinline__ bool handover_wait(const int32_t* flag, int32_t* err_
 #else
 #define SLICE_SYNC() __syncthreads()
 #endif
-constexpr int kThreads = 512;
-#ifndef FP_GROUP_THREADS
-#define FP_GROUP_THREADS 1024  // threads per workgroup of the grouped instances
-#endif
-constexpr int kHitCap = 1024;    // block-wide list of (lon profile, row, obstacle) hits of one B pass  // block-wide list of live narrow-phase items (pair, lateral sample) of one B pass: 24 KB
-// block-wide list of (row, obstacle) items that pass the group test (+ their poses, 32 B each).  Two kernel variants: OCC = 4 waves per
-// SIMD (two workgroups per CU, up to 128 VGPRs, winner epilogue inside) and OCC = 6 (THREE workgroups per CU: 80 VGPRs - a few spill
-// - and at most 53 KB of LDS, so a shorter list; no winner epilogue, the batches it serves get theirs from winner_traj_kernel or from the
-// appended epilogue workgroups) and, for BASELINE.json's dense shape, OCC = 8 (FOUR per CU: 64 VGPRs, none spilled, and the 40 KB "slim"
-// layout of make_layout with a 256-entry list - the largest ego of the headline workload keeps 221; longer lists take the chunked redo)
-__host__ __device__ constexpr int item_cap(int occ) { return occ > 6 ? 256 : occ > 4 ? 320 : 512; }
-constexpr int kItemCapMax = 512;
 
 struct __attribute__((aligned(16))) Frame {  // reference-line frame of one lon-profile point
     double px, py, tx, ty;
@@ -151,94 +141,13 @@ struct SplitTab {
     __device__ __forceinline__ SplitTab at(int off) const { return SplitTab{lo + off, hi + off}; }
 };
 
-// LDS carve-up (all offsets in bytes, 16-byte aligned)
-struct Layout {
-    int knots, coef, lut, dim, pose, frames, lat, dmax, ddmax, wfat, grp, iqueue, pows, samples, lon_sum, lat_sum, lon_meta, qlon, qlat, box, coll, queue, cnt, nslice, best, konst, nvert, poly, total;
-};
 
-__host__ __device__ inline int align16(int v) { return (v + 15) & ~15; }
-
-// Two organisations of the collision stages share the kernel's prologue (FP_SLICE_LOOP selects the older one for A/B runs):
-//   walk (default)  every wavefront takes one lon profile (T, v) at a time and does everything for it by itself - frames, fan
-//                   half-widths, broad phase, narrow phase - with NO workgroup barrier; the per-slice tables (frames, half-widths,
-//                   hit list) are per WAVEFRONT, the lateral bounds and coefficients of all slices are computed once per ego
-//   slice loop      all wavefronts work on one time-horizon slice (or a group of gs slices) per barrier interval
-#if defined(FP_SLICE_LOOP)
-constexpr bool kWalk = false;
-#else
-constexpr bool kWalk = true;
-#endif
-// gs = time-horizon slices the collision stages work on per barrier interval (1: one at a time; the per-slice tables are gs deep)
-// Polygon columns (POLY instances): the vertex counts always sit in LDS, the rings when they are small (kPolyLdsMax: a few KB keep the
-// three-workgroups-per-CU instance inside its 52 KB; 9.6 KB of 12-gons pushed config-3-sized scenes to two per CU: 208 -> 234 us) - a
-// narrow-phase lane reads another obstacle than its neighbour, and from global memory a ring costs it two dependent L2 round trips
-// (count, then vertices) per round.  Measured on config-3 sizes, half of the columns rings (same box): rectangle-only scene on its
-// shaped instance 138.7 us; the run-time-shape POLY instance with no polygon at all 162.5; 4-vertex rings that ARE their rectangles
-// 177.6 (185.9 with counts and rings in global memory).
-constexpr int kPolyLdsMax = 4 * 1024;
-__host__ __device__ inline int poly_lds_verts(int n_obs, int poly_stride) { return poly_stride > 0 && n_obs * poly_stride * 16 <= kPolyLdsMax ? n_obs * poly_stride : 0; }
 
 // the walk's fan bounds in LDS: fp32, or (slim layout) fp16 that is never below the fp32 value: x (1 + 2^-10) survives the rounding to
 // 11 bits (relative error <= 2^-11), the offset keeps the result a normal half (no dependence on the denormal mode), NaN stays NaN
 template <bool SLIM> struct FanType { using type = float; static __device__ __forceinline__ float above(float x) { return x; } };
 template <> struct FanType<true> { using type = _Float16; static __device__ __forceinline__ _Float16 above(float x) { return (_Float16)(x * 1.001f + 6.2e-5f); } };
 
-// coef_cols: columns (segments) of the spline's coefficient rows the workgroup keeps in LDS: all nx_max of them (default), or a WINDOW
-// of that many segments placed at the ego's position (the kernel's `wcap`): 64 of the 76 bytes a knot costs.  Long reference lines
-// (200+ knots) then still fit the three- / four-per-CU layouts; a point whose segment lies outside the window reads global memory.
-__host__ __device__ inline Layout make_layout(int nx_max, int n_obs, int rows, int hp, int nd, int nv, int nt, int kItemCap, int gs, int nwaves, int poly_stride = 0, bool slim = false,
-                                              int coef_cols = -1)
-{
-    // slim (the four-per-CU instance, kWalk, no polygon columns): the same tables in 40 KB - no inner radii, fp16 fan bounds, 16-bit
-    // hit codes, the row boxes inside the power sums' / hit lists' bytes (they are read for the last time before the first hit is written)
-    Layout L;
-    int o = 0;
-    L.dim = o;      o = align16(o + (slim ? 24 : 32) * n_obs);
-    L.pose = o;     o = align16(o + 32 * kItemCap);  // poses of the group test's survivors (x, y, cos, sin), in list order
-    if (kWalk) {
-        L.frames = o;   o = align16(o + 32 * nwaves * hp);   // [wavefront][point]: the profile the wavefront is working on
-        L.lat = o;
-        L.dmax = o;     o = align16(o + (slim ? 2 : 4) * nt * hp);   // [slice][point] float (slim: half), rounded up: max |d| over the lateral samples
-        L.ddmax = o;    o = align16(o + (slim ? 2 : 4) * nt * hp);   // max |d(i + 1) - d(i)|
-        L.wfat = o;     o = align16(o + 4 * nwaves * (rows > 0 ? rows : 1));  // [wavefront][row] float, rounded up
-    } else {
-        L.frames = o;   o = align16(o + 32 * gs * nv * hp);
-        L.lat = o;      o = align16(o + 8 * gs * nd * hp);
-        L.dmax = o;     o = align16(o + 2 * 4 * gs * hp);   // float, rounded up; two buffers (group parity): LDS atomic max in phase A
-        L.ddmax = o;    o = align16(o + 2 * 4 * gs * hp);
-        L.wfat = o;     o = align16(o + 4 * gs * nv * hp);  // float, rounded up
-    }
-    L.grp = o;      o = align16(o + 32 * (rows > 0 ? rows : 1));       // per checked pose row: circle enclosing all lon profiles' points
-    L.iqueue = o;   o = align16(o + 2 * kItemCap);                           // (row, obstacle) items that pass the group test
-    L.samples = o;  o = align16(o + 8 * (nt + nv + nd));  // t / v / d sample grids (read all over the kernel: keep them out of HBM latency)
-    L.lon_sum = o;  o = align16(o + 24 * nt * nv);   // sum_v, sum_as, sum_js
-    L.lat_sum = o;  o = align16(o + 24 * nd * nt);   // sum_ad, sum_jd, sum_d
-    L.lon_meta = o; o = align16(o + 8 * nt * nv);    // int M, uint flags
-    L.qlon = o;     o = align16(o + 16 * nt * nv);   // a3, a4 of every lon profile (a0..a2 are the ego state)
-    L.qlat = o;     o = align16(o + 24 * (kWalk ? nt : gs) * nd);   // a3, a4, a5 of the lat profiles (walk: of every slice; else of the CURRENT slices)
-    L.box = o;      if (!slim) o = align16(o + 16 * (rows > 0 ? rows : 1));  // per checked pose row: bounding box of the slice's reference points (ordered-uint fp32)
-    L.coll = o;     o = align16(o + (kWalk ? 8 * nt * nv : nd * nv * nt));  // walk: one bit per lateral sample, a 64-bit word per lon profile; else a byte per candidate
-    // per-wave hit queues; before the slice loop the same bytes hold the power sums S_k(N) = sum_i (i*tick - c)^k, k = 0..10, per slice
-    L.queue = o;    L.pows = o;
-    {
-        const int q = kWalk ? (slim ? 2 : 4) * 64 * nwaves : 4 * kHitCap;
-        int pw = align16(88 * nt);
-        if (slim) { L.box = o + pw; pw += 16 * (rows > 0 ? rows : 1); }
-        o = align16(o + (q > pw ? q : pw));
-    }
-    L.cnt = o;      o = align16(o + 32);  // list counters (monotone) + scan mask + ticket + two fp32 bounds
-    L.nslice = o;   o = align16(o + 4 * nt);  // points per slice, len(np.arange(0, T, tick))
-    L.best = o;     o = align16(o + 16 * (slim ? 8 : 16));  // (up to 16 wavefronts; slim: 8)
-    L.konst = o;    o = align16(o + 96);  // per-ego constants the collision stages re-read (instead of registers held through the kernel)
-    L.nvert = o;    o = align16(o + (poly_stride > 0 ? 4 * n_obs : 0));                              // polygon columns: vertices per obstacle
-    L.poly = o;     o = align16(o + 16 * poly_lds_verts(n_obs, poly_stride));                        // ... and the rings, when they fit
-    // the spline tables last: theirs is the one size no instance of the kernel knows at compile time, so every other offset folds
-    L.knots = o;    o = align16(o + 8 * nx_max);
-    L.coef = o;     o = align16(o + 64 * (coef_cols >= 0 && coef_cols < nx_max ? coef_cols : nx_max));
-    L.lut = o;      o = align16(o + 2 * (2 * nx_max + 1));  // uint16 segment hint per arclength bucket
-    L.total = o;
-    return L;
-}
 
 }  // namespace
 
@@ -273,12 +182,6 @@ __device__ __forceinline__ int lut_segment(const double* knots, const unsigned s
 // an ego costs 4 intervals instead of 4 nt and needs no split over workgroups (no ticket, no merge).
 // NTH: threads per workgroup, 512 or - the grouped latency instances, one workgroup per CU - 1024 (twice the wavefronts per pass).
 // the kernel's parameters as one struct: where InlineIn::bytes sits in the argument segment
-// LDS of an epilogue workgroup (kThreads / 128 trajectories): [4][FP_FAST_POINTS] doubles of difference-chain scratch per trajectory,
-// {first point off the spline} x 2, the argmin and the "had to wait" flag per trajectory; then, for reference lines of at most
-// kEpiSplineNX knots, room for one spline copy per trajectory
-constexpr int kEpiPairsC = 512 / (2 * kWave);
-constexpr int kEpiLdsBytes = kEpiPairsC * 4 * FP_FAST_POINTS * 8 + kEpiPairsC * 4 * 4 + 16;
-constexpr int kEpiSplineNX = 96;
 struct LatticeKernarg {
     KernelArgs ka; int rows_max_arg, hp_max_arg, nsplit; Best* part_best; int* part_count; const int* perm; int* dur; int gs_arg, tail_from, epi_from, wcap; FissTail ft; InlineIn inl;
 };
@@ -1737,233 +1640,75 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
     if (ka.has_loop && tid == 0) advance_ego(ka, b, win, nullptr, ka.loop);
 }
 
-// Returns hipErrorInvalidValue when the problem does not fit this kernel (caller falls back to the lane-per-candidate kernel).
-// LDS budget of one workgroup (the CU has 160 KB; beyond ~82 KB only one workgroup fits per CU)
-constexpr int kLdsLimit = 150 * 1024;
-constexpr int kLdsQuarter = 40 * 1024 - 512;  // (a margin below 160 KB / 4 for the allocation granule)
 
-static bool fused_shape(const fp_params& p, const fp_batch& b, int* rows_out, int* hp_out)
-{
-    if (p.nd > kWave || p.nv > 255 || b.n_obs > 4095) return false;
-    const int stride = p.check_stride;
-    int rows = 0, hp = 0;
-    if (b.n_obs > 0) {
-        rows = (points_cap(p) + stride - 1) / stride;
-        const int rows_tab = (b.T_obs + stride - 1) / stride;
-        if (rows_tab < rows) rows = rows_tab;
-        hp = rows * stride + 1;
-        if (hp > points_cap(p)) hp = points_cap(p);
-        if (rows > 4095 || (long)rows * b.n_obs > 65535) return false;
-    }
-    *rows_out = rows;
-    *hp_out = hp;
-    return true;
-}
-
-// Largest number of time-horizon slices one workgroup can hold at once (the grouped instances, GS = 0): LDS budget and the 8-bit
-// profile index of the hit word.  0 when the problem does not fit the fused kernel at all.
-int lattice_group_fit(const fp_params& p, const fp_batch& b)
-{
-    int rows = 0, hp = 0;
-    if (!fused_shape(p, b, &rows, &hp)) return 0;
-    int gs = 0;
-    for (int g = 1; g <= p.nt; ++g) {
-        if (g * p.nv > 256 || make_layout(b.NX, b.n_obs, rows, hp, p.nd, p.nv, p.nt, item_cap(4), g, FP_GROUP_THREADS / kWave, b.obs_nvert ? b.poly_stride : 0).total > kLdsLimit) break;
-        gs = g;
-    }
-    return gs;
-}
+int lattice_group_fit(const fp_params& p, const fp_batch& b) { return group_fit(p, b); }
 
 static std::atomic<long> g_launches_per_cu[3];
 long lattice_launches_per_cu(int which) { return which >= 0 && which < 3 ? g_launches_per_cu[which].load(std::memory_order_relaxed) : 0; }
 
-hipError_t launch_lattice_fused(const KernelArgs& ka, hipStream_t stream, void* part_scratch, int nsplit, bool* winner_done, const int* perm, int* dur,
-                                int group, const InlineIn* inl, int tail, bool* step_done, const FissTail* ft, bool* search_done)
+// The instances of kLatticeInstances, in its order: kernel and its LDS-attribute slot (see ensure_dynamic_lds).
+using LatticeFn = void (*)(KernelArgs, int, int, int, Best*, int*, const int*, int*, int, int, int, int, FissTail, InlineIn);
+template <int I>
+constexpr LatticeFn lattice_kernel_of()
 {
-    if (step_done) *step_done = false;
-    if (search_done) *search_done = false;
-    static const InlineIn kNoInline{};
-    const InlineIn& in = inl ? *inl : kNoInline;
-    if (winner_done) *winner_done = false;
-    const fp_params& p = ka.p;
-    const fp_batch& b = ka.b;
-    int rows = 0, hp = 0;
-    if (!fused_shape(p, b, &rows, &hp)) return hipErrorInvalidValue;
-    if (!part_scratch || nsplit < 1) nsplit = 1;
-    // Three workgroups per CU (the OCC = 6 variant) when the launch has more egos than two per CU can hold at once, nobody needs the
-    // series from this kernel and a workgroup's LDS fits a third of the CU's 160 KB; else two per CU (OCC = 4).
-    // slices per barrier interval (the grouped instances): as asked for, as far as one workgroup's LDS holds them
-    int gs = group < 1 ? 1 : (group > p.nt ? p.nt : group);
-    if (gs > 1) {
-        const int fit = lattice_group_fit(p, b);
-        gs = fit < 1 ? 1 : (gs > fit ? fit : gs);
-    }
-    const int pstride = b.obs_nvert && b.n_obs > 0 ? b.poly_stride : 0;  // (polygon columns: their counts - and rings, when they fit - live in LDS)
-    // Coefficient window (the kernel's wcap): when the whole spline does not fit a residency's LDS share, the largest window that does -
-    // if it is at least kWinMin segments (below that too many points would read global memory)
-    constexpr int kWinMin = 32;
-    auto window_for = [&](int cap_bytes, int occ, int ps, bool slim) {
-        const int base = make_layout(b.NX, b.n_obs, rows, hp, p.nd, p.nv, p.nt, item_cap(occ), 1, kThreads / kWave, ps, slim, 0).total;
-        const int w = (cap_bytes - base - 16) / 64;
-        if (gs > 1) return w >= b.NX ? b.NX : 0;  // (no WIN instance with grouped slices)
-        return w >= b.NX ? b.NX : (w >= kWinMin ? w : 0);  // 0: not even a useful window fits
-    };
-    const int w6 = window_for(52 * 1024, 6, pstride, false);
-    const Layout L6 = make_layout(b.NX, b.n_obs, rows, hp, p.nd, p.nv, p.nt, item_cap(6), 1, kThreads / kWave, pstride, false, w6 > 0 ? w6 : b.NX);
-    // the series of a three-per-CU launch: by epilogue workgroups appended to the grid (ka.epi_flag + ka.idx_shadow from the caller), if
-    // there are fewer of them than resident slots (see the kernel); else the caller launches winner_traj_kernel behind this launch
-    constexpr int kEpiPairs = kEpiPairsC;
-    const int kEpiLds = kEpiLdsBytes + (b.NX <= kEpiSplineNX ? kEpiPairs * 9 * b.NX * 8 : 0);
-#if defined(FP_PHASE_STAMPS) || defined(FP_COUNTERS)  // (the stamps travel in the series block: the three-workgroup variant leaves the series themselves unwritten)
-    const bool can_epi = false;
-    bool three = gs == 1 && nsplit == 1 && b.B > ka.resident2 && L6.total <= 52 * 1024;
-#else
-    const bool can_epi = ka.r.best_traj && ka.epi_flag && ka.idx_shadow && !ka.has_loop;
-    // (series asked of THIS kernel pin it to the two-per-CU instances; series offered to the epilogue workgroups do not)
-    bool three = gs == 1 && nsplit == 1 && (!ka.r.best_traj || ka.epi_flag) && b.B > ka.resident2 && L6.total <= 52 * 1024;  // (a margin below 160 KB / 3 for the allocation granule)
-#endif
-    if (ka.lds_cu_kb < 160) three = false;  // (the 52 KB / 40 KB layouts are thirds / quarters of gfx950's 160 KB; a CU with less LDS keeps two per CU)
-    if (in.on) three = false;  // (inline inputs are read by the two-workgroup instances only; they belong to tiny batches anyway)
-#if defined(FP_NO_OCC6)  // (A/B diagnostic)
-    three = false;
-#endif
-    if (ka.occ_cap == 2) three = false;  // (fp_ctx_set_option("lattice_occupancy"))
-    const bool epilogue = three && can_epi;
-    // the FISS+ search in appended workgroups: three-per-CU launches that write their tables, lattices the 1024-sample search instance holds
-    const int C_all = p.nd * p.nv * p.nt;
-    bool search = three && ft && ft->flag && ka.r.cost_tbl && ka.r.flag_tbl && !ka.r.best_traj && !ka.has_loop && C_all > 4 * kWave && C_all <= 1024 &&
-                        ft->opts.kind == FP_FISS_PLUS && !(b.obs_nvert && b.n_obs > 0);
-    static const FissTail kNoFiss{};
-    FissTail fx = search ? *ft : kNoFiss;
-    if (search) fx.NB = 512;  // (a multiple of 64 x the 8 wavefronts of the appended workgroups)
-    const int search_lds = search ? fsp::fissplus_lds_bytes(C_all, fx.NB) : 0;
-    // FOUR workgroups per CU when the slim layout (make_layout) and the appended workgroups' LDS fit a quarter of the CU (BASELINE.json's
-    // dense shape: reference lines of up to ~80 knots); 64 VGPRs a lane, the ego's start state re-read from LDS (kEgoLds)
-    const int w8 = window_for(kLdsQuarter, 8, 0, true);
-    const Layout L8 = make_layout(b.NX, b.n_obs, rows, hp, p.nd, p.nv, p.nt, item_cap(8), 1, kThreads / kWave, 0, true, w8 > 0 ? w8 : b.NX);
-    bool four = three && !pstride && L8.total <= kLdsQuarter && (!epilogue || kEpiLds <= kLdsQuarter) && (!search || search_lds <= kLdsQuarter) && (long)b.B * 2 > (long)ka.resident2 * 3 &&
-                (!b.skip || ka.occ_cap == 4);  // (a closed-loop batch: its finished egos leave at once, what runs rarely fills three per CU - measured 68 -> 71-75 us per cycle with four; "lattice_occupancy" 4 asks for it anyway)
-#if defined(FP_NO_OCC8)  // (A/B diagnostic)
-    four = false;
-#endif
-    if (ka.occ_cap == 2 || ka.occ_cap == 3) four = false;
-    KernelArgs kx = ka;  // (epilogue workgroups offered but not taken: the caller's winner_traj_kernel writes the series)
-    if (ka.epi_flag && !epilogue) { kx.r.best_traj = nullptr; kx.epi_flag = nullptr; }
-    Layout L = four ? L8 : three ? L6 : make_layout(b.NX, b.n_obs, rows, hp, p.nd, p.nv, p.nt, item_cap(4), gs, (gs > 1 ? FP_GROUP_THREADS : kThreads) / kWave, pstride);
-    if (L.total > kLdsLimit) return hipErrorInvalidValue;
-    if (epilogue && L.total < kEpiLds) L.total = kEpiLds;  // (every workgroup of a launch gets the same dynamic LDS)
-    if (search && L.total < search_lds) L.total = search_lds;
-    const int wcap = in.on ? b.NX : four ? (w8 > 0 ? w8 : b.NX) : three ? (w6 > 0 ? w6 : b.NX) : b.NX;  // (two per CU: the whole table, as before)
-    const bool windowed = wcap < b.NX;
-    if (windowed && search) { search = false; fx = kNoFiss; }  // (no WIN instance with appended search workgroups: the search follows in its own launch)
-    if (nsplit > p.nt) nsplit = p.nt;
-    // part_scratch: [ticket counters: kTicketBytes, zero between launches][partial argmins: Best x B x nsplit]
-    int* part_count = (int*)part_scratch;
-    Best* part_best = part_scratch ? (Best*)((char*)part_scratch + kTicketBytes) : nullptr;
-    if (nsplit != 1) perm = nullptr;
-    // Tail split: a launch of several rounds of workgroups (one per ego) ends on the egos that happened to start last - with ~50 us
-    // per ego and the last workgroup starting ~40 us before the end, a fifth of the launch runs on a draining chip.  The last `tail`
-    // dispatch slots are cut in two (time-horizon slices it_lo .. it_hi per part, ticket + merge like the latency mode): each half
-    // repeats the ego's prologue, so only a quarter of a round's worth of slots is cut (tail < 0: auto).  Results do not depend on it.
-    int tail_from = -1;
-#if !defined(FP_PHASE_STAMPS) && !defined(FP_COUNTERS)
-    if (tail != 0 && nsplit == 1 && gs == 1 && part_scratch && p.nt >= 2 && b.S > 0 && b.n_obs > 0 && (size_t)b.B * 4 <= kTicketBytes) {
-        const int resident = (four ? 4 : three ? 3 : 2) * (tail < 0 ? -tail : 0);  // workgroups the device holds at once (auto: tail = -compute units)
-        // (three per CU: 128 ... 384 of 768 slots measured within 1 %; 576: no gain; 768: slower.  Four per CU, launch order = the batch's own
-        // history, round 6: 96-192 of 1024 within 1 % of each other and of no cut at all, 512: 4 % slower - an eighth of a round, which also
-        // halves the inputs staged twice)
-        int n_tail = tail > 0 ? tail : (b.B > resident ? resident / (four ? 8 : 4) : 0);
-        if (n_tail > b.B - resident && tail < 0) n_tail = b.B - resident;
-        if (n_tail > b.B) n_tail = b.B;
-        if (n_tail > 0) tail_from = b.B - n_tail;
-    }
-#endif
-    const unsigned lattice_grid = tail_from >= 0 ? (unsigned)(2 * b.B - tail_from) : (unsigned)(b.B * nsplit);
-    const int epi_from = epilogue || search ? (int)lattice_grid : -1;
-    const unsigned grid = lattice_grid + (epilogue ? (unsigned)((b.B + kEpiPairs - 1) / kEpiPairs) : 0u) + (search ? (unsigned)b.B : 0u);
-    hipError_t e;
-    if (p.curvature_mask) {  // optional curvature checks: their own launch, ORed into the flag words by the assembly stage
-        if (!ka.curv_tbl) return hipErrorInvalidValue;
-        e = launch_curvature_flags(ka, const_cast<uint8_t*>(ka.curv_tbl), stream);
+    constexpr LatticeKey k = kLatticeInstances[I];
+    constexpr LatticeShapeDims d = kLatticeShapes[k.shape];
+    constexpr bool grouped = k.family == kGrouped || k.family == kPolyGrouped;
+    constexpr bool poly = k.family == kPoly || k.family == kPolyGrouped || k.family == kPolyWindow;
+    constexpr bool win = k.family == kWindow || k.family == kPolyWindow;
+    return lattice_fused_kernel<d.nd, d.nv, d.nt, d.stride, d.n_obs, d.rows, 2 * k.per_cu, grouped ? 0 : 1, grouped ? FP_GROUP_THREADS : kThreads, poly,
+                                k.family == kSearch, win>;
+}
+struct LatticeInstance {
+    LatticeFn kernel;
+    int lds_slot[kMaxDevices];  // (zero-initialised where ensure_dynamic_lds expects -1: no plan's LDS is zero)
+};
+template <size_t... I>
+static LatticeInstance& lattice_instance_at(int i, std::index_sequence<I...>)
+{
+    static LatticeInstance table[] = {{lattice_kernel_of<I>(), {}}...};
+    return table[i];
+}
+
+static hipError_t launch_lattice_fused(const KernelArgs& ka, hipStream_t stream, const LatticeRequest& rq, const LatticePlan& pl, LatticeResult* res)
+{
+    if (ka.p.curvature_mask) {  // optional curvature checks: their own launch, ORed into the flag words by the assembly stage
+        if (!ka.curv_tbl) return hipErrorInvalidValue;  // (internal: the caller provides the table)
+        const hipError_t e = launch_curvature_flags(ka, const_cast<uint8_t*>(ka.curv_tbl), stream);
         if (e != hipSuccess) return e;
     }
-    // the instance whose compile-time shape is this problem's (BASELINE.json's two lattice shapes), else the run-time one
-    auto go = [&](auto kernel, int* configured, int threads = kThreads) -> hipError_t {
-        hipError_t err = ensure_dynamic_lds((const void*)kernel, L.total, configured);
-        if (err != hipSuccess) return err;
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), L.total, stream, kx, rows, hp, nsplit, part_best, part_count, perm, dur, gs, tail_from, epi_from, wcap, fx, in);
-        return hipGetLastError();
-    };
-    FP_LDS_SLOTS(cfg_generic);
-    FP_LDS_SLOTS(cfg_997);
-    FP_LDS_SLOTS(cfg_555);
-    FP_LDS_SLOTS(cfg_generic6);
-    FP_LDS_SLOTS(cfg_9976);
-    FP_LDS_SLOTS(cfg_9978);
-    FP_LDS_SLOTS(cfg_9978f);
-    FP_LDS_SLOTS(cfg_generic8);
-    FP_LDS_SLOTS(cfg_generic8f);
-    FP_LDS_SLOTS(cfg_5556);
-    FP_LDS_SLOTS(cfg_generic_g);
-    FP_LDS_SLOTS(cfg_997_g);
-    FP_LDS_SLOTS(cfg_555_g);
-    FP_LDS_SLOTS(cfg_9976f);
-    FP_LDS_SLOTS(cfg_generic6f);
-    FP_LDS_SLOTS(cfg_poly);
-    FP_LDS_SLOTS(cfg_poly6);
-    FP_LDS_SLOTS(cfg_poly9976);
-    FP_LDS_SLOTS(cfg_poly6w);
-    FP_LDS_SLOTS(cfg_poly9976w);
-    FP_LDS_SLOTS(cfg_poly_g);
-    FP_LDS_SLOTS(cfg_9978w);
-    FP_LDS_SLOTS(cfg_generic8w);
-    FP_LDS_SLOTS(cfg_9976w);
-    FP_LDS_SLOTS(cfg_generic6w);
-    auto is = [&](int nd, int nv, int nt, int stride, int n_obs, int r) {
-        return p.nd == nd && p.nv == nv && p.nt == nt && p.check_stride == stride && b.n_obs == n_obs && rows == r;
-    };
-#if defined(FP_NO_SHAPES)  // (A/B diagnostic: the run-time instance for every shape)
-    e = gs > 1 ? go(lattice_fused_kernel<0, 0, 0, 0, 0, 0, 4, 0, FP_GROUP_THREADS, true>, cfg_generic_g, FP_GROUP_THREADS) : go(lattice_fused_kernel<0, 0, 0, 0, 0, 0, 4, 1, 512, true>, cfg_generic);
-#else
-    if (b.obs_nvert && b.n_obs > 0) {  // convex-polygon columns: the run-time-shape instances with the polygon narrow phase
-        if (gs > 1) e = go(lattice_fused_kernel<0, 0, 0, 0, 0, 0, 4, 0, FP_GROUP_THREADS, true>, cfg_poly_g, FP_GROUP_THREADS);
-        else if (three && windowed && is(9, 9, 7, 2, 50, 25)) e = go(lattice_fused_kernel<9, 9, 7, 2, 50, 25, 6, 1, 512, true, false, true>, cfg_poly9976w);
-        else if (three && windowed) e = go(lattice_fused_kernel<0, 0, 0, 0, 0, 0, 6, 1, 512, true, false, true>, cfg_poly6w);
-        else if (three && is(9, 9, 7, 2, 50, 25)) e = go(lattice_fused_kernel<9, 9, 7, 2, 50, 25, 6, 1, 512, true>, cfg_poly9976);
-        else if (three) e = go(lattice_fused_kernel<0, 0, 0, 0, 0, 0, 6, 1, 512, true>, cfg_poly6);
-        else e = go(lattice_fused_kernel<0, 0, 0, 0, 0, 0, 4, 1, 512, true>, cfg_poly);
-    } else if (gs > 1) {
-        if (is(9, 9, 7, 2, 50, 25)) e = go(lattice_fused_kernel<9, 9, 7, 2, 50, 25, 4, 0, FP_GROUP_THREADS>, cfg_997_g, FP_GROUP_THREADS);
-        else if (is(5, 5, 5, 2, 10, 50)) e = go(lattice_fused_kernel<5, 5, 5, 2, 10, 50, 4, 0, FP_GROUP_THREADS>, cfg_555_g, FP_GROUP_THREADS);
-        else e = go(lattice_fused_kernel<0, 0, 0, 0, 0, 0, 4, 0, FP_GROUP_THREADS>, cfg_generic_g, FP_GROUP_THREADS);
-    } else if (search) {
-        if (four && is(9, 9, 7, 2, 50, 25)) e = go(lattice_fused_kernel<9, 9, 7, 2, 50, 25, 8, 1, 512, false, true>, cfg_9978f);
-        else if (four) e = go(lattice_fused_kernel<0, 0, 0, 0, 0, 0, 8, 1, 512, false, true>, cfg_generic8f);
-        else if (is(9, 9, 7, 2, 50, 25)) e = go(lattice_fused_kernel<9, 9, 7, 2, 50, 25, 6, 1, 512, false, true>, cfg_9976f);
-        else e = go(lattice_fused_kernel<0, 0, 0, 0, 0, 0, 6, 1, 512, false, true>, cfg_generic6f);
-    } else if (three && windowed) {  // long reference lines: the instances that keep a window of the coefficient columns in LDS
-        if (four && is(9, 9, 7, 2, 50, 25)) e = go(lattice_fused_kernel<9, 9, 7, 2, 50, 25, 8, 1, 512, false, false, true>, cfg_9978w);
-        else if (four) e = go(lattice_fused_kernel<0, 0, 0, 0, 0, 0, 8, 1, 512, false, false, true>, cfg_generic8w);
-        else if (is(9, 9, 7, 2, 50, 25)) e = go(lattice_fused_kernel<9, 9, 7, 2, 50, 25, 6, 1, 512, false, false, true>, cfg_9976w);
-        else e = go(lattice_fused_kernel<0, 0, 0, 0, 0, 0, 6, 1, 512, false, false, true>, cfg_generic6w);
-    } else if (three) {
-        if (four && is(9, 9, 7, 2, 50, 25)) e = go(lattice_fused_kernel<9, 9, 7, 2, 50, 25, 8, 1, 512>, cfg_9978);
-        else if (four) e = go(lattice_fused_kernel<0, 0, 0, 0, 0, 0, 8, 1, 512>, cfg_generic8);
-        else if (is(9, 9, 7, 2, 50, 25)) e = go(lattice_fused_kernel<9, 9, 7, 2, 50, 25, 6, 1, 512>, cfg_9976);
-        else if (is(5, 5, 5, 2, 10, 50)) e = go(lattice_fused_kernel<5, 5, 5, 2, 10, 50, 6, 1, 512>, cfg_5556);
-        else e = go(lattice_fused_kernel<0, 0, 0, 0, 0, 0, 6, 1, 512>, cfg_generic6);
-    } else {
-        if (is(9, 9, 7, 2, 50, 25)) e = go(lattice_fused_kernel<9, 9, 7, 2, 50, 25, 4, 1, 512>, cfg_997);
-        else if (is(5, 5, 5, 2, 10, 50)) e = go(lattice_fused_kernel<5, 5, 5, 2, 10, 50, 4, 1, 512>, cfg_555);
-        else e = go(lattice_fused_kernel<0, 0, 0, 0, 0, 0, 4, 1, 512>, cfg_generic);
-    }
-#endif
+    // the kernel's arguments, one variable per parameter
+    KernelArgs kx = ka;  // (epilogue workgroups offered but not taken: the caller's winner_traj_kernel writes the series)
+    if (ka.epi_flag && !pl.epilogue) { kx.r.best_traj = nullptr; kx.epi_flag = nullptr; }
+    int rows = pl.rows, hp = pl.hp, nsplit = pl.nsplit, gs = pl.gs, tail_from = pl.tail_from, epi_from = pl.epi_from, wcap = pl.wcap;
+    // part_scratch: [ticket counters: kTicketBytes, zero between launches][partial argmins: Best x B x nsplit]
+    int* part_count = (int*)rq.part_scratch;
+    Best* part_best = rq.part_scratch ? (Best*)((char*)rq.part_scratch + kTicketBytes) : nullptr;
+    const int* perm = pl.nsplit == 1 ? rq.perm : nullptr;
+    int* dur = rq.dur;
+    FissTail fx{};
+    if (pl.search) { fx = *rq.ft; fx.NB = kAppendedSearchNB; }
+    static const InlineIn kNoInline{};
+    const InlineIn* in = rq.inl ? rq.inl : &kNoInline;
+    void* args[] = {&kx, &rows, &hp, &nsplit, &part_best, &part_count, &perm, &dur, &gs, &tail_from, &epi_from, &wcap, &fx, (void*)in};
+    LatticeInstance& inst = lattice_instance_at(pl.instance, std::make_index_sequence<kLatticeInstanceCount>());
+    hipError_t e = ensure_dynamic_lds((const void*)inst.kernel, pl.lds, inst.lds_slot);
     if (e != hipSuccess) return e;
-    g_launches_per_cu[four ? 2 : three ? 1 : 0].fetch_add(1, std::memory_order_relaxed);
-    if (winner_done) *winner_done = kx.r.best_traj != nullptr && (!three || epilogue);
-    if (step_done) *step_done = ka.has_loop != 0 && !three;  // (ka.has_loop: the two-per-CU instances hand the egos over themselves)
-    if (search_done) *search_done = search;
+    e = hipLaunchKernel((const void*)inst.kernel, dim3(pl.grid), dim3(pl.threads), args, pl.lds, stream);
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    g_launches_per_cu[pl.per_cu - 2].fetch_add(1, std::memory_order_relaxed);
+    *res = LatticeResult{pl.series, ka.has_loop != 0 && pl.per_cu == 2, pl.search};  // (the two-per-CU instances hand the egos over themselves)
     return hipSuccess;
+}
+
+hipError_t launch_lattice(const KernelArgs& ka, hipStream_t stream, int which, const LatticeRequest& rq, LatticeResult* res)
+{
+    *res = LatticeResult{};
+    const LatticePlan pl = which == 1 ? LatticePlan{} : plan_lattice(ka, rq);
+    if (pl.fits) return launch_lattice_fused(ka, stream, rq, pl, res);
+    if (which == 2 || (rq.inl && rq.inl->on)) return hipErrorInvalidValue;  // (the fused kernel or nothing)
+    return launch_lattice_percand(ka, stream);
 }
 
 }  // namespace fp
