@@ -99,6 +99,9 @@ class ProblemBatch:
     # (max_curvature, max_kappa_d, max_kappa_dd): turns on the curvature checks the reference carries commented out
     # (frenet_optimal_planner.py:145-150); None = off = the reference's behaviour
     curvature_limits: tuple | None = None
+    # weight of the obstacle-clearance cost term the reference keeps as a stub (cost_function.py:9,21-27,43; fp_params.w_obstacle):
+    # survivors of the dense FOP pass cost (base_sum + w_obstacle * sum exp(-dist)) / N; 0 = off = the reference's behaviour
+    w_obstacle: float = 0.0
     # obstacle columns that are convex polygons instead of rectangles (fp_batch.obs_poly / obs_nvert); None = rectangles only
     obs_poly: np.ndarray | None = None   # [S, n_obs, PV, 2]
     obs_nvert: np.ndarray | None = None  # [S, n_obs] int32
@@ -165,6 +168,7 @@ class ProblemBatch:
             samp_min=None if self.samp_min is None else self.samp_min[sel],
             samp_max=None if self.samp_max is None else self.samp_max[sel],
             samp_res=None if self.samp_res is None else self.samp_res[sel], curvature_limits=self.curvature_limits,
+            w_obstacle=self.w_obstacle,
             obs_poly=None if self.obs_nvert is None else self.obs_poly[keep_s],
             obs_nvert=None if self.obs_nvert is None else self.obs_nvert[keep_s],
             meta=dict(self.meta, **(meta or {})))

@@ -190,6 +190,7 @@ struct fp_ctx {
     // longest-first and uploads the order the following launches dispatch in.  A stale or missing order only costs speed.
     int lattice_order = 1;
     int lattice_launches = 0, lattice_ordered_launches = 0;  // fp_ctx_get_option counters
+    int clearance_launches = 0;    // fp_ctx_get_option("clearance_launches"): launches of the clearance rescoring kernel (fp_params.w_obstacle > 0)
     OrderSet order_lattice, order_refine;
     DeviceBuf idx_shadow;          // [B] device copy of best_idx for the winner kernel of a dense call (KernelArgs::idx_shadow)
     DeviceBuf epi_flags;           // [B] hand-over flags of the epilogue workgroups appended to a multi-round lattice launch (KernelArgs::epi_flag); zero between launches
@@ -390,6 +391,7 @@ int check_params(const fp_params* p)
     if (p->points_max < 0 || p->points_max > FP_MAX_POINTS) return fail(FP_ELIMIT, "points_max=%d outside 0..FP_MAX_POINTS", p->points_max);
     if (p->curvature_mask && (!(p->max_curvature >= 0) || !(p->max_kappa_d >= 0) || !(p->max_kappa_dd >= 0)))
         return fail(FP_EINVAL, "curvature_mask is set but max_curvature / max_kappa_d / max_kappa_dd are not all >= 0");
+    if (!(p->w_obstacle >= 0) || p->w_obstacle > 1.7976931348623157e308) return fail(FP_EINVAL, "w_obstacle must be finite and >= 0");
     return FP_OK;
 }
 
@@ -824,7 +826,7 @@ void ctx_lattice_args(const fp_ctx* ctx, fp::KernelArgs* ka)
 // offers of the KernelArgs (the series inside, epilogue workgroups, the loop hand-over); inl / ft offer inline inputs and the
 // appended FISS+ search (either may be nullptr); *res says what the launch took.
 int lattice_step(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, fp::KernelArgs kl, hipStream_t stream, int which, const int* hint,
-                 const fp::InlineIn* inl, const fp::FissTail* ft, fp::LatticeResult* res)
+                 const fp::InlineIn* inl, const fp::FissTail* ft, fp::LatticeResult* res, bool provisional = false)
 {
     if (params->curvature_mask) {  // optional curvature checks: the fused lattice kernel reads them from a [B][C] byte table it fills first
         const size_t need = (size_t)batch->B * params->nd * params->nv * params->nt + kAlign;
@@ -838,7 +840,7 @@ int lattice_step(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, fp
     FP_TRY(lattice_split_for(ctx, params, batch, stream, &rq.nsplit, &rq.part_scratch, &rq.group, &rq.tail));
     LaunchOrder* oslot = nullptr;
     FP_TRY(launch_order_before(ctx, ctx->order_lattice, ctx->resident_groups, batch, rq.nsplit, stream, &rq.perm, &rq.dur, hint, &oslot));
-    rq.inl = inl; rq.ft = ft;
+    rq.inl = inl; rq.ft = ft; rq.provisional = provisional;
     LAUNCH_TRY(fp::launch_lattice(kl, stream, which, rq, res), "lattice kernel");
     return launch_order_after(oslot, batch, rq.dur, stream);
 }
@@ -854,16 +856,26 @@ bool winner_inside_lattice(const fp_ctx* ctx, const fp_batch* b)
     return b->B <= ctx->resident_groups;
 }
 
+// The clearance cost term (fp_params.w_obstacle > 0) behind the lattice pass of a dense call: survivors re-priced in ka's tables, the
+// ego's argmin over the new costs in best_idx / best_cost (and the shadow the winner kernel reads).
+int clearance_step(fp_ctx* ctx, const fp::KernelArgs& ka, const int32_t* launch_order, hipStream_t stream)
+{
+    LAUNCH_TRY(fp::launch_clearance_rescore(ka, launch_order, stream), "clearance rescoring kernel");
+    ++ctx->clearance_launches;
+    return FP_OK;
+}
+
 fp_result no_result() { return fp_result{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0}; }
 
-// FopPlusPlanner counts pops over the dense tables: when the caller did not ask for them they live in the ctx's scratch buffer.
+// FopPlusPlanner counts pops over the dense tables, the audit and the clearance rescoring walk them: when the caller did not ask
+// for them they live in the ctx's scratch buffer.
 int fopplus_tables(fp_ctx* ctx, size_t B, size_t C, fp_result* r, hipStream_t stream)
 {
     const size_t need = align_up(sizeof(double) * B * C) + align_up(sizeof(uint32_t) * B * C);
     if (need > ctx->scratch.cap) {  // growing the buffer frees the old one: not inside a stream capture, and not under its users
         hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
         if (hipStreamIsCapturing(stream, &cap) != hipSuccess) (void)hipGetLastError();
-        if (cap != hipStreamCaptureStatusNone) return fail(FP_EINVAL, "result.fopplus: the ctx's table scratch must grow - run one call of this size outside the stream capture first");
+        if (cap != hipStreamCaptureStatusNone) return fail(FP_EINVAL, "result.fopplus / result.audit / w_obstacle: the ctx's table scratch must grow - run one call of this size outside the stream capture first");
         HIP_TRY(hipStreamSynchronize(stream));
     }
     FP_TRY(ctx->scratch.reserve(need));
@@ -1432,7 +1444,7 @@ int fp_ctx_get_option(fp_ctx* ctx, const char* name, int* value)
     if (!ctx || !name || !value) return fail(FP_EINVAL, "ctx/name/value is NULL");
     const struct { const char* n; int v; } tab[] = {
         {"lattice_kernel", ctx->lattice_kernel}, {"lattice_split", ctx->lattice_split}, {"lattice_group", ctx->lattice_group}, {"lattice_tail", ctx->lattice_tail}, {"lattice_occupancy", ctx->lattice_occupancy}, {"resident_groups", ctx->resident_groups}, {"zero_copy_in", ctx->zero_copy_in}, {"stage_kernel", ctx->stage_kernel}, {"inline_inputs", ctx->inline_inputs}, {"lattice_order", ctx->lattice_order},
-        {"refine_table_kb", ctx->refine_table_kb}, {"fiss_stages", ctx->fiss_stages}, {"fiss_jump", ctx->fiss_jump}, {"validate", ctx->validate}, {"lattice_winner", ctx->lattice_winner}, {"fiss_fused", ctx->fiss_fused}, {"appended_workgroups", ctx->appended_ok ? 1 : 0}, {"handover_failed", ctx->hand_err ? *(volatile int32_t*)ctx->hand_err : 0}, {"overlap", ctx->overlap}, {"overlapped_calls", ctx->overlapped_calls}, {"lattice_launches", ctx->lattice_launches + (ctx->twin ? ctx->twin->lattice_launches : 0)},
+        {"refine_table_kb", ctx->refine_table_kb}, {"fiss_stages", ctx->fiss_stages}, {"fiss_jump", ctx->fiss_jump}, {"validate", ctx->validate}, {"lattice_winner", ctx->lattice_winner}, {"fiss_fused", ctx->fiss_fused}, {"appended_workgroups", ctx->appended_ok ? 1 : 0}, {"handover_failed", ctx->hand_err ? *(volatile int32_t*)ctx->hand_err : 0}, {"overlap", ctx->overlap}, {"overlapped_calls", ctx->overlapped_calls}, {"clearance_launches", ctx->clearance_launches + (ctx->twin ? ctx->twin->clearance_launches : 0)}, {"lattice_launches", ctx->lattice_launches + (ctx->twin ? ctx->twin->lattice_launches : 0)},
         {"lattice_ordered_launches", ctx->lattice_ordered_launches + (ctx->twin ? ctx->twin->lattice_ordered_launches : 0)},
         {"lattice_launches_2", (int)fp::lattice_launches_per_cu(0)}, {"lattice_launches_3", (int)fp::lattice_launches_per_cu(1)}, {"lattice_launches_4", (int)fp::lattice_launches_per_cu(2)}};
     for (const auto& t : tab)
@@ -1463,6 +1475,9 @@ static int plan_dense_impl(fp_ctx* ctx, const fp_params* params, const fp_batch*
     if (!result || !result->best_idx || !result->best_cost) return fail(FP_EINVAL, "result.best_idx/best_cost must not be NULL");
     if (result->best_traj && !result->best_flags) return fail(FP_EINVAL, "result.best_traj requires result.best_flags");
     if (result->audit && result->fopplus) return fail(FP_EINVAL, "result.audit settles FrenetOptimalPlanner's argmin: not together with result.fopplus");
+    const bool clearance = params->w_obstacle > 0;
+    if (clearance && (result->fopplus || result->audit))
+        return fail(FP_EINVAL, "w_obstacle > 0: the clearance term is defined for FrenetOptimalPlanner's dense pass only - result.fopplus / result.audit must be NULL");
     if (batch->B == 0) return FP_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     const hipStream_t st = mem == FP_MEM_DEVICE ? (hipStream_t)stream : ctx->stream;
@@ -1491,7 +1506,7 @@ static int plan_dense_impl(fp_ctx* ctx, const fp_params* params, const fp_batch*
                           HostStage::need<double>(traj_doubles) + HostStage::need<int32_t>(B * 2) + HostStage::need<uint32_t>(B),
                           /*zero_copy_out=*/B <= 8));
         // (inline inputs need the fused kernel with the winner's series inside it: no other kernel of this call may read the batch)
-        const bool try_inline = ctx->inline_inputs && B <= 8 && !params->curvature_mask && ctx->lattice_kernel != 1 && !big_points(ka.p) &&
+        const bool try_inline = ctx->inline_inputs && B <= 8 && !params->curvature_mask && ctx->lattice_kernel != 1 && !big_points(ka.p) && !clearance &&
                                 (!result->best_traj || winner_inside_lattice(ctx, batch)) && !result->audit && fp::lattice_group_fit(*params, *batch) >= 1;
         FP_TRY(stage_batch(hs, params, batch, &ka.b, try_inline ? &inl : nullptr));
         FP_TRY(hs.flush_in());
@@ -1509,19 +1524,20 @@ static int plan_dense_impl(fp_ctx* ctx, const fp_params* params, const fp_batch*
         // sparse rows are only partly written by the kernels: the host block comes back with the caller's own bytes elsewhere
         if (result->traj_sparse && ka.r.best_traj) HIP_TRY(hipMemcpyAsync(ka.r.best_traj, result->best_traj, traj_doubles * sizeof(double), hipMemcpyDefault, st));
     }
-    if ((result->fopplus || result->audit) && (!ka.r.cost_tbl || !ka.r.flag_tbl)) FP_TRY(fopplus_tables(ctx, B, C, &ka.r, st));
+    if ((result->fopplus || result->audit || clearance) && (!ka.r.cost_tbl || !ka.r.flag_tbl)) FP_TRY(fopplus_tables(ctx, B, C, &ka.r, st));
     // the series: inside the lattice workgroups, else by the epilogue workgroups appended to the launch or by winner_traj_kernel behind
-    // it (the audit pass may move the winner: its series are written after it, by their own launch)
+    // it (the audit pass and the clearance rescoring may move the winner: its series are written after them, by their own launch)
     const bool big = big_points(ka.p);
-    const bool inside = winner_inside_lattice(ctx, batch) && !result->audit && !big;
+    const bool inside = winner_inside_lattice(ctx, batch) && !result->audit && !big && !clearance;
     if (result->best_traj && !inside) ka.idx_shadow = idx_shadow_for(ctx, B, st);
     fp::KernelArgs kl = ka;
     if (!inside) kl.r.best_traj = nullptr;
-    if (!inside && !result->audit && !big && ctx->lattice_winner == 0 && ctx->appended_ok && ka.r.best_traj && ka.idx_shadow) {  // ("lattice_winner" 0: auto)
+    if (!inside && !result->audit && !big && !clearance && ctx->lattice_winner == 0 && ctx->appended_ok && ka.r.best_traj && ka.idx_shadow) {  // ("lattice_winner" 0: auto)
         if (int32_t* flags = epi_flags_for(ctx, B, st)) { kl.r.best_traj = ka.r.best_traj; kl.epi_flag = flags; }  // (taken by three-per-CU launches)
     }
     fp::LatticeResult lr;
-    FP_TRY(lattice_step(ctx, params, batch, kl, st, ctx->lattice_kernel, mem == FP_MEM_DEVICE ? batch->launch_order : nullptr, inl.on ? &inl : nullptr, nullptr, &lr));
+    FP_TRY(lattice_step(ctx, params, batch, kl, st, ctx->lattice_kernel, mem == FP_MEM_DEVICE ? batch->launch_order : nullptr, inl.on ? &inl : nullptr, nullptr, &lr, clearance));
+    if (clearance) FP_TRY(clearance_step(ctx, ka, mem == FP_MEM_DEVICE ? batch->launch_order : nullptr, st));
     if (audit) LAUNCH_TRY(fp::launch_audit(ka, audit, st), "audit kernel");
     if (result->best_traj && !lr.winner_done) {
         if (inl.on) return fail(FP_EHIP, "internal: inline inputs without the series inside the lattice kernel");
@@ -1629,6 +1645,8 @@ int plan_fiss_impl(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, 
 {
     FP_TRY(common_checks(ctx, params, batch, mem, stream_v));
     if (!opts || !io) return fail(FP_EINVAL, "opts/io is NULL");
+    if (params->w_obstacle > 0)
+        return fail(FP_EINVAL, "w_obstacle > 0: FISS / FISS+ order candidates by cost before they have Cartesian points - the clearance term is defined for fp_plan_dense / fp_plan_step only");
     if (opts->kind != FP_FISS && opts->kind != FP_FISS_PLUS) return fail(FP_EINVAL, "opts.kind must be FP_FISS or FP_FISS_PLUS");
     if (opts->max_refine_iters < 0 || opts->max_refine_iters * 7 > 64) return fail(FP_ELIMIT, "max_refine_iters must be in 0..9");
     if ((long)params->nd * params->nv * params->nt > FP_MAX_CAND_SEARCH)
@@ -1878,13 +1896,17 @@ int fp_plan_step(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, co
     ka.r = *result;
     // the hand-over is offered to the lattice launch unless that launch cannot write the series it is asked for itself (the standalone
     // epilogue reads the ego's state, so it has to run BEFORE the state moves on)
-    const bool series_elsewhere = result->best_traj && (!winner_inside_lattice(ctx, batch) || big_points(ka.p));
+    // (nor when the clearance rescoring decides the winner behind the launch: series and hand-over follow it)
+    const bool clearance = params->w_obstacle > 0;
+    if (clearance && (!ka.r.cost_tbl || !ka.r.flag_tbl)) FP_TRY(fopplus_tables(ctx, B, (size_t)params->nd * params->nv * params->nt, &ka.r, (hipStream_t)stream));
+    const bool series_elsewhere = result->best_traj && (!winner_inside_lattice(ctx, batch) || big_points(ka.p) || clearance);
     if (series_elsewhere) ka.idx_shadow = idx_shadow_for(ctx, B, (hipStream_t)stream);
     fp::KernelArgs kl = ka;
     if (series_elsewhere) kl.r.best_traj = nullptr;
-    else { kl.loop = *io; kl.has_loop = 1; }
+    else if (!clearance) { kl.loop = *io; kl.has_loop = 1; }
     fp::LatticeResult lr;
-    FP_TRY(lattice_step(ctx, params, batch, kl, (hipStream_t)stream, ctx->lattice_kernel, batch->launch_order, nullptr, nullptr, &lr));
+    FP_TRY(lattice_step(ctx, params, batch, kl, (hipStream_t)stream, ctx->lattice_kernel, batch->launch_order, nullptr, nullptr, &lr, clearance));
+    if (clearance) FP_TRY(clearance_step(ctx, ka, batch->launch_order, (hipStream_t)stream));
     if (result->best_traj && !lr.winner_done) LAUNCH_TRY(fp::launch_winner_traj(ka, nullptr, (hipStream_t)stream), "winner epilogue");
     if (!lr.step_done) LAUNCH_TRY(fp::launch_advance(ka, ka.r.best_idx, nullptr, *io, (hipStream_t)stream), "advance kernel");
     return FP_OK;

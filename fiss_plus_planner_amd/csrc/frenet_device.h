@@ -422,6 +422,70 @@ __device__ __forceinline__ bool shape_overlap(const Obb& ego, const Obb& ob, con
     return true;
 }
 
+// ---------------------------------------------------------------------------
+// True Euclidean distances for the obstacle-clearance cost term (fp_params.w_obstacle): the distance between two CLOSED convex
+// sets, 0 when they touch or overlap - not the separating-axis lower bound obb_gap / poly_gap return.  Two disjoint convex polygons
+// are closest at a vertex of one and a point (vertex or edge) of the other, so the distance is the smallest of the vertex-to-set
+// distances both ways; a rectangle makes its half trivial in its own frame (point against [-hl, hl] x [-hw, hw]).
+// ---------------------------------------------------------------------------
+// squared distance of the point (px, py) to the box [-hl, hl] x [-hw, hw] (0 inside)
+__device__ __forceinline__ double point_box_dist2(double px, double py, double hl, double hw)
+{
+    const double ax = fmax(fabs(px) - hl, 0.0), ay = fmax(fabs(py) - hw, 0.0);
+    return fma(ax, ax, ay * ay);
+}
+// smallest squared distance of b's four corners to the box a
+__device__ __forceinline__ double corners_box_dist2(const Obb& a, const Obb& b)
+{
+    const double dx = b.x - a.x, dy = b.y - a.y;
+    const double px = fma(dx, a.c, dy * a.s), py = fma(dy, a.c, -dx * a.s);     // b's centre in a's frame
+    const double C = fma(b.c, a.c, b.s * a.s), S = fma(b.s, a.c, -b.c * a.s);   // cos / sin of (b's yaw - a's yaw)
+    const double lx = C * b.hl, ly = S * b.hl, wx = -S * b.hw, wy = C * b.hw;   // b's half axes in a's frame
+    const double d0 = point_box_dist2(px + lx + wx, py + ly + wy, a.hl, a.hw);
+    const double d1 = point_box_dist2(px + lx - wx, py + ly - wy, a.hl, a.hw);
+    const double d2 = point_box_dist2(px - lx + wx, py - ly + wy, a.hl, a.hw);
+    const double d3 = point_box_dist2(px - lx - wx, py - ly - wy, a.hl, a.hw);
+    return fmin(fmin(d0, d1), fmin(d2, d3));
+}
+__device__ __forceinline__ double obb_distance(const Obb& a, const Obb& b)
+{
+    if (obb_overlap(a, b)) return 0.0;  // (two boxes can cross without a corner of one inside the other)
+    return sqrt(fmin(corners_box_dist2(a, b), corners_box_dist2(b, a)));
+}
+
+// squared distance of the point (px, py) to the segment from (ax, ay) along (ex, ey); inv_len2 = 1 / |e|^2, or 0 for a repeated vertex
+__device__ __forceinline__ double point_segment_dist2(double px, double py, double ax, double ay, double ex, double ey, double inv_len2)
+{
+    const double rx = px - ax, ry = py - ay;
+    const double t = fmin(fmax(fma(rx, ex, ry * ey) * inv_len2, 0.0), 1.0);
+    const double qx = fma(-t, ex, rx), qy = fma(-t, ey, ry);
+    return fma(qx, qx, qy * qy);
+}
+// the ego box against a convex counter-clockwise ring (arguments as poly_gap's), in the ego's frame: every ring vertex against the box,
+// every box corner against every ring edge
+__device__ __forceinline__ double poly_distance(const Obb& ego, double ox, double oy, double oc, double os, const double* __restrict__ v, int n)
+{
+    if (poly_overlap(ego, ox, oy, oc, os, v, n)) return 0.0;
+    const double dx = ox - ego.x, dy = oy - ego.y;
+    const double px = fma(dx, ego.c, dy * ego.s), py = fma(dy, ego.c, -dx * ego.s);
+    const double C = fma(oc, ego.c, os * ego.s), S = fma(os, ego.c, -oc * ego.s);
+    double ux = v[2 * (n - 1)], uy = v[2 * (n - 1) + 1];
+    double qpx = px + fma(C, ux, -S * uy), qpy = py + fma(S, ux, C * uy);  // previous vertex
+    double d2 = __builtin_inf();
+    for (int i = 0; i < n; ++i) {
+        ux = v[2 * i]; uy = v[2 * i + 1];
+        const double qx = px + fma(C, ux, -S * uy), qy = py + fma(S, ux, C * uy);
+        d2 = fmin(d2, point_box_dist2(qx, qy, ego.hl, ego.hw));
+        const double ex = qx - qpx, ey = qy - qpy;
+        const double len2 = fma(ex, ex, ey * ey);
+        const double inv = len2 > 0.0 ? 1.0 / len2 : 0.0;
+        d2 = fmin(d2, fmin(fmin(point_segment_dist2(ego.hl, ego.hw, qpx, qpy, ex, ey, inv), point_segment_dist2(ego.hl, -ego.hw, qpx, qpy, ex, ey, inv)),
+                           fmin(point_segment_dist2(-ego.hl, ego.hw, qpx, qpy, ex, ey, inv), point_segment_dist2(-ego.hl, -ego.hw, qpx, qpy, ex, ey, inv))));
+        qpx = qx; qpy = qy;
+    }
+    return sqrt(d2);
+}
+
 // heading unit vector of the step (dx,dy): cos/sin(atan2(dy,dx)); atan2(0,0) = 0 -> (1,0).
 // An axis-parallel step gives exactly (+-1, 0) / (0, +-1), as cos / sin of atan2's exact 0, pi, +-pi/2 do after shapely's snap
 // (see sincos_snapped): boxes that touch exactly are then decided by exact arithmetic, like in the reference.

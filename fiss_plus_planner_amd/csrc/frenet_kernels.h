@@ -133,6 +133,9 @@ struct LatticeRequest {
     int tail = 0;                  // (needs part_scratch) cut the last `tail` slots of a multi-round launch in two; < 0: auto for -tail CUs
     const InlineIn* inl = nullptr;  // inline inputs: the fused kernel or nothing
     const FissTail* ft = nullptr;   // the FISS+ search in workgroups appended to the launch (three- / four-per-CU launches)
+    // a pass behind the launch decides the winner (the clearance rescoring, fp_params.w_obstacle > 0): the launch writes its tables and
+    // a provisional argmin - no series from its workgroups, no epilogue workgroups, no loop hand-over, whatever the KernelArgs offer
+    bool provisional = false;
 };
 // What the launch did: wrote the winner's series (else winner_traj_kernel follows), handed the egos over (else advance_kernel),
 // ran the FISS+ search (else the search kernel).
@@ -144,6 +147,9 @@ int lattice_group_fit(const fp_params& p, const fp_batch& b);
 // counters behind fp_ctx_get_option("lattice_launches_2 / _3 / _4") - what the tests use to know which instance family they ran
 long lattice_launches_per_cu(int which);
 hipError_t launch_lattice_percand(const KernelArgs& ka, hipStream_t stream);
+// The clearance cost term (frenet_clearance.hip): re-prices the survivors in ka.r.cost_tbl (ka.r.flag_tbl says who survived), rewrites
+// ka.r.best_idx / best_cost (+ idx_shadow) with the argmin of the new costs.  One workgroup per ego, in the order of perm (optional).
+hipError_t launch_clearance_rescore(const KernelArgs& ka, const int* perm, hipStream_t stream);
 // Curvature flags of every lattice candidate -> out [B][C] (one workgroup per ego, one lane per candidate, spline in LDS).
 hipError_t launch_curvature_flags(const KernelArgs& ka, uint8_t* out, hipStream_t stream);
 // The lattice pass of a dense, FISS or closed-loop call.  which: 0 = auto (the fused kernel when the problem fits it, else the

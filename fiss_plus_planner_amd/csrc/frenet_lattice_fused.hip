@@ -1680,6 +1680,7 @@ static hipError_t launch_lattice_fused(const KernelArgs& ka, hipStream_t stream,
     // the kernel's arguments, one variable per parameter
     KernelArgs kx = ka;  // (epilogue workgroups offered but not taken: the caller's winner_traj_kernel writes the series)
     if (ka.epi_flag && !pl.epilogue) { kx.r.best_traj = nullptr; kx.epi_flag = nullptr; }
+    if (rq.provisional) { kx.r.best_traj = nullptr; kx.epi_flag = nullptr; kx.has_loop = 0; }  // (as planned: tables and a provisional argmin only)
     int rows = pl.rows, hp = pl.hp, nsplit = pl.nsplit, gs = pl.gs, tail_from = pl.tail_from, epi_from = pl.epi_from, wcap = pl.wcap;
     // part_scratch: [ticket counters: kTicketBytes, zero between launches][partial argmins: Best x B x nsplit]
     int* part_count = (int*)rq.part_scratch;
@@ -1698,7 +1699,7 @@ static hipError_t launch_lattice_fused(const KernelArgs& ka, hipStream_t stream,
     if (e == hipSuccess) e = hipGetLastError();
     if (e != hipSuccess) return e;
     g_launches_per_cu[pl.per_cu - 2].fetch_add(1, std::memory_order_relaxed);
-    *res = LatticeResult{pl.series, ka.has_loop != 0 && pl.per_cu == 2, pl.search};  // (the two-per-CU instances hand the egos over themselves)
+    *res = LatticeResult{pl.series, kx.has_loop != 0 && pl.per_cu == 2, pl.search};  // (the two-per-CU instances hand the egos over themselves)
     return hipSuccess;
 }
 

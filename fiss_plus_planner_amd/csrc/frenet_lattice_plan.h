@@ -225,6 +225,11 @@ inline LatticePlan plan_lattice(const KernelArgs& ka, const LatticeRequest& rq)
     constexpr bool stamps = diag & kStamps, no_occ6 = diag & kNoOcc6, no_occ8 = diag & kNoOcc8, no_shapes = diag & kNoShapes;
     const fp_params& p = ka.p;
     const fp_batch& b = ka.b;
+    if (rq.provisional && (ka.r.best_traj || ka.epi_flag || ka.has_loop)) {  // the winner is decided behind this launch: plan it without the offers
+        KernelArgs plain = ka;
+        plain.r.best_traj = nullptr; plain.epi_flag = nullptr; plain.has_loop = 0;
+        return plan_lattice(plain, rq);
+    }
     LatticePlan pl;
     // 1. shape
     if (!fused_shape(p, b, &pl.rows, &pl.hp)) return pl;

@@ -31,7 +31,7 @@ def make_params(batch, nd=None, nv=None, nt=None) -> _abi.FpParams:
     every scalar it is built from."""
     lim0 = getattr(batch, "curvature_limits", None)
     key = (nd or batch.nd, nv or batch.nv, nt or batch.nt, batch.check_stride, batch.tick_t, batch.veh_l, batch.veh_w, batch.max_speed, batch.max_accel,
-           None if lim0 is None else tuple(lim0), _t_max(batch))  # (the VALUE points_max is derived from: an in-place edit of the arrays is seen)
+           None if lim0 is None else tuple(lim0), getattr(batch, "w_obstacle", 0.0), _t_max(batch))  # (the VALUE points_max is derived from: an in-place edit of the arrays is seen)
     cached = getattr(batch, "__dict__", {}).get("_fp_cache")
     if cached is not None and cached[0] == key:
         return _abi.FpParams.from_buffer_copy(cached[1])  # a copy: callers may edit their struct
@@ -64,6 +64,7 @@ def _make_params(batch, nd=None, nv=None, nt=None) -> _abi.FpParams:
     if lim is not None:  # optional checks of check_constraints (reference :145-150, commented out there)
         p.curvature_mask = 1
         p.max_curvature, p.max_kappa_d, p.max_kappa_dd = (float(v) for v in lim)
+    p.w_obstacle = float(getattr(batch, "w_obstacle", 0.0))  # optional clearance cost term (a stub in the reference, cost_function.py:9,21-27,43)
     return p
 
 

@@ -73,6 +73,11 @@ class FrenetOptimalPlannerSettings:
         # not in the reference's settings: turns on the curvature / curvature-rate checks that its check_constraints carries
         # commented out (:145-150), with the Vehicle's max_curvature / max_kappa_d / max_kappa_dd (vehicle.py:44-46)
         self.check_curvature = False
+        # not in the reference's settings: the weight of the obstacle-clearance cost term that its CostFunction keeps as a stub
+        # (cost_function.py:9 w_D = 0.1, :21-27 cost_dist_obstacle, :43 cost_obstacle = 0.0).  > 0: FrenetOptimalPlanner.plan() prices
+        # every surviving candidate with (base_sum + w_obstacle * sum exp(-dist)) / N over has_collision's poses and returns the
+        # argmin of that; FOP+, FISS and FISS+ order candidates before they have Cartesian points and raise ValueError
+        self.w_obstacle = 0.0
 
 
 class FissPlannerSettings(FrenetOptimalPlannerSettings):
@@ -181,9 +186,13 @@ class FrenetOptimalPlanner:
         tab = self._obstacle_table(obstacles)
         sp = self.cubic_spline
         curv = (self.vehicle.max_curvature, self.vehicle.max_kappa_d, self.vehicle.max_kappa_dd) if getattr(st, "check_curvature", False) else None
+        w_obs = float(getattr(st, "w_obstacle", 0.0))
+        if w_obs != 0.0 and self.KIND != "FOP":
+            raise ValueError(f"settings.w_obstacle = {w_obs}: the clearance cost term is defined for FrenetOptimalPlanner only "
+                             f"({self.KIND} orders candidates by cost before they have Cartesian points)")
         cache_tables = getattr(self, "cache_tables", True)
         key = (id(sp), id(tab), getattr(tab, "version", 0), cache_tables, st.num_width, st.num_speed, st.num_t, st.min_t, st.max_t, st.tick_t, st.max_road_width, st.lowest_speed,
-               self.vehicle.l, self.vehicle.w, self.vehicle.max_speed, self.vehicle.max_accel, curv)
+               self.vehicle.l, self.vehicle.w, self.vehicle.max_speed, self.vehicle.max_accel, curv, w_obs)
         cache = getattr(self, "_batch_cache", None)
         if cache is None or cache[0] != key:
             sw = self._sampling_width()
@@ -199,7 +208,7 @@ class FrenetOptimalPlanner:
                 obs_pose=pose, obs_dims=dims, final_time_step=fts, veh_l=self.vehicle.l, veh_w=self.vehicle.w,
                 max_speed=self.vehicle.max_speed, max_accel=self.vehicle.max_accel, tick_t=st.tick_t, check_stride=2,
                 samp_min=np.array([[-sw / 2, st.lowest_speed, st.min_t]]), samp_max=np.array([[sw / 2, 0.0, st.max_t]]),
-                samp_res=np.array([[rd, 0.0, rt]]), curvature_limits=curv,
+                samp_res=np.array([[rd, 0.0, rt]]), curvature_limits=curv, w_obstacle=w_obs,
                 obs_poly=None if tab is None or tab.nvert is None else tab.poly[None],
                 obs_nvert=None if tab is None or tab.nvert is None else tab.nvert[None])
             # fp_batch.tables_tag: the library keeps this batch's spline and obstacle tables on the device until the planner builds

@@ -189,5 +189,5 @@ def with_random_shapes(batch: ProblemBatch, seed: int, frac: float = 0.6, max_ve
             dims[sc, j] = 2.0 * np.abs(ring).max(axis=0)
     kw = {k: getattr(batch, k) for k in ("d_samples", "t_samples", "v_samples", "target_speed", "ego", "frame_of", "scene_of", "t_now", "nx", "knots", "coef",
                                           "obs_pose", "final_time_step", "veh_l", "veh_w", "max_speed", "max_accel", "tick_t", "check_stride", "samp_min", "samp_max",
-                                          "samp_res", "curvature_limits")}
+                                          "samp_res", "curvature_limits", "w_obstacle")}
     return ProblemBatch(**kw, obs_dims=dims, obs_poly=poly, obs_nvert=nvert, meta=dict(batch.meta, shapes=seed))

@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define FP_ABI_VERSION 15
+#define FP_ABI_VERSION 16
 
 /* error codes */
 #define FP_OK 0
@@ -111,6 +111,24 @@ typedef struct {
      * yields NaN cost + FP_FLAG_INFEASIBLE for those candidates, as beyond FP_MAX_POINTS. */
     int32_t points_max;
     double max_curvature, max_kappa_d, max_kappa_dd;
+    /* Optional obstacle-clearance cost term (ABI 16).  The reference defines the weight (w_D = 0.1, cost_function.py:9), sketches the
+     * term (cost_dist_obstacle, :21-27: `Xis = np.exp(-dists); return w_D * sum(Xis)`) and keeps its slot in cost_total at zero
+     * (`cost_obstacle = 0.0`, :43), so 0 = off is the reference's behaviour, bit for bit and launch for launch.  > 0: fp_plan_dense and
+     * fp_plan_step price every candidate that SURVIVED the checks (no FP_FLAG_INFEASIBLE bit) as
+     *     cost_final = (base_sum + w_obstacle * clearance) / N,   clearance = sum_i sum_j exp(-dist(i, j)),
+     * base_sum / N being the cost_final without the term: i runs over has_collision's poses (frenet_optimal_planner.py:168-195:
+     * i = 0, check_stride, 2 check_stride, ... < min(M, final_time_step - t_now), the veh_l x veh_w footprint at x[i], y[i], yaw[i]), j over
+     * the obstacle columns with a valid pose at step i + t_now, and dist is the Euclidean distance in metres between the two closed
+     * convex shapes (rectangle against rectangle, or against the column's ring when obs_nvert > 0; 0 when they touch - which a survivor
+     * never does).  Pairs at least 48 m apart are not summed (together below 2e-15 per candidate).  cost_tbl holds the new value for
+     * the survivors and the old one for every other candidate; best_idx / best_cost / best_traj belong to the argmin of the new costs
+     * (last minimum in FOP order on exact ties, :264-268); Stats do not change.  A second kernel behind the lattice pass does it (over
+     * the call's tables, or tables of [B][C] in the ctx's scratch when the caller passed none).
+     * FopPlusPlanner, FissPlanner and FissPlusPlanner order candidates by cost BEFORE a trajectory has Cartesian points
+     * (fop_plus_planner.py:16-41, fiss_planner.py:101-138), so the term has no defined place there yet: result.fopplus, result.audit,
+     * fp_plan_fiss and fp_plan_fiss_step return FP_EINVAL when it is non-zero.  fp_eval_trajs prices arbitrary end states and ignores it.
+     * < 0 or not finite: FP_EINVAL. */
+    double w_obstacle;
 } fp_params;
 
 /* A batch of B independent ego planning problems (layout: DESIGN.md "problem batch"). */
@@ -292,7 +310,8 @@ int fp_ctx_destroy(fp_ctx* ctx);
  * "fiss_stages": timing diagnostic of fp_plan_fiss, 3 (default) = the whole pipeline, 2 = stop after the search walk (no
  * refinement), 1 = stop after the dense lattice pass; with 1 or 2 the outputs of the skipped stages are NOT produced. */
 int fp_ctx_set_option(fp_ctx* ctx, const char* name, int value);
-/* Reads an option back, or one of the read-only counters "lattice_launches" (dense lattice launches of this ctx so far) and
+/* Reads an option back, or one of the read-only counters "clearance_launches" (launches of the clearance rescoring kernel,
+ * fp_params.w_obstacle > 0, of this ctx so far), "lattice_launches" (dense lattice launches of this ctx so far) and
  * "lattice_ordered_launches" (those dispatched in a feedback order or in the order of fp_batch.launch_order) - bench.py reports when an
  * order took effect -, "lattice_launches_2" / "_3" / "_4" (PROCESS-wide: fused lattice launches so far by workgroups per compute unit). */
 int fp_ctx_get_option(fp_ctx* ctx, const char* name, int* value);
