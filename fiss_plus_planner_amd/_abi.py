@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libfrenetgpu.so")
 
-FP_ABI_VERSION = 16
+FP_ABI_VERSION = 17
 FP_FISS, FP_FISS_PLUS = 0, 1
 FP_MEM_HOST, FP_MEM_DEVICE = 0, 1
 FP_MAX_POINTS, FP_MAX_KNOTS, FP_MAX_CAND, FP_MAX_POLY_VERTS = 256, 1024, 16384, 128
@@ -29,7 +29,7 @@ _up = C.POINTER(C.c_uint32)
 
 # every symbol include/frenet_gpu.h declares (tests check the library exports all of them)
 EXPORTED_SYMBOLS = ("fp_abi_version", "fp_build_flags", "fp_build_compiler", "fp_last_error", "fp_device_count", "fp_device_info", "fp_ctx_create", "fp_ctx_destroy", "fp_ctx_set_option", "fp_ctx_get_option", "fp_ctx_join",
-                    "fp_plan_dense", "fp_winner_trajs", "fp_eval_trajs", "fp_plan_fiss", "fp_advance", "fp_plan_step", "fp_plan_fiss_step", "fp_frames_build", "fp_from_state", "fp_materialize_all",
+                    "fp_plan_dense", "fp_winner_trajs", "fp_eval_trajs", "fp_plan_fiss", "fp_advance", "fp_plan_step", "fp_plan_fiss_step", "fp_loop_record", "fp_frames_build", "fp_from_state", "fp_materialize_all",
                     "fp_group_create", "fp_group_destroy", "fp_group_submit", "fp_group_wait")
 
 
@@ -78,6 +78,18 @@ class FpLoopIo(C.Structure):
 
 
 RUNNING, DONE_GOAL, DONE_END_OF_LINE, DONE_NO_SOLUTION, DONE_GOAL_REGION = 0, 1, 2, 3, 4
+
+
+# columns of a loop-log row (fp_loop_log.rows [B][max_rows][FP_LOG_COLS], include/frenet_gpu.h)
+FP_LOG_COLS = 16
+(LOG_TIME_STEP, LOG_X, LOG_Y, LOG_YAW, LOG_VELOCITY, LOG_VELOCITY_Y, LOG_S, LOG_S_DD, LOG_D, LOG_D_DD, LOG_COST, LOG_D_END, LOG_V_END,
+ LOG_T_END, LOG_BEST_IDX, LOG_DONE) = range(FP_LOG_COLS)
+
+
+class FpLoopLog(C.Structure):
+    """The driven-trajectory log of a device-resident loop (fp_loop_record)."""
+    _fields_ = [("max_rows", C.c_int32), ("reserved0", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("rows", "row_stats", "n_rows", "sealed", "stats_sum", "n_running")]
 
 
 class FpCopy(C.Structure):
@@ -143,6 +155,8 @@ def load() -> C.CDLL:
     L.fp_advance.argtypes = [C.c_void_p, C.POINTER(FpParams), C.POINTER(FpBatch), C.c_void_p, C.c_void_p, C.POINTER(FpLoopIo), C.c_int, C.c_void_p]
     L.fp_plan_step.argtypes = [C.c_void_p, C.POINTER(FpParams), C.POINTER(FpBatch), C.POINTER(FpResult), C.POINTER(FpLoopIo), C.c_int, C.c_void_p]
     L.fp_plan_fiss_step.argtypes = [C.c_void_p, C.POINTER(FpParams), C.POINTER(FpBatch), C.POINTER(FpFissOpts), C.POINTER(FpFissIo), C.POINTER(FpLoopIo), C.c_int, C.c_void_p]
+    L.fp_loop_record.argtypes = [C.c_void_p, C.POINTER(FpParams), C.POINTER(FpBatch), C.POINTER(FpLoopIo), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.POINTER(FpLoopLog), C.c_int, C.c_void_p]
     L.fp_frames_build.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     L.fp_from_state.argtypes = [C.c_void_p, C.POINTER(FpBatch), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     L.fp_materialize_all.argtypes = [C.c_void_p, C.POINTER(FpParams), C.POINTER(FpBatch), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int, C.c_void_p]

@@ -191,6 +191,7 @@ struct fp_ctx {
     int lattice_order = 1;
     int lattice_launches = 0, lattice_ordered_launches = 0;  // fp_ctx_get_option counters
     int clearance_launches = 0;    // fp_ctx_get_option("clearance_launches"): launches of the clearance rescoring kernel (fp_params.w_obstacle > 0)
+    int looplog_launches = 0;      // fp_ctx_get_option("looplog_launches"): launches of the loop-log kernel (fp_loop_record)
     OrderSet order_lattice, order_refine;
     DeviceBuf idx_shadow;          // [B] device copy of best_idx for the winner kernel of a dense call (KernelArgs::idx_shadow)
     DeviceBuf epi_flags;           // [B] hand-over flags of the epilogue workgroups appended to a multi-round lattice launch (KernelArgs::epi_flag); zero between launches
@@ -1445,7 +1446,7 @@ int fp_ctx_get_option(fp_ctx* ctx, const char* name, int* value)
     const struct { const char* n; int v; } tab[] = {
         {"lattice_kernel", ctx->lattice_kernel}, {"lattice_split", ctx->lattice_split}, {"lattice_group", ctx->lattice_group}, {"lattice_tail", ctx->lattice_tail}, {"lattice_occupancy", ctx->lattice_occupancy}, {"resident_groups", ctx->resident_groups}, {"zero_copy_in", ctx->zero_copy_in}, {"stage_kernel", ctx->stage_kernel}, {"inline_inputs", ctx->inline_inputs}, {"lattice_order", ctx->lattice_order},
         {"refine_table_kb", ctx->refine_table_kb}, {"fiss_stages", ctx->fiss_stages}, {"fiss_jump", ctx->fiss_jump}, {"validate", ctx->validate}, {"lattice_winner", ctx->lattice_winner}, {"fiss_fused", ctx->fiss_fused}, {"appended_workgroups", ctx->appended_ok ? 1 : 0}, {"handover_failed", ctx->hand_err ? *(volatile int32_t*)ctx->hand_err : 0}, {"overlap", ctx->overlap}, {"overlapped_calls", ctx->overlapped_calls}, {"clearance_launches", ctx->clearance_launches + (ctx->twin ? ctx->twin->clearance_launches : 0)}, {"lattice_launches", ctx->lattice_launches + (ctx->twin ? ctx->twin->lattice_launches : 0)},
-        {"lattice_ordered_launches", ctx->lattice_ordered_launches + (ctx->twin ? ctx->twin->lattice_ordered_launches : 0)},
+        {"looplog_launches", ctx->looplog_launches}, {"lattice_ordered_launches", ctx->lattice_ordered_launches + (ctx->twin ? ctx->twin->lattice_ordered_launches : 0)},
         {"lattice_launches_2", (int)fp::lattice_launches_per_cu(0)}, {"lattice_launches_3", (int)fp::lattice_launches_per_cu(1)}, {"lattice_launches_4", (int)fp::lattice_launches_per_cu(2)}};
     for (const auto& t : tab)
         if (strcmp(name, t.n) == 0) { *value = t.v; return FP_OK; }
@@ -1865,6 +1866,71 @@ int fp_advance(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, cons
     dio.cart_state = hs.out(io->cart_state, B * 3);
     if (dio.cart_state) HIP_TRY(hipMemsetAsync(dio.cart_state, 0xFF, sizeof(double) * B * 3, ctx->stream));  // NaN for egos that do not move
     LAUNCH_TRY(fp::launch_advance(ka, d_idx, d_es, dio, ctx->stream), "advance kernel");
+    return hs.fetch_out();
+}
+
+int fp_loop_record(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, const fp_loop_io* io, const int32_t* best_idx,
+                   const double* end_state, const double* best_cost, const int32_t* stats, const fp_loop_log* log, int mem, void* stream)
+{
+    FP_TRY(common_checks(ctx, params, batch, mem, stream));
+    if ((best_idx == nullptr) == (end_state == nullptr)) return fail(FP_EINVAL, "exactly one of best_idx / end_state must be given");
+    if (!io || !io->ego || !io->t_now || !io->done || !io->cycles) return fail(FP_EINVAL, "fp_loop_io has a NULL mandatory array");
+    if (!io->cart_state) return fail(FP_EINVAL, "fp_loop_record: fp_loop_io.cart_state is mandatory (the rows' x, y, yaw)");
+    if (!best_cost) return fail(FP_EINVAL, "fp_loop_record: best_cost is NULL");
+    if (!log || !log->rows || !log->n_rows || !log->sealed) return fail(FP_EINVAL, "fp_loop_log has a NULL mandatory array (rows / n_rows / sealed)");
+    if (log->max_rows < 0) return fail(FP_EINVAL, "fp_loop_log.max_rows=%d is negative", log->max_rows);
+    if (!stats && (log->row_stats || log->stats_sum)) return fail(FP_EINVAL, "fp_loop_record: stats is NULL but the log asks for row_stats / stats_sum");
+    if (batch->B == 0) return FP_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t B = (size_t)batch->B;
+    fp::LoopLogArgs a;
+    a.B = batch->B; a.nv = params->nv; a.nt = params->nt;
+    if (mem == FP_MEM_DEVICE) {
+        // (a lane stores its row as 16-byte words and moves a Stats row as one)
+        if (((uintptr_t)log->rows | (uintptr_t)stats | (uintptr_t)log->row_stats) & 15u)
+            return fail(FP_EINVAL, "fp_loop_record: rows / stats / row_stats must be 16-byte aligned");
+        a.d_samples = batch->d_samples; a.v_samples = batch->v_samples; a.t_samples = batch->t_samples;
+        a.io = *io; a.best_idx = best_idx; a.end_state = end_state; a.best_cost = best_cost; a.stats = stats; a.log = *log;
+        if (log->n_running) HIP_TRY(hipMemsetAsync(log->n_running, 0, sizeof(int32_t), (hipStream_t)stream));
+        LAUNCH_TRY(fp::launch_loop_record(a, (hipStream_t)stream), "loop-log kernel");
+        ++ctx->looplog_launches;
+        return FP_OK;
+    }
+    // host arrays: only what the kernel reads travels (the three sample arrays of the batch, the loop state, the step's results, the log)
+    const size_t R = (size_t)log->max_rows;
+    HostStage hs(ctx);
+    FP_TRY(hs.reserve(HostStage::need<double>(params->nd) + HostStage::need<double>(params->nt) + HostStage::need<double>(B * params->nv) +
+                      HostStage::need<double>(B * 6) + 6 * HostStage::need<int32_t>(B) + 2 * HostStage::need<double>(B * 3) + HostStage::need<double>(B) +
+                      HostStage::need<int32_t>(B * 4) + HostStage::need<double>(B * R * FP_LOG_COLS) + HostStage::need<int32_t>(B * R * 4) +
+                      HostStage::need<int64_t>(B * 4) + HostStage::need<int32_t>(1)));
+    FP_TRY(hs.in(batch->d_samples, (size_t)params->nd, &a.d_samples));
+    FP_TRY(hs.in(batch->v_samples, B * params->nv, &a.v_samples));
+    FP_TRY(hs.in(batch->t_samples, (size_t)params->nt, &a.t_samples));
+    fp_loop_io dio = *io;
+    fp_loop_log dlg = *log;
+    const double* c_ego = nullptr; const double* c_cart = nullptr; const int32_t* c_t = nullptr; const int32_t* c_done = nullptr; const int32_t* c_cyc = nullptr;
+    FP_TRY(hs.in((const double*)io->ego, B * 6, &c_ego));
+    FP_TRY(hs.in((const double*)io->cart_state, B * 3, &c_cart));
+    FP_TRY(hs.in((const int32_t*)io->t_now, B, &c_t));
+    FP_TRY(hs.in((const int32_t*)io->done, B, &c_done));
+    FP_TRY(hs.in((const int32_t*)io->cycles, B, &c_cyc));
+    dio.ego = const_cast<double*>(c_ego); dio.cart_state = const_cast<double*>(c_cart);
+    dio.t_now = const_cast<int32_t*>(c_t); dio.done = const_cast<int32_t*>(c_done); dio.cycles = const_cast<int32_t*>(c_cyc);
+    if (best_idx) FP_TRY(hs.in(best_idx, B, &a.best_idx));
+    if (end_state) FP_TRY(hs.in(end_state, B * 3, &a.end_state));
+    FP_TRY(hs.in(best_cost, B, &a.best_cost));
+    if (stats) FP_TRY(hs.in(stats, B * 4, &a.stats));
+    FP_TRY(hs.in_mut(log->rows, B * R * FP_LOG_COLS, &dlg.rows));
+    if (log->row_stats) FP_TRY(hs.in_mut(log->row_stats, B * R * 4, &dlg.row_stats));
+    FP_TRY(hs.in_mut(log->n_rows, B, &dlg.n_rows));
+    FP_TRY(hs.in_mut(log->sealed, B, &dlg.sealed));
+    if (log->stats_sum) FP_TRY(hs.in_mut(log->stats_sum, B * 4, &dlg.stats_sum));
+    FP_TRY(hs.flush_in());
+    dlg.n_running = hs.out(log->n_running, 1);
+    if (dlg.n_running) HIP_TRY(hipMemsetAsync(dlg.n_running, 0, sizeof(int32_t), ctx->stream));
+    a.io = dio; a.log = dlg;
+    LAUNCH_TRY(fp::launch_loop_record(a, ctx->stream), "loop-log kernel");
+    ++ctx->looplog_launches;
     return hs.fetch_out();
 }
 

@@ -171,6 +171,22 @@ hipError_t launch_frames_build(int F, int NX, const int32_t* n, const double* po
 hipError_t launch_from_state(const fp_batch& bt, const double* states, double* ego, hipStream_t stream);
 // Closed-loop bookkeeping between two plan cycles (one lane per ego).
 hipError_t launch_advance(const KernelArgs& ka, const int32_t* best_idx, const double* end_state, const fp_loop_io& io, hipStream_t stream);
+// The driven-trajectory log of a resident loop (frenet_looplog.hip, fp_loop_record): behind a step, one lane per ego copies the ego's
+// new state into its next free row.  Device addresses; exactly one of best_idx / end_state set; stats may be nullptr when the log
+// asks for none.  log.n_running (optional) must be zero on the stream before the launch.
+struct LoopLogArgs {
+    int B = 0, nv = 1, nt = 1;
+    const double* d_samples = nullptr;
+    const double* v_samples = nullptr;
+    const double* t_samples = nullptr;
+    fp_loop_io io = {};
+    const int32_t* best_idx = nullptr;
+    const double* end_state = nullptr;
+    const double* best_cost = nullptr;
+    const int32_t* stats = nullptr;
+    fp_loop_log log = {};
+};
+hipError_t launch_loop_record(const LoopLogArgs& a, hipStream_t stream);
 // Series of EVERY lattice candidate: ka.r.best_traj [B*C][16][traj_stride], ka.r.best_flags [B*C] (N, M, truncated).
 hipError_t launch_materialize_all(const KernelArgs& ka, hipStream_t stream);
 hipError_t launch_eval_trajs(const KernelArgs& ka, int K, const double* end_states, double* cost, uint32_t* flags, double* traj,

@@ -3,7 +3,8 @@
 PyTorch is plumbing here (device allocations + the stream handle); every array crosses the C ABI as a raw
 device address.  `DeviceBatch` uploads a ProblemBatch once; `ClosedLoopRunner` enqueues
 [plan -> advance] x cycles on one stream (reference loop: planners/benchmark/planning.py:120-162) and only
-reads back at the end (or per cycle, when a trace is requested).
+reads back at the end (or per cycle, when a trace is requested).  With record=True the driven trajectory of every ego - what the
+reference's loop returns as state_list - is written on the device by fp_loop_record behind every step and read back once.
 """
 from __future__ import annotations
 
@@ -13,10 +14,13 @@ import numpy as np
 
 from . import _abi
 from .batch import ProblemBatch
+from .closed_loop import LoopLog
 from .engine import FrenetEngine, device_batch, launch_order_hint, make_params
 
 _NAMES = ("d_samples", "t_samples", "v_samples", "target_speed", "ego", "frame_of", "scene_of", "t_now", "nx", "knots", "coef",
           "obs_pose", "obs_dims", "final_time_step")
+
+LOG_POLL_CYCLES = 16  # run(record=True) reads the log's 4-byte count of running egos this often and stops enqueueing at 0
 
 
 class DeviceBatch:
@@ -115,17 +119,65 @@ class ClosedLoopRunner:
             _abi.check(lib.fp_advance(ctx, C.byref(self.db.params), C.byref(self.fb), None, self.end_state.data_ptr(), C.byref(self.io),
                                       _abi.FP_MEM_DEVICE, stream or None))
 
-    def run_graph(self, max_cycles: int):
+    def log_reset(self, max_rows: int, poll: bool = True):
+        """A fresh device log for the cycles that follow (fp_loop_log): max_rows rows per ego beyond the cycles driven so far, egos that are
+        already finished sealed.  poll=False: no count of running egos (one memset less per record call)."""
+        torch = self.db.torch
+        B, dev = self.db.B, self.db.dev
+        self.log_row0 = self.cycles.cpu().numpy().copy()
+        rows = int(max_rows) + (int(self.log_row0.max()) if B else 0)
+        self.log_rows = torch.full((B, rows, _abi.FP_LOG_COLS), float("nan"), dtype=torch.float64, device=dev)
+        self.log_row_stats = torch.zeros((B, rows, 4), dtype=torch.int32, device=dev)
+        self.log_n_rows = self.cycles.clone()
+        self.log_sealed = (self.done != 0).to(torch.int32)
+        self.log_stats_sum = torch.zeros((B, 4), dtype=torch.int64, device=dev)
+        self.log_running = torch.full((1,), -1, dtype=torch.int32, device=dev)
+        lg = _abi.FpLoopLog()
+        lg.max_rows = rows
+        lg.rows, lg.row_stats, lg.n_rows = self.log_rows.data_ptr(), self.log_row_stats.data_ptr(), self.log_n_rows.data_ptr()
+        lg.sealed, lg.stats_sum = self.log_sealed.data_ptr(), self.log_stats_sum.data_ptr()
+        lg.n_running = self.log_running.data_ptr() if poll else None
+        self.flog = lg
+
+    def record(self, stream: int = 0):
+        """fp_loop_record behind the step just enqueued on `stream`: every running ego's new state goes to its next log row."""
+        import ctypes as C
+
+        fop = self.planner == "FOP"
+        _abi.check(self.eng._lib.fp_loop_record(self.eng._ctx, C.byref(self.db.params), C.byref(self.fb), C.byref(self.io),
+                                                self.best_idx.data_ptr() if fop else None, None if fop else self.end_state.data_ptr(),
+                                                self.best_cost.data_ptr(), self.stats.data_ptr(), C.byref(self.flog), _abi.FP_MEM_DEVICE, stream or None))
+
+    def log_fetch(self) -> LoopLog:
+        """The log as numpy arrays (one read-back; synchronises)."""
+        return LoopLog(rows=self.log_rows.cpu().numpy(), n_rows=self.log_n_rows.cpu().numpy(), row_stats=self.log_row_stats.cpu().numpy(),
+                       stats_sum=self.log_stats_sum.cpu().numpy(), sealed=self.log_sealed.cpu().numpy(), row0=self.log_row0)
+
+    def _result(self, rows, record):
+        out = SimpleNamespace(done=self.done.cpu().numpy(), cycles=self.cycles.cpu().numpy(), ego=self.db.t["ego"].cpu().numpy(),
+                              t_now=self.db.t["t_now"].cpu().numpy(), cart=self.cart.cpu().numpy(), trace=rows)
+        if record:
+            out.log = self.log_fetch()
+        return out
+
+    def run_graph(self, max_cycles: int, record: bool = False):
         """The same loop as run(), but one [plan -> advance] cycle is captured into a HIP graph once and replayed: the cycle is
         launch-bound for small batches (2-5 short kernels), and every pointer it touches is fixed (state lives in HBM and is
-        updated in place), so a replay needs no host work beyond hipGraphLaunch."""
+        updated in place), so a replay needs no host work beyond hipGraphLaunch.
+        record: fp_loop_record is captured behind the step - the log's row index lives on the device, so every replay appends."""
         torch = self.db.torch
+        if record:
+            self.log_reset(max_cycles, poll=False)  # (nobody polls between replays)
         self.step(torch.cuda.current_stream(self.db.dev).cuda_stream)  # warm-up outside capture: first-use allocations, LDS attributes
+        if record:
+            self.record(torch.cuda.current_stream(self.db.dev).cuda_stream)
         torch.cuda.synchronize(self.db.dev)
         side = torch.cuda.Stream(self.db.dev)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph, stream=side):
             self.step(side.cuda_stream)
+            if record:
+                self.record(side.cuda_stream)
         torch.cuda.synchronize(self.db.dev)
         import time
         t0 = time.perf_counter()
@@ -133,22 +185,29 @@ class ClosedLoopRunner:
             graph.replay()
         torch.cuda.synchronize(self.db.dev)
         self.replay_seconds = time.perf_counter() - t0  # capture / instantiation excluded
-        return SimpleNamespace(done=self.done.cpu().numpy(), cycles=self.cycles.cpu().numpy(), ego=self.db.t["ego"].cpu().numpy(),
-                               t_now=self.db.t["t_now"].cpu().numpy(), cart=self.cart.cpu().numpy(), trace=[])
+        return self._result([], record)
 
-    def run(self, max_cycles: int, trace: bool = False):
+    def run(self, max_cycles: int, trace: bool = False, record: bool = False):
+        """trace: the host reads every cycle back (five blocking copies per cycle).  record: the device keeps the driven trajectory
+        (out.log, a closed_loop.LoopLog; closed_loop.result_from_log makes a ClosedLoopResult of one ego's rows) and the loop stops
+        enqueueing once no ego is running - the count is read every LOG_POLL_CYCLES cycles."""
         torch = self.db.torch
         stream = torch.cuda.current_stream(self.db.dev).cuda_stream
         rows = []
-        for _ in range(max_cycles):
+        if record:
+            self.log_reset(max_cycles)
+        for i in range(max_cycles):
             if trace:
                 start = self.db.t["ego"].cpu().numpy().copy()
             self.step(stream)
+            if record:
+                self.record(stream)
+                if not trace and (i + 1) % LOG_POLL_CYCLES == 0 and int(self.log_running.item()) == 0:
+                    break
             if trace:
                 rows.append(SimpleNamespace(start=start, cost=self.best_cost.cpu().numpy().copy(), stats=self.stats.cpu().numpy().copy(),
                                             done=self.done.cpu().numpy().copy(), cart=self.cart.cpu().numpy().copy()))
                 if (rows[-1].done != 0).all():
                     break
         torch.cuda.synchronize(self.db.dev)
-        return SimpleNamespace(done=self.done.cpu().numpy(), cycles=self.cycles.cpu().numpy(), ego=self.db.t["ego"].cpu().numpy(),
-                               t_now=self.db.t["t_now"].cpu().numpy(), cart=self.cart.cpu().numpy(), trace=rows)
+        return self._result(rows, record)

@@ -264,10 +264,12 @@ class ShardedEngine:
             sb, kind, None if prev is None else prev[lo:hi], w_heuristic, max_refine_iters, decaying_factor, winner, trace, traj_stride,
             traj_sparse, out=view))
 
-    def _closed_loop_host(self, batch: ProblemBatch, goal_xy: np.ndarray, planner: str = "FOP", max_cycles: int = 100):
+    def _closed_loop_host(self, batch: ProblemBatch, goal_xy: np.ndarray, planner: str = "FOP", max_cycles: int = 100, record: bool = False):
         """The closed loop of planners/benchmark/planning.py:120-162 for every ego, device-resident: every shard uploads its egos
         once, steps [plan -> advance] max_cycles times on its own GPU without a host round trip (device_batch.ClosedLoopRunner) and
-        only the final states come back, merged in ego order."""
+        only the final states come back, merged in ego order.  record: every shard's runner keeps the driven trajectory of its egos
+        in a device log of its own (fp_loop_record behind every step); out.log is the logs merged in ego order (closed_loop.LoopLog)."""
+        from .closed_loop import LoopLog
         from .device_batch import ClosedLoopRunner, DeviceBatch
 
         goal = np.ascontiguousarray(goal_xy, dtype=np.float64).reshape(batch.B, 2)
@@ -282,11 +284,18 @@ class ShardedEngine:
             # device overlap their cycles - a cycle of a few hundred running egos is one round of workgroups, as long as its slowest
             # ego, and leaves most of the chip idle for the other shard
             with torch.cuda.stream(torch.cuda.Stream(torch.device("cuda", eng.device))):
-                res = ClosedLoopRunner(eng, DeviceBatch(sb, eng.device), goal[lo:hi], planner).run(max_cycles)
+                res = ClosedLoopRunner(eng, DeviceBatch(sb, eng.device), goal[lo:hi], planner).run(max_cycles, record=record)
             for k in ("done", "cycles", "ego", "t_now", "cart"):
                 getattr(view, k)[...] = getattr(res, k)
+            if record:
+                logs[lo] = res.log
 
-        return self._run(batch, out, call)
+        logs = {}
+        out = self._run(batch, out, call)
+        if record:  # (fresh runners: every shard's log has max_cycles rows per ego, starting at row 0)
+            parts = [logs[lo] for lo in sorted(logs)]
+            out.log = LoopLog(**{k: np.concatenate([getattr(p, k) for p in parts]) for k in ("rows", "n_rows", "row_stats", "stats_sum", "sealed", "row0")})
+        return out
 
     # ------------------------------------------------------------------ entry points: host batch (staged per call) or resident shards
     def plan_dense(self, batch, *args, **kw):
@@ -374,11 +383,15 @@ class ShardedEngine:
         self._round(sdb, sdb.round_calls(("fiss", plus, R, float(w_heuristic), float(decaying_factor), bool(winner)), build), sync)
         return sdb.host
 
-    def _closed_loop_resident(self, sdb: ShardedDeviceBatch, goal_xy: np.ndarray, planner: str = "FOP", max_cycles: int = 100):
+    def _closed_loop_resident(self, sdb: ShardedDeviceBatch, goal_xy: np.ndarray, planner: str = "FOP", max_cycles: int = 100, record: bool = False):
         """The device-resident closed loop (planning.py:120-162) on shards that are ALREADY resident: no upload, the resident start
         states are advanced in place (sdb.reset_state(batch) rewinds them).  One fp_group round per cycle: fp_plan_step for FOP,
-        fp_plan_fiss + fp_advance for FISS / FISS+ - the host thread posts max_cycles rounds, the workers enqueue them."""
+        fp_plan_fiss + fp_advance for FISS / FISS+ - the host thread posts max_cycles rounds, the workers enqueue them.
+        record: not here - fp_shard_call has no slot for fp_loop_record behind the step; use a host batch (closed_loop(batch, ...))."""
         from .device_batch import ClosedLoopRunner
+
+        if record:
+            raise NotImplementedError("closed_loop(record=True) on resident shards: fp_shard_call cannot carry fp_loop_record - pass the host batch")
 
         torch = sdb.torch
         goal = np.ascontiguousarray(goal_xy, dtype=np.float64).reshape(sdb.B, 2)

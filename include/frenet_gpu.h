@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define FP_ABI_VERSION 16
+#define FP_ABI_VERSION 17
 
 /* error codes */
 #define FP_OK 0
@@ -311,7 +311,7 @@ int fp_ctx_destroy(fp_ctx* ctx);
  * refinement), 1 = stop after the dense lattice pass; with 1 or 2 the outputs of the skipped stages are NOT produced. */
 int fp_ctx_set_option(fp_ctx* ctx, const char* name, int value);
 /* Reads an option back, or one of the read-only counters "clearance_launches" (launches of the clearance rescoring kernel,
- * fp_params.w_obstacle > 0, of this ctx so far), "lattice_launches" (dense lattice launches of this ctx so far) and
+ * fp_params.w_obstacle > 0, of this ctx so far), "looplog_launches" (launches of fp_loop_record's kernel), "lattice_launches" (dense lattice launches of this ctx so far) and
  * "lattice_ordered_launches" (those dispatched in a feedback order or in the order of fp_batch.launch_order) - bench.py reports when an
  * order took effect -, "lattice_launches_2" / "_3" / "_4" (PROCESS-wide: fused lattice launches so far by workgroups per compute unit). */
 int fp_ctx_get_option(fp_ctx* ctx, const char* name, int* value);
@@ -467,6 +467,47 @@ int fp_plan_step(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, co
  * the pipeline; otherwise the advance kernel follows.  Identical to fp_plan_fiss + fp_advance in every output. */
 int fp_plan_fiss_step(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, const fp_fiss_opts* opts, const fp_fiss_io* io,
                       const fp_loop_io* loop, int mem, void* stream);
+
+/* ---- the driven trajectory of a device-resident loop (ABI 17) ---------------------------------------------------
+ * The reference's loop returns `state_list` - one row per driven cycle: time step, position, orientation, velocity, velocity_y
+ * (planners/benchmark/planning.py:135-148) - beside the summed Stats and goal_reached (:129, :150-161).  fp_loop_record keeps that
+ * record ON THE DEVICE: enqueue it directly behind a step (fp_plan_step, fp_plan_fiss_step, or a plan call + fp_advance) on the same
+ * stream, with the step's own fp_loop_io and result arrays; one small kernel, one lane per ego, copies the ego's new state into the
+ * ego's next free row.  For every ego with sealed[b] == 0:
+ *   - stats_sum[b] += stats[b] (the loop's `stats += planner.stats`, :129 - also for the plan that found no solution);
+ *   - io->cycles[b] > n_rows[b]: the ego moved in this step.  Row n_rows[b] is written when it is below max_rows (the columns:
+ *     FP_LOG_* below; row_stats gets the stats row) and n_rows[b] = io->cycles[b];
+ *   - io->done[b] != FP_RUNNING: sealed[b] = 1.  An ego that ends with FP_DONE_NO_SOLUTION adds Stats but no row (the reference
+ *     breaks before state_list.append, :131-133).
+ * Whoever resets a log (n_rows = cycles so far, usually 0) seals the egos that are already finished: their stats rows are stale.
+ * n_running: an exact count of the egos with done == FP_RUNNING after the step (the call zeroes the word on the stream first) - what a
+ * host loop polls, now and then, to stop enqueueing.
+ * The row index lives on the device and every pointer is fixed, so a captured [step, record] pair replays for any number of cycles:
+ * no allocation, no synchronisation (FP_MEM_DEVICE).  FP_MEM_HOST stages every array through the ctx and waits, like fp_advance.
+ * Exactly one of best_idx / end_state is non-NULL, as for fp_advance (end_state: FP_LOG_BEST_IDX = -1; best_idx: the end state is
+ * decoded from the index as fp_advance decodes it).  io->cart_state, best_cost, log->rows / n_rows / sealed are mandatory; stats is
+ * mandatory when row_stats or stats_sum is set; rows must be 16-byte aligned (a lane stores its 128-byte row as eight 16-byte words).
+ * Violations: FP_EINVAL.  The rows hold copies: every value is bit for bit what the step left in its arrays. */
+#define FP_LOG_COLS 16
+enum { FP_LOG_TIME_STEP = 0, FP_LOG_X, FP_LOG_Y, FP_LOG_YAW, FP_LOG_VELOCITY /* s_d */, FP_LOG_VELOCITY_Y /* d_d */,
+       FP_LOG_S, FP_LOG_S_DD, FP_LOG_D, FP_LOG_D_DD, FP_LOG_COST, FP_LOG_D_END, FP_LOG_V_END, FP_LOG_T_END,
+       FP_LOG_BEST_IDX /* flat FOP index, -1 when the trajectory is not a lattice sample */, FP_LOG_DONE /* FP_RUNNING / FP_DONE_* after the cycle */ };
+
+typedef struct {
+    int32_t max_rows;     /* rows per ego the arrays below hold */
+    int32_t reserved0;
+    double*  rows;        /* [B][max_rows][FP_LOG_COLS] */
+    int32_t* row_stats;   /* NULL or [B][max_rows][4]: Stats of the plan() that produced the row */
+    int32_t* n_rows;      /* [B] in/out: cycles recorded so far (can exceed max_rows: such rows are counted, not written) */
+    int32_t* sealed;      /* [B] in/out: 0 = still recording; set when the ego is seen finished */
+    int64_t* stats_sum;   /* NULL or [B][4] in/out: the loop's `stats += planner.stats` (planning.py:129), incl. the plan that found no solution */
+    int32_t* n_running;   /* NULL or [1] out: egos with done == FP_RUNNING after this step */
+} fp_loop_log;
+
+/* Also read-only in fp_ctx_get_option: "looplog_launches" = launches of the record kernel of this ctx so far (a loop that does not ask
+ * for a log pays nothing: 0). */
+int fp_loop_record(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, const fp_loop_io* io, const int32_t* best_idx,
+                   const double* end_state, const double* best_cost, const int32_t* stats, const fp_loop_log* log, int mem, void* stream);
 
 /* ---- several devices from one host thread ----------------------------------------------------------------------
  * The path shards over independent egos, one shard per GPU, no collective (planning.py:120-162 plans its scenarios one after the
