@@ -192,6 +192,7 @@ struct fp_ctx {
     int lattice_launches = 0, lattice_ordered_launches = 0;  // fp_ctx_get_option counters
     int clearance_launches = 0;    // fp_ctx_get_option("clearance_launches"): launches of the clearance rescoring kernel (fp_params.w_obstacle > 0)
     int looplog_launches = 0;      // fp_ctx_get_option("looplog_launches"): launches of the loop-log kernel (fp_loop_record)
+    int rank_launches = 0;         // fp_ctx_get_option("rank_launches"): launches of the ranking kernel (fp_rank_feasible)
     OrderSet order_lattice, order_refine;
     DeviceBuf idx_shadow;          // [B] device copy of best_idx for the winner kernel of a dense call (KernelArgs::idx_shadow)
     DeviceBuf epi_flags;           // [B] hand-over flags of the epilogue workgroups appended to a multi-round lattice launch (KernelArgs::epi_flag); zero between launches
@@ -1446,7 +1447,7 @@ int fp_ctx_get_option(fp_ctx* ctx, const char* name, int* value)
     const struct { const char* n; int v; } tab[] = {
         {"lattice_kernel", ctx->lattice_kernel}, {"lattice_split", ctx->lattice_split}, {"lattice_group", ctx->lattice_group}, {"lattice_tail", ctx->lattice_tail}, {"lattice_occupancy", ctx->lattice_occupancy}, {"resident_groups", ctx->resident_groups}, {"zero_copy_in", ctx->zero_copy_in}, {"stage_kernel", ctx->stage_kernel}, {"inline_inputs", ctx->inline_inputs}, {"lattice_order", ctx->lattice_order},
         {"refine_table_kb", ctx->refine_table_kb}, {"fiss_stages", ctx->fiss_stages}, {"fiss_jump", ctx->fiss_jump}, {"validate", ctx->validate}, {"lattice_winner", ctx->lattice_winner}, {"fiss_fused", ctx->fiss_fused}, {"appended_workgroups", ctx->appended_ok ? 1 : 0}, {"handover_failed", ctx->hand_err ? *(volatile int32_t*)ctx->hand_err : 0}, {"overlap", ctx->overlap}, {"overlapped_calls", ctx->overlapped_calls}, {"clearance_launches", ctx->clearance_launches + (ctx->twin ? ctx->twin->clearance_launches : 0)}, {"lattice_launches", ctx->lattice_launches + (ctx->twin ? ctx->twin->lattice_launches : 0)},
-        {"looplog_launches", ctx->looplog_launches}, {"lattice_ordered_launches", ctx->lattice_ordered_launches + (ctx->twin ? ctx->twin->lattice_ordered_launches : 0)},
+        {"looplog_launches", ctx->looplog_launches}, {"rank_launches", ctx->rank_launches}, {"lattice_ordered_launches", ctx->lattice_ordered_launches + (ctx->twin ? ctx->twin->lattice_ordered_launches : 0)},
         {"lattice_launches_2", (int)fp::lattice_launches_per_cu(0)}, {"lattice_launches_3", (int)fp::lattice_launches_per_cu(1)}, {"lattice_launches_4", (int)fp::lattice_launches_per_cu(2)}};
     for (const auto& t : tab)
         if (strcmp(name, t.n) == 0) { *value = t.v; return FP_OK; }
@@ -1596,6 +1597,40 @@ int fp_winner_trajs(fp_ctx* ctx, const fp_params* params, const fp_batch* batch,
     ka.r.best_traj = hs.out(best_traj, traj_doubles);
     if (traj_sparse) HIP_TRY(hipMemcpyAsync(ka.r.best_traj, best_traj, traj_doubles * sizeof(double), hipMemcpyDefault, ctx->stream));
     LAUNCH_TRY(fp::launch_winner_traj(ka, nullptr, ctx->stream), "winner epilogue");
+    return hs.fetch_out();
+}
+
+int fp_rank_feasible(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, const double* cost_tbl, const uint32_t* flag_tbl,
+                     int32_t K, int32_t* rank_idx, double* rank_cost, int32_t* n_feasible, int mem, void* stream)
+{
+    FP_TRY(common_checks(ctx, params, batch, mem, stream));
+    if (!cost_tbl || !flag_tbl || !rank_idx || !rank_cost) return fail(FP_EINVAL, "fp_rank_feasible: cost_tbl/flag_tbl/rank_idx/rank_cost must not be NULL");
+    if (K < 1 || K > FP_MAX_RANK) return fail(FP_EINVAL, "fp_rank_feasible: K=%d outside 1..FP_MAX_RANK", K);
+    if (batch->B == 0) return FP_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t B = (size_t)batch->B, C = (size_t)params->nd * params->nv * params->nt;
+    fp::RankArgs a;
+    a.B = batch->B; a.C = (int)C; a.K = K;
+    if (mem == FP_MEM_DEVICE) {
+        a.cost_tbl = cost_tbl; a.flag_tbl = flag_tbl; a.skip = batch->skip; a.perm = batch->launch_order;
+        a.rank_idx = rank_idx; a.rank_cost = rank_cost; a.n_feasible = n_feasible;
+        LAUNCH_TRY(fp::launch_rank_feasible(a, (hipStream_t)stream), "ranking kernel");
+        ++ctx->rank_launches;
+        return FP_OK;
+    }
+    // host arrays: only what the kernel reads travels (the two tables and skip)
+    HostStage hs(ctx);
+    FP_TRY(hs.reserve(HostStage::need<double>(B * C) + HostStage::need<uint32_t>(B * C) + 2 * HostStage::need<int32_t>(B) +
+                      HostStage::need<int32_t>(B * K) + HostStage::need<double>(B * K)));
+    FP_TRY(hs.in(cost_tbl, B * C, &a.cost_tbl));
+    FP_TRY(hs.in(flag_tbl, B * C, &a.flag_tbl));
+    if (batch->skip) FP_TRY(hs.in(batch->skip, B, &a.skip));
+    FP_TRY(hs.flush_in());
+    a.rank_idx = hs.out(rank_idx, B * K);
+    a.rank_cost = hs.out(rank_cost, B * K);
+    a.n_feasible = hs.out(n_feasible, B);
+    LAUNCH_TRY(fp::launch_rank_feasible(a, ctx->stream), "ranking kernel");
+    ++ctx->rank_launches;
     return hs.fetch_out();
 }
 

@@ -187,6 +187,19 @@ struct LoopLogArgs {
     fp_loop_log log = {};
 };
 hipError_t launch_loop_record(const LoopLogArgs& a, hipStream_t stream);
+// The K cheapest survivors of every ego from the dense tables (frenet_rank.hip, fp_rank_feasible): one workgroup per ego, in the order
+// of perm (optional).  Device addresses; rank_idx / rank_cost are [K][B], n_feasible (optional) [B].
+struct RankArgs {
+    int B = 0, C = 0, K = 0;
+    const double* cost_tbl = nullptr;
+    const uint32_t* flag_tbl = nullptr;
+    const int32_t* skip = nullptr;
+    const int32_t* perm = nullptr;
+    int32_t* rank_idx = nullptr;
+    double* rank_cost = nullptr;
+    int32_t* n_feasible = nullptr;
+};
+hipError_t launch_rank_feasible(const RankArgs& a, hipStream_t stream);
 // Series of EVERY lattice candidate: ka.r.best_traj [B*C][16][traj_stride], ka.r.best_flags [B*C] (N, M, truncated).
 hipError_t launch_materialize_all(const KernelArgs& ka, hipStream_t stream);
 hipError_t launch_eval_trajs(const KernelArgs& ka, int K, const double* end_states, double* cost, uint32_t* flags, double* traj,

@@ -206,15 +206,33 @@ class FrenetEngine:
             best_traj=(np.full((B, 16, traj_stride), np.nan) if traj_sparse else np.empty((B, 16, traj_stride))) if winner else None)
 
     def plan_dense(self, batch: ProblemBatch, tables: bool = True, winner: bool = False, traj_stride: int = TRAJ_STRIDE, traj_sparse: bool = False,
-                   out: SimpleNamespace | None = None, audit: bool = False):
+                   out: SimpleNamespace | None = None, audit: bool = False, top_k: int = 0):
         """FrenetOptimalPlanner.plan() for every ego of the batch (reference frenet_optimal_planner.py:247-270).
 
         Returns best_idx [B] (flat (i_d*nt+i_T)*nv+i_v, -1 = none), best_cost [B], stats [B,4] and, with
         tables=True, cost [B,C] and flags [B,C]; with winner=True also best_flags [B] and best_traj [B,16,128]
         (the argmin's full series, written by the lattice kernel itself).  audit=True: also `audit` [B] (FP_AUDIT_* bits: another
         feasible candidate within 1e-9 of the winner's cost - settled by point-by-point sums -, a collision verdict within 1e-9 m of
-        contact; include/frenet_gpu.h).
+        contact; include/frenet_gpu.h).  top_k > 0: also rank_idx [top_k, B], rank_cost [top_k, B] and n_feasible [B], the top_k
+        cheapest survivors of every ego ranked on the device (rank_feasible); the tables are computed for it whether asked for or not
+        (`cost` / `flags` are returned only with tables=True).
         """
+        if top_k:
+            if not 1 <= int(top_k) <= _abi.FP_MAX_RANK:
+                raise ValueError(f"top_k={top_k}: 0 (off) or 1 .. FP_MAX_RANK ({_abi.FP_MAX_RANK})")
+            want_tables = tables
+            if out is not None and not tables:  # the caller's arrays hold no tables: the call brings its own
+                out.cost, out.flags = np.empty((batch.B, batch.C)), np.empty((batch.B, batch.C), dtype=np.uint32)
+                out.__dict__.pop("_res", None)
+            out = self.plan_dense(batch, True, winner, traj_stride, traj_sparse, out, audit)
+            if batch.B:
+                out.rank_idx, out.rank_cost, out.n_feasible = self.rank_feasible(batch, out.cost, out.flags, int(top_k))
+            else:
+                out.rank_idx, out.rank_cost, out.n_feasible = np.empty((int(top_k), 0), dtype=np.int32), np.empty((int(top_k), 0)), np.empty(0, dtype=np.int32)
+            if not want_tables:
+                out.cost = out.flags = None
+                out.__dict__.pop("_res", None)
+            return out
         B, Cn = batch.B, batch.C
         if out is None:  # (out: arrays of dense_outputs' shapes, e.g. contiguous slices of a bigger batch's outputs)
             out = self.dense_outputs(B, Cn, tables, winner, traj_stride, traj_sparse, audit)
@@ -243,6 +261,30 @@ class FrenetEngine:
         p, fb = host_structs(batch)
         _abi.check(self._lib.fp_plan_dense(self._ctx, C.byref(p), C.byref(fb), C.byref(res), _abi.FP_MEM_HOST, None))
         return out
+
+    def rank_feasible(self, batch: ProblemBatch, cost: np.ndarray, flags: np.ndarray, k: int):
+        """The k cheapest survivors of every ego from plan_dense's tables (fp_rank_feasible): cost [B,C], flags [B,C] ->
+        rank_idx [k,B] (flat FOP index, -1 past the last survivor), rank_cost [k,B] (the table's entry, NaN where -1), n_feasible [B]
+        (all survivors of the ego).  Ascending cost, the higher index first among equal costs: row 0 is plan_dense's best_idx /
+        best_cost, and every row is a best_idx argument for winner_trajs."""
+        B, Cn, k = batch.B, batch.C, int(k)
+        cost = np.ascontiguousarray(cost, dtype=np.float64)
+        flags = np.ascontiguousarray(flags, dtype=np.uint32)
+        if cost.shape != (B, Cn) or flags.shape != (B, Cn):
+            raise ValueError(f"rank_feasible: cost / flags must be [B={B}, C={Cn}] tables, got {cost.shape} / {flags.shape}")
+        rank_idx = np.empty((max(k, 0), B), dtype=np.int32); rank_cost = np.empty((max(k, 0), B)); n_feasible = np.empty(B, dtype=np.int32)
+        p, fb = host_structs(batch)
+        # (B == 0 still crosses the ABI: the argument checks are the library's)
+        _abi.check(self._lib.fp_rank_feasible(self._ctx, C.byref(p), C.byref(fb), _ptr(cost), _ptr(flags), k, _ptr(rank_idx), _ptr(rank_cost),
+                                              _ptr(n_feasible), _abi.FP_MEM_HOST, None))
+        return rank_idx, rank_cost, n_feasible
+
+    def rank_feasible_device(self, params: _abi.FpParams, fb: _abi.FpBatch, cost_tbl: int, flag_tbl: int, k: int, rank_idx: int, rank_cost: int,
+                             n_feasible: int = 0, stream: int = 0):
+        """Enqueue the ranking behind a dense call (device addresses): rank_idx / rank_cost [k][B], n_feasible [B] or 0.
+        rank_idx + 4 * j * B is the best_idx argument of winner_trajs_device / fp_advance for the j-th alternatives."""
+        _abi.check(self._lib.fp_rank_feasible(self._ctx, C.byref(params), C.byref(fb), cost_tbl or None, flag_tbl or None, int(k), rank_idx or None,
+                                              rank_cost or None, n_feasible or None, _abi.FP_MEM_DEVICE, stream or None))
 
     def plan_fopplus(self, batch: ProblemBatch, winner: bool = False, traj_stride: int = TRAJ_STRIDE, traj_sparse: bool = False):
         """FopPlusPlanner.plan() for every ego of the batch (fop_plus_planner.py:16-41) on the device: the cheapest feasible

@@ -78,6 +78,11 @@ class FrenetOptimalPlannerSettings:
         # every surviving candidate with (base_sum + w_obstacle * sum exp(-dist)) / N over has_collision's poses and returns the
         # argmin of that; FOP+, FISS and FISS+ order candidates before they have Cartesian points and raise ValueError
         self.w_obstacle = 0.0
+        # not in the reference's settings: > 0 (at most FP_MAX_RANK = 64): FrenetOptimalPlanner.plan() returns what it returns anyway and
+        # leaves `planner.alternatives`, up to that many FrenetTrajectory objects - the cheapest survivors in rank order (ascending
+        # cost, FOP's "last minimum wins" among equal costs), entry 0 the returned trajectory.  FOP+, FISS and FISS+ walk the lattice in
+        # their own order and raise ValueError
+        self.num_alternatives = 0
 
 
 class FissPlannerSettings(FrenetOptimalPlannerSettings):
@@ -190,6 +195,12 @@ class FrenetOptimalPlanner:
         if w_obs != 0.0 and self.KIND != "FOP":
             raise ValueError(f"settings.w_obstacle = {w_obs}: the clearance cost term is defined for FrenetOptimalPlanner only "
                              f"({self.KIND} orders candidates by cost before they have Cartesian points)")
+        n_alt = int(getattr(st, "num_alternatives", 0))
+        if n_alt != 0 and self.KIND != "FOP":
+            raise ValueError(f"settings.num_alternatives = {n_alt}: ranked alternatives are defined for FrenetOptimalPlanner only "
+                             f"({self.KIND} walks the lattice in its own order)")
+        if not 0 <= n_alt <= _abi.FP_MAX_RANK:
+            raise ValueError(f"settings.num_alternatives = {n_alt}: 0 (off) or 1 .. FP_MAX_RANK ({_abi.FP_MAX_RANK})")
         cache_tables = getattr(self, "cache_tables", True)
         key = (id(sp), id(tab), getattr(tab, "version", 0), cache_tables, st.num_width, st.num_speed, st.num_t, st.min_t, st.max_t, st.tick_t, st.max_road_width, st.lowest_speed,
                self.vehicle.l, self.vehicle.w, self.vehicle.max_speed, self.vehicle.max_accel, curv, w_obs)
@@ -296,7 +307,31 @@ class FrenetOptimalPlanner:
             fl = int(out.best_flags[0])  # N and M ride in the flag word (FP_FLAG_N_SHIFT / FP_FLAG_M_SHIFT)
             self.best_traj = FrenetTrajectory.from_dump(out.best_traj[0], (fl >> 8) & 0xFFF, fl >> 20, float(out.best_cost[0]))
             self.best_traj.lattice_index = best
+        n_alt = int(getattr(self.settings, "num_alternatives", 0))
+        if n_alt > 0:
+            self.alternatives = self._alternatives(batch, out, n_alt)
+        else:
+            self.__dict__.pop("alternatives", None)
         return self.best_traj
+
+    def _alternatives(self, batch: ProblemBatch, out, n_alt: int):
+        """The n_alt cheapest survivors of this plan() call in rank order (fp_rank_feasible over the call's tables); the series of
+        entries 1 .. come from fp_winner_trajs on the rank planes.  Off the hot path: one call per entry."""
+        rank_idx, rank_cost, _ = self._engine.rank_feasible(batch, out.cost, out.flags, n_alt)
+        alts = []
+        for k in range(n_alt):
+            idx = int(rank_idx[k, 0])
+            if idx < 0:
+                break
+            if k == 0 and idx == int(out.best_idx[0]):
+                alts.append(self.best_traj)
+                continue
+            w = self._engine.winner_trajs(batch, rank_idx[k], self._stride())
+            fl = int(w.best_flags[0])
+            traj = FrenetTrajectory.from_dump(w.best_traj[0], (fl >> 8) & 0xFFF, fl >> 20, float(rank_cost[k, 0]))
+            traj.lattice_index = idx
+            alts.append(traj)
+        return alts
 
 
 class FopPlusPlanner(FrenetOptimalPlanner):

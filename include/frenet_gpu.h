@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define FP_ABI_VERSION 17
+#define FP_ABI_VERSION 18
 
 /* error codes */
 #define FP_OK 0
@@ -65,6 +65,7 @@ extern "C" {
                                    it FP_ELIMIT - walk the dense tables on the host (fiss_plus_planner_amd/search.py), as the drop-in
                                    planner classes then do by themselves */
 #define FP_MAX_POLY_VERTS 128 /* vertices of one convex-polygon obstacle column (shapely's buffer() circle has 64) */
+#define FP_MAX_RANK 64      /* K of fp_rank_feasible */
 
 /* candidate flag word: low bits = why a candidate is infeasible, then N and M */
 #define FP_FLAG_SPEED 1u      /* any(s_d > max_speed)       frenet_optimal_planner.py:152 */
@@ -311,7 +312,8 @@ int fp_ctx_destroy(fp_ctx* ctx);
  * refinement), 1 = stop after the dense lattice pass; with 1 or 2 the outputs of the skipped stages are NOT produced. */
 int fp_ctx_set_option(fp_ctx* ctx, const char* name, int value);
 /* Reads an option back, or one of the read-only counters "clearance_launches" (launches of the clearance rescoring kernel,
- * fp_params.w_obstacle > 0, of this ctx so far), "looplog_launches" (launches of fp_loop_record's kernel), "lattice_launches" (dense lattice launches of this ctx so far) and
+ * fp_params.w_obstacle > 0, of this ctx so far), "looplog_launches" (launches of fp_loop_record's kernel), "rank_launches" (launches of
+ * fp_rank_feasible's kernel), "lattice_launches" (dense lattice launches of this ctx so far) and
  * "lattice_ordered_launches" (those dispatched in a feedback order or in the order of fp_batch.launch_order) - bench.py reports when an
  * order took effect -, "lattice_launches_2" / "_3" / "_4" (PROCESS-wide: fused lattice launches so far by workgroups per compute unit). */
 int fp_ctx_get_option(fp_ctx* ctx, const char* name, int* value);
@@ -334,6 +336,31 @@ int fp_plan_dense(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, c
  * themselves.  Replaces the object hand-back of plan() (:264-270). */
 int fp_winner_trajs(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, const int32_t* best_idx, uint32_t* best_flags,
                     double* best_traj, int32_t traj_stride, int32_t traj_sparse, int mem, void* stream);
+
+/* ---- the K cheapest feasible candidates of every ego (ABI 18) ------------------------------------------------------
+ * fp_plan_dense returns one index per ego, the argmin; whoever wants the runner-up (a behaviour layer that picks among the cheapest
+ * survivors, a fallback when the winner is vetoed downstream, a visualiser that draws the best handful) would otherwise read back
+ * both tables.  fp_rank_feasible ranks them on the device: cost_tbl / flag_tbl are [B][C] (C = nd*nv*nt) as fp_plan_dense wrote them.
+ *   survivor   a candidate with no FP_FLAG_INFEASIBLE bit and a cost that is not NaN (`min_cost >= cost_final`,
+ *              frenet_optimal_planner.py:266, never selects a NaN either).
+ *   order      ascending cost; among equal costs the HIGHER flat index first - the order in which the "last minimum wins" loop
+ *              (:263-268) would hand out winners if each winner were removed in turn.
+ *   rank_idx   [K][B]  flat FOP index of the k-th cheapest survivor, -1 past the last one.
+ *   rank_cost  [K][B]  its cost_tbl entry, bit for bit; NaN where rank_idx = -1.
+ *   n_feasible NULL or [B]: the number of survivors of the ego (can exceed K).
+ * Plane 0 is bit for bit best_idx / best_cost of the fp_plan_dense call that wrote the tables - with w_obstacle > 0 too (the tables then
+ * hold the re-priced costs).  The one exception: an ego whose FP_AUDIT_NEAR_TIE bit is set when result.audit was requested, because
+ * that path re-prices the tied candidates point by point and best_idx / best_cost are the outcome of those sums, not of the tables.
+ * The layout is rank-major on purpose: rank_idx + k*B is a valid best_idx argument of fp_winner_trajs and fp_advance - the k-th
+ * alternatives' series or hand-over need no new code and no gather.
+ * An ego with batch->skip[b] != 0 has no table rows: its planes are -1 / NaN, its count 0, and its rows are not read.
+ * FP_MEM_DEVICE: one kernel is enqueued (one workgroup per ego, in the order of batch->launch_order when there is one) - no
+ * allocation, no wait; it can be captured behind a dense call.  FP_MEM_HOST stages the tables through the ctx and waits, like
+ * fp_winner_trajs.  Of the batch only B and skip are used.  K < 1, K > FP_MAX_RANK or a NULL mandatory pointer: FP_EINVAL;
+ * nd*nv*nt > FP_MAX_CAND: FP_ELIMIT.  Two calls on the same tables give the same bits.
+ * Also read-only in fp_ctx_get_option: "rank_launches" = launches of the kernel on this ctx so far (0 for a caller that never asks). */
+int fp_rank_feasible(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, const double* cost_tbl, const uint32_t* flag_tbl,
+                     int32_t K, int32_t* rank_idx, double* rank_cost, int32_t* n_feasible, int mem, void* stream);
 
 /* Materialise the whole lattice: the full series of EVERY candidate of every ego, in FOP order
  *   traj [B][C][16][traj_stride] (traj_stride / traj_sparse as in fp_result), flags [B][C] (N << 8 | M << 20 | FP_FLAG_TRUNCATED; the feasibility bits

@@ -1,0 +1,142 @@
+"""CPU: the ranking rule of fp_rank_feasible, restated in numpy (tests/rank_ref.py), against the oracle - and the facts about the fixture
+batches that let tests/test_gpu_rank.py compare EVERY rank position of the kernel with the oracle's tables, leaving out none."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import rank_ref as R
+from fiss_plus_planner_amd import _abi, synth
+from fiss_plus_planner_amd.batch import ProblemBatch
+from fiss_plus_planner_amd.spline import build_frames
+
+# the batches the GPU test compares with the oracle position by position
+FIXTURES = {"5x5x5": lambda: synth.make_batch(64, 5, 5, 5, 10, 100, True, 101),
+            "9x9x7": lambda: synth.make_batch(64, 9, 9, 7, 50, 100, True, 7),
+            "9x9x7 free": lambda: synth.make_batch(32, 9, 9, 7, 0, 100, True, 11)}
+K_ALL = _abi.FP_MAX_RANK + 1  # "the first 65": every position a K = 64 list can hold and the one behind it
+NEAR = 2e-9  # twice the project's 1e-9 cost bar (tests/test_gpu_edges.py::cost_close), once per side
+
+
+def oracle_tables(oracle, batch):
+    tabs = [p.dense_tables() for p in oracle.problems_from_batch(batch)]
+    return np.stack([t[0] for t in tabs]), np.stack([t[1] for t in tabs])
+
+
+def tie_batch():
+    """One ego on a straight reference line with zero lateral state, a symmetric d_samples grid and no obstacles: the candidates at
+    +d and -d are mirror images, their costs bit-equal."""
+    xs = np.linspace(0.0, 400.0, 81)
+    knots, coef = build_frames(np.stack([xs, np.zeros_like(xs)], axis=1)[None])
+    base = synth.make_batch(1, 5, 5, 5, 0, 100, True, 101)
+    half = np.array([0.4, 0.8])
+    return ProblemBatch(d_samples=np.concatenate([-half[::-1], [0.0], half]), t_samples=base.t_samples, v_samples=base.v_samples, target_speed=base.target_speed,
+                        ego=np.array([[20.0, 8.0, 0.0, 0.0, 0.0, 0.0]]), frame_of=[0], scene_of=[-1], t_now=[0], nx=[81], knots=knots, coef=coef,
+                        obs_pose=base.obs_pose, obs_dims=base.obs_dims, final_time_step=base.final_time_step, veh_l=base.veh_l, veh_w=base.veh_w,
+                        max_speed=base.max_speed, max_accel=base.max_accel, tick_t=base.tick_t, check_stride=2, samp_min=base.samp_min,
+                        samp_max=base.samp_max, samp_res=base.samp_res)
+
+
+@pytest.mark.parametrize("name", sorted(FIXTURES))
+def test_plane_zero_is_the_fop_rule(oracle, name):
+    batch = FIXTURES[name]()
+    cost, flags = oracle_tables(oracle, batch)
+    idx, rc, n = R.rank_tables(cost, flags, 3)
+    plans = [p.fop_plan() for p in oracle.problems_from_batch(batch)]
+    assert np.array_equal(idx[0], [p.best_idx for p in plans])
+    assert np.array_equal(rc[0], [p.best_cost for p in plans], equal_nan=True)
+    assert (n > 0).any() and np.array_equal(idx[0] < 0, n == 0)
+
+
+def test_egos_without_a_survivor_give_minus_one(oracle):
+    batch = synth.make_batch(6, 5, 5, 5, 10, 100, True, 101)
+    batch.max_speed = 1.0  # every candidate breaks the speed limit
+    cost, flags = oracle_tables(oracle, batch)
+    idx, rc, n = R.rank_tables(cost, flags, 4)
+    assert (idx == -1).all() and np.isnan(rc).all() and (n == 0).all()
+    assert [p.fop_plan().best_idx for p in oracle.problems_from_batch(batch)] == [-1] * 6
+
+
+def test_padding_and_count(oracle):
+    batch = FIXTURES["5x5x5"]()
+    cost, flags = oracle_tables(oracle, batch)
+    alive = ((flags & R.FLAG_INFEASIBLE) == 0) & ~np.isnan(cost)
+    idx, rc, n = R.rank_tables(cost, flags, 64)
+    assert np.array_equal(n, alive.sum(axis=1))
+    assert (n < 64).any() and (n > 7).any()  # both sides of the K = 7 case: padded lists and cut ones
+    for b in range(batch.B):
+        m = min(int(n[b]), 64)
+        assert (idx[:m, b] >= 0).all() and (idx[m:, b] == -1).all() and np.isnan(rc[m:, b]).all()
+        assert alive[b, idx[:m, b]].all() and len(set(idx[:m, b].tolist())) == m
+        assert (np.diff(rc[:m, b]) >= 0).all() and np.array_equal(rc[:m, b], cost[b, idx[:m, b]])
+        rest = np.setdiff1d(np.nonzero(alive[b])[0], idx[:m, b])
+        assert rest.size == n[b] - m and (rest.size == 0 or cost[b, rest].min() >= rc[m - 1, b])
+    short, _, n7 = R.rank_tables(cost, flags, 7)
+    assert np.array_equal(short, idx[:7]) and np.array_equal(n7, n)  # the count is of all survivors, whatever K
+    skip = np.zeros(batch.B, dtype=np.int32)
+    skip[[1, 5]] = 1
+    si, sc, sn = R.rank_tables(cost, flags, 7, skip)
+    assert (si[:, [1, 5]] == -1).all() and np.isnan(sc[:, [1, 5]]).all() and (sn[[1, 5]] == 0).all()
+    live = skip == 0
+    assert np.array_equal(si[:, live], short[:, live])
+    # a NaN cost without an infeasible bit is no survivor either
+    c2, f2 = cost.copy(), flags.copy()
+    b0 = int(np.argmax(n))
+    c2[b0, idx[0, b0]] = np.nan
+    i2, _, n2 = R.rank_tables(c2, f2, 3)
+    assert n2[b0] == n[b0] - 1 and i2[0, b0] == idx[1, b0]
+
+
+@pytest.mark.parametrize("name", sorted(FIXTURES))
+def test_fixture_batches_have_no_near_ties(oracle, name):
+    """No two adjacent ranked survivors of the oracle's tables within 2e-9 max(1, |cost|) among the first 65: a kernel whose costs
+    are within the 1e-9 bar of the oracle's must then produce the oracle's ORDER at every position."""
+    cost, flags = oracle_tables(oracle, FIXTURES[name]())
+    idx, rc, n = R.rank_tables(cost, flags, K_ALL)
+    pairs, smallest = 0, np.inf
+    for b in range(cost.shape[0]):
+        m = min(int(n[b]), K_ALL)
+        if m < 2:
+            continue
+        gap = np.diff(rc[:m, b]) / np.maximum(1.0, np.abs(rc[1:m, b]))
+        pairs += m - 1
+        smallest = min(smallest, float(gap.min()))
+        assert (gap > NEAR).all(), (name, b, gap.min())
+    print(f"{name}: {pairs} adjacent pairs, smallest relative gap {smallest:.3g}")
+    assert pairs >= 1000 and smallest > NEAR
+
+
+def test_exact_tie_fixture(oracle):
+    batch = tie_batch()
+    cost, flags = oracle_tables(oracle, batch)
+    nd, nv, nt = batch.nd, batch.nv, batch.nt
+    alive = ((flags[0] & R.FLAG_INFEASIBLE) == 0) & ~np.isnan(cost[0])
+    grid, ok = cost[0].reshape(nd, nt, nv), alive.reshape(nd, nt, nv)  # flat FOP index (i_d * nt + i_T) * nv + i_v
+    assert np.array_equal(batch.d_samples, -batch.d_samples[::-1])
+    mirrored = ok & ok[::-1]
+    mirrored[nd // 2] = False
+    assert mirrored.any()
+    assert np.array_equal(grid[mirrored].view(np.uint64), grid[::-1][mirrored].view(np.uint64))  # bit-equal at +d and -d
+    idx, rc, n = R.rank_tables(cost, flags, 64)
+    m = min(int(n[0]), 64)
+    same = np.nonzero(rc[:m - 1, 0] == rc[1:m, 0])[0]
+    assert same.size >= 2
+    assert (idx[same, 0] > idx[same + 1, 0]).all()  # the higher index first
+    assert idx[0, 0] == oracle.problems_from_batch(batch)[0].fop_plan().best_idx
+
+
+def test_no_gpu_means_loud_failure():
+    import torch
+
+    if torch.cuda.is_available():
+        pytest.skip("a GPU is visible")
+    lib = _abi.load()
+    assert "fp_rank_feasible" in _abi.EXPORTED_SYMBOLS and _abi.FP_MAX_RANK == 64 and lib.fp_abi_version() == 18
+    p, fb = _abi.FpParams(), _abi.FpBatch()
+    rc = lib.fp_rank_feasible(None, C.byref(p), C.byref(fb), None, None, 4, None, None, None, _abi.FP_MEM_HOST, None)
+    assert rc == -1 and b"ctx is NULL" in lib.fp_last_error()
+    from fiss_plus_planner_amd.engine import FrenetEngine
+
+    assert callable(FrenetEngine.rank_feasible) and callable(FrenetEngine.rank_feasible_device)
+    with pytest.raises(_abi.FrenetGpuError):
+        FrenetEngine(0).rank_feasible(synth.make_batch(1, 3, 3, 2, 0, 20, False, 5), np.zeros((1, 18)), np.zeros((1, 18), dtype=np.uint32), 4)
