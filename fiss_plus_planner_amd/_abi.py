@@ -21,7 +21,8 @@ FP_MAX_RANK = 64  # K of fp_rank_feasible
 FLAG_SPEED, FLAG_ACCEL, FLAG_COLLISION, FLAG_TRUNCATED = 1, 2, 4, 8
 FLAG_CURVATURE, FLAG_KAPPA_D, FLAG_KAPPA_DD = 16, 32, 64   # optional checks (fp_params.curvature_mask)
 FLAG_CONSTRAINTS = FLAG_SPEED | FLAG_ACCEL | FLAG_CURVATURE | FLAG_KAPPA_D | FLAG_KAPPA_DD
-FLAG_INFEASIBLE = FLAG_CONSTRAINTS | FLAG_COLLISION
+FLAG_BOUNDARY = 128  # the candidate leaves the road corridor (written by fp_boundary_mask only)
+FLAG_INFEASIBLE = FLAG_CONSTRAINTS | FLAG_COLLISION | FLAG_BOUNDARY
 FLAG_N_SHIFT, FLAG_M_SHIFT = 8, 20
 
 _dp = C.POINTER(C.c_double)
@@ -30,7 +31,7 @@ _up = C.POINTER(C.c_uint32)
 
 # every symbol include/frenet_gpu.h declares (tests check the library exports all of them)
 EXPORTED_SYMBOLS = ("fp_abi_version", "fp_build_flags", "fp_build_compiler", "fp_last_error", "fp_device_count", "fp_device_info", "fp_ctx_create", "fp_ctx_destroy", "fp_ctx_set_option", "fp_ctx_get_option", "fp_ctx_join",
-                    "fp_plan_dense", "fp_winner_trajs", "fp_rank_feasible", "fp_eval_trajs", "fp_plan_fiss", "fp_advance", "fp_plan_step", "fp_plan_fiss_step", "fp_loop_record", "fp_frames_build", "fp_from_state", "fp_materialize_all",
+                    "fp_plan_dense", "fp_winner_trajs", "fp_rank_feasible", "fp_boundary_mask", "fp_eval_trajs", "fp_plan_fiss", "fp_advance", "fp_plan_step", "fp_plan_fiss_step", "fp_loop_record", "fp_frames_build", "fp_from_state", "fp_materialize_all",
                     "fp_group_create", "fp_group_destroy", "fp_group_submit", "fp_group_wait")
 
 
@@ -58,6 +59,11 @@ class FpResult(C.Structure):
     _fields_ = [("best_idx", C.c_void_p), ("best_cost", C.c_void_p), ("cost_tbl", C.c_void_p), ("flag_tbl", C.c_void_p),
                 ("stats", C.c_void_p), ("best_flags", C.c_void_p), ("best_traj", C.c_void_p), ("fopplus", C.c_void_p), ("audit", C.c_void_p),
                 ("traj_stride", C.c_int32), ("traj_sparse", C.c_int32)]
+
+
+class FpCorridor(C.Structure):
+    """The road edges as lateral offsets per reference-line knot (fp_boundary_mask)."""
+    _fields_ = [("left", C.c_void_p), ("right", C.c_void_p), ("margin", C.c_double)]
 
 
 AUDIT_NEAR_TIE, AUDIT_CONTACT, AUDIT_REORDERED, AUDIT_TIES_OVERFLOW = 1, 2, 4, 8
@@ -152,6 +158,9 @@ def load() -> C.CDLL:
                                   C.c_int, C.c_void_p]
     L.fp_rank_feasible.argtypes = [C.c_void_p, C.POINTER(FpParams), C.POINTER(FpBatch), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_int, C.c_void_p]
+    # (added within ABI 18: a library of the same version built before it lacks the symbol, and the attribute look-up says so)
+    L.fp_boundary_mask.argtypes = [C.c_void_p, C.POINTER(FpParams), C.POINTER(FpBatch), C.POINTER(FpCorridor), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_int, C.c_void_p]
     L.fp_eval_trajs.argtypes = [C.c_void_p, C.POINTER(FpParams), C.POINTER(FpBatch), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.c_int32, C.c_int32, C.c_int, C.c_void_p]
     L.fp_plan_fiss.argtypes = [C.c_void_p, C.POINTER(FpParams), C.POINTER(FpBatch), C.POINTER(FpFissOpts), C.POINTER(FpFissIo), C.c_int, C.c_void_p]

@@ -105,6 +105,12 @@ class ProblemBatch:
     # obstacle columns that are convex polygons instead of rectangles (fp_batch.obs_poly / obs_nvert); None = rectangles only
     obs_poly: np.ndarray | None = None   # [S, n_obs, PV, 2]
     obs_nvert: np.ndarray | None = None  # [S, n_obs] int32
+    # the road corridor of the boundary check the reference declares and never runs (`check_boundary`, frenet_optimal_planner.py:56;
+    # fp_corridor): lateral offset of the left (positive) / right (negative) road edge at every knot of every frame, +-inf = no edge;
+    # None = no corridor = the reference's behaviour
+    bound_left: np.ndarray | None = None   # [F, NX]
+    bound_right: np.ndarray | None = None  # [F, NX]
+    bound_margin: float = 0.0              # extra distance kept from both edges (m)
     meta: dict = field(default_factory=dict)
 
     def __post_init__(self):
@@ -132,6 +138,10 @@ class ProblemBatch:
             self.obs_poly, self.obs_nvert = f8(self.obs_poly), i4(self.obs_nvert)
             assert self.obs_nvert.shape == (self.S, self.n_obs) and self.obs_poly.ndim == 4
             assert self.obs_poly.shape[:2] == (self.S, self.n_obs) and self.obs_poly.shape[3] == 2 and self.obs_poly.shape[2] >= 3
+        assert (self.bound_left is None) == (self.bound_right is None), "bound_left and bound_right come together"
+        if self.bound_left is not None:
+            self.bound_left, self.bound_right = f8(self.bound_left), f8(self.bound_right)
+            assert self.bound_left.shape == (self.F, self.NX) and self.bound_right.shape == (self.F, self.NX)
 
     B = property(lambda self: self.ego.shape[0])
     nd = property(lambda self: self.d_samples.shape[0])
@@ -171,6 +181,8 @@ class ProblemBatch:
             w_obstacle=self.w_obstacle,
             obs_poly=None if self.obs_nvert is None else self.obs_poly[keep_s],
             obs_nvert=None if self.obs_nvert is None else self.obs_nvert[keep_s],
+            bound_left=None if self.bound_left is None else self.bound_left[fr],
+            bound_right=None if self.bound_right is None else self.bound_right[fr], bound_margin=self.bound_margin,
             meta=dict(self.meta, **(meta or {})))
 
     def shard(self, rank: int, world: int) -> "ProblemBatch":
@@ -189,4 +201,9 @@ class ProblemBatch:
             for name in ("obs_poly", "obs_nvert"):
                 a = getattr(self, name)
                 h.update(name.encode()); h.update(str(a.shape).encode()); h.update(np.ascontiguousarray(a).tobytes())
+        if self.bound_left is not None:  # (batches without a corridor keep their digests)
+            for name in ("bound_left", "bound_right"):
+                a = getattr(self, name)
+                h.update(name.encode()); h.update(str(a.shape).encode()); h.update(np.ascontiguousarray(a).tobytes())
+            h.update(b"bound_margin"); h.update(np.float64(self.bound_margin).tobytes())
         return h.hexdigest()

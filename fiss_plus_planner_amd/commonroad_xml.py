@@ -8,6 +8,8 @@ Replaces, for the reference's demo inputs, `CommonRoadFileReader(...).open()` (p
   (the reference asks commonroad-route-planner for it; all five demo scenarios have a unique such route - SURVEY.md 8f);
   like the reference (:68-75) the first successor of the last lanelet is appended when there is one;
 * centerline = concatenated centre vertices with duplicates removed, first occurrence kept (:79-82);
+* corridor = the same vertices' left / right bounds as lateral offsets from the centre line (the reference parses the bounds only to
+  average them; here they feed the road-boundary check, fp_boundary_mask);
 * dynamic obstacles -> pose table [T, n, 4] = x, y, yaw, valid + dims [n, 2] (what has_collision() reads); shapes other than
   centred rectangles - rectangles with a centre / orientation, circles, polygons - become polygon columns (obstacles.shape_columns:
   `obstacle_shape.shapely_object` is any polygon in the reference, frenet_optimal_planner.py:189-191).
@@ -38,6 +40,9 @@ class Scenario:
     goal_lanelet: int
     goal_center: np.ndarray       # middle centre vertex of the goal lanelet (planning.py:54-58)
     goal_speed: tuple | None      # (start, end) of the goal velocity interval, if any (planning.py:44-48)
+    # [n, 2] = left, right: distance of the route lanelets' own bound vertices from the centre vertex, left positive and right
+    # negative, row for row with `centerline` (what FrenetOptimalPlanner.set_road_boundary takes).  Adjacent lanelets are not merged in
+    corridor: np.ndarray | None = None
 
     @property
     def max_speed(self) -> float:
@@ -139,7 +144,12 @@ def load_scenario(path: str, circle_buffer_factor: float = CIRCLE_BUFFER_FACTOR)
         lanes.append(lanelets[route[-1]]["succ"][0])
     cc = np.concatenate([lanelets[i]["center"] for i in lanes])
     _, first = np.unique(cc, return_index=True, axis=0)
-    centerline = cc[np.sort(first)]
+    keep = np.sort(first)
+    centerline = cc[keep]
+    # the road edges of the route: one bound vertex per centre vertex (CommonRoad), under the centre line's de-duplication index
+    lb = np.concatenate([lanelets[i]["left"] for i in lanes])[keep]
+    rb = np.concatenate([lanelets[i]["right"] for i in lanes])[keep]
+    corridor = np.column_stack((np.hypot(*(lb - centerline).T), -np.hypot(*(rb - centerline).T)))
     gc = lanelets[goal_lanelet]["center"]
     goal_center = gc[int((gc.shape[0] - 1) / 2)]
 
@@ -168,4 +178,4 @@ def load_scenario(path: str, circle_buffer_factor: float = CIRCLE_BUFFER_FACTOR)
             pose[t, j] = (x + cx, y + cy, yaw, 1.0)
     fts = max(obs[0][1])  # dynamic_obstacles[0].prediction.final_time_step
     return Scenario(root.get("benchmarkID"), float(root.get("timeStepSize")), route, centerline,
-                    ObstacleTable(pose[:max(fts, 1)], dims, fts, poly=poly, nvert=nvert), init, goal_lanelet, np.asarray(goal_center), goal_speed)
+                    ObstacleTable(pose[:max(fts, 1)], dims, fts, poly=poly, nvert=nvert), init, goal_lanelet, np.asarray(goal_center), goal_speed, corridor)

@@ -193,6 +193,7 @@ struct fp_ctx {
     int clearance_launches = 0;    // fp_ctx_get_option("clearance_launches"): launches of the clearance rescoring kernel (fp_params.w_obstacle > 0)
     int looplog_launches = 0;      // fp_ctx_get_option("looplog_launches"): launches of the loop-log kernel (fp_loop_record)
     int rank_launches = 0;         // fp_ctx_get_option("rank_launches"): launches of the ranking kernel (fp_rank_feasible)
+    int boundary_launches = 0;     // fp_ctx_get_option("boundary_launches"): launches of the road-boundary kernel (fp_boundary_mask)
     OrderSet order_lattice, order_refine;
     DeviceBuf idx_shadow;          // [B] device copy of best_idx for the winner kernel of a dense call (KernelArgs::idx_shadow)
     DeviceBuf epi_flags;           // [B] hand-over flags of the epilogue workgroups appended to a multi-round lattice launch (KernelArgs::epi_flag); zero between launches
@@ -1447,7 +1448,7 @@ int fp_ctx_get_option(fp_ctx* ctx, const char* name, int* value)
     const struct { const char* n; int v; } tab[] = {
         {"lattice_kernel", ctx->lattice_kernel}, {"lattice_split", ctx->lattice_split}, {"lattice_group", ctx->lattice_group}, {"lattice_tail", ctx->lattice_tail}, {"lattice_occupancy", ctx->lattice_occupancy}, {"resident_groups", ctx->resident_groups}, {"zero_copy_in", ctx->zero_copy_in}, {"stage_kernel", ctx->stage_kernel}, {"inline_inputs", ctx->inline_inputs}, {"lattice_order", ctx->lattice_order},
         {"refine_table_kb", ctx->refine_table_kb}, {"fiss_stages", ctx->fiss_stages}, {"fiss_jump", ctx->fiss_jump}, {"validate", ctx->validate}, {"lattice_winner", ctx->lattice_winner}, {"fiss_fused", ctx->fiss_fused}, {"appended_workgroups", ctx->appended_ok ? 1 : 0}, {"handover_failed", ctx->hand_err ? *(volatile int32_t*)ctx->hand_err : 0}, {"overlap", ctx->overlap}, {"overlapped_calls", ctx->overlapped_calls}, {"clearance_launches", ctx->clearance_launches + (ctx->twin ? ctx->twin->clearance_launches : 0)}, {"lattice_launches", ctx->lattice_launches + (ctx->twin ? ctx->twin->lattice_launches : 0)},
-        {"looplog_launches", ctx->looplog_launches}, {"rank_launches", ctx->rank_launches}, {"lattice_ordered_launches", ctx->lattice_ordered_launches + (ctx->twin ? ctx->twin->lattice_ordered_launches : 0)},
+        {"looplog_launches", ctx->looplog_launches}, {"rank_launches", ctx->rank_launches}, {"boundary_launches", ctx->boundary_launches}, {"lattice_ordered_launches", ctx->lattice_ordered_launches + (ctx->twin ? ctx->twin->lattice_ordered_launches : 0)},
         {"lattice_launches_2", (int)fp::lattice_launches_per_cu(0)}, {"lattice_launches_3", (int)fp::lattice_launches_per_cu(1)}, {"lattice_launches_4", (int)fp::lattice_launches_per_cu(2)}};
     for (const auto& t : tab)
         if (strcmp(name, t.n) == 0) { *value = t.v; return FP_OK; }
@@ -1631,6 +1632,63 @@ int fp_rank_feasible(fp_ctx* ctx, const fp_params* params, const fp_batch* batch
     a.n_feasible = hs.out(n_feasible, B);
     LAUNCH_TRY(fp::launch_rank_feasible(a, ctx->stream), "ranking kernel");
     ++ctx->rank_launches;
+    return hs.fetch_out();
+}
+
+int fp_boundary_mask(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, const fp_corridor* corridor, const double* cost_tbl,
+                     uint32_t* flag_tbl, int32_t* best_idx, double* best_cost, int32_t* n_masked, int mem, void* stream)
+{
+    FP_TRY(common_checks(ctx, params, batch, mem, stream));
+    if (!corridor || !corridor->left || !corridor->right) return fail(FP_EINVAL, "fp_boundary_mask: corridor / left / right must not be NULL");
+    if (!cost_tbl || !flag_tbl || !best_idx || !best_cost) return fail(FP_EINVAL, "fp_boundary_mask: cost_tbl/flag_tbl/best_idx/best_cost must not be NULL");
+    if (!(corridor->margin >= 0) || corridor->margin > 1.7976931348623157e308) return fail(FP_EINVAL, "fp_boundary_mask: margin must be finite and >= 0");
+    if (batch->B == 0) return FP_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t B = (size_t)batch->B, C = (size_t)params->nd * params->nv * params->nt, fn = (size_t)batch->F * batch->NX;
+    fp::BoundaryArgs a;
+    a.B = batch->B; a.NX = batch->NX; a.nd = params->nd; a.nv = params->nv; a.nt = params->nt;
+    a.tick_t = params->tick_t; a.veh_l = params->veh_l; a.veh_w = params->veh_w; a.margin = corridor->margin;
+    if (mem == FP_MEM_DEVICE) {
+        a.d_samples = batch->d_samples; a.t_samples = batch->t_samples; a.v_samples = batch->v_samples; a.ego = batch->ego;
+        a.frame_of = batch->frame_of; a.nx = batch->nx; a.knots = batch->knots; a.left = corridor->left; a.right = corridor->right;
+        a.skip = batch->skip; a.perm = batch->launch_order;
+        a.cost_tbl = cost_tbl; a.flag_tbl = flag_tbl; a.best_idx = best_idx; a.best_cost = best_cost; a.n_masked = n_masked;
+        LAUNCH_TRY(fp::launch_boundary_mask(a, (hipStream_t)stream), "road-boundary kernel");
+        ++ctx->boundary_launches;
+        return FP_OK;
+    }
+    // host arrays: only what the kernel reads travels (the lattice samples, the ego states, the knots, the corridor and the two tables)
+    for (int i = 0; i < batch->B; ++i)
+        if (batch->frame_of[i] < 0 || batch->frame_of[i] >= batch->F) return fail(FP_EINVAL, "frame_of[%d]=%d out of range", i, batch->frame_of[i]);
+    for (int f = 0; f < batch->F; ++f) {
+        if (batch->nx[f] < 2 || batch->nx[f] > batch->NX) return fail(FP_EINVAL, "nx[%d]=%d out of range", f, batch->nx[f]);
+        for (int k = 0; k < batch->nx[f]; ++k) {
+            const double l = corridor->left[(size_t)f * batch->NX + k], r = corridor->right[(size_t)f * batch->NX + k];
+            if (!(l == l) || !(r == r)) return fail(FP_EINVAL, "fp_boundary_mask: corridor has a NaN at frame %d, knot %d (+-inf says \"no edge\")", f, k);
+        }
+    }
+    HostStage hs(ctx);
+    FP_TRY(hs.reserve(HostStage::need<double>(params->nd) + HostStage::need<double>(params->nt) + HostStage::need<double>(B * params->nv) +
+                      HostStage::need<double>(B * 6) + 4 * HostStage::need<int32_t>(B) + HostStage::need<int32_t>(batch->F) + 3 * HostStage::need<double>(fn) +
+                      HostStage::need<double>(B * C) + HostStage::need<uint32_t>(B * C) + HostStage::need<double>(B)));
+    FP_TRY(hs.in(batch->d_samples, (size_t)params->nd, &a.d_samples));
+    FP_TRY(hs.in(batch->t_samples, (size_t)params->nt, &a.t_samples));
+    FP_TRY(hs.in(batch->v_samples, B * params->nv, &a.v_samples));
+    FP_TRY(hs.in(batch->ego, B * 6, &a.ego));
+    FP_TRY(hs.in(batch->frame_of, B, &a.frame_of));
+    FP_TRY(hs.in(batch->nx, (size_t)batch->F, &a.nx));
+    FP_TRY(hs.in(batch->knots, fn, &a.knots));
+    FP_TRY(hs.in(corridor->left, fn, &a.left));
+    FP_TRY(hs.in(corridor->right, fn, &a.right));
+    if (batch->skip) FP_TRY(hs.in(batch->skip, B, &a.skip));
+    FP_TRY(hs.in(cost_tbl, B * C, &a.cost_tbl));
+    FP_TRY(hs.in_mut(flag_tbl, B * C, &a.flag_tbl));
+    FP_TRY(hs.flush_in());
+    a.best_idx = hs.out(best_idx, B);
+    a.best_cost = hs.out(best_cost, B);
+    a.n_masked = hs.out(n_masked, B);
+    LAUNCH_TRY(fp::launch_boundary_mask(a, ctx->stream), "road-boundary kernel");
+    ++ctx->boundary_launches;
     return hs.fetch_out();
 }
 

@@ -200,6 +200,30 @@ struct RankArgs {
     int32_t* n_feasible = nullptr;
 };
 hipError_t launch_rank_feasible(const RankArgs& a, hipStream_t stream);
+// The road-boundary check behind the dense pass (frenet_boundary.hip, fp_boundary_mask): writes FP_FLAG_BOUNDARY of every candidate in
+// flag_tbl [B][C] and the ego's argmin over what is still feasible.  One workgroup per ego, in the order of perm (optional).  Device
+// addresses; left / right are [F][NX] lateral offsets of the road edges at the knots; n_masked (optional) [B].
+struct BoundaryArgs {
+    int B = 0, NX = 0, nd = 1, nv = 1, nt = 1;
+    double tick_t = 0.0, veh_l = 0.0, veh_w = 0.0, margin = 0.0;
+    const double* d_samples = nullptr;
+    const double* t_samples = nullptr;
+    const double* v_samples = nullptr;
+    const double* ego = nullptr;
+    const int32_t* frame_of = nullptr;
+    const int32_t* nx = nullptr;
+    const double* knots = nullptr;
+    const double* left = nullptr;
+    const double* right = nullptr;
+    const int32_t* skip = nullptr;
+    const int32_t* perm = nullptr;
+    const double* cost_tbl = nullptr;
+    uint32_t* flag_tbl = nullptr;
+    int32_t* best_idx = nullptr;
+    double* best_cost = nullptr;
+    int32_t* n_masked = nullptr;
+};
+hipError_t launch_boundary_mask(const BoundaryArgs& a, hipStream_t stream);
 // Series of EVERY lattice candidate: ka.r.best_traj [B*C][16][traj_stride], ka.r.best_flags [B*C] (N, M, truncated).
 hipError_t launch_materialize_all(const KernelArgs& ka, hipStream_t stream);
 hipError_t launch_eval_trajs(const KernelArgs& ka, int K, const double* end_states, double* cost, uint32_t* flags, double* traj,

@@ -32,7 +32,7 @@ class DeviceBatch:
         self.host = batch
         self.dev = torch.device("cuda", device)
         self.t = {k: torch.from_numpy(np.ascontiguousarray(getattr(batch, k))).to(self.dev) for k in _NAMES}
-        for k in ("samp_min", "samp_max", "samp_res", "obs_poly", "obs_nvert"):
+        for k in ("samp_min", "samp_max", "samp_res", "obs_poly", "obs_nvert", "bound_left", "bound_right"):  # (the corridor: boundary_mask_device)
             if getattr(batch, k, None) is not None:
                 self.t[k] = torch.from_numpy(getattr(batch, k)).to(self.dev)
         if order_hint and batch.B > 0:

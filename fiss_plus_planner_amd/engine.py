@@ -206,7 +206,7 @@ class FrenetEngine:
             best_traj=(np.full((B, 16, traj_stride), np.nan) if traj_sparse else np.empty((B, 16, traj_stride))) if winner else None)
 
     def plan_dense(self, batch: ProblemBatch, tables: bool = True, winner: bool = False, traj_stride: int = TRAJ_STRIDE, traj_sparse: bool = False,
-                   out: SimpleNamespace | None = None, audit: bool = False, top_k: int = 0):
+                   out: SimpleNamespace | None = None, audit: bool = False, top_k: int = 0, boundary: bool = False):
         """FrenetOptimalPlanner.plan() for every ego of the batch (reference frenet_optimal_planner.py:247-270).
 
         Returns best_idx [B] (flat (i_d*nt+i_T)*nv+i_v, -1 = none), best_cost [B], stats [B,4] and, with
@@ -215,8 +215,41 @@ class FrenetEngine:
         feasible candidate within 1e-9 of the winner's cost - settled by point-by-point sums -, a collision verdict within 1e-9 m of
         contact; include/frenet_gpu.h).  top_k > 0: also rank_idx [top_k, B], rank_cost [top_k, B] and n_feasible [B], the top_k
         cheapest survivors of every ego ranked on the device (rank_feasible); the tables are computed for it whether asked for or not
-        (`cost` / `flags` are returned only with tables=True).
+        (`cost` / `flags` are returned only with tables=True).  boundary=True (the batch must carry a corridor: bound_left /
+        bound_right): the road-boundary check (boundary_mask) runs behind the dense call over its tables - computed for it whether
+        asked for or not -; best_idx / best_cost are the argmin among the candidates that stay inside the corridor, `flags` carry
+        FLAG_BOUNDARY, top_k ranks the masked tables, also n_masked [B]; with winner=True the series come from winner_trajs on the new
+        best_idx (the lattice launch's own series may belong to a masked winner).
         """
+        if boundary:
+            if getattr(batch, "bound_left", None) is None:
+                raise ValueError("plan_dense(boundary=True): the batch carries no corridor (ProblemBatch.bound_left / bound_right)")
+            if audit:
+                raise ValueError("plan_dense(boundary=True, audit=True): the audit bits describe the dense call's own answer, not the masked one")
+            want_tables = tables
+            if out is not None and not tables:  # the caller's arrays hold no tables: the call brings its own
+                out.cost, out.flags = np.empty((batch.B, batch.C)), np.empty((batch.B, batch.C), dtype=np.uint32)
+                out.__dict__.pop("_res", None)
+            out = self.plan_dense(batch, True, winner, traj_stride, traj_sparse, out)
+            if batch.B:
+                _, bi, bc, out.n_masked = self.boundary_mask(batch, out.cost, out.flags, inplace=True)
+                out.best_idx[...], out.best_cost[...] = bi, bc
+                if winner:
+                    w = self.winner_trajs(batch, out.best_idx, traj_stride, traj_sparse)
+                    out.best_flags[...], out.best_traj[...] = w.best_flags, w.best_traj
+            else:
+                out.n_masked = np.empty(0, dtype=np.int32)
+            if top_k:
+                if not 1 <= int(top_k) <= _abi.FP_MAX_RANK:
+                    raise ValueError(f"top_k={top_k}: 0 (off) or 1 .. FP_MAX_RANK ({_abi.FP_MAX_RANK})")
+                if batch.B:
+                    out.rank_idx, out.rank_cost, out.n_feasible = self.rank_feasible(batch, out.cost, out.flags, int(top_k))
+                else:
+                    out.rank_idx, out.rank_cost, out.n_feasible = np.empty((int(top_k), 0), dtype=np.int32), np.empty((int(top_k), 0)), np.empty(0, dtype=np.int32)
+            if not want_tables:
+                out.cost = out.flags = None
+                out.__dict__.pop("_res", None)
+            return out
         if top_k:
             if not 1 <= int(top_k) <= _abi.FP_MAX_RANK:
                 raise ValueError(f"top_k={top_k}: 0 (off) or 1 .. FP_MAX_RANK ({_abi.FP_MAX_RANK})")
@@ -285,6 +318,40 @@ class FrenetEngine:
         rank_idx + 4 * j * B is the best_idx argument of winner_trajs_device / fp_advance for the j-th alternatives."""
         _abi.check(self._lib.fp_rank_feasible(self._ctx, C.byref(params), C.byref(fb), cost_tbl or None, flag_tbl or None, int(k), rank_idx or None,
                                               rank_cost or None, n_feasible or None, _abi.FP_MEM_DEVICE, stream or None))
+
+    def boundary_mask(self, batch: ProblemBatch, cost: np.ndarray, flags: np.ndarray, skip: np.ndarray | None = None, inplace: bool = False):
+        """The road-boundary check over plan_dense's tables (fp_boundary_mask; the definition: include/frenet_gpu.h): cost [B,C],
+        flags [B,C] and the batch's corridor (bound_left / bound_right [F,NX], bound_margin) -> (flags, best_idx, best_cost, n_masked):
+        the flag words with FLAG_BOUNDARY written (a copy, unless inplace=True and `flags` is a contiguous uint32 array), the argmin
+        among the candidates without a FLAG_INFEASIBLE bit - which includes FLAG_BOUNDARY - and the number of candidates per ego that
+        carry the bit.  skip [B] (optional): egos whose rows are neither read nor written (-1 / NaN / 0)."""
+        if getattr(batch, "bound_left", None) is None:
+            raise ValueError("boundary_mask: the batch carries no corridor (ProblemBatch.bound_left / bound_right)")
+        B, Cn = batch.B, batch.C
+        cost = np.ascontiguousarray(cost, dtype=np.float64)
+        if not (inplace and isinstance(flags, np.ndarray) and flags.dtype == np.uint32 and flags.flags.c_contiguous and flags.flags.writeable):
+            flags = np.array(flags, dtype=np.uint32, order="C", copy=True)
+        if cost.shape != (B, Cn) or flags.shape != (B, Cn):
+            raise ValueError(f"boundary_mask: cost / flags must be [B={B}, C={Cn}] tables, got {cost.shape} / {flags.shape}")
+        best_idx = np.empty(B, dtype=np.int32); best_cost = np.empty(B); n_masked = np.empty(B, dtype=np.int32)
+        p, fb = host_structs(batch)
+        if skip is not None:
+            skip = np.ascontiguousarray(skip, dtype=np.int32)
+            assert skip.shape == (B,)
+            fb.skip = _ptr(skip)
+        cor = _abi.FpCorridor(_ptr(batch.bound_left), _ptr(batch.bound_right), float(batch.bound_margin))
+        _abi.check(self._lib.fp_boundary_mask(self._ctx, C.byref(p), C.byref(fb), C.byref(cor), _ptr(cost), _ptr(flags), _ptr(best_idx), _ptr(best_cost),
+                                              _ptr(n_masked), _abi.FP_MEM_HOST, None))
+        return flags, best_idx, best_cost, n_masked
+
+    def boundary_mask_device(self, params: _abi.FpParams, fb: _abi.FpBatch, left: int, right: int, margin: float, cost_tbl: int, flag_tbl: int,
+                             best_idx: int, best_cost: int, n_masked: int = 0, stream: int = 0):
+        """Enqueue the road-boundary check behind a dense call (device addresses): left / right [F][NX], the dense call's cost_tbl /
+        flag_tbl [B][C] (flag_tbl in/out), best_idx / best_cost [B] out, n_masked [B] or 0.  best_idx is a valid argument of
+        winner_trajs_device / fp_advance as it stands."""
+        cor = _abi.FpCorridor(left or None, right or None, float(margin))
+        _abi.check(self._lib.fp_boundary_mask(self._ctx, C.byref(params), C.byref(fb), C.byref(cor), cost_tbl or None, flag_tbl or None, best_idx or None,
+                                              best_cost or None, n_masked or None, _abi.FP_MEM_DEVICE, stream or None))
 
     def plan_fopplus(self, batch: ProblemBatch, winner: bool = False, traj_stride: int = TRAJ_STRIDE, traj_sparse: bool = False):
         """FopPlusPlanner.plan() for every ego of the batch (fop_plus_planner.py:16-41) on the device: the cheapest feasible

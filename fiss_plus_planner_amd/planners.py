@@ -69,6 +69,8 @@ class FrenetOptimalPlannerSettings:
         self.max_t = 10.0
         self.num_t = num_t
         self.check_obstacle = True   # present in the reference, never read there either
+        # declared by the reference and never read there.  Here: FrenetOptimalPlanner.plan() rejects the candidates that leave the road
+        # corridor when this is true AND the caller handed the road edges over (set_road_boundary); without edges nothing changes
         self.check_boundary = True
         # not in the reference's settings: turns on the curvature / curvature-rate checks that its check_constraints carries
         # commented out (:145-150), with the Vehicle's max_curvature / max_kappa_d / max_kappa_dd (vehicle.py:44-46)
@@ -163,6 +165,25 @@ class FrenetOptimalPlanner:
         x, y, yaw, kappa = self.cubic_spline.sample(s)
         return self.cubic_spline, np.column_stack((x, y, yaw, kappa))
 
+    def set_road_boundary(self, left, right, margin: float = 0.0):
+        """The road edges for the check the reference declares as `settings.check_boundary` and never runs: one lateral offset per
+        centre-line point handed to generate_frenet_frame() - left positive, right negative, +-inf = no edge at that point - and an extra
+        distance kept from both.  While settings.check_boundary is true, plan() then returns the cheapest candidate whose footprint stays
+        inside the corridor at every point (fp_boundary_mask, include/frenet_gpu.h).  left = None removes the edges again.
+        FOP+, FISS and FISS+ order candidates by cost before validation and raise ValueError."""
+        if self.KIND != "FOP":
+            raise ValueError(f"set_road_boundary: the road-boundary check is defined for FrenetOptimalPlanner only "
+                             f"({self.KIND} orders candidates by cost before validation)")
+        if left is None:
+            self._boundary = None
+            return
+        left, right = np.array(left, dtype=np.float64).ravel(), np.array(right, dtype=np.float64).ravel()
+        if left.shape != right.shape or np.isnan(left).any() or np.isnan(right).any():
+            raise ValueError("set_road_boundary: left and right need one value per centre-line point each, none of them NaN")
+        if not (np.isfinite(margin) and margin >= 0):
+            raise ValueError(f"set_road_boundary: margin = {margin} must be finite and >= 0")
+        self._boundary = (left, right, float(margin))
+
     # ------------------------------------------------------------------ problem marshalling
     def _obstacle_table(self, obstacles) -> ObstacleTable | None:
         if isinstance(obstacles, ObstacleTable):
@@ -201,9 +222,12 @@ class FrenetOptimalPlanner:
                              f"({self.KIND} walks the lattice in its own order)")
         if not 0 <= n_alt <= _abi.FP_MAX_RANK:
             raise ValueError(f"settings.num_alternatives = {n_alt}: 0 (off) or 1 .. FP_MAX_RANK ({_abi.FP_MAX_RANK})")
+        bound = getattr(self, "_boundary", None) if getattr(st, "check_boundary", False) else None
+        if bound is not None and len(bound[0]) != len(sp.knots):
+            raise ValueError(f"set_road_boundary: {len(bound[0])} edge values for a centre line of {len(sp.knots)} points")
         cache_tables = getattr(self, "cache_tables", True)
         key = (id(sp), id(tab), getattr(tab, "version", 0), cache_tables, st.num_width, st.num_speed, st.num_t, st.min_t, st.max_t, st.tick_t, st.max_road_width, st.lowest_speed,
-               self.vehicle.l, self.vehicle.w, self.vehicle.max_speed, self.vehicle.max_accel, curv, w_obs)
+               self.vehicle.l, self.vehicle.w, self.vehicle.max_speed, self.vehicle.max_accel, curv, w_obs, id(bound))
         cache = getattr(self, "_batch_cache", None)
         if cache is None or cache[0] != key:
             sw = self._sampling_width()
@@ -221,7 +245,9 @@ class FrenetOptimalPlanner:
                 samp_min=np.array([[-sw / 2, st.lowest_speed, st.min_t]]), samp_max=np.array([[sw / 2, 0.0, st.max_t]]),
                 samp_res=np.array([[rd, 0.0, rt]]), curvature_limits=curv, w_obstacle=w_obs,
                 obs_poly=None if tab is None or tab.nvert is None else tab.poly[None],
-                obs_nvert=None if tab is None or tab.nvert is None else tab.nvert[None])
+                obs_nvert=None if tab is None or tab.nvert is None else tab.nvert[None],
+                bound_left=None if bound is None else bound[0][None], bound_right=None if bound is None else bound[1][None],
+                bound_margin=0.0 if bound is None else bound[2])
             # fp_batch.tables_tag: the library keeps this batch's spline and obstacle tables on the device until the planner builds
             # a new batch (another centerline / another obstacle list / ObstacleTable.update()) - per cycle only the start state
             # travels.  Contract (class docstring): the cached arrays are frozen, so an in-place edit raises instead of going stale;
@@ -233,7 +259,7 @@ class FrenetOptimalPlanner:
                 sp.knots.setflags(write=False)
                 sp.coef.setflags(write=False)
             host_structs(batch, freeze=True)  # (this batch is the planner's own: its arrays are only ever updated in place)
-            cache = [key, batch, None, sp, tab]  # sp / tab kept alive so their ids cannot be recycled
+            cache = [key, batch, None, sp, tab, bound]  # sp / tab / bound kept alive so their ids cannot be recycled
             self._batch_cache = cache
         batch = cache[1]
         if cache[2] != st.highest_speed:
@@ -281,7 +307,8 @@ class FrenetOptimalPlanner:
         reuse = outs.get(key)
         if reuse is None:
             reuse = outs[key] = self._engine.dense_outputs(1, batch.C, True, winner, stride)
-        out = self._engine.plan_dense(batch, tables=True, winner=winner, traj_stride=stride, out=reuse)
+        # (a corridor on the batch: the road-boundary check runs behind the dense call and decides the winner)
+        out = self._engine.plan_dense(batch, tables=True, winner=winner, traj_stride=stride, out=reuse, boundary=batch.bound_left is not None)
         self.last_tables = (out.cost[0].copy(), out.flags[0].copy())
         if self.materialize_all:  # visualisation payload (reference :102): every candidate's series in one launch
             m = self._engine.materialize_all(batch, traj_stride=stride)

@@ -78,7 +78,8 @@ extern "C" {
 #define FP_FLAG_KAPPA_D 32u   /* any(|c_d| > max_kappa_d)    :147-148 */
 #define FP_FLAG_KAPPA_DD 64u  /* any(|c_dd| > max_kappa_dd)  :149-150 */
 #define FP_FLAG_CONSTRAINTS (FP_FLAG_SPEED | FP_FLAG_ACCEL | FP_FLAG_CURVATURE | FP_FLAG_KAPPA_D | FP_FLAG_KAPPA_DD) /* check_constraints */
-#define FP_FLAG_INFEASIBLE (FP_FLAG_CONSTRAINTS | FP_FLAG_COLLISION)
+#define FP_FLAG_BOUNDARY 128u  /* the candidate leaves the road corridor; written by fp_boundary_mask only (no other entry point sets it) */
+#define FP_FLAG_INFEASIBLE (FP_FLAG_CONSTRAINTS | FP_FLAG_COLLISION | FP_FLAG_BOUNDARY)
 #define FP_FLAG_N_SHIFT 8     /* bits 8..19  N = len(t) */
 #define FP_FLAG_M_SHIFT 20    /* bits 20..31 M = len(x) */
 
@@ -313,7 +314,7 @@ int fp_ctx_destroy(fp_ctx* ctx);
 int fp_ctx_set_option(fp_ctx* ctx, const char* name, int value);
 /* Reads an option back, or one of the read-only counters "clearance_launches" (launches of the clearance rescoring kernel,
  * fp_params.w_obstacle > 0, of this ctx so far), "looplog_launches" (launches of fp_loop_record's kernel), "rank_launches" (launches of
- * fp_rank_feasible's kernel), "lattice_launches" (dense lattice launches of this ctx so far) and
+ * fp_rank_feasible's kernel), "boundary_launches" (launches of fp_boundary_mask's kernel), "lattice_launches" (dense lattice launches of this ctx so far) and
  * "lattice_ordered_launches" (those dispatched in a feedback order or in the order of fp_batch.launch_order) - bench.py reports when an
  * order took effect -, "lattice_launches_2" / "_3" / "_4" (PROCESS-wide: fused lattice launches so far by workgroups per compute unit). */
 int fp_ctx_get_option(fp_ctx* ctx, const char* name, int* value);
@@ -361,6 +362,64 @@ int fp_winner_trajs(fp_ctx* ctx, const fp_params* params, const fp_batch* batch,
  * Also read-only in fp_ctx_get_option: "rank_launches" = launches of the kernel on this ctx so far (0 for a caller that never asks). */
 int fp_rank_feasible(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, const double* cost_tbl, const uint32_t* flag_tbl,
                      int32_t K, int32_t* rank_idx, double* rank_cost, int32_t* n_feasible, int mem, void* stream);
+
+/* ---- the road-boundary check (added WITHIN ABI 18: detect it by looking the symbol up, e.g. dlsym) --------------------
+ * The reference declares the check - `check_boundary = True  # True if check collison with road boundaries`,
+ * frenet_optimal_planner.py:56 - and never reads the setting.  The lattice confines only the END offset of a candidate to the road
+ * width; nothing stops a candidate from swinging over the road edge on the way there (a large d_d or d at the start, a road narrower
+ * than max_road_width).  fp_boundary_mask finishes it, behind fp_plan_dense and over its tables: cost_tbl / flag_tbl are [B][C]
+ * (C = nd*nv*nt) as fp_plan_dense wrote them.  The road is a corridor in Frenet coordinates: one lateral offset per reference-line
+ * knot and side (CommonRoad gives one bound vertex per centre vertex).
+ *
+ * Definition, for every candidate c of every ego b that is not skipped, N and M taken from the candidate's flag word:
+ *   checked points   i = 1 .. M-1 of the trajectory.  Point 0 is the ego's present state, common to all candidates: it selects
+ *                    nothing.  Points at or after M are off the reference line and have no frame.  M <= 1: nothing is checked, no bit.
+ *   at point i       s, s_d, d, d_d = the candidate's series values at t = i * tick_t;
+ *                    k = the segment index the Cartesian conversion uses for that s (bisect(knots, s) - 1), clamped to nx - 2;
+ *                    u = (s - knots[k]) / (knots[k+1] - knots[k]).
+ *   edges            L = left[k] + (left[k+1] - left[k]) * u, and R likewise from `right`.  A side whose two knot values are not both
+ *                    finite is unbounded on that segment and cannot be violated there: +-inf is how a caller says "no edge here".
+ *   half extent      r = hypot(s_d, d_d);  h = (veh_w / 2) |s_d| / r + (veh_l / 2) |d_d| / r, or veh_w / 2 when r == 0: the reach of
+ *                    the veh_l x veh_w rectangle along the frame normal, its heading taken relative to the line as atan2(d_d, s_d).
+ *                    The (1 - kappa d) factor of the exact heading is deliberately NOT applied.
+ *   violation        d + h + margin > L   or   d - h - margin < R.
+ *   the bit          FP_FLAG_BOUNDARY of the candidate's flag word is WRITTEN: set when any checked point violates, cleared otherwise
+ *                    (two calls with two corridors leave the second one's verdicts).  No other bit of the word changes and cost_tbl is
+ *                    never written.  The bit is independent of the other bits: it is evaluated for candidates that are already
+ *                    infeasible too, like the constraint bits.
+ *   best_idx / best_cost  [B] the argmin of cost_tbl over the candidates with no FP_FLAG_INFEASIBLE bit (which includes
+ *                    FP_FLAG_BOUNDARY) and a cost that is not NaN; the last minimum in FOP order wins exact ties (:263-268); -1 / NaN when
+ *                    there is none.  With w_obstacle > 0 the tables already hold the re-priced costs.  Bit for bit plane 0 of an
+ *                    fp_rank_feasible call on the masked tables (which honours the bit through FP_FLAG_INFEASIBLE).
+ *   n_masked         NULL or [B]: the candidates of the ego that carry the bit.
+ *   Stats            do not change (FOP counts every candidate regardless).
+ *   skipped egos     batch->skip[b] != 0: -1 / NaN / 0, the ego's rows are neither read nor written.
+ * The kernel's series arithmetic (fma Horner) rounds differently from a point-by-point restatement: a candidate whose footprint comes
+ * within ~FP_AUDIT_GAP_TOL of an edge may be decided either way by another rounding of the same numbers.
+ *
+ * FP_MEM_DEVICE: one kernel is enqueued (one workgroup per ego, in the order of batch->launch_order when there is one) - no
+ * allocation, no wait; it can be captured directly behind a dense call in a linear chain.  FP_MEM_HOST stages the tables and the
+ * corridor through the ctx and waits, like fp_rank_feasible.  Batch fields used: B, F, NX, nx, knots, frame_of, ego, d_samples,
+ * t_samples, v_samples, skip, launch_order.  Rows k >= nx[f] of left / right are ignored.
+ * Errors: a NULL mandatory pointer, margin negative or not finite, or (FP_MEM_HOST only) a NaN in a used row of left / right:
+ * FP_EINVAL; nd*nv*nt > FP_MAX_CAND: FP_ELIMIT.  (A NaN a FP_MEM_DEVICE caller leaves in a used row makes its segments unbounded.)
+ * Two calls on the same tables and corridor give the same bits.
+ * Also read-only in fp_ctx_get_option: "boundary_launches" = launches of the kernel on this ctx so far (0 for a caller that never asks:
+ * such a caller gets the bits and the launch counts it got before the symbol existed).
+ *
+ * Deliberately not done:
+ *   - fp_plan_step and the FISS entry points take no corridor.  A closed loop that wants the check enqueues fp_plan_dense ->
+ *     fp_boundary_mask -> fp_advance: the best_idx array is a valid argument of fp_advance (and fp_winner_trajs) as it stands.  FISS and
+ *     FISS+ order candidates by cost BEFORE validation; where a boundary verdict belongs in those walks is a separate decision.
+ *   - fp_shard_call has no slot for it. */
+typedef struct {
+    const double* left;    /* [F][NX] lateral offset (m, positive to the left) of the left road edge at every knot of the frame */
+    const double* right;   /* [F][NX] the right edge (normally negative) */
+    double margin;         /* extra distance kept from both edges, finite, >= 0 */
+} fp_corridor;
+
+int fp_boundary_mask(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, const fp_corridor* corridor, const double* cost_tbl,
+                     uint32_t* flag_tbl, int32_t* best_idx, double* best_cost, int32_t* n_masked, int mem, void* stream);
 
 /* Materialise the whole lattice: the full series of EVERY candidate of every ego, in FOP order
  *   traj [B][C][16][traj_stride] (traj_stride / traj_sparse as in fp_result), flags [B][C] (N << 8 | M << 20 | FP_FLAG_TRUNCATED; the feasibility bits
