@@ -111,6 +111,11 @@ class ProblemBatch:
     bound_left: np.ndarray | None = None   # [F, NX]
     bound_right: np.ndarray | None = None  # [F, NX]
     bound_margin: float = 0.0              # extra distance kept from both edges (m)
+    # the obstacle tracks obs_pose can be predicted from on the device (fp_tracks, fp_obstacles_predict; DeviceBatch.predict): the
+    # model (FP_TRACK_*) and six numbers per obstacle column, and the frame the LANE tracks of every scene follow; None = no tracks
+    track_model: np.ndarray | None = None  # [S, n_obs] int32
+    track_state: np.ndarray | None = None  # [S, n_obs, 6]  LANE: s0, d, v, a, -, -   ARC: x, y, yaw, v, a, kappa
+    track_frame: np.ndarray | None = None  # [S] int32 (None with tracks: no scene has a LANE column)
     meta: dict = field(default_factory=dict)
 
     def __post_init__(self):
@@ -142,6 +147,14 @@ class ProblemBatch:
         if self.bound_left is not None:
             self.bound_left, self.bound_right = f8(self.bound_left), f8(self.bound_right)
             assert self.bound_left.shape == (self.F, self.NX) and self.bound_right.shape == (self.F, self.NX)
+        assert (self.track_model is None) == (self.track_state is None), "track_model and track_state come together"
+        assert self.track_frame is None or self.track_model is not None, "track_frame without tracks"
+        if self.track_model is not None:
+            self.track_model, self.track_state = i4(self.track_model), f8(self.track_state)
+            assert self.track_model.shape == (self.S, self.n_obs) and self.track_state.shape == (self.S, self.n_obs, 6)
+            if self.track_frame is not None:
+                self.track_frame = i4(self.track_frame)
+                assert self.track_frame.shape == (self.S,)
 
     B = property(lambda self: self.ego.shape[0])
     nd = property(lambda self: self.d_samples.shape[0])
@@ -162,12 +175,19 @@ class ProblemBatch:
     def take(self, egos, meta: dict | None = None) -> "ProblemBatch":
         """The sub-batch of the given egos (index array or slice, in that order); the frames / scenes they reference are re-indexed."""
         sel = egos if isinstance(egos, slice) else np.asarray(egos, dtype=np.int64)
-        fr, fi = np.unique(self.frame_of[sel], return_inverse=True)
         sc_all = self.scene_of[sel]
         sc, si = np.unique(sc_all[sc_all >= 0], return_inverse=True)
         scene_of = np.full(len(sc_all), -1, dtype=np.int32)
         scene_of[sc_all >= 0] = si
         keep_s = sc if sc.size else np.zeros(0, dtype=np.int64)
+        fr, fi = np.unique(self.frame_of[sel], return_inverse=True)
+        track_frame = None
+        if self.track_frame is not None:  # the frames the kept scenes' LANE tracks follow stay too (entries outside 0 .. F-1 stay as they are)
+            tf = self.track_frame[keep_s]
+            ok = (tf >= 0) & (tf < self.F)
+            fr = np.unique(np.concatenate([self.frame_of[sel], tf[ok]]))
+            fi = np.searchsorted(fr, self.frame_of[sel])
+            track_frame = np.where(ok, np.searchsorted(fr, np.where(ok, tf, fr[0] if fr.size else 0)), np.where(tf < 0, tf, np.iinfo(np.int32).max)).astype(np.int32)
         return ProblemBatch(
             d_samples=self.d_samples, t_samples=self.t_samples, v_samples=self.v_samples[sel],
             target_speed=self.target_speed[sel], ego=self.ego[sel], frame_of=fi, scene_of=scene_of,
@@ -183,6 +203,8 @@ class ProblemBatch:
             obs_nvert=None if self.obs_nvert is None else self.obs_nvert[keep_s],
             bound_left=None if self.bound_left is None else self.bound_left[fr],
             bound_right=None if self.bound_right is None else self.bound_right[fr], bound_margin=self.bound_margin,
+            track_model=None if self.track_model is None else self.track_model[keep_s],
+            track_state=None if self.track_state is None else self.track_state[keep_s], track_frame=track_frame,
             meta=dict(self.meta, **(meta or {})))
 
     def shard(self, rank: int, world: int) -> "ProblemBatch":
@@ -206,4 +228,8 @@ class ProblemBatch:
                 a = getattr(self, name)
                 h.update(name.encode()); h.update(str(a.shape).encode()); h.update(np.ascontiguousarray(a).tobytes())
             h.update(b"bound_margin"); h.update(np.float64(self.bound_margin).tobytes())
+        if self.track_model is not None:  # (batches without tracks keep their digests)
+            for name in ("track_model", "track_state") + (("track_frame",) if self.track_frame is not None else ()):
+                a = getattr(self, name)
+                h.update(name.encode()); h.update(str(a.shape).encode()); h.update(np.ascontiguousarray(a).tobytes())
         return h.hexdigest()

@@ -194,6 +194,7 @@ struct fp_ctx {
     int looplog_launches = 0;      // fp_ctx_get_option("looplog_launches"): launches of the loop-log kernel (fp_loop_record)
     int rank_launches = 0;         // fp_ctx_get_option("rank_launches"): launches of the ranking kernel (fp_rank_feasible)
     int boundary_launches = 0;     // fp_ctx_get_option("boundary_launches"): launches of the road-boundary kernel (fp_boundary_mask)
+    int predict_launches = 0;      // fp_ctx_get_option("predict_launches"): launches of the obstacle prediction kernel (fp_obstacles_predict)
     OrderSet order_lattice, order_refine;
     DeviceBuf idx_shadow;          // [B] device copy of best_idx for the winner kernel of a dense call (KernelArgs::idx_shadow)
     DeviceBuf epi_flags;           // [B] hand-over flags of the epilogue workgroups appended to a multi-round lattice launch (KernelArgs::epi_flag); zero between launches
@@ -1448,7 +1449,7 @@ int fp_ctx_get_option(fp_ctx* ctx, const char* name, int* value)
     const struct { const char* n; int v; } tab[] = {
         {"lattice_kernel", ctx->lattice_kernel}, {"lattice_split", ctx->lattice_split}, {"lattice_group", ctx->lattice_group}, {"lattice_tail", ctx->lattice_tail}, {"lattice_occupancy", ctx->lattice_occupancy}, {"resident_groups", ctx->resident_groups}, {"zero_copy_in", ctx->zero_copy_in}, {"stage_kernel", ctx->stage_kernel}, {"inline_inputs", ctx->inline_inputs}, {"lattice_order", ctx->lattice_order},
         {"refine_table_kb", ctx->refine_table_kb}, {"fiss_stages", ctx->fiss_stages}, {"fiss_jump", ctx->fiss_jump}, {"validate", ctx->validate}, {"lattice_winner", ctx->lattice_winner}, {"fiss_fused", ctx->fiss_fused}, {"appended_workgroups", ctx->appended_ok ? 1 : 0}, {"handover_failed", ctx->hand_err ? *(volatile int32_t*)ctx->hand_err : 0}, {"overlap", ctx->overlap}, {"overlapped_calls", ctx->overlapped_calls}, {"clearance_launches", ctx->clearance_launches + (ctx->twin ? ctx->twin->clearance_launches : 0)}, {"lattice_launches", ctx->lattice_launches + (ctx->twin ? ctx->twin->lattice_launches : 0)},
-        {"looplog_launches", ctx->looplog_launches}, {"rank_launches", ctx->rank_launches}, {"boundary_launches", ctx->boundary_launches}, {"lattice_ordered_launches", ctx->lattice_ordered_launches + (ctx->twin ? ctx->twin->lattice_ordered_launches : 0)},
+        {"looplog_launches", ctx->looplog_launches}, {"rank_launches", ctx->rank_launches}, {"boundary_launches", ctx->boundary_launches}, {"predict_launches", ctx->predict_launches}, {"lattice_ordered_launches", ctx->lattice_ordered_launches + (ctx->twin ? ctx->twin->lattice_ordered_launches : 0)},
         {"lattice_launches_2", (int)fp::lattice_launches_per_cu(0)}, {"lattice_launches_3", (int)fp::lattice_launches_per_cu(1)}, {"lattice_launches_4", (int)fp::lattice_launches_per_cu(2)}};
     for (const auto& t : tab)
         if (strcmp(name, t.n) == 0) { *value = t.v; return FP_OK; }
@@ -1689,6 +1690,92 @@ int fp_boundary_mask(fp_ctx* ctx, const fp_params* params, const fp_batch* batch
     a.n_masked = hs.out(n_masked, B);
     LAUNCH_TRY(fp::launch_boundary_mask(a, ctx->stream), "road-boundary kernel");
     ++ctx->boundary_launches;
+    return hs.fetch_out();
+}
+
+int fp_obstacles_predict(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, const fp_tracks* tracks, double* obs_pose,
+                         int32_t* final_time_step, int mem, void* stream)
+{
+    if (!ctx) return fail(FP_EINVAL, "ctx is NULL");
+    if (!params || !batch) return fail(FP_EINVAL, "fp_obstacles_predict: params / batch must not be NULL");
+    if (mem != FP_MEM_HOST && mem != FP_MEM_DEVICE) return fail(FP_EINVAL, "mem must be FP_MEM_HOST or FP_MEM_DEVICE");
+    if (!tracks || !tracks->model || !tracks->state || !tracks->t0 || !obs_pose)
+        return fail(FP_EINVAL, "fp_obstacles_predict: tracks / model / state / t0 / obs_pose must not be NULL");
+    if (tracks->n_rows <= 0) return fail(FP_EINVAL, "fp_obstacles_predict: n_rows=%d must be > 0", tracks->n_rows);
+    if (!(params->tick_t > 0) || params->tick_t > 1.7976931348623157e308) return fail(FP_EINVAL, "fp_obstacles_predict: tick_t must be finite and > 0");
+    if (batch->S < 0 || batch->T_obs < 0 || batch->n_obs < 0 || batch->F < 0 || batch->NX < 0 || batch->NX > FP_MAX_KNOTS)
+        return fail(FP_EINVAL, "fp_obstacles_predict: bad batch sizes S=%d T_obs=%d n_obs=%d F=%d NX=%d", batch->S, batch->T_obs, batch->n_obs, batch->F, batch->NX);
+    // (the table may be an input of overlapped dense calls still in flight on the ctx's internal streams)
+    if (ctx->ov_pending[0] || ctx->ov_pending[1]) FP_TRY(overlap_join(ctx, mem == FP_MEM_DEVICE ? (hipStream_t)stream : ctx->stream));
+    if (batch->S == 0 || batch->T_obs == 0 || batch->n_obs == 0) return FP_OK;  // no element to write
+    HIP_TRY(hipSetDevice(ctx->device));
+    fp::PredictArgs a;
+    a.S = batch->S; a.T_obs = batch->T_obs; a.n_obs = batch->n_obs; a.F = batch->F; a.NX = batch->NX; a.n_rows = tracks->n_rows;
+    a.tick_t = params->tick_t;
+    if (mem == FP_MEM_DEVICE) {
+        if ((uintptr_t)obs_pose & 15u) return fail(FP_EINVAL, "fp_obstacles_predict: obs_pose must be 16-byte aligned");
+        a.nx = batch->nx; a.knots = batch->knots; a.coef = batch->coef;
+        a.model = tracks->model; a.state = tracks->state; a.frame_of_scene = tracks->frame_of_scene; a.t0 = tracks->t0;
+        a.obs_pose = obs_pose; a.final_time_step = final_time_step;
+        LAUNCH_TRY(fp::launch_obstacles_predict(a, (hipStream_t)stream), "obstacle prediction kernel");
+        ++ctx->predict_launches;
+        return FP_OK;
+    }
+    // host arrays: what the device path decides silently (such a column has no pose) is an error the host path can name
+    const size_t S = (size_t)batch->S, n = (size_t)batch->n_obs, fn = (size_t)batch->F * batch->NX;
+    bool any_lane = false;
+    for (size_t s = 0; s < S; ++s)
+        for (size_t j = 0; j < n; ++j) {
+            const int32_t m = tracks->model[s * n + j];
+            if (m < FP_TRACK_NONE || m > FP_TRACK_ARC) return fail(FP_EINVAL, "fp_obstacles_predict: model of scene %zu, column %zu is %d, not one of FP_TRACK_*", s, j, m);
+            if (m != FP_TRACK_LANE) continue;
+            any_lane = true;
+            if (!tracks->frame_of_scene || !batch->nx || !batch->knots || !batch->coef)
+                return fail(FP_EINVAL, "fp_obstacles_predict: scene %zu, column %zu is a LANE track but frame_of_scene / nx / knots / coef is NULL", s, j);
+            const int32_t f = tracks->frame_of_scene[s];
+            if (f < 0 || f >= batch->F) return fail(FP_EINVAL, "fp_obstacles_predict: scene %zu, column %zu is a LANE track on frame %d, outside 0 .. F-1 (F=%d)", s, j, f, batch->F);
+            if (batch->nx[f] < 2 || batch->nx[f] > batch->NX) return fail(FP_EINVAL, "fp_obstacles_predict: scene %zu, column %zu: nx[%d]=%d out of range", s, j, f, batch->nx[f]);
+        }
+    const size_t span = (size_t)(tracks->n_rows < batch->T_obs ? tracks->n_rows : batch->T_obs);
+    HostStage hs(ctx);
+    FP_TRY(hs.reserve(HostStage::need<int32_t>(S * n) + HostStage::need<double>(S * n * 6) + 3 * HostStage::need<int32_t>(S) + HostStage::need<int32_t>(batch->F) +
+                      HostStage::need<double>(fn) + HostStage::need<double>(fn * 8) + HostStage::need<double>(S * span * n * 4)));
+    FP_TRY(hs.in(tracks->model, S * n, &a.model));
+    FP_TRY(hs.in(tracks->state, S * n * 6, &a.state));
+    FP_TRY(hs.in(tracks->t0, S, &a.t0));
+    if (any_lane) {  // (only then are the frames read)
+        FP_TRY(hs.in(tracks->frame_of_scene, S, &a.frame_of_scene));
+        FP_TRY(hs.in(batch->nx, (size_t)batch->F, &a.nx));
+        FP_TRY(hs.in(batch->knots, fn, &a.knots));
+        FP_TRY(hs.in(batch->coef, fn * 8, &a.coef));
+    }
+    FP_TRY(hs.flush_in());
+    a.final_time_step = hs.out(final_time_step, S);
+    a.obs_pose = hs.temp<double>(S * span * n * 4);  // [S][span][n_obs][4]: a scene's written rows from its row 0 on
+    a.compact = 1;
+    LAUNCH_TRY(fp::launch_obstacles_predict(a, ctx->stream), "obstacle prediction kernel");
+    ++ctx->predict_launches;
+    // only the written rows travel back; runs that are contiguous on both sides (whole tables) go as one copy
+    const double* src = nullptr;
+    double* dst = nullptr;
+    size_t run = 0;
+    for (size_t s = 0; s < S; ++s) {
+        const long t0 = tracks->t0[s];
+        const long rlo = t0 > 0 ? t0 : 0;
+        long rhi = t0 + tracks->n_rows;
+        if (rhi > batch->T_obs) rhi = batch->T_obs;
+        if (rhi <= rlo) continue;
+        const double* sc_src = a.obs_pose + s * span * n * 4;
+        double* sc_dst = obs_pose + (s * (size_t)batch->T_obs + (size_t)rlo) * n * 4;
+        const size_t count = (size_t)(rhi - rlo) * n * 4;
+        if (run && sc_src == src + run && sc_dst == dst + run) {
+            run += count;
+            continue;
+        }
+        if (run) HIP_TRY(hipMemcpyAsync(dst, src, run * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        src = sc_src; dst = sc_dst; run = count;
+    }
+    if (run) HIP_TRY(hipMemcpyAsync(dst, src, run * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     return hs.fetch_out();
 }
 

@@ -224,6 +224,25 @@ struct BoundaryArgs {
     int32_t* n_masked = nullptr;
 };
 hipError_t launch_boundary_mask(const BoundaryArgs& a, hipStream_t stream);
+// The obstacle pose table from tracks (frenet_predict.hip, fp_obstacles_predict): rows max(t0, 0) .. min(T_obs, t0 + n_rows) - 1 of
+// every scene of obs_pose [S][T_obs][n_obs][4].  Device addresses; nx / knots / coef / frame_of_scene may be NULL (LANE columns then
+// have no pose).  compact: the output is [S][span][n_obs][4], span = min(T_obs, n_rows), and a scene's first written row lands in
+// its row 0 (what a host call reads back).  span, rows_per_slab, n_slabs and stage_tracks are filled in by the launcher.
+struct PredictArgs {
+    int S = 0, T_obs = 0, n_obs = 0, F = 0, NX = 0, n_rows = 0, compact = 0;
+    int span = 0, rows_per_slab = 0, n_slabs = 0, stage_tracks = 0;
+    double tick_t = 0.0;
+    const int32_t* nx = nullptr;
+    const double* knots = nullptr;
+    const double* coef = nullptr;
+    const int32_t* model = nullptr;
+    const double* state = nullptr;
+    const int32_t* frame_of_scene = nullptr;
+    const int32_t* t0 = nullptr;
+    double* obs_pose = nullptr;
+    int32_t* final_time_step = nullptr;
+};
+hipError_t launch_obstacles_predict(PredictArgs a, hipStream_t stream);
 // Series of EVERY lattice candidate: ka.r.best_traj [B*C][16][traj_stride], ka.r.best_flags [B*C] (N, M, truncated).
 hipError_t launch_materialize_all(const KernelArgs& ka, hipStream_t stream);
 hipError_t launch_eval_trajs(const KernelArgs& ka, int K, const double* end_states, double* cost, uint32_t* flags, double* traj,

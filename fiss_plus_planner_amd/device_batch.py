@@ -32,13 +32,29 @@ class DeviceBatch:
         self.host = batch
         self.dev = torch.device("cuda", device)
         self.t = {k: torch.from_numpy(np.ascontiguousarray(getattr(batch, k))).to(self.dev) for k in _NAMES}
-        for k in ("samp_min", "samp_max", "samp_res", "obs_poly", "obs_nvert", "bound_left", "bound_right"):  # (the corridor: boundary_mask_device)
+        for k in ("samp_min", "samp_max", "samp_res", "obs_poly", "obs_nvert", "bound_left", "bound_right",  # (the corridor: boundary_mask_device)
+                  "track_model", "track_state", "track_frame"):  # (the obstacle tracks: predict)
             if getattr(batch, k, None) is not None:
                 self.t[k] = torch.from_numpy(getattr(batch, k)).to(self.dev)
         if order_hint and batch.B > 0:
             self.t["launch_order"] = torch.from_numpy(launch_order_hint(batch)).to(self.dev)
         self.params = make_params(batch)
         self.fb = device_batch(batch, {k: (v.data_ptr() if v.numel() else 0) for k, v in self.t.items() if k in _NAMES + ("obs_poly", "obs_nvert", "launch_order")})
+
+    def predict(self, engine: FrenetEngine, t0, n_rows: int, stream: int = 0):
+        """Rewrite the resident obs_pose / final_time_step in place from the batch's tracks (fp_obstacles_predict, one launch enqueued
+        on `stream`): rows max(t0, 0) .. min(T_obs, t0 + n_rows) - 1 of every scene.  t0: a device int32 tensor [S] - the absolute
+        time step the track states are valid at; it is read when the kernel runs, like t["track_state"] / t["track_model"], which a
+        caller that re-perceives updates in place between calls."""
+        if "track_model" not in self.t:
+            raise ValueError("DeviceBatch.predict: the batch carries no tracks (ProblemBatch.track_model / track_state)")
+        if not (t0.is_cuda and t0.dtype == self.torch.int32 and tuple(t0.shape) == (self.host.S,) and t0.is_contiguous()):
+            raise ValueError(f"DeviceBatch.predict: t0 must be a contiguous device int32 tensor of shape ({self.host.S},)")
+        if self.host.S == 0 or self.host.n_obs == 0:
+            return
+        tr = _abi.FpTracks(self.t["track_model"].data_ptr(), self.t["track_state"].data_ptr(),
+                           self.t["track_frame"].data_ptr() if "track_frame" in self.t else None, t0.data_ptr(), int(n_rows))
+        engine.predict_obstacles_device(self.params, self.fb, tr, self.t["obs_pose"].data_ptr(), self.t["final_time_step"].data_ptr(), stream)
 
     def empty(self, shape, dtype):
         return self.torch.empty(shape, dtype=dtype, device=self.dev)

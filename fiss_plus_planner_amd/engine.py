@@ -353,6 +353,51 @@ class FrenetEngine:
         _abi.check(self._lib.fp_boundary_mask(self._ctx, C.byref(params), C.byref(fb), C.byref(cor), cost_tbl or None, flag_tbl or None, best_idx or None,
                                               best_cost or None, n_masked or None, _abi.FP_MEM_DEVICE, stream or None))
 
+    def predict_obstacles(self, batch, model, state, frame_of_scene=None, t0=0, n_rows: int | None = None, out: np.ndarray | None = None):
+        """The obstacle pose table of `batch` predicted from tracks (fp_obstacles_predict through FP_MEM_HOST; the definition:
+        include/frenet_gpu.h): model [S, n_obs] FP_TRACK_*, state [S, n_obs, 6], frame_of_scene [S] or None, t0 an int or [S],
+        n_rows (default: T_obs) -> (obs_pose [S, T_obs, n_obs, 4], final_time_step [S]).  Of `batch` only S, T_obs, n_obs, the frames
+        (nx, knots, coef) and tick_t are read - any object that carries them will do; its obs_pose is not read.  Rows outside
+        max(t0, 0) .. min(T_obs, t0 + n_rows) - 1 are not written: they keep the content of `out` (a contiguous float64 array of the
+        table's shape, returned as obs_pose) or, without one, zeros (= no obstacle has a pose there)."""
+        S, T_obs, n_obs = int(batch.S), int(batch.T_obs), int(batch.n_obs)
+        model = np.ascontiguousarray(model, dtype=np.int32)
+        state = np.ascontiguousarray(state, dtype=np.float64)
+        if model.shape != (S, n_obs) or state.shape != (S, n_obs, 6):
+            raise ValueError(f"predict_obstacles: model / state must be [S={S}, n_obs={n_obs}] / [S, n_obs, 6], got {model.shape} / {state.shape}")
+        t0 = np.ascontiguousarray(np.broadcast_to(np.asarray(t0, dtype=np.int32), (S,)))
+        if frame_of_scene is not None:
+            frame_of_scene = np.ascontiguousarray(frame_of_scene, dtype=np.int32)
+            if frame_of_scene.shape != (S,):
+                raise ValueError(f"predict_obstacles: frame_of_scene must be [S={S}], got {frame_of_scene.shape}")
+        if out is None:
+            out = np.zeros((S, T_obs, n_obs, 4))
+        elif not (isinstance(out, np.ndarray) and out.dtype == np.float64 and out.shape == (S, T_obs, n_obs, 4) and out.flags.c_contiguous and out.flags.writeable):
+            raise ValueError(f"predict_obstacles: out must be a writable C-contiguous float64 array of shape {(S, T_obs, n_obs, 4)}")
+        fts = np.zeros(S, dtype=np.int32)
+        nx = np.ascontiguousarray(batch.nx, dtype=np.int32)
+        knots = np.ascontiguousarray(batch.knots, dtype=np.float64)
+        coef = np.ascontiguousarray(batch.coef, dtype=np.float64)
+        p = _abi.FpParams()
+        p.tick_t = float(batch.tick_t)
+        fb = _abi.FpBatch()
+        fb.S, fb.T_obs, fb.n_obs, fb.F, fb.NX = S, T_obs, n_obs, int(knots.shape[0]), int(knots.shape[1]) if knots.ndim == 2 else 0
+        if knots.size:
+            fb.nx, fb.knots, fb.coef = _ptr(nx), _ptr(knots), _ptr(coef)
+        tr = _abi.FpTracks(_ptr(model) if model.size else None, _ptr(state) if state.size else None,
+                           None if frame_of_scene is None else _ptr(frame_of_scene), _ptr(t0) if t0.size else None, int(T_obs if n_rows is None else n_rows))
+        if S == 0 or n_obs == 0 or T_obs == 0:
+            return out, fts
+        _abi.check(self._lib.fp_obstacles_predict(self._ctx, C.byref(p), C.byref(fb), C.byref(tr), _ptr(out), _ptr(fts), _abi.FP_MEM_HOST, None))
+        return out, fts
+
+    def predict_obstacles_device(self, params: _abi.FpParams, fb: _abi.FpBatch, ftracks: _abi.FpTracks, obs_pose_ptr: int, fts_ptr: int = 0, stream: int = 0):
+        """Enqueue the prediction kernel (device addresses in fb / ftracks; obs_pose_ptr [S][T_obs][n_obs][4], 16-byte aligned,
+        fts_ptr [S] or 0): one launch, nothing allocated, nothing waited for.  model / state / t0 are read when the kernel runs, so a
+        captured call replays against whatever the tracks hold then."""
+        _abi.check(self._lib.fp_obstacles_predict(self._ctx, C.byref(params), C.byref(fb), C.byref(ftracks), obs_pose_ptr or None, fts_ptr or None,
+                                                  _abi.FP_MEM_DEVICE, stream or None))
+
     def plan_fopplus(self, batch: ProblemBatch, winner: bool = False, traj_stride: int = TRAJ_STRIDE, traj_sparse: bool = False):
         """FopPlusPlanner.plan() for every ego of the batch (fop_plus_planner.py:16-41) on the device: the cheapest feasible
         candidate + Stats = how many candidates the cost-ordered lazy validation pops before it.  Egos whose outcome hangs on an

@@ -14,6 +14,7 @@ bound, :173-176), so T_obs = final_time_step rows are enough.
 from __future__ import annotations
 
 from dataclasses import dataclass
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -72,6 +73,87 @@ class ObstacleTable:
                              "(a new pose table with another column count needs new rings too)")
         self.version += 1
         return self
+
+
+TRACK_NONE, TRACK_LANE, TRACK_ARC = 0, 1, 2  # FP_TRACK_* (include/frenet_gpu.h)
+
+
+@dataclass
+class ObstacleTracks:
+    """What a tracker knows about the obstacles of one scene - a motion model and six numbers per obstacle column - instead of a pose
+    table: the table is predicted from them on the device (fp_obstacles_predict; the definition: include/frenet_gpu.h).
+
+        TRACK_LANE  state = s0, d, v, a, -, -          along the planner's reference line at the lateral offset d
+        TRACK_ARC   state = x, y, yaw, v, a, kappa     Cartesian, constant path curvature and acceleration
+        TRACK_NONE  the column has no pose
+
+    A planner that is handed the tracks predicts the table against its own frame from `time_step_now` and keeps it until the tracks
+    change: like ObstacleTable the arrays are FROZEN while a planner holds them and ``update(...)`` swaps them and bumps ``version``."""
+    model: np.ndarray          # [n_obs] int32
+    state: np.ndarray          # [n_obs, 6]
+    dims: np.ndarray           # [n_obs, 2] length, width
+    poly: np.ndarray | None = None    # [n_obs, PV, 2] (ObstacleTable.poly)
+    nvert: np.ndarray | None = None   # [n_obs] int32
+    version: int = 0           # bumped by update(); part of the planners' cache key
+
+    def __post_init__(self):
+        self.model = np.array(self.model, dtype=np.int32, order="C")
+        self.state = np.array(self.state, dtype=np.float64, order="C")
+        self.dims = np.array(self.dims, dtype=np.float64, order="C")
+        if (self.poly is None) != (self.nvert is None):
+            raise ValueError("ObstacleTracks: poly and nvert come together (the rings and their vertex counts)")
+        if self.nvert is not None:
+            self.poly, self.nvert = np.array(self.poly, dtype=np.float64, order="C"), np.array(self.nvert, dtype=np.int32, order="C")
+        self._validate("ObstacleTracks")
+
+    def _validate(self, who: str) -> None:
+        n = self.model.shape[0] if self.model.ndim == 1 else -1
+        if self.model.ndim != 1 or self.state.shape != (n, 6) or self.dims.shape != (n, 2):
+            raise ValueError(f"{who}: model {self.model.shape} / state {self.state.shape} / dims {self.dims.shape} are not [n] / [n, 6] / [n, 2]")
+        if n and (int(self.model.min()) < TRACK_NONE or int(self.model.max()) > TRACK_ARC):
+            raise ValueError(f"{who}: model holds a value outside TRACK_NONE, TRACK_LANE, TRACK_ARC (0 .. 2)")
+        if self.nvert is not None and (self.nvert.shape != (n,) or self.poly.ndim != 3 or self.poly.shape[0] != n or self.poly.shape[2] != 2
+                                       or (self.nvert.size and int(self.nvert.max()) > self.poly.shape[1])):
+            raise ValueError(f"{who}: poly {self.poly.shape} / nvert {self.nvert.shape} do not match the {n} obstacle columns")
+
+    def freeze(self) -> None:
+        """Called by a planner when it caches the prediction: writes through these arrays raise from now on."""
+        for a in (self.model, self.state, self.dims) + (() if self.nvert is None else (self.poly, self.nvert)):
+            a.setflags(write=False)
+
+    def update(self, model=None, state=None, dims=None, poly=None, nvert=None) -> "ObstacleTracks":
+        """Replace (never edit) the arrays; every planner that cached a prediction of the old content predicts again on its next plan()."""
+        if (poly is None) != (nvert is None):
+            raise ValueError("ObstacleTracks.update: poly and nvert come together (the rings and their vertex counts)")
+        old = (self.model, self.state, self.dims, self.poly, self.nvert)
+        if model is not None:
+            self.model = np.array(model, dtype=np.int32, order="C")
+        if state is not None:
+            self.state = np.array(state, dtype=np.float64, order="C")
+        if dims is not None:
+            self.dims = np.array(dims, dtype=np.float64, order="C")
+        if nvert is not None:
+            self.poly, self.nvert = np.array(poly, dtype=np.float64, order="C"), np.array(nvert, dtype=np.int32, order="C")
+        try:
+            self._validate("ObstacleTracks.update")
+        except ValueError:
+            self.model, self.state, self.dims, self.poly, self.nvert = old
+            raise
+        self.version += 1
+        return self
+
+    def table(self, engine, knots, coef, tick_t: float, T_obs: int, t0: int = 0, n_rows: int | None = None) -> ObstacleTable:
+        """The pose table of these tracks: one fp_obstacles_predict call through FP_MEM_HOST on `engine` (a FrenetEngine) against the
+        reference line knots [nx] / coef [8, nx] (spline.CubicSpline2D.knots / .coef).  Rows max(t0, 0) .. min(T_obs, t0 + n_rows) - 1
+        hold the prediction - the states are valid at time step t0, n_rows defaults to T_obs -, every other row no pose;
+        final_time_step = min(T_obs, t0 + n_rows)."""
+        knots = np.ascontiguousarray(knots, dtype=np.float64).reshape(1, -1)
+        coef = np.ascontiguousarray(coef, dtype=np.float64).reshape(1, 8, knots.shape[1])
+        n = self.model.shape[0]
+        shape = SimpleNamespace(S=1, T_obs=int(T_obs), n_obs=n, nx=np.array([knots.shape[1]], dtype=np.int32), knots=knots, coef=coef, tick_t=float(tick_t))
+        pose, fts = engine.predict_obstacles(shape, self.model[None], self.state[None], np.zeros(1, dtype=np.int32), int(t0), n_rows)
+        return ObstacleTable(pose[0], self.dims.copy(), int(fts[0]), poly=None if self.nvert is None else self.poly.copy(),
+                             nvert=None if self.nvert is None else self.nvert.copy())
 
 
 def _ring(poly):

@@ -21,7 +21,7 @@ from . import _abi, search
 from .batch import FISS_KINDS, ProblemBatch
 from .engine import TRAJ_STRIDE, FrenetEngine, host_structs, unpack_flags
 from .frenet import FrenetState, FrenetTrajectory
-from .obstacles import ObstacleTable, flatten_obstacles, obstacles_fingerprint
+from .obstacles import ObstacleTable, ObstacleTracks, flatten_obstacles, obstacles_fingerprint
 from .spline import CubicSpline2D
 from .vehicle import Vehicle
 
@@ -185,9 +185,29 @@ class FrenetOptimalPlanner:
         self._boundary = (left, right, float(margin))
 
     # ------------------------------------------------------------------ problem marshalling
-    def _obstacle_table(self, obstacles) -> ObstacleTable | None:
+    def _predicted_table(self, tracks: ObstacleTracks, time_step_now: int) -> ObstacleTable:
+        """The pose table of an ObstacleTracks against this planner's own frame: the track states are valid at time_step_now and
+        ceil(max_t / tick_t) rows - the longest candidate - are predicted from there (ObstacleTracks.table, one fp_obstacles_predict
+        call); kept until the tracks, their version, the time step or the frame change."""
+        if self.cubic_spline is None:
+            raise RuntimeError("generate_frenet_frame() must be called before plan()")
+        st, sp = self.settings, self.cubic_spline
+        t_now = max(int(time_step_now), 0)
+        n_rows = max(int(np.ceil(st.max_t / st.tick_t)), 1)
+        key = (id(tracks), tracks.version, t_now, id(sp), st.tick_t, n_rows)
+        cache = getattr(self, "_tracks_cache", None)
+        if cache is None or cache[0] != key:
+            tab = tracks.table(self._engine, sp.knots, sp.coef, st.tick_t, t_now + n_rows, t0=t_now, n_rows=n_rows)
+            if self.cache_tables:
+                tracks.freeze()
+            cache = self._tracks_cache = (key, tab, tracks, sp)  # tracks / sp kept alive so their ids cannot be recycled
+        return cache[1]
+
+    def _obstacle_table(self, obstacles, time_step_now: int = 0) -> ObstacleTable | None:
         if isinstance(obstacles, ObstacleTable):
             return obstacles
+        if isinstance(obstacles, ObstacleTracks):
+            return self._predicted_table(obstacles, time_step_now) if len(obstacles.model) else None
         if obstacles is None or len(obstacles) == 0:
             return None  # has_collision: empty list -> no collision (:170-171)
         # The flattened table is reused only while the list holds the SAME obstacle objects (element identities + horizon); the
@@ -209,7 +229,7 @@ class FrenetOptimalPlanner:
         if self.cubic_spline is None:
             raise RuntimeError("generate_frenet_frame() must be called before plan()")
         st = self.settings
-        tab = self._obstacle_table(obstacles)
+        tab = self._obstacle_table(obstacles, time_step_now)
         sp = self.cubic_spline
         curv = (self.vehicle.max_curvature, self.vehicle.max_kappa_d, self.vehicle.max_kappa_dd) if getattr(st, "check_curvature", False) else None
         w_obs = float(getattr(st, "w_obstacle", 0.0))

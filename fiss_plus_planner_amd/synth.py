@@ -48,20 +48,10 @@ def sample_frames(knots, coef, s):
     return px.reshape(shp), py.reshape(shp), yaw.reshape(shp)
 
 
-def make_batch(B: int, nd: int, nv: int, nt: int, n_obs: int, T_obs: int, moving: bool, seed: int,
-               kind: str = "FOP", vehicle: Vehicle | None = None, max_target_speed: float = 13.5,
-               ego_offset: int = 0, layout: str = "lanes", n_knots: int = 81) -> ProblemBatch:
-    """B egos, each with its own 81-knot centerline and its own n_obs-rectangle scene.
-
-    ego_offset lets a rank generate only its shard [ego_offset, ego_offset+B) of a larger batch:
-    every ego draws from its own child stream SeedSequence(seed).spawn-like key (seed, index).
-    layout: "lanes" (module docstring; the bench default) or "survey8d" = SURVEY.md section 8d verbatim: every obstacle
-    at s_o = s + U(8, 120), d_o ~ U(-4, 4), speed U(0, 12) when moving.
-    """
+def _draw_scenes(B: int, n_obs: int, moving: bool, seed: int, ego_offset: int, layout: str, NX: int):
+    """The one draw loop behind make_batch and make_tracks (both consume the RNG streams identically): centerline points [B, NX, 2],
+    ego states [B, 6], obstacle dims [B, n, 2] and the obstacles' arclength so, lateral offset do and speed vo [B, n] at t = 0."""
     assert layout in ("lanes", "survey8d")
-    veh = vehicle or Vehicle()
-    st = default_settings(nd, nv, nt)
-    NX = int(n_knots)  # knots of every ego's reference line (the same 400 m road sampled finer or coarser; 81 = one knot per 5 m)
     pts = np.empty((B, NX, 2))
     ego = np.empty((B, 6))
     dims = np.empty((B, max(n_obs, 0), 2))
@@ -97,6 +87,23 @@ def make_batch(B: int, nd: int, nv: int, nt: int, n_obs: int, T_obs: int, moving
             so[b] = np.maximum(ego[b, 0] + np.where(in_lane, ahead_lane, ahead_side), 1.0)
             if moving:
                 vo[b] = rng.uniform(0, 10, n_obs)
+    return pts, ego, dims, so, do, vo
+
+
+def make_batch(B: int, nd: int, nv: int, nt: int, n_obs: int, T_obs: int, moving: bool, seed: int,
+               kind: str = "FOP", vehicle: Vehicle | None = None, max_target_speed: float = 13.5,
+               ego_offset: int = 0, layout: str = "lanes", n_knots: int = 81) -> ProblemBatch:
+    """B egos, each with its own 81-knot centerline and its own n_obs-rectangle scene.
+
+    ego_offset lets a rank generate only its shard [ego_offset, ego_offset+B) of a larger batch:
+    every ego draws from its own child stream SeedSequence(seed).spawn-like key (seed, index).
+    layout: "lanes" (module docstring; the bench default) or "survey8d" = SURVEY.md section 8d verbatim: every obstacle
+    at s_o = s + U(8, 120), d_o ~ U(-4, 4), speed U(0, 12) when moving.
+    """
+    veh = vehicle or Vehicle()
+    st = default_settings(nd, nv, nt)
+    NX = int(n_knots)  # knots of every ego's reference line (the same 400 m road sampled finer or coarser; 81 = one knot per 5 m)
+    pts, ego, dims, so, do, vo = _draw_scenes(B, n_obs, moving, seed, ego_offset, layout, NX)
     knots, coef = build_frames(pts)
     if n_obs > 0:
         tt = np.arange(T_obs) * st.tick_t
@@ -124,6 +131,20 @@ def make_batch(B: int, nd: int, nv: int, nt: int, n_obs: int, T_obs: int, moving
         obs_pose=pose, obs_dims=dims, final_time_step=fts, veh_l=veh.l, veh_w=veh.w, max_speed=veh.max_speed,
         max_accel=veh.max_accel, tick_t=st.tick_t, check_stride=2, samp_min=samp_min, samp_max=samp_max, samp_res=samp_res,
         meta=dict(seed=seed, kind=kind, moving=moving, ego_offset=ego_offset, layout=layout, **({"n_knots": NX} if NX != 81 else {})))
+
+
+def make_tracks(B: int, nd: int, nv: int, nt: int, n_obs: int, T_obs: int, moving: bool, seed: int,
+                kind: str = "FOP", vehicle: Vehicle | None = None, max_target_speed: float = 13.5,
+                ego_offset: int = 0, layout: str = "lanes", n_knots: int = 81) -> SimpleNamespace:
+    """The obstacle tracks whose prediction make_batch's obs_pose is (same arguments, same draws): every obstacle a LANE track
+    (FP_TRACK_LANE = 1) along its ego's own centre line - state = so, do, vo, a = 0 -, frame_of_scene = arange(B).
+    -> model [B, n_obs] int32, state [B, n_obs, 6], frame_of_scene [B] int32, dims [B, n_obs, 2]
+    (fp_obstacles_predict / ProblemBatch.track_model, track_state, track_frame)."""
+    _, _, dims, so, do, vo = _draw_scenes(B, n_obs, moving, seed, ego_offset, layout, int(n_knots))
+    n = max(n_obs, 0)
+    state = np.zeros((B, n, 6))
+    state[..., 0], state[..., 1], state[..., 2] = so, do, vo
+    return SimpleNamespace(model=np.ones((B, n), dtype=np.int32), state=state, frame_of_scene=np.arange(B, dtype=np.int32), dims=dims)
 
 
 def with_rectangle_rings(batch: ProblemBatch, seed: int, frac: float = 0.5, canonical: bool = True) -> ProblemBatch:

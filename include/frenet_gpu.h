@@ -314,7 +314,8 @@ int fp_ctx_destroy(fp_ctx* ctx);
 int fp_ctx_set_option(fp_ctx* ctx, const char* name, int value);
 /* Reads an option back, or one of the read-only counters "clearance_launches" (launches of the clearance rescoring kernel,
  * fp_params.w_obstacle > 0, of this ctx so far), "looplog_launches" (launches of fp_loop_record's kernel), "rank_launches" (launches of
- * fp_rank_feasible's kernel), "boundary_launches" (launches of fp_boundary_mask's kernel), "lattice_launches" (dense lattice launches of this ctx so far) and
+ * fp_rank_feasible's kernel), "boundary_launches" (launches of fp_boundary_mask's kernel), "predict_launches" (launches of
+ * fp_obstacles_predict's kernel), "lattice_launches" (dense lattice launches of this ctx so far) and
  * "lattice_ordered_launches" (those dispatched in a feedback order or in the order of fp_batch.launch_order) - bench.py reports when an
  * order took effect -, "lattice_launches_2" / "_3" / "_4" (PROCESS-wide: fused lattice launches so far by workgroups per compute unit). */
 int fp_ctx_get_option(fp_ctx* ctx, const char* name, int* value);
@@ -420,6 +421,61 @@ typedef struct {
 
 int fp_boundary_mask(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, const fp_corridor* corridor, const double* cost_tbl,
                      uint32_t* flag_tbl, int32_t* best_idx, double* best_cost, int32_t* n_masked, int mem, void* stream);
+
+/* ---- obstacle pose tables from tracks (added WITHIN ABI 18: detect it by looking the symbol up, e.g. dlsym) --------------
+ * The reference has no predictor: it reads CommonRoad's recorded trajectories through `state_at_time` and skips an obstacle that has no
+ * state at a step (frenet_optimal_planner.py:187-188).  A caller fed by a tracker has a few numbers per obstacle - position, heading,
+ * speed, acceleration, path curvature - and a prediction that changes every cycle; fp_obstacles_predict writes the rows of
+ * obs_pose [S][T_obs][n_obs][4] (x, y, yaw, valid) from those numbers on the device, so the table never crosses the link.
+ *
+ * The call reads params->tick_t and, from `batch`, S, T_obs, n_obs, F, NX, nx, knots, coef - nothing else; batch->obs_pose is NOT read
+ * (a caller normally passes the same address as `obs_pose`).
+ *
+ * Definition.  For scene s the rows r = max(t0[s], 0) .. min(T_obs, t0[s] + n_rows) - 1 are written, all n_obs columns, four doubles
+ * each; every other row of the scene is neither read nor written.
+ *   tau              = (r - t0[s]) * tick_t, computed as that product (the way the lattice forms t_i = i * tick_t).
+ *   final_time_step  [s] = min(T_obs, t0[s] + n_rows), clamped to 0 below; written when the pointer is not NULL.
+ *   travelled distance (both models)
+ *                    v0 = (v < 0) ? 0 : v  (a NaN speed stays NaN);   tau_e = (a < 0 and v0 / (-a) < tau) ? v0 / (-a) : tau  - a braking
+ *                    obstacle stops and never reverses -;   l = v0 * tau_e + 0.5 * a * tau_e * tau_e.
+ *   FP_TRACK_LANE    state = s0, d, v, a, -, -.   s = s0 + l;  k = bisect_right(knots, s) - 1 on frame frame_of_scene[scene], the segment
+ *                    the Cartesian conversion uses;  pose = P(s) + d * n(s),  n = (-P'_y, P'_x) / |P'|;  yaw = atan2(P'_y, P'_x);  valid = 1.
+ *                    The column is invalid at this row when s < knots[0], s >= knots[nx - 1], s or d is not finite, frame_of_scene is
+ *                    NULL, the frame index is outside 0 .. F - 1 (or the frame's tables are NULL / its nx outside 2 .. NX).
+ *   FP_TRACK_ARC     state = x0, y0, yaw0, v, a, kappa.   u = kappa * l / 2;  sinc = (|u| < 1e-4) ? 1 - u * u / 6 : sin(u) / u  (the
+ *                    truncation error is below 1e-17);  x = x0 + l * sinc * cos(yaw0 + u);  y = y0 + l * sinc * sin(yaw0 + u);
+ *                    yaw = yaw0 + kappa * l, not wrapped;  valid = 1.  This is the exact chord of a circular arc of length l, for any
+ *                    speed profile.  Any state entry that is not finite makes the column invalid.
+ *   invalid element  written as 0, 0, 0, 0 - what "no state at that step" means to every kernel.  FP_TRACK_NONE is invalid in every
+ *                    row; on FP_MEM_DEVICE so is a model value outside 0 .. 2.
+ * An element is a function of its track, its row and the frame alone: two runs, and the two memory spaces, give the same bits.
+ *
+ * FP_MEM_DEVICE: one kernel is enqueued - nothing is allocated and nothing waited for.  model, state, t0 (and the frames) are read on
+ * the device when the kernel runs, so a captured call replays against new tracks.  obs_pose must be 16-byte aligned.
+ * FP_MEM_HOST stages the inputs through the ctx like fp_winner_trajs, waits, and copies back only the written rows.
+ * Errors: FP_EINVAL for a NULL tracks / model / state / t0 / obs_pose, n_rows <= 0, tick_t not finite or not positive; on FP_MEM_HOST
+ * also - with a message that names the scene and the column - for a model outside 0 .. 2 and for a LANE track whose scene has no
+ * frame (frame_of_scene NULL or its entry outside 0 .. F - 1).  S, T_obs or n_obs of 0: nothing is written, FP_OK.
+ * Also read-only in fp_ctx_get_option: "predict_launches" = launches of the kernel on this ctx so far (0 for a caller that never
+ * asks: such a caller gets the bits and the launch counts it got before the symbol existed).
+ *
+ * Deliberately not done: fp_shard_call has no slot for it; the closed-loop entry points do not call it (a loop that re-perceives
+ * updates state / t0 on the device and enqueues this call in front of its plan step); a scene follows ONE line - there is no frame
+ * index per track. */
+#define FP_TRACK_NONE 0   /* the column has no pose in any written row */
+#define FP_TRACK_LANE 1   /* follows a reference line at a fixed lateral offset */
+#define FP_TRACK_ARC  2   /* Cartesian, constant path curvature, constant acceleration */
+
+typedef struct {
+    const int32_t* model;           /* [S][n_obs]     FP_TRACK_* */
+    const double*  state;           /* [S][n_obs][6]  LANE: s0, d, v, a, -, -    ARC: x, y, yaw, v, a, kappa */
+    const int32_t* frame_of_scene;  /* NULL or [S]    the frame LANE tracks of the scene follow */
+    const int32_t* t0;              /* [S]            absolute time step the states are valid at */
+    int32_t n_rows;                 /* rows written per scene, starting at row max(t0, 0) */
+} fp_tracks;
+
+int fp_obstacles_predict(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, const fp_tracks* tracks,
+                         double* obs_pose, int32_t* final_time_step, int mem, void* stream);
 
 /* Materialise the whole lattice: the full series of EVERY candidate of every ego, in FOP order
  *   traj [B][C][16][traj_stride] (traj_stride / traj_sparse as in fp_result), flags [B][C] (N << 8 | M << 20 | FP_FLAG_TRUNCATED; the feasibility bits
