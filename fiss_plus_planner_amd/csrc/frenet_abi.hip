@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "frenet_kernels.h"
+#include "frenet_stage_plan.h"
 
 // Toolchain pin.  The kernels were validated on ROCm 7.2.0's clang 22 (AMD clang 22.0.0git roc-7.2.0): no kernel may spill a VGPR
 // (tests/test_abi_cpu.py:test_no_kernel_spills_a_vgpr - this compiler's spill placement in divergent loop exits is wrong), the build
@@ -64,12 +65,11 @@ int fail(int code, const char* fmt, ...)
         if (_e != hipSuccess) return fail(FP_EHIP, what " launch failed: %s", hipGetErrorString(_e));   \
     } while (0)
 
-constexpr size_t kAlign = 256;
-constexpr size_t kSmallRegion = 4u << 20;  // device bytes mirrored by the pinned host block
-constexpr size_t kSmallMax = 64u << 10;    // arrays up to this size travel through the pinned block
-constexpr size_t kZeroCopyInMax = 256u << 10;  // latency regime: inputs the kernels read straight from the pinned block (all of a call's arrays together)
-
-inline size_t align_up(size_t v) { return (v + kAlign - 1) & ~(kAlign - 1); }
+using fp::align_up;
+using fp::kAlign;
+using fp::kSmallRegion;
+using fp::StageList;
+using fp::StageRegime;
 
 // grow-only device buffer
 struct DeviceBuf {
@@ -230,159 +230,71 @@ __global__ __launch_bounds__(256) void stage_copy_kernel(uint4* __restrict__ dst
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += gridDim.x * blockDim.x) dst[i] = src[i];
 }
 
-// One FP_MEM_HOST call: reserve(), in()/in_mut() for every input, flush_in(), out() for every output, launch kernels,
-// fetch_out().
+// One FP_MEM_HOST call: the entry point declares its arrays in a StageList (frenet_stage_plan.h), commit() places them, sizes the
+// arena from them and brings the inputs over, the kernels are launched, fetch_out() brings the outputs back.
 class HostStage {
   public:
     explicit HostStage(fp_ctx* ctx) : ctx_(ctx) {}
 
-    // zero_copy_out (latency regime, a handful of egos): small outputs are written by the kernels straight into the pinned
-    // host block (it is device-visible) - no D2H command at all after the launch, only the stream synchronisation.  Larger
-    // batches keep the outputs in HBM (kernels of the same call read each other's outputs) and fetch them with one copy.
-    // The same regime reads its INPUTS from the pinned block too (zero-copy in): the host's memcpy into the block is the whole
-    // transfer, the kernels fetch what they touch over the link (a few dependent reads, ~1 us more each than from HBM) - no copy
-    // command, no blit kernel, no gap behind them: a single-ego plan cycle is ~15 us shorter.  Only while the inputs of the call
-    // stay below kZeroCopyInMax bytes in total (a kernel re-reads parts of them; beyond that the copy engine wins).
-    int reserve(size_t large_bytes, bool zero_copy_out = false)
+    // The stream sees: the large inputs, one copy each in declaration order; then the window's flush.  Inputs the kernels address in the
+    // pinned block itself need neither.  `list` has to outlive fetch_out().  The default regime is the throughput one: no zero copy.
+    int commit(const StageList& list, const StageRegime& rg = StageRegime())
     {
-        FP_TRY(ctx_->arena.reserve(kSmallRegion + large_bytes + kAlign));
-        zero_copy_out_ = zero_copy_out;
-        zero_copy_in_ = zero_copy_out && ctx_->zero_copy_in == 2;
-        small_ = 0;
-        small_dirty_ = false;
-        large_ = kSmallRegion;
-        outs_.clear();
-        small_out_lo_ = small_out_hi_ = 0;
-        return FP_OK;
-    }
-    // bytes a `count`-element array may add to the large region
-    template <typename T>
-    static size_t need(size_t count) { return align_up(sizeof(T) * count) + kAlign; }
-    fp_ctx* ctx() const { return ctx_; }
-    bool latency() const { return zero_copy_out_; }
-    // (latency regime with the big tables resident on the device: the per-ego arrays that are left are a few hundred bytes - the
-    // kernels read them from the pinned block, one more microsecond in their first round of loads, and no copy is enqueued at all)
-    void small_inputs_only() { if (zero_copy_out_ && ctx_->zero_copy_in != 0) zero_copy_in_ = true; }
-
-    template <typename T>
-    int in(const T* host, size_t count, const T** dev)
-    {
-        const size_t bytes = sizeof(T) * count;
-        if (count == 0) { *dev = (const T*)(ctx_->arena.base + large_); return FP_OK; }
-        if (zero_copy_in_ && align_up(small_) + bytes <= kZeroCopyInMax) {
-            small_ = align_up(small_);
-            memcpy(ctx_->pinned + small_, host, bytes);
-            *dev = (const T*)(ctx_->pinned + small_);
-            small_ += bytes;
-            return FP_OK;
+        if (list.overflow()) return fail(FP_EHIP, "internal: a call staged %d arrays, the staging list holds %d", list.n, fp::kStageCap);
+        list_ = &list;
+        plan_ = fp::plan_stage(list, rg);
+        zero_copy_out_ = rg.zero_copy_out;
+        if (!fp::stage_plan_inside(list, plan_)) return fail(FP_EHIP, "internal: the staging plan places an array outside the arena it sized");
+        FP_TRY(ctx_->arena.reserve(plan_.arena_bytes));
+        for (int i = 0; i < list.n; ++i) {
+            const fp::StageItem& it = list.item[i];
+            *it.dev = addr(i);
+            if ((it.kind != fp::StageKind::IN && it.kind != fp::StageKind::IN_MUT) || it.bytes == 0) continue;
+            if (plan_.region[i] == fp::StageRegion::LARGE) HIP_TRY(hipMemcpyAsync(*it.dev, it.host, it.bytes, hipMemcpyHostToDevice, ctx_->stream));
+            else memcpy(ctx_->pinned + plan_.offset[i], it.host, it.bytes);
         }
-        if (zero_copy_in_) {  // does not fit the zero-copy window: its own copy (the mirrored window below is not flushed in this mode)
-            large_ = align_up(large_);
-            T* d = (T*)(ctx_->arena.base + large_);
-            large_ += bytes;
-            HIP_TRY(hipMemcpyAsync(d, host, bytes, hipMemcpyHostToDevice, ctx_->stream));
-            *dev = d;
-            return FP_OK;
-        }
-        // (latency regime: bigger arrays too - one transfer for the whole call instead of one more copy command per array)
-        if (bytes <= (zero_copy_out_ ? kZeroCopyInMax : kSmallMax) && align_up(small_) + bytes <= kSmallRegion) {
-            small_ = align_up(small_);
-            memcpy(ctx_->pinned + small_, host, bytes);
-            *dev = (const T*)(ctx_->arena.base + small_);
-            small_ += bytes;
-            small_dirty_ = true;  // the arena's copy of the window has to be brought up to date (flush_in)
-            return FP_OK;
-        }
-        large_ = align_up(large_);
-        T* d = (T*)(ctx_->arena.base + large_);
-        large_ += bytes;
-        HIP_TRY(hipMemcpyAsync(d, host, bytes, hipMemcpyHostToDevice, ctx_->stream));
-        *dev = d;
-        return FP_OK;
-    }
-    template <typename T>
-    int in_mut(T* host, size_t count, T** dev)  // in/out array: staged in, copied straight back by fetch_out
-    {
-        const size_t bytes = sizeof(T) * count;
-        if (zero_copy_out_ && count > 0 && bytes <= kSmallMax && align_up(small_) + bytes <= kSmallRegion) {
-            // latency regime: the kernels read and update the array in the pinned host block itself - no copy either way
-            small_ = align_up(small_);
-            memcpy(ctx_->pinned + small_, host, bytes);
-            *dev = (T*)(ctx_->pinned + small_);
-            outs_.push_back({host, small_, (char*)*dev, bytes, true});
-            small_ += bytes;
-            return FP_OK;
-        }
-        const T* c = nullptr;
-        FP_TRY(in((const T*)host, count, &c));
-        *dev = const_cast<T*>(c);
-        outs_.push_back({host, 0, (char*)*dev, bytes, false});
-        return FP_OK;
-    }
-    int flush_in()  // the output window of the small region starts after the inputs
-    {
-        if (small_ > 0 && small_dirty_ && !zero_copy_in_) {  // (arrays the kernels address in the pinned block itself need no mirror)
+        if (plan_.flush) {  // the arena's copy of the window has to be brought up to date
+            // Latency regime: by a copy kernel, see stage_copy_kernel
             if (zero_copy_out_ && ctx_->stage_kernel) {
-                const int n16 = (int)((small_ + 15) / 16);  // (both blocks are 256-byte aligned and kSmallRegion long)
+                const int n16 = (int)((plan_.small_in + 15) / 16);  // (both blocks are 256-byte aligned and kSmallRegion long)
                 const int blocks = (n16 + 255) / 256;
                 hipLaunchKernelGGL(stage_copy_kernel, dim3(blocks < 512 ? blocks : 512), dim3(256), 0, ctx_->stream, (uint4*)ctx_->arena.base, (const uint4*)ctx_->pinned, n16);
                 HIP_TRY(hipGetLastError());
             } else {
-                HIP_TRY(hipMemcpyAsync(ctx_->arena.base, ctx_->pinned, small_, hipMemcpyHostToDevice, ctx_->stream));
+                HIP_TRY(hipMemcpyAsync(ctx_->arena.base, ctx_->pinned, plan_.small_in, hipMemcpyHostToDevice, ctx_->stream));
             }
         }
-        small_out_lo_ = small_out_hi_ = align_up(small_);
         return FP_OK;
     }
-    template <typename T>
-    T* out(T* host, size_t count)
-    {
-        const size_t bytes = sizeof(T) * count;
-        if (!host || count == 0) return nullptr;
-        if (bytes <= kSmallMax && align_up(small_out_hi_) + bytes <= kSmallRegion) {
-            small_out_hi_ = align_up(small_out_hi_);
-            T* d = (T*)((zero_copy_out_ ? ctx_->pinned : ctx_->arena.base) + small_out_hi_);
-            outs_.push_back({host, small_out_hi_, (char*)d, bytes, true});
-            small_out_hi_ += bytes;
-            return d;
-        }
-        T* d = temp<T>(count);
-        outs_.push_back({host, 0, (char*)d, bytes, false});
-        return d;
-    }
-    template <typename T>
-    T* temp(size_t count)  // device-only scratch inside the arena
-    {
-        large_ = align_up(large_);
-        T* d = (T*)(ctx_->arena.base + large_);
-        large_ += sizeof(T) * count;
-        return d;
-    }
+    // One D2H copy for the output window (none when the kernels wrote the pinned block itself), one per output outside it, the
+    // stream's synchronisation, then the host's copies out of the pinned block.
     int fetch_out()
     {
-        if (small_out_hi_ > small_out_lo_ && !zero_copy_out_)
-            HIP_TRY(hipMemcpyAsync(ctx_->pinned + small_out_lo_, ctx_->arena.base + small_out_lo_, small_out_hi_ - small_out_lo_,
+        if (plan_.small_out_hi > plan_.small_out_lo && !zero_copy_out_)
+            HIP_TRY(hipMemcpyAsync(ctx_->pinned + plan_.small_out_lo, ctx_->arena.base + plan_.small_out_lo, plan_.small_out_hi - plan_.small_out_lo,
                                    hipMemcpyDeviceToHost, ctx_->stream));
-        for (const Out& o : outs_)
-            if (!o.via_pinned) HIP_TRY(hipMemcpyAsync(o.host, o.dev, o.bytes, hipMemcpyDeviceToHost, ctx_->stream));
+        for (int i = 0; i < list_->n; ++i)
+            if (returns(i) && !via_pinned(i)) HIP_TRY(hipMemcpyAsync(list_->item[i].host, addr(i), list_->item[i].bytes, hipMemcpyDeviceToHost, ctx_->stream));
         HIP_TRY(hipStreamSynchronize(ctx_->stream));
-        for (const Out& o : outs_)
-            if (o.via_pinned) memcpy(o.host, ctx_->pinned + o.small_off, o.bytes);
+        for (int i = 0; i < list_->n; ++i)
+            if (returns(i) && via_pinned(i)) memcpy(list_->item[i].host, ctx_->pinned + plan_.offset[i], list_->item[i].bytes);
         return FP_OK;
     }
 
   private:
-    struct Out {
-        void* host;
-        size_t small_off;  // offset in the small region (via_pinned)
-        char* dev;
-        size_t bytes;
-        bool via_pinned;
-    };
+    char* addr(int i) const
+    {
+        if (plan_.region[i] == fp::StageRegion::NONE) return nullptr;
+        return (plan_.region[i] == fp::StageRegion::PINNED ? ctx_->pinned : ctx_->arena.base) + plan_.offset[i];
+    }
+    bool returns(int i) const { return list_->item[i].kind == fp::StageKind::IN_MUT || (list_->item[i].kind == fp::StageKind::OUT && plan_.region[i] != fp::StageRegion::NONE); }
+    // (an in/out array of the window was copied in with it, but comes back by a copy of its own)
+    bool via_pinned(int i) const { return plan_.region[i] == fp::StageRegion::PINNED || (plan_.region[i] == fp::StageRegion::WINDOW && list_->item[i].kind == fp::StageKind::OUT); }
+
     fp_ctx* ctx_;
-    bool zero_copy_out_ = false, zero_copy_in_ = false, small_dirty_ = false;
-    size_t small_ = 0, large_ = 0, small_out_lo_ = 0, small_out_hi_ = 0;
-    std::vector<Out> outs_;
+    const StageList* list_ = nullptr;
+    fp::StagePlan plan_;
+    bool zero_copy_out_ = false;
 };
 
 int check_params(const fp_params* p)
@@ -446,16 +358,24 @@ int check_batch(const fp_batch* b)
     return FP_OK;
 }
 
-// Host-side validation of the index arrays (only possible for FP_MEM_HOST calls).
+// Host-side validation of the index arrays (only possible for FP_MEM_HOST calls): the frames the egos sit on ...
+int check_frames_host(const fp_batch* b)
+{
+    for (int i = 0; i < b->B; ++i)
+        if (b->frame_of[i] < 0 || b->frame_of[i] >= b->F) return fail(FP_EINVAL, "frame_of[%d]=%d out of range", i, b->frame_of[i]);
+    for (int f = 0; f < b->F; ++f)
+        if (b->nx[f] < 2 || b->nx[f] > b->NX) return fail(FP_EINVAL, "nx[%d]=%d out of range", f, b->nx[f]);
+    return FP_OK;
+}
+
+// ... and everything else a planning call reads
 int check_batch_host(const fp_params* p, const fp_batch* b)
 {
+    FP_TRY(check_frames_host(b));
     for (int i = 0; i < b->B; ++i) {
-        if (b->frame_of[i] < 0 || b->frame_of[i] >= b->F) return fail(FP_EINVAL, "frame_of[%d]=%d out of range", i, b->frame_of[i]);
         if (b->scene_of[i] >= b->S) return fail(FP_EINVAL, "scene_of[%d]=%d out of range", i, b->scene_of[i]);
         if (b->t_now[i] < 0) return fail(FP_EINVAL, "t_now[%d]=%d is negative", i, b->t_now[i]);
     }
-    for (int f = 0; f < b->F; ++f)
-        if (b->nx[f] < 2 || b->nx[f] > b->NX) return fail(FP_EINVAL, "nx[%d]=%d out of range", f, b->nx[f]);
     for (int k = 0; k < p->nt; ++k) {
         const double n = b->t_samples[k] / p->tick_t;
         if (!(n > 0) || n > FP_MAX_POINTS) return fail(FP_ELIMIT, "t_samples[%d]=%g needs more than FP_MAX_POINTS points", k, b->t_samples[k]);
@@ -493,20 +413,33 @@ int check_batch_host(const fp_params* p, const fp_batch* b)
     return FP_OK;
 }
 
-size_t batch_need(const fp_params* p, const fp_batch* b)
+// The lattice's sample arrays, as every kernel that walks the lattice reads them
+void stage_samples(StageList& sl, const fp_params* p, const fp_batch* b, const double** d_samples, const double** t_samples, const double** v_samples)
 {
-    const size_t B = (size_t)b->B, fn = (size_t)b->F * b->NX, so = (size_t)b->S * b->n_obs;
-    return HostStage::need<double>(p->nd) + HostStage::need<double>(p->nt) + HostStage::need<double>(B * p->nv) + HostStage::need<double>(B) +
-           HostStage::need<double>(B * 6) + 4 * HostStage::need<int32_t>(B) + HostStage::need<int32_t>(b->F) + HostStage::need<double>(fn) +
-           HostStage::need<double>(fn * 8) + HostStage::need<double>(so * b->T_obs * 4) + HostStage::need<double>(so * 2) +
-           HostStage::need<int32_t>(b->S) + (b->obs_nvert ? HostStage::need<double>(so * 2 * b->poly_stride) + HostStage::need<int32_t>(so) : 0);
+    sl.in(b->d_samples, (size_t)p->nd, d_samples);
+    sl.in(b->t_samples, (size_t)p->nt, t_samples);
+    sl.in(b->v_samples, (size_t)b->B * p->nv, v_samples);
 }
 
 // Inline inputs of a multi-kernel call (fp::InlineIn::publish): besides the eight per-ego arrays of the batch the blob carries
 // the call's other small inputs (`extra`), the lattice kernel copies it to a device mirror, and `dev_pub` / the extras' `dev`
-// get the mirror's addresses - what the kernels behind the lattice kernel read.
+// get the mirror's addresses - what the kernels behind the lattice kernel read.  The mirror is an item of the call's list like any
+// other: until commit() has placed it (InlineIn::publish), they hold offsets into it and inline_publish() turns them into addresses.
 struct InlineExtra { const void* src; size_t bytes; const void** dev; };
-int stage_batch(HostStage& hs, const fp_params* p, const fp_batch* b, fp_batch* dev, fp::InlineIn* inl = nullptr,
+template <typename T>
+void mirror_address(const T** field, const unsigned char* mirror) { *field = (const T*)(mirror + (size_t)*field); }
+void inline_publish(const fp::InlineIn& inl, fp_batch* dev_pub, const InlineExtra* extra, int n_extra)
+{
+    const unsigned char* mirror = (const unsigned char*)inl.publish;
+    mirror_address(&dev_pub->d_samples, mirror); mirror_address(&dev_pub->t_samples, mirror); mirror_address(&dev_pub->v_samples, mirror);
+    mirror_address(&dev_pub->target_speed, mirror); mirror_address(&dev_pub->ego, mirror); mirror_address(&dev_pub->frame_of, mirror);
+    mirror_address(&dev_pub->scene_of, mirror); mirror_address(&dev_pub->t_now, mirror);
+    for (int i = 0; i < n_extra; ++i) mirror_address(extra[i].dev, mirror);
+}
+
+// Appends the batch's arrays to the call's list (`dev` gets their device addresses at commit).  The tables of a tagged batch do not
+// use the arena: their upload, if one is due, is enqueued here - ahead of the call's other copies.
+int stage_batch(fp_ctx* ctx, StageList& sl, StageRegime& rg, const fp_params* p, const fp_batch* b, fp_batch* dev, fp::InlineIn* inl = nullptr,
                 fp_batch* dev_pub = nullptr, const InlineExtra* extra = nullptr, int n_extra = 0)
 {
     *dev = *b;
@@ -516,7 +449,6 @@ int stage_batch(HostStage& hs, const fp_params* p, const fp_batch* b, fp_batch* 
     bool tables_resident = false;
     if (b->tables_tag != 0) {
         // the frame / scene tables of a tagged call live in their own device buffer across calls (fp_batch.tables_tag)
-        fp_ctx* ctx = hs.ctx();
         const int key[7] = {b->tables_tag, b->F, b->NX, b->S, b->T_obs, has_obs ? b->n_obs : 0, has_poly ? b->poly_stride : 0};
         const void* src[8] = {b->nx, b->knots, b->coef, b->obs_pose, b->obs_dims, b->final_time_step, b->obs_poly, b->obs_nvert};
         const size_t bytes[8] = {sizeof(int32_t) * (size_t)b->F, sizeof(double) * (size_t)b->F * b->NX, sizeof(double) * (size_t)b->F * 8 * b->NX,
@@ -552,12 +484,12 @@ int stage_batch(HostStage& hs, const fp_params* p, const fp_batch* b, fp_batch* 
         dev->final_time_step = (const int32_t*)(tb + ts->off[5]);
         if (has_poly) { dev->obs_poly = (const double*)(tb + ts->off[6]); dev->obs_nvert = (const int32_t*)(tb + ts->off[7]); }
         tables_resident = true;
-        hs.small_inputs_only();
+        rg.small_inputs_only = true;
     }
-#define PUSH(field, count) FP_TRY(hs.in(b->field, (size_t)(count), &dev->field))
+#define PUSH(field, count) sl.in(b->field, (size_t)(count), &dev->field)
     // Inline inputs (fp::InlineIn): with the tables resident, what is left of a tiny batch fits the kernel's argument block
     bool inlined = false;
-    if (inl && tables_resident && hs.latency() && !b->skip) {
+    if (inl && tables_resident && rg.zero_copy_out && !b->skip) {
         const void* src[8] = {b->d_samples, b->t_samples, b->v_samples, b->target_speed, b->ego, b->frame_of, b->scene_of, b->t_now};
         const size_t bytes[8] = {sizeof(double) * (size_t)p->nd, sizeof(double) * (size_t)p->nt, sizeof(double) * (size_t)b->B * p->nv, sizeof(double) * (size_t)b->B,
                                  sizeof(double) * (size_t)b->B * 6, sizeof(int32_t) * (size_t)b->B, sizeof(int32_t) * (size_t)b->B, sizeof(int32_t) * (size_t)b->B};
@@ -572,28 +504,21 @@ int stage_batch(HostStage& hs, const fp_params* p, const fp_batch* b, fp_batch* 
             dev->scene_of = (const int32_t*)off[6]; dev->t_now = (const int32_t*)off[7];
             inl->on = 1;
             inlined = true;
-            if (dev_pub) {  // the device mirror the lattice kernel fills for the kernels behind it
-                const unsigned char* mirror = hs.temp<unsigned char>(fp::kInlineMax);
+            if (dev_pub) {  // the device mirror the lattice kernel fills for the kernels behind it (addresses: inline_publish)
+                sl.temp(fp::kInlineMax, (unsigned char**)&inl->publish);
                 *dev_pub = *dev;
-                dev_pub->d_samples = (const double*)(mirror + off[0]); dev_pub->t_samples = (const double*)(mirror + off[1]);
-                dev_pub->v_samples = (const double*)(mirror + off[2]); dev_pub->target_speed = (const double*)(mirror + off[3]);
-                dev_pub->ego = (const double*)(mirror + off[4]); dev_pub->frame_of = (const int32_t*)(mirror + off[5]);
-                dev_pub->scene_of = (const int32_t*)(mirror + off[6]); dev_pub->t_now = (const int32_t*)(mirror + off[7]);
                 size_t o = total;
                 for (int i = 0; i < n_extra; ++i) {
                     memcpy(inl->bytes + o, extra[i].src, extra[i].bytes);
-                    *extra[i].dev = mirror + o;
+                    *extra[i].dev = (const void*)o;
                     o += (extra[i].bytes + 7) & ~(size_t)7;
                 }
-                inl->publish = (void*)mirror;
                 inl->n8 = (int)((total_x + 7) / 8);
             }
         }
     }
     if (!inlined) {
-        PUSH(d_samples, p->nd);
-        PUSH(t_samples, p->nt);
-        PUSH(v_samples, (size_t)b->B * p->nv);
+        stage_samples(sl, p, b, &dev->d_samples, &dev->t_samples, &dev->v_samples);
         PUSH(target_speed, b->B);
         PUSH(ego, (size_t)b->B * 6);
         PUSH(frame_of, b->B);
@@ -1495,6 +1420,7 @@ static int plan_dense_impl(fp_ctx* ctx, const fp_params* params, const fp_batch*
     int32_t* fopplus = result->fopplus;
     uint32_t* audit = result->audit;
     HostStage hs(ctx);
+    StageList sl;
     fp::InlineIn inl;
     if (mem == FP_MEM_DEVICE) {
         ka.b = *batch;
@@ -1505,26 +1431,23 @@ static int plan_dense_impl(fp_ctx* ctx, const fp_params* params, const fp_batch*
         if (result->best_traj) FP_TRY(check_stride_host(params, batch, stride));
         ka.p.points_max = host_points_max(params, batch, nullptr, 0, 0);
         const size_t traj_doubles = result->best_traj ? B * FP_ARR_COUNT * (size_t)stride : 0;
-        FP_TRY(hs.reserve(batch_need(params, batch) + HostStage::need<int32_t>(B * 4) + 2 * HostStage::need<double>(B) + HostStage::need<int32_t>(B) +
-                          HostStage::need<double>(B * C) + HostStage::need<uint32_t>(B * C) + HostStage::need<uint32_t>(B) +
-                          HostStage::need<double>(traj_doubles) + HostStage::need<int32_t>(B * 2) + HostStage::need<uint32_t>(B),
-                          /*zero_copy_out=*/B <= 8));
+        StageRegime rg{/*zero_copy_out=*/B <= 8, ctx->zero_copy_in};
         // (inline inputs need the fused kernel with the winner's series inside it: no other kernel of this call may read the batch)
         const bool try_inline = ctx->inline_inputs && B <= 8 && !params->curvature_mask && ctx->lattice_kernel != 1 && !big_points(ka.p) && !clearance &&
                                 (!result->best_traj || winner_inside_lattice(ctx, batch)) && !result->audit && fp::lattice_group_fit(*params, *batch) >= 1;
-        FP_TRY(stage_batch(hs, params, batch, &ka.b, try_inline ? &inl : nullptr));
-        FP_TRY(hs.flush_in());
-        ka.r.best_idx = hs.out(result->best_idx, B);
-        ka.r.best_cost = hs.out(result->best_cost, B);
-        ka.r.stats = hs.out(result->stats, B * 4);
-        ka.r.cost_tbl = hs.out(result->cost_tbl, B * C);
-        ka.r.flag_tbl = hs.out(result->flag_tbl, B * C);
-        ka.r.best_flags = hs.out(result->best_flags, B);
-        ka.r.best_traj = hs.out(result->best_traj, traj_doubles);
+        FP_TRY(stage_batch(ctx, sl, rg, params, batch, &ka.b, try_inline ? &inl : nullptr));
+        sl.out(result->best_idx, B, &ka.r.best_idx);
+        sl.out(result->best_cost, B, &ka.r.best_cost);
+        sl.out(result->stats, B * 4, &ka.r.stats);
+        sl.out(result->cost_tbl, B * C, &ka.r.cost_tbl);
+        sl.out(result->flag_tbl, B * C, &ka.r.flag_tbl);
+        sl.out(result->best_flags, B, &ka.r.best_flags);
+        sl.out(result->best_traj, traj_doubles, &ka.r.best_traj);
         ka.r.traj_stride = result->traj_stride;
         ka.r.traj_sparse = result->traj_sparse;
-        fopplus = hs.out(result->fopplus, B * 2);
-        audit = hs.out(result->audit, B);
+        sl.out(result->fopplus, B * 2, &fopplus);
+        sl.out(result->audit, B, &audit);
+        FP_TRY(hs.commit(sl, rg));
         // sparse rows are only partly written by the kernels: the host block comes back with the caller's own bytes elsewhere
         if (result->traj_sparse && ka.r.best_traj) HIP_TRY(hipMemcpyAsync(ka.r.best_traj, result->best_traj, traj_doubles * sizeof(double), hipMemcpyDefault, st));
     }
@@ -1589,14 +1512,13 @@ int fp_winner_trajs(fp_ctx* ctx, const fp_params* params, const fp_batch* batch,
     for (size_t i = 0; i < B; ++i)
         if (best_idx[i] >= C) return fail(FP_EINVAL, "best_idx[%zu]=%d out of range", i, best_idx[i]);
     HostStage hs(ctx);
-    FP_TRY(hs.reserve(batch_need(params, batch) + HostStage::need<int32_t>(B) + HostStage::need<uint32_t>(B) + HostStage::need<double>(traj_doubles)));
-    FP_TRY(stage_batch(hs, params, batch, &ka.b));
-    const int32_t* d_idx = nullptr;
-    FP_TRY(hs.in(best_idx, B, &d_idx));
-    FP_TRY(hs.flush_in());
-    ka.r.best_idx = const_cast<int32_t*>(d_idx);
-    ka.r.best_flags = hs.out(best_flags, B);
-    ka.r.best_traj = hs.out(best_traj, traj_doubles);
+    StageList sl;
+    StageRegime rg;  // (throughput)
+    FP_TRY(stage_batch(ctx, sl, rg, params, batch, &ka.b));
+    sl.in(best_idx, B, &ka.r.best_idx);
+    sl.out(best_flags, B, &ka.r.best_flags);
+    sl.out(best_traj, traj_doubles, &ka.r.best_traj);
+    FP_TRY(hs.commit(sl, rg));
     if (traj_sparse) HIP_TRY(hipMemcpyAsync(ka.r.best_traj, best_traj, traj_doubles * sizeof(double), hipMemcpyDefault, ctx->stream));
     LAUNCH_TRY(fp::launch_winner_traj(ka, nullptr, ctx->stream), "winner epilogue");
     return hs.fetch_out();
@@ -1622,15 +1544,14 @@ int fp_rank_feasible(fp_ctx* ctx, const fp_params* params, const fp_batch* batch
     }
     // host arrays: only what the kernel reads travels (the two tables and skip)
     HostStage hs(ctx);
-    FP_TRY(hs.reserve(HostStage::need<double>(B * C) + HostStage::need<uint32_t>(B * C) + 2 * HostStage::need<int32_t>(B) +
-                      HostStage::need<int32_t>(B * K) + HostStage::need<double>(B * K)));
-    FP_TRY(hs.in(cost_tbl, B * C, &a.cost_tbl));
-    FP_TRY(hs.in(flag_tbl, B * C, &a.flag_tbl));
-    if (batch->skip) FP_TRY(hs.in(batch->skip, B, &a.skip));
-    FP_TRY(hs.flush_in());
-    a.rank_idx = hs.out(rank_idx, B * K);
-    a.rank_cost = hs.out(rank_cost, B * K);
-    a.n_feasible = hs.out(n_feasible, B);
+    StageList sl;
+    sl.in(cost_tbl, B * C, &a.cost_tbl);
+    sl.in(flag_tbl, B * C, &a.flag_tbl);
+    if (batch->skip) sl.in(batch->skip, B, &a.skip);
+    sl.out(rank_idx, B * K, &a.rank_idx);
+    sl.out(rank_cost, B * K, &a.rank_cost);
+    sl.out(n_feasible, B, &a.n_feasible);
+    FP_TRY(hs.commit(sl));
     LAUNCH_TRY(fp::launch_rank_feasible(a, ctx->stream), "ranking kernel");
     ++ctx->rank_launches;
     return hs.fetch_out();
@@ -1659,35 +1580,28 @@ int fp_boundary_mask(fp_ctx* ctx, const fp_params* params, const fp_batch* batch
         return FP_OK;
     }
     // host arrays: only what the kernel reads travels (the lattice samples, the ego states, the knots, the corridor and the two tables)
-    for (int i = 0; i < batch->B; ++i)
-        if (batch->frame_of[i] < 0 || batch->frame_of[i] >= batch->F) return fail(FP_EINVAL, "frame_of[%d]=%d out of range", i, batch->frame_of[i]);
-    for (int f = 0; f < batch->F; ++f) {
-        if (batch->nx[f] < 2 || batch->nx[f] > batch->NX) return fail(FP_EINVAL, "nx[%d]=%d out of range", f, batch->nx[f]);
+    FP_TRY(check_frames_host(batch));
+    for (int f = 0; f < batch->F; ++f)
         for (int k = 0; k < batch->nx[f]; ++k) {
             const double l = corridor->left[(size_t)f * batch->NX + k], r = corridor->right[(size_t)f * batch->NX + k];
             if (!(l == l) || !(r == r)) return fail(FP_EINVAL, "fp_boundary_mask: corridor has a NaN at frame %d, knot %d (+-inf says \"no edge\")", f, k);
         }
-    }
     HostStage hs(ctx);
-    FP_TRY(hs.reserve(HostStage::need<double>(params->nd) + HostStage::need<double>(params->nt) + HostStage::need<double>(B * params->nv) +
-                      HostStage::need<double>(B * 6) + 4 * HostStage::need<int32_t>(B) + HostStage::need<int32_t>(batch->F) + 3 * HostStage::need<double>(fn) +
-                      HostStage::need<double>(B * C) + HostStage::need<uint32_t>(B * C) + HostStage::need<double>(B)));
-    FP_TRY(hs.in(batch->d_samples, (size_t)params->nd, &a.d_samples));
-    FP_TRY(hs.in(batch->t_samples, (size_t)params->nt, &a.t_samples));
-    FP_TRY(hs.in(batch->v_samples, B * params->nv, &a.v_samples));
-    FP_TRY(hs.in(batch->ego, B * 6, &a.ego));
-    FP_TRY(hs.in(batch->frame_of, B, &a.frame_of));
-    FP_TRY(hs.in(batch->nx, (size_t)batch->F, &a.nx));
-    FP_TRY(hs.in(batch->knots, fn, &a.knots));
-    FP_TRY(hs.in(corridor->left, fn, &a.left));
-    FP_TRY(hs.in(corridor->right, fn, &a.right));
-    if (batch->skip) FP_TRY(hs.in(batch->skip, B, &a.skip));
-    FP_TRY(hs.in(cost_tbl, B * C, &a.cost_tbl));
-    FP_TRY(hs.in_mut(flag_tbl, B * C, &a.flag_tbl));
-    FP_TRY(hs.flush_in());
-    a.best_idx = hs.out(best_idx, B);
-    a.best_cost = hs.out(best_cost, B);
-    a.n_masked = hs.out(n_masked, B);
+    StageList sl;
+    stage_samples(sl, params, batch, &a.d_samples, &a.t_samples, &a.v_samples);
+    sl.in(batch->ego, B * 6, &a.ego);
+    sl.in(batch->frame_of, B, &a.frame_of);
+    sl.in(batch->nx, (size_t)batch->F, &a.nx);
+    sl.in(batch->knots, fn, &a.knots);
+    sl.in(corridor->left, fn, &a.left);
+    sl.in(corridor->right, fn, &a.right);
+    if (batch->skip) sl.in(batch->skip, B, &a.skip);
+    sl.in(cost_tbl, B * C, &a.cost_tbl);
+    sl.in_mut(flag_tbl, B * C, &a.flag_tbl);
+    sl.out(best_idx, B, &a.best_idx);
+    sl.out(best_cost, B, &a.best_cost);
+    sl.out(n_masked, B, &a.n_masked);
+    FP_TRY(hs.commit(sl));
     LAUNCH_TRY(fp::launch_boundary_mask(a, ctx->stream), "road-boundary kernel");
     ++ctx->boundary_launches;
     return hs.fetch_out();
@@ -1738,20 +1652,19 @@ int fp_obstacles_predict(fp_ctx* ctx, const fp_params* params, const fp_batch* b
         }
     const size_t span = (size_t)(tracks->n_rows < batch->T_obs ? tracks->n_rows : batch->T_obs);
     HostStage hs(ctx);
-    FP_TRY(hs.reserve(HostStage::need<int32_t>(S * n) + HostStage::need<double>(S * n * 6) + 3 * HostStage::need<int32_t>(S) + HostStage::need<int32_t>(batch->F) +
-                      HostStage::need<double>(fn) + HostStage::need<double>(fn * 8) + HostStage::need<double>(S * span * n * 4)));
-    FP_TRY(hs.in(tracks->model, S * n, &a.model));
-    FP_TRY(hs.in(tracks->state, S * n * 6, &a.state));
-    FP_TRY(hs.in(tracks->t0, S, &a.t0));
+    StageList sl;
+    sl.in(tracks->model, S * n, &a.model);
+    sl.in(tracks->state, S * n * 6, &a.state);
+    sl.in(tracks->t0, S, &a.t0);
     if (any_lane) {  // (only then are the frames read)
-        FP_TRY(hs.in(tracks->frame_of_scene, S, &a.frame_of_scene));
-        FP_TRY(hs.in(batch->nx, (size_t)batch->F, &a.nx));
-        FP_TRY(hs.in(batch->knots, fn, &a.knots));
-        FP_TRY(hs.in(batch->coef, fn * 8, &a.coef));
+        sl.in(tracks->frame_of_scene, S, &a.frame_of_scene);
+        sl.in(batch->nx, (size_t)batch->F, &a.nx);
+        sl.in(batch->knots, fn, &a.knots);
+        sl.in(batch->coef, fn * 8, &a.coef);
     }
-    FP_TRY(hs.flush_in());
-    a.final_time_step = hs.out(final_time_step, S);
-    a.obs_pose = hs.temp<double>(S * span * n * 4);  // [S][span][n_obs][4]: a scene's written rows from its row 0 on
+    sl.out(final_time_step, S, &a.final_time_step);
+    sl.temp(S * span * n * 4, &a.obs_pose);  // [S][span][n_obs][4]: a scene's written rows from its row 0 on
+    FP_TRY(hs.commit(sl));
     a.compact = 1;
     LAUNCH_TRY(fp::launch_obstacles_predict(a, ctx->stream), "obstacle prediction kernel");
     ++ctx->predict_launches;
@@ -1806,11 +1719,12 @@ int fp_materialize_all(fp_ctx* ctx, const fp_params* params, const fp_batch* bat
     FP_TRY(check_stride_host(params, batch, stride));
     ka.p.points_max = host_points_max(params, batch, nullptr, 0, 0);
     HostStage hs(ctx);
-    FP_TRY(hs.reserve(batch_need(params, batch) + HostStage::need<uint32_t>(BC) + HostStage::need<double>(traj_doubles)));
-    FP_TRY(stage_batch(hs, params, batch, &ka.b));
-    FP_TRY(hs.flush_in());
-    ka.r.best_flags = hs.out(flags, BC);
-    ka.r.best_traj = hs.out(traj, traj_doubles);
+    StageList sl;
+    StageRegime rg;  // (throughput)
+    FP_TRY(stage_batch(ctx, sl, rg, params, batch, &ka.b));
+    sl.out(flags, BC, &ka.r.best_flags);
+    sl.out(traj, traj_doubles, &ka.r.best_traj);
+    FP_TRY(hs.commit(sl, rg));
     if (traj_sparse) HIP_TRY(hipMemcpyAsync(ka.r.best_traj, traj, traj_doubles * sizeof(double), hipMemcpyDefault, ctx->stream));
     LAUNCH_TRY(fp::launch_materialize_all(ka, ctx->stream), "materialise kernel");
     return hs.fetch_out();
@@ -1872,6 +1786,7 @@ int plan_fiss_impl(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, 
     const size_t traj_doubles = io->best_traj ? B * FP_ARR_COUNT * (size_t)stride : 0;
     const size_t trace_doubles = (io->trace && R > 0) ? B * (size_t)R * 7 * 4 : 0;
     HostStage hs(ctx);
+    StageList sl;
     fp::InlineIn inl;   // (host entry, latency regime: see below)
     fp_batch lat_b;     // the batch as the lattice kernel addresses it (byte offsets into inl.bytes when inl.on)
     if (mem == FP_MEM_DEVICE) {
@@ -1891,10 +1806,7 @@ int plan_fiss_impl(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, 
                 if (ceil(io->samp_max[3 * i + 2] / params->tick_t) > stride) return fail(FP_EINVAL, "traj_stride=%d is smaller than the points of samp_max[%zu].T=%g", stride, i, io->samp_max[3 * i + 2]);
             FP_TRY(check_stride_host(params, batch, stride));
         }
-        FP_TRY(hs.reserve(batch_need(params, batch) + 4 * HostStage::need<double>(B * 3) + 2 * HostStage::need<int32_t>(B * 3) +
-                          HostStage::need<double>(B) + 2 * HostStage::need<int32_t>(B * 4) + HostStage::need<uint32_t>(B) +
-                          HostStage::need<double>(trace_doubles) + HostStage::need<double>(traj_doubles) + HostStage::need<unsigned char>(fp::kInlineMax),
-                          /*zero_copy_out=*/B <= 8));
+        StageRegime rg{/*zero_copy_out=*/B <= 8, ctx->zero_copy_in};
         // Latency regime with the tables resident (fp_batch.tables_tag): the per-ego arrays and the three sampling-range arrays ride
         // inside the lattice kernel's argument block, which also leaves them in a device mirror for the search and refinement
         // kernels - no copy kernel, no dependency in front of the lattice kernel (a single-ego FISS+ cycle: ~5 us of ~80).
@@ -1904,23 +1816,24 @@ int plan_fiss_impl(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, 
         const InlineExtra ex[3] = {{io->samp_min, sizeof(double) * B * 3, (const void**)&fa.io.samp_min},
                                    {io->samp_max, sizeof(double) * B * 3, (const void**)&fa.io.samp_max},
                                    {io->samp_res, sizeof(double) * B * 3, (const void**)&fa.io.samp_res}};
-        FP_TRY(stage_batch(hs, params, batch, &lat_b, try_inline ? &inl : nullptr, &fa.ka.b, ex, 3));
+        FP_TRY(stage_batch(ctx, sl, rg, params, batch, &lat_b, try_inline ? &inl : nullptr, &fa.ka.b, ex, 3));
         if (!inl.on) {
-            fa.ka.b = lat_b;
-            FP_TRY(hs.in(io->samp_min, B * 3, &fa.io.samp_min));
-            FP_TRY(hs.in(io->samp_max, B * 3, &fa.io.samp_max));
-            FP_TRY(hs.in(io->samp_res, B * 3, &fa.io.samp_res));
+            sl.in(io->samp_min, B * 3, &fa.io.samp_min);
+            sl.in(io->samp_max, B * 3, &fa.io.samp_max);
+            sl.in(io->samp_res, B * 3, &fa.io.samp_res);
         }
-        FP_TRY(hs.in_mut(io->prev_best_idx, B * 3, &fa.io.prev_best_idx));
-        FP_TRY(hs.flush_in());
-        fa.io.best_ijk = hs.out(io->best_ijk, B * 3);
-        fa.io.best_cost = hs.out(io->best_cost, B);
-        fa.io.end_state = hs.out(io->end_state, B * 3);
-        fa.io.refined = hs.out(io->refined, B);
-        fa.io.stats = hs.out(io->stats, B * 4);
-        fa.io.trace = trace_doubles ? hs.out(io->trace, trace_doubles) : nullptr;
-        fa.io.best_flags = hs.out(io->best_flags, B);
-        fa.io.best_traj = hs.out(io->best_traj, traj_doubles);
+        sl.in_mut(io->prev_best_idx, B * 3, &fa.io.prev_best_idx);
+        sl.out(io->best_ijk, B * 3, &fa.io.best_ijk);
+        sl.out(io->best_cost, B, &fa.io.best_cost);
+        sl.out(io->end_state, B * 3, &fa.io.end_state);
+        sl.out(io->refined, B, &fa.io.refined);
+        sl.out(io->stats, B * 4, &fa.io.stats);
+        sl.out(io->trace, trace_doubles, &fa.io.trace);
+        sl.out(io->best_flags, B, &fa.io.best_flags);
+        sl.out(io->best_traj, traj_doubles, &fa.io.best_traj);
+        FP_TRY(hs.commit(sl, rg));
+        if (inl.on) inline_publish(inl, &fa.ka.b, ex, 3);
+        else fa.ka.b = lat_b;
         if (io->traj_sparse && fa.io.best_traj) HIP_TRY(hipMemcpyAsync(fa.io.best_traj, io->best_traj, traj_doubles * sizeof(double), hipMemcpyDefault, ctx->stream));
     }
     // inline inputs: the lattice kernel reads the batch from its argument block (lat_b) - the fused kernel or nothing.  Else the FISS+
@@ -2021,29 +1934,28 @@ int fp_advance(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, cons
     }
     FP_TRY(check_batch_host(params, batch));
     HostStage hs(ctx);
-    const size_t goal_v = io->goal_poly && io->goal_max_vertices >= 3 ? (size_t)io->goal_max_vertices : 0;
-    FP_TRY(hs.reserve(batch_need(params, batch) + HostStage::need<double>(B * 6) + 5 * HostStage::need<int32_t>(B) + HostStage::need<double>(B * 2) +
-                      2 * HostStage::need<double>(B * 3) + HostStage::need<double>(B * goal_v * 2) + HostStage::need<double>(B * 6)));
-    FP_TRY(stage_batch(hs, params, batch, &ka.b));
+    StageList sl;
+    StageRegime rg;  // (throughput)
+    FP_TRY(stage_batch(ctx, sl, rg, params, batch, &ka.b));
     fp_loop_io dio = *io;
-    FP_TRY(hs.in_mut(io->ego, B * 6, &dio.ego));
-    FP_TRY(hs.in_mut(io->t_now, B, &dio.t_now));
-    FP_TRY(hs.in_mut(io->done, B, &dio.done));
-    FP_TRY(hs.in_mut(io->cycles, B, &dio.cycles));
-    FP_TRY(hs.in(io->goal_xy, B * 2, &dio.goal_xy));
+    sl.in_mut(io->ego, B * 6, &dio.ego);
+    sl.in_mut(io->t_now, B, &dio.t_now);
+    sl.in_mut(io->done, B, &dio.done);
+    sl.in_mut(io->cycles, B, &dio.cycles);
+    sl.in(io->goal_xy, B * 2, &dio.goal_xy);
     if (io->goal_poly && io->goal_nv && io->goal_max_vertices >= 3) {
-        FP_TRY(hs.in(io->goal_poly, B * (size_t)io->goal_max_vertices * 2, &dio.goal_poly));
-        FP_TRY(hs.in(io->goal_nv, B, &dio.goal_nv));
-        if (io->goal_intervals) FP_TRY(hs.in(io->goal_intervals, B * 6, &dio.goal_intervals));
+        sl.in(io->goal_poly, B * (size_t)io->goal_max_vertices * 2, &dio.goal_poly);
+        sl.in(io->goal_nv, B, &dio.goal_nv);
+        if (io->goal_intervals) sl.in(io->goal_intervals, B * 6, &dio.goal_intervals);
     } else {
         dio.goal_poly = nullptr;
     }
     const int32_t* d_idx = nullptr;
     const double* d_es = nullptr;
-    if (best_idx) FP_TRY(hs.in(best_idx, B, &d_idx));
-    if (end_state) FP_TRY(hs.in(end_state, B * 3, &d_es));
-    FP_TRY(hs.flush_in());
-    dio.cart_state = hs.out(io->cart_state, B * 3);
+    if (best_idx) sl.in(best_idx, B, &d_idx);
+    if (end_state) sl.in(end_state, B * 3, &d_es);
+    sl.out(io->cart_state, B * 3, &dio.cart_state);
+    FP_TRY(hs.commit(sl, rg));
     if (dio.cart_state) HIP_TRY(hipMemsetAsync(dio.cart_state, 0xFF, sizeof(double) * B * 3, ctx->stream));  // NaN for egos that do not move
     LAUNCH_TRY(fp::launch_advance(ka, d_idx, d_es, dio, ctx->stream), "advance kernel");
     return hs.fetch_out();
@@ -2079,36 +1991,27 @@ int fp_loop_record(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, 
     // host arrays: only what the kernel reads travels (the three sample arrays of the batch, the loop state, the step's results, the log)
     const size_t R = (size_t)log->max_rows;
     HostStage hs(ctx);
-    FP_TRY(hs.reserve(HostStage::need<double>(params->nd) + HostStage::need<double>(params->nt) + HostStage::need<double>(B * params->nv) +
-                      HostStage::need<double>(B * 6) + 6 * HostStage::need<int32_t>(B) + 2 * HostStage::need<double>(B * 3) + HostStage::need<double>(B) +
-                      HostStage::need<int32_t>(B * 4) + HostStage::need<double>(B * R * FP_LOG_COLS) + HostStage::need<int32_t>(B * R * 4) +
-                      HostStage::need<int64_t>(B * 4) + HostStage::need<int32_t>(1)));
-    FP_TRY(hs.in(batch->d_samples, (size_t)params->nd, &a.d_samples));
-    FP_TRY(hs.in(batch->v_samples, B * params->nv, &a.v_samples));
-    FP_TRY(hs.in(batch->t_samples, (size_t)params->nt, &a.t_samples));
-    fp_loop_io dio = *io;
-    fp_loop_log dlg = *log;
-    const double* c_ego = nullptr; const double* c_cart = nullptr; const int32_t* c_t = nullptr; const int32_t* c_done = nullptr; const int32_t* c_cyc = nullptr;
-    FP_TRY(hs.in((const double*)io->ego, B * 6, &c_ego));
-    FP_TRY(hs.in((const double*)io->cart_state, B * 3, &c_cart));
-    FP_TRY(hs.in((const int32_t*)io->t_now, B, &c_t));
-    FP_TRY(hs.in((const int32_t*)io->done, B, &c_done));
-    FP_TRY(hs.in((const int32_t*)io->cycles, B, &c_cyc));
-    dio.ego = const_cast<double*>(c_ego); dio.cart_state = const_cast<double*>(c_cart);
-    dio.t_now = const_cast<int32_t*>(c_t); dio.done = const_cast<int32_t*>(c_done); dio.cycles = const_cast<int32_t*>(c_cyc);
-    if (best_idx) FP_TRY(hs.in(best_idx, B, &a.best_idx));
-    if (end_state) FP_TRY(hs.in(end_state, B * 3, &a.end_state));
-    FP_TRY(hs.in(best_cost, B, &a.best_cost));
-    if (stats) FP_TRY(hs.in(stats, B * 4, &a.stats));
-    FP_TRY(hs.in_mut(log->rows, B * R * FP_LOG_COLS, &dlg.rows));
-    if (log->row_stats) FP_TRY(hs.in_mut(log->row_stats, B * R * 4, &dlg.row_stats));
-    FP_TRY(hs.in_mut(log->n_rows, B, &dlg.n_rows));
-    FP_TRY(hs.in_mut(log->sealed, B, &dlg.sealed));
-    if (log->stats_sum) FP_TRY(hs.in_mut(log->stats_sum, B * 4, &dlg.stats_sum));
-    FP_TRY(hs.flush_in());
-    dlg.n_running = hs.out(log->n_running, 1);
-    if (dlg.n_running) HIP_TRY(hipMemsetAsync(dlg.n_running, 0, sizeof(int32_t), ctx->stream));
-    a.io = dio; a.log = dlg;
+    StageList sl;
+    stage_samples(sl, params, batch, &a.d_samples, &a.t_samples, &a.v_samples);
+    a.io = *io;  // (the kernel only reads the loop state)
+    a.log = *log;
+    sl.in(io->ego, B * 6, &a.io.ego);
+    sl.in(io->cart_state, B * 3, &a.io.cart_state);
+    sl.in(io->t_now, B, &a.io.t_now);
+    sl.in(io->done, B, &a.io.done);
+    sl.in(io->cycles, B, &a.io.cycles);
+    if (best_idx) sl.in(best_idx, B, &a.best_idx);
+    if (end_state) sl.in(end_state, B * 3, &a.end_state);
+    sl.in(best_cost, B, &a.best_cost);
+    if (stats) sl.in(stats, B * 4, &a.stats);
+    sl.in_mut(log->rows, B * R * FP_LOG_COLS, &a.log.rows);
+    if (log->row_stats) sl.in_mut(log->row_stats, B * R * 4, &a.log.row_stats);
+    sl.in_mut(log->n_rows, B, &a.log.n_rows);
+    sl.in_mut(log->sealed, B, &a.log.sealed);
+    if (log->stats_sum) sl.in_mut(log->stats_sum, B * 4, &a.log.stats_sum);
+    sl.out(log->n_running, 1, &a.log.n_running);
+    FP_TRY(hs.commit(sl));
+    if (a.log.n_running) HIP_TRY(hipMemsetAsync(a.log.n_running, 0, sizeof(int32_t), ctx->stream));
     LAUNCH_TRY(fp::launch_loop_record(a, ctx->stream), "loop-log kernel");
     ++ctx->looplog_launches;
     return hs.fetch_out();
@@ -2175,14 +2078,16 @@ int fp_frames_build(fp_ctx* ctx, int32_t F, int32_t NX, const int32_t* n, const 
         if (n[f] < 2 || n[f] > NX) return fail(FP_EINVAL, "n[%d]=%d out of range", f, n[f]);
     const size_t fn = (size_t)F * NX;
     HostStage hs(ctx);
-    FP_TRY(hs.reserve(HostStage::need<int32_t>(F) + HostStage::need<double>(fn * 2) + HostStage::need<double>(fn) + HostStage::need<double>(fn * 8)));
+    StageList sl;
     const int32_t* d_n = nullptr;
     const double* d_pts = nullptr;
-    FP_TRY(hs.in(n, (size_t)F, &d_n));
-    FP_TRY(hs.in(points, fn * 2, &d_pts));
-    FP_TRY(hs.flush_in());
-    double* d_k = hs.out(knots, fn);
-    double* d_c = hs.out(coef, fn * 8);
+    double* d_k = nullptr;
+    double* d_c = nullptr;
+    sl.in(n, (size_t)F, &d_n);
+    sl.in(points, fn * 2, &d_pts);
+    sl.out(knots, fn, &d_k);
+    sl.out(coef, fn * 8, &d_c);
+    FP_TRY(hs.commit(sl));
     LAUNCH_TRY(fp::launch_frames_build(F, NX, d_n, d_pts, d_k, d_c, ctx->stream), "frame build");
     return hs.fetch_out();
 }
@@ -2201,20 +2106,19 @@ int fp_from_state(fp_ctx* ctx, const fp_batch* batch, const double* states, doub
         return FP_OK;
     }
     const size_t B = (size_t)batch->B, fn = (size_t)batch->F * batch->NX;
-    for (size_t i = 0; i < B; ++i)
-        if (batch->frame_of[i] < 0 || batch->frame_of[i] >= batch->F) return fail(FP_EINVAL, "frame_of[%zu] out of range", i);
+    FP_TRY(check_frames_host(batch));
     HostStage hs(ctx);
-    FP_TRY(hs.reserve(HostStage::need<int32_t>(B) + HostStage::need<int32_t>(batch->F) + HostStage::need<double>(fn) + HostStage::need<double>(fn * 8) +
-                      HostStage::need<double>(B * 4) + HostStage::need<double>(B * 6)));
+    StageList sl;
     fp_batch db = *batch;
-    FP_TRY(hs.in(batch->frame_of, B, &db.frame_of));
-    FP_TRY(hs.in(batch->nx, (size_t)batch->F, &db.nx));
-    FP_TRY(hs.in(batch->knots, fn, &db.knots));
-    FP_TRY(hs.in(batch->coef, fn * 8, &db.coef));
+    sl.in(batch->frame_of, B, &db.frame_of);
+    sl.in(batch->nx, (size_t)batch->F, &db.nx);
+    sl.in(batch->knots, fn, &db.knots);
+    sl.in(batch->coef, fn * 8, &db.coef);
     const double* d_states = nullptr;
-    FP_TRY(hs.in(states, B * 4, &d_states));
-    FP_TRY(hs.flush_in());
-    double* d_ego = hs.out(ego, B * 6);
+    double* d_ego = nullptr;
+    sl.in(states, B * 4, &d_states);
+    sl.out(ego, B * 6, &d_ego);
+    FP_TRY(hs.commit(sl));
     LAUNCH_TRY(fp::launch_from_state(db, d_states, d_ego, ctx->stream), "from_state");
     return hs.fetch_out();
 }
@@ -2248,15 +2152,18 @@ int fp_eval_trajs(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, i
     ka.p.points_max = host_points_max(params, batch, end_states + 2, BK, 3);
     const size_t traj_doubles = traj ? BK * FP_ARR_COUNT * (size_t)stride : 0;
     HostStage hs(ctx);
-    FP_TRY(hs.reserve(batch_need(params, batch) + HostStage::need<double>(BK * 3) + HostStage::need<double>(BK) + HostStage::need<uint32_t>(BK) +
-                      HostStage::need<double>(traj_doubles)));
-    FP_TRY(stage_batch(hs, params, batch, &ka.b));
+    StageList sl;
+    StageRegime rg;  // (throughput)
+    FP_TRY(stage_batch(ctx, sl, rg, params, batch, &ka.b));
     const double* d_end = nullptr;
-    FP_TRY(hs.in(end_states, BK * 3, &d_end));
-    FP_TRY(hs.flush_in());
-    double* d_cost = cost ? hs.out(cost, BK) : hs.temp<double>(BK);
-    uint32_t* d_flags = flags ? hs.out(flags, BK) : hs.temp<uint32_t>(BK);
-    double* d_traj = hs.out(traj, traj_doubles);
+    double* d_cost = nullptr;
+    uint32_t* d_flags = nullptr;
+    double* d_traj = nullptr;
+    sl.in(end_states, BK * 3, &d_end);
+    if (cost) sl.out(cost, BK, &d_cost); else sl.temp(BK, &d_cost);  // (the kernel writes both whether or not the caller wants them)
+    if (flags) sl.out(flags, BK, &d_flags); else sl.temp(BK, &d_flags);
+    sl.out(traj, traj_doubles, &d_traj);
+    FP_TRY(hs.commit(sl, rg));
     if (traj_sparse && d_traj) HIP_TRY(hipMemcpyAsync(d_traj, traj, traj_doubles * sizeof(double), hipMemcpyDefault, ctx->stream));
     LAUNCH_TRY(fp::launch_eval_trajs(ka, K, d_end, d_cost, d_flags, d_traj, stride, traj_sparse, ctx->stream), "eval kernel");
     return hs.fetch_out();
