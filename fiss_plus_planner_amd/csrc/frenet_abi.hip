@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "frenet_kernels.h"
+#include "frenet_project.h"
 #include "frenet_stage_plan.h"
 
 // Toolchain pin.  The kernels were validated on ROCm 7.2.0's clang 22 (AMD clang 22.0.0git roc-7.2.0): no kernel may spill a VGPR
@@ -195,6 +196,7 @@ struct fp_ctx {
     int rank_launches = 0;         // fp_ctx_get_option("rank_launches"): launches of the ranking kernel (fp_rank_feasible)
     int boundary_launches = 0;     // fp_ctx_get_option("boundary_launches"): launches of the road-boundary kernel (fp_boundary_mask)
     int predict_launches = 0;      // fp_ctx_get_option("predict_launches"): launches of the obstacle prediction kernel (fp_obstacles_predict)
+    int from_state_launches = 0;   // fp_ctx_get_option("from_state_launches"): launches of the projection kernel (fp_from_state)
     OrderSet order_lattice, order_refine;
     DeviceBuf idx_shadow;          // [B] device copy of best_idx for the winner kernel of a dense call (KernelArgs::idx_shadow)
     DeviceBuf epi_flags;           // [B] hand-over flags of the epilogue workgroups appended to a multi-round lattice launch (KernelArgs::epi_flag); zero between launches
@@ -1374,7 +1376,7 @@ int fp_ctx_get_option(fp_ctx* ctx, const char* name, int* value)
     const struct { const char* n; int v; } tab[] = {
         {"lattice_kernel", ctx->lattice_kernel}, {"lattice_split", ctx->lattice_split}, {"lattice_group", ctx->lattice_group}, {"lattice_tail", ctx->lattice_tail}, {"lattice_occupancy", ctx->lattice_occupancy}, {"resident_groups", ctx->resident_groups}, {"zero_copy_in", ctx->zero_copy_in}, {"stage_kernel", ctx->stage_kernel}, {"inline_inputs", ctx->inline_inputs}, {"lattice_order", ctx->lattice_order},
         {"refine_table_kb", ctx->refine_table_kb}, {"fiss_stages", ctx->fiss_stages}, {"fiss_jump", ctx->fiss_jump}, {"validate", ctx->validate}, {"lattice_winner", ctx->lattice_winner}, {"fiss_fused", ctx->fiss_fused}, {"appended_workgroups", ctx->appended_ok ? 1 : 0}, {"handover_failed", ctx->hand_err ? *(volatile int32_t*)ctx->hand_err : 0}, {"overlap", ctx->overlap}, {"overlapped_calls", ctx->overlapped_calls}, {"clearance_launches", ctx->clearance_launches + (ctx->twin ? ctx->twin->clearance_launches : 0)}, {"lattice_launches", ctx->lattice_launches + (ctx->twin ? ctx->twin->lattice_launches : 0)},
-        {"looplog_launches", ctx->looplog_launches}, {"rank_launches", ctx->rank_launches}, {"boundary_launches", ctx->boundary_launches}, {"predict_launches", ctx->predict_launches}, {"lattice_ordered_launches", ctx->lattice_ordered_launches + (ctx->twin ? ctx->twin->lattice_ordered_launches : 0)},
+        {"looplog_launches", ctx->looplog_launches}, {"rank_launches", ctx->rank_launches}, {"boundary_launches", ctx->boundary_launches}, {"predict_launches", ctx->predict_launches}, {"from_state_launches", ctx->from_state_launches}, {"lattice_ordered_launches", ctx->lattice_ordered_launches + (ctx->twin ? ctx->twin->lattice_ordered_launches : 0)},
         {"lattice_launches_2", (int)fp::lattice_launches_per_cu(0)}, {"lattice_launches_3", (int)fp::lattice_launches_per_cu(1)}, {"lattice_launches_4", (int)fp::lattice_launches_per_cu(2)}};
     for (const auto& t : tab)
         if (strcmp(name, t.n) == 0) { *value = t.v; return FP_OK; }
@@ -2103,10 +2105,22 @@ int fp_from_state(fp_ctx* ctx, const fp_batch* batch, const double* states, doub
     HIP_TRY(hipSetDevice(ctx->device));
     if (mem == FP_MEM_DEVICE) {
         LAUNCH_TRY(fp::launch_from_state(*batch, states, ego, (hipStream_t)stream), "from_state");
+        ++ctx->from_state_launches;
         return FP_OK;
     }
     const size_t B = (size_t)batch->B, fn = (size_t)batch->F * batch->NX;
     FP_TRY(check_frames_host(batch));
+    // host arrays: what the device path answers with a NaN row is an error the host path can name, before anything is launched
+    // (only the frames some ego sits on are looked at, as fp_obstacles_predict does for its LANE tracks)
+    for (size_t b = 0; b < B; ++b) {
+        static const char* const kName[4] = {"x", "y", "yaw", "v"};
+        for (int k = 0; k < 4; ++k)
+            if (!fp::project_finite(states[b * 4 + k])) return fail(FP_EINVAL, "fp_from_state: ego %zu: %s=%g is not finite", b, kName[k], states[b * 4 + k]);
+        const int32_t f = batch->frame_of[b];
+        const double s_last = batch->knots[(size_t)f * batch->NX + batch->nx[f] - 1];
+        if (fp::project_point_count(s_last) == 0)
+            return fail(FP_EINVAL, "fp_from_state: ego %zu sits on frame %d, whose line of length %g has fewer than two resampled points (0.1 m apart)", b, f, s_last);
+    }
     HostStage hs(ctx);
     StageList sl;
     fp_batch db = *batch;
@@ -2120,6 +2134,7 @@ int fp_from_state(fp_ctx* ctx, const fp_batch* batch, const double* states, doub
     sl.out(ego, B * 6, &d_ego);
     FP_TRY(hs.commit(sl));
     LAUNCH_TRY(fp::launch_from_state(db, d_states, d_ego, ctx->stream), "from_state");
+    ++ctx->from_state_launches;
     return hs.fetch_out();
 }
 

@@ -6,12 +6,12 @@
 //                         FrenetState.from_state (reference common/scenario/frenet.py:32-99)
 #include "frenet_device.h"
 #include "frenet_kernels.h"
+#include "frenet_project.h"
 
 namespace fp {
 
 namespace {
 constexpr int kFrameThreads = 128;
-constexpr double kPi = 3.141592653589793;
 }
 
 // LDS: s[NX], h[NX], then per axis: a[NX], c[NX], cp[NX], dp[NX]
@@ -91,9 +91,11 @@ struct RefPoint {
 
 __device__ __forceinline__ RefPoint ref_point(const SplineLds& sp, double s)
 {
-    // calc_position / calc_yaw at s (cubic_spline.py:170-232); s is inside [0, s_last) by construction
+    // calc_position / calc_yaw at s (cubic_spline.py:170-232); s = i * 0.1 with i < project_point_count(s_last), which keeps it
+    // below s_last (the ceil of the quotient alone does not).  A table whose first knot is not 0 would still give -1: segment 0 then
     RefPoint r;
-    const int seg = spline_segment(sp, s, -1);
+    const int seg0 = spline_segment(sp, s, -1);
+    const int seg = seg0 < 0 ? 0 : seg0;
     const double* c = sp.coef + seg;
     const int ld = sp.ld;
     const double dx = s - sp.knots[seg];
@@ -111,13 +113,23 @@ __global__ __launch_bounds__(256) void from_state_kernel(fp_batch bt, const doub
     __shared__ int red_i[4];
     __shared__ double red_s[4];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+    const double sx = states[(size_t)b * 4], sy = states[(size_t)b * 4 + 1], syaw = states[(size_t)b * 4 + 2], sv = states[(size_t)b * 4 + 3];
+    // An ego with a non-finite state, or on a frame nothing can be projected on (index or knot count out of range, fewer than two
+    // resampled points), gets six NaN; of the tables only the frame's last knot is read, for that count.  Every term depends on b alone: the condition is uniform over the
+    // workgroup, so leaving before the barriers below is safe.
     const int f = bt.frame_of[b];
+    int n_ref = 0;
+    if (project_state_ok(sx, sy, syaw, sv) && f >= 0 && f < bt.F) {
+        const int nxf = bt.nx[f];
+        if (nxf >= 2 && nxf <= bt.NX) n_ref = project_point_count(bt.knots[(size_t)f * bt.NX + nxf - 1]);  // len(np.arange(0, s_last, 0.1))  (frenet_optimal_planner.py:274)
+    }
+    if (n_ref == 0) {
+        if (tid < 6) ego_out[(size_t)b * 6 + tid] = project_nan();
+        return;
+    }
     const int nx = bt.nx[f];
     const double* knots = bt.knots + (size_t)f * bt.NX;
     SplineLds sp{knots, bt.coef + (size_t)f * 8 * bt.NX, nx, bt.NX};
-    const double sx = states[(size_t)b * 4], sy = states[(size_t)b * 4 + 1], syaw = states[(size_t)b * 4 + 2], sv = states[(size_t)b * 4 + 3];
-    const double s_last = knots[nx - 1];
-    const int n_ref = (int)ceil(s_last / 0.1);  // len(np.arange(0, s_last, 0.1))  (frenet_optimal_planner.py:274)
     // nearest resampled point: np.argmin -> first minimum (frenet.py:34-36)
     double best = __builtin_inf();
     int bi = 0x7fffffff;
@@ -139,13 +151,8 @@ __global__ __launch_bounds__(256) void from_state_kernel(fp_batch bt, const doub
     const int nearest = bi;
     // find_next_point_idx (:38-56)
     const RefPoint pn = ref_point(sp, (double)nearest * 0.1);
-    const double heading = atan2(pn.y - sy, pn.x - sx);
-    double angle = fabs(syaw - heading);
-    angle = fmin(2.0 * kPi - angle, angle);
-    int next = angle > kPi / 2.0 ? nearest + 1 : nearest;
-    if (next < 1) next = 1;
-    else if (next >= n_ref) next = n_ref - 1;
-    const int prev = next - 1 > 0 ? next - 1 : 0;
+    const int next = project_next_idx(nearest, n_ref, project_fold_angle(syaw, atan2(pn.y - sy, pn.x - sx)));
+    const int prev = project_prev_idx(next);
     // s = sum of the polyline segment lengths before prev (:86-88)
     double acc = 0.0;
     for (int i = tid; i < prev; i += blockDim.x) {
@@ -160,19 +167,11 @@ __global__ __launch_bounds__(256) void from_state_kernel(fp_batch bt, const doub
         double s = 0.0;
         for (int w = 0; w < (int)blockDim.x / kWave; ++w) s += red_s[w];
         const RefPoint pp = ref_point(sp, (double)prev * 0.1), px = ref_point(sp, (double)next * 0.1);
-        const double n_x = px.x - pp.x, n_y = px.y - pp.y;
-        const double x_x = sx - pp.x, x_y = sy - pp.y;
-        const double x_yaw = atan2(x_y, x_x);
-        const double proj = (x_x * n_x + x_y * n_y) / (n_x * n_x + n_y * n_y);
-        double d = hypot(x_x - proj * n_x, x_y - proj * n_y);
-        const double wp_yaw = pp.yaw;
-        double delta = syaw - wp_yaw;  // unifyAngleRange (math_utils.py:28-34)
-        while (delta > kPi) delta -= 2.0 * kPi;
-        while (delta < -kPi) delta += 2.0 * kPi;
-        if (wp_yaw <= x_yaw) d = -d;  // :82-83
+        double s_d, d, d_d;
+        project_on_segment(sx, sy, syaw, sv, pp.x, pp.y, pp.yaw, px.x, px.y, &s_d, &d, &d_d);
         double* o = ego_out + (size_t)b * 6;
-        o[0] = s; o[1] = sv * cos(delta); o[2] = 0.0;
-        o[3] = d; o[4] = sv * sin(delta); o[5] = 0.0;
+        o[0] = s; o[1] = s_d; o[2] = 0.0;
+        o[3] = d; o[4] = d_d; o[5] = 0.0;
     }
 }
 

@@ -544,6 +544,15 @@ class FrenetEngine:
         _abi.check(self._lib.fp_from_state(self._ctx, C.byref(fb), st.ctypes.data, ego.ctypes.data, _abi.FP_MEM_HOST, None))
         return ego
 
+    def build_frames_device(self, F: int, NX: int, n: int, points: int, knots: int, coef: int, stream: int = 0):
+        """Enqueue the frame build (device addresses: n [F] int32, points [F,NX,2], knots [F,NX], coef [F,8,NX])."""
+        _abi.check(self._lib.fp_frames_build(self._ctx, int(F), int(NX), n, points, knots, coef, _abi.FP_MEM_DEVICE, stream or None))
+
+    def from_state_device(self, fb: _abi.FpBatch, states: int, ego: int, stream: int = 0):
+        """Enqueue the projection (device addresses in fb: frame_of, nx, knots, coef; states [B,4], ego [B,6]).  An ego that cannot be
+        projected (non-finite state, unusable frame) gets a NaN row instead of the host path's FP_EINVAL."""
+        _abi.check(self._lib.fp_from_state(self._ctx, C.byref(fb), states, ego, _abi.FP_MEM_DEVICE, stream or None))
+
     # ------------------------------------------------------------------ resident device memory
     def plan_dense_device(self, params: _abi.FpParams, fb: _abi.FpBatch, best_idx: int, best_cost: int, stats: int = 0,
                           cost_tbl: int = 0, flag_tbl: int = 0, stream: int = 0, best_flags: int = 0, best_traj: int = 0,

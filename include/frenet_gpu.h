@@ -315,7 +315,7 @@ int fp_ctx_set_option(fp_ctx* ctx, const char* name, int value);
 /* Reads an option back, or one of the read-only counters "clearance_launches" (launches of the clearance rescoring kernel,
  * fp_params.w_obstacle > 0, of this ctx so far), "looplog_launches" (launches of fp_loop_record's kernel), "rank_launches" (launches of
  * fp_rank_feasible's kernel), "boundary_launches" (launches of fp_boundary_mask's kernel), "predict_launches" (launches of
- * fp_obstacles_predict's kernel), "lattice_launches" (dense lattice launches of this ctx so far) and
+ * fp_obstacles_predict's kernel), "from_state_launches" (launches of fp_from_state's kernel), "lattice_launches" (dense lattice launches of this ctx so far) and
  * "lattice_ordered_launches" (those dispatched in a feedback order or in the order of fp_batch.launch_order) - bench.py reports when an
  * order took effect -, "lattice_launches_2" / "_3" / "_4" (PROCESS-wide: fused lattice launches so far by workgroups per compute unit). */
 int fp_ctx_get_option(fp_ctx* ctx, const char* name, int* value);
@@ -550,7 +550,18 @@ int fp_frames_build(fp_ctx* ctx, int32_t F, int32_t NX, const int32_t* n, const 
  * (x, y, yaw, v) on the 0.1 m-resampled reference line of its frame (generate_frenet_frame, frenet_optimal_planner.py:272-278):
  * nearest point (first minimum), next-waypoint rule by heading, projection on the segment, sign from `wp_yaw <= x_yaw`,
  * s = polyline length up to the previous waypoint.  states [B][4]  ->  ego [B][6] = s, s_d, 0, d, d_d, 0.
- * Uses batch->F, NX, nx, knots, coef, frame_of (the other batch fields may be NULL). */
+ * Uses batch->F, NX, nx, knots, coef, frame_of (the other batch fields may be NULL).
+ * The number of resampled points of a line is len(np.arange(0, s_last, 0.1)) = ceil(s_last / 0.1), MINUS ONE when the last of them
+ * would lie at s_last itself (s_last within an ulp of a multiple of 0.1, e.g. 3 * 0.1): the spline has no segment there.  A deviation
+ * from the reference, which raises IndexError on such a line; here the line loses that point (both memory modes).
+ * What cannot be projected - a state with a NaN or infinite x, y, yaw or v (the reference's angle unification never returns for an
+ * infinite yaw), or a frame whose line has fewer than two resampled points (s_last <= 0.1 m, or not finite) -
+ *   FP_MEM_HOST:   is refused with FP_EINVAL before anything is launched; the message names the ego, the entry or the frame, and the
+ *                  value.  Only frames that some frame_of[b] references are looked at.
+ *   FP_MEM_DEVICE: gives that ego a row of six NaN (so does a frame_of[b] outside 0 .. F-1 or an nx outside 2 .. NX); the other
+ *                  egos of the call are not affected.
+ * A finite yaw whose difference to the line's yaw exceeds 25000 rad (3979 turns) gives NaN in s_d and d_d; s and d are valid.
+ * Also read-only in fp_ctx_get_option: "from_state_launches" = launches of the kernel on this ctx so far. */
 int fp_from_state(fp_ctx* ctx, const fp_batch* batch, const double* states, double* ego, int mem, void* stream);
 
 /* ---- closed-loop stepping on the device ---------------------------------------------------------------------

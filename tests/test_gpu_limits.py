@@ -107,6 +107,19 @@ def test_reference_line_of_1024_knots(oracle, engine):
     gk, gc = engine.build_frames(pts)
     np.testing.assert_allclose(gk, knots, rtol=0, atol=1e-9)
     np.testing.assert_allclose(gc, coef, rtol=0, atol=1e-7)
+    # from_state on these lines: ~4000 resampled points each, so every one of the 256 threads walks 16 of them and the sum of the
+    # segment lengths before the ego spans all four wavefronts (tests/frame_ref.py: the reference and the comparison rules)
+    import frame_ref
+
+    nx = np.full(3, NX, dtype=np.int32)
+    fo, poses = frame_ref.random_poses(gk, gc, nx, [2, 0, 1], per_frame=30, seed=80)
+    fc, pc = frame_ref.clamp_poses(gk, gc, nx, [0, 1, 2])
+    fo, poses = np.concatenate([fo, fc]), np.concatenate([poses, pc])
+    assert (frame_ref.point_count_margin(gk, nx) >= 1e-3).all()
+    ref, dec, pls = frame_ref.reference_rows(oracle, gk, gc, nx, fo, poses)
+    assert all(15 * 256 < len(pl) <= 16 * 256 for pl in pls.values()) and max(d.nearest for d in dec) > 3 * 1024
+    r = frame_ref.assert_projection(engine.from_state(gk, gc, nx, fo, poses), ref, dec, what="1024 knots")
+    print(f"1024 knots: {r.n} poses, undecidable {r.undecidable * r.n:.0f}, max err s {r.err_s:.2e} s_d {r.err_sd:.2e} d {r.err_d:.2e} d_d {r.err_dd:.2e}")
     base.knots, base.coef, base.nx = knots, coef, np.full(3, NX, dtype=np.int32)
     for kernel in (2, 1, 0):
         engine.set_option("lattice_kernel", kernel)
