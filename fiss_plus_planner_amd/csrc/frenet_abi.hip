@@ -1935,6 +1935,12 @@ int fp_advance(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, cons
         return FP_OK;
     }
     FP_TRY(check_batch_host(params, batch));
+    if (best_idx) {  // (the kernel decodes the index of every running ego and reads d_samples / t_samples / v_samples with it; negative = no solution)
+        const long n_cand = (long)params->nd * params->nv * params->nt;
+        for (int i = 0; i < batch->B; ++i)
+            if (io->done[i] == FP_RUNNING && best_idx[i] >= n_cand)
+                return fail(FP_EINVAL, "fp_advance: best_idx[%d]=%d is not below nd*nv*nt=%ld", i, best_idx[i], n_cand);
+    }
     HostStage hs(ctx);
     StageList sl;
     StageRegime rg;  // (throughput)

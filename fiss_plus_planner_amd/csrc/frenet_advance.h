@@ -4,6 +4,7 @@
 #pragma once
 #include "frenet_device.h"
 #include "frenet_kernels.h"
+#include "frenet_project.h"
 
 namespace fp {
 
@@ -123,16 +124,18 @@ __device__ __forceinline__ void advance_ego_to(const KernelArgs& ka, int b, doub
         io.done[b] = FP_DONE_GOAL;
         return;
     }
-    // the end of the map is the last point of np.arange(0, s_last, 0.1)
-    const double s_last = knots[nx - 1];
-    int n_ref = (int)ceil(s_last / 0.1);
-    if (n_ref < 1) n_ref = 1;
-    const double s_ref = (double)(n_ref - 1) * 0.1;
-    const int seg = spline_segment(sp, s_ref, -1);
-    if (seg >= 0) {
-        double px, py, tx, ty;
-        spline_frame(sp, seg, s_ref - knots[seg], px, py, tx, ty);
-        if (hypot(xs1 - px, ys1 - py) <= 3.0) io.done[b] = FP_DONE_END_OF_LINE;
+    // the end of the map is the last point of np.arange(0, s_last, 0.1): the resampled line's point count is project_point_count's (one
+    // rule for fp_from_state and for this one - a last sample that would land on s_last itself, where the spline has no segment, is not
+    // a point of the line); a line of fewer than two points (count 0) has no end-of-map point and the rule is off
+    const int n_ref = project_point_count(knots[nx - 1]);
+    if (n_ref >= 2) {
+        const double s_ref = (double)(n_ref - 1) * kProjectStep;
+        const int seg = spline_segment(sp, s_ref, -1);
+        if (seg >= 0) {
+            double px, py, tx, ty;
+            spline_frame(sp, seg, s_ref - knots[seg], px, py, tx, ty);
+            if (hypot(xs1 - px, ys1 - py) <= 3.0) io.done[b] = FP_DONE_END_OF_LINE;
+        }
     }
 }
 

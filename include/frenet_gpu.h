@@ -575,7 +575,13 @@ int fp_from_state(fp_ctx* ctx, const fp_batch* batch, const double* states, doub
  * The chosen trajectory is given either as a lattice index (best_idx, FOP order) or as explicit end states
  * (end_state [B][3] = d, v, T; NaN = no solution) - exactly one of the two pointers is non-NULL.
  * Plan + advance can be enqueued back to back on one stream for as many cycles as wanted: no host round trip; fp_plan_step does
- * both in ONE launch. */
+ * both in ONE launch.
+ * FP_DONE_END_OF_LINE: the resampled line's last point is point n - 1 at arclength (n - 1) * 0.1, n = the point count fp_from_state uses
+ * (len(np.arange(0, s_last, 0.1)), less one when that last sample would reach s_last itself, where the spline has no segment).  A line
+ * of fewer than two such points (s_last <= 0.1 m) has no end-of-map point: the rule is off for its egos, the other rules apply.
+ * best_idx: a negative index = no solution.  FP_MEM_HOST: an index >= nd*nv*nt of a running ego is refused with FP_EINVAL (ego and
+ * value named) before anything is staged.  FP_MEM_DEVICE: the caller guarantees best_idx[b] < nd*nv*nt for every running ego - the
+ * kernel decodes the index and reads d_samples / t_samples / v_samples with it unchecked. */
 #define FP_RUNNING 0
 #define FP_DONE_GOAL 1
 #define FP_DONE_END_OF_LINE 2
