@@ -195,6 +195,7 @@ struct fp_ctx {
     int looplog_launches = 0;      // fp_ctx_get_option("looplog_launches"): launches of the loop-log kernel (fp_loop_record)
     int rank_launches = 0;         // fp_ctx_get_option("rank_launches"): launches of the ranking kernel (fp_rank_feasible)
     int boundary_launches = 0;     // fp_ctx_get_option("boundary_launches"): launches of the road-boundary kernel (fp_boundary_mask)
+    int margin_launches = 0;       // fp_ctx_get_option("margin_launches"): launches of the plan-margin kernel (fp_traj_margins)
     int predict_launches = 0;      // fp_ctx_get_option("predict_launches"): launches of the obstacle prediction kernel (fp_obstacles_predict)
     int from_state_launches = 0;   // fp_ctx_get_option("from_state_launches"): launches of the projection kernel (fp_from_state)
     OrderSet order_lattice, order_refine;
@@ -1376,7 +1377,7 @@ int fp_ctx_get_option(fp_ctx* ctx, const char* name, int* value)
     const struct { const char* n; int v; } tab[] = {
         {"lattice_kernel", ctx->lattice_kernel}, {"lattice_split", ctx->lattice_split}, {"lattice_group", ctx->lattice_group}, {"lattice_tail", ctx->lattice_tail}, {"lattice_occupancy", ctx->lattice_occupancy}, {"resident_groups", ctx->resident_groups}, {"zero_copy_in", ctx->zero_copy_in}, {"stage_kernel", ctx->stage_kernel}, {"inline_inputs", ctx->inline_inputs}, {"lattice_order", ctx->lattice_order},
         {"refine_table_kb", ctx->refine_table_kb}, {"fiss_stages", ctx->fiss_stages}, {"fiss_jump", ctx->fiss_jump}, {"validate", ctx->validate}, {"lattice_winner", ctx->lattice_winner}, {"fiss_fused", ctx->fiss_fused}, {"appended_workgroups", ctx->appended_ok ? 1 : 0}, {"handover_failed", ctx->hand_err ? *(volatile int32_t*)ctx->hand_err : 0}, {"overlap", ctx->overlap}, {"overlapped_calls", ctx->overlapped_calls}, {"clearance_launches", ctx->clearance_launches + (ctx->twin ? ctx->twin->clearance_launches : 0)}, {"lattice_launches", ctx->lattice_launches + (ctx->twin ? ctx->twin->lattice_launches : 0)},
-        {"looplog_launches", ctx->looplog_launches}, {"rank_launches", ctx->rank_launches}, {"boundary_launches", ctx->boundary_launches}, {"predict_launches", ctx->predict_launches}, {"from_state_launches", ctx->from_state_launches}, {"lattice_ordered_launches", ctx->lattice_ordered_launches + (ctx->twin ? ctx->twin->lattice_ordered_launches : 0)},
+        {"looplog_launches", ctx->looplog_launches}, {"rank_launches", ctx->rank_launches}, {"boundary_launches", ctx->boundary_launches}, {"margin_launches", ctx->margin_launches}, {"predict_launches", ctx->predict_launches}, {"from_state_launches", ctx->from_state_launches}, {"lattice_ordered_launches", ctx->lattice_ordered_launches + (ctx->twin ? ctx->twin->lattice_ordered_launches : 0)},
         {"lattice_launches_2", (int)fp::lattice_launches_per_cu(0)}, {"lattice_launches_3", (int)fp::lattice_launches_per_cu(1)}, {"lattice_launches_4", (int)fp::lattice_launches_per_cu(2)}};
     for (const auto& t : tab)
         if (strcmp(name, t.n) == 0) { *value = t.v; return FP_OK; }
@@ -1606,6 +1607,64 @@ int fp_boundary_mask(fp_ctx* ctx, const fp_params* params, const fp_batch* batch
     FP_TRY(hs.commit(sl));
     LAUNCH_TRY(fp::launch_boundary_mask(a, ctx->stream), "road-boundary kernel");
     ++ctx->boundary_launches;
+    return hs.fetch_out();
+}
+
+int fp_traj_margins(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, int32_t K, const int32_t* best_idx, const double* end_state,
+                    int32_t pose_stride, double* min_dist, int32_t* min_step, int32_t* min_obs, int mem, void* stream)
+{
+    FP_TRY(common_checks(ctx, params, batch, mem, stream));
+    if (K < 1 || K > FP_MAX_RANK) return fail(FP_EINVAL, "fp_traj_margins: K=%d outside 1..FP_MAX_RANK", K);
+    if (pose_stride < 1) return fail(FP_EINVAL, "fp_traj_margins: pose_stride=%d must be >= 1", pose_stride);
+    if ((best_idx == nullptr) == (end_state == nullptr)) return fail(FP_EINVAL, "fp_traj_margins: exactly one of best_idx / end_state must be given");
+    if (!min_dist || !min_step || !min_obs) return fail(FP_EINVAL, "fp_traj_margins: min_dist/min_step/min_obs must not be NULL");
+    if (batch->B == 0) return FP_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t KB = (size_t)K * batch->B;
+    fp::KernelArgs ka;
+    ka.p = *params;
+    ka.p.check_stride = pose_stride;  // (the kernel's staging and pose set read it there; the caller's own check_stride is not used)
+    ka.r = no_result();
+    fp::MarginArgs m;
+    m.K = K;
+    if (mem == FP_MEM_DEVICE) {
+        ka.b = *batch;
+        if (!(batch->S > 0 && batch->n_obs > 0)) ka.b.n_obs = 0;
+        m.best_idx = best_idx; m.end_state = end_state; m.perm = batch->launch_order;
+        m.min_dist = min_dist; m.min_step = min_step; m.min_obs = min_obs;
+        LAUNCH_TRY(fp::launch_traj_margins(ka, m, (hipStream_t)stream), "plan-margin kernel");
+        ++ctx->margin_launches;
+        return FP_OK;
+    }
+    FP_TRY(check_batch_host(params, batch));
+    if (best_idx) {
+        const int C = params->nd * params->nv * params->nt;
+        for (size_t i = 0; i < KB; ++i) {
+            const size_t b = i % (size_t)batch->B;
+            if (best_idx[i] >= C && !(batch->skip && batch->skip[b]))
+                return fail(FP_EINVAL, "fp_traj_margins: best_idx of ego %zu, plane %zu = %d is outside the lattice (nd*nv*nt = %d)", b, i / (size_t)batch->B, best_idx[i], C);
+        }
+        ka.p.points_max = host_points_max(params, batch, nullptr, 0, 0);
+    } else {
+        for (size_t i = 0; i < KB; ++i) {
+            const double n = end_state[3 * i + 2] / params->tick_t;
+            if (n != n || (batch->skip && batch->skip[i % (size_t)batch->B])) continue;  // NaN end state = "no trajectory"
+            if (!(n > 0) || n > FP_MAX_POINTS)
+                return fail(FP_ELIMIT, "fp_traj_margins: end_state of ego %zu, plane %zu: T=%g needs 1..FP_MAX_POINTS points", i % (size_t)batch->B, i / (size_t)batch->B, end_state[3 * i + 2]);
+        }
+        ka.p.points_max = host_points_max(params, batch, end_state + 2, KB, 3);
+    }
+    HostStage hs(ctx);
+    StageList sl;
+    StageRegime rg;  // (throughput)
+    FP_TRY(stage_batch(ctx, sl, rg, params, batch, &ka.b));
+    if (best_idx) sl.in(best_idx, KB, &m.best_idx); else sl.in(end_state, KB * 3, &m.end_state);
+    sl.out(min_dist, KB, &m.min_dist);
+    sl.out(min_step, KB, &m.min_step);
+    sl.out(min_obs, KB, &m.min_obs);
+    FP_TRY(hs.commit(sl, rg));
+    LAUNCH_TRY(fp::launch_traj_margins(ka, m, ctx->stream), "plan-margin kernel");
+    ++ctx->margin_launches;
     return hs.fetch_out();
 }
 

@@ -224,6 +224,19 @@ struct BoundaryArgs {
     int32_t* n_masked = nullptr;
 };
 hipError_t launch_boundary_mask(const BoundaryArgs& a, hipStream_t stream);
+// The obstacle margin of K chosen plans per ego (frenet_margins.hip, fp_traj_margins): one workgroup per ego, in the order of perm
+// (optional).  ka.p.check_stride is the call's pose_stride; ka.r is not read.  Device addresses; exactly one of best_idx [K][B] /
+// end_state [K][B][3] set; the outputs are [K][B].
+struct MarginArgs {
+    int K = 0;
+    const int32_t* best_idx = nullptr;
+    const double* end_state = nullptr;
+    const int32_t* perm = nullptr;
+    double* min_dist = nullptr;
+    int32_t* min_step = nullptr;
+    int32_t* min_obs = nullptr;
+};
+hipError_t launch_traj_margins(const KernelArgs& ka, const MarginArgs& m, hipStream_t stream);
 // The obstacle pose table from tracks (frenet_predict.hip, fp_obstacles_predict): rows max(t0, 0) .. min(T_obs, t0 + n_rows) - 1 of
 // every scene of obs_pose [S][T_obs][n_obs][4].  Device addresses; nx / knots / coef / frame_of_scene may be NULL (LANE columns then
 // have no pose).  compact: the output is [S][span][n_obs][4], span = min(T_obs, n_rows), and a scene's first written row lands in

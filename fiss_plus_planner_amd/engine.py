@@ -206,7 +206,7 @@ class FrenetEngine:
             best_traj=(np.full((B, 16, traj_stride), np.nan) if traj_sparse else np.empty((B, 16, traj_stride))) if winner else None)
 
     def plan_dense(self, batch: ProblemBatch, tables: bool = True, winner: bool = False, traj_stride: int = TRAJ_STRIDE, traj_sparse: bool = False,
-                   out: SimpleNamespace | None = None, audit: bool = False, top_k: int = 0, boundary: bool = False):
+                   out: SimpleNamespace | None = None, audit: bool = False, top_k: int = 0, boundary: bool = False, margins: bool = False):
         """FrenetOptimalPlanner.plan() for every ego of the batch (reference frenet_optimal_planner.py:247-270).
 
         Returns best_idx [B] (flat (i_d*nt+i_T)*nv+i_v, -1 = none), best_cost [B], stats [B,4] and, with
@@ -219,8 +219,18 @@ class FrenetEngine:
         bound_right): the road-boundary check (boundary_mask) runs behind the dense call over its tables - computed for it whether
         asked for or not -; best_idx / best_cost are the argmin among the candidates that stay inside the corridor, `flags` carry
         FLAG_BOUNDARY, top_k ranks the masked tables, also n_masked [B]; with winner=True the series come from winner_trajs on the new
-        best_idx (the lattice launch's own series may belong to a masked winner).
+        best_idx (the lattice launch's own series may belong to a masked winner).  margins=True: also margin_dist / margin_step /
+        margin_obs (traj_margins at the batch's check_stride) of the result - [B] for best_idx, or [top_k, B] for rank_idx together with
+        top_k; with boundary=True they are taken on the masked result.
         """
+        if margins:
+            out = self.plan_dense(batch, tables, winner, traj_stride, traj_sparse, out, audit, top_k, boundary)
+            plans = out.rank_idx if top_k else out.best_idx
+            if batch.B:
+                out.margin_dist, out.margin_step, out.margin_obs = self.traj_margins(batch, best_idx=plans)
+            else:
+                out.margin_dist, out.margin_step, out.margin_obs = np.empty(plans.shape), np.empty(plans.shape, dtype=np.int32), np.empty(plans.shape, dtype=np.int32)
+            return out
         if boundary:
             if getattr(batch, "bound_left", None) is None:
                 raise ValueError("plan_dense(boundary=True): the batch carries no corridor (ProblemBatch.bound_left / bound_right)")
@@ -352,6 +362,51 @@ class FrenetEngine:
         cor = _abi.FpCorridor(left or None, right or None, float(margin))
         _abi.check(self._lib.fp_boundary_mask(self._ctx, C.byref(params), C.byref(fb), C.byref(cor), cost_tbl or None, flag_tbl or None, best_idx or None,
                                               best_cost or None, n_masked or None, _abi.FP_MEM_DEVICE, stream or None))
+
+    def traj_margins(self, batch: ProblemBatch, best_idx: np.ndarray | None = None, end_state: np.ndarray | None = None, pose_stride: int | None = None,
+                     skip: np.ndarray | None = None):
+        """The obstacle margin of chosen plans (fp_traj_margins; the definition: include/frenet_gpu.h): best_idx [B] or [K, B] flat FOP
+        indices (plan_dense's best_idx, rank_feasible's rank_idx), or end_state [B, 3] / [K, B, 3] explicit (d, v, T) end states
+        (plan_fiss' end_state; NaN = none) -> (min_dist, min_step, min_obs), each shaped like the plans: the smallest distance between
+        the footprint at a checked pose and an obstacle valid there (0 on contact, +inf without a pair, NaN without a trajectory), and the
+        point index and obstacle column where it occurs (-1, -1 for +inf / NaN).  pose_stride None = the batch's check_stride (the
+        collision check's pose set), 1 = every pose.  skip [B] (optional): egos that have no plan (NaN, their rows are not read)."""
+        if (best_idx is None) == (end_state is None):
+            raise ValueError("traj_margins: exactly one of best_idx / end_state")
+        B = batch.B
+        if best_idx is not None:
+            plans = np.ascontiguousarray(best_idx, dtype=np.int32)
+            flat = plans.ndim == 1
+            if plans.shape[-1:] != (B,) or plans.ndim not in (1, 2):
+                raise ValueError(f"traj_margins: best_idx must be [B={B}] or [K, B], got {plans.shape}")
+            K = 1 if flat else plans.shape[0]
+        else:
+            plans = np.ascontiguousarray(end_state, dtype=np.float64)
+            flat = plans.ndim == 2
+            if plans.shape[-2:] != (B, 3) or plans.ndim not in (2, 3):
+                raise ValueError(f"traj_margins: end_state must be [B={B}, 3] or [K, B, 3], got {plans.shape}")
+            K = 1 if flat else plans.shape[0]
+        shape = (B,) if flat else (K, B)
+        dist = np.empty(shape); step = np.empty(shape, dtype=np.int32); obs = np.empty(shape, dtype=np.int32)
+        p, fb = host_structs(batch)
+        if skip is not None:
+            skip = np.ascontiguousarray(skip, dtype=np.int32)
+            assert skip.shape == (B,)
+            fb.skip = _ptr(skip)
+        ps = int(batch.check_stride if pose_stride is None else pose_stride)
+        # (B == 0 still crosses the ABI: the argument checks are the library's)
+        _abi.check(self._lib.fp_traj_margins(self._ctx, C.byref(p), C.byref(fb), K, _ptr(plans) if best_idx is not None else None,
+                                             _ptr(plans) if best_idx is None else None, ps, _ptr(dist), _ptr(step), _ptr(obs), _abi.FP_MEM_HOST, None))
+        return dist, step, obs
+
+    def traj_margins_device(self, params: _abi.FpParams, fb: _abi.FpBatch, k: int, min_dist: int, min_step: int, min_obs: int, best_idx: int = 0,
+                            end_state: int = 0, pose_stride: int | None = None, stream: int = 0):
+        """Enqueue the plan margins behind a dense / ranking / FISS call (device addresses): best_idx [k][B] (rank_idx of
+        rank_feasible_device, or best_idx with k = 1) or end_state [k][B][3]; min_dist / min_step / min_obs [k][B].  pose_stride None =
+        params.check_stride.  One launch, nothing allocated, nothing waited for."""
+        _abi.check(self._lib.fp_traj_margins(self._ctx, C.byref(params), C.byref(fb), int(k), best_idx or None, end_state or None,
+                                             int(params.check_stride if pose_stride is None else pose_stride), min_dist or None, min_step or None, min_obs or None,
+                                             _abi.FP_MEM_DEVICE, stream or None))
 
     def predict_obstacles(self, batch, model, state, frame_of_scene=None, t0=0, n_rows: int | None = None, out: np.ndarray | None = None):
         """The obstacle pose table of `batch` predicted from tracks (fp_obstacles_predict through FP_MEM_HOST; the definition:

@@ -85,6 +85,11 @@ class FrenetOptimalPlannerSettings:
         # cost, FOP's "last minimum wins" among equal costs), entry 0 the returned trajectory.  FOP+, FISS and FISS+ walk the lattice in
         # their own order and raise ValueError
         self.num_alternatives = 0
+        # not in the reference's settings: True: plan() of every planner class leaves `planner.best_margin` = (distance, point index,
+        # obstacle index) of the trajectory it returns - the smallest distance between the ego footprint at one of has_collision's
+        # poses and an obstacle present there, and where it occurs (fp_traj_margins; None when plan() found nothing) -, and with
+        # num_alternatives `planner.alternative_margins`, one such tuple per entry of `planner.alternatives`
+        self.report_margins = False
 
 
 class FissPlannerSettings(FrenetOptimalPlannerSettings):
@@ -359,7 +364,29 @@ class FrenetOptimalPlanner:
             self.alternatives = self._alternatives(batch, out, n_alt)
         else:
             self.__dict__.pop("alternatives", None)
+        self._margins(batch, self.best_traj if best >= 0 else None)
         return self.best_traj
+
+    def _margins(self, batch: ProblemBatch, traj):
+        """settings.report_margins: best_margin of the trajectory this plan() call found (None: it found none) and, beside
+        `alternatives`, alternative_margins.  A lattice candidate goes in by its index, a refined FISS+ winner by its end state."""
+        self.__dict__.pop("best_margin", None)
+        self.__dict__.pop("alternative_margins", None)
+        if not getattr(self.settings, "report_margins", False):
+            return
+
+        def one(t):
+            idx = t.__dict__.get("lattice_index")
+            if idx is not None:
+                d, i, j = self._engine.traj_margins(batch, best_idx=np.array([idx], dtype=np.int32))
+            else:
+                es = t.end_state
+                d, i, j = self._engine.traj_margins(batch, end_state=np.array([[es.d, es.s_d, es.t]]))
+            return float(d[0]), int(i[0]), int(j[0])
+
+        self.best_margin = None if traj is None else one(traj)
+        if "alternatives" in self.__dict__:
+            self.alternative_margins = [one(a) for a in self.alternatives]
 
     def _alternatives(self, batch: ProblemBatch, out, n_alt: int):
         """The n_alt cheapest survivors of this plan() call in rank order (fp_rank_feasible over the call's tables); the series of
@@ -394,11 +421,13 @@ class FopPlusPlanner(FrenetOptimalPlanner):
         best, st = search.fopplus_search(out.cost[0], out.flags[0])
         self.stats = Stats(*st)
         if best is None:
+            self._margins(batch, None)
             return None
         es, _ = self._end_state_of_flat(batch, best)
         trajs, _ = self._materialize(batch, es[None])
         self.best_traj = trajs[0]
         self.best_traj.lattice_index = best
+        self._margins(batch, self.best_traj)
         return self.best_traj
 
 
@@ -476,6 +505,7 @@ class FissPlanner(FrenetOptimalPlanner):
         if plus and R > 0 and found:
             self.sampling_res = self.sampling_res * st.decaying_factor ** R  # decays in place in the reference (:282)
         if not found:
+            self._margins(batch, None)
             return None
         self.prev_best_idx = out.prev_best_idx[0].copy()
         fl = int(out.best_flags[0])  # N and M ride in the flag word (FP_FLAG_N_SHIFT / FP_FLAG_M_SHIFT)
@@ -483,6 +513,7 @@ class FissPlanner(FrenetOptimalPlanner):
         end = FrenetState(t=es[2], s=0.0, s_d=es[1], d=es[0])
         idx = [-1, -1, -1] if out.refined[0] else out.best_ijk[0].tolist()
         self.best_traj = FrenetTrajectory.from_dump(out.best_traj[0], (fl >> 8) & 0xFFF, fl >> 20, best_cost, end, idx)
+        self._margins(batch, self.best_traj)
         return self.best_traj
 
     def _refine_rounds(self) -> int:
@@ -513,11 +544,13 @@ class FissPlanner(FrenetOptimalPlanner):
             return self._plan_on_device(frenet_state, max_target_speed, obstacles, time_step_now)
         batch, idx = self._coarse(frenet_state, max_target_speed, obstacles, time_step_now)
         if idx is None:
+            self._margins(batch, None)
             return None
         es = np.array([batch.d_samples[idx[0]], batch.v_samples[0, idx[1]], batch.t_samples[idx[2]]])
         trajs, _ = self._materialize(batch, es[None], [np.array(idx)])
         self.best_traj = trajs[0]
         self.prev_best_idx = self.best_traj.idx  # persists across cycles (:252)
+        self._margins(batch, self.best_traj)
         return self.best_traj
 
 
@@ -533,6 +566,7 @@ class FissPlusPlanner(FissPlanner):
             return self._plan_on_device(frenet_state, max_target_speed, obstacles, time_step_now)
         batch, idx = self._coarse(frenet_state, max_target_speed, obstacles, time_step_now)
         if idx is None:
+            self._margins(batch, None)
             return None
         x = np.array([batch.d_samples[idx[0]], batch.v_samples[0, idx[1]], batch.t_samples[idx[2]]])
         coarse_cost = float(self.last_tables[0][(idx[0] * batch.nt + idx[2]) * batch.nv + idx[1]])
@@ -547,6 +581,7 @@ class FissPlusPlanner(FissPlanner):
                 winner = (refined, np.array([-1, -1, -1]))
         trajs, _ = self._materialize(batch, winner[0][None], [winner[1]])
         self.best_traj = trajs[0]
+        self._margins(batch, self.best_traj)
         return self.best_traj
 
     def _refine(self, batch: ProblemBatch, x: np.ndarray, coarse_cost: float, time_limit: float = float("inf")):

@@ -314,7 +314,7 @@ int fp_ctx_destroy(fp_ctx* ctx);
 int fp_ctx_set_option(fp_ctx* ctx, const char* name, int value);
 /* Reads an option back, or one of the read-only counters "clearance_launches" (launches of the clearance rescoring kernel,
  * fp_params.w_obstacle > 0, of this ctx so far), "looplog_launches" (launches of fp_loop_record's kernel), "rank_launches" (launches of
- * fp_rank_feasible's kernel), "boundary_launches" (launches of fp_boundary_mask's kernel), "predict_launches" (launches of
+ * fp_rank_feasible's kernel), "boundary_launches" (launches of fp_boundary_mask's kernel), "margin_launches" (launches of fp_traj_margins' kernel), "predict_launches" (launches of
  * fp_obstacles_predict's kernel), "from_state_launches" (launches of fp_from_state's kernel), "lattice_launches" (dense lattice launches of this ctx so far) and
  * "lattice_ordered_launches" (those dispatched in a feedback order or in the order of fp_batch.launch_order) - bench.py reports when an
  * order took effect -, "lattice_launches_2" / "_3" / "_4" (PROCESS-wide: fused lattice launches so far by workgroups per compute unit). */
@@ -421,6 +421,53 @@ typedef struct {
 
 int fp_boundary_mask(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, const fp_corridor* corridor, const double* cost_tbl,
                      uint32_t* flag_tbl, int32_t* best_idx, double* best_cost, int32_t* n_masked, int mem, void* stream);
+
+/* ---- the obstacle margin of chosen plans (added WITHIN ABI 18: detect it by looking the symbol up, e.g. dlsym) ------------
+ * fp_rank_feasible hands a behaviour layer K alternatives per ego as an index and a cost.  How close each of them comes to anything,
+ * when, and to what, is not in either number: a plan without FP_FLAG_COLLISION may pass 2 cm from a truck or 6 m from it, and it may
+ * even touch an obstacle at a pose has_collision never looks at (it checks every check_stride-th pose).  fp_traj_margins answers on
+ * the device, for K chosen plans per ego, against the obstacle table that is already resident.  It prices nothing and changes nothing.
+ *
+ * Definition, for plane k < K and ego b:
+ *   trajectory   the series fp_winner_trajs would write for best_idx[k][b] (a flat FOP index), or fp_eval_trajs for the end state
+ *                end_state[k][b] = (d, v, T); its points are 0 .. M-1, with x, y and yaw from the series.  M < 2: the series has no
+ *                heading, hence no pose.
+ *   poses        i = 0, pose_stride, 2 pose_stride, ... < min(M, final_time_step[scene] - t_now[b]) with 0 <= i + t_now[b] < T_obs;
+ *                each pose is the veh_l x veh_w rectangle at point i.  pose_stride = params->check_stride reproduces has_collision's
+ *                pose set (and the clearance term's), 1 looks at every pose.  params->check_stride itself is not used.
+ *   obstacles    the columns j of the ego's scene with a valid pose (valid != 0) at row i + t_now[b]; the shape is the rectangle of
+ *                obs_dims, or the column's ring (obs_poly / obs_nvert).
+ *   dist(i, j)   the Euclidean distance between the two shapes, 0 on contact (touching counts): the clearance term's distance.
+ *   min_dist     [K][B] the minimum of dist over all pairs; +inf when there is no pair (scene_of < 0, n_obs == 0, no pose in the
+ *                horizon, no valid column); NaN when there is no trajectory (index < 0, a NaN in the end state, more points than the
+ *                call is sized for - what makes fp_winner_trajs write a NaN series -, or batch->skip[b] != 0: such an ego's rows are
+ *                not read).
+ *   min_step, min_obs  [K][B] the point index i and the column j of the minimum.  Among equal distances the smallest i wins, then the
+ *                smallest j: for a plan in contact this is the first contact.  -1, -1 when min_dist is +inf or NaN.
+ * The layout is rank-major like fp_rank_feasible's: its rank_idx array is a valid best_idx argument with the same K, and the best_idx
+ * array of fp_plan_dense / fp_boundary_mask with K = 1.  end_state takes what fp_advance takes: the refined winners of fp_plan_fiss.
+ * Two calls give the same bits; the result depends neither on batch->launch_order nor on the memory space.  The kernel's arithmetic
+ * rounds differently from a restatement of the definition: distances agree to ~1e-12 m, and a contact within ~FP_AUDIT_GAP_TOL may be
+ * decided either way.  With pose_stride = check_stride the contact verdicts are the collision check's own (same arithmetic).
+ *
+ * FP_MEM_DEVICE: one kernel is enqueued (one workgroup per ego, in the order of batch->launch_order when there is one) - no
+ * allocation, no wait; it can be captured behind fp_plan_dense -> fp_rank_feasible.  FP_MEM_HOST stages the batch through the ctx
+ * and waits, like fp_winner_trajs.
+ * Errors: K < 1, K > FP_MAX_RANK, pose_stride < 1, both or neither of best_idx / end_state, a NULL output: FP_EINVAL.  The compiled-in
+ * limits answer as they do for fp_winner_trajs (FP_ELIMIT).  FP_MEM_HOST refuses an index >= nd*nv*nt of an ego that is not skipped
+ * (FP_EINVAL, naming ego and plane) and an end state whose T needs more than FP_MAX_POINTS points (FP_ELIMIT); FP_MEM_DEVICE treats
+ * both as "no trajectory".
+ * Also read-only in fp_ctx_get_option: "margin_launches" = launches of the kernel on this ctx so far (0 for a caller that never asks).
+ * Deliberately not done: no fp_shard_call slot, no loop-log columns, nothing inside fp_plan_step (a loop enqueues the call behind its
+ * plan call). */
+int fp_traj_margins(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, int32_t K,
+                    const int32_t* best_idx,     /* NULL or [K][B] */
+                    const double* end_state,     /* NULL or [K][B][3] */
+                    int32_t pose_stride,         /* >= 1 */
+                    double* min_dist,            /* [K][B] */
+                    int32_t* min_step,           /* [K][B] */
+                    int32_t* min_obs,            /* [K][B] */
+                    int mem, void* stream);
 
 /* ---- obstacle pose tables from tracks (added WITHIN ABI 18: detect it by looking the symbol up, e.g. dlsym) --------------
  * The reference has no predictor: it reads CommonRoad's recorded trajectories through `state_at_time` and skips an obstacle that has no
