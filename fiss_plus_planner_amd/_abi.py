@@ -31,7 +31,7 @@ _up = C.POINTER(C.c_uint32)
 
 # every symbol include/frenet_gpu.h declares (tests check the library exports all of them)
 EXPORTED_SYMBOLS = ("fp_abi_version", "fp_build_flags", "fp_build_compiler", "fp_last_error", "fp_device_count", "fp_device_info", "fp_ctx_create", "fp_ctx_destroy", "fp_ctx_set_option", "fp_ctx_get_option", "fp_ctx_join",
-                    "fp_plan_dense", "fp_winner_trajs", "fp_rank_feasible", "fp_boundary_mask", "fp_traj_margins", "fp_obstacles_predict", "fp_eval_trajs", "fp_plan_fiss", "fp_advance", "fp_plan_step", "fp_plan_fiss_step", "fp_loop_record", "fp_frames_build", "fp_from_state", "fp_materialize_all",
+                    "fp_plan_dense", "fp_winner_trajs", "fp_rank_feasible", "fp_boundary_mask", "fp_speed_envelope", "fp_traj_margins", "fp_obstacles_predict", "fp_eval_trajs", "fp_plan_fiss", "fp_advance", "fp_plan_step", "fp_plan_fiss_step", "fp_loop_record", "fp_frames_build", "fp_from_state", "fp_materialize_all",
                     "fp_group_create", "fp_group_destroy", "fp_group_submit", "fp_group_wait")
 
 
@@ -64,6 +64,11 @@ class FpResult(C.Structure):
 class FpCorridor(C.Structure):
     """The road edges as lateral offsets per reference-line knot (fp_boundary_mask)."""
     _fields_ = [("left", C.c_void_p), ("right", C.c_void_p), ("margin", C.c_double)]
+
+
+class FpSpeedProfile(C.Structure):
+    """Per-segment speed limits, read at s + front, and the lateral-acceleration bound on the reference line (fp_speed_envelope)."""
+    _fields_ = [("v_limit", C.c_void_p), ("front", C.c_double), ("tol", C.c_double), ("max_lat_accel", C.c_double)]
 
 
 FP_TRACK_NONE, FP_TRACK_LANE, FP_TRACK_ARC = 0, 1, 2  # fp_tracks.model (fp_obstacles_predict)
@@ -169,6 +174,9 @@ def load() -> C.CDLL:
     # (added within ABI 18: a library of the same version built before it lacks the symbol, and the attribute look-up says so)
     L.fp_boundary_mask.argtypes = [C.c_void_p, C.POINTER(FpParams), C.POINTER(FpBatch), C.POINTER(FpCorridor), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_int, C.c_void_p]
+    if hasattr(L, "fp_speed_envelope"):  # (a library of the same ABI version built before the symbol existed lacks it)
+        L.fp_speed_envelope.argtypes = [C.c_void_p, C.POINTER(FpParams), C.POINTER(FpBatch), C.POINTER(FpSpeedProfile), C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     L.fp_traj_margins.argtypes = [C.c_void_p, C.POINTER(FpParams), C.POINTER(FpBatch), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_int, C.c_void_p]
     L.fp_obstacles_predict.argtypes = [C.c_void_p, C.POINTER(FpParams), C.POINTER(FpBatch), C.POINTER(FpTracks), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]

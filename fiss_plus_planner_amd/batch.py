@@ -111,6 +111,13 @@ class ProblemBatch:
     bound_left: np.ndarray | None = None   # [F, NX]
     bound_right: np.ndarray | None = None  # [F, NX]
     bound_margin: float = 0.0              # extra distance kept from both edges (m)
+    # position-dependent speed limits the reference's data carries and its planner never sees (the last column of the reference path,
+    # planners/waymo_interface/waymo_interface.py:160-189; fp_speed_profile): the limit (m/s) of the SEGMENT that starts at every knot of
+    # every frame, +inf = none, 0 = stop line / red light; None = no profile = the reference's behaviour
+    speed_limit: np.ndarray | None = None  # [F, NX]
+    limit_front: float = 0.0               # the limit is read at s + limit_front (veh_l / 2: the front bumper obeys it)
+    limit_tol: float = 0.0                 # a point violates when s_d > limit + limit_tol
+    max_lat_accel: float = 0.0             # > 0: a point violates when s_d^2 |curvature of the reference line| exceeds it; 0 = off
     # the obstacle tracks obs_pose can be predicted from on the device (fp_tracks, fp_obstacles_predict; DeviceBatch.predict): the
     # model (FP_TRACK_*) and six numbers per obstacle column, and the frame the LANE tracks of every scene follow; None = no tracks
     track_model: np.ndarray | None = None  # [S, n_obs] int32
@@ -147,6 +154,9 @@ class ProblemBatch:
         if self.bound_left is not None:
             self.bound_left, self.bound_right = f8(self.bound_left), f8(self.bound_right)
             assert self.bound_left.shape == (self.F, self.NX) and self.bound_right.shape == (self.F, self.NX)
+        if self.speed_limit is not None:
+            self.speed_limit = f8(self.speed_limit)
+            assert self.speed_limit.shape == (self.F, self.NX)
         assert (self.track_model is None) == (self.track_state is None), "track_model and track_state come together"
         assert self.track_frame is None or self.track_model is not None, "track_frame without tracks"
         if self.track_model is not None:
@@ -203,6 +213,8 @@ class ProblemBatch:
             obs_nvert=None if self.obs_nvert is None else self.obs_nvert[keep_s],
             bound_left=None if self.bound_left is None else self.bound_left[fr],
             bound_right=None if self.bound_right is None else self.bound_right[fr], bound_margin=self.bound_margin,
+            speed_limit=None if self.speed_limit is None else self.speed_limit[fr], limit_front=self.limit_front, limit_tol=self.limit_tol,
+            max_lat_accel=self.max_lat_accel,
             track_model=None if self.track_model is None else self.track_model[keep_s],
             track_state=None if self.track_state is None else self.track_state[keep_s], track_frame=track_frame,
             meta=dict(self.meta, **(meta or {})))
@@ -228,6 +240,12 @@ class ProblemBatch:
                 a = getattr(self, name)
                 h.update(name.encode()); h.update(str(a.shape).encode()); h.update(np.ascontiguousarray(a).tobytes())
             h.update(b"bound_margin"); h.update(np.float64(self.bound_margin).tobytes())
+        if self.speed_limit is not None or self.max_lat_accel:  # (batches without a speed profile keep their digests)
+            if self.speed_limit is not None:
+                a = self.speed_limit
+                h.update(b"speed_limit"); h.update(str(a.shape).encode()); h.update(np.ascontiguousarray(a).tobytes())
+            for name in ("limit_front", "limit_tol", "max_lat_accel"):
+                h.update(name.encode()); h.update(np.float64(getattr(self, name)).tobytes())
         if self.track_model is not None:  # (batches without tracks keep their digests)
             for name in ("track_model", "track_state") + (("track_frame",) if self.track_frame is not None else ()):
                 a = getattr(self, name)

@@ -195,6 +195,7 @@ struct fp_ctx {
     int looplog_launches = 0;      // fp_ctx_get_option("looplog_launches"): launches of the loop-log kernel (fp_loop_record)
     int rank_launches = 0;         // fp_ctx_get_option("rank_launches"): launches of the ranking kernel (fp_rank_feasible)
     int boundary_launches = 0;     // fp_ctx_get_option("boundary_launches"): launches of the road-boundary kernel (fp_boundary_mask)
+    int envelope_launches = 0;     // fp_ctx_get_option("envelope_launches"): launches of the speed-envelope kernel (fp_speed_envelope)
     int margin_launches = 0;       // fp_ctx_get_option("margin_launches"): launches of the plan-margin kernel (fp_traj_margins)
     int predict_launches = 0;      // fp_ctx_get_option("predict_launches"): launches of the obstacle prediction kernel (fp_obstacles_predict)
     int from_state_launches = 0;   // fp_ctx_get_option("from_state_launches"): launches of the projection kernel (fp_from_state)
@@ -344,13 +345,13 @@ int host_points_max(const fp_params* p, const fp_batch* b, const double* extra_T
 }
 bool big_points(const fp_params& p) { return p.points_max > FP_FAST_POINTS; }
 
-int check_batch(const fp_batch* b)
+int check_batch(const fp_batch* b, bool need_coef = true)  // (need_coef = false: the caller decides itself whether it reads coef)
 {
     if (!b) return fail(FP_EINVAL, "batch is NULL");
     if (b->B < 0 || b->F < 1 || b->NX < 2) return fail(FP_EINVAL, "bad batch sizes B=%d F=%d NX=%d", b->B, b->F, b->NX);
     if (b->NX > FP_MAX_KNOTS) return fail(FP_ELIMIT, "NX=%d exceeds FP_MAX_KNOTS", b->NX);
     if (!b->d_samples || !b->t_samples || !b->v_samples || !b->target_speed || !b->ego || !b->frame_of || !b->scene_of ||
-        !b->t_now || !b->nx || !b->knots || !b->coef)
+        !b->t_now || !b->nx || !b->knots || (need_coef && !b->coef))
         return fail(FP_EINVAL, "batch has a NULL array");
     if (b->S > 0 && b->n_obs > 0 && (!b->obs_pose || !b->obs_dims || !b->final_time_step))
         return fail(FP_EINVAL, "batch has obstacles but a NULL obstacle array");
@@ -930,13 +931,13 @@ int overlap_join(fp_ctx* ctx, hipStream_t stream)
     return FP_OK;
 }
 
-int common_checks(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, int mem, void* stream = nullptr)
+int common_checks(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, int mem, void* stream = nullptr, bool need_coef = true)
 {
     if (!ctx) return fail(FP_EINVAL, "ctx is NULL");
     // any entry point but the overlapped dense path itself first joins what that path left in flight: its inputs may be those calls' outputs
     if (ctx->ov_pending[0] || ctx->ov_pending[1]) FP_TRY(overlap_join(ctx, mem == FP_MEM_DEVICE ? (hipStream_t)stream : ctx->stream));
     FP_TRY(check_params(params));
-    FP_TRY(check_batch(batch));
+    FP_TRY(check_batch(batch, need_coef));
     if (mem != FP_MEM_HOST && mem != FP_MEM_DEVICE) return fail(FP_EINVAL, "mem must be FP_MEM_HOST or FP_MEM_DEVICE");
     if (mem == FP_MEM_DEVICE && ctx->validate && batch->B > 0) FP_TRY(device_validate(ctx, params, batch, (hipStream_t)stream));
     return FP_OK;
@@ -1377,7 +1378,7 @@ int fp_ctx_get_option(fp_ctx* ctx, const char* name, int* value)
     const struct { const char* n; int v; } tab[] = {
         {"lattice_kernel", ctx->lattice_kernel}, {"lattice_split", ctx->lattice_split}, {"lattice_group", ctx->lattice_group}, {"lattice_tail", ctx->lattice_tail}, {"lattice_occupancy", ctx->lattice_occupancy}, {"resident_groups", ctx->resident_groups}, {"zero_copy_in", ctx->zero_copy_in}, {"stage_kernel", ctx->stage_kernel}, {"inline_inputs", ctx->inline_inputs}, {"lattice_order", ctx->lattice_order},
         {"refine_table_kb", ctx->refine_table_kb}, {"fiss_stages", ctx->fiss_stages}, {"fiss_jump", ctx->fiss_jump}, {"validate", ctx->validate}, {"lattice_winner", ctx->lattice_winner}, {"fiss_fused", ctx->fiss_fused}, {"appended_workgroups", ctx->appended_ok ? 1 : 0}, {"handover_failed", ctx->hand_err ? *(volatile int32_t*)ctx->hand_err : 0}, {"overlap", ctx->overlap}, {"overlapped_calls", ctx->overlapped_calls}, {"clearance_launches", ctx->clearance_launches + (ctx->twin ? ctx->twin->clearance_launches : 0)}, {"lattice_launches", ctx->lattice_launches + (ctx->twin ? ctx->twin->lattice_launches : 0)},
-        {"looplog_launches", ctx->looplog_launches}, {"rank_launches", ctx->rank_launches}, {"boundary_launches", ctx->boundary_launches}, {"margin_launches", ctx->margin_launches}, {"predict_launches", ctx->predict_launches}, {"from_state_launches", ctx->from_state_launches}, {"lattice_ordered_launches", ctx->lattice_ordered_launches + (ctx->twin ? ctx->twin->lattice_ordered_launches : 0)},
+        {"looplog_launches", ctx->looplog_launches}, {"rank_launches", ctx->rank_launches}, {"boundary_launches", ctx->boundary_launches}, {"envelope_launches", ctx->envelope_launches}, {"margin_launches", ctx->margin_launches}, {"predict_launches", ctx->predict_launches}, {"from_state_launches", ctx->from_state_launches}, {"lattice_ordered_launches", ctx->lattice_ordered_launches + (ctx->twin ? ctx->twin->lattice_ordered_launches : 0)},
         {"lattice_launches_2", (int)fp::lattice_launches_per_cu(0)}, {"lattice_launches_3", (int)fp::lattice_launches_per_cu(1)}, {"lattice_launches_4", (int)fp::lattice_launches_per_cu(2)}};
     for (const auto& t : tab)
         if (strcmp(name, t.n) == 0) { *value = t.v; return FP_OK; }
@@ -1607,6 +1608,63 @@ int fp_boundary_mask(fp_ctx* ctx, const fp_params* params, const fp_batch* batch
     FP_TRY(hs.commit(sl));
     LAUNCH_TRY(fp::launch_boundary_mask(a, ctx->stream), "road-boundary kernel");
     ++ctx->boundary_launches;
+    return hs.fetch_out();
+}
+
+int fp_speed_envelope(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, const fp_speed_profile* profile, const double* cost_tbl,
+                      uint32_t* flag_tbl, int32_t* best_idx, double* best_cost, int32_t* n_limited, int mem, void* stream)
+{
+    FP_TRY(common_checks(ctx, params, batch, mem, stream, /*need_coef=*/false));  // (coef is read by the lateral check alone: see below)
+    if (!profile || !profile->v_limit) return fail(FP_EINVAL, "fp_speed_envelope: profile / v_limit must not be NULL");
+    if (!cost_tbl || !flag_tbl || !best_idx || !best_cost) return fail(FP_EINVAL, "fp_speed_envelope: cost_tbl/flag_tbl/best_idx/best_cost must not be NULL");
+    const double dmax = 1.7976931348623157e308;
+    if (!(profile->front >= 0) || profile->front > dmax) return fail(FP_EINVAL, "fp_speed_envelope: front must be finite and >= 0");
+    if (!(profile->tol >= 0) || profile->tol > dmax) return fail(FP_EINVAL, "fp_speed_envelope: tol must be finite and >= 0");
+    if (!(profile->max_lat_accel >= 0) || profile->max_lat_accel > dmax) return fail(FP_EINVAL, "fp_speed_envelope: max_lat_accel must be finite and >= 0 (0 = off)");
+    const bool lateral = profile->max_lat_accel > 0;
+    if (lateral && !batch->coef) return fail(FP_EINVAL, "fp_speed_envelope: max_lat_accel > 0 needs batch->coef");
+    if (batch->B == 0) return FP_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t B = (size_t)batch->B, C = (size_t)params->nd * params->nv * params->nt, fn = (size_t)batch->F * batch->NX;
+    fp::EnvelopeArgs a;
+    a.B = batch->B; a.NX = batch->NX; a.nd = params->nd; a.nv = params->nv; a.nt = params->nt;
+    a.tick_t = params->tick_t; a.front = profile->front; a.tol = profile->tol; a.max_lat_accel = profile->max_lat_accel;
+    if (mem == FP_MEM_DEVICE) {
+        a.t_samples = batch->t_samples; a.v_samples = batch->v_samples; a.ego = batch->ego;
+        a.frame_of = batch->frame_of; a.nx = batch->nx; a.knots = batch->knots; a.coef = lateral ? batch->coef : nullptr; a.v_limit = profile->v_limit;
+        a.skip = batch->skip; a.perm = batch->launch_order;
+        a.cost_tbl = cost_tbl; a.flag_tbl = flag_tbl; a.best_idx = best_idx; a.best_cost = best_cost; a.n_limited = n_limited;
+        LAUNCH_TRY(fp::launch_speed_envelope(a, (hipStream_t)stream), "speed-envelope kernel");
+        ++ctx->envelope_launches;
+        return FP_OK;
+    }
+    // host arrays: only what the kernel reads travels (the lattice samples, the ego states, the knots, the limits, the two tables and - for
+    // the lateral check - the coefficients)
+    FP_TRY(check_frames_host(batch));
+    for (int f = 0; f < batch->F; ++f)
+        for (int k = 0; k + 1 < batch->nx[f]; ++k) {
+            const double l = profile->v_limit[(size_t)f * batch->NX + k];
+            if (!(l >= 0)) return fail(FP_EINVAL, "fp_speed_envelope: v_limit is %g at frame %d, knot %d (+inf says \"no limit\", 0 \"stop\")", l, f, k);
+        }
+    HostStage hs(ctx);
+    StageList sl;
+    sl.in(batch->t_samples, (size_t)params->nt, &a.t_samples);
+    sl.in(batch->v_samples, B * params->nv, &a.v_samples);
+    sl.in(batch->ego, B * 6, &a.ego);
+    sl.in(batch->frame_of, B, &a.frame_of);
+    sl.in(batch->nx, (size_t)batch->F, &a.nx);
+    sl.in(batch->knots, fn, &a.knots);
+    if (lateral) sl.in(batch->coef, fn * 8, &a.coef);
+    sl.in(profile->v_limit, fn, &a.v_limit);
+    if (batch->skip) sl.in(batch->skip, B, &a.skip);
+    sl.in(cost_tbl, B * C, &a.cost_tbl);
+    sl.in_mut(flag_tbl, B * C, &a.flag_tbl);
+    sl.out(best_idx, B, &a.best_idx);
+    sl.out(best_cost, B, &a.best_cost);
+    sl.out(n_limited, B, &a.n_limited);
+    FP_TRY(hs.commit(sl));
+    LAUNCH_TRY(fp::launch_speed_envelope(a, ctx->stream), "speed-envelope kernel");
+    ++ctx->envelope_launches;
     return hs.fetch_out();
 }
 

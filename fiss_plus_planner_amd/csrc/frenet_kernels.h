@@ -224,6 +224,30 @@ struct BoundaryArgs {
     int32_t* n_masked = nullptr;
 };
 hipError_t launch_boundary_mask(const BoundaryArgs& a, hipStream_t stream);
+// Position-dependent speed limits behind the dense pass (frenet_envelope.hip, fp_speed_envelope): ORs FP_FLAG_SPEED / FP_FLAG_ACCEL into
+// the flag words of flag_tbl [B][C] and writes the ego's argmin over what is still feasible.  One workgroup per ego, in the order of perm
+// (optional).  Device addresses; v_limit is [F][NX] (the limit of the segment that starts at the knot); coef is read only when
+// max_lat_accel > 0; n_limited (optional) [B].
+struct EnvelopeArgs {
+    int B = 0, NX = 0, nd = 1, nv = 1, nt = 1;
+    double tick_t = 0.0, front = 0.0, tol = 0.0, max_lat_accel = 0.0;
+    const double* t_samples = nullptr;
+    const double* v_samples = nullptr;
+    const double* ego = nullptr;
+    const int32_t* frame_of = nullptr;
+    const int32_t* nx = nullptr;
+    const double* knots = nullptr;
+    const double* coef = nullptr;
+    const double* v_limit = nullptr;
+    const int32_t* skip = nullptr;
+    const int32_t* perm = nullptr;
+    const double* cost_tbl = nullptr;
+    uint32_t* flag_tbl = nullptr;
+    int32_t* best_idx = nullptr;
+    double* best_cost = nullptr;
+    int32_t* n_limited = nullptr;
+};
+hipError_t launch_speed_envelope(const EnvelopeArgs& a, hipStream_t stream);
 // The obstacle margin of K chosen plans per ego (frenet_margins.hip, fp_traj_margins): one workgroup per ego, in the order of perm
 // (optional).  ka.p.check_stride is the call's pose_stride; ka.r is not read.  Device addresses; exactly one of best_idx [K][B] /
 // end_state [K][B][3] set; the outputs are [K][B].

@@ -33,6 +33,7 @@ class DeviceBatch:
         self.dev = torch.device("cuda", device)
         self.t = {k: torch.from_numpy(np.ascontiguousarray(getattr(batch, k))).to(self.dev) for k in _NAMES}
         for k in ("samp_min", "samp_max", "samp_res", "obs_poly", "obs_nvert", "bound_left", "bound_right",  # (the corridor: boundary_mask_device)
+                  "speed_limit",  # (the per-segment speed limits: speed_envelope_device)
                   "track_model", "track_state", "track_frame"):  # (the obstacle tracks: predict)
             if getattr(batch, k, None) is not None:
                 self.t[k] = torch.from_numpy(getattr(batch, k)).to(self.dev)

@@ -135,6 +135,10 @@ def fiss_rounds(kind, max_refine_iters: int) -> int:
     return int(max_refine_iters) if kind in ("FISS+", _abi.FP_FISS_PLUS) else 0
 
 
+def _has_speed_profile(batch) -> bool:
+    return getattr(batch, "speed_limit", None) is not None or float(getattr(batch, "max_lat_accel", 0.0) or 0.0) > 0.0
+
+
 def _check_out(out: SimpleNamespace, B: int, spec: dict) -> None:
     """Caller-provided output arrays cross the C ABI as bare addresses: every array the call writes must be a writable,
     C-contiguous array of the dtype and shape [B, ...] the engine would have allocated itself (a strided or wrong-dtype array
@@ -206,7 +210,8 @@ class FrenetEngine:
             best_traj=(np.full((B, 16, traj_stride), np.nan) if traj_sparse else np.empty((B, 16, traj_stride))) if winner else None)
 
     def plan_dense(self, batch: ProblemBatch, tables: bool = True, winner: bool = False, traj_stride: int = TRAJ_STRIDE, traj_sparse: bool = False,
-                   out: SimpleNamespace | None = None, audit: bool = False, top_k: int = 0, boundary: bool = False, margins: bool = False):
+                   out: SimpleNamespace | None = None, audit: bool = False, top_k: int = 0, boundary: bool = False, margins: bool = False,
+                   envelope: bool = False):
         """FrenetOptimalPlanner.plan() for every ego of the batch (reference frenet_optimal_planner.py:247-270).
 
         Returns best_idx [B] (flat (i_d*nt+i_T)*nv+i_v, -1 = none), best_cost [B], stats [B,4] and, with
@@ -221,34 +226,46 @@ class FrenetEngine:
         FLAG_BOUNDARY, top_k ranks the masked tables, also n_masked [B]; with winner=True the series come from winner_trajs on the new
         best_idx (the lattice launch's own series may belong to a masked winner).  margins=True: also margin_dist / margin_step /
         margin_obs (traj_margins at the batch's check_stride) of the result - [B] for best_idx, or [top_k, B] for rank_idx together with
-        top_k; with boundary=True they are taken on the masked result.
+        top_k; with boundary=True they are taken on the masked result.  envelope=True (the batch must carry a speed profile:
+        speed_limit and / or max_lat_accel): the position-dependent speed limits (speed_envelope) run behind the dense call over its
+        tables, before the boundary check when both are asked for; best_idx / best_cost are the argmin among the candidates that obey the
+        envelope (and the corridor), `flags` carry the added FLAG_SPEED / FLAG_ACCEL bits, also n_limited [B]; top_k, margins and
+        winner=True follow the masked result like with boundary=True.
         """
         if margins:
-            out = self.plan_dense(batch, tables, winner, traj_stride, traj_sparse, out, audit, top_k, boundary)
+            out = self.plan_dense(batch, tables, winner, traj_stride, traj_sparse, out, audit, top_k, boundary, envelope=envelope)
             plans = out.rank_idx if top_k else out.best_idx
             if batch.B:
                 out.margin_dist, out.margin_step, out.margin_obs = self.traj_margins(batch, best_idx=plans)
             else:
                 out.margin_dist, out.margin_step, out.margin_obs = np.empty(plans.shape), np.empty(plans.shape, dtype=np.int32), np.empty(plans.shape, dtype=np.int32)
             return out
-        if boundary:
-            if getattr(batch, "bound_left", None) is None:
+        if boundary or envelope:
+            if boundary and getattr(batch, "bound_left", None) is None:
                 raise ValueError("plan_dense(boundary=True): the batch carries no corridor (ProblemBatch.bound_left / bound_right)")
+            if envelope and not _has_speed_profile(batch):
+                raise ValueError("plan_dense(envelope=True): the batch carries no speed profile (ProblemBatch.speed_limit / max_lat_accel)")
             if audit:
-                raise ValueError("plan_dense(boundary=True, audit=True): the audit bits describe the dense call's own answer, not the masked one")
+                raise ValueError("plan_dense(boundary / envelope=True, audit=True): the audit bits describe the dense call's own answer, not the masked one")
             want_tables = tables
             if out is not None and not tables:  # the caller's arrays hold no tables: the call brings its own
                 out.cost, out.flags = np.empty((batch.B, batch.C)), np.empty((batch.B, batch.C), dtype=np.uint32)
                 out.__dict__.pop("_res", None)
             out = self.plan_dense(batch, True, winner, traj_stride, traj_sparse, out)
             if batch.B:
-                _, bi, bc, out.n_masked = self.boundary_mask(batch, out.cost, out.flags, inplace=True)
+                if envelope:  # (first: the boundary check's argmin then honours its bits)
+                    _, bi, bc, out.n_limited = self.speed_envelope(batch, out.cost, out.flags, inplace=True)
+                if boundary:
+                    _, bi, bc, out.n_masked = self.boundary_mask(batch, out.cost, out.flags, inplace=True)
                 out.best_idx[...], out.best_cost[...] = bi, bc
                 if winner:
                     w = self.winner_trajs(batch, out.best_idx, traj_stride, traj_sparse)
                     out.best_flags[...], out.best_traj[...] = w.best_flags, w.best_traj
             else:
-                out.n_masked = np.empty(0, dtype=np.int32)
+                if envelope:
+                    out.n_limited = np.empty(0, dtype=np.int32)
+                if boundary:
+                    out.n_masked = np.empty(0, dtype=np.int32)
             if top_k:
                 if not 1 <= int(top_k) <= _abi.FP_MAX_RANK:
                     raise ValueError(f"top_k={top_k}: 0 (off) or 1 .. FP_MAX_RANK ({_abi.FP_MAX_RANK})")
@@ -362,6 +379,42 @@ class FrenetEngine:
         cor = _abi.FpCorridor(left or None, right or None, float(margin))
         _abi.check(self._lib.fp_boundary_mask(self._ctx, C.byref(params), C.byref(fb), C.byref(cor), cost_tbl or None, flag_tbl or None, best_idx or None,
                                               best_cost or None, n_masked or None, _abi.FP_MEM_DEVICE, stream or None))
+
+    def speed_envelope(self, batch: ProblemBatch, cost: np.ndarray, flags: np.ndarray, skip: np.ndarray | None = None, inplace: bool = False):
+        """Position-dependent speed limits and stop lines over plan_dense's tables (fp_speed_envelope; the definition:
+        include/frenet_gpu.h): cost [B,C], flags [B,C] and the batch's speed profile (speed_limit [F,NX] - None = no limit anywhere -,
+        limit_front, limit_tol, max_lat_accel) -> (flags, best_idx, best_cost, n_limited): the flag words with FLAG_SPEED / FLAG_ACCEL
+        ORed in where a checked point violates (a copy, unless inplace=True and `flags` is a contiguous uint32 array; no bit is ever
+        cleared), the argmin among the candidates without a FLAG_INFEASIBLE bit, and the number of candidates per ego that violate in
+        this call.  skip [B] (optional): egos whose rows are neither read nor written (-1 / NaN / 0)."""
+        if not _has_speed_profile(batch):
+            raise ValueError("speed_envelope: the batch carries no speed profile (ProblemBatch.speed_limit / max_lat_accel)")
+        B, Cn = batch.B, batch.C
+        cost = np.ascontiguousarray(cost, dtype=np.float64)
+        if not (inplace and isinstance(flags, np.ndarray) and flags.dtype == np.uint32 and flags.flags.c_contiguous and flags.flags.writeable):
+            flags = np.array(flags, dtype=np.uint32, order="C", copy=True)
+        if cost.shape != (B, Cn) or flags.shape != (B, Cn):
+            raise ValueError(f"speed_envelope: cost / flags must be [B={B}, C={Cn}] tables, got {cost.shape} / {flags.shape}")
+        best_idx = np.empty(B, dtype=np.int32); best_cost = np.empty(B); n_limited = np.empty(B, dtype=np.int32)
+        p, fb = host_structs(batch)
+        if skip is not None:
+            skip = np.ascontiguousarray(skip, dtype=np.int32)
+            assert skip.shape == (B,)
+            fb.skip = _ptr(skip)
+        limit = batch.speed_limit if batch.speed_limit is not None else np.full((batch.F, batch.NX), np.inf)
+        prof = _abi.FpSpeedProfile(_ptr(limit), float(batch.limit_front), float(batch.limit_tol), float(batch.max_lat_accel))
+        _abi.check(self._lib.fp_speed_envelope(self._ctx, C.byref(p), C.byref(fb), C.byref(prof), _ptr(cost), _ptr(flags), _ptr(best_idx), _ptr(best_cost),
+                                               _ptr(n_limited), _abi.FP_MEM_HOST, None))
+        return flags, best_idx, best_cost, n_limited
+
+    def speed_envelope_device(self, params: _abi.FpParams, fb: _abi.FpBatch, v_limit: int, front: float, tol: float, max_lat_accel: float,
+                              cost_tbl: int, flag_tbl: int, best_idx: int, best_cost: int, n_limited: int = 0, stream: int = 0):
+        """Enqueue the speed envelope behind a dense call (device addresses): v_limit [F][NX], the dense call's cost_tbl / flag_tbl
+        [B][C] (flag_tbl in/out), best_idx / best_cost [B] out, n_limited [B] or 0.  best_idx is a valid argument of
+        winner_trajs_device / fp_advance as it stands, the tables of boundary_mask_device / rank_feasible_device."""
+        prof = _abi.FpSpeedProfile(v_limit or None, float(front), float(tol), float(max_lat_accel))
+        _abi.check(self._lib.fp_speed_envelope(self._ctx, C.byref(params), C.byref(fb), C.byref(prof), cost_tbl or None, flag_tbl or None, best_idx or None,
+                                               best_cost or None, n_limited or None, _abi.FP_MEM_DEVICE, stream or None))
 
     def traj_margins(self, batch: ProblemBatch, best_idx: np.ndarray | None = None, end_state: np.ndarray | None = None, pose_stride: int | None = None,
                      skip: np.ndarray | None = None):

@@ -189,6 +189,29 @@ class FrenetOptimalPlanner:
             raise ValueError(f"set_road_boundary: margin = {margin} must be finite and >= 0")
         self._boundary = (left, right, float(margin))
 
+    def set_speed_profile(self, v_limit, front: float | None = None, tol: float = 0.05, max_lat_accel: float = 0.0):
+        """Position-dependent speed limits for plan(): one value per centre-line point handed to generate_frenet_frame() - the limit
+        (m/s) of the segment that STARTS at that point, +inf = none, 0 = stop line / red light (spline.limits_from_path_column maps the
+        reference's Waymo-style path column) - read at s + front (None: vehicle.l / 2, the front bumper), violated when s_d > limit +
+        tol; max_lat_accel > 0 also rejects the candidates whose s_d^2 |curvature of the reference line| exceeds it somewhere.  plan()
+        then returns the cheapest candidate that obeys the envelope at every point (fp_speed_envelope, include/frenet_gpu.h).
+        v_limit = None: no limits (with max_lat_accel = 0 the profile is removed again).
+        FOP+, FISS and FISS+ order candidates by cost before validation and raise ValueError."""
+        if self.KIND != "FOP":
+            raise ValueError(f"set_speed_profile: the speed envelope is defined for FrenetOptimalPlanner only "
+                             f"({self.KIND} orders candidates by cost before validation)")
+        front = 0.5 * float(self.vehicle.l) if front is None else float(front)
+        for name, v in (("front", front), ("tol", tol), ("max_lat_accel", max_lat_accel)):
+            if not (np.isfinite(v) and v >= 0):
+                raise ValueError(f"set_speed_profile: {name} = {v} must be finite and >= 0")
+        if v_limit is None:
+            self._speed_profile = (None, front, float(tol), float(max_lat_accel)) if max_lat_accel > 0 else None
+            return
+        v_limit = np.array(v_limit, dtype=np.float64).ravel()
+        if np.isnan(v_limit).any() or (v_limit < 0).any():
+            raise ValueError("set_speed_profile: v_limit needs one value per centre-line point, none of them NaN or negative")
+        self._speed_profile = (v_limit, front, float(tol), float(max_lat_accel))
+
     # ------------------------------------------------------------------ problem marshalling
     def _predicted_table(self, tracks: ObstacleTracks, time_step_now: int) -> ObstacleTable:
         """The pose table of an ObstacleTracks against this planner's own frame: the track states are valid at time_step_now and
@@ -250,9 +273,12 @@ class FrenetOptimalPlanner:
         bound = getattr(self, "_boundary", None) if getattr(st, "check_boundary", False) else None
         if bound is not None and len(bound[0]) != len(sp.knots):
             raise ValueError(f"set_road_boundary: {len(bound[0])} edge values for a centre line of {len(sp.knots)} points")
+        prof = getattr(self, "_speed_profile", None)
+        if prof is not None and prof[0] is not None and len(prof[0]) != len(sp.knots):
+            raise ValueError(f"set_speed_profile: {len(prof[0])} limits for a centre line of {len(sp.knots)} points")
         cache_tables = getattr(self, "cache_tables", True)
         key = (id(sp), id(tab), getattr(tab, "version", 0), cache_tables, st.num_width, st.num_speed, st.num_t, st.min_t, st.max_t, st.tick_t, st.max_road_width, st.lowest_speed,
-               self.vehicle.l, self.vehicle.w, self.vehicle.max_speed, self.vehicle.max_accel, curv, w_obs, id(bound))
+               self.vehicle.l, self.vehicle.w, self.vehicle.max_speed, self.vehicle.max_accel, curv, w_obs, id(bound), id(prof))
         cache = getattr(self, "_batch_cache", None)
         if cache is None or cache[0] != key:
             sw = self._sampling_width()
@@ -272,7 +298,9 @@ class FrenetOptimalPlanner:
                 obs_poly=None if tab is None or tab.nvert is None else tab.poly[None],
                 obs_nvert=None if tab is None or tab.nvert is None else tab.nvert[None],
                 bound_left=None if bound is None else bound[0][None], bound_right=None if bound is None else bound[1][None],
-                bound_margin=0.0 if bound is None else bound[2])
+                bound_margin=0.0 if bound is None else bound[2],
+                speed_limit=None if prof is None or prof[0] is None else prof[0][None], limit_front=0.0 if prof is None else prof[1],
+                limit_tol=0.0 if prof is None else prof[2], max_lat_accel=0.0 if prof is None else prof[3])
             # fp_batch.tables_tag: the library keeps this batch's spline and obstacle tables on the device until the planner builds
             # a new batch (another centerline / another obstacle list / ObstacleTable.update()) - per cycle only the start state
             # travels.  Contract (class docstring): the cached arrays are frozen, so an in-place edit raises instead of going stale;
@@ -284,7 +312,7 @@ class FrenetOptimalPlanner:
                 sp.knots.setflags(write=False)
                 sp.coef.setflags(write=False)
             host_structs(batch, freeze=True)  # (this batch is the planner's own: its arrays are only ever updated in place)
-            cache = [key, batch, None, sp, tab, bound]  # sp / tab / bound kept alive so their ids cannot be recycled
+            cache = [key, batch, None, sp, tab, bound, prof]  # sp / tab / bound / prof kept alive so their ids cannot be recycled
             self._batch_cache = cache
         batch = cache[1]
         if cache[2] != st.highest_speed:
@@ -332,8 +360,9 @@ class FrenetOptimalPlanner:
         reuse = outs.get(key)
         if reuse is None:
             reuse = outs[key] = self._engine.dense_outputs(1, batch.C, True, winner, stride)
-        # (a corridor on the batch: the road-boundary check runs behind the dense call and decides the winner)
-        out = self._engine.plan_dense(batch, tables=True, winner=winner, traj_stride=stride, out=reuse, boundary=batch.bound_left is not None)
+        # (a corridor / a speed profile on the batch: the checks run behind the dense call and decide the winner)
+        out = self._engine.plan_dense(batch, tables=True, winner=winner, traj_stride=stride, out=reuse, boundary=batch.bound_left is not None,
+                                      envelope=batch.speed_limit is not None or batch.max_lat_accel > 0)
         self.last_tables = (out.cost[0].copy(), out.flags[0].copy())
         if self.materialize_all:  # visualisation payload (reference :102): every candidate's series in one launch
             m = self._engine.materialize_all(batch, traj_stride=stride)

@@ -173,3 +173,16 @@ class CubicSpline2D:
         d2x = 2 * c[2, i] + 6 * c[3, i] * dx
         d2y = 2 * c[6, i] + 6 * c[7, i] * dx
         return px, py, np.arctan2(d1y, d1x), (d2y * d1x - d2x * d1y) / (d1x ** 2 + d1y ** 2) ** 1.5
+
+
+def limits_from_path_column(values) -> np.ndarray:
+    """Per-segment speed limits (fp_speed_profile.v_limit, ProblemBatch.speed_limit, FrenetOptimalPlanner.set_speed_profile) from the
+    last column of the reference path the reference's Waymo interface receives - "0 is red light, 1 is crosswalk, other is speed_limi[t]"
+    (planners/waymo_interface/waymo_interface.py:160-189): 0 -> 0.0 (a red light: stop before it), 1 -> +inf (a crosswalk carries no
+    limit), anything else -> itself (m/s).  Assumes ONE value per knot of the Frenet frame, i.e. the column of the very points handed to
+    generate_frenet_frame(): entry k becomes the limit of the segment that starts at knot k (the last entry starts no segment and is
+    ignored by the check).  NaN and negative values raise."""
+    v = np.array(values, dtype=np.float64)
+    if np.isnan(v).any() or (v < 0).any():
+        raise ValueError("limits_from_path_column: the column holds a NaN or a negative value")
+    return np.where(v == 1.0, np.inf, v)

@@ -314,7 +314,7 @@ int fp_ctx_destroy(fp_ctx* ctx);
 int fp_ctx_set_option(fp_ctx* ctx, const char* name, int value);
 /* Reads an option back, or one of the read-only counters "clearance_launches" (launches of the clearance rescoring kernel,
  * fp_params.w_obstacle > 0, of this ctx so far), "looplog_launches" (launches of fp_loop_record's kernel), "rank_launches" (launches of
- * fp_rank_feasible's kernel), "boundary_launches" (launches of fp_boundary_mask's kernel), "margin_launches" (launches of fp_traj_margins' kernel), "predict_launches" (launches of
+ * fp_rank_feasible's kernel), "boundary_launches" (launches of fp_boundary_mask's kernel), "envelope_launches" (launches of fp_speed_envelope's kernel), "margin_launches" (launches of fp_traj_margins' kernel), "predict_launches" (launches of
  * fp_obstacles_predict's kernel), "from_state_launches" (launches of fp_from_state's kernel), "lattice_launches" (dense lattice launches of this ctx so far) and
  * "lattice_ordered_launches" (those dispatched in a feedback order or in the order of fp_batch.launch_order) - bench.py reports when an
  * order took effect -, "lattice_launches_2" / "_3" / "_4" (PROCESS-wide: fused lattice launches so far by workgroups per compute unit). */
@@ -421,6 +421,75 @@ typedef struct {
 
 int fp_boundary_mask(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, const fp_corridor* corridor, const double* cost_tbl,
                      uint32_t* flag_tbl, int32_t* best_idx, double* best_cost, int32_t* n_masked, int mem, void* stream);
+
+/* ---- position-dependent speed limits and stop lines (added WITHIN ABI 18: detect it by looking the symbol up, e.g. dlsym) ----
+ * The planner knows one speed limit, fp_params.max_speed: one number for the whole batch, line and horizon (`any(s_d > max_speed)`,
+ * frenet_optimal_planner.py:152).  The reference's second caller receives more - the last column of its reference path holds, per
+ * point, "0 is red light, 1 is crosswalk, other is speed_limi[t]" (planners/waymo_interface/waymo_interface.py:160-189) - and hands the
+ * planner `np.amax(ref_path[:, -1])`, the largest value anywhere on the path: a 30 km/h zone, a red light 60 m ahead and a bend that
+ * cannot be taken at 13 m/s all look the same to the lattice.  fp_speed_envelope finishes it, behind fp_plan_dense and over its tables:
+ * cost_tbl / flag_tbl are [B][C] (C = nd*nv*nt) as fp_plan_dense wrote them.
+ *
+ * Definition, for every candidate c of every ego b that is not skipped, N and M taken from the candidate's flag word:
+ *   checked points   i = 1 .. M-1 of the trajectory.  Point 0 is the ego's present state, common to all candidates: it selects
+ *                    nothing.  M <= 1: nothing is checked, no bit is set.
+ *   at point i       s, s_d = the candidate's longitudinal series values at t = i * tick_t (rows FP_ARR_S, FP_ARR_S_D); f = frame_of[b].
+ *   speed limit      s_q = s + front;  k_q = bisect_right(knots, s_q) - 1, clamped to 0 .. nx-2;  lim = v_limit[f][k_q].
+ *                    Violation A: s_d > lim + tol (never for lim = +inf).  A stop line or a red light is a stretch of segments with
+ *                    lim = 0: a candidate that is at rest (s_d <= tol) before s + front reaches the stretch survives, every other one
+ *                    violates.
+ *   lateral accel.   only when max_lat_accel > 0:  k = the segment index the Cartesian conversion uses for s, clamped to nx-2 (as in
+ *                    fp_boundary_mask);  dx = s - knots[k];  x' = bx + 2 cx dx + 3 dx_ dx^2,  x'' = 2 cx + 6 dx_ dx, and y', y''
+ *                    likewise (bx, cx, dx_ = rows 1, 2, 3 of coef; rows 5, 6, 7 for y);
+ *                    kappa_r = (x' y'' - y' x'') / (x'^2 + y'^2)^1.5, the curvature of the REFERENCE LINE at s.
+ *                    Violation B: s_d * s_d * |kappa_r| > max_lat_accel.  The (1 - kappa d) factor and d_dd are deliberately NOT
+ *                    applied - the same choice fp_boundary_mask made for its heading.
+ *   the bits         violation A at any checked point ORs FP_FLAG_SPEED into the candidate's flag word, violation B FP_FLAG_ACCEL.  The
+ *                    low byte of the flag word is full, and these two bits already mean "too fast somewhere" and "too much acceleration
+ *                    somewhere": the envelope refines what is allowed.  The call NEVER CLEARS a bit - the lattice's own verdict lives in
+ *                    the same bits - so it is idempotent; a caller who wants another envelope runs the dense call again or keeps a copy
+ *                    of flag_tbl.  No other bit changes and cost_tbl is never written.  Candidates that are already infeasible are
+ *                    evaluated too.
+ *   best_idx / best_cost  [B] the argmin of cost_tbl over the candidates with no FP_FLAG_INFEASIBLE bit and a cost that is not NaN; the
+ *                    last minimum in FOP order wins exact ties (:263-268); -1 / NaN when there is none.  Bit for bit plane 0 of an
+ *                    fp_rank_feasible call on the masked tables, and a valid argument of fp_advance, fp_winner_trajs, fp_traj_margins;
+ *                    the masked tables are valid arguments of fp_boundary_mask.
+ *   n_limited        NULL or [B]: the candidates of the ego with violation A or B in THIS call, whatever bits they carried before.
+ *   Stats            do not change (FOP counts every candidate regardless).
+ *   skipped egos     batch->skip[b] != 0: -1 / NaN / 0, the ego's rows are neither read nor written.
+ * s, s_d and M depend on the candidate's longitudinal profile (i_v, i_T) alone (calc_global_paths stops at the first s off the line,
+ * :112-113), so the nd candidates of a profile share one verdict; the kernel evaluates nv*nt profiles per ego, not nd*nv*nt candidates.
+ * Its series arithmetic (fma Horner) rounds differently from a point-by-point restatement: a point with s_d within ~FP_AUDIT_GAP_TOL
+ * of its threshold may be decided either way by another rounding of the same numbers, and so may a point with s_q within that of a
+ * knot where the limit changes.
+ *
+ * FP_MEM_DEVICE: one kernel is enqueued (one workgroup per ego, in the order of batch->launch_order when there is one) - no
+ * allocation, no wait; it can be captured directly behind a dense call in a linear chain.  FP_MEM_HOST stages the tables and the
+ * profile through the ctx and waits, like fp_boundary_mask.  Batch fields used: B, F, NX, nx, knots, coef (only when
+ * max_lat_accel > 0), frame_of, ego, t_samples, v_samples, skip, launch_order.
+ * Errors: a NULL mandatory pointer (profile, v_limit, cost_tbl, flag_tbl, best_idx, best_cost; coef when max_lat_accel > 0), front /
+ * tol negative or not finite, max_lat_accel negative or not finite: FP_EINVAL; (FP_MEM_HOST only) a NaN or a negative value in a used
+ * entry of v_limit: FP_EINVAL, the message names frame and knot; nd*nv*nt > FP_MAX_CAND: FP_ELIMIT.  A NaN a FP_MEM_DEVICE caller
+ * leaves in a used entry compares false: it means "no limit there" (a negative entry violates at every speed above it).
+ * Also read-only in fp_ctx_get_option: "envelope_launches" = launches of the kernel on this ctx so far (0 for a caller that never asks:
+ * such a caller gets the bits and the launch counts it got before the symbol existed).
+ *
+ * Deliberately not done:
+ *   - fp_plan_step and the FISS entry points take no profile.  A closed loop that wants the envelope enqueues fp_plan_dense ->
+ *     fp_speed_envelope -> fp_advance.
+ *   - fp_shard_call has no slot for it.
+ *   - there is no time-dependent limit (a light that turns green): the profile is a function of s alone. */
+typedef struct {
+    const double* v_limit;  /* [F][NX] speed limit (m/s) of the SEGMENT that starts at knot k: it holds on knots[k] <= s < knots[k+1].
+                               +inf = no limit there.  Entries k >= nx[f] - 1 are ignored. */
+    double front;           /* >= 0, finite: the limit is read at s + front (veh_l / 2 = the front bumper obeys the sign / stop line) */
+    double tol;             /* >= 0, finite: a point violates when s_d > limit + tol */
+    double max_lat_accel;   /* 0 = off; > 0 finite: a point violates when s_d^2 |kappa_r(s)| > max_lat_accel, kappa_r = curvature of the reference line */
+} fp_speed_profile;
+
+int fp_speed_envelope(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, const fp_speed_profile* profile,
+                      const double* cost_tbl, uint32_t* flag_tbl, int32_t* best_idx, double* best_cost, int32_t* n_limited,
+                      int mem, void* stream);
 
 /* ---- the obstacle margin of chosen plans (added WITHIN ABI 18: detect it by looking the symbol up, e.g. dlsym) ------------
  * fp_rank_feasible hands a behaviour layer K alternatives per ego as an index and a cost.  How close each of them comes to anything,
