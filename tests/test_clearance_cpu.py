@@ -4,6 +4,7 @@ without the feature would pass) and leave no near tie (or "best_idx exact" would
 import numpy as np
 import pytest
 
+import clearance_cases as K
 import clearance_ref as R
 from fiss_plus_planner_amd import synth
 
@@ -67,6 +68,37 @@ def test_fixture_search_recorded(oracle, name):
     assert has.sum() >= 4 and 4 * moved >= has.sum()
     for e in range(b.B):
         assert R.margin(cost[e], flags[e]) > 1e-6, e
+
+
+@pytest.mark.parametrize("name", sorted(K.PATH_CASES))
+def test_path_cases_recorded(oracle, name):
+    """The cases of tests/clearance_cases.py (chunk loop, rows from the scene table, t_now > 0, mixed knot counts, broad phase, the
+    lattice instances underneath): every compared ego decidable, the path reached by the batch's own numbers, the term at work there.  Recorded:
+      chunk 1024    egos 2, 6   plain 514, 634 -> 514, 578      margin 2.2e-4   survivors 288 / 384
+      chunk 1025    egos 1, 4   214, 615 -> 214, 410            1.1e-3          [1024, 1] / [82, 0]; candidate 1024 survives, 50 poses
+      chunk 2197    egos 4, 6   1184, 1356 -> 1015, 1356        4.1e-4          [44, 44, 3] / [287, 286, 38]; 1184 -> 1015 changes chunk
+      scene table   egos 1, 3   51, 45 -> 61, 65                2.2e-4          50 / 25 survivors, 80 .. 99 poses
+      padded table  egos 0, 2   109, 51 -> 124, 76              5.4e-3          31 / 40 survivors
+      t_now lds     egos 0 - 3  29, 79, 74, 72 -> 29, 79, 74, 97   3.7e-4       poses 20 / 25 / 0 / 40 .. 46 (40 .. 50 at t_now 0)
+      t_now table   egos 0, 1, 3, 4   29, 79, 74, 54 -> 54, 54, 74, 54   8.1e-5  poses 20 / 39 / 40 .. 46 / 0
+      mixed knots   egos 0, 2, 3, 4   54, 49, 74, 74 -> 29, 74, 74, 74   1.2e-2  poses 40 .. 50 / 40 .. 50 / 9 / 7; staged: no, no, yes, yes
+      broad phase   egos 0, 1, 2      49, 94, 73 -> 44, 94, 63           9.2e-5  far pairs inside / beyond the radius 33 / 207 and 80 / 400
+      short table   egos 1, 7, 10, 14  94, 54, 54, 54 -> 94, 59, 89, 64  1.1e-4  25 poses each (final_time_step 49); lattice plain/3, plain/4
+      knots 220 / 400   the same egos, winners and poses on 220- / 400-knot lines  1.1e-4  lattice window/4 wcap 141, window/3 wcap 232"""
+    assert K.W == W_TEST
+    rec = K.prove(oracle, name)
+    print(name, rec)
+
+
+def test_closed_loop_cycles_recorded(oracle):
+    """Three cycles of the config-2 batch under the weight, simulated with the restatement: egos 0, 1, 2 have a winner and no near
+    tie at t_now = 0, 1 and 2 (recorded winners 39, 94, 63 / 74, 99, 53 / 74, 99, 53; smallest margin 1.5e-4)."""
+    loop = K.loop_reference(oracle)
+    assert len(loop) == K.LOOP_CYCLES == 3
+    for cycle, (ego, idx, best, margins) in enumerate(loop):
+        print("cycle", cycle, "winners", idx, "margins", margins)
+        assert min(idx) >= 0 and min(margins) > 1e-6, cycle
+    assert not np.array_equal(loop[0][0], loop[2][0])
 
 
 def test_settings_and_batch_carry_the_weight():

@@ -1,12 +1,18 @@
 """GPU: the obstacle-clearance cost term (fp_params.w_obstacle) against its independent restatement (tests/clearance_ref.py: oracle
 tables + brute-force distances).  Costs within the project's bar (|d| <= 1e-9 max(1, |ref|), tests/test_gpu_edges.py::cost_close),
 flags and Stats exact, best_idx exact for every ego.  tests/test_clearance_cpu.py shows that the cases could not pass by returning the
-plain winner."""
+plain winner.
+
+The cases of tests/clearance_cases.py take the kernel where the config-2 / config-3 cases never go - a second and a third chunk of 1024
+candidates, obstacle rows read from the scene table, t_now > 0, lines of different knot counts in one launch, the broad-phase skip,
+the multi-round and windowed lattice instances underneath, a launch order, the later cycles of a closed loop - with the same
+comparisons; tests/test_clearance_cpu.py proves on the CPU that each of them reaches its path and is decidable."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+import clearance_cases as K
 import clearance_ref as R
 from conftest import assert_series_close, load_golden
 from fiss_plus_planner_amd import _abi, synth
@@ -22,14 +28,15 @@ def weighted(batch, w=W_TEST):
     return batch
 
 
-def check_against_restatement(engine, oracle, batch, egos=None, stride=128, what=""):
-    """plan_dense with tables and without them, both against the restatement; returns the table call's output."""
+def check_against_restatement(engine, oracle, batch, egos=None, stride=128, what="", ref=None):
+    """plan_dense with tables and without them, both against the restatement (ref: its cost, flags, best_idx, best_cost over `egos` when
+    the caller already has them); returns the table call's output."""
     launches = engine.get_option("clearance_launches")
     out = engine.plan_dense(batch, tables=True, winner=True, traj_stride=stride)
     bare = engine.plan_dense(batch, tables=False, winner=True, traj_stride=stride)
     assert engine.get_option("clearance_launches") == launches + 2
     egos = list(range(batch.B)) if egos is None else egos
-    cost, flags, idx, best = R.batch_tables(oracle, batch, egos=egos)
+    cost, flags, idx, best = R.batch_tables(oracle, batch, egos=egos) if ref is None else ref
     assert np.array_equal(out.flags[egos], flags), what
     cost_close(out.cost[egos], cost, what + " cost table")
     assert np.array_equal(out.best_idx[egos], idx), (what, out.best_idx[egos], idx)
@@ -223,3 +230,170 @@ def test_refusals_name_the_field(engine):
     a = engine.eval_trajs(weighted(batch, W_TEST), es)
     b = engine.eval_trajs(weighted(batch, 0.0), es)
     assert np.array_equal(a.cost, b.cost, equal_nan=True) and np.array_equal(a.flags, b.flags)
+
+
+# ---------------------------------------------------------------------------
+# the paths of tests/clearance_cases.py
+# ---------------------------------------------------------------------------
+TABLE_KEYS = ("best_idx", "best_cost", "cost", "flags", "stats", "best_flags", "best_traj")
+
+
+def same_bits(a, b):
+    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(np.ascontiguousarray(a).view(np.uint8), np.ascontiguousarray(b).view(np.uint8))
+
+
+def run_case(engine, oracle, name):
+    """A case of K.PATH_CASES against its restatement, every ego it lists; -> (reference, output of the call with tables)."""
+    ref = K.reference(oracle, name)
+    out = check_against_restatement(engine, oracle, ref.batch, egos=ref.egos, ref=K.tables(ref), what=name)
+    return ref, out
+
+
+def plain_of(engine, name):
+    return engine.plan_dense(weighted(K.PATH_CASES[name][0](), 0.0))
+
+
+@pytest.mark.parametrize("name", ["chunk 1024", "chunk 1025", "chunk 2197"])
+def test_chunk_boundaries(engine, oracle, name):
+    """C = 1024 fills one pass of the chunk loop to the last thread, 1025 leaves one candidate to a second pass, 2197 takes three."""
+    ref, out = run_case(engine, oracle, name)
+    again = engine.plan_dense(ref.batch, tables=True, winner=True)
+    for k in TABLE_KEYS:
+        assert same_bits(getattr(out, k), getattr(again, k)), (name, k)  # one fixed reduction tree: two runs, the same bits
+    plain = plain_of(engine, name)
+    live = ~np.isnan(plain.cost) & ((plain.flags & R.FLAG_INFEASIBLE) == 0)
+    for c0 in range(0, ref.batch.C, K.CHUNK):  # every chunk holds survivors, and the term re-priced survivors in every chunk
+        assert (out.cost[:, c0:c0 + K.CHUNK][live[:, c0:c0 + K.CHUNK]] > plain.cost[:, c0:c0 + K.CHUNK][live[:, c0:c0 + K.CHUNK]]).any(), (name, c0)
+
+
+def test_rows_from_the_scene_table(engine, oracle):
+    ref, out = run_case(engine, oracle, "scene table")
+    assert (out.best_idx[ref.egos] != plain_of(engine, "scene table").best_idx[ref.egos]).all()
+
+
+def test_rows_in_lds_and_rows_from_the_scene_table_give_the_same_bits(engine, oracle):
+    """One batch through both row paths (tests/clearance_cases.py::staged_40): poses and obstacles are summed in the same order on both,
+    so the cost table, the winners and their costs are equal bit for bit; the padded one also against the restatement."""
+    ref, padded = run_case(engine, oracle, "padded table")
+    staged = engine.plan_dense(K.staged_40(), tables=True, winner=True)
+    for k in TABLE_KEYS:
+        assert same_bits(getattr(staged, k), getattr(padded, k)), k
+    plain = engine.plan_dense(weighted(K.staged_40(), 0.0))
+    assert (staged.best_idx != plain.best_idx).sum() >= 1 and np.nansum(staged.cost > plain.cost) >= 100
+
+
+@pytest.mark.parametrize("name", ["t_now lds", "t_now table"])
+def test_t_now_offsets(engine, oracle, name):
+    """Per-ego t_now > 0 on both row paths: a horizon that cuts the poses, rows beyond the table, no pose at all, an odd offset."""
+    ref, out = run_case(engine, oracle, name)
+    plain = plain_of(engine, name)
+    none = [e for e in range(ref.batch.B) if ref.batch.final_time_step[ref.batch.scene_of[e]] - ref.batch.t_now[e] <= 0]
+    assert len(none) == 2 and set(none) & set(ref.egos)
+    for e in none:  # no pose at all: the plain costs and winner, bit for bit
+        assert same_bits(out.cost[e], plain.cost[e]) and out.best_idx[e] == plain.best_idx[e] and same_bits(out.best_cost[e:e + 1], plain.best_cost[e:e + 1])
+    some = [e for e in ref.egos if e not in none]
+    assert all((out.cost[e] > plain.cost[e]).sum() >= 50 for e in some)
+
+
+def test_frames_of_different_knot_counts(engine, oracle):
+    """One launch sized by 400-knot lines and without obstacle rows, in which two 81-knot egos stage theirs and a third cannot."""
+    ref, out = run_case(engine, oracle, "mixed knots")
+    for e in ref.egos:  # the same egos planned alone: launches of another NX and another LDS size
+        solo = engine.plan_dense(K.alone(ref.batch, e), tables=True)
+        assert same_bits(solo.cost[0], out.cost[e]) and solo.best_idx[0] == out.best_idx[e] and same_bits(solo.best_cost, out.best_cost[e:e + 1]), e
+
+
+def test_broad_phase(engine, oracle):
+    """Obstacles 40 .. 60 m beside the road, on both sides of the skip radius: the restatement sums every pair, the kernel may drop
+    less than 2e-15 per candidate.  (The skip branch taken and harmless - not a check of the radius's value: pairs 35 m apart are already
+    below the cost bar, so 30 m would pass as well; a radius that drops pairs that matter fails the near obstacles of every case.)"""
+    run_case(engine, oracle, "broad phase")
+
+
+def with_options(engine, opts, counter, run):
+    """run() under ctx options; the lattice launch counter `counter` (a|b: either) must move: the instance asked for was taken."""
+    reset = {"lattice_kernel": 0, "resident_groups": 0, "lattice_occupancy": 0}
+    try:
+        for k, v in opts.items():
+            engine.set_option(k, v)
+        before = sum(engine.get_option(c) for c in counter.split("|"))
+        run()
+        assert sum(engine.get_option(c) for c in counter.split("|")) > before, (opts, counter)
+    finally:
+        for k, v in reset.items():
+            engine.set_option(k, v)
+
+
+def test_multi_round_lattice_pass_underneath(engine, oracle):
+    """resident_groups = 2 models a one-CU device: the 24 egos of config 2 are planned in rounds, their tail cut in two, and the
+    provisional argmin of that launch is what the term replaces.  (With config 2's 100-row table the lattice layout is past a third of a
+    CU's LDS, so these rounds run on the two-per-CU instance - row clearance_config2 of tests/test_lattice_plan_cpu.py; the next test takes
+    the others.)"""
+    batch = weighted(CASES["config2"]())
+    with_options(engine, {"lattice_kernel": 2, "resident_groups": 2}, "lattice_launches_2",
+                 lambda: check_against_restatement(engine, oracle, batch, egos=[0, 1, 2, 5], what="resident_groups 2"))
+
+
+@pytest.mark.parametrize("name,k", [(n, k) for n in sorted(K.LATTICE_UNDERNEATH) for k in range(len(K.LATTICE_UNDERNEATH[n]))])
+def test_three_and_four_per_cu_and_windowed_lattice_instances_underneath(engine, oracle, name, k):
+    """The 50-row cases on the modelled one-CU device: three and four per CU on 81-knot lines, and - the line no longer fitting the
+    LDS share beside the table - the windowed (WIN) instances at four per CU on 220 knots and at three per CU on 400.  Which instance
+    each launch is, is decided by plan_lattice and proven on the CPU (clearance_cases.prove_lattice_row); the counter confirms it ran."""
+    opts, counter, _row = K.LATTICE_UNDERNEATH[name][k]
+    with_options(engine, opts, counter, lambda: run_case(engine, oracle, name))
+
+
+def test_device_call_with_launch_order_and_skip(engine):
+    import torch
+
+    from fiss_plus_planner_amd.device_batch import DeviceBatch
+
+    batch = weighted(CASES["config2"]())
+    host = engine.plan_dense(batch, tables=True)
+    db = DeviceBatch(batch, 0, order_hint=False)
+    B, Cn = batch.B, batch.C
+    order = np.roll(np.arange(B, dtype=np.int32)[::-1], 7)
+    assert sorted(order.tolist()) == list(range(B)) and (order != np.arange(B)).sum() >= B - 2
+    skip = np.zeros(B, dtype=np.int32)
+    skip[[3, 4, 17]] = 1
+    d_order, d_skip = torch.from_numpy(np.ascontiguousarray(order)).to(db.dev), torch.from_numpy(skip).to(db.dev)
+    fb = _abi.FpBatch.from_buffer_copy(db.fb)
+    fb.launch_order, fb.skip = d_order.data_ptr(), d_skip.data_ptr()
+    bi, bc = torch.full((B,), -7, dtype=torch.int32, device=db.dev), torch.full((B,), -7.0, dtype=torch.float64, device=db.dev)
+    cost, flags = db.empty((B, Cn), torch.float64), db.empty((B, Cn), torch.int32)
+    launches = engine.get_option("clearance_launches")
+    engine.plan_dense_device(db.params, fb, bi.data_ptr(), bc.data_ptr(), cost_tbl=cost.data_ptr(), flag_tbl=flags.data_ptr(),
+                             stream=torch.cuda.current_stream(db.dev).cuda_stream)
+    torch.cuda.synchronize(db.dev)
+    assert engine.get_option("clearance_launches") == launches + 1
+    idx, best, tbl = bi.cpu().numpy(), bc.cpu().numpy(), cost.cpu().numpy()
+    live = skip == 0
+    assert (idx[~live] == -1).all() and (host.best_idx[live] >= 0).sum() >= 15
+    assert np.array_equal(idx[live], host.best_idx[live]) and same_bits(best[live], host.best_cost[live])
+    assert same_bits(tbl[live], host.cost[live])
+
+
+def test_closed_loop_cycles_at_t_now_above_zero(engine, oracle):
+    """Three cycles of a ClosedLoopRunner under the weight; every cycle's winners against the restatement of the problem the device
+    state describes (ego, t_now read back before the step)."""
+    import torch
+
+    from fiss_plus_planner_amd.device_batch import ClosedLoopRunner, DeviceBatch
+
+    run = ClosedLoopRunner(engine, DeviceBatch(K.loop_batch(), 0), np.tile([1e6, 1e6], (6, 1)), "FOP")
+    egos = list(K.LOOP_EGOS)
+    loop = K.loop_reference(oracle)
+    for cycle in range(K.LOOP_CYCLES):
+        ego, t_now = run.db.t["ego"].cpu().numpy().copy(), run.db.t["t_now"].cpu().numpy().copy()
+        assert (t_now == cycle).all() and (run.done.cpu().numpy()[egos] == 0).all()
+        np.testing.assert_allclose(ego[egos], loop[cycle][0], rtol=0, atol=1e-9)  # the state the simulated loop reached
+        launches = engine.get_option("clearance_launches")
+        run.step()
+        torch.cuda.synchronize()
+        assert engine.get_option("clearance_launches") == launches + 1
+        host = K.with_state(K.loop_batch(), ego, t_now)
+        cost, flags, idx, best = R.batch_tables(oracle, host, egos=egos)
+        assert all(R.margin(cost[k], flags[k]) > 1e-6 for k in range(len(egos))), cycle
+        got_idx, got_cost = run.best_idx.cpu().numpy(), run.best_cost.cpu().numpy()
+        assert np.array_equal(got_idx[egos], idx) and idx.tolist() == loop[cycle][1], (cycle, got_idx[egos], idx)
+        cost_close(got_cost[egos], best, f"closed loop cycle {cycle}")

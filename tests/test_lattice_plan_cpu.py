@@ -69,6 +69,12 @@ CASES = [
     ("nofit_nobs4096", "obs=4096 T_obs=2"),
     ("nofit_nobs4095_lds", "obs=4095 T_obs=2"),
     ("nofit_rows_x_obs", "obs=3000"),
+    # the lattice launch under the clearance term in tests/clearance_cases.py (24 egos on a modelled one-CU device: resident_groups = 2)
+    ("clearance_config2", "B=24 res2=2 nd=5 nv=5 nt=5 obs=10 T_obs=100 tables parts tail=-1"),
+    ("clearance_short_table", "B=24 res2=2 nd=5 nv=5 nt=5 obs=10 T_obs=50 tables parts tail=-1"),
+    ("clearance_short_table_occ3", "B=24 res2=2 nd=5 nv=5 nt=5 obs=10 T_obs=50 occ=3 tables parts tail=-1"),
+    ("clearance_knots220", "B=24 res2=2 nd=5 nv=5 nt=5 obs=10 T_obs=50 NX=220 tables parts tail=-1"),
+    ("clearance_knots400_occ3", "B=24 res2=2 nd=5 nv=5 nt=5 obs=10 T_obs=50 NX=400 occ=3 tables parts tail=-1"),
 ]
 
 FLAGS = {
@@ -181,6 +187,11 @@ nofit_nd65 nofit
 nofit_nobs4096 nofit
 nofit_nobs4095_lds nofit
 nofit_rows_x_obs nofit
+clearance_config2 plain/2/555 rows=50 hp=101 gs=1 nsplit=1 wcap=81 epi=0 search=0 series=0 tail_from=-1 epi_from=-1 grid=24 lds=63056 threads=512
+clearance_short_table plain/4/rt rows=25 hp=51 gs=1 nsplit=1 wcap=81 epi=0 search=0 series=0 tail_from=-1 epi_from=-1 grid=24 lds=34880 threads=512
+clearance_short_table_occ3 plain/3/rt rows=25 hp=51 gs=1 nsplit=1 wcap=81 epi=0 search=0 series=0 tail_from=-1 epi_from=-1 grid=24 lds=39712 threads=512
+clearance_knots220 window/4/rt rows=25 hp=51 gs=1 nsplit=1 wcap=141 epi=0 search=0 series=0 tail_from=-1 epi_from=-1 grid=24 lds=40384 threads=512
+clearance_knots400_occ3 window/3/rt rows=25 hp=51 gs=1 nsplit=1 wcap=232 epi=0 search=0 series=0 tail_from=-1 epi_from=-1 grid=24 lds=53200 threads=512
 """
 
 
