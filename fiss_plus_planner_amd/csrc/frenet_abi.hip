@@ -301,6 +301,10 @@ class HostStage {
     bool zero_copy_out_ = false;
 };
 
+// "finite and >= 0" / "finite and > 0" of a caller's scalar (a NaN fails both)
+bool finite_nonneg(double v) { return v >= 0 && v <= fp::kF64Max; }
+bool finite_pos(double v) { return v > 0 && v <= fp::kF64Max; }
+
 int check_params(const fp_params* p)
 {
     if (!p) return fail(FP_EINVAL, "params is NULL");
@@ -311,7 +315,7 @@ int check_params(const fp_params* p)
     if (p->points_max < 0 || p->points_max > FP_MAX_POINTS) return fail(FP_ELIMIT, "points_max=%d outside 0..FP_MAX_POINTS", p->points_max);
     if (p->curvature_mask && (!(p->max_curvature >= 0) || !(p->max_kappa_d >= 0) || !(p->max_kappa_dd >= 0)))
         return fail(FP_EINVAL, "curvature_mask is set but max_curvature / max_kappa_d / max_kappa_dd are not all >= 0");
-    if (!(p->w_obstacle >= 0) || p->w_obstacle > 1.7976931348623157e308) return fail(FP_EINVAL, "w_obstacle must be finite and >= 0");
+    if (!finite_nonneg(p->w_obstacle)) return fail(FP_EINVAL, "w_obstacle must be finite and >= 0");
     return FP_OK;
 }
 
@@ -423,6 +427,42 @@ void stage_samples(StageList& sl, const fp_params* p, const fp_batch* b, const d
     sl.in(b->d_samples, (size_t)p->nd, d_samples);
     sl.in(b->t_samples, (size_t)p->nt, t_samples);
     sl.in(b->v_samples, (size_t)b->B * p->nv, v_samples);
+}
+
+// The argument block the table passes behind the dense pass share (fp::TablePassArgs), holding the caller's arrays as they were given:
+// all an FP_MEM_DEVICE call needs
+void table_pass_args(fp::TablePassArgs* a, const fp_params* p, const fp_batch* b, const double* cost_tbl, uint32_t* flag_tbl, int32_t* best_idx,
+                     double* best_cost, int32_t* count)
+{
+    a->B = b->B; a->NX = b->NX; a->nd = p->nd; a->nv = p->nv; a->nt = p->nt;
+    a->tick_t = p->tick_t;
+    a->t_samples = b->t_samples; a->v_samples = b->v_samples; a->ego = b->ego;
+    a->frame_of = b->frame_of; a->nx = b->nx; a->knots = b->knots;
+    a->skip = b->skip; a->perm = b->launch_order;
+    a->cost_tbl = cost_tbl; a->flag_tbl = flag_tbl; a->best_idx = best_idx; a->best_cost = best_cost; a->count = count;
+}
+// FP_MEM_HOST: every array of the block is declared for staging and gets its device address at commit.  Only what the kernels read
+// travels (the lattice samples, the ego states, the knots, the two tables); a host call has no launch order.  `own` declares the
+// entry point's own arrays where they have always stood in its list, behind the knots: the order of a list decides the arena's layout
+// (plan_stage).
+template <typename Own>
+void table_pass_stage(StageList& sl, fp::TablePassArgs* a, int F, Own own)
+{
+    const size_t B = (size_t)a->B, C = (size_t)a->nd * a->nv * a->nt;
+    a->perm = nullptr;
+    sl.in(a->t_samples, (size_t)a->nt, &a->t_samples);
+    sl.in(a->v_samples, B * a->nv, &a->v_samples);
+    sl.in(a->ego, B * 6, &a->ego);
+    sl.in(a->frame_of, B, &a->frame_of);
+    sl.in(a->nx, (size_t)F, &a->nx);
+    sl.in(a->knots, (size_t)F * a->NX, &a->knots);
+    own(sl);
+    if (a->skip) sl.in(a->skip, B, &a->skip);
+    sl.in(a->cost_tbl, B * C, &a->cost_tbl);
+    sl.in_mut(a->flag_tbl, B * C, &a->flag_tbl);
+    sl.out(a->best_idx, B, &a->best_idx);
+    sl.out(a->best_cost, B, &a->best_cost);
+    sl.out(a->count, B, &a->count);
 }
 
 // Inline inputs of a multi-kernel call (fp::InlineIn::publish): besides the eight per-ego arrays of the batch the blob carries
@@ -1567,44 +1607,32 @@ int fp_boundary_mask(fp_ctx* ctx, const fp_params* params, const fp_batch* batch
     FP_TRY(common_checks(ctx, params, batch, mem, stream));
     if (!corridor || !corridor->left || !corridor->right) return fail(FP_EINVAL, "fp_boundary_mask: corridor / left / right must not be NULL");
     if (!cost_tbl || !flag_tbl || !best_idx || !best_cost) return fail(FP_EINVAL, "fp_boundary_mask: cost_tbl/flag_tbl/best_idx/best_cost must not be NULL");
-    if (!(corridor->margin >= 0) || corridor->margin > 1.7976931348623157e308) return fail(FP_EINVAL, "fp_boundary_mask: margin must be finite and >= 0");
+    if (!finite_nonneg(corridor->margin)) return fail(FP_EINVAL, "fp_boundary_mask: margin must be finite and >= 0");
     if (batch->B == 0) return FP_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    const size_t B = (size_t)batch->B, C = (size_t)params->nd * params->nv * params->nt, fn = (size_t)batch->F * batch->NX;
     fp::BoundaryArgs a;
-    a.B = batch->B; a.NX = batch->NX; a.nd = params->nd; a.nv = params->nv; a.nt = params->nt;
-    a.tick_t = params->tick_t; a.veh_l = params->veh_l; a.veh_w = params->veh_w; a.margin = corridor->margin;
+    table_pass_args(&a, params, batch, cost_tbl, flag_tbl, best_idx, best_cost, n_masked);
+    a.veh_l = params->veh_l; a.veh_w = params->veh_w; a.margin = corridor->margin;
+    a.d_samples = batch->d_samples; a.left = corridor->left; a.right = corridor->right;
     if (mem == FP_MEM_DEVICE) {
-        a.d_samples = batch->d_samples; a.t_samples = batch->t_samples; a.v_samples = batch->v_samples; a.ego = batch->ego;
-        a.frame_of = batch->frame_of; a.nx = batch->nx; a.knots = batch->knots; a.left = corridor->left; a.right = corridor->right;
-        a.skip = batch->skip; a.perm = batch->launch_order;
-        a.cost_tbl = cost_tbl; a.flag_tbl = flag_tbl; a.best_idx = best_idx; a.best_cost = best_cost; a.n_masked = n_masked;
         LAUNCH_TRY(fp::launch_boundary_mask(a, (hipStream_t)stream), "road-boundary kernel");
         ++ctx->boundary_launches;
         return FP_OK;
     }
-    // host arrays: only what the kernel reads travels (the lattice samples, the ego states, the knots, the corridor and the two tables)
     FP_TRY(check_frames_host(batch));
     for (int f = 0; f < batch->F; ++f)
         for (int k = 0; k < batch->nx[f]; ++k) {
             const double l = corridor->left[(size_t)f * batch->NX + k], r = corridor->right[(size_t)f * batch->NX + k];
             if (!(l == l) || !(r == r)) return fail(FP_EINVAL, "fp_boundary_mask: corridor has a NaN at frame %d, knot %d (+-inf says \"no edge\")", f, k);
         }
+    const size_t fn = (size_t)batch->F * batch->NX;
     HostStage hs(ctx);
     StageList sl;
-    stage_samples(sl, params, batch, &a.d_samples, &a.t_samples, &a.v_samples);
-    sl.in(batch->ego, B * 6, &a.ego);
-    sl.in(batch->frame_of, B, &a.frame_of);
-    sl.in(batch->nx, (size_t)batch->F, &a.nx);
-    sl.in(batch->knots, fn, &a.knots);
-    sl.in(corridor->left, fn, &a.left);
-    sl.in(corridor->right, fn, &a.right);
-    if (batch->skip) sl.in(batch->skip, B, &a.skip);
-    sl.in(cost_tbl, B * C, &a.cost_tbl);
-    sl.in_mut(flag_tbl, B * C, &a.flag_tbl);
-    sl.out(best_idx, B, &a.best_idx);
-    sl.out(best_cost, B, &a.best_cost);
-    sl.out(n_masked, B, &a.n_masked);
+    sl.in(a.d_samples, (size_t)a.nd, &a.d_samples);
+    table_pass_stage(sl, &a, batch->F, [&](StageList& l) {
+        l.in(a.left, fn, &a.left);
+        l.in(a.right, fn, &a.right);
+    });
     FP_TRY(hs.commit(sl));
     LAUNCH_TRY(fp::launch_boundary_mask(a, ctx->stream), "road-boundary kernel");
     ++ctx->boundary_launches;
@@ -1617,51 +1645,35 @@ int fp_speed_envelope(fp_ctx* ctx, const fp_params* params, const fp_batch* batc
     FP_TRY(common_checks(ctx, params, batch, mem, stream, /*need_coef=*/false));  // (coef is read by the lateral check alone: see below)
     if (!profile || !profile->v_limit) return fail(FP_EINVAL, "fp_speed_envelope: profile / v_limit must not be NULL");
     if (!cost_tbl || !flag_tbl || !best_idx || !best_cost) return fail(FP_EINVAL, "fp_speed_envelope: cost_tbl/flag_tbl/best_idx/best_cost must not be NULL");
-    const double dmax = 1.7976931348623157e308;
-    if (!(profile->front >= 0) || profile->front > dmax) return fail(FP_EINVAL, "fp_speed_envelope: front must be finite and >= 0");
-    if (!(profile->tol >= 0) || profile->tol > dmax) return fail(FP_EINVAL, "fp_speed_envelope: tol must be finite and >= 0");
-    if (!(profile->max_lat_accel >= 0) || profile->max_lat_accel > dmax) return fail(FP_EINVAL, "fp_speed_envelope: max_lat_accel must be finite and >= 0 (0 = off)");
+    if (!finite_nonneg(profile->front)) return fail(FP_EINVAL, "fp_speed_envelope: front must be finite and >= 0");
+    if (!finite_nonneg(profile->tol)) return fail(FP_EINVAL, "fp_speed_envelope: tol must be finite and >= 0");
+    if (!finite_nonneg(profile->max_lat_accel)) return fail(FP_EINVAL, "fp_speed_envelope: max_lat_accel must be finite and >= 0 (0 = off)");
     const bool lateral = profile->max_lat_accel > 0;
     if (lateral && !batch->coef) return fail(FP_EINVAL, "fp_speed_envelope: max_lat_accel > 0 needs batch->coef");
     if (batch->B == 0) return FP_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    const size_t B = (size_t)batch->B, C = (size_t)params->nd * params->nv * params->nt, fn = (size_t)batch->F * batch->NX;
     fp::EnvelopeArgs a;
-    a.B = batch->B; a.NX = batch->NX; a.nd = params->nd; a.nv = params->nv; a.nt = params->nt;
-    a.tick_t = params->tick_t; a.front = profile->front; a.tol = profile->tol; a.max_lat_accel = profile->max_lat_accel;
+    table_pass_args(&a, params, batch, cost_tbl, flag_tbl, best_idx, best_cost, n_limited);
+    a.front = profile->front; a.tol = profile->tol; a.max_lat_accel = profile->max_lat_accel;
+    a.coef = lateral ? batch->coef : nullptr; a.v_limit = profile->v_limit;  // (coef is read by the lateral check alone)
     if (mem == FP_MEM_DEVICE) {
-        a.t_samples = batch->t_samples; a.v_samples = batch->v_samples; a.ego = batch->ego;
-        a.frame_of = batch->frame_of; a.nx = batch->nx; a.knots = batch->knots; a.coef = lateral ? batch->coef : nullptr; a.v_limit = profile->v_limit;
-        a.skip = batch->skip; a.perm = batch->launch_order;
-        a.cost_tbl = cost_tbl; a.flag_tbl = flag_tbl; a.best_idx = best_idx; a.best_cost = best_cost; a.n_limited = n_limited;
         LAUNCH_TRY(fp::launch_speed_envelope(a, (hipStream_t)stream), "speed-envelope kernel");
         ++ctx->envelope_launches;
         return FP_OK;
     }
-    // host arrays: only what the kernel reads travels (the lattice samples, the ego states, the knots, the limits, the two tables and - for
-    // the lateral check - the coefficients)
     FP_TRY(check_frames_host(batch));
     for (int f = 0; f < batch->F; ++f)
         for (int k = 0; k + 1 < batch->nx[f]; ++k) {
             const double l = profile->v_limit[(size_t)f * batch->NX + k];
             if (!(l >= 0)) return fail(FP_EINVAL, "fp_speed_envelope: v_limit is %g at frame %d, knot %d (+inf says \"no limit\", 0 \"stop\")", l, f, k);
         }
+    const size_t fn = (size_t)batch->F * batch->NX;
     HostStage hs(ctx);
     StageList sl;
-    sl.in(batch->t_samples, (size_t)params->nt, &a.t_samples);
-    sl.in(batch->v_samples, B * params->nv, &a.v_samples);
-    sl.in(batch->ego, B * 6, &a.ego);
-    sl.in(batch->frame_of, B, &a.frame_of);
-    sl.in(batch->nx, (size_t)batch->F, &a.nx);
-    sl.in(batch->knots, fn, &a.knots);
-    if (lateral) sl.in(batch->coef, fn * 8, &a.coef);
-    sl.in(profile->v_limit, fn, &a.v_limit);
-    if (batch->skip) sl.in(batch->skip, B, &a.skip);
-    sl.in(cost_tbl, B * C, &a.cost_tbl);
-    sl.in_mut(flag_tbl, B * C, &a.flag_tbl);
-    sl.out(best_idx, B, &a.best_idx);
-    sl.out(best_cost, B, &a.best_cost);
-    sl.out(n_limited, B, &a.n_limited);
+    table_pass_stage(sl, &a, batch->F, [&](StageList& l) {
+        if (lateral) l.in(a.coef, fn * 8, &a.coef);
+        l.in(a.v_limit, fn, &a.v_limit);
+    });
     FP_TRY(hs.commit(sl));
     LAUNCH_TRY(fp::launch_speed_envelope(a, ctx->stream), "speed-envelope kernel");
     ++ctx->envelope_launches;
@@ -1735,7 +1747,7 @@ int fp_obstacles_predict(fp_ctx* ctx, const fp_params* params, const fp_batch* b
     if (!tracks || !tracks->model || !tracks->state || !tracks->t0 || !obs_pose)
         return fail(FP_EINVAL, "fp_obstacles_predict: tracks / model / state / t0 / obs_pose must not be NULL");
     if (tracks->n_rows <= 0) return fail(FP_EINVAL, "fp_obstacles_predict: n_rows=%d must be > 0", tracks->n_rows);
-    if (!(params->tick_t > 0) || params->tick_t > 1.7976931348623157e308) return fail(FP_EINVAL, "fp_obstacles_predict: tick_t must be finite and > 0");
+    if (!finite_pos(params->tick_t)) return fail(FP_EINVAL, "fp_obstacles_predict: tick_t must be finite and > 0");
     if (batch->S < 0 || batch->T_obs < 0 || batch->n_obs < 0 || batch->F < 0 || batch->NX < 0 || batch->NX > FP_MAX_KNOTS)
         return fail(FP_EINVAL, "fp_obstacles_predict: bad batch sizes S=%d T_obs=%d n_obs=%d F=%d NX=%d", batch->S, batch->T_obs, batch->n_obs, batch->F, batch->NX);
     // (the table may be an input of overlapped dense calls still in flight on the ctx's internal streams)
@@ -2238,7 +2250,7 @@ int fp_from_state(fp_ctx* ctx, const fp_batch* batch, const double* states, doub
     for (size_t b = 0; b < B; ++b) {
         static const char* const kName[4] = {"x", "y", "yaw", "v"};
         for (int k = 0; k < 4; ++k)
-            if (!fp::project_finite(states[b * 4 + k])) return fail(FP_EINVAL, "fp_from_state: ego %zu: %s=%g is not finite", b, kName[k], states[b * 4 + k]);
+            if (!fp::finite_f64(states[b * 4 + k])) return fail(FP_EINVAL, "fp_from_state: ego %zu: %s=%g is not finite", b, kName[k], states[b * 4 + k]);
         const int32_t f = batch->frame_of[b];
         const double s_last = batch->knots[(size_t)f * batch->NX + batch->nx[f] - 1];
         if (fp::project_point_count(s_last) == 0)

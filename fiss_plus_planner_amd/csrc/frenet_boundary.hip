@@ -15,13 +15,14 @@
 //     every lattice size keeps all four wavefronts busy;
 //   - a wavefront then takes its 64 candidates one at a time (the candidate's flag word and profile indices come out of the owning
 //     lane's registers), its lanes the points 1 + lane, 65 + lane, ... < M: two fma Horner chains per series (quintic_eval /
-//     quartic_eval, the arithmetic of every series dump), the segment look-up (spline_segment with the uniform-spacing guess), one
-//     hypot, one division, two compares.  __ballot is the verdict; a round that finds a violation ends the candidate;
+//     quartic_eval, the arithmetic of every series dump), the segment look-up (see spline_segment_clamped), one hypot, one division,
+//     two compares.  __ballot is the verdict; a round that finds a violation ends the candidate;
 //   - the owning lane rewrites the bit in its flag word (a vector store, and only when the word changes) and keeps the ego's argmin
-//     among its own candidates; wave_best and a merge over the four wavefronts in LDS finish it (best_merge: the last minimum wins).
+//     among its own candidates; see finish_ego for the rest.
 // No atomics, no scratch, every reduction a fixed tree or a ballot: two runs give the same bits.
 #include "frenet_device.h"
 #include "frenet_kernels.h"
+#include "frenet_project.h"
 
 namespace fp {
 
@@ -31,22 +32,14 @@ constexpr int kBoundWaves = kBoundThreads / kWave;
 // 40 x 1 x 40) solves the two boundary-value problems per candidate instead - same arithmetic, same bits.
 constexpr int kBoundProfBytes = 64 * 1024;
 
-__device__ __forceinline__ bool bound_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }
-
 __global__ __launch_bounds__(kBoundThreads) void boundary_mask_kernel(BoundaryArgs a, int staged)
 {
     extern __shared__ __attribute__((aligned(16))) double lds[];
-    __shared__ Best s_best[kBoundWaves];
-    __shared__ int s_masked[kBoundWaves];
     const int b = a.perm ? a.perm[blockIdx.x] : (int)blockIdx.x;
     const int tid = threadIdx.x, lane = tid & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane(tid / kWave);
     if (a.skip && a.skip[b]) {  // not planned: the dense pass wrote no rows for this ego
-        if (tid == 0) {
-            a.best_idx[b] = -1;
-            a.best_cost[b] = __builtin_nan("");
-            if (a.n_masked) a.n_masked[b] = 0;
-        }
+        skip_ego(b, a.best_idx, a.best_cost, a.count);
         return;
     }
     const int nd = a.nd, nv = a.nv, nt = a.nt, C = nd * nv * nt;
@@ -69,7 +62,7 @@ __global__ __launch_bounds__(kBoundThreads) void boundary_mask_kernel(BoundaryAr
         if (i + 1 < nx) {
             const double inv = 1.0 / (gk[i + 1] - k0);
             const double la = gl[i], lb = gl[i + 1], ra = gr[i], rb = gr[i + 1];
-            const bool lfin = bound_finite(la) && bound_finite(lb), rfin = bound_finite(ra) && bound_finite(rb);
+            const bool lfin = finite_f64(la) && finite_f64(lb), rfin = finite_f64(ra) && finite_f64(rb);
             l0[i] = lfin ? la : __builtin_inf();
             l1[i] = lfin ? (lb - la) * inv : 0.0;
             r0[i] = rfin ? ra : -__builtin_inf();
@@ -94,7 +87,6 @@ __global__ __launch_bounds__(kBoundThreads) void boundary_mask_kernel(BoundaryAr
     __syncthreads();
     const SplineLds sp{knots, nullptr, nx, nx};
     const double guess_scale = (double)(nx - 1) / (knots[nx - 1] - knots[0]);
-    const double first_knot = knots[0];
     const double hw = 0.5 * a.veh_w, hl = 0.5 * a.veh_l, margin = a.margin, tick = a.tick_t;
     const double* cost = a.cost_tbl + (size_t)b * C;
     uint32_t* flag = a.flag_tbl + (size_t)b * C;
@@ -142,8 +134,7 @@ __global__ __launch_bounds__(kBoundThreads) void boundary_mask_kernel(BoundaryAr
                     double s, s_d, d, d_d, unused_a, unused_j;
                     quartic_eval(lon, t, s, s_d, unused_a, unused_j);
                     quintic_eval(lat, t, d, d_d, unused_a, unused_j);
-                    int k = spline_segment(sp, s, -1, guess_scale);
-                    if (k < 0) k = s < first_knot || nx < 2 ? 0 : nx - 2;  // (a point below M lies on the line; the clamp keeps the reads inside the rows whatever s is)
+                    const int k = spline_segment_clamped(sp, s, guess_scale);  // (a point below M lies on the line)
                     const double ds = s - knots[k];
                     const double L = fma(l1[k], ds, l0[k]), R = fma(r1[k], ds, r0[k]);
                     const double r = hypot(s_d, d_d);
@@ -166,23 +157,7 @@ __global__ __launch_bounds__(kBoundThreads) void boundary_mask_kernel(BoundaryAr
             if (!(fl_new & FP_FLAG_INFEASIBLE) && cost_own == cost_own) mine = best_merge(mine, Best{cost_own, c});  // (a NaN cost can never win, :266)
         }
     }
-    mine = wave_best(mine);
-    if (lane == 0) {
-        s_best[wave] = mine;
-        s_masked[wave] = masked;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        Best r = s_best[0];
-        int n = s_masked[0];
-        for (int w = 1; w < kBoundWaves; ++w) {
-            r = best_merge(r, s_best[w]);
-            n += s_masked[w];
-        }
-        a.best_idx[b] = r.idx;
-        a.best_cost[b] = r.idx >= 0 ? r.cost : __builtin_nan("");
-        if (a.n_masked) a.n_masked[b] = n;
-    }
+    finish_ego<kBoundWaves>(mine, masked, b, a.best_idx, a.best_cost, a.count);
 }
 
 hipError_t launch_boundary_mask(const BoundaryArgs& a, hipStream_t stream)
@@ -193,11 +168,7 @@ hipError_t launch_boundary_mask(const BoundaryArgs& a, hipStream_t stream)
     const long prof = (6L * a.nd + 5L * a.nv) * a.nt * 8;
     const int staged = prof <= kBoundProfBytes ? 1 : 0;
     const int bytes = 5 * a.NX * 8 + (staged ? (int)prof : 0);  // <= 40 KB + 64 KB
-    FP_LDS_SLOTS(configured);
-    hipError_t err = ensure_dynamic_lds((const void*)boundary_mask_kernel, bytes, configured);
-    if (err != hipSuccess) return err;
-    hipLaunchKernelGGL(boundary_mask_kernel, dim3(a.B), dim3(kBoundThreads), bytes, stream, a, staged);
-    return hipGetLastError();
+    return launch_with_lds<boundary_mask_kernel>(dim3(a.B), dim3(kBoundThreads), bytes, stream, a, staged);
 }
 
 }  // namespace fp

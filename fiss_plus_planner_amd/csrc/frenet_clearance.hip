@@ -9,11 +9,11 @@
 // for the candidates that survived the checks; every other candidate keeps its cost.
 //
 // clearance_rescore_kernel runs behind the lattice pass, over its tables: one workgroup per ego, staged like the lane-per-candidate
-// kernel (stage_ego: spline, obstacle sizes and - when they fit - the obstacle rows as x, y, cos, sin in LDS).  The flag table is
+// kernel (stage_ego: spline, obstacle sizes and - when they fit - the obstacle rows in LDS; see frenet_ego.h).  The flag table is
 // walked in chunks of one candidate per thread, the survivors of a chunk compacted by ballot + popcount; then every wavefront takes
-// one survivor at a time, its lanes the checked poses (lane, lane + 64, ...), each lane looping over the obstacles of its row.  A
-// candidate's sum is its lanes' sums (poses ascending, obstacles ascending) reduced by wave_sum_f64: one fixed tree, no atomics -
-// two runs give the same bits.  The ego's argmin over the new costs (best_merge: the last minimum wins) replaces the lattice pass's.
+// one survivor at a time, its lanes the checked poses (lane, lane + 64, ...; see checked_pose), each lane looping over the obstacles of
+// its row.  A candidate's sum is its lanes' sums (poses ascending, obstacles ascending) reduced by wave_sum_f64: one fixed tree, no
+// atomics - two runs give the same bits.  The ego's argmin over the new costs (see finish_ego) replaces the lattice pass's.
 #include "frenet_device.h"
 #include "frenet_kernels.h"
 #include "frenet_ego.h"
@@ -27,51 +27,24 @@ constexpr int kClearWaves = kClearThreads / kWave;
 // exp(-48) * 1.05e6 < 2e-15, far below the 1e-12 the definition allows.
 constexpr double kClearSkip = 48.0;
 
-// exp(-dist) of the ego box at a checked pose against every obstacle present at that pose's row, obstacles in column order
-__device__ __forceinline__ double pose_clearance(const KernelArgs& ka, const EgoCtx& e, int i, double x, double y, double c, double s)
+// exp(-dist) of the ego box at checked pose i against every obstacle present at that pose's row (obs_row, frenet_ego.h), obstacles in
+// column order
+__device__ __forceinline__ double pose_clearance(const KernelArgs& ka, const EgoCtx& e, int i, const Obb& ego)
 {
-    const Obb ego{x, y, c, s, 0.5 * ka.p.veh_l, 0.5 * ka.p.veh_w};
     const double r_e = sqrt(fma(ego.hl, ego.hl, ego.hw * ego.hw)) + kClearSkip;
-    const int n = e.n_obs;
-    const int stride = ka.p.check_stride;
-    const double* row;
-    if (e.obs_lds) {
-        if (i / stride >= e.rows) return 0.0;  // beyond the table: state_at_time() is None for every obstacle
-        row = e.obs_lds + (size_t)(i / stride) * n * 4;
-    } else {
-        const int ts = i + e.t_now;
-        if (ts < 0 || ts >= e.T_obs) return 0.0;
-        row = e.obs_glb + (size_t)ts * n * 4;
-    }
+    const double* row = obs_row(e, i, ka.p.check_stride);
+    if (!row) return 0.0;  // state_at_time() is None for every obstacle
     double acc = 0.0;
-    for (int j = 0; j < n; ++j) {
-        const double ox = row[4 * j], oy = row[4 * j + 1];
-        if (!e.obs_lds && row[4 * j + 3] == 0.0) continue;
+    for (int j = 0; j < e.n_obs; ++j) {
+        double ox, oy, oc, os;
+        if (!obs_centre(e, row, j, ox, oy, /*nan_ok=*/true)) continue;
         const double R = r_e + e.obs_dim[4 * j + 2];
-        const double dx = ox - x, dy = oy - y;
-        if (!(fma(dx, dx, dy * dy) < R * R)) continue;  // kClearSkip; also skips NaN (no state)
-        double oc = row[4 * j + 2], os = row[4 * j + 3];
-        if (!e.obs_lds) sincos_snapped(row[4 * j + 2], os, oc);
-        const int nvert = ka.b.obs_nvert ? ka.b.obs_nvert[e.col0 + j] : 0;
-        const double dist = nvert > 0 ? poly_distance(ego, ox, oy, oc, os, ka.b.obs_poly + (e.col0 + j) * 2 * (size_t)ka.b.poly_stride, nvert)
-                                      : obb_distance(ego, Obb{ox, oy, oc, os, e.obs_dim[4 * j], e.obs_dim[4 * j + 1]});
-        acc += exp(-dist);
+        const double dx = ox - ego.x, dy = oy - ego.y;
+        if (!(fma(dx, dx, dy * dy) < R * R)) continue;  // kClearSkip; also skips NaN (no state in an LDS row)
+        obs_heading(e, row, j, oc, os);
+        acc += exp(-shape_distance(ka, e, ego, j, ox, oy, oc, os));
     }
     return acc;
-}
-
-// Cartesian point i of the candidate (lon, lat); false when it lies off the reference line
-__device__ __forceinline__ bool traj_point(const fp_params& p, const SplineLds& sp, double guess_scale, const Quartic& lon, const Quintic& lat, int i, double& x, double& y)
-{
-    const double t = (double)i * p.tick_t;
-    const double sv = fma(fma(fma(fma(lon.a4, t, lon.a3), t, lon.a2), t, lon.a1), t, lon.a0);
-    const int seg = spline_segment(sp, sv, -1, guess_scale);
-    if (seg < 0) return false;
-    const double dv = fma(fma(fma(fma(fma(lat.a5, t, lat.a4), t, lat.a3), t, lat.a2), t, lat.a1), t, lat.a0);
-    double px, py, tx, ty;
-    spline_frame(sp, seg, sv - sp.knots[seg], px, py, tx, ty);
-    frenet_to_cartesian(px, py, tx, ty, dv, x, y);
-    return true;
 }
 
 __global__ __launch_bounds__(kClearThreads) void clearance_rescore_kernel(KernelArgs ka, int lds_doubles, const int* perm)
@@ -79,7 +52,6 @@ __global__ __launch_bounds__(kClearThreads) void clearance_rescore_kernel(Kernel
     extern __shared__ __attribute__((aligned(16))) double lds[];
     __shared__ int s_list[kClearThreads];  // survivors of the current chunk, in index order
     __shared__ int s_count[kClearWaves];
-    __shared__ Best s_best[kClearWaves];
     const int b = perm ? perm[blockIdx.x] : blockIdx.x;
     const int tid = threadIdx.x, wave = tid / kWave, lane = tid & (kWave - 1);
     const fp_params& p = ka.p;
@@ -121,12 +93,8 @@ __global__ __launch_bounds__(kClearThreads) void clearance_rescore_kernel(Kernel
                 const Quartic lon = quartic_bvp(e.s0, e.s_d0, e.s_dd0, vs[iv], 0.0, T_end);
                 const int limit = M < e.horizon_cap ? M : e.horizon_cap;  // poses i = 0, cs, 2 cs, ... < min(M, final_time_step - t_now)
                 for (int i = lane * cs; i < limit; i += kWave * cs) {
-                    // heading of pose i: the step to the next point; the last pose repeats the previous heading (:129)
-                    const int i0 = i + 1 < M ? i : i - 1;
-                    double x0, y0, x1, y1, hc, hs;
-                    if (!traj_point(p, e.sp, guess_scale, lon, lat, i0, x0, y0) || !traj_point(p, e.sp, guess_scale, lon, lat, i0 + 1, x1, y1)) continue;
-                    step_heading(x1 - x0, y1 - y0, hc, hs);
-                    sum += i0 == i ? pose_clearance(ka, e, i, x0, y0, hc, hs) : pose_clearance(ka, e, i, x1, y1, hc, hs);
+                    Obb ego;
+                    if (checked_pose(p, e.sp, guess_scale, lon, lat, i, M, ego)) sum += pose_clearance(ka, e, i, ego);
                 }
             }
             sum = wave_sum_f64(sum);
@@ -137,15 +105,7 @@ __global__ __launch_bounds__(kClearThreads) void clearance_rescore_kernel(Kernel
         }
         __syncthreads();  // s_list is rewritten by the next chunk
     }
-    if (lane == 0) s_best[wave] = mine;
-    __syncthreads();
-    if (tid == 0) {
-        Best r = s_best[0];
-        for (int w = 1; w < kClearWaves; ++w) r = best_merge(r, s_best[w]);
-        ka.r.best_idx[b] = r.idx;
-        if (ka.idx_shadow) ka.idx_shadow[b] = r.idx;
-        ka.r.best_cost[b] = r.idx >= 0 ? r.cost : __builtin_nan("");
-    }
+    finish_ego<kClearWaves>(mine, 0, b, ka.r.best_idx, ka.r.best_cost, nullptr, ka.idx_shadow);
 }
 
 hipError_t launch_clearance_rescore(const KernelArgs& ka, const int* perm, hipStream_t stream)
@@ -154,11 +114,7 @@ hipError_t launch_clearance_rescore(const KernelArgs& ka, const int* perm, hipSt
     int lds_doubles = 0;
     // the static tables of the kernel (survivor list, counts, argmins) come out of the same 160 KB
     const int bytes = ego_lds_bytes(ka.p, ka.b, 144 * 1024, &lds_doubles);
-    FP_LDS_SLOTS(configured);
-    hipError_t err = ensure_dynamic_lds((const void*)clearance_rescore_kernel, bytes, configured);
-    if (err != hipSuccess) return err;
-    hipLaunchKernelGGL(clearance_rescore_kernel, dim3(ka.b.B), dim3(kClearThreads), bytes, stream, ka, lds_doubles, perm);
-    return hipGetLastError();
+    return launch_with_lds<clearance_rescore_kernel>(dim3(ka.b.B), dim3(kClearThreads), bytes, stream, ka, lds_doubles, perm);
 }
 
 }  // namespace fp

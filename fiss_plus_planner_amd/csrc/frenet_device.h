@@ -78,17 +78,27 @@ __device__ __forceinline__ Quartic quartic_bvp(double xs, double vxs, double axs
     return q;
 }
 
+// position alone, Horner form: s(t) of a longitudinal quartic, d(t) of a lateral quintic
+__device__ __forceinline__ double quartic_pos(const Quartic& lon, double t)
+{
+    return fma(fma(fma(fma(lon.a4, t, lon.a3), t, lon.a2), t, lon.a1), t, lon.a0);
+}
+__device__ __forceinline__ double quintic_pos(const Quintic& lat, double t)
+{
+    return fma(fma(fma(fma(fma(lat.a5, t, lat.a4), t, lat.a3), t, lat.a2), t, lat.a1), t, lat.a0);
+}
+
 // value and three derivatives, Horner form
 __device__ __forceinline__ void quintic_eval(const Quintic& q, double t, double& p, double& v, double& a, double& j)
 {
-    p = fma(fma(fma(fma(fma(q.a5, t, q.a4), t, q.a3), t, q.a2), t, q.a1), t, q.a0);
+    p = quintic_pos(q, t);
     v = fma(fma(fma(fma(5.0 * q.a5, t, 4.0 * q.a4), t, 3.0 * q.a3), t, 2.0 * q.a2), t, q.a1);
     a = fma(fma(fma(20.0 * q.a5, t, 12.0 * q.a4), t, 6.0 * q.a3), t, 2.0 * q.a2);
     j = fma(fma(60.0 * q.a5, t, 24.0 * q.a4), t, 6.0 * q.a3);
 }
 __device__ __forceinline__ void quartic_eval(const Quartic& q, double t, double& p, double& v, double& a, double& j)
 {
-    p = fma(fma(fma(fma(q.a4, t, q.a3), t, q.a2), t, q.a1), t, q.a0);
+    p = quartic_pos(q, t);
     v = fma(fma(fma(4.0 * q.a4, t, 3.0 * q.a3), t, 2.0 * q.a2), t, q.a1);
     a = fma(fma(12.0 * q.a4, t, 6.0 * q.a3), t, 2.0 * q.a2);
     j = fma(24.0 * q.a4, t, 6.0 * q.a3);
@@ -249,6 +259,15 @@ __device__ __forceinline__ int spline_segment(const SplineLds& sp, double s, int
         if (s < sp.knots[mid]) hi = mid; else lo = mid + 1;
     }
     return lo - 1;
+}
+
+// spline_segment for a table with one row per segment that is read whatever s is: below the line the first segment, at or past its end
+// (and for a NaN) the last one.  The clamp keeps the reads inside the rows.
+__device__ __forceinline__ int spline_segment_clamped(const SplineLds& sp, double s, double guess_scale)
+{
+    const int k = spline_segment(sp, s, -1, guess_scale);
+    if (k >= 0) return k;
+    return s < sp.knots[0] || sp.nx < 2 ? 0 : sp.nx - 2;
 }
 
 // position (px,py) and UNIT tangent (tx,ty) of the reference line at (segment i, offset dx)
@@ -502,6 +521,33 @@ __device__ __forceinline__ void step_heading(double dx, double dy, double& c, do
     }
 }
 
+// Cartesian point i of the plan (lon, lat); false when it lies off the reference line (the arithmetic of every series dump)
+__device__ __forceinline__ bool traj_point(const fp_params& p, const SplineLds& sp, double guess_scale, const Quartic& lon, const Quintic& lat, int i, double& x, double& y)
+{
+    const double t = (double)i * p.tick_t;
+    const double sv = quartic_pos(lon, t);
+    const int seg = spline_segment(sp, sv, -1, guess_scale);
+    if (seg < 0) return false;
+    const double dv = quintic_pos(lat, t);
+    double px, py, tx, ty;
+    spline_frame(sp, seg, sv - sp.knots[seg], px, py, tx, ty);
+    frenet_to_cartesian(px, py, tx, ty, dv, x, y);
+    return true;
+}
+
+// The ego footprint at checked pose i of a plan whose series has M points (has_collision's pose, frenet_optimal_planner.py:168-195):
+// the heading of pose i is the step to point i + 1, the last pose repeats the previous heading (:129).  false when one of the two
+// points lies off the reference line.
+__device__ __forceinline__ bool checked_pose(const fp_params& p, const SplineLds& sp, double guess_scale, const Quartic& lon, const Quintic& lat, int i, int M, Obb& ego)
+{
+    const int i0 = i + 1 < M ? i : i - 1;
+    double x0, y0, x1, y1, hc, hs;
+    if (!traj_point(p, sp, guess_scale, lon, lat, i0, x0, y0) || !traj_point(p, sp, guess_scale, lon, lat, i0 + 1, x1, y1)) return false;
+    step_heading(x1 - x0, y1 - y0, hc, hs);
+    ego = Obb{i0 == i ? x0 : x1, i0 == i ? y0 : y1, hc, hs, 0.5 * p.veh_l, 0.5 * p.veh_w};
+    return true;
+}
+
 // cos / sin of an obstacle's orientation as shapely.affinity.rotate computes them (construct_polygon,
 // frenet_optimal_planner.py:162-166): |cos| or |sin| below 2.5e-16 is snapped to 0, so that yaw = k pi/2 rotates exactly.
 __device__ __forceinline__ void sincos_snapped(double yaw, double& s, double& c)
@@ -565,10 +611,10 @@ __device__ __forceinline__ uint32_t curvature_flags(const fp_params& p, const Sp
     double xp = 0.0, yp = 0.0;
     for (int i = 0; i < N; ++i) {
         const double t = (double)i * p.tick_t;
-        const double s = fma(fma(fma(fma(lon.a4, t, lon.a3), t, lon.a2), t, lon.a1), t, lon.a0);
+        const double s = quartic_pos(lon, t);
         seg = spline_segment(sp, s, seg);
         if (seg < 0) break;  // truncation (:112-113)
-        const double d = fma(fma(fma(fma(fma(lat.a5, t, lat.a4), t, lat.a3), t, lat.a2), t, lat.a1), t, lat.a0);
+        const double d = quintic_pos(lat, t);
         double px, py, tx, ty, x, y;
         spline_frame(sp, seg, s - sp.knots[seg], px, py, tx, ty);
         frenet_to_cartesian(px, py, tx, ty, d, x, y);
@@ -648,6 +694,44 @@ __device__ __forceinline__ Best wave_best(Best v)
         v = best_merge(v, o);
     }
     return v;
+}
+
+// The end of a one-workgroup-per-ego table pass of WAVES wavefronts: the ego's argmin from every lane's `mine` (wave_best, then a merge
+// over the wavefronts in LDS) and the sum of the wave-uniform `count`s; thread 0 writes best_idx (+ idx_shadow), best_cost (NaN when
+// nothing survived) and the count.  idx_shadow and n_out are optional.  All threads of the block take part (one barrier).
+template <int WAVES>
+__device__ __forceinline__ void finish_ego(Best mine, int count, int b, int32_t* best_idx, double* best_cost, int32_t* n_out, int32_t* idx_shadow = nullptr)
+{
+    __shared__ Best s_best[WAVES];
+    __shared__ int s_count[WAVES];
+    const int tid = threadIdx.x;
+    mine = wave_best(mine);
+    if ((tid & (kWave - 1)) == 0) {
+        s_best[tid / kWave] = mine;
+        s_count[tid / kWave] = count;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        Best r = s_best[0];
+        int n = s_count[0];
+        for (int w = 1; w < WAVES; ++w) {
+            r = best_merge(r, s_best[w]);
+            n += s_count[w];
+        }
+        best_idx[b] = r.idx;
+        if (idx_shadow) idx_shadow[b] = r.idx;
+        best_cost[b] = r.idx >= 0 ? r.cost : __builtin_nan("");
+        if (n_out) n_out[b] = n;
+    }
+}
+// What such a pass leaves for an ego it does not plan (fp_batch.skip): no argmin, no count
+__device__ __forceinline__ void skip_ego(int b, int32_t* best_idx, double* best_cost, int32_t* n_out)
+{
+    if (threadIdx.x == 0) {
+        best_idx[b] = -1;
+        best_cost[b] = __builtin_nan("");
+        if (n_out) n_out[b] = 0;
+    }
 }
 
 }  // namespace fp

@@ -110,6 +110,44 @@ __device__ inline void stage_ego(const KernelArgs& ka, int b, double* lds, EgoCt
     __syncthreads();
 }
 
+// ---------------------------------------------------------------------------
+// The reader of the obstacle rows stage_ego leaves: LDS rows are x, y, cos, sin with x = NaN for "no state", one row per checked pose
+// (row i / check_stride); scene-table rows are x, y, yaw, valid with valid == 0.0 for "no state", one row per time step (row i + t_now).
+// Column j of either is obstacle e.col0 + j of obs_nvert / obs_poly.  A caller keeps its own broad phase between obs_centre and
+// obs_heading: the trigonometry of a table row is paid only for the pairs that pass it.
+// ---------------------------------------------------------------------------
+// the row of checked pose i, or nullptr: the pose lies outside the table, where no obstacle has a state
+__device__ __forceinline__ const double* obs_row(const EgoCtx& e, int i, int stride)
+{
+    if (e.obs_lds) return i / stride < e.rows ? e.obs_lds + (size_t)(i / stride) * e.n_obs * 4 : nullptr;
+    const int ts = i + e.t_now;
+    return ts >= 0 && ts < e.T_obs ? e.obs_glb + (size_t)ts * e.n_obs * 4 : nullptr;
+}
+// centre of column j in that row; false: the obstacle has no state there.  nan_ok: the caller's next test is false for a NaN centre
+// anyway (a broad phase written as !(d2 < R2)) and takes an LDS row's "no state" as that NaN - one compare less per pair
+__device__ __forceinline__ bool obs_centre(const EgoCtx& e, const double* row, int j, double& ox, double& oy, bool nan_ok = false)
+{
+    ox = row[4 * j];
+    oy = row[4 * j + 1];
+    return e.obs_lds ? nan_ok || ox == ox : row[4 * j + 3] != 0.0;
+}
+// cos / sin of the column's orientation: stored in LDS, sincos_snapped from the table
+__device__ __forceinline__ void obs_heading(const EgoCtx& e, const double* row, int j, double& oc, double& os)
+{
+    oc = row[4 * j + 2];
+    os = row[4 * j + 3];
+    if (!e.obs_lds) sincos_snapped(row[4 * j + 2], os, oc);
+}
+// vertices of the column's polygon (0: a rectangle of the staged sizes) and its ring
+__device__ __forceinline__ int obs_nvert(const KernelArgs& ka, const EgoCtx& e, int j) { return ka.b.obs_nvert ? ka.b.obs_nvert[e.col0 + j] : 0; }
+__device__ __forceinline__ const double* obs_ring(const KernelArgs& ka, const EgoCtx& e, int j) { return ka.b.obs_poly + (e.col0 + j) * 2 * (size_t)ka.b.poly_stride; }
+// Euclidean distance of the ego footprint to column j at pose (ox, oy, oc, os), whatever the column's shape
+__device__ __forceinline__ double shape_distance(const KernelArgs& ka, const EgoCtx& e, const Obb& ego, int j, double ox, double oy, double oc, double os)
+{
+    const int nvert = obs_nvert(ka, e, j);
+    return nvert > 0 ? poly_distance(ego, ox, oy, oc, os, obs_ring(ka, e, j), nvert) : obb_distance(ego, Obb{ox, oy, oc, os, e.obs_dim[4 * j], e.obs_dim[4 * j + 1]});
+}
+
 // dynamic LDS of a kernel that calls stage_ego: the spline and the obstacle sizes always, the pose rows when they fit max_bytes
 inline int ego_lds_bytes(const fp_params& p, const fp_batch& b, int max_bytes, int* lds_doubles)
 {

@@ -14,12 +14,12 @@
 //     line ((2 + 8) nx doubles, at most 80 KB at FP_MAX_KNOTS), then one byte per profile for its verdict;
 //   - profile pass: the wavefronts take the profiles round-robin.  Every lane solves the profile's quartic (quartic_bvp: a division and
 //     a dozen multiplications, cheaper than a staging pass with a barrier of its own, and a lattice of any size needs no fallback); the
-//     lanes take the points 1 + lane, 65 + lane, ... < M: quartic_eval (the arithmetic of every series dump), spline_segment with the
-//     uniform-spacing guess for s + front - and for s when the lateral check is on -, the compares.  __ballot gives the two verdicts; a
+//     lanes take the points 1 + lane, 65 + lane, ... < M: quartic_eval (the arithmetic of every series dump), the segment look-up (see
+//     spline_segment_clamped) for s + front - and for s when the lateral check is on -, the compares.  __ballot gives the two verdicts; a
 //     profile ends once every bit it can get is found;
 //   - row pass, after a barrier: one coalesced pass over the ego's C flag words, one candidate per thread - OR the profile's bits in (a
 //     vector store, and only when the word changes), keep the argmin among the own candidates, count the violating ones by ballot;
-//     wave_best and a merge over the four wavefronts in LDS finish it (best_merge: the last minimum wins).
+//     see finish_ego for the rest.
 // No atomics, no scratch, every reduction a fixed tree or a ballot: two runs give the same bits.
 #include "frenet_device.h"
 #include "frenet_kernels.h"
@@ -32,17 +32,11 @@ constexpr int kEnvWaves = kEnvThreads / kWave;
 __global__ __launch_bounds__(kEnvThreads) void speed_envelope_kernel(EnvelopeArgs a, int lateral)
 {
     extern __shared__ __attribute__((aligned(16))) double lds[];
-    __shared__ Best s_best[kEnvWaves];
-    __shared__ int s_limited[kEnvWaves];
     const int b = a.perm ? a.perm[blockIdx.x] : (int)blockIdx.x;
     const int tid = threadIdx.x, lane = tid & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane(tid / kWave);
     if (a.skip && a.skip[b]) {  // not planned: the dense pass wrote no rows for this ego
-        if (tid == 0) {
-            a.best_idx[b] = -1;
-            a.best_cost[b] = __builtin_nan("");
-            if (a.n_limited) a.n_limited[b] = 0;
-        }
+        skip_ego(b, a.best_idx, a.best_cost, a.count);
         return;
     }
     const int nv = a.nv, P = a.nv * a.nt, C = a.nd * P;
@@ -69,7 +63,6 @@ __global__ __launch_bounds__(kEnvThreads) void speed_envelope_kernel(EnvelopeArg
     __syncthreads();
     const SplineLds sp{knots, coef, nx, nx};
     const double guess_scale = (double)(nx - 1) / (knots[nx - 1] - knots[0]);
-    const double first_knot = knots[0];
     const double tick = a.tick_t, front = a.front, tol = a.tol, max_lat = a.max_lat_accel;
     const double* eg = a.ego + (size_t)b * 6;
     const double s0 = eg[0], s_d0 = eg[1], s_dd0 = eg[2];
@@ -90,12 +83,10 @@ __global__ __launch_bounds__(kEnvThreads) void speed_envelope_kernel(EnvelopeArg
                     double s, s_d, unused_a, unused_j;
                     quartic_eval(lon, (double)i * tick, s, s_d, unused_a, unused_j);
                     const double s_q = s + front;
-                    int k = spline_segment(sp, s_q, -1, guess_scale);
-                    if (k < 0) k = s_q < first_knot || nx < 2 ? 0 : nx - 2;  // (the clamp keeps the reads inside the rows whatever s_q is)
+                    int k = spline_segment_clamped(sp, s_q, guess_scale);
                     fast = s_d > lim[k] + tol;  // (+inf, and a NaN, compare false: no limit there)
                     if (lateral) {
-                        k = spline_segment(sp, s, -1, guess_scale);
-                        if (k < 0) k = s < first_knot || nx < 2 ? 0 : nx - 2;
+                        k = spline_segment_clamped(sp, s, guess_scale);
                         const double dx = s - knots[k];
                         const double* c = coef + k;
                         const double bx = c[nx], cx = c[2 * nx], dx3 = c[3 * nx], by = c[5 * nx], cy = c[6 * nx], dy3 = c[7 * nx];
@@ -129,23 +120,7 @@ __global__ __launch_bounds__(kEnvThreads) void speed_envelope_kernel(EnvelopeArg
         }
         limited += __popcll(__ballot(bits != 0u));
     }
-    mine = wave_best(mine);
-    if (lane == 0) {
-        s_best[wave] = mine;
-        s_limited[wave] = limited;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        Best r = s_best[0];
-        int n = s_limited[0];
-        for (int w = 1; w < kEnvWaves; ++w) {
-            r = best_merge(r, s_best[w]);
-            n += s_limited[w];
-        }
-        a.best_idx[b] = r.idx;
-        a.best_cost[b] = r.idx >= 0 ? r.cost : __builtin_nan("");
-        if (a.n_limited) a.n_limited[b] = n;
-    }
+    finish_ego<kEnvWaves>(mine, limited, b, a.best_idx, a.best_cost, a.count);
 }
 
 hipError_t launch_speed_envelope(const EnvelopeArgs& a, hipStream_t stream)
@@ -155,11 +130,7 @@ hipError_t launch_speed_envelope(const EnvelopeArgs& a, hipStream_t stream)
         !a.flag_tbl || !a.best_idx || !a.best_cost || !a.v_limit || (lateral && !a.coef))
         return hipErrorInvalidValue;  // (internal: fp_speed_envelope has checked its arguments)
     const int bytes = (2 + (lateral ? 8 : 0)) * a.NX * 8 + ((a.nv * a.nt + 15) & ~15);  // <= 80 KB + 16 KB
-    FP_LDS_SLOTS(configured);
-    hipError_t err = ensure_dynamic_lds((const void*)speed_envelope_kernel, bytes, configured);
-    if (err != hipSuccess) return err;
-    hipLaunchKernelGGL(speed_envelope_kernel, dim3(a.B), dim3(kEnvThreads), bytes, stream, a, lateral);
-    return hipGetLastError();
+    return launch_with_lds<speed_envelope_kernel>(dim3(a.B), dim3(kEnvThreads), bytes, stream, a, lateral);
 }
 
 }  // namespace fp

@@ -613,7 +613,7 @@ __device__ uint32_t wave_traj_flags(const KernelArgs& ka, int b, const double* e
             // Cartesian points: the collision checks read poses k < min(M, horizon) and the point after each (heading); the optional
             // curvature checks read all of them.  The rest of the trajectory only needs its masks and the range test above.
             if (!off && i <= need_xy) {
-                const double d = fma(fma(fma(fma(fma(lat.a5, t, lat.a4), t, lat.a3), t, lat.a2), t, lat.a1), t, lat.a0);
+                const double d = quintic_pos(lat, t);
                 const int seg = spline_segment(sp, s, -1, seg_scale < 1e300 ? seg_scale : 0.0);
                 double px, py, tx, ty, cx, cy;
                 spline_frame(sp, seg, s - L.knots[seg], px, py, tx, ty);
@@ -1178,8 +1178,8 @@ hipError_t launch_fiss_refine(const FissArgs& fa, hipStream_t stream, int table_
         if (fa.ka.b.n_obs < (1 << 23) && (long)rows * fa.ka.b.n_obs * 16 <= (long)table_kb * 1024) pt_rows = rows;
     }
     const int bytes = refine_lds_bytes(fa.ka.b.NX, pt_rows * fa.ka.b.n_obs, pts);
-    FP_LDS_SLOTS(configured);
-    FP_LDS_SLOTS(configured_big);
+    static LdsSlots configured;
+    static LdsSlots configured_big;
     if (big) {
         hipError_t e = ensure_dynamic_lds((const void*)fiss_refine_kernel<4>, bytes, configured_big);
         if (e != hipSuccess) return e;
@@ -1198,8 +1198,8 @@ hipError_t launch_fiss_search(const FissArgs& fa, hipStream_t stream)
     const int C = fa.ka.p.nd * fa.ka.p.nv * fa.ka.p.nt;
     int P = kWave;  // (at least one element per lane: the register sort of small lattices)
     while (P < C) P <<= 1;  // C <= FP_MAX_CAND = 4096: at most 64 words of rank bits, one per lane
-    FP_LDS_SLOTS(configured);
-    FP_LDS_SLOTS(configured_wide);
+    static LdsSlots configured;
+    static LdsSlots configured_wide;
     if (P <= 4 * kWave) {  // the register sorts of one wavefront
         const int bytes = C * (8 + 8 + 2 + 2 + 1 + 1) + P * (8 + 2) + 32;
         hipError_t e = ensure_dynamic_lds((const void*)fiss_search_kernel<1>, bytes, configured);

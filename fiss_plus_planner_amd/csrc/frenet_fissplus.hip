@@ -23,10 +23,10 @@ __global__ __launch_bounds__(W * kWave, W >= 8 ? 8 : 1) void fissplus_search_ker
 hipError_t launch_fissplus_search(const FissArgs& fa, hipStream_t stream)
 {
     const int C = fa.ka.p.nd * fa.ka.p.nv * fa.ka.p.nt;
-    FP_LDS_SLOTS(cfg_1);
-    FP_LDS_SLOTS(cfg_4);
-    FP_LDS_SLOTS(cfg_4s);
-    FP_LDS_SLOTS(cfg_4w);
+    static LdsSlots cfg_1;
+    static LdsSlots cfg_4;
+    static LdsSlots cfg_4s;
+    static LdsSlots cfg_4w;
 #ifndef FP_SEARCH_SMALL
 #define FP_SEARCH_SMALL (4 * kWave)  // lattices up to this size: one wavefront
 #endif

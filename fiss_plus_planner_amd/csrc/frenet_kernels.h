@@ -10,30 +10,43 @@
 namespace fp {
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is per device and not free: remember the largest size configured per
-// (kernel, device).  `slot` is a function-local static array of kMaxDevices ints initialised to -1.  Several host threads may
-// launch on one device (ShardedEngine(shards_per_device > 1), two contexts on two streams): the check-and-set is serialised, so
-// the recorded size is always the size the runtime was last told (a smaller request can never land after a larger one).
+// (kernel, device).  `slot` is a static LdsSlots of the kernel: per device the configured bytes + 1, so that the zeroes a static
+// object starts with say "nothing configured yet".  Several host threads may launch on one device (ShardedEngine(shards_per_device >
+// 1), two contexts on two streams): the check-and-set is serialised, so the recorded size is always the size the runtime was last
+// told (a smaller request can never land after a larger one).
 constexpr int kMaxDevices = 64;
+struct LdsSlots {
+    int bytes1[kMaxDevices];
+};
 inline std::mutex& dynamic_lds_mutex()
 {
     static std::mutex m;
     return m;
 }
-inline hipError_t ensure_dynamic_lds(const void* kernel, int bytes, int* slot)
+inline hipError_t ensure_dynamic_lds(const void* kernel, int bytes, LdsSlots& slot)
 {
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
     std::lock_guard<std::mutex> lock(dynamic_lds_mutex());
     if (dev < 0 || dev >= kMaxDevices) return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (bytes > slot[dev]) {
+    if (bytes >= slot.bytes1[dev]) {
         e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
         if (e != hipSuccess) return e;
-        slot[dev] = bytes;
+        slot.bytes1[dev] = bytes + 1;
     }
     return hipSuccess;
 }
-#define FP_LDS_SLOTS(name) static int name[fp::kMaxDevices] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1}
+// The launch of a kernel that has one instance: its slots, the LDS attribute, the launch, the launch's error
+template <auto Kernel, typename... Args>
+hipError_t launch_with_lds(dim3 grid, dim3 block, int bytes, hipStream_t stream, const Args&... args)
+{
+    static LdsSlots configured;
+    hipError_t err = ensure_dynamic_lds((const void*)Kernel, bytes, configured);
+    if (err != hipSuccess) return err;
+    hipLaunchKernelGGL(Kernel, grid, block, bytes, stream, args...);
+    return hipGetLastError();
+}
 
 // Everything a kernel needs, passed by value as the kernel argument block.
 // All pointers are device addresses.
@@ -200,52 +213,41 @@ struct RankArgs {
     int32_t* n_feasible = nullptr;
 };
 hipError_t launch_rank_feasible(const RankArgs& a, hipStream_t stream);
-// The road-boundary check behind the dense pass (frenet_boundary.hip, fp_boundary_mask): writes FP_FLAG_BOUNDARY of every candidate in
-// flag_tbl [B][C] and the ego's argmin over what is still feasible.  One workgroup per ego, in the order of perm (optional).  Device
-// addresses; left / right are [F][NX] lateral offsets of the road edges at the knots; n_masked (optional) [B].
-struct BoundaryArgs {
+// What the table passes behind the dense pass share (frenet_boundary.hip, frenet_envelope.hip): one workgroup per ego, in the order of
+// perm (optional), over the ego's rows of cost_tbl / flag_tbl [B][C]; each rewrites bits of the flag words and writes the ego's argmin
+// over what is still feasible, and - optionally - how many candidates it flagged (count [B]).  Device addresses.
+struct TablePassArgs {
     int B = 0, NX = 0, nd = 1, nv = 1, nt = 1;
-    double tick_t = 0.0, veh_l = 0.0, veh_w = 0.0, margin = 0.0;
-    const double* d_samples = nullptr;
+    double tick_t = 0.0;
     const double* t_samples = nullptr;
     const double* v_samples = nullptr;
     const double* ego = nullptr;
     const int32_t* frame_of = nullptr;
     const int32_t* nx = nullptr;
     const double* knots = nullptr;
+    const int32_t* skip = nullptr;
+    const int32_t* perm = nullptr;
+    const double* cost_tbl = nullptr;
+    uint32_t* flag_tbl = nullptr;
+    int32_t* best_idx = nullptr;
+    double* best_cost = nullptr;
+    int32_t* count = nullptr;
+};
+// The road-boundary check (fp_boundary_mask): FP_FLAG_BOUNDARY of every candidate.  left / right are [F][NX] lateral offsets of the road
+// edges at the knots; count = n_masked.
+struct BoundaryArgs : TablePassArgs {
+    double veh_l = 0.0, veh_w = 0.0, margin = 0.0;
+    const double* d_samples = nullptr;
     const double* left = nullptr;
     const double* right = nullptr;
-    const int32_t* skip = nullptr;
-    const int32_t* perm = nullptr;
-    const double* cost_tbl = nullptr;
-    uint32_t* flag_tbl = nullptr;
-    int32_t* best_idx = nullptr;
-    double* best_cost = nullptr;
-    int32_t* n_masked = nullptr;
 };
 hipError_t launch_boundary_mask(const BoundaryArgs& a, hipStream_t stream);
-// Position-dependent speed limits behind the dense pass (frenet_envelope.hip, fp_speed_envelope): ORs FP_FLAG_SPEED / FP_FLAG_ACCEL into
-// the flag words of flag_tbl [B][C] and writes the ego's argmin over what is still feasible.  One workgroup per ego, in the order of perm
-// (optional).  Device addresses; v_limit is [F][NX] (the limit of the segment that starts at the knot); coef is read only when
-// max_lat_accel > 0; n_limited (optional) [B].
-struct EnvelopeArgs {
-    int B = 0, NX = 0, nd = 1, nv = 1, nt = 1;
-    double tick_t = 0.0, front = 0.0, tol = 0.0, max_lat_accel = 0.0;
-    const double* t_samples = nullptr;
-    const double* v_samples = nullptr;
-    const double* ego = nullptr;
-    const int32_t* frame_of = nullptr;
-    const int32_t* nx = nullptr;
-    const double* knots = nullptr;
+// Position-dependent speed limits (fp_speed_envelope): ORs FP_FLAG_SPEED / FP_FLAG_ACCEL into the flag words.  v_limit is [F][NX] (the
+// limit of the segment that starts at the knot); coef is read only when max_lat_accel > 0; count = n_limited.
+struct EnvelopeArgs : TablePassArgs {
+    double front = 0.0, tol = 0.0, max_lat_accel = 0.0;
     const double* coef = nullptr;
     const double* v_limit = nullptr;
-    const int32_t* skip = nullptr;
-    const int32_t* perm = nullptr;
-    const double* cost_tbl = nullptr;
-    uint32_t* flag_tbl = nullptr;
-    int32_t* best_idx = nullptr;
-    double* best_cost = nullptr;
-    int32_t* n_limited = nullptr;
 };
 hipError_t launch_speed_envelope(const EnvelopeArgs& a, hipStream_t stream);
 // The obstacle margin of K chosen plans per ego (frenet_margins.hip, fp_traj_margins): one workgroup per ego, in the order of perm

@@ -227,26 +227,23 @@ __device__ double pose_min_gap(const KernelArgs& ka, const EgoCtx& e, int i, dou
     if (!(x == x) || !(y == y) || !(c == c)) return -__builtin_inf();
     Obb ego{x, y, c, s, 0.5 * ka.p.veh_l, 0.5 * ka.p.veh_w};
     const double r_e = sqrt(fma(ego.hl, ego.hl, ego.hw * ego.hw));
-    const int n = e.n_obs;
-    const int ts = i + e.t_now;
     double g = __builtin_inf();
-    if (ts < 0 || ts >= e.T_obs) return g;
-    const double* row = e.obs_glb + (size_t)ts * n * 4;
-    for (int j = 0; j < n; ++j) {
-        if (row[4 * j + 3] == 0.0) continue;
-        const double ox = row[4 * j], oy = row[4 * j + 1];
+    const double* row = obs_row(e, i, ka.p.check_stride);  // (see frenet_ego.h; launch_audit leaves the rows in the scene table)
+    if (!row) return g;
+    for (int j = 0; j < e.n_obs; ++j) {
+        double ox, oy, oc, os;
+        if (!obs_centre(e, row, j, ox, oy)) continue;
         const double R = r_e + e.obs_dim[4 * j + 2] + 2.0 * FP_AUDIT_GAP_TOL;  // beyond it the boxes miss by more than the tolerance
         const double dx = ox - x, dy = oy - y;
         if (!(fma(dx, dx, dy * dy) <= R * R)) {
             if (!(dx == dx) || !(dy == dy)) g = -__builtin_inf();  // NaN pose: polygon construction fails -> collision
             continue;
         }
-        double oc, os;
-        sincos_snapped(row[4 * j + 2], os, oc);
+        obs_heading(e, row, j, oc, os);
         // (a polygon column: the larger of the two gaps - its box is a necessary condition, the polygon itself decides)
         double gj = obb_gap(ego, Obb{ox, oy, oc, os, e.obs_dim[4 * j], e.obs_dim[4 * j + 1]});
-        const int nvert = ka.b.obs_nvert ? ka.b.obs_nvert[e.col0 + j] : 0;
-        if (nvert > 0) gj = fmax(gj, poly_gap(ego, ox, oy, oc, os, ka.b.obs_poly + (e.col0 + j) * 2 * (size_t)ka.b.poly_stride, nvert));
+        const int nvert = obs_nvert(ka, e, j);
+        if (nvert > 0) gj = fmax(gj, poly_gap(ego, ox, oy, oc, os, obs_ring(ka, e, j), nvert));
         g = fmin(g, gj);
     }
     return g;
@@ -266,10 +263,10 @@ __device__ double candidate_min_gap(const KernelArgs& ka, const EgoCtx& e, doubl
     const int cs = p.check_stride;
     for (int i = 0; i < N; ++i) {
         const double t = (double)i * p.tick_t;
-        const double sv = fma(fma(fma(fma(lon.a4, t, lon.a3), t, lon.a2), t, lon.a1), t, lon.a0);
+        const double sv = quartic_pos(lon, t);
         seg = spline_segment(e.sp, sv, seg);
         if (seg < 0) { M = i; break; }
-        const double dv = fma(fma(fma(fma(fma(lat.a5, t, lat.a4), t, lat.a3), t, lat.a2), t, lat.a1), t, lat.a0);
+        const double dv = quintic_pos(lat, t);
         double px, py, tx, ty, x, y;
         spline_frame(e.sp, seg, sv - e.sp.knots[seg], px, py, tx, ty);
         frenet_to_cartesian(px, py, tx, ty, dv, x, y);
@@ -605,11 +602,7 @@ hipError_t launch_audit(const KernelArgs& ka, uint32_t* audit, hipStream_t strea
 {
     int lds_doubles = 0;
     const int bytes = ego_lds_bytes(ka.p, ka.b, 0, &lds_doubles)  /* spline + sizes only: the poses are read from the scene table */;
-    FP_LDS_SLOTS(configured);
-    hipError_t err = ensure_dynamic_lds((const void*)audit_kernel, bytes, configured);
-    if (err != hipSuccess) return err;
-    hipLaunchKernelGGL(audit_kernel, dim3(ka.b.B), dim3(kAuditThreads), bytes, stream, ka, lds_doubles, audit);
-    return hipGetLastError();
+    return launch_with_lds<audit_kernel>(dim3(ka.b.B), dim3(kAuditThreads), bytes, stream, ka, lds_doubles, audit);
 }
 
 hipError_t launch_lattice_percand(const KernelArgs& ka, hipStream_t stream)
@@ -619,8 +612,8 @@ hipError_t launch_lattice_percand(const KernelArgs& ka, hipStream_t stream)
     if (threads > 512) threads = 512;
     int lds_doubles = 0;
     const int bytes = ego_lds_bytes(ka.p, ka.b, 150 * 1024, &lds_doubles);
-    FP_LDS_SLOTS(configured);
-    FP_LDS_SLOTS(configured_curv);
+    static LdsSlots configured;
+    static LdsSlots configured_curv;
     if (ka.p.curvature_mask) {
         hipError_t err = ensure_dynamic_lds((const void*)lattice_percand_kernel<true>, bytes, configured_curv);
         if (err != hipSuccess) return err;
@@ -714,8 +707,8 @@ hipError_t launch_eval_trajs(const KernelArgs& ka, int K, const double* end_stat
     if (threads > 256) threads = 256;
     int lds_doubles = 0;
     const int bytes = ego_lds_bytes(ka.p, ka.b, 150 * 1024, &lds_doubles);
-    FP_LDS_SLOTS(configured);
-    FP_LDS_SLOTS(configured_curv);
+    static LdsSlots configured;
+    static LdsSlots configured_curv;
     if (ka.p.curvature_mask) {
         hipError_t err = ensure_dynamic_lds((const void*)eval_trajs_kernel<true>, bytes, configured_curv);
         if (err != hipSuccess) return err;

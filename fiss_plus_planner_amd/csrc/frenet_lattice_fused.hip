@@ -1661,7 +1661,7 @@ constexpr LatticeFn lattice_kernel_of()
 }
 struct LatticeInstance {
     LatticeFn kernel;
-    int lds_slot[kMaxDevices];  // (zero-initialised where ensure_dynamic_lds expects -1: no plan's LDS is zero)
+    LdsSlots lds_slot;
 };
 template <size_t... I>
 static LatticeInstance& lattice_instance_at(int i, std::index_sequence<I...>)

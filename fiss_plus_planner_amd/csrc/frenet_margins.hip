@@ -6,14 +6,13 @@
 // the batch and writes three numbers per plan.
 //
 // margins_kernel: one 512-thread workgroup per ego, staged by stage_ego like the clearance rescoring kernel (spline, obstacle sizes
-// and - when they fit kMarginLdsBytes - the rows the pose set can touch as x, y, cos, sin in LDS, once for all K planes; else the rows
-// are read from the scene table).  A wavefront takes one plane at a time:
+// and - when they fit kMarginLdsBytes - the rows the pose set can touch in LDS, once for all K planes; else the rows are read from the
+// scene table: see obs_row, frenet_ego.h).  A wavefront takes one plane at a time:
 //   - M, the first point off the reference line, by a ballot over the longitudinal quartic (64 points per round, any N up to
 //     FP_MAX_POINTS: no series is written, so the 128-point chunks of the series writers do not apply);
 //   - the lanes are the checked poses (i = 0, pose_stride, ... < min(M, final_time_step - t_now)); a plan with at most 32 poses gives
 //     every pose 2, 4 or kMarginSplit lanes, which share the pose's columns round-robin.  A lane evaluates its pose from the
-//     polynomials (traj_point, step_heading: the arithmetic of the collision check and of the clearance term) and keeps it in
-//     registers;
+//     polynomials (see checked_pose: the arithmetic of the collision check and of the clearance term) and keeps it in registers;
 //   - broad phase: a pair is skipped only when (centre distance) > (lane's minimum + both circumradii), the right-hand side widened by
 //     1e-9 relative + 1e-9 absolute - the true distance is at least centre distance - circumradii, so a skipped pair is strictly
 //     further away than what the lane already holds and can neither win nor tie; a lane that holds a contact (distance 0) is done:
@@ -42,20 +41,6 @@ __device__ __forceinline__ MarginMin margin_merge(MarginMin a, MarginMin b)
 {
     const bool take_b = b.d < a.d || (b.d == a.d && (b.i < a.i || (b.i == a.i && b.j < a.j)));
     return take_b ? b : a;
-}
-
-// Cartesian point i of the plan (lon, lat); false when it lies off the reference line (the arithmetic of every series dump)
-__device__ __forceinline__ bool margin_point(const fp_params& p, const SplineLds& sp, double guess_scale, const Quartic& lon, const Quintic& lat, int i, double& x, double& y)
-{
-    const double t = (double)i * p.tick_t;
-    const double sv = fma(fma(fma(fma(lon.a4, t, lon.a3), t, lon.a2), t, lon.a1), t, lon.a0);
-    const int seg = spline_segment(sp, sv, -1, guess_scale);
-    if (seg < 0) return false;
-    const double dv = fma(fma(fma(fma(fma(lat.a5, t, lat.a4), t, lat.a3), t, lat.a2), t, lat.a1), t, lat.a0);
-    double px, py, tx, ty;
-    spline_frame(sp, seg, sv - sp.knots[seg], px, py, tx, ty);
-    frenet_to_cartesian(px, py, tx, ty, dv, x, y);
-    return true;
 }
 
 __global__ __launch_bounds__(kMarginThreads) void margins_kernel(KernelArgs ka, MarginArgs m, int lds_doubles)
@@ -106,7 +91,7 @@ __global__ __launch_bounds__(kMarginThreads) void margins_kernel(KernelArgs ka, 
         for (int i0 = 0; i0 < N; i0 += kWave) {
             const int i = i0 + lane;
             const double t = (double)i * p.tick_t;
-            const double sv = fma(fma(fma(fma(lon.a4, t, lon.a3), t, lon.a2), t, lon.a1), t, lon.a0);
+            const double sv = quartic_pos(lon, t);
             const unsigned long long off = __ballot(i < N && (!(sv >= k0) || !(sv < kl)));
             if (off) { M = i0 + __ffsll((long long)off) - 1; break; }
         }
@@ -121,33 +106,18 @@ __global__ __launch_bounds__(kMarginThreads) void margins_kernel(KernelArgs ka, 
             for (int q = lane / split; q < n_pose; q += per_round) {
                 if (mine.d == 0.0) break;  // a contact: every later pair of this lane loses the tie
                 const int i = q * cs;
-                const double* row;
-                if (e.obs_lds) {
-                    if (q >= e.rows) break;  // beyond the table: no obstacle has a state there, nor at any later pose
-                    row = e.obs_lds + (size_t)q * n_obs * 4;
-                } else {
-                    const int ts = i + e.t_now;
-                    if (ts < 0 || ts >= e.T_obs) continue;
-                    row = e.obs_glb + (size_t)ts * n_obs * 4;
-                }
-                // heading of pose i: the step to the next point; the last pose repeats the previous heading
-                const int ia = i + 1 < M ? i : i - 1;
-                double x0, y0, x1, y1, hc, hs;
-                if (!margin_point(p, e.sp, guess_scale, lon, lat, ia, x0, y0) || !margin_point(p, e.sp, guess_scale, lon, lat, ia + 1, x1, y1)) continue;
-                step_heading(x1 - x0, y1 - y0, hc, hs);
-                const Obb ego{ia == i ? x0 : x1, ia == i ? y0 : y1, hc, hs, hl, hw};
+                const double* row = obs_row(e, i, cs);
+                Obb ego;
+                if (!row || !checked_pose(p, e.sp, guess_scale, lon, lat, i, M, ego)) continue;  // no obstacle has a state there / off the line
                 for (int j = sub; j < n_obs; j += split) {
                     if (mine.d == 0.0) break;
-                    const double ox = row[4 * j], oy = row[4 * j + 1];
-                    if (e.obs_lds ? ox != ox : row[4 * j + 3] == 0.0) continue;  // no valid pose in this row
+                    double ox, oy, oc, os;
+                    if (!obs_centre(e, row, j, ox, oy)) continue;
                     const double reach = (mine.d + (r_e + e.obs_dim[4 * j + 2])) * (1.0 + 1e-9) + 1e-9;
                     const double dx = ox - ego.x, dy = oy - ego.y;
                     if (fma(dx, dx, dy * dy) > reach * reach) continue;  // strictly further than the lane's minimum
-                    double oc = row[4 * j + 2], os = row[4 * j + 3];
-                    if (!e.obs_lds) sincos_snapped(row[4 * j + 2], os, oc);
-                    const int nvert = ka.b.obs_nvert ? ka.b.obs_nvert[e.col0 + j] : 0;
-                    const double dist = nvert > 0 ? poly_distance(ego, ox, oy, oc, os, ka.b.obs_poly + (e.col0 + j) * 2 * (size_t)ka.b.poly_stride, nvert)
-                                                  : obb_distance(ego, Obb{ox, oy, oc, os, e.obs_dim[4 * j], e.obs_dim[4 * j + 1]});
+                    obs_heading(e, row, j, oc, os);
+                    const double dist = shape_distance(ka, e, ego, j, ox, oy, oc, os);
                     if (dist < mine.d) mine = MarginMin{dist, i, j};  // (poses and columns ascending: the first of equal distances stays)
                 }
             }
@@ -176,11 +146,7 @@ hipError_t launch_traj_margins(const KernelArgs& ka, const MarginArgs& m, hipStr
         return hipErrorInvalidValue;  // (internal: fp_traj_margins has checked its arguments)
     int lds_doubles = 0;
     const int bytes = ego_lds_bytes(ka.p, ka.b, kMarginLdsBytes, &lds_doubles);
-    FP_LDS_SLOTS(configured);
-    hipError_t err = ensure_dynamic_lds((const void*)margins_kernel, bytes, configured);
-    if (err != hipSuccess) return err;
-    hipLaunchKernelGGL(margins_kernel, dim3(ka.b.B), dim3(kMarginThreads), bytes, stream, ka, m, lds_doubles);
-    return hipGetLastError();
+    return launch_with_lds<margins_kernel>(dim3(ka.b.B), dim3(kMarginThreads), bytes, stream, ka, m, lds_doubles);
 }
 
 }  // namespace fp

@@ -18,6 +18,7 @@
 // lives: two runs, and the two memory spaces, give the same bits.  Plain FP64, no atomics, no scratch.
 #include "frenet_device.h"
 #include "frenet_kernels.h"
+#include "frenet_project.h"
 
 namespace fp {
 
@@ -25,8 +26,6 @@ constexpr int kPredictThreads = 256;
 constexpr int kPredictStagedCols = 1024;         // tracks staged in LDS up to this many columns (52 KB; with 1024 knots: 124 KB)
 constexpr int kPredictTargetGroups = 2048;       // workgroups a launch aims at (8 per compute unit)
 constexpr long kPredictSlabElems = 1L << 24;     // elements per slab at most (the flat index stays far inside 32 bits)
-
-__device__ __forceinline__ bool predict_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }
 
 __global__ __launch_bounds__(kPredictThreads) void obstacles_predict_kernel(PredictArgs a)
 {
@@ -112,7 +111,7 @@ __global__ __launch_bounds__(kPredictThreads) void obstacles_predict_kernel(Pred
             const double l = v0 * tau_e + 0.5 * acc * tau_e * tau_e;
             if (arc) {
                 const double x0 = q[0], y0 = q[1], yaw0 = q[2], kappa = q[5];
-                if (predict_finite(x0) && predict_finite(y0) && predict_finite(yaw0) && predict_finite(v) && predict_finite(acc) && predict_finite(kappa)) {
+                if (finite_f64(x0) && finite_f64(y0) && finite_f64(yaw0) && finite_f64(v) && finite_f64(acc) && finite_f64(kappa)) {
                     const double u = kappa * l / 2.0;
                     const double sinc = fabs(u) < 1e-4 ? 1.0 - u * u / 6.0 : sin(u) / u;
                     double sn, cs;
@@ -124,7 +123,7 @@ __global__ __launch_bounds__(kPredictThreads) void obstacles_predict_kernel(Pred
                 }
             } else {
                 const double sv = q[0] + l, d = q[1];
-                const int seg = nx >= 2 && predict_finite(d) ? spline_segment(sp, sv, -1, guess_scale) : -1;  // (-1: s is NaN or off the line)
+                const int seg = nx >= 2 && finite_f64(d) ? spline_segment(sp, sv, -1, guess_scale) : -1;  // (-1: s is NaN or off the line)
                 if (seg >= 0) {
                     double px, py, tx, ty;
                     spline_frame(sp, seg, sv - sp.knots[seg], px, py, tx, ty);
@@ -158,11 +157,7 @@ hipError_t launch_obstacles_predict(PredictArgs a, hipStream_t stream)
     a.stage_tracks = a.n_obs <= kPredictStagedCols ? 1 : 0;
     const bool frames = a.F > 0 && a.NX >= 2 && a.frame_of_scene && a.nx && a.knots && a.coef;
     const int bytes = (a.stage_tracks ? (6 * a.n_obs + (a.n_obs + 1) / 2) * 8 : 0) + (frames ? 9 * a.NX * 8 : 0);  // <= 52 KB + 72 KB
-    FP_LDS_SLOTS(configured);
-    hipError_t err = ensure_dynamic_lds((const void*)obstacles_predict_kernel, bytes, configured);
-    if (err != hipSuccess) return err;
-    hipLaunchKernelGGL(obstacles_predict_kernel, dim3((unsigned)(a.S * slabs)), dim3(kPredictThreads), bytes, stream, a);
-    return hipGetLastError();
+    return launch_with_lds<obstacles_predict_kernel>(dim3((unsigned)(a.S * slabs)), dim3(kPredictThreads), bytes, stream, a);
 }
 
 }  // namespace fp

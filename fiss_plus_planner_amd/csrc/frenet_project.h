@@ -21,14 +21,15 @@ constexpr double kProjectUnifyMax = 25000.0;
 
 FP_PROJECT_HD inline double project_nan() { return __builtin_nan(""); }
 
-// (NaN and +-inf both fail the comparison)
-FP_PROJECT_HD inline bool project_finite(double v) { return std::fabs(v) <= 1.7976931348623157e308; }
+// The library's one "finite" (NaN and +-inf both fail the comparison): the kernels and the host checks of frenet_abi.hip use it too
+constexpr double kF64Max = 1.7976931348623157e308;
+FP_PROJECT_HD inline bool finite_f64(double v) { return std::fabs(v) <= kF64Max; }
 
 // The state check: x, y, yaw, v all finite.  A NaN position makes every distance comparison false (no nearest point), an infinite
 // yaw never leaves the reference's unification loops.
 FP_PROJECT_HD inline bool project_state_ok(double x, double y, double yaw, double v)
 {
-    return project_finite(x) && project_finite(y) && project_finite(yaw) && project_finite(v);
+    return finite_f64(x) && finite_f64(y) && finite_f64(yaw) && finite_f64(v);
 }
 
 // Number of resampled points of a line of arclength s_last: len(np.arange(0, s_last, 0.1)) = ceil(s_last / 0.1), reduced while the
@@ -39,7 +40,7 @@ FP_PROJECT_HD inline bool project_state_ok(double x, double y, double yaw, doubl
 // indexes past its one-point polyline).
 FP_PROJECT_HD inline int project_point_count(double s_last)
 {
-    if (!project_finite(s_last) || !(s_last > 0.0)) return 0;
+    if (!finite_f64(s_last) || !(s_last > 0.0)) return 0;
     const double c = std::ceil(s_last / kProjectStep);
     if (!(c < 2147483647.0)) return 0;
     int n = (int)c;
