@@ -18,6 +18,7 @@ FP_MAX_POINTS, FP_MAX_KNOTS, FP_MAX_CAND, FP_MAX_POLY_VERTS = 256, 1024, 16384, 
 FP_FAST_POINTS, FP_DEFAULT_STRIDE = 128, 128  # the fast paths' points per trajectory; columns of a series row when traj_stride = 0
 FP_MAX_CAND_SEARCH = 4096  # device-side FISS / FISS+ walks (fp_plan_fiss)
 FP_MAX_RANK = 64  # K of fp_rank_feasible
+FP_MAX_GATES = 32  # gates per frame of fp_gate_mask
 FLAG_SPEED, FLAG_ACCEL, FLAG_COLLISION, FLAG_TRUNCATED = 1, 2, 4, 8
 FLAG_CURVATURE, FLAG_KAPPA_D, FLAG_KAPPA_DD = 16, 32, 64   # optional checks (fp_params.curvature_mask)
 FLAG_CONSTRAINTS = FLAG_SPEED | FLAG_ACCEL | FLAG_CURVATURE | FLAG_KAPPA_D | FLAG_KAPPA_DD
@@ -31,7 +32,7 @@ _up = C.POINTER(C.c_uint32)
 
 # every symbol include/frenet_gpu.h declares (tests check the library exports all of them)
 EXPORTED_SYMBOLS = ("fp_abi_version", "fp_build_flags", "fp_build_compiler", "fp_last_error", "fp_device_count", "fp_device_info", "fp_ctx_create", "fp_ctx_destroy", "fp_ctx_set_option", "fp_ctx_get_option", "fp_ctx_join",
-                    "fp_plan_dense", "fp_winner_trajs", "fp_rank_feasible", "fp_boundary_mask", "fp_speed_envelope", "fp_traj_margins", "fp_obstacles_predict", "fp_eval_trajs", "fp_plan_fiss", "fp_advance", "fp_plan_step", "fp_plan_fiss_step", "fp_loop_record", "fp_frames_build", "fp_from_state", "fp_materialize_all",
+                    "fp_plan_dense", "fp_winner_trajs", "fp_rank_feasible", "fp_boundary_mask", "fp_speed_envelope", "fp_gate_mask", "fp_traj_margins", "fp_obstacles_predict", "fp_eval_trajs", "fp_plan_fiss", "fp_advance", "fp_plan_step", "fp_plan_fiss_step", "fp_loop_record", "fp_frames_build", "fp_from_state", "fp_materialize_all",
                     "fp_group_create", "fp_group_destroy", "fp_group_submit", "fp_group_wait")
 
 
@@ -69,6 +70,12 @@ class FpCorridor(C.Structure):
 class FpSpeedProfile(C.Structure):
     """Per-segment speed limits, read at s + front, and the lateral-acceleration bound on the reference line (fp_speed_envelope)."""
     _fields_ = [("v_limit", C.c_void_p), ("front", C.c_double), ("tol", C.c_double), ("max_lat_accel", C.c_double)]
+
+
+class FpGates(C.Structure):
+    """Stop lines with a state per absolute time step (fp_gate_mask)."""
+    _fields_ = [("gate_s", C.c_void_p), ("closed", C.c_void_p), ("gate_stride", C.c_int32), ("T_gate", C.c_int32), ("front", C.c_double),
+                ("max_decel", C.c_double)]
 
 
 FP_TRACK_NONE, FP_TRACK_LANE, FP_TRACK_ARC = 0, 1, 2  # fp_tracks.model (fp_obstacles_predict)
@@ -177,6 +184,9 @@ def load() -> C.CDLL:
     if hasattr(L, "fp_speed_envelope"):  # (a library of the same ABI version built before the symbol existed lacks it)
         L.fp_speed_envelope.argtypes = [C.c_void_p, C.POINTER(FpParams), C.POINTER(FpBatch), C.POINTER(FpSpeedProfile), C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    if hasattr(L, "fp_gate_mask"):  # (likewise)
+        L.fp_gate_mask.argtypes = [C.c_void_p, C.POINTER(FpParams), C.POINTER(FpBatch), C.POINTER(FpGates), C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     L.fp_traj_margins.argtypes = [C.c_void_p, C.POINTER(FpParams), C.POINTER(FpBatch), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_int, C.c_void_p]
     L.fp_obstacles_predict.argtypes = [C.c_void_p, C.POINTER(FpParams), C.POINTER(FpBatch), C.POINTER(FpTracks), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]

@@ -118,6 +118,13 @@ class ProblemBatch:
     limit_front: float = 0.0               # the limit is read at s + limit_front (veh_l / 2: the front bumper obeys it)
     limit_tol: float = 0.0                 # a point violates when s_d > limit + limit_tol
     max_lat_accel: float = 0.0             # > 0: a point violates when s_d^2 |curvature of the reference line| exceeds it; 0 = off
+    # stop lines that open and close (fp_gates, fp_gate_mask): the arclength of up to FP_MAX_GATES lines per frame (NaN = unused slot) and,
+    # per absolute time step of the obstacle table's clock, the word whose bit g says "gate g is closed" (spline.gate_bits packs it); a
+    # candidate whose front bumper (s + gate_front) moves over a line at a closed step violates; None = no gates
+    gate_s: np.ndarray | None = None        # [F, G]
+    gate_closed: np.ndarray | None = None   # [F, T_gate] uint32
+    gate_front: float = 0.0                 # the line is crossed by s + gate_front (veh_l / 2: the front bumper)
+    gate_max_decel: float = 0.0             # > 0: a gate the ego can no longer stop in front of at this deceleration is waived; 0 = off
     # the obstacle tracks obs_pose can be predicted from on the device (fp_tracks, fp_obstacles_predict; DeviceBatch.predict): the
     # model (FP_TRACK_*) and six numbers per obstacle column, and the frame the LANE tracks of every scene follow; None = no tracks
     track_model: np.ndarray | None = None  # [S, n_obs] int32
@@ -157,6 +164,11 @@ class ProblemBatch:
         if self.speed_limit is not None:
             self.speed_limit = f8(self.speed_limit)
             assert self.speed_limit.shape == (self.F, self.NX)
+        assert (self.gate_s is None) == (self.gate_closed is None), "gate_s and gate_closed come together"
+        if self.gate_s is not None:
+            self.gate_s, self.gate_closed = f8(self.gate_s), np.ascontiguousarray(self.gate_closed, dtype=np.uint32)
+            assert self.gate_s.ndim == 2 and self.gate_s.shape[0] == self.F and 1 <= self.gate_s.shape[1] <= 32  # (FP_MAX_GATES)
+            assert self.gate_closed.ndim == 2 and self.gate_closed.shape[0] == self.F and self.gate_closed.shape[1] >= 1
         assert (self.track_model is None) == (self.track_state is None), "track_model and track_state come together"
         assert self.track_frame is None or self.track_model is not None, "track_frame without tracks"
         if self.track_model is not None:
@@ -215,6 +227,8 @@ class ProblemBatch:
             bound_right=None if self.bound_right is None else self.bound_right[fr], bound_margin=self.bound_margin,
             speed_limit=None if self.speed_limit is None else self.speed_limit[fr], limit_front=self.limit_front, limit_tol=self.limit_tol,
             max_lat_accel=self.max_lat_accel,
+            gate_s=None if self.gate_s is None else self.gate_s[fr], gate_closed=None if self.gate_closed is None else self.gate_closed[fr],
+            gate_front=self.gate_front, gate_max_decel=self.gate_max_decel,
             track_model=None if self.track_model is None else self.track_model[keep_s],
             track_state=None if self.track_state is None else self.track_state[keep_s], track_frame=track_frame,
             meta=dict(self.meta, **(meta or {})))
@@ -245,6 +259,12 @@ class ProblemBatch:
                 a = self.speed_limit
                 h.update(b"speed_limit"); h.update(str(a.shape).encode()); h.update(np.ascontiguousarray(a).tobytes())
             for name in ("limit_front", "limit_tol", "max_lat_accel"):
+                h.update(name.encode()); h.update(np.float64(getattr(self, name)).tobytes())
+        if self.gate_s is not None:  # (batches without gates keep their digests)
+            for name in ("gate_s", "gate_closed"):
+                a = getattr(self, name)
+                h.update(name.encode()); h.update(str(a.shape).encode()); h.update(np.ascontiguousarray(a).tobytes())
+            for name in ("gate_front", "gate_max_decel"):
                 h.update(name.encode()); h.update(np.float64(getattr(self, name)).tobytes())
         if self.track_model is not None:  # (batches without tracks keep their digests)
             for name in ("track_model", "track_state") + (("track_frame",) if self.track_frame is not None else ()):

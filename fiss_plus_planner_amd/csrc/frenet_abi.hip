@@ -196,6 +196,7 @@ struct fp_ctx {
     int rank_launches = 0;         // fp_ctx_get_option("rank_launches"): launches of the ranking kernel (fp_rank_feasible)
     int boundary_launches = 0;     // fp_ctx_get_option("boundary_launches"): launches of the road-boundary kernel (fp_boundary_mask)
     int envelope_launches = 0;     // fp_ctx_get_option("envelope_launches"): launches of the speed-envelope kernel (fp_speed_envelope)
+    int gate_launches = 0;         // fp_ctx_get_option("gate_launches"): launches of the gate kernel (fp_gate_mask)
     int margin_launches = 0;       // fp_ctx_get_option("margin_launches"): launches of the plan-margin kernel (fp_traj_margins)
     int predict_launches = 0;      // fp_ctx_get_option("predict_launches"): launches of the obstacle prediction kernel (fp_obstacles_predict)
     int from_state_launches = 0;   // fp_ctx_get_option("from_state_launches"): launches of the projection kernel (fp_from_state)
@@ -1418,7 +1419,7 @@ int fp_ctx_get_option(fp_ctx* ctx, const char* name, int* value)
     const struct { const char* n; int v; } tab[] = {
         {"lattice_kernel", ctx->lattice_kernel}, {"lattice_split", ctx->lattice_split}, {"lattice_group", ctx->lattice_group}, {"lattice_tail", ctx->lattice_tail}, {"lattice_occupancy", ctx->lattice_occupancy}, {"resident_groups", ctx->resident_groups}, {"zero_copy_in", ctx->zero_copy_in}, {"stage_kernel", ctx->stage_kernel}, {"inline_inputs", ctx->inline_inputs}, {"lattice_order", ctx->lattice_order},
         {"refine_table_kb", ctx->refine_table_kb}, {"fiss_stages", ctx->fiss_stages}, {"fiss_jump", ctx->fiss_jump}, {"validate", ctx->validate}, {"lattice_winner", ctx->lattice_winner}, {"fiss_fused", ctx->fiss_fused}, {"appended_workgroups", ctx->appended_ok ? 1 : 0}, {"handover_failed", ctx->hand_err ? *(volatile int32_t*)ctx->hand_err : 0}, {"overlap", ctx->overlap}, {"overlapped_calls", ctx->overlapped_calls}, {"clearance_launches", ctx->clearance_launches + (ctx->twin ? ctx->twin->clearance_launches : 0)}, {"lattice_launches", ctx->lattice_launches + (ctx->twin ? ctx->twin->lattice_launches : 0)},
-        {"looplog_launches", ctx->looplog_launches}, {"rank_launches", ctx->rank_launches}, {"boundary_launches", ctx->boundary_launches}, {"envelope_launches", ctx->envelope_launches}, {"margin_launches", ctx->margin_launches}, {"predict_launches", ctx->predict_launches}, {"from_state_launches", ctx->from_state_launches}, {"lattice_ordered_launches", ctx->lattice_ordered_launches + (ctx->twin ? ctx->twin->lattice_ordered_launches : 0)},
+        {"looplog_launches", ctx->looplog_launches}, {"rank_launches", ctx->rank_launches}, {"boundary_launches", ctx->boundary_launches}, {"envelope_launches", ctx->envelope_launches}, {"gate_launches", ctx->gate_launches}, {"margin_launches", ctx->margin_launches}, {"predict_launches", ctx->predict_launches}, {"from_state_launches", ctx->from_state_launches}, {"lattice_ordered_launches", ctx->lattice_ordered_launches + (ctx->twin ? ctx->twin->lattice_ordered_launches : 0)},
         {"lattice_launches_2", (int)fp::lattice_launches_per_cu(0)}, {"lattice_launches_3", (int)fp::lattice_launches_per_cu(1)}, {"lattice_launches_4", (int)fp::lattice_launches_per_cu(2)}};
     for (const auto& t : tab)
         if (strcmp(name, t.n) == 0) { *value = t.v; return FP_OK; }
@@ -1677,6 +1678,46 @@ int fp_speed_envelope(fp_ctx* ctx, const fp_params* params, const fp_batch* batc
     FP_TRY(hs.commit(sl));
     LAUNCH_TRY(fp::launch_speed_envelope(a, ctx->stream), "speed-envelope kernel");
     ++ctx->envelope_launches;
+    return hs.fetch_out();
+}
+
+int fp_gate_mask(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, const fp_gates* gates, const double* cost_tbl, uint32_t* flag_tbl,
+                 int32_t* best_idx, double* best_cost, int32_t* n_gated, int mem, void* stream)
+{
+    FP_TRY(common_checks(ctx, params, batch, mem, stream, /*need_coef=*/false));  // (the line's coefficients are not read)
+    if (!gates || !gates->gate_s || !gates->closed) return fail(FP_EINVAL, "fp_gate_mask: gates / gate_s / closed must not be NULL");
+    if (!cost_tbl || !flag_tbl || !best_idx || !best_cost) return fail(FP_EINVAL, "fp_gate_mask: cost_tbl/flag_tbl/best_idx/best_cost must not be NULL");
+    if (gates->gate_stride < 1 || gates->gate_stride > FP_MAX_GATES) return fail(FP_EINVAL, "fp_gate_mask: gate_stride=%d outside 1..FP_MAX_GATES", gates->gate_stride);
+    if (gates->T_gate < 1) return fail(FP_EINVAL, "fp_gate_mask: T_gate=%d must be >= 1", gates->T_gate);
+    if (!finite_nonneg(gates->front)) return fail(FP_EINVAL, "fp_gate_mask: front must be finite and >= 0");
+    if (!finite_nonneg(gates->max_decel)) return fail(FP_EINVAL, "fp_gate_mask: max_decel must be finite and >= 0 (0 = off)");
+    if (batch->B == 0) return FP_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    fp::GateArgs a;
+    table_pass_args(&a, params, batch, cost_tbl, flag_tbl, best_idx, best_cost, n_gated);
+    a.front = gates->front; a.max_decel = gates->max_decel;
+    a.gate_stride = gates->gate_stride; a.T_gate = gates->T_gate;
+    a.t_now = batch->t_now; a.gate_s = gates->gate_s; a.closed = gates->closed;
+    a.points_cap = big_points(*params) ? params->points_max : FP_FAST_POINTS;
+    if (mem == FP_MEM_DEVICE) {
+        LAUNCH_TRY(fp::launch_gate_mask(a, (hipStream_t)stream), "gate kernel");
+        ++ctx->gate_launches;
+        return FP_OK;
+    }
+    FP_TRY(check_frames_host(batch));
+    const int pts = host_points_max(params, batch, nullptr, 0, 0);  // (host calls look at their time samples themselves)
+    a.points_cap = pts > FP_FAST_POINTS ? pts : FP_FAST_POINTS;
+    const size_t F = (size_t)batch->F;
+    HostStage hs(ctx);
+    StageList sl;
+    table_pass_stage(sl, &a, batch->F, [&](StageList& l) {
+        l.in(a.t_now, (size_t)a.B, &a.t_now);
+        l.in(a.gate_s, F * a.gate_stride, &a.gate_s);
+        l.in(a.closed, F * a.T_gate, &a.closed);
+    });
+    FP_TRY(hs.commit(sl));
+    LAUNCH_TRY(fp::launch_gate_mask(a, ctx->stream), "gate kernel");
+    ++ctx->gate_launches;
     return hs.fetch_out();
 }
 

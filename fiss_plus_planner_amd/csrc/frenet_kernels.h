@@ -213,7 +213,7 @@ struct RankArgs {
     int32_t* n_feasible = nullptr;
 };
 hipError_t launch_rank_feasible(const RankArgs& a, hipStream_t stream);
-// What the table passes behind the dense pass share (frenet_boundary.hip, frenet_envelope.hip): one workgroup per ego, in the order of
+// What the table passes behind the dense pass share (frenet_boundary.hip, frenet_envelope.hip, frenet_gates.hip): one workgroup per ego, in the order of
 // perm (optional), over the ego's rows of cost_tbl / flag_tbl [B][C]; each rewrites bits of the flag words and writes the ego's argmin
 // over what is still feasible, and - optionally - how many candidates it flagged (count [B]).  Device addresses.
 struct TablePassArgs {
@@ -250,6 +250,17 @@ struct EnvelopeArgs : TablePassArgs {
     const double* v_limit = nullptr;
 };
 hipError_t launch_speed_envelope(const EnvelopeArgs& a, hipStream_t stream);
+// Stop lines that open and close (frenet_gates.hip, fp_gate_mask): ORs FP_FLAG_SPEED into the flag word of a candidate that crosses a
+// closed gate.  gate_s is [F][gate_stride] (NaN = unused slot), closed [F][T_gate] (bit g = gate g closed at that absolute step), t_now
+// [B] the egos' clocks; points_cap = the points a trajectory of the call can have (the closed words staged per ego); count = n_gated.
+struct GateArgs : TablePassArgs {
+    double front = 0.0, max_decel = 0.0;
+    int gate_stride = 0, T_gate = 0, points_cap = 0;
+    const int32_t* t_now = nullptr;
+    const double* gate_s = nullptr;
+    const uint32_t* closed = nullptr;
+};
+hipError_t launch_gate_mask(const GateArgs& a, hipStream_t stream);
 // The obstacle margin of K chosen plans per ego (frenet_margins.hip, fp_traj_margins): one workgroup per ego, in the order of perm
 // (optional).  ka.p.check_stride is the call's pose_stride; ka.r is not read.  Device addresses; exactly one of best_idx [K][B] /
 // end_state [K][B][3] set; the outputs are [K][B].

@@ -3,8 +3,10 @@
 PyTorch is plumbing here (device allocations + the stream handle); every array crosses the C ABI as a raw
 device address.  `DeviceBatch` uploads a ProblemBatch once; `ClosedLoopRunner` enqueues
 [plan -> advance] x cycles on one stream (reference loop: planners/benchmark/planning.py:120-162) and only
-reads back at the end (or per cycle, when a trace is requested).  With record=True the driven trajectory of every ego - what the
-reference's loop returns as state_list - is written on the device by fp_loop_record behind every step and read back once.
+reads back at the end (or per cycle, when a trace is requested).  With rules=(...) the cycle is [plan -> rule passes -> advance]: the
+speed envelope, the gates and the road-boundary check run over the dense call's tables and decide which candidate the ego follows.
+With record=True the driven trajectory of every ego - what the reference's loop returns as state_list - is written on the device by
+fp_loop_record behind every step and read back once.
 """
 from __future__ import annotations
 
@@ -19,6 +21,8 @@ from .engine import FrenetEngine, device_batch, launch_order_hint, make_params
 
 _NAMES = ("d_samples", "t_samples", "v_samples", "target_speed", "ego", "frame_of", "scene_of", "t_now", "nx", "knots", "coef",
           "obs_pose", "obs_dims", "final_time_step")
+
+RULES = ("envelope", "gates", "boundary")  # the rule passes of ClosedLoopRunner(rules=...), in the order they run
 
 LOG_POLL_CYCLES = 16  # run(record=True) reads the log's 4-byte count of running egos this often and stops enqueueing at 0
 
@@ -37,6 +41,9 @@ class DeviceBatch:
                   "track_model", "track_state", "track_frame"):  # (the obstacle tracks: predict)
             if getattr(batch, k, None) is not None:
                 self.t[k] = torch.from_numpy(getattr(batch, k)).to(self.dev)
+        if getattr(batch, "gate_s", None) is not None:  # (the gates: gate_mask_device; the uint32 words travel as their int32 bit patterns)
+            self.t["gate_s"] = torch.from_numpy(batch.gate_s).to(self.dev)
+            self.t["gate_closed"] = torch.from_numpy(batch.gate_closed.view(np.int32)).to(self.dev)
         if order_hint and batch.B > 0:
             self.t["launch_order"] = torch.from_numpy(launch_order_hint(batch)).to(self.dev)
         self.params = make_params(batch)
@@ -73,11 +80,17 @@ class ClosedLoopRunner:
     """[plan -> advance] for a whole batch on the device.  planner: "FOP" (fp_plan_dense) or "FISS"/"FISS+" (fp_plan_fiss)."""
 
     def __init__(self, engine: FrenetEngine, dbatch: DeviceBatch, goal_xy: np.ndarray, planner: str = "FOP", fused: bool = True,
-                 goal_poly: np.ndarray | None = None, goal_nv: np.ndarray | None = None, goal_intervals: np.ndarray | None = None):
-        """fused: an FOP cycle is ONE launch (fp_plan_step: the workgroup that finds an ego's argmin advances the ego); False = the two
+                 goal_poly: np.ndarray | None = None, goal_nv: np.ndarray | None = None, goal_intervals: np.ndarray | None = None,
+                 rules=()):
+        """rules: any subset of ("envelope", "gates", "boundary") - FOP only, and the batch must carry each rule's data (speed profile /
+        gates / corridor).  The cycle then is fp_plan_dense into the runner's own [B][C] tables, the passes asked for in that order
+        (fp_speed_envelope, fp_gate_mask, fp_boundary_mask), each writing best_idx / best_cost, and fp_advance on the last one's winner;
+        `fused` has no say.  rules=(): the calls below, unchanged.
+        fused: an FOP cycle is ONE launch (fp_plan_step: the workgroup that finds an ego's argmin advances the ego); False = the two
         calls fp_plan_dense + fp_advance (same results; the A/B of tests and bench).
         goal_poly [B, V, 2] + goal_nv [B] (+ goal_intervals [B, 6] = time_step / velocity / orientation lo, hi; NaN = undefined): the
         goal region of goal_region.is_reached() (planning.py:150-153), see fp_loop_io in include/frenet_gpu.h."""
+        self.rules = self._check_rules(rules, planner, dbatch.host)  # (first: the argument errors need no device)
         torch = dbatch.torch
         self.eng, self.db, self.planner, self.fused = engine, dbatch, planner, fused
         B = dbatch.B
@@ -105,6 +118,12 @@ class ClosedLoopRunner:
             if goal_intervals is not None:
                 self.goal_iv = torch.from_numpy(np.ascontiguousarray(goal_intervals, dtype=np.float64).reshape(B, 6)).to(dbatch.dev)
                 self.io.goal_intervals = self.goal_iv.data_ptr()
+        if self.rules:  # the tables the passes mask, and how many candidates each pass flagged in the last cycle
+            self.cost_tbl = dbatch.empty((B, dbatch.C), f64)
+            self.flag_tbl = torch.zeros((B, dbatch.C), dtype=i32, device=dbatch.dev)
+            self.n_flagged = {r: torch.zeros(B, dtype=i32, device=dbatch.dev) for r in self.rules}
+            if "envelope" in self.rules and "speed_limit" not in dbatch.t:  # (a lateral bound alone: no limit anywhere)
+                dbatch.t["speed_limit"] = torch.full((dbatch.host.F, dbatch.host.NX), float("inf"), dtype=f64, device=dbatch.dev)
         if planner != "FOP":
             self.prev = torch.full((B, 3), -1, dtype=i32, device=dbatch.dev)
             self.ijk = dbatch.empty((B, 3), i32)
@@ -117,10 +136,47 @@ class ClosedLoopRunner:
             f.refined, f.stats, f.trace, f.best_flags, f.best_traj = self.refined.data_ptr(), self.stats.data_ptr(), None, None, None
             self.fio = f
 
+    @staticmethod
+    def _check_rules(rules, planner, batch) -> tuple:
+        """The rules in the order they run; ValueError for an unknown rule, a planner that is not FOP, or a rule without its data."""
+        rules = (rules,) if isinstance(rules, str) else tuple(rules)
+        for r in rules:
+            if r not in RULES:
+                raise ValueError(f"ClosedLoopRunner: unknown rule {r!r} (rules are a subset of {RULES})")
+        if rules and planner != "FOP":
+            raise ValueError(f"ClosedLoopRunner: rules are defined for the FOP planner only ({planner} orders candidates by cost before validation)")
+        has = dict(envelope=getattr(batch, "speed_limit", None) is not None or float(getattr(batch, "max_lat_accel", 0.0) or 0.0) > 0.0,
+                   gates=getattr(batch, "gate_s", None) is not None, boundary=getattr(batch, "bound_left", None) is not None)
+        for r in rules:
+            if not has[r]:
+                raise ValueError(f"ClosedLoopRunner: rule {r!r} needs data the batch does not carry "
+                                 "(envelope: speed_limit / max_lat_accel, gates: gate_s / gate_closed, boundary: bound_left / bound_right)")
+        return tuple(r for r in RULES if r in rules)
+
+    def _step_rules(self, stream: int):
+        """fp_plan_dense -> the rule passes -> fp_advance: a linear chain on `stream`."""
+        import ctypes as C
+
+        db, h, eng = self.db, self.db.host, self.eng
+        bi, bc, cost, flags = self.best_idx.data_ptr(), self.best_cost.data_ptr(), self.cost_tbl.data_ptr(), self.flag_tbl.data_ptr()
+        eng.plan_dense_device(db.params, self.fb, bi, bc, self.stats.data_ptr(), cost_tbl=cost, flag_tbl=flags, stream=stream)
+        for r in self.rules:
+            n = self.n_flagged[r].data_ptr()
+            if r == "envelope":
+                eng.speed_envelope_device(db.params, self.fb, db.t["speed_limit"].data_ptr(), h.limit_front, h.limit_tol, h.max_lat_accel, cost, flags, bi, bc, n, stream)
+            elif r == "gates":
+                eng.gate_mask_device(db.params, self.fb, db.t["gate_s"].data_ptr(), db.t["gate_closed"].data_ptr(), h.gate_s.shape[1], h.gate_closed.shape[1],
+                                     h.gate_front, h.gate_max_decel, cost, flags, bi, bc, n, stream)
+            else:
+                eng.boundary_mask_device(db.params, self.fb, db.t["bound_left"].data_ptr(), db.t["bound_right"].data_ptr(), h.bound_margin, cost, flags, bi, bc, n, stream)
+        _abi.check(eng._lib.fp_advance(eng._ctx, C.byref(db.params), C.byref(self.fb), bi, None, C.byref(self.io), _abi.FP_MEM_DEVICE, stream or None))
+
     def step(self, stream: int = 0):
         """One plan cycle for every running ego + the state hand-over, enqueued on `stream`."""
         import ctypes as C
 
+        if self.rules:
+            return self._step_rules(stream)
         lib, ctx = self.eng._lib, self.eng._ctx
         if self.planner == "FOP" and self.fused:
             self.eng.plan_step_device(self.db.params, self.fb, self.io, self.best_idx.data_ptr(), self.best_cost.data_ptr(), self.stats.data_ptr(), stream=stream)

@@ -211,7 +211,7 @@ class FrenetEngine:
 
     def plan_dense(self, batch: ProblemBatch, tables: bool = True, winner: bool = False, traj_stride: int = TRAJ_STRIDE, traj_sparse: bool = False,
                    out: SimpleNamespace | None = None, audit: bool = False, top_k: int = 0, boundary: bool = False, margins: bool = False,
-                   envelope: bool = False):
+                   envelope: bool = False, gates: bool = False):
         """FrenetOptimalPlanner.plan() for every ego of the batch (reference frenet_optimal_planner.py:247-270).
 
         Returns best_idx [B] (flat (i_d*nt+i_T)*nv+i_v, -1 = none), best_cost [B], stats [B,4] and, with
@@ -230,23 +230,27 @@ class FrenetEngine:
         speed_limit and / or max_lat_accel): the position-dependent speed limits (speed_envelope) run behind the dense call over its
         tables, before the boundary check when both are asked for; best_idx / best_cost are the argmin among the candidates that obey the
         envelope (and the corridor), `flags` carry the added FLAG_SPEED / FLAG_ACCEL bits, also n_limited [B]; top_k, margins and
-        winner=True follow the masked result like with boundary=True.
+        winner=True follow the masked result like with boundary=True.  gates=True (the batch must carry gates: gate_s / gate_closed): the
+        stop lines that open and close (gate_mask) run behind the envelope and before the boundary check; `flags` carry the added
+        FLAG_SPEED bits of the candidates that cross a closed gate, also n_gated [B]; everything else follows the masked result likewise.
         """
         if margins:
-            out = self.plan_dense(batch, tables, winner, traj_stride, traj_sparse, out, audit, top_k, boundary, envelope=envelope)
+            out = self.plan_dense(batch, tables, winner, traj_stride, traj_sparse, out, audit, top_k, boundary, envelope=envelope, gates=gates)
             plans = out.rank_idx if top_k else out.best_idx
             if batch.B:
                 out.margin_dist, out.margin_step, out.margin_obs = self.traj_margins(batch, best_idx=plans)
             else:
                 out.margin_dist, out.margin_step, out.margin_obs = np.empty(plans.shape), np.empty(plans.shape, dtype=np.int32), np.empty(plans.shape, dtype=np.int32)
             return out
-        if boundary or envelope:
+        if boundary or envelope or gates:
             if boundary and getattr(batch, "bound_left", None) is None:
                 raise ValueError("plan_dense(boundary=True): the batch carries no corridor (ProblemBatch.bound_left / bound_right)")
             if envelope and not _has_speed_profile(batch):
                 raise ValueError("plan_dense(envelope=True): the batch carries no speed profile (ProblemBatch.speed_limit / max_lat_accel)")
+            if gates and getattr(batch, "gate_s", None) is None:
+                raise ValueError("plan_dense(gates=True): the batch carries no gates (ProblemBatch.gate_s / gate_closed)")
             if audit:
-                raise ValueError("plan_dense(boundary / envelope=True, audit=True): the audit bits describe the dense call's own answer, not the masked one")
+                raise ValueError("plan_dense(boundary / envelope / gates=True, audit=True): the audit bits describe the dense call's own answer, not the masked one")
             want_tables = tables
             if out is not None and not tables:  # the caller's arrays hold no tables: the call brings its own
                 out.cost, out.flags = np.empty((batch.B, batch.C)), np.empty((batch.B, batch.C), dtype=np.uint32)
@@ -255,6 +259,8 @@ class FrenetEngine:
             if batch.B:
                 if envelope:  # (first: the boundary check's argmin then honours its bits)
                     _, bi, bc, out.n_limited = self.speed_envelope(batch, out.cost, out.flags, inplace=True)
+                if gates:  # (behind the envelope, ahead of the boundary check: every argmin honours the bits set before it)
+                    _, bi, bc, out.n_gated = self.gate_mask(batch, out.cost, out.flags, inplace=True)
                 if boundary:
                     _, bi, bc, out.n_masked = self.boundary_mask(batch, out.cost, out.flags, inplace=True)
                 out.best_idx[...], out.best_cost[...] = bi, bc
@@ -264,6 +270,8 @@ class FrenetEngine:
             else:
                 if envelope:
                     out.n_limited = np.empty(0, dtype=np.int32)
+                if gates:
+                    out.n_gated = np.empty(0, dtype=np.int32)
                 if boundary:
                     out.n_masked = np.empty(0, dtype=np.int32)
             if top_k:
@@ -415,6 +423,43 @@ class FrenetEngine:
         prof = _abi.FpSpeedProfile(v_limit or None, float(front), float(tol), float(max_lat_accel))
         _abi.check(self._lib.fp_speed_envelope(self._ctx, C.byref(params), C.byref(fb), C.byref(prof), cost_tbl or None, flag_tbl or None, best_idx or None,
                                                best_cost or None, n_limited or None, _abi.FP_MEM_DEVICE, stream or None))
+
+    def gate_mask(self, batch: ProblemBatch, cost: np.ndarray, flags: np.ndarray, skip: np.ndarray | None = None, inplace: bool = False):
+        """Stop lines that open and close over plan_dense's tables (fp_gate_mask; the definition: include/frenet_gpu.h): cost [B,C],
+        flags [B,C] and the batch's gates (gate_s [F,G], gate_closed [F,T_gate] uint32, gate_front, gate_max_decel) -> (flags, best_idx,
+        best_cost, n_gated): the flag words with FLAG_SPEED ORed in where the candidate's front bumper moves over the line of a gate that
+        is closed at that step (a copy, unless inplace=True and `flags` is a contiguous uint32 array; no bit is ever cleared), the argmin
+        among the candidates without a FLAG_INFEASIBLE bit, and the number of candidates per ego that violate in this call.  The step is
+        batch.t_now[b] + the point's index.  skip [B] (optional): egos whose rows are neither read nor written (-1 / NaN / 0)."""
+        if getattr(batch, "gate_s", None) is None:
+            raise ValueError("gate_mask: the batch carries no gates (ProblemBatch.gate_s / gate_closed)")
+        B, Cn = batch.B, batch.C
+        cost = np.ascontiguousarray(cost, dtype=np.float64)
+        if not (inplace and isinstance(flags, np.ndarray) and flags.dtype == np.uint32 and flags.flags.c_contiguous and flags.flags.writeable):
+            flags = np.array(flags, dtype=np.uint32, order="C", copy=True)
+        if cost.shape != (B, Cn) or flags.shape != (B, Cn):
+            raise ValueError(f"gate_mask: cost / flags must be [B={B}, C={Cn}] tables, got {cost.shape} / {flags.shape}")
+        best_idx = np.empty(B, dtype=np.int32); best_cost = np.empty(B); n_gated = np.empty(B, dtype=np.int32)
+        p, fb = host_structs(batch)
+        if skip is not None:
+            skip = np.ascontiguousarray(skip, dtype=np.int32)
+            assert skip.shape == (B,)
+            fb.skip = _ptr(skip)
+        g = _abi.FpGates(_ptr(batch.gate_s), _ptr(batch.gate_closed), int(batch.gate_s.shape[1]), int(batch.gate_closed.shape[1]), float(batch.gate_front),
+                         float(batch.gate_max_decel))
+        _abi.check(self._lib.fp_gate_mask(self._ctx, C.byref(p), C.byref(fb), C.byref(g), _ptr(cost), _ptr(flags), _ptr(best_idx), _ptr(best_cost),
+                                          _ptr(n_gated), _abi.FP_MEM_HOST, None))
+        return flags, best_idx, best_cost, n_gated
+
+    def gate_mask_device(self, params: _abi.FpParams, fb: _abi.FpBatch, gate_s: int, closed: int, gate_stride: int, T_gate: int, front: float,
+                         max_decel: float, cost_tbl: int, flag_tbl: int, best_idx: int, best_cost: int, n_gated: int = 0, stream: int = 0):
+        """Enqueue the gates behind a dense call (device addresses): gate_s [F][gate_stride], closed [F][T_gate], the dense call's cost_tbl
+        / flag_tbl [B][C] (flag_tbl in/out), best_idx / best_cost [B] out, n_gated [B] or 0.  t_now, ego and the gate arrays are read when
+        the kernel runs.  best_idx is a valid argument of winner_trajs_device / fp_advance as it stands, the tables of
+        speed_envelope_device / boundary_mask_device / rank_feasible_device."""
+        g = _abi.FpGates(gate_s or None, closed or None, int(gate_stride), int(T_gate), float(front), float(max_decel))
+        _abi.check(self._lib.fp_gate_mask(self._ctx, C.byref(params), C.byref(fb), C.byref(g), cost_tbl or None, flag_tbl or None, best_idx or None,
+                                          best_cost or None, n_gated or None, _abi.FP_MEM_DEVICE, stream or None))
 
     def traj_margins(self, batch: ProblemBatch, best_idx: np.ndarray | None = None, end_state: np.ndarray | None = None, pose_stride: int | None = None,
                      skip: np.ndarray | None = None):

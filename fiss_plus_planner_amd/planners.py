@@ -22,7 +22,7 @@ from .batch import FISS_KINDS, ProblemBatch
 from .engine import TRAJ_STRIDE, FrenetEngine, host_structs, unpack_flags
 from .frenet import FrenetState, FrenetTrajectory
 from .obstacles import ObstacleTable, ObstacleTracks, flatten_obstacles, obstacles_fingerprint
-from .spline import CubicSpline2D
+from .spline import CubicSpline2D, gate_bits
 from .vehicle import Vehicle
 
 
@@ -212,6 +212,31 @@ class FrenetOptimalPlanner:
             raise ValueError("set_speed_profile: v_limit needs one value per centre-line point, none of them NaN or negative")
         self._speed_profile = (v_limit, front, float(tol), float(max_lat_accel))
 
+    def set_gates(self, gate_s, closed, front: float | None = None, max_decel: float = 0.0):
+        """Stop lines that open and close for plan(): gate_s = the arclengths of up to FP_MAX_GATES lines on the centre line handed to
+        generate_frenet_frame() (NaN = unused slot), closed = [T, G] truth values (gate g is closed at absolute time step t; the last row
+        holds from then on) or [T] uint32 words already packed (spline.gate_bits).  The step is plan()'s time_step_now + the point's index.
+        A candidate whose front bumper (s + front; None: vehicle.l / 2) moves over a line at a closed step is rejected; max_decel > 0
+        waives a gate the ego can no longer stop in front of at that deceleration (fp_gate_mask, include/frenet_gpu.h).
+        gate_s = None removes the gates again.  FOP+, FISS and FISS+ order candidates by cost before validation and raise ValueError."""
+        if self.KIND != "FOP":
+            raise ValueError(f"set_gates: gates are defined for FrenetOptimalPlanner only ({self.KIND} orders candidates by cost before validation)")
+        front = 0.5 * float(self.vehicle.l) if front is None else float(front)
+        for name, v in (("front", front), ("max_decel", max_decel)):
+            if not (np.isfinite(v) and v >= 0):
+                raise ValueError(f"set_gates: {name} = {v} must be finite and >= 0")
+        if gate_s is None:
+            self._gates = None
+            return
+        gate_s = np.array(gate_s, dtype=np.float64).ravel()
+        if not 1 <= len(gate_s) <= _abi.FP_MAX_GATES:
+            raise ValueError(f"set_gates: {len(gate_s)} gates, need 1 .. FP_MAX_GATES ({_abi.FP_MAX_GATES})")
+        closed = np.asarray(closed)
+        words = gate_bits(closed) if closed.ndim == 2 else np.array(closed, dtype=np.uint32)
+        if words.ndim != 1 or len(words) < 1 or (closed.ndim == 2 and closed.shape[1] != len(gate_s)):
+            raise ValueError(f"set_gates: closed must be [T, {len(gate_s)}] truth values or [T] words with T >= 1, got {closed.shape}")
+        self._gates = (gate_s, words, front, float(max_decel))
+
     # ------------------------------------------------------------------ problem marshalling
     def _predicted_table(self, tracks: ObstacleTracks, time_step_now: int) -> ObstacleTable:
         """The pose table of an ObstacleTracks against this planner's own frame: the track states are valid at time_step_now and
@@ -276,9 +301,10 @@ class FrenetOptimalPlanner:
         prof = getattr(self, "_speed_profile", None)
         if prof is not None and prof[0] is not None and len(prof[0]) != len(sp.knots):
             raise ValueError(f"set_speed_profile: {len(prof[0])} limits for a centre line of {len(sp.knots)} points")
+        gates = getattr(self, "_gates", None)
         cache_tables = getattr(self, "cache_tables", True)
         key = (id(sp), id(tab), getattr(tab, "version", 0), cache_tables, st.num_width, st.num_speed, st.num_t, st.min_t, st.max_t, st.tick_t, st.max_road_width, st.lowest_speed,
-               self.vehicle.l, self.vehicle.w, self.vehicle.max_speed, self.vehicle.max_accel, curv, w_obs, id(bound), id(prof))
+               self.vehicle.l, self.vehicle.w, self.vehicle.max_speed, self.vehicle.max_accel, curv, w_obs, id(bound), id(prof), id(gates))
         cache = getattr(self, "_batch_cache", None)
         if cache is None or cache[0] != key:
             sw = self._sampling_width()
@@ -300,7 +326,9 @@ class FrenetOptimalPlanner:
                 bound_left=None if bound is None else bound[0][None], bound_right=None if bound is None else bound[1][None],
                 bound_margin=0.0 if bound is None else bound[2],
                 speed_limit=None if prof is None or prof[0] is None else prof[0][None], limit_front=0.0 if prof is None else prof[1],
-                limit_tol=0.0 if prof is None else prof[2], max_lat_accel=0.0 if prof is None else prof[3])
+                limit_tol=0.0 if prof is None else prof[2], max_lat_accel=0.0 if prof is None else prof[3],
+                gate_s=None if gates is None else gates[0][None], gate_closed=None if gates is None else gates[1][None],
+                gate_front=0.0 if gates is None else gates[2], gate_max_decel=0.0 if gates is None else gates[3])
             # fp_batch.tables_tag: the library keeps this batch's spline and obstacle tables on the device until the planner builds
             # a new batch (another centerline / another obstacle list / ObstacleTable.update()) - per cycle only the start state
             # travels.  Contract (class docstring): the cached arrays are frozen, so an in-place edit raises instead of going stale;
@@ -312,7 +340,7 @@ class FrenetOptimalPlanner:
                 sp.knots.setflags(write=False)
                 sp.coef.setflags(write=False)
             host_structs(batch, freeze=True)  # (this batch is the planner's own: its arrays are only ever updated in place)
-            cache = [key, batch, None, sp, tab, bound, prof]  # sp / tab / bound / prof kept alive so their ids cannot be recycled
+            cache = [key, batch, None, sp, tab, bound, prof, gates]  # sp / tab / bound / prof / gates kept alive so their ids cannot be recycled
             self._batch_cache = cache
         batch = cache[1]
         if cache[2] != st.highest_speed:
@@ -360,9 +388,9 @@ class FrenetOptimalPlanner:
         reuse = outs.get(key)
         if reuse is None:
             reuse = outs[key] = self._engine.dense_outputs(1, batch.C, True, winner, stride)
-        # (a corridor / a speed profile on the batch: the checks run behind the dense call and decide the winner)
+        # (a corridor / a speed profile / gates on the batch: the checks run behind the dense call and decide the winner)
         out = self._engine.plan_dense(batch, tables=True, winner=winner, traj_stride=stride, out=reuse, boundary=batch.bound_left is not None,
-                                      envelope=batch.speed_limit is not None or batch.max_lat_accel > 0)
+                                      envelope=batch.speed_limit is not None or batch.max_lat_accel > 0, gates=batch.gate_s is not None)
         self.last_tables = (out.cost[0].copy(), out.flags[0].copy())
         if self.materialize_all:  # visualisation payload (reference :102): every candidate's series in one launch
             m = self._engine.materialize_all(batch, traj_stride=stride)

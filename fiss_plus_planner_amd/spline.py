@@ -186,3 +186,14 @@ def limits_from_path_column(values) -> np.ndarray:
     if np.isnan(v).any() or (v < 0).any():
         raise ValueError("limits_from_path_column: the column holds a NaN or a negative value")
     return np.where(v == 1.0, np.inf, v)
+
+
+def gate_bits(closed) -> np.ndarray:
+    """The `closed` words of fp_gates (ProblemBatch.gate_closed, FrenetOptimalPlanner.set_gates) from one truth value per frame, absolute
+    time step and gate: closed [F, T, G] (or [T, G] for one frame) -> uint32 [F, T] (or [T]), bit g of a word set = gate g is closed
+    at that step.  G is at most 32 (FP_MAX_GATES)."""
+    c = np.asarray(closed)
+    if c.ndim not in (2, 3) or c.shape[-1] < 1 or c.shape[-1] > 32:
+        raise ValueError(f"gate_bits: closed must be [F, T, G] or [T, G] with 1 <= G <= 32, got {c.shape}")
+    bits = (c != 0).astype(np.uint64) << np.arange(c.shape[-1], dtype=np.uint64)
+    return np.ascontiguousarray(bits.sum(axis=-1).astype(np.uint32))

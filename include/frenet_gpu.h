@@ -66,6 +66,7 @@ extern "C" {
                                    planner classes then do by themselves */
 #define FP_MAX_POLY_VERTS 128 /* vertices of one convex-polygon obstacle column (shapely's buffer() circle has 64) */
 #define FP_MAX_RANK 64      /* K of fp_rank_feasible */
+#define FP_MAX_GATES 32     /* gates per frame of fp_gate_mask (one bit each of a `closed` word) */
 
 /* candidate flag word: low bits = why a candidate is infeasible, then N and M */
 #define FP_FLAG_SPEED 1u      /* any(s_d > max_speed)       frenet_optimal_planner.py:152 */
@@ -314,7 +315,7 @@ int fp_ctx_destroy(fp_ctx* ctx);
 int fp_ctx_set_option(fp_ctx* ctx, const char* name, int value);
 /* Reads an option back, or one of the read-only counters "clearance_launches" (launches of the clearance rescoring kernel,
  * fp_params.w_obstacle > 0, of this ctx so far), "looplog_launches" (launches of fp_loop_record's kernel), "rank_launches" (launches of
- * fp_rank_feasible's kernel), "boundary_launches" (launches of fp_boundary_mask's kernel), "envelope_launches" (launches of fp_speed_envelope's kernel), "margin_launches" (launches of fp_traj_margins' kernel), "predict_launches" (launches of
+ * fp_rank_feasible's kernel), "boundary_launches" (launches of fp_boundary_mask's kernel), "envelope_launches" (launches of fp_speed_envelope's kernel), "gate_launches" (launches of fp_gate_mask's kernel), "margin_launches" (launches of fp_traj_margins' kernel), "predict_launches" (launches of
  * fp_obstacles_predict's kernel), "from_state_launches" (launches of fp_from_state's kernel), "lattice_launches" (dense lattice launches of this ctx so far) and
  * "lattice_ordered_launches" (those dispatched in a feedback order or in the order of fp_batch.launch_order) - bench.py reports when an
  * order took effect -, "lattice_launches_2" / "_3" / "_4" (PROCESS-wide: fused lattice launches so far by workgroups per compute unit). */
@@ -478,7 +479,8 @@ int fp_boundary_mask(fp_ctx* ctx, const fp_params* params, const fp_batch* batch
  *   - fp_plan_step and the FISS entry points take no profile.  A closed loop that wants the envelope enqueues fp_plan_dense ->
  *     fp_speed_envelope -> fp_advance.
  *   - fp_shard_call has no slot for it.
- *   - there is no time-dependent limit (a light that turns green): the profile is a function of s alone. */
+ * The profile is a function of s alone; a stop line that opens and closes with time (a light that turns green) is a gate: fp_gate_mask
+ * below. */
 typedef struct {
     const double* v_limit;  /* [F][NX] speed limit (m/s) of the SEGMENT that starts at knot k: it holds on knots[k] <= s < knots[k+1].
                                +inf = no limit there.  Entries k >= nx[f] - 1 are ignored. */
@@ -490,6 +492,71 @@ typedef struct {
 int fp_speed_envelope(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, const fp_speed_profile* profile,
                       const double* cost_tbl, uint32_t* flag_tbl, int32_t* best_idx, double* best_cost, int32_t* n_limited,
                       int mem, void* stream);
+
+/* ---- stop lines that open and close: gates (added WITHIN ABI 18: detect it by looking the symbol up, e.g. dlsym) ------------------
+ * fp_speed_envelope models a red light as a stretch of zero speed limit, a function of s alone: the light never turns green, and an ego
+ * that obeys it in a closed loop waits for ever.  The reference's data says what kind of line it is - "0 is red light, 1 is crosswalk"
+ * (planners/waymo_interface/waymo_interface.py:160-189) - and not when it holds.  A GATE is a stop line at an arclength of a reference
+ * line with a state per absolute time step: a traffic light with phases, a crossing while a pedestrian is predicted on it, a barrier.
+ * The time index is the obstacle table's own clock, t_now[b] + i.  fp_gate_mask runs behind fp_plan_dense and over its tables: cost_tbl /
+ * flag_tbl are [B][C] (C = nd*nv*nt) as fp_plan_dense wrote them.
+ *
+ * Definition, for every candidate c of every ego b that is not skipped, N and M taken from the candidate's flag word, f = frame_of[b]:
+ *   points           q_0 = ego[b][0] + front, computed exactly so (not from the series);  q_i = s_i + front for i = 1 .. M-1, s_i = the
+ *                    candidate's longitudinal series value (row FP_ARR_S) at t = i * tick_t.  M <= 1: nothing is checked, no bit is set.
+ *   crossing         the candidate crosses gate g at point i (1 <= i <= M-1) when  q_{i-1} <= gate_s[f][g]  &&  gate_s[f][g] < q_i.
+ *                    A NaN slot compares false.  An ego whose bumper is already past the line (q_0 > gate_s) never crosses it: it is in
+ *                    the junction and must clear it.
+ *   gate state       read at the arrival step:  w = closed[f][clamp(t_now[b] + i, 0, T_gate - 1)]  (before step 0 the first, at or
+ *                    after T_gate the last known state holds).
+ *   waiver           only when max_decel > 0.  Gate g is waived for ego b when, with v0 = ego[b][1]:  v0 > 0,  q_0 <= gate_s[f][g]  and
+ *                    q_0 + v0 * v0 / (2 * max_decel) > gate_s[f][g]:  the ego cannot stop in front of the line any more (the dilemma
+ *                    zone: without the rule such an ego would be left without a plan).
+ *   violation        a crossing at i of a gate that is not waived and whose bit g is set in w.
+ *   the bit          a violating candidate gets FP_FLAG_SPEED ORed into its flag word - the bit fp_speed_envelope gives a candidate
+ *                    that runs its static red light; the low byte of the flag word is full.  The call NEVER CLEARS a bit and changes
+ *                    no other bit, so it is idempotent; cost_tbl is never written.  Candidates that are already infeasible are
+ *                    evaluated too.
+ *   best_idx / best_cost  [B] the argmin of cost_tbl over the candidates with no FP_FLAG_INFEASIBLE bit and a cost that is not NaN; the
+ *                    last minimum in FOP order wins exact ties (:263-268); -1 / NaN when there is none.  Bit for bit plane 0 of an
+ *                    fp_rank_feasible call on the masked tables, and a valid argument of fp_advance, fp_winner_trajs, fp_traj_margins;
+ *                    the masked tables are valid arguments of fp_boundary_mask and fp_speed_envelope.
+ *   n_gated          NULL or [B]: the candidates of the ego that violate in THIS call, whatever bits they carried before.
+ *   Stats            do not change (FOP counts every candidate regardless).
+ *   skipped egos     batch->skip[b] != 0: -1 / NaN / 0, the ego's rows are neither read nor written.
+ * s_i and M depend on the candidate's longitudinal profile (i_v, i_T) alone, so the nd candidates of a profile share one verdict; the
+ * kernel evaluates nv*nt profiles per ego.  Its series arithmetic (fma Horner) rounds differently from a point-by-point restatement: a
+ * point with q_i within ~FP_AUDIT_GAP_TOL of a line may be decided either way by another rounding of the same numbers (q_0 and the
+ * waiver's left side are computed as written above on every side).
+ *
+ * FP_MEM_DEVICE: one kernel is enqueued (one workgroup per ego, in the order of batch->launch_order when there is one) - no
+ * allocation, no wait; it can be captured directly behind a dense call in a linear chain.  t_now, ego, closed and gate_s are read when
+ * the kernel runs: a replayed graph follows a loop whose t_now advances on the device (fp_advance), and a caller may rewrite the
+ * phases in place between cycles.  params->points_max announces the points per trajectory as for every FP_MEM_DEVICE call.
+ * FP_MEM_HOST stages the tables and the gates through the ctx and waits, like fp_speed_envelope.  Batch fields used: B, F, frame_of,
+ * ego, t_now, t_samples, v_samples, skip, launch_order (NX, nx, knots travel with a host call and are not read).
+ * Errors: a NULL mandatory pointer (gates, gate_s, closed, cost_tbl, flag_tbl, best_idx, best_cost), gate_stride outside
+ * 1 .. FP_MAX_GATES, T_gate < 1, front or max_decel negative or not finite: FP_EINVAL; nd*nv*nt > FP_MAX_CAND: FP_ELIMIT.  Bits of a
+ * closed word at or above gate_stride are ignored.
+ * Also read-only in fp_ctx_get_option: "gate_launches" = launches of the kernel on this ctx so far (0 for a caller that never asks: such
+ * a caller gets the bits and the launch counts it got before the symbol existed).
+ *
+ * Deliberately not done:
+ *   - fp_plan_step, the FISS entry points and fp_shard_call take no gates.  A closed loop enqueues fp_plan_dense -> fp_gate_mask ->
+ *     fp_advance (ClosedLoopRunner(rules=...) of the Python package does, eagerly or from a graph).
+ *   - the waiver looks at the ego's present speed alone; a yellow phase is the caller's: it closes the gate's bit from the step the
+ *     light turns red and sets max_decel to the braking it asks of a driver. */
+typedef struct {
+    const double*   gate_s;   /* [F][gate_stride]  arclength of the stop line on the frame; NaN = unused slot */
+    const uint32_t* closed;   /* [F][T_gate]       bit g set = gate g of the frame is closed at absolute time step t */
+    int32_t gate_stride;      /* 1 .. FP_MAX_GATES */
+    int32_t T_gate;           /* >= 1; steps before 0 read row 0, steps at or after T_gate read row T_gate-1 (the last known state holds) */
+    double  front;            /* >= 0, finite: the line is crossed by s + front (veh_l / 2 = the front bumper) */
+    double  max_decel;        /* 0 = off; > 0 finite: a gate the ego can no longer stop in front of is waived (above) */
+} fp_gates;
+
+int fp_gate_mask(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, const fp_gates* gates, const double* cost_tbl,
+                 uint32_t* flag_tbl, int32_t* best_idx, double* best_cost, int32_t* n_gated, int mem, void* stream);
 
 /* ---- the obstacle margin of chosen plans (added WITHIN ABI 18: detect it by looking the symbol up, e.g. dlsym) ------------
  * fp_rank_feasible hands a behaviour layer K alternatives per ego as an index and a cost.  How close each of them comes to anything,
