@@ -166,6 +166,20 @@ __device__ __forceinline__ int lut_segment(const double* knots, const unsigned s
     return seg;
 }
 
+// The same segment in ONE step, for lines whose knots are all further apart than a bucket is wide (the walk's `lut_crowded` == 0): the bucket
+// index is off by rounding at most at a bucket edge, so s lies within a hair of [sb, sb + width], sb the bucket's start, and that stretch
+// holds at most one knot.  lut[bkt] is the last knot at or below sb: the segment of s is that one, or the one before it (the knot sits
+// at sb and s a hair below it), or the one after it (the knot lies between sb and s) - one compare each, against knots the hint names.
+__device__ __forceinline__ int lut_segment_step(const double* knots, const unsigned short* lut, int nx, double s, double knot0,
+                                                double inv_bucket_w, int n_buckets)
+{
+    int bkt = (int)((s - knot0) * inv_bucket_w);
+    bkt = bkt < 0 ? 0 : (bkt > n_buckets ? n_buckets : bkt);
+    const int seg = lut[bkt];  // (<= nx - 2: knots[seg + 1] exists)
+    const double k_lo = knots[seg], k_hi = knots[seg + 1];
+    return seg - (int)(seg > 0 && s < k_lo) + (int)(seg < nx - 2 && s >= k_hi);
+}
+
 // nsplit > 1 (latency mode for small batches): the time-horizon slices of one ego are spread over nsplit workgroups, each
 // writes its partial argmin to part_best[ego * nsplit + part]; the last one to arrive (ticket counter) merges them.
 //
@@ -408,7 +422,11 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
     fan_t* s_fan_dd = (fan_t*)(smem + L.ddmax);
     float* s_wfat = (float*)(smem + L.wfat);
     ObsDim* s_grp = (ObsDim*)(smem + L.grp);  // reused as {cx, cy, radius, -}
-    unsigned short* s_items = (unsigned short*)(smem + L.iqueue);  // item index mul24(r, n_obs) + j
+    unsigned short* s_items = (unsigned short*)(smem + L.iqueue);  // item (row r, obstacle j), see kItemShift
+    // A survivor's item in the walk's list: the shaped instances pack it as r << kItemShift | j (kItemShift = bits of NOBS - 1), so that
+    // B and N take it apart with a shift and a mask; where the shape is a run-time value, or the packed code would not fit the list's
+    // 16 bits, it is the table index mul24(r, n_obs) + j and a division takes it apart (kItemShift = 0).
+    constexpr int kItemShift = (kWalk && kShape) ? item_shift(NOBS, ROWS) : 0;
     double* s_pows = (double*)(smem + L.pows);
     double* s_ts = (double*)(smem + L.samples);
     double* s_vs = s_ts + nt;
@@ -426,7 +444,7 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
     int* s_cnt = (int*)(smem + L.cnt);
     int* s_nslice = (int*)(smem + L.nslice);
     Best* s_best = (Best*)(smem + L.best);
-    // {first knot, bucket width reciprocal, ego half length, half width, half diagonal}: uniform FP64 values live in VECTOR registers
+    // {first knot, bucket width reciprocal, ego half length, half width, half diagonal; [5..10] ego start state, [11] d_dd0 / 2}: uniform FP64 values live in VECTOR registers
     // (the scalar unit has no FP64); kept in registers from the prologue to the last slice they cost the three-workgroup variant spills
     double* s_k = (double*)(smem + L.konst);
 
@@ -521,8 +539,8 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
     {
         const double* gk = bt.knots + (size_t)f * NX;
         const double* gc = bt.coef + (size_t)f * 8 * NX;
-        // [0], [1]: list counters; [2]: slices whose lon profiles need the point-by-point scan; [3]: ticket; [5], [6]: fp32 bit patterns
-        // of the spline's speed bound and of the largest lateral offset
+        // [0], [1]: list counters; [2]: slices whose lon profiles need the point-by-point scan; [3]: ticket; [4]: knots closer than a
+        // bucket (the segment hint needs its loops); [5], [6]: fp32 bit patterns of the spline's speed bound and of the largest lateral offset
         if (tid < 8) s_cnt[tid] = 0;
 #if defined(FP_PHASE_STAMPS)
         if (tid == 0) { s_walk_t[0] = 0xFFFFFFFFu; s_walk_t[1] = 0u; }
@@ -583,7 +601,7 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
             spline_frame(SplineLds{bt.knots + (size_t)fg * bt.NX, bt.coef + (size_t)fg * 8 * bt.NX, nx, bt.NX}, seg, dxs, px, py, tx, ty);
         }
     };
-    if (kEgoEarly && tid == 8) { s_k[5] = s0; s_k[6] = s_d0; s_k[7] = s_dd0; s_k[8] = d0; s_k[9] = d_d0; s_k[10] = d_dd0; }
+    if (kEgoEarly && tid == 8) { s_k[5] = s0; s_k[6] = s_d0; s_k[7] = s_dd0; s_k[8] = d0; s_k[9] = d_d0; s_k[10] = d_dd0; s_k[11] = d_dd0 * 0.5; }
     __syncthreads();
     FP_STAMP(0);
     // the ego's start state as the prologue's solves read it (kEgoEarly: from LDS already)
@@ -611,6 +629,7 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
         s_lut[bkt] = (unsigned short)seg;
     }
 #if defined(FP_ABL_NO_VMAX)
+    if (tid == 0) s_cnt[4] = 1;  // (the knot spacing is checked in the loop below)
     if (false) {
 #else
     if (n_obs > 0) {
@@ -620,12 +639,20 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
         // once-per-ego group test turns an arclength interval into a circle with it.  Wave maximum of fp32 bit patterns, one LDS
         // atomic per wavefront (a NaN coefficient is the largest pattern: the circle then keeps every obstacle).
         // (coefficient window: over its segments only - a row whose arclength range leaves the window gets an infinite circle below)
+        // In the same pass, s_cnt[4] != 0: some knots are no further apart than a bucket is wide (or the line is degenerate, or only its
+        // window was looked at) - a point's segment can then lie several knots from its bucket's hint, and the walk's frames take
+        // lut_segment's loops instead of lut_segment_step.  (A uniform line's knots are 2 nx / (nx - 1) buckets apart.)
         const int seg_end = windowed ? (w0 + wcap < nx - 1 ? w0 + wcap : nx - 1) : nx - 1;
+        // The 1e-6 of slack below has to cover the rounding of (s - knot0) / width and of a bucket's start, which grow with the
+        // arclengths themselves (2^-52 |knot| each), not with the bucket: a line whose |knot| 2^-50 exceeds it (arclengths of 1e9 m with
+        // metre-sized buckets) takes the loops too.
+        if (tid == 0 && (windowed || !(inv_bucket_w > 0.0) || !(fmax(fabs(s_knots[0]), fabs(s_knots[nx - 1])) * inv_bucket_w < 1e-6 * 0x1p50))) s_cnt[4] = 1;
         for (int i0 = w0 + wave * kWave; i0 < seg_end; i0 += kThreads) {
             const int i = i0 + lane;
             uint32_t bits = 0u;
             if (i < seg_end) {
                 const double h = s_knots[i + 1] - s_knots[i];
+                if (!(h * inv_bucket_w >= 1.0 + 1e-6)) atomicOr((unsigned int*)&s_cnt[4], 1u);
                 double m2 = 0.0;
 #pragma unroll
                 for (int ax = 0; ax < 2; ++ax) {
@@ -761,7 +788,7 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
         }
     }
     if (tid == 0) { s_k[0] = knot0; s_k[1] = inv_bucket_w; s_k[2] = veh_hl; s_k[3] = veh_hw; s_k[4] = r_ego; }
-    if (kEgoLds && !kEgoEarly && tid == 1) { s_k[5] = s0; s_k[6] = s_d0; s_k[7] = s_dd0; s_k[8] = d0; s_k[9] = d_d0; s_k[10] = d_dd0; }
+    if (kEgoLds && !kEgoEarly && tid == 1) { s_k[5] = s0; s_k[6] = s_d0; s_k[7] = s_dd0; s_k[8] = d0; s_k[9] = d_d0; s_k[10] = d_dd0; s_k[11] = d_dd0 * 0.5; }
     {   // power sums of every slice (they need nothing but the time samples): a few threads of the middle
         const int i = tid - kThreads / 2;
         if (i >= 0 && i < n_it) power_sums_closed(arange_len(s_ts[it_lo + i], tick), tick, s_pows + (it_lo + i) * 11);
@@ -774,6 +801,7 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
     auto eD0 = [&]() -> double { if constexpr (kEgoLds) return s_k[8]; else return d0; };
     auto eDd0 = [&]() -> double { if constexpr (kEgoLds) return s_k[9]; else return d_d0; };
     auto eDdd0 = [&]() -> double { if constexpr (kEgoLds) return s_k[10]; else return d_dd0; };
+    auto eDdd0Half = [&]() -> double { if constexpr (kEgoLds) return s_k[11]; else return d_dd0 * 0.5; };  // (the walk's N: the product, ready)
     if (n_obs > 0 && pose_limit > 0) {
         // ---- arclength range of every checked pose row over the lon profiles of ALL slices of this workgroup: lane = (row, slice),
         // loop over the end-speed samples, then LDS atomic min / max on order-preserving fp32 bit patterns (relative to the first knot).
@@ -997,7 +1025,12 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
                         if (lane == first) base = atomicAdd(&s_cnt[0], __popcll(m));
                         const int pos = __builtin_amdgcn_readlane(base, first) - item_base + __popcll(m & ((1ull << lane) - 1ull));
                         if (keep && pos < kItemCap) {
-                            s_items[pos] = (unsigned short)e;
+                            if constexpr (kItemShift > 0) {  // (taken apart again here: a survivor is rare, a register held across the ballot is not free)
+                                const int r_e = div_by<NOBS, ROWS * NOBS>(e, inv_nobs);
+                                s_items[pos] = (unsigned short)((r_e << kItemShift) | (e - mul24(r_e, n_obs)));
+                            } else {
+                                s_items[pos] = (unsigned short)e;
+                            }
                             s_spose.set(pos, ps[u].x, ps[u].y, ps[u].z, 0.0);
                         }
                     }
@@ -1047,6 +1080,24 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
                     const unsigned long long lt_mask = (1ull << lane) - 1ull;
                     const int n_prof = mul24(n_it, nv);
                     const float inv_stride = 1.0f / (float)stride;
+                    // wave-uniform, in scalar registers across the profile loop: whether the segment hint is exact to one step (s_cnt[4], see
+                    // the LUT build), and prep's fp32 ego sizes (the bits of float_above(s_k[4]), (s_k[2]), (s_k[3]))
+                    // (the builtin would not do: the compiler knows these values to be uniform, drops it and keeps them in VECTOR registers
+                    // through the whole walk - this instance has none to spare.  The compiler's hazard recogniser does not look into an asm:
+                    // of gfx950's VALU-writes-SGPR hazards (VMEM reading it as an address: 5 wait states; v_readlane / v_writelane taking it as
+                    // the lane select: 4) neither use exists - the four values only ever feed s_cmp and the constant operand of v_min_f32 /
+                    // v_mul_f32 / v_add_f32, which need none - and the first reader is behind the profile loop's header, LDS waits included.
+                    // Whoever gives them another use pads it.  tools/resource_usage.py after this change: the four-per-CU instances 63 VGPRs
+                    // (shaped) / 64 (run-time shape), 62 - 64 with the appended search, 0 spilled in all 25.)
+                    auto in_sgpr = [](int v) { int r; asm volatile("v_readfirstlane_b32 %0, %1" : "=s"(r) : "v"(v)); return r; };
+                    const int lut_crowded = kShape ? in_sgpr(s_cnt[4]) : 1;  // (run-time shape: the loops, see FRAMES)
+                    // (shaped instances only: the run-time-shape ones have no scalar register left either - held there, the four cost more
+                    // lane operations on spilled SGPRs than they save - and convert per profile as before)
+                    const float r_ego_s = kShape ? __int_as_float(in_sgpr(__float_as_int(float_above(s_k[4])))) : 0.0f;
+                    const float hl_s = kShape ? __int_as_float(in_sgpr(__float_as_int(float_above(s_k[2])))) : 0.0f;
+                    const float hw_s = kShape ? __int_as_float(in_sgpr(__float_as_int(float_above(s_k[3])))) : 0.0f;
+                    // the last pose row a lane can hold: a profile with more points than that has no hit on its own last point
+                    const int k_last = kShape ? mul24(rows - 1, stride) : 0;
                     // Profiles are dealt to the wavefronts round-robin (wave w takes w, w + 8, ...: a mix of end speeds each); the first
                     // wavefront to run out waits ~3 of the walk's 24 us for the last one.  Dealing them from a shared LDS counter instead was
                     // built and measured: no difference (153.1 / 154.4 against 155.1 / 154.1 us per step in same-box runs) - the waiting
@@ -1068,7 +1119,14 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
                         for (int i = lane; i < npm; i += kWave) {
                             const double t = (double)i * tick;
                             const double s = fma(fma(fma(fma(a4, t, a3), t, eSdd0() * 0.5), t, eSd0()), t, eS0());
-                            const int seg = lut_segment(s_knots, s_lut, nx, s, s_k[0], s_k[1], n_buckets);
+                            int seg;
+                            if (kShape && lut_crowded == 0) {  // (the run-time-shape instances keep the loops alone: both lookups in one instance make it larger than it was)
+                                seg = lut_segment_step(s_knots, s_lut, nx, s, s_k[0], s_k[1], n_buckets);
+                            } else {
+    // [section LUTWALK]
+                                seg = lut_segment(s_knots, s_lut, nx, s, s_k[0], s_k[1], n_buckets);
+    // [/section LUTWALK]
+                            }
                             Frame fr;
                             frame_at(seg, s - s_knots[seg], fr.px, fr.py, fr.tx, fr.ty);
                             wfr.set(i, fr.px, fr.py, fr.tx, fr.ty);
@@ -1078,7 +1136,7 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
                         const fan_t* dm = s_fan_d + mul24(it, hp_max);
                         const fan_t* ddm = s_fan_dd + mul24(it, hp_max);
                         {   // prep (see the slice loop's comment for the bound): conservative, fp32
-                            const float r_ego_f = float_above(s_k[4]), hl_f = float_above(s_k[2]), hw_f = float_above(s_k[3]);
+                            const float r_ego_f = kShape ? r_ego_s : float_above(s_k[4]), hl_f = kShape ? hl_s : float_above(s_k[2]), hw_f = kShape ? hw_s : float_above(s_k[3]);
     // [section PREP]
                             for (int r = lane; r < rows; r += kWave) {
                                 const int k = mul24(r, stride);
@@ -1117,9 +1175,11 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
                             const int si = c0 + lane;
                             bool pass = false;
                             uint32_t code = 0;
+    // [section B]
                             if (si < n_walk) {
                                 const int item = s_items[si];
-                                const int r = div_by<NOBS, ROWS * NOBS>(item, inv_nobs), j = item - mul24(r, n_obs);
+                                const int r = kItemShift > 0 ? item >> kItemShift : div_by<NOBS, ROWS * NOBS>(item, inv_nobs);
+                                const int j = kItemShift > 0 ? item & ((1 << kItemShift) - 1) : item - mul24(r, n_obs);
                                 const int k = mul24(r, stride);
                                 const ObsPose op = s_spose.get(si);
                                 const ObsDim od = s_dim.get(j);
@@ -1138,6 +1198,7 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
                                        !(fabs(u) > r_ego_b * (1.0 + 1e-12) + reach_t);
                                 code = (uint32_t)k | ((uint32_t)si << 8);  // k < 128, si < 512 (slim: si < 256, 16 bits)
                             }
+    // [/section B]
                             const unsigned long long m = __ballot(pass);
                             if (lane == 0) { FP_COUNT(1, 1); FP_COUNT(2, __popcll(m)); }
                             if (!m) continue;
@@ -1153,26 +1214,47 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
                             for (int h0 = 0; h0 < n_exact; h0 += hpw) {
                                 const int h = h0 + hh_l;
                                 bool hit = false;
+    // [section N]
                                 if (hh_l < hpw && h < n_exact && !((coll >> id_l) & 1ull)) {
                                     const uint32_t hc = wh[h];
                                     const int k = hc & 0xFF, si2 = hc >> 8;
-                                    const int j = (int)s_items[si2] - mul24(div_by<STRIDE, FP_MAX_POINTS>(k, inv_stride), n_obs);  // item = row * n_obs + obstacle
+                                    const int j = kItemShift > 0 ? (int)s_items[si2] & ((1 << kItemShift) - 1)
+                                                                 : (int)s_items[si2] - mul24(div_by<STRIDE, FP_MAX_POINTS>(k, inv_stride), n_obs);  // (table index: row * n_obs + obstacle)
                                     FP_COUNT(3, 1);
                                     // heading of pose k: forward difference, or the previous one for the last point (:127-129)
-                                    const int ka_ = (k + 1 < M) ? k : k - 1;
+                                    // (only a profile whose line ends inside the checked rows has such a point: the others take k without the compare and the selects)
+                                    int ka_ = k;
+                                    unsigned long long on_last = 0;  // the round's lanes that stand on their profile's last point
+                                    // (run-time shape: every profile takes the block - one more scalar held through the walk costs those instances more
+                                    // lane operations on spilled SGPRs than the block has instructions)
+                                    if (!kShape || M <= k_last + 1) {  // (scalar: the line ends inside the checked rows)
+    // [section NLAST]
+                                        asm volatile("");  // (nothing is emitted: it keeps this a wave-uniform BRANCH - without it the compiler folds the block into selects that every profile pays)
+                                        on_last = __builtin_amdgcn_ballot_w64(k + 1 >= M);
+                                        ka_ = (k + 1 < M) ? k : k - 1;
+    // [/section NLAST]
+                                    }
                                     const Frame f0 = wfr.get(ka_), f1 = wfr.get(ka_ + 1);
                                     const double* ql = qlat + mul24(id_l, 3);
                                     const double b3 = ql[0], b4 = ql[1], b5 = ql[2];
                                     const double ta = (double)ka_ * tick, tb = (double)(ka_ + 1) * tick;
-                                    const double da = fma(fma(fma(fma(fma(b5, ta, b4), ta, b3), ta, eDdd0() * 0.5), ta, eDd0()), ta, eD0());
-                                    const double db = fma(fma(fma(fma(fma(b5, tb, b4), tb, b3), tb, eDdd0() * 0.5), tb, eDd0()), tb, eD0());
+                                    const double da = fma(fma(fma(fma(fma(b5, ta, b4), ta, b3), ta, eDdd0Half()), ta, eDd0()), ta, eD0());
+                                    const double db = fma(fma(fma(fma(fma(b5, tb, b4), tb, b3), tb, eDdd0Half()), tb, eDd0()), tb, eD0());
                                     double xa, ya, xb, yb;
                                     frenet_to_cartesian(f0.px, f0.py, f0.tx, f0.ty, da, xa, ya);
                                     frenet_to_cartesian(f1.px, f1.py, f1.tx, f1.ty, db, xb, yb);
                                     Obb ego;
                                     step_heading(xb - xa, yb - ya, ego.c, ego.s);
-                                    ego.x = (ka_ == k) ? xa : xb;
-                                    ego.y = (ka_ == k) ? ya : yb;
+                                    ego.x = xa;
+                                    ego.y = ya;
+                                    if (on_last) {
+    // [section NLAST]
+                                        asm volatile("");
+                                        const bool mine = __builtin_amdgcn_inverse_ballot_w64(on_last);
+                                        ego.x = mine ? xb : xa;
+                                        ego.y = mine ? yb : ya;
+    // [/section NLAST]
+                                    }
                                     ego.hl = s_k[2];
                                     ego.hw = s_k[3];
                                     const ObsPose op = s_spose.get(si2);
@@ -1192,6 +1274,7 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
                                     }
                                     if (hit) FP_COUNT(5, 1);
                                 }
+    // [/section N]
                                 if (lane == 0) FP_COUNT(6, 1);
                                 unsigned long long hm = __ballot(hit);
                                 // fold the round's hits onto the nd lateral samples (scalar arithmetic on the ballot)

@@ -22,6 +22,16 @@ constexpr int kHitCap = 1024;    // block-wide list of (lon profile, row, obstac
 // layout of make_layout with a 256-entry list - the largest ego of the headline workload keeps 221; longer lists take the chunked redo)
 __host__ __device__ constexpr int item_cap(int occ) { return occ > 6 ? 256 : occ > 4 ? 320 : 512; }
 constexpr int kItemCapMax = 512;
+// bits of the obstacle index in a packed walk item (row << bits | obstacle), or 0 where such a code does not fit the list's 16 bits
+constexpr int item_shift(int n_obs, int rows)
+{
+    int s = 0;
+    while ((1 << s) < n_obs) ++s;
+    return s > 0 && ((long long)(rows > 0 ? rows - 1 : 0) << s) + (n_obs - 1) <= 0xFFFF ? s : 0;
+}
+static_assert(item_shift(50, 25) == 6 && item_shift(10, 50) == 4, "the two compiled-in shapes pack their items");
+static_assert(item_shift(64, 1024) == 6 && item_shift(65, 1024) == 0 && item_shift(64, 1025) == 0, "(1023 << 6 | 63 is the last code that fits 16 bits)");
+static_assert(item_shift(1, 25) == 0 && item_shift(2, 25) == 1 && item_shift(4095, 16) == 12 && item_shift(4095, 17) == 0, "one obstacle has no bits to pack");
 
 // LDS carve-up (all offsets in bytes, 16-byte aligned)
 struct Layout {
