@@ -125,6 +125,12 @@ class ProblemBatch:
     gate_closed: np.ndarray | None = None   # [F, T_gate] uint32
     gate_front: float = 0.0                 # the line is crossed by s + gate_front (veh_l / 2: the front bumper)
     gate_max_decel: float = 0.0             # > 0: a gate the ego can no longer stop in front of at this deceleration is waived; 0 = off
+    # a time gap to moving obstacles (fp_time_gap, fp_gap_mask), in steps of tick_t: the ego may not be where an obstacle was up to
+    # gap_follow steps earlier, no obstacle where the ego was up to gap_lead steps earlier; ego points before gap_first are not checked
+    # (the grace of an ego that starts too close).  0 / 0 = no rule
+    gap_follow: int = 0
+    gap_lead: int = 0
+    gap_first: int = 1
     # the obstacle tracks obs_pose can be predicted from on the device (fp_tracks, fp_obstacles_predict; DeviceBatch.predict): the
     # model (FP_TRACK_*) and six numbers per obstacle column, and the frame the LANE tracks of every scene follow; None = no tracks
     track_model: np.ndarray | None = None  # [S, n_obs] int32
@@ -169,6 +175,9 @@ class ProblemBatch:
             self.gate_s, self.gate_closed = f8(self.gate_s), np.ascontiguousarray(self.gate_closed, dtype=np.uint32)
             assert self.gate_s.ndim == 2 and self.gate_s.shape[0] == self.F and 1 <= self.gate_s.shape[1] <= 32  # (FP_MAX_GATES)
             assert self.gate_closed.ndim == 2 and self.gate_closed.shape[0] == self.F and self.gate_closed.shape[1] >= 1
+        self.gap_follow, self.gap_lead, self.gap_first = int(self.gap_follow), int(self.gap_lead), int(self.gap_first)
+        assert 0 <= self.gap_follow <= 256 and 0 <= self.gap_lead <= 256, "gap_follow / gap_lead: 0 .. FP_MAX_POINTS steps"
+        assert 1 <= self.gap_first <= 2**31 - 1, "gap_first: 1 .. INT32_MAX (anything from FP_MAX_POINTS on lies beyond every pose)"
         assert (self.track_model is None) == (self.track_state is None), "track_model and track_state come together"
         assert self.track_frame is None or self.track_model is not None, "track_frame without tracks"
         if self.track_model is not None:
@@ -229,6 +238,7 @@ class ProblemBatch:
             max_lat_accel=self.max_lat_accel,
             gate_s=None if self.gate_s is None else self.gate_s[fr], gate_closed=None if self.gate_closed is None else self.gate_closed[fr],
             gate_front=self.gate_front, gate_max_decel=self.gate_max_decel,
+            gap_follow=self.gap_follow, gap_lead=self.gap_lead, gap_first=self.gap_first,
             track_model=None if self.track_model is None else self.track_model[keep_s],
             track_state=None if self.track_state is None else self.track_state[keep_s], track_frame=track_frame,
             meta=dict(self.meta, **(meta or {})))
@@ -266,6 +276,9 @@ class ProblemBatch:
                 h.update(name.encode()); h.update(str(a.shape).encode()); h.update(np.ascontiguousarray(a).tobytes())
             for name in ("gate_front", "gate_max_decel"):
                 h.update(name.encode()); h.update(np.float64(getattr(self, name)).tobytes())
+        if self.gap_follow or self.gap_lead:  # (batches without a time gap keep their digests)
+            for name in ("gap_follow", "gap_lead", "gap_first"):
+                h.update(name.encode()); h.update(np.int32(getattr(self, name)).tobytes())
         if self.track_model is not None:  # (batches without tracks keep their digests)
             for name in ("track_model", "track_state") + (("track_frame",) if self.track_frame is not None else ()):
                 a = getattr(self, name)

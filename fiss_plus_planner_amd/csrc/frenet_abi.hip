@@ -197,6 +197,7 @@ struct fp_ctx {
     int boundary_launches = 0;     // fp_ctx_get_option("boundary_launches"): launches of the road-boundary kernel (fp_boundary_mask)
     int envelope_launches = 0;     // fp_ctx_get_option("envelope_launches"): launches of the speed-envelope kernel (fp_speed_envelope)
     int gate_launches = 0;         // fp_ctx_get_option("gate_launches"): launches of the gate kernel (fp_gate_mask)
+    int gap_launches = 0;          // fp_ctx_get_option("gap_launches"): launches of the time-gap kernel (fp_gap_mask)
     int margin_launches = 0;       // fp_ctx_get_option("margin_launches"): launches of the plan-margin kernel (fp_traj_margins)
     int predict_launches = 0;      // fp_ctx_get_option("predict_launches"): launches of the obstacle prediction kernel (fp_obstacles_predict)
     int from_state_launches = 0;   // fp_ctx_get_option("from_state_launches"): launches of the projection kernel (fp_from_state)
@@ -1419,7 +1420,7 @@ int fp_ctx_get_option(fp_ctx* ctx, const char* name, int* value)
     const struct { const char* n; int v; } tab[] = {
         {"lattice_kernel", ctx->lattice_kernel}, {"lattice_split", ctx->lattice_split}, {"lattice_group", ctx->lattice_group}, {"lattice_tail", ctx->lattice_tail}, {"lattice_occupancy", ctx->lattice_occupancy}, {"resident_groups", ctx->resident_groups}, {"zero_copy_in", ctx->zero_copy_in}, {"stage_kernel", ctx->stage_kernel}, {"inline_inputs", ctx->inline_inputs}, {"lattice_order", ctx->lattice_order},
         {"refine_table_kb", ctx->refine_table_kb}, {"fiss_stages", ctx->fiss_stages}, {"fiss_jump", ctx->fiss_jump}, {"validate", ctx->validate}, {"lattice_winner", ctx->lattice_winner}, {"fiss_fused", ctx->fiss_fused}, {"appended_workgroups", ctx->appended_ok ? 1 : 0}, {"handover_failed", ctx->hand_err ? *(volatile int32_t*)ctx->hand_err : 0}, {"overlap", ctx->overlap}, {"overlapped_calls", ctx->overlapped_calls}, {"clearance_launches", ctx->clearance_launches + (ctx->twin ? ctx->twin->clearance_launches : 0)}, {"lattice_launches", ctx->lattice_launches + (ctx->twin ? ctx->twin->lattice_launches : 0)},
-        {"looplog_launches", ctx->looplog_launches}, {"rank_launches", ctx->rank_launches}, {"boundary_launches", ctx->boundary_launches}, {"envelope_launches", ctx->envelope_launches}, {"gate_launches", ctx->gate_launches}, {"margin_launches", ctx->margin_launches}, {"predict_launches", ctx->predict_launches}, {"from_state_launches", ctx->from_state_launches}, {"lattice_ordered_launches", ctx->lattice_ordered_launches + (ctx->twin ? ctx->twin->lattice_ordered_launches : 0)},
+        {"looplog_launches", ctx->looplog_launches}, {"rank_launches", ctx->rank_launches}, {"boundary_launches", ctx->boundary_launches}, {"envelope_launches", ctx->envelope_launches}, {"gate_launches", ctx->gate_launches}, {"gap_launches", ctx->gap_launches}, {"margin_launches", ctx->margin_launches}, {"predict_launches", ctx->predict_launches}, {"from_state_launches", ctx->from_state_launches}, {"lattice_ordered_launches", ctx->lattice_ordered_launches + (ctx->twin ? ctx->twin->lattice_ordered_launches : 0)},
         {"lattice_launches_2", (int)fp::lattice_launches_per_cu(0)}, {"lattice_launches_3", (int)fp::lattice_launches_per_cu(1)}, {"lattice_launches_4", (int)fp::lattice_launches_per_cu(2)}};
     for (const auto& t : tab)
         if (strcmp(name, t.n) == 0) { *value = t.v; return FP_OK; }
@@ -1718,6 +1719,51 @@ int fp_gate_mask(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, co
     FP_TRY(hs.commit(sl));
     LAUNCH_TRY(fp::launch_gate_mask(a, ctx->stream), "gate kernel");
     ++ctx->gate_launches;
+    return hs.fetch_out();
+}
+
+int fp_gap_mask(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, const fp_time_gap* gap, const double* cost_tbl, uint32_t* flag_tbl,
+                int32_t* best_idx, double* best_cost, int32_t* n_close, int mem, void* stream)
+{
+    FP_TRY(common_checks(ctx, params, batch, mem, stream));
+    if (!gap) return fail(FP_EINVAL, "fp_gap_mask: gap must not be NULL");
+    if (!cost_tbl || !flag_tbl || !best_idx || !best_cost) return fail(FP_EINVAL, "fp_gap_mask: cost_tbl/flag_tbl/best_idx/best_cost must not be NULL");
+    if (gap->lag_follow < 0 || gap->lag_follow > FP_MAX_POINTS) return fail(FP_EINVAL, "fp_gap_mask: lag_follow=%d outside 0..FP_MAX_POINTS", gap->lag_follow);
+    if (gap->lag_lead < 0 || gap->lag_lead > FP_MAX_POINTS) return fail(FP_EINVAL, "fp_gap_mask: lag_lead=%d outside 0..FP_MAX_POINTS", gap->lag_lead);
+    if (gap->first < 1) return fail(FP_EINVAL, "fp_gap_mask: first=%d must be >= 1", gap->first);
+    if (batch->B == 0) return FP_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t B = (size_t)batch->B, C = (size_t)params->nd * params->nv * params->nt;
+    fp::KernelArgs ka;
+    ka.p = *params;
+    ka.r = no_result();
+    fp::GapArgs g;
+    g.lag_follow = gap->lag_follow; g.lag_lead = gap->lag_lead;
+    g.first = gap->first < FP_MAX_POINTS ? gap->first : FP_MAX_POINTS;  // (points are 0 .. FP_MAX_POINTS - 1: anything above is "beyond every pose")
+    if (mem == FP_MEM_DEVICE) {
+        ka.b = *batch;
+        if (!(batch->S > 0 && batch->n_obs > 0)) ka.b.n_obs = 0;
+        ka.r.cost_tbl = const_cast<double*>(cost_tbl);  // (read only)
+        ka.r.flag_tbl = flag_tbl; ka.r.best_idx = best_idx; ka.r.best_cost = best_cost;
+        g.perm = batch->launch_order; g.count = n_close;
+        LAUNCH_TRY(fp::launch_gap_mask(ka, g, (hipStream_t)stream), "time-gap kernel");
+        ++ctx->gap_launches;
+        return FP_OK;
+    }
+    FP_TRY(check_batch_host(params, batch));
+    ka.p.points_max = host_points_max(params, batch, nullptr, 0, 0);  // (host calls look at their time samples themselves)
+    HostStage hs(ctx);
+    StageList sl;
+    StageRegime rg;  // (throughput)
+    FP_TRY(stage_batch(ctx, sl, rg, params, batch, &ka.b));
+    sl.in(cost_tbl, B * C, &ka.r.cost_tbl);
+    sl.in_mut(flag_tbl, B * C, &ka.r.flag_tbl);
+    sl.out(best_idx, B, &ka.r.best_idx);
+    sl.out(best_cost, B, &ka.r.best_cost);
+    sl.out(n_close, B, &g.count);
+    FP_TRY(hs.commit(sl, rg));
+    LAUNCH_TRY(fp::launch_gap_mask(ka, g, ctx->stream), "time-gap kernel");
+    ++ctx->gap_launches;
     return hs.fetch_out();
 }
 

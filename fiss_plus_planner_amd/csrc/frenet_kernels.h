@@ -261,6 +261,18 @@ struct GateArgs : TablePassArgs {
     const uint32_t* closed = nullptr;
 };
 hipError_t launch_gate_mask(const GateArgs& a, hipStream_t stream);
+// A time gap to moving obstacles (frenet_gaps.hip, fp_gap_mask): ORs FP_FLAG_COLLISION into the flag word of a survivor in ka.r.flag_tbl
+// whose footprint overlaps an obstacle's with the two time indices up to lag_follow / lag_lead steps apart, and writes the argmin of
+// ka.r.cost_tbl over the survivors that are left to ka.r.best_idx / best_cost.  One workgroup per ego, in the order of perm (optional);
+// count = n_close (optional).  Device addresses.  grid_cap and bound_off are filled in by the launcher: the grid poses its LDS cull
+// table holds (0: none) and where the table starts, in doubles.
+struct GapArgs {
+    int lag_follow = 0, lag_lead = 0, first = 1;
+    int grid_cap = 0, bound_off = 0;
+    const int32_t* perm = nullptr;
+    int32_t* count = nullptr;
+};
+hipError_t launch_gap_mask(const KernelArgs& ka, GapArgs g, hipStream_t stream);
 // The obstacle margin of K chosen plans per ego (frenet_margins.hip, fp_traj_margins): one workgroup per ego, in the order of perm
 // (optional).  ka.p.check_stride is the call's pose_stride; ka.r is not read.  Device addresses; exactly one of best_idx [K][B] /
 // end_state [K][B][3] set; the outputs are [K][B].

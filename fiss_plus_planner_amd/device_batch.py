@@ -4,7 +4,8 @@ PyTorch is plumbing here (device allocations + the stream handle); every array c
 device address.  `DeviceBatch` uploads a ProblemBatch once; `ClosedLoopRunner` enqueues
 [plan -> advance] x cycles on one stream (reference loop: planners/benchmark/planning.py:120-162) and only
 reads back at the end (or per cycle, when a trace is requested).  With rules=(...) the cycle is [plan -> rule passes -> advance]: the
-speed envelope, the gates and the road-boundary check run over the dense call's tables and decide which candidate the ego follows.
+speed envelope, the gates, the road-boundary check and the time gap to moving obstacles run over the dense call's tables and decide which
+candidate the ego follows.
 With record=True the driven trajectory of every ego - what the reference's loop returns as state_list - is written on the device by
 fp_loop_record behind every step and read back once.
 """
@@ -17,12 +18,13 @@ import numpy as np
 from . import _abi
 from .batch import ProblemBatch
 from .closed_loop import LoopLog
-from .engine import FrenetEngine, device_batch, launch_order_hint, make_params
+from .engine import FrenetEngine, _has_time_gap, device_batch, launch_order_hint, make_params
 
 _NAMES = ("d_samples", "t_samples", "v_samples", "target_speed", "ego", "frame_of", "scene_of", "t_now", "nx", "knots", "coef",
           "obs_pose", "obs_dims", "final_time_step")
 
 RULES = ("envelope", "gates", "boundary")  # the rule passes of ClosedLoopRunner(rules=...), in the order they run
+OBSTACLE_RULES = ("gaps",)  # ... and the passes that do geometry against the obstacle table: behind the others, which leave them fewer survivors
 
 LOG_POLL_CYCLES = 16  # run(record=True) reads the log's 4-byte count of running egos this often and stops enqueueing at 0
 
@@ -82,9 +84,10 @@ class ClosedLoopRunner:
     def __init__(self, engine: FrenetEngine, dbatch: DeviceBatch, goal_xy: np.ndarray, planner: str = "FOP", fused: bool = True,
                  goal_poly: np.ndarray | None = None, goal_nv: np.ndarray | None = None, goal_intervals: np.ndarray | None = None,
                  rules=()):
-        """rules: any subset of ("envelope", "gates", "boundary") - FOP only, and the batch must carry each rule's data (speed profile /
-        gates / corridor).  The cycle then is fp_plan_dense into the runner's own [B][C] tables, the passes asked for in that order
-        (fp_speed_envelope, fp_gate_mask, fp_boundary_mask), each writing best_idx / best_cost, and fp_advance on the last one's winner;
+        """rules: any subset of ("envelope", "gates", "boundary", "gaps") - FOP only, and the batch must carry each rule's data (speed
+        profile / gates / corridor / a time gap with a lag above 0).  The cycle then is fp_plan_dense into the runner's own [B][C] tables,
+        the passes asked for in that order (fp_speed_envelope, fp_gate_mask, fp_boundary_mask, fp_gap_mask), each writing best_idx /
+        best_cost, and fp_advance on the last one's winner;
         `fused` has no say.  rules=(): the calls below, unchanged.
         fused: an FOP cycle is ONE launch (fp_plan_step: the workgroup that finds an ego's argmin advances the ego); False = the two
         calls fp_plan_dense + fp_advance (same results; the A/B of tests and bench).
@@ -141,17 +144,19 @@ class ClosedLoopRunner:
         """The rules in the order they run; ValueError for an unknown rule, a planner that is not FOP, or a rule without its data."""
         rules = (rules,) if isinstance(rules, str) else tuple(rules)
         for r in rules:
-            if r not in RULES:
-                raise ValueError(f"ClosedLoopRunner: unknown rule {r!r} (rules are a subset of {RULES})")
+            if r not in RULES and r not in OBSTACLE_RULES:
+                raise ValueError(f"ClosedLoopRunner: unknown rule {r!r} (rules are a subset of {RULES + OBSTACLE_RULES})")
         if rules and planner != "FOP":
             raise ValueError(f"ClosedLoopRunner: rules are defined for the FOP planner only ({planner} orders candidates by cost before validation)")
         has = dict(envelope=getattr(batch, "speed_limit", None) is not None or float(getattr(batch, "max_lat_accel", 0.0) or 0.0) > 0.0,
-                   gates=getattr(batch, "gate_s", None) is not None, boundary=getattr(batch, "bound_left", None) is not None)
+                   gates=getattr(batch, "gate_s", None) is not None, boundary=getattr(batch, "bound_left", None) is not None,
+                   gaps=_has_time_gap(batch))
         for r in rules:
             if not has[r]:
                 raise ValueError(f"ClosedLoopRunner: rule {r!r} needs data the batch does not carry "
-                                 "(envelope: speed_limit / max_lat_accel, gates: gate_s / gate_closed, boundary: bound_left / bound_right)")
-        return tuple(r for r in RULES if r in rules)
+                                 "(envelope: speed_limit / max_lat_accel, gates: gate_s / gate_closed, boundary: bound_left / bound_right, "
+                                 "gaps: gap_follow / gap_lead)")
+        return tuple(r for r in RULES + OBSTACLE_RULES if r in rules)
 
     def _step_rules(self, stream: int):
         """fp_plan_dense -> the rule passes -> fp_advance: a linear chain on `stream`."""
@@ -167,8 +172,10 @@ class ClosedLoopRunner:
             elif r == "gates":
                 eng.gate_mask_device(db.params, self.fb, db.t["gate_s"].data_ptr(), db.t["gate_closed"].data_ptr(), h.gate_s.shape[1], h.gate_closed.shape[1],
                                      h.gate_front, h.gate_max_decel, cost, flags, bi, bc, n, stream)
-            else:
+            elif r == "boundary":
                 eng.boundary_mask_device(db.params, self.fb, db.t["bound_left"].data_ptr(), db.t["bound_right"].data_ptr(), h.bound_margin, cost, flags, bi, bc, n, stream)
+            else:
+                eng.gap_mask_device(db.params, self.fb, h.gap_follow, h.gap_lead, h.gap_first, cost, flags, bi, bc, n, stream)
         _abi.check(eng._lib.fp_advance(eng._ctx, C.byref(db.params), C.byref(self.fb), bi, None, C.byref(self.io), _abi.FP_MEM_DEVICE, stream or None))
 
     def step(self, stream: int = 0):

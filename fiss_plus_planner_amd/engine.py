@@ -135,6 +135,21 @@ def fiss_rounds(kind, max_refine_iters: int) -> int:
     return int(max_refine_iters) if kind in ("FISS+", _abi.FP_FISS_PLUS) else 0
 
 
+def _has_time_gap(batch) -> bool:
+    """A batch with both lags 0 carries no time gap."""
+    return int(getattr(batch, "gap_follow", 0) or 0) > 0 or int(getattr(batch, "gap_lead", 0) or 0) > 0
+
+
+def _time_gap(follow, lead, first, who: str) -> "_abi.FpTimeGap":
+    """fp_time_gap of three Python ints; a value outside the struct's range raises here (a ctypes field would wrap it silently)."""
+    follow, lead, first = int(follow), int(lead), int(first)
+    if not (0 <= follow <= _abi.FP_MAX_POINTS and 0 <= lead <= _abi.FP_MAX_POINTS):
+        raise ValueError(f"{who}: follow = {follow} / lead = {lead} outside 0 .. FP_MAX_POINTS ({_abi.FP_MAX_POINTS}) steps")
+    if not 1 <= first <= 2**31 - 1:
+        raise ValueError(f"{who}: first = {first} outside 1 .. INT32_MAX")
+    return _abi.FpTimeGap(follow, lead, first, 0)
+
+
 def _has_speed_profile(batch) -> bool:
     return getattr(batch, "speed_limit", None) is not None or float(getattr(batch, "max_lat_accel", 0.0) or 0.0) > 0.0
 
@@ -211,7 +226,7 @@ class FrenetEngine:
 
     def plan_dense(self, batch: ProblemBatch, tables: bool = True, winner: bool = False, traj_stride: int = TRAJ_STRIDE, traj_sparse: bool = False,
                    out: SimpleNamespace | None = None, audit: bool = False, top_k: int = 0, boundary: bool = False, margins: bool = False,
-                   envelope: bool = False, gates: bool = False):
+                   envelope: bool = False, gates: bool = False, gaps: bool = False):
         """FrenetOptimalPlanner.plan() for every ego of the batch (reference frenet_optimal_planner.py:247-270).
 
         Returns best_idx [B] (flat (i_d*nt+i_T)*nv+i_v, -1 = none), best_cost [B], stats [B,4] and, with
@@ -233,24 +248,29 @@ class FrenetEngine:
         winner=True follow the masked result like with boundary=True.  gates=True (the batch must carry gates: gate_s / gate_closed): the
         stop lines that open and close (gate_mask) run behind the envelope and before the boundary check; `flags` carry the added
         FLAG_SPEED bits of the candidates that cross a closed gate, also n_gated [B]; everything else follows the masked result likewise.
+        gaps=True (the batch must carry a time gap: gap_follow / gap_lead > 0): the time gap to moving obstacles (gap_mask) runs last,
+        behind envelope, gates and boundary check, so that fewer survivors reach it; `flags` carry the added FLAG_COLLISION bits, also
+        n_close [B].
         """
         if margins:
-            out = self.plan_dense(batch, tables, winner, traj_stride, traj_sparse, out, audit, top_k, boundary, envelope=envelope, gates=gates)
+            out = self.plan_dense(batch, tables, winner, traj_stride, traj_sparse, out, audit, top_k, boundary, envelope=envelope, gates=gates, gaps=gaps)
             plans = out.rank_idx if top_k else out.best_idx
             if batch.B:
                 out.margin_dist, out.margin_step, out.margin_obs = self.traj_margins(batch, best_idx=plans)
             else:
                 out.margin_dist, out.margin_step, out.margin_obs = np.empty(plans.shape), np.empty(plans.shape, dtype=np.int32), np.empty(plans.shape, dtype=np.int32)
             return out
-        if boundary or envelope or gates:
+        if boundary or envelope or gates or gaps:
             if boundary and getattr(batch, "bound_left", None) is None:
                 raise ValueError("plan_dense(boundary=True): the batch carries no corridor (ProblemBatch.bound_left / bound_right)")
             if envelope and not _has_speed_profile(batch):
                 raise ValueError("plan_dense(envelope=True): the batch carries no speed profile (ProblemBatch.speed_limit / max_lat_accel)")
             if gates and getattr(batch, "gate_s", None) is None:
                 raise ValueError("plan_dense(gates=True): the batch carries no gates (ProblemBatch.gate_s / gate_closed)")
+            if gaps and not _has_time_gap(batch):
+                raise ValueError("plan_dense(gaps=True): the batch carries no time gap (ProblemBatch.gap_follow / gap_lead)")
             if audit:
-                raise ValueError("plan_dense(boundary / envelope / gates=True, audit=True): the audit bits describe the dense call's own answer, not the masked one")
+                raise ValueError("plan_dense(boundary / envelope / gates / gaps=True, audit=True): the audit bits describe the dense call's own answer, not the masked one")
             want_tables = tables
             if out is not None and not tables:  # the caller's arrays hold no tables: the call brings its own
                 out.cost, out.flags = np.empty((batch.B, batch.C)), np.empty((batch.B, batch.C), dtype=np.uint32)
@@ -263,6 +283,8 @@ class FrenetEngine:
                     _, bi, bc, out.n_gated = self.gate_mask(batch, out.cost, out.flags, inplace=True)
                 if boundary:
                     _, bi, bc, out.n_masked = self.boundary_mask(batch, out.cost, out.flags, inplace=True)
+                if gaps:  # (last: the geometry is paid only for the candidates the cheaper rules left)
+                    _, bi, bc, out.n_close = self.gap_mask(batch, out.cost, out.flags, inplace=True)
                 out.best_idx[...], out.best_cost[...] = bi, bc
                 if winner:
                     w = self.winner_trajs(batch, out.best_idx, traj_stride, traj_sparse)
@@ -274,6 +296,8 @@ class FrenetEngine:
                     out.n_gated = np.empty(0, dtype=np.int32)
                 if boundary:
                     out.n_masked = np.empty(0, dtype=np.int32)
+                if gaps:
+                    out.n_close = np.empty(0, dtype=np.int32)
             if top_k:
                 if not 1 <= int(top_k) <= _abi.FP_MAX_RANK:
                     raise ValueError(f"top_k={top_k}: 0 (off) or 1 .. FP_MAX_RANK ({_abi.FP_MAX_RANK})")
@@ -460,6 +484,44 @@ class FrenetEngine:
         g = _abi.FpGates(gate_s or None, closed or None, int(gate_stride), int(T_gate), float(front), float(max_decel))
         _abi.check(self._lib.fp_gate_mask(self._ctx, C.byref(params), C.byref(fb), C.byref(g), cost_tbl or None, flag_tbl or None, best_idx or None,
                                           best_cost or None, n_gated or None, _abi.FP_MEM_DEVICE, stream or None))
+
+    def gap_mask(self, batch: ProblemBatch, cost: np.ndarray, flags: np.ndarray, skip: np.ndarray | None = None, inplace: bool = False,
+                 follow: int | None = None, lead: int | None = None, first: int | None = None):
+        """A time gap to moving obstacles over plan_dense's tables (fp_gap_mask; the definition: include/frenet_gpu.h): cost [B,C], flags
+        [B,C] and the batch's gap_follow / gap_lead / gap_first in steps of tick_t (follow / lead / first override them) -> (flags,
+        best_idx, best_cost, n_close): the flag words with FLAG_COLLISION ORed in where a survivor's footprint at point a overlaps an
+        obstacle's at step r with 0 < a - r <= follow or 0 < r - a <= lead, a >= first, both on the check grid (a copy, unless
+        inplace=True and `flags` is a contiguous uint32 array; no bit is ever cleared), the argmin among the candidates without a
+        FLAG_INFEASIBLE bit, and the number of survivors per ego that violate in this call.  Both lags 0 flags nothing, and so does a
+        `first` beyond every pose (any value up to INT32_MAX); lags outside 0 .. FP_MAX_POINTS or a `first` outside 1 .. INT32_MAX raise
+        ValueError.
+        skip [B] (optional): egos whose rows are neither read nor written (-1 / NaN / 0)."""
+        B, Cn = batch.B, batch.C
+        cost = np.ascontiguousarray(cost, dtype=np.float64)
+        if not (inplace and isinstance(flags, np.ndarray) and flags.dtype == np.uint32 and flags.flags.c_contiguous and flags.flags.writeable):
+            flags = np.array(flags, dtype=np.uint32, order="C", copy=True)
+        if cost.shape != (B, Cn) or flags.shape != (B, Cn):
+            raise ValueError(f"gap_mask: cost / flags must be [B={B}, C={Cn}] tables, got {cost.shape} / {flags.shape}")
+        best_idx = np.empty(B, dtype=np.int32); best_cost = np.empty(B); n_close = np.empty(B, dtype=np.int32)
+        p, fb = host_structs(batch)
+        if skip is not None:
+            skip = np.ascontiguousarray(skip, dtype=np.int32)
+            assert skip.shape == (B,)
+            fb.skip = _ptr(skip)
+        g = _time_gap(batch.gap_follow if follow is None else follow, batch.gap_lead if lead is None else lead,
+                      batch.gap_first if first is None else first, "gap_mask")
+        _abi.check(self._lib.fp_gap_mask(self._ctx, C.byref(p), C.byref(fb), C.byref(g), _ptr(cost), _ptr(flags), _ptr(best_idx), _ptr(best_cost),
+                                         _ptr(n_close), _abi.FP_MEM_HOST, None))
+        return flags, best_idx, best_cost, n_close
+
+    def gap_mask_device(self, params: _abi.FpParams, fb: _abi.FpBatch, follow: int, lead: int, first: int, cost_tbl: int, flag_tbl: int,
+                        best_idx: int, best_cost: int, n_close: int = 0, stream: int = 0):
+        """Enqueue the time gap behind a dense call or another pass (device addresses): the lags and `first` in steps, cost_tbl / flag_tbl
+        [B][C] (flag_tbl in/out), best_idx / best_cost [B] out, n_close [B] or 0.  t_now, ego and the obstacle table are read when the
+        kernel runs.  best_idx is a valid argument of winner_trajs_device / fp_advance as it stands."""
+        g = _time_gap(follow, lead, first, "gap_mask_device")
+        _abi.check(self._lib.fp_gap_mask(self._ctx, C.byref(params), C.byref(fb), C.byref(g), cost_tbl or None, flag_tbl or None, best_idx or None,
+                                         best_cost or None, n_close or None, _abi.FP_MEM_DEVICE, stream or None))
 
     def traj_margins(self, batch: ProblemBatch, best_idx: np.ndarray | None = None, end_state: np.ndarray | None = None, pose_stride: int | None = None,
                      skip: np.ndarray | None = None):

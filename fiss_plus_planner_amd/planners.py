@@ -237,6 +237,25 @@ class FrenetOptimalPlanner:
             raise ValueError(f"set_gates: closed must be [T, {len(gate_s)}] truth values or [T] words with T >= 1, got {closed.shape}")
         self._gates = (gate_s, words, front, float(max_decel))
 
+    def set_time_gap(self, follow_s: float, lead_s: float = 0.0, grace_s: float = 0.0):
+        """A time gap to moving obstacles for plan(): the ego may not be where an obstacle was less than follow_s seconds earlier, and no
+        obstacle may reach a place the ego held less than lead_s seconds earlier (the ego does not cut in front of it); the first grace_s
+        seconds of a plan are not checked, so that an ego that starts too close can open the gap.  Seconds become steps of
+        settings.tick_t (rounded to the nearest; the grace is at least one step) when plan() builds its batch.  plan() then returns the
+        cheapest candidate that keeps the gap (fp_gap_mask, include/frenet_gpu.h).  follow_s = lead_s = 0 removes the rule again.
+        FOP+, FISS and FISS+ order candidates by cost before validation and raise ValueError."""
+        if self.KIND != "FOP":
+            raise ValueError(f"set_time_gap: the time gap is defined for FrenetOptimalPlanner only ({self.KIND} orders candidates by cost before validation)")
+        for name, v in (("follow_s", follow_s), ("lead_s", lead_s), ("grace_s", grace_s)):
+            if not (np.isfinite(v) and v >= 0):
+                raise ValueError(f"set_time_gap: {name} = {v} must be finite and >= 0")
+        tick = float(self.settings.tick_t)
+        if max(follow_s, lead_s) / tick > _abi.FP_MAX_POINTS:
+            raise ValueError(f"set_time_gap: a gap of {max(follow_s, lead_s)} s is more than FP_MAX_POINTS ({_abi.FP_MAX_POINTS}) steps of {tick} s")
+        if grace_s / tick > 2**31 - 1:
+            raise ValueError(f"set_time_gap: a grace of {grace_s} s is more than INT32_MAX steps of {tick} s")
+        self._time_gap = (float(follow_s), float(lead_s), float(grace_s)) if follow_s > 0 or lead_s > 0 else None
+
     # ------------------------------------------------------------------ problem marshalling
     def _predicted_table(self, tracks: ObstacleTracks, time_step_now: int) -> ObstacleTable:
         """The pose table of an ObstacleTracks against this planner's own frame: the track states are valid at time_step_now and
@@ -302,9 +321,11 @@ class FrenetOptimalPlanner:
         if prof is not None and prof[0] is not None and len(prof[0]) != len(sp.knots):
             raise ValueError(f"set_speed_profile: {len(prof[0])} limits for a centre line of {len(sp.knots)} points")
         gates = getattr(self, "_gates", None)
+        gap = getattr(self, "_time_gap", None)
+        gap_steps = (0, 0, 1) if gap is None else (int(round(gap[0] / st.tick_t)), int(round(gap[1] / st.tick_t)), min(max(int(round(gap[2] / st.tick_t)), 1), 2**31 - 1))
         cache_tables = getattr(self, "cache_tables", True)
         key = (id(sp), id(tab), getattr(tab, "version", 0), cache_tables, st.num_width, st.num_speed, st.num_t, st.min_t, st.max_t, st.tick_t, st.max_road_width, st.lowest_speed,
-               self.vehicle.l, self.vehicle.w, self.vehicle.max_speed, self.vehicle.max_accel, curv, w_obs, id(bound), id(prof), id(gates))
+               self.vehicle.l, self.vehicle.w, self.vehicle.max_speed, self.vehicle.max_accel, curv, w_obs, id(bound), id(prof), id(gates), gap_steps)
         cache = getattr(self, "_batch_cache", None)
         if cache is None or cache[0] != key:
             sw = self._sampling_width()
@@ -328,7 +349,8 @@ class FrenetOptimalPlanner:
                 speed_limit=None if prof is None or prof[0] is None else prof[0][None], limit_front=0.0 if prof is None else prof[1],
                 limit_tol=0.0 if prof is None else prof[2], max_lat_accel=0.0 if prof is None else prof[3],
                 gate_s=None if gates is None else gates[0][None], gate_closed=None if gates is None else gates[1][None],
-                gate_front=0.0 if gates is None else gates[2], gate_max_decel=0.0 if gates is None else gates[3])
+                gate_front=0.0 if gates is None else gates[2], gate_max_decel=0.0 if gates is None else gates[3],
+                gap_follow=gap_steps[0], gap_lead=gap_steps[1], gap_first=gap_steps[2])
             # fp_batch.tables_tag: the library keeps this batch's spline and obstacle tables on the device until the planner builds
             # a new batch (another centerline / another obstacle list / ObstacleTable.update()) - per cycle only the start state
             # travels.  Contract (class docstring): the cached arrays are frozen, so an in-place edit raises instead of going stale;
@@ -388,9 +410,10 @@ class FrenetOptimalPlanner:
         reuse = outs.get(key)
         if reuse is None:
             reuse = outs[key] = self._engine.dense_outputs(1, batch.C, True, winner, stride)
-        # (a corridor / a speed profile / gates on the batch: the checks run behind the dense call and decide the winner)
+        # (a corridor / a speed profile / gates / a time gap on the batch: the checks run behind the dense call and decide the winner)
         out = self._engine.plan_dense(batch, tables=True, winner=winner, traj_stride=stride, out=reuse, boundary=batch.bound_left is not None,
-                                      envelope=batch.speed_limit is not None or batch.max_lat_accel > 0, gates=batch.gate_s is not None)
+                                      envelope=batch.speed_limit is not None or batch.max_lat_accel > 0, gates=batch.gate_s is not None,
+                                      gaps=batch.gap_follow > 0 or batch.gap_lead > 0)
         self.last_tables = (out.cost[0].copy(), out.flags[0].copy())
         if self.materialize_all:  # visualisation payload (reference :102): every candidate's series in one launch
             m = self._engine.materialize_all(batch, traj_stride=stride)

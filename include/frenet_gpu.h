@@ -558,6 +558,71 @@ typedef struct {
 int fp_gate_mask(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, const fp_gates* gates, const double* cost_tbl,
                  uint32_t* flag_tbl, int32_t* best_idx, double* best_cost, int32_t* n_gated, int mem, void* stream);
 
+/* ---- a time gap to moving obstacles (added WITHIN ABI 18: detect it by looking the symbol up, e.g. dlsym) -------------------------
+ * What decides how close an ego gets to another vehicle is has_collision alone: a plan that passes a hand's width behind a car doing
+ * 12 m/s is as feasible as one 40 m back, and so is one that pulls out just in front of a faster car.  The reference has no such rule;
+ * like the gates and the envelope this finishes what its planner leaves to luck.  A time gap of tau seconds means: the ego does not
+ * occupy a place an obstacle occupied less than tau seconds earlier (FOLLOW), and no obstacle reaches a place the ego occupied less
+ * than tau seconds earlier (LEAD: the ego does not cut in front of it).  That is the post-encroachment time on the candidate's own
+ * path - it bends with the road, scales with speed, works for crossing traffic - and it is the collision check with the two time
+ * indices apart.  It is silent for parked obstacles: a shape that does not move is overlapped at a lag exactly when it is overlapped at
+ * lag 0, which is the collision check's business.  fp_gap_mask runs behind fp_plan_dense (or another pass) and over its tables:
+ * cost_tbl / flag_tbl are [B][C] (C = nd*nv*nt).
+ *
+ * Definition, for every ego b that is not skipped and every candidate c of it that carries NO FP_FLAG_INFEASIBLE bit on entry
+ * (candidates that are already infeasible are not evaluated and keep their words); N and M from the flag word, cs = check_stride:
+ *   pose set P       { i = 0, cs, 2 cs, ... : i < min(M, final_time_step[scene] - t_now[b]) and 0 <= i + t_now[b] < T_obs }:
+ *                    has_collision's own pose set, as in the clearance term and fp_traj_margins.  M < 2: no pose, no bit.
+ *   pairs            (a, r) with a, r in P and a >= first, and either 0 < a - r <= lag_follow (the ego at point a against the
+ *                    obstacles at step r: the ego arrives later) or 0 < r - a <= lag_lead (the obstacle arrives later).  Both lags are
+ *                    in steps of tick_t; only pairs on the check grid exist.  first >= 1 is the grace: an ego that is already too
+ *                    close gets `first` steps to open the gap (point 0 selects nothing anyway).  Any value up to INT32_MAX is legal:
+ *                    `first` >= FP_MAX_POINTS lies beyond every pose and flags nothing (it is read as FP_MAX_POINTS).
+ *   ego shape        the veh_l x veh_w rectangle at x[a], y[a], yaw[a] of the candidate's series.
+ *   obstacle shape   the columns j of the ego's scene with valid != 0 at row r + t_now[b]; the rectangle of obs_dims, or the column's
+ *                    ring (obs_poly / obs_nvert), at that row's pose.
+ *   violation        the two closed shapes intersect for any such pair and column - the collision check's own predicates, so touching
+ *                    counts.
+ *   the bit          a violating candidate gets FP_FLAG_COLLISION ORed into its flag word: the low byte is full, and the bit already
+ *                    means "too close to an obstacle" (the choice the gates made with FP_FLAG_SPEED).  The call NEVER CLEARS a bit and
+ *                    touches no other bit; cost_tbl is never written; Stats do not change.  A second call on the masked tables changes
+ *                    nothing and reports n_close = 0: its violators are no longer evaluated.
+ *   best_idx / best_cost  [B] the argmin of cost_tbl over the candidates with no FP_FLAG_INFEASIBLE bit and a cost that is not NaN; the
+ *                    last minimum in FOP order wins exact ties (:263-268); -1 / NaN when there is none.  Bit for bit plane 0 of an
+ *                    fp_rank_feasible call on the masked tables, and a valid argument of fp_advance, fp_winner_trajs, fp_traj_margins.
+ *   n_close          NULL or [B]: the candidates of the ego that violate in THIS call.
+ *   skipped egos     batch->skip[b] != 0: -1 / NaN / 0, the ego's rows are neither read nor written.
+ *   no scene         an ego with scene_of < 0, or a batch with n_obs == 0: nothing is flagged, the argmin is that of the tables as they are.
+ * Both lags 0 is legal and flags nothing; so does a lag below check_stride.
+ * Rounding: the kernel's pose arithmetic rounds differently from a point-by-point restatement: a pair within ~FP_AUDIT_GAP_TOL of
+ * touching may be decided either way.
+ * Sampling: pairs exist on the check grid only, so the lag is sampled every cs * tick_t seconds.  That leaves no hole while the ego moves
+ * less than veh_l per grid step - with cs = 2 and tick_t = 0.1 s that is 22 m/s for a 4.5 m car; a faster ego can step over a place an
+ * obstacle held between two samples.
+ *
+ * FP_MEM_DEVICE: one kernel is enqueued (one workgroup per ego, in the order of batch->launch_order when there is one) - no
+ * allocation, no wait; it can be captured directly behind a dense call or another pass in a linear chain.  t_now, ego and the obstacle
+ * table are read when the kernel runs: a replayed graph follows a loop whose state advances on the device (fp_advance).
+ * params->points_max announces the points per trajectory as for every FP_MEM_DEVICE call.  FP_MEM_HOST stages the batch and the tables
+ * through the ctx and waits, like fp_gate_mask.  The result depends neither on launch_order nor on the memory space; two calls on the
+ * same tables give the same bits.
+ * Errors: a NULL mandatory pointer (gap, cost_tbl, flag_tbl, best_idx, best_cost), a negative lag, a lag above FP_MAX_POINTS, first < 1:
+ * FP_EINVAL; nd*nv*nt > FP_MAX_CAND: FP_ELIMIT.
+ * Also read-only in fp_ctx_get_option: "gap_launches" = launches of the kernel on this ctx so far (0 for a caller that never asks).
+ *
+ * Deliberately not done: fp_plan_step does not call it, the FISS entry points do not call it, and fp_shard_call has no slot for it.  A
+ * closed loop enqueues fp_plan_dense -> (other passes) -> fp_gap_mask -> fp_advance (ClosedLoopRunner(rules=("gaps",)) of the Python
+ * package does, eagerly or from a graph). */
+typedef struct {
+    int32_t lag_follow;  /* >= 0 steps: the ego may not be where an obstacle was up to this many steps earlier */
+    int32_t lag_lead;    /* >= 0 steps: an obstacle may not be where the ego was up to this many steps earlier */
+    int32_t first;       /* >= 1: ego points before this one are not checked (>= FP_MAX_POINTS: none is) */
+    int32_t reserved0;
+} fp_time_gap;
+
+int fp_gap_mask(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, const fp_time_gap* gap, const double* cost_tbl,
+                uint32_t* flag_tbl, int32_t* best_idx, double* best_cost, int32_t* n_close, int mem, void* stream);
+
 /* ---- the obstacle margin of chosen plans (added WITHIN ABI 18: detect it by looking the symbol up, e.g. dlsym) ------------
  * fp_rank_feasible hands a behaviour layer K alternatives per ego as an index and a cost.  How close each of them comes to anything,
  * when, and to what, is not in either number: a plan without FP_FLAG_COLLISION may pass 2 cm from a truck or 6 m from it, and it may

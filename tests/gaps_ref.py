@@ -1,0 +1,366 @@
+"""Independent restatement of the time gap to moving obstacles (fp_gap_mask), numpy + the CPU oracle only.
+
+For one ego of a ProblemBatch everything about a candidate comes from the ORACLE - its flag word, its cost (dense_tables), its dumped
+x / y / yaw series and N / M (eval_traj) - and the rule is restated from its definition (include/frenet_gpu.h), pair by pair:
+
+    survivors   candidates without an infeasible bit on entry; the others are not evaluated and keep their words
+    pose set    P = { i = 0, cs, 2 cs, ... : i < min(M, final_time_step - t_now) and 0 <= i + t_now < T_obs };  M < 2: none
+    pairs       (a, r), a, r in P, a >= first, 0 < a - r <= follow (the ego arrives later) or 0 < r - a <= lead (the obstacle does)
+    shapes      the veh_l x veh_w rectangle at x[a], y[a], yaw[a];  the columns valid at row r + t_now, as the rectangle of obs_dims
+                or the column's ring, at that row's pose
+    violation   the closed shapes intersect (oracle.boxes_intersect / box_ring_intersect: touching counts)
+    bit         a violating survivor gets FLAG_COLLISION ORed in; nothing is ever cleared, no other bit touched
+    winner      minimum cost over candidates without an infeasible bit and a non-NaN cost, the LAST one in FOP index order on exact ties
+
+Per survivor it also returns the SLACK: the smallest |signed separating-axis gap| (numpy, the edge normals of both shapes) over all its
+pairs.  The kernel's pose arithmetic rounds differently from the oracle's: a survivor with slack < UNDECIDED_TOL (the project's
+FP_AUDIT_GAP_TOL) may be decided either way and is excluded from exact comparisons; the tests cap how many there may be.  Pairs whose
+centres are more than NEAR metres beyond the two circumradii are neither tested nor part of the slack: they are at least NEAR apart.
+
+ref_loop drives one ego through the closed loop [oracle dense tables -> this rule -> argmin -> tests/advance_ref.py hand-over].
+
+Nothing here calls the library under test."""
+import dataclasses
+from types import SimpleNamespace
+
+import numpy as np
+
+FLAG_COLLISION = 4
+FLAG_INFEASIBLE = 1 | 2 | 4 | 16 | 32 | 64 | 128  # FP_FLAG_CONSTRAINTS | FP_FLAG_COLLISION | FP_FLAG_BOUNDARY
+UNDECIDED_TOL = 1e-9                              # FP_AUDIT_GAP_TOL (include/frenet_gpu.h)
+MAX_UNDECIDED_SHARE = 0.005                       # of the candidates of a test batch
+MAX_EXCLUDED_EGOS = 1                             # per test batch
+NEAR = 0.5                                        # m: pairs further apart than the circumradii + NEAR are not looked at
+X, Y, YAW = 9, 10, 11                             # rows of a [16, stride] dump (FP_ARR_X / _Y / _YAW)
+SEED = 33055                                      # the seed of every test batch (the other rule passes' batches use the same one)
+
+
+def argmin(cost, flags):
+    """`min_cost >= cost`: the last minimum wins; a NaN cost never does (frenet_optimal_planner.py:264-268)."""
+    best_idx, best_cost = -1, np.nan
+    for c in range(len(cost)):
+        if not (int(flags[c]) & FLAG_INFEASIBLE) and cost[c] == cost[c] and (best_idx < 0 or best_cost >= cost[c]):
+            best_idx, best_cost = c, float(cost[c])
+    return best_idx, best_cost
+
+
+def pose_set(M, horizon, t_now, T_obs, cs):
+    """P of the definition: has_collision's own pose set."""
+    if M < 2:
+        return np.zeros(0, dtype=np.int64)
+    i = np.arange(0, max(min(M, horizon), 0), cs, dtype=np.int64)
+    return i[(i + t_now >= 0) & (i + t_now < T_obs)]
+
+
+def _corners(l, w, x, y, yaw):
+    """[..., 4, 2] corners of rectangles, counter-clockwise."""
+    c, s = np.cos(yaw), np.sin(yaw)
+    u = np.array([[0.5, 0.5], [-0.5, 0.5], [-0.5, -0.5], [0.5, -0.5]])
+    lx, ly = u[:, 0] * np.asarray(l)[..., None], u[:, 1] * np.asarray(w)[..., None]
+    return np.stack([np.asarray(x)[..., None] + c[..., None] * lx - s[..., None] * ly, np.asarray(y)[..., None] + s[..., None] * lx + c[..., None] * ly], axis=-1)
+
+
+def sat_gap(pa, pb):
+    """Signed separating-axis gap of two convex counter-clockwise polygons pa [n, 2], pb [m, 2] over the edge normals of both: <= 0 they
+    overlap (by that much along the best axis), > 0 they are separated by at least that much."""
+    best = -np.inf
+    for p, q in ((pa, pb), (pb, pa)):
+        e = np.roll(p, -1, axis=0) - p
+        ln = np.hypot(e[:, 0], e[:, 1])
+        ok = ln > 0
+        n = np.stack([e[ok, 1], -e[ok, 0]], axis=1) / ln[ok, None]  # outward normals
+        # for every edge: the other polygon's lowest point along the normal, from the edge's own line
+        d = (q @ n.T).min(axis=0) - np.einsum("ij,ij->i", p[ok], n)
+        best = max(best, float(d.max()))
+    return best
+
+
+def box_gap(a, b):
+    """sat_gap of rectangles a, b [n, 5] = (l, w, x, y, yaw), all pairs at once: the four edge normals."""
+    dx, dy = b[:, 2] - a[:, 2], b[:, 3] - a[:, 3]
+    ca, sa, cb, sb = np.cos(a[:, 4]), np.sin(a[:, 4]), np.cos(b[:, 4]), np.sin(b[:, 4])
+    C, S = np.abs(ca * cb + sa * sb), np.abs(sa * cb - ca * sb)
+    hla, hwa, hlb, hwb = 0.5 * a[:, 0], 0.5 * a[:, 1], 0.5 * b[:, 0], 0.5 * b[:, 1]
+    g = [np.abs(dx * ca + dy * sa) - (hla + hlb * C + hwb * S), np.abs(dy * ca - dx * sa) - (hwa + hlb * S + hwb * C),
+         np.abs(dx * cb + dy * sb) - (hlb + hla * C + hwa * S), np.abs(dy * cb - dx * sb) - (hwb + hla * S + hwa * C)]
+    return np.max(g, axis=0)
+
+
+def ego_gaps(O, batch, b, follow=None, lead=None, first=None, tables=None):
+    """The rule for ego b.  follow / lead / first default to the batch's gap_follow / gap_lead / gap_first; tables = (cost [C], flags
+    [C]) to mask (default: the oracle's dense tables).  Returns a namespace: cost [C], flags_in [C], flags [C] (bit ORed in), close [C],
+    slack [C], undecided [C], M [C], survivors (on entry), pairs (near pairs tested), best_idx, best_cost (the masked winner), best_in
+    (the winner of flags_in), n_close."""
+    follow = int(batch.gap_follow if follow is None else follow)
+    lead = int(batch.gap_lead if lead is None else lead)
+    first = int(batch.gap_first if first is None else first)
+    prob = O.problems_from_batch(batch, egos=[b])[0]
+    cost, flags_in = prob.dense_tables() if tables is None else (np.asarray(tables[0], dtype=np.float64), np.asarray(tables[1], dtype=np.uint32))
+    Cn, nv, nt, cs = batch.C, batch.nv, batch.nt, int(batch.check_stride)
+    sc, t_now = int(batch.scene_of[b]), int(batch.t_now[b])
+    has_obs = sc >= 0 and batch.n_obs > 0
+    close, slack = np.zeros(Cn, dtype=bool), np.full(Cn, np.inf)
+    Ms = (flags_in >> 20).astype(np.int64)
+    alive = (flags_in & FLAG_INFEASIBLE) == 0
+    n_pairs = 0
+    if has_obs and (follow > 0 or lead > 0):
+        pose, dims = batch.obs_pose[sc], batch.obs_dims[sc]
+        nvert = None if getattr(batch, "obs_nvert", None) is None else batch.obs_nvert[sc]
+        horizon = int(batch.final_time_step[sc]) - t_now
+        r_e = 0.5 * np.hypot(batch.veh_l, batch.veh_w)
+        r_o = 0.5 * np.hypot(dims[:, 0], dims[:, 1])
+        for c in np.nonzero(alive)[0]:
+            iv, it, i_d = c % nv, (c // nv) % nt, c // (nv * nt)
+            r = prob.eval_traj(float(batch.d_samples[i_d]), float(batch.v_samples[b, iv]), float(batch.t_samples[it]), dump=True, stride=256)
+            assert r.M == Ms[c], (b, c, r.M, Ms[c])
+            P = pose_set(r.M, horizon, t_now, batch.T_obs, cs)
+            A = P[P >= first]
+            if not len(A):
+                continue
+            lag = A[:, None] - P[None, :]
+            pair = ((lag > 0) & (lag <= follow)) | ((lag < 0) & (-lag <= lead))  # [na, nr]
+            rows = pose[P + t_now]                                               # [nr, n, 4]
+            ex, ey, eyaw = r.arrays[X, A], r.arrays[Y, A], r.arrays[YAW, A]
+            dist = np.hypot(rows[None, :, :, 0] - ex[:, None, None], rows[None, :, :, 1] - ey[:, None, None])  # [na, nr, n]
+            near = pair[:, :, None] & (rows[None, :, :, 3] != 0.0) & (dist <= r_e + r_o[None, None, :] + NEAR)
+            ia, ir, ij = np.nonzero(near)
+            n_pairs += len(ia)
+            if not len(ia):
+                continue
+            ego_box = np.column_stack([np.full(len(ia), batch.veh_l), np.full(len(ia), batch.veh_w), ex[ia], ey[ia], eyaw[ia]])
+            obs_box = np.column_stack([dims[ij, 0], dims[ij, 1], rows[ir, ij, 0], rows[ir, ij, 1], rows[ir, ij, 2]])
+            is_poly = np.zeros(len(ia), dtype=bool) if nvert is None else nvert[ij] > 0
+            hit = np.zeros(len(ia), dtype=bool)
+            if (~is_poly).any():
+                hit[~is_poly] = O.boxes_intersect_batch(ego_box[~is_poly], obs_box[~is_poly]) > 0
+            if (~is_poly).any():
+                slack[c] = min(slack[c], np.abs(box_gap(ego_box[~is_poly], obs_box[~is_poly])).min())
+            for k in np.nonzero(is_poly)[0]:
+                j = ij[k]
+                res, world = O.box_ring_intersect(ego_box[k], batch.obs_poly[sc, j, :nvert[j]], obs_box[k, 2:5], world=True)
+                hit[k] = bool(res)
+                slack[c] = min(slack[c], abs(sat_gap(_corners(*ego_box[k]), world)))
+            close[c] = hit.any()
+    flags = flags_in | np.where(close, FLAG_COLLISION, 0).astype(np.uint32)
+    bi, bc = argmin(cost, flags)
+    return SimpleNamespace(cost=cost, flags_in=flags_in, flags=flags, close=close, slack=slack, undecided=slack < UNDECIDED_TOL, M=Ms,
+                           survivors=int(alive.sum()), pairs=n_pairs, best_idx=bi, best_cost=bc, best_in=argmin(cost, flags_in)[0], n_close=int(close.sum()))
+
+
+def batch_gaps(O, batch, tables=None, egos=None, **kw):
+    """ego_gaps for the egos asked for (all by default) -> list; tables = (cost [B, C], flags [B, C]) or None."""
+    egos = range(batch.B) if egos is None else egos
+    return [ego_gaps(O, batch, b, tables=None if tables is None else (tables[0][b], tables[1][b]), **kw) for b in egos]
+
+
+def check_caps(refs, what=""):
+    """The caps the tests rely on: at most 0.5 % of the batch's candidates undecided, at most one ego excluded for having one."""
+    total = sum(len(r.slack) for r in refs)
+    und = sum(int(r.undecided.sum()) for r in refs)
+    egos = sum(1 for r in refs if r.undecided.any())
+    assert und <= MAX_UNDECIDED_SHARE * total, (what, und, total)
+    assert egos <= MAX_EXCLUDED_EGOS, (what, egos)
+    return und, egos
+
+
+def close_share(refs):
+    """Violating candidates over all candidates of the batch."""
+    return sum(r.n_close for r in refs) / sum(len(r.slack) for r in refs)
+
+
+# ---------------------------------------------------------------------------
+# the test batches (shared by tests/test_gaps_cpu.py, which checks caps and shares on the reference alone, and tests/test_gpu_gaps.py)
+# ---------------------------------------------------------------------------
+def kernel_constant(name):
+    """`constexpr int <name> = <integer expression>;` of csrc/frenet_gaps.hip: the cases below are built to reach the kernel's paths, so
+    they follow the kernel's own numbers."""
+    import os
+    import re
+
+    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "fiss_plus_planner_amd", "csrc", "frenet_gaps.hip")).read()
+    expr = re.search(r"constexpr int %s = ([0-9 *]+);" % name, src).group(1)
+    value = 1
+    for f in expr.split("*"):
+        value *= int(f)
+    return value
+
+
+CHUNK = kernel_constant("kGapThreads")        # candidates per pass of the kernel's chunk loop
+LDS_BUDGET = kernel_constant("kGapLdsBytes")  # what the launch may spend on stage_ego's layout and the cull table
+POINTS_CAP = 128          # points_cap() at tick_t = 0.1 (FP_FAST_POINTS)
+
+
+def with_gap(batch, follow=20, lead=10, first=2, **kw):
+    return dataclasses.replace(batch, gap_follow=follow, gap_lead=lead, gap_first=first, **kw)
+
+
+def moving_batch(B=5, nd=5, nv=4, nt=3, n_obs=12, T_obs=120, seed=SEED):
+    """The smallest shape that still exercises every loop: 5 egos x 5 x 4 x 3 (C = 60), 12 moving obstacles in lanes, 120 rows,
+    check_stride 2."""
+    from fiss_plus_planner_amd import synth
+
+    return synth.make_batch(B, nd, nv, nt, n_obs, T_obs, True, seed)
+
+
+def lds_plan(batch):
+    """(rows in LDS, cull table in LDS) of a launch on `batch`: launch_gap_mask restated (csrc/frenet_gaps.hip, frenet_ego.h)."""
+    assert batch.tick_t == 0.1
+    cs = int(batch.check_stride)
+    rows = min(-(-POINTS_CAP // cs), -(-batch.T_obs // cs))
+    base = (batch.NX * 9 + batch.n_obs * 4) * 8
+    bound = rows * batch.n_obs * 16
+    full = base + rows * batch.n_obs * 32
+    if base + bound + 8 <= LDS_BUDGET:
+        return full <= LDS_BUDGET - bound - 8, True
+    return full <= LDS_BUDGET, False
+
+
+def _line_ends():
+    b = moving_batch()
+    ego = b.ego.copy()
+    ego[1, 0] = b.knots[1, -1] - 40.0  # within 40 m of the end of its line: fast candidates leave it (M < N)
+    ego[3, 0] = b.knots[3, -1] + 5.0   # past the end: M = 0 for every candidate, nothing is checked
+    return with_gap(b, ego=ego)
+
+
+def _short_table():
+    """The table ends inside the horizon (T_obs = 30 rows, N up to 50) and the scenario one step earlier for two of the scenes."""
+    b = moving_batch(T_obs=30)
+    return with_gap(b, final_time_step=np.array([29, 18, 29, 11, 29], dtype=np.int32))
+
+
+def _table_rows(n_obs, seed):
+    """check_stride 1 and 100 rows: the obstacle rows do not fit LDS and are read from the scene table; some rows without a state."""
+    b = moving_batch(2, 5, 4, 3, n_obs, 100, seed)
+    b.check_stride = 1
+    b.obs_pose[:, 7::9, ::2, 3] = 0.0
+    return with_gap(b)
+
+
+def _polygons():
+    from fiss_plus_planner_amd import synth
+
+    return with_gap(synth.with_random_shapes(moving_batch(), 77, frac=0.7))
+
+
+def lead_batch():
+    """The hand-built lead case: a straight 400 m line, the ego at s = 60 doing 5 m/s in the lane d = 0, and one faster obstacle (8
+    m/s) 16 m behind it in the adjacent lane d = 3, which the lattice's d_samples reach.  A candidate that pulls out to d = 3 has the
+    obstacle run over its place a moment later: with lag_follow = 0 only the lead direction can flag it."""
+    from fiss_plus_planner_amd import synth
+    from fiss_plus_planner_amd.batch import ProblemBatch
+
+    T_obs = 100
+    pts = np.zeros((1, 81, 2))
+    pts[:, :, 0] = np.linspace(0.0, 400.0, 81)
+    knots, coef = synth.build_frames(pts)
+    pose = np.zeros((1, T_obs, 1, 4))
+    pose[0, :, 0, 0] = 44.0 + 8.0 * 0.1 * np.arange(T_obs)
+    pose[0, :, 0, 1] = 3.0
+    pose[0, :, 0, 3] = 1.0
+    return ProblemBatch(d_samples=[0.0, 1.5, 3.0], t_samples=[3.0, 4.0, 5.0], v_samples=[[3.0, 5.0, 7.0]], target_speed=[7.0], ego=[[60.0, 5.0, 0.0, 0.0, 0.0, 0.0]],
+                        frame_of=[0], scene_of=[0], t_now=[0], nx=[81], knots=knots, coef=coef, obs_pose=pose, obs_dims=[[[4.5, 1.8]]],
+                        final_time_step=[T_obs - 1], veh_l=4.5, veh_w=1.8, max_speed=30.0, max_accel=10.0, gap_follow=0, gap_lead=20, gap_first=2)
+
+
+CASES = {
+    "base": lambda: with_gap(moving_batch()),                                           # follow 20, lead 10
+    "f10": lambda: with_gap(moving_batch(), follow=10, lead=10),                        # a shorter gap flags fewer
+    "t_now": lambda: with_gap(moving_batch(), t_now=[3, 17, 40, 8, 25]),                # every ego on its own clock
+    "dense24": lambda: with_gap(moving_batch(n_obs=24), follow=20, lead=20),            # more columns than one split round
+    "lattice567": lambda: with_gap(moving_batch(2, 9, 9, 7)),                           # 63 longitudinal profiles
+    "chunks": lambda: with_gap(moving_batch(2, 11, 9, 9)),                              # C = 891 > CHUNK: two passes of the chunk loop
+    "cull_only": lambda: _table_rows(40, 104),                                          # rows from the scene table, the cull table in LDS
+    "no_lds": lambda: _table_rows(100, 104),                                            # neither fits: no cull table at all
+    "polygons": _polygons,                                                              # convex rings among the columns
+    "short_table": _short_table,                                                        # the table / the scenario end inside the horizon
+    "line_ends": _line_ends,                                                            # M < N and M <= 1
+    "lead": lead_batch,                                                                 # lag_follow = 0: the lead direction alone
+}
+# every case is meant to flag something: the floor on the violating share of its candidates (the follow cases of the base batch flagged
+# 8 .. 23 % when the rule was first restated; the hand-built lead case has 27 candidates)
+SHARE_FLOOR = {name: 0.02 for name in CASES}
+SHARE_FLOOR["lead"] = 1.0 / 27.0
+BASE_CASES = ("base", "t_now")
+_cache = {}
+
+
+def case(O, name):
+    """(batch, refs) of a named test batch; the reference is computed once per process and shared (do not modify it)."""
+    if name not in _cache:
+        batch = CASES[name]()
+        _cache[name] = (batch, batch_gaps(O, batch))
+    return _cache[name]
+
+
+# ---------------------------------------------------------------------------
+# the closed loop on the reference
+# ---------------------------------------------------------------------------
+# the lead obstacle: a rectangle centred at s = LEAD_S0 + LEAD_V t in the ego's lane.  No round numbers: with s = 45 + 4 t and an ego at 9 m/s
+# candidates touch the obstacle's earlier places EXACTLY (0.9 a - 0.4 r = 29.6 has grid solutions), which no two roundings decide alike
+LEAD_S0, LEAD_V, LEAD_L = 45.37, 4.1, 4.5
+LOOP_CYCLES = 60
+LOOP_FOLLOW, LOOP_FIRST = 20, 4
+
+
+def loop_batch(cycles=LOOP_CYCLES):
+    """The closed-loop scenario: one straight 400 m line of 81 knots, d_samples -0.5 / 0 / 0.5 (no way round), t_samples 3 / 5 / 7 s,
+    v_samples 0 / 3 / 6 / 9, the ego at s = 10.31 doing 8.7 m/s, a lead obstacle doing 4.1 m/s from s = 45.37, a table long enough for the run."""
+    from fiss_plus_planner_amd import synth
+    from fiss_plus_planner_amd.batch import ProblemBatch
+
+    T_obs = cycles + 80
+    pts = np.zeros((1, 81, 2))
+    pts[:, :, 0] = np.linspace(0.0, 400.0, 81)
+    knots, coef = synth.build_frames(pts)
+    pose = np.zeros((1, T_obs, 1, 4))
+    pose[0, :, 0, 0] = LEAD_S0 + LEAD_V * 0.1 * np.arange(T_obs)
+    pose[0, :, 0, 3] = 1.0
+    return ProblemBatch(d_samples=[-0.5, 0.0, 0.5], t_samples=[3.0, 5.0, 7.0], v_samples=[[0.0, 3.0, 6.0, 9.0]], target_speed=[9.0],
+                        ego=[[10.31, 8.7, 0.0, 0.0, 0.0, 0.0]], frame_of=[0], scene_of=[0], t_now=[0], nx=[81], knots=knots, coef=coef, obs_pose=pose,
+                        obs_dims=[[[LEAD_L, 1.8]]], final_time_step=[T_obs - 1], veh_l=4.5, veh_w=1.8, max_speed=30.0, max_accel=10.0,
+                        gap_follow=LOOP_FOLLOW, gap_lead=0, gap_first=LOOP_FIRST)
+
+
+def ref_loop(O, batch, b, cycles, gaps=True):
+    """Ego b of `batch` through `cycles` cycles of [dense tables -> the rule -> argmin -> hand-over] on the reference (gaps=False: the
+    lattice's own winner).  -> list of rows, one per cycle driven: t_now (on entry), best_idx, n_close, undecided (any candidate), ego [6]
+    (after the hand-over), done."""
+    import advance_ref
+
+    f = int(batch.frame_of[b])
+    nx = int(batch.nx[f])
+    ego, t_now, done, n_cycles = batch.ego[b].copy(), int(batch.t_now[b]), 0, 0
+    rows = []
+    for _ in range(cycles):
+        if done:
+            break
+        e2 = batch.ego.copy()
+        e2[b] = ego
+        tn = batch.t_now.copy()
+        tn[b] = t_now
+        r = ego_gaps(O, dataclasses.replace(batch, ego=e2, t_now=tn), b, **({} if gaps else dict(follow=0, lead=0)))
+        best = r.best_idx if gaps else r.best_in
+        a = advance_ref.advance(O, tick_t=batch.tick_t, veh_l=batch.veh_l, knots=batch.knots[f, :nx], coef=batch.coef[f][:, :nx], ego=ego, t_now=t_now,
+                                cycles=n_cycles, best_idx=best, d_samples=batch.d_samples, v_samples=batch.v_samples[b], t_samples=batch.t_samples)
+        rows.append(SimpleNamespace(t_now=t_now, best_idx=best, n_close=r.n_close, undecided=bool(r.undecided.any()), ego=a.ego.copy(), done=a.done))
+        ego, t_now, done, n_cycles = a.ego, a.t_now, a.done, a.cycles
+    return rows
+
+
+def bumper_distance(batch, s_after, t_after):
+    """Smallest distance between the ego's front bumper and the lead's rear bumper over the driven states (s [n] at time steps t [n])."""
+    lead_rear = LEAD_S0 + LEAD_V * batch.tick_t * np.asarray(t_after) - 0.5 * LEAD_L
+    return float(np.min(lead_rear - (np.asarray(s_after) + 0.5 * batch.veh_l)))
+
+
+_loops = {}
+
+
+def loop_case(O, cycles=LOOP_CYCLES, gaps=True):
+    """(batch, rows of ego 0) of the scenario; computed once per process and shared (do not modify it)."""
+    key = (cycles, gaps)
+    if key not in _loops:
+        batch = loop_batch(cycles)
+        _loops[key] = (batch, ref_loop(O, batch, 0, cycles, gaps))
+    return _loops[key]
