@@ -4,8 +4,8 @@ PyTorch is plumbing here (device allocations + the stream handle); every array c
 device address.  `DeviceBatch` uploads a ProblemBatch once; `ClosedLoopRunner` enqueues
 [plan -> advance] x cycles on one stream (reference loop: planners/benchmark/planning.py:120-162) and only
 reads back at the end (or per cycle, when a trace is requested).  With rules=(...) the cycle is [plan -> rule passes -> advance]: the
-speed envelope, the gates, the road-boundary check and the time gap to moving obstacles run over the dense call's tables and decide which
-candidate the ego follows.
+speed envelope, the gates, the road-boundary check and the time gap to moving obstacles run over the dense call's tables, in the order of
+rules.TABLE, and decide which candidate the ego follows.
 With record=True the driven trajectory of every ego - what the reference's loop returns as state_list - is written on the device by
 fp_loop_record behind every step and read back once.
 """
@@ -16,15 +16,16 @@ from types import SimpleNamespace
 import numpy as np
 
 from . import _abi
+from . import rules as _rules  # (`rules` is an argument name here)
 from .batch import ProblemBatch
 from .closed_loop import LoopLog
-from .engine import FrenetEngine, _has_time_gap, device_batch, launch_order_hint, make_params
+from .engine import FrenetEngine, device_batch, launch_order_hint, make_params
 
 _NAMES = ("d_samples", "t_samples", "v_samples", "target_speed", "ego", "frame_of", "scene_of", "t_now", "nx", "knots", "coef",
           "obs_pose", "obs_dims", "final_time_step")
 
-RULES = ("envelope", "gates", "boundary")  # the rule passes of ClosedLoopRunner(rules=...), in the order they run
-OBSTACLE_RULES = ("gaps",)  # ... and the passes that do geometry against the obstacle table: behind the others, which leave them fewer survivors
+RULES = tuple(r.name for r in _rules.TABLE if r.arrays)  # the rule passes of ClosedLoopRunner(rules=...) that read arrays of their own, in the order they run
+OBSTACLE_RULES = tuple(r.name for r in _rules.TABLE if not r.arrays)  # ... and the passes that do geometry against the obstacle table instead: behind the others
 
 LOG_POLL_CYCLES = 16  # run(record=True) reads the log's 4-byte count of running egos this often and stops enqueueing at 0
 
@@ -38,14 +39,12 @@ class DeviceBatch:
         self.host = batch
         self.dev = torch.device("cuda", device)
         self.t = {k: torch.from_numpy(np.ascontiguousarray(getattr(batch, k))).to(self.dev) for k in _NAMES}
-        for k in ("samp_min", "samp_max", "samp_res", "obs_poly", "obs_nvert", "bound_left", "bound_right",  # (the corridor: boundary_mask_device)
-                  "speed_limit",  # (the per-segment speed limits: speed_envelope_device)
-                  "track_model", "track_state", "track_frame"):  # (the obstacle tracks: predict)
+        for k in ("samp_min", "samp_max", "samp_res", "obs_poly", "obs_nvert", "track_model", "track_state", "track_frame"):  # (the obstacle tracks: predict)
             if getattr(batch, k, None) is not None:
                 self.t[k] = torch.from_numpy(getattr(batch, k)).to(self.dev)
-        if getattr(batch, "gate_s", None) is not None:  # (the gates: gate_mask_device; the uint32 words travel as their int32 bit patterns)
-            self.t["gate_s"] = torch.from_numpy(batch.gate_s).to(self.dev)
-            self.t["gate_closed"] = torch.from_numpy(batch.gate_closed.view(np.int32)).to(self.dev)
+        for rule in _rules.TABLE:  # what the rule passes the batch carries data for read (the *_device methods, ClosedLoopRunner(rules=...))
+            if rule.carried(batch):
+                self.t.update((k, torch.from_numpy(_rules.array(batch, k)).to(self.dev)) for k in rule.arrays)
         if order_hint and batch.B > 0:
             self.t["launch_order"] = torch.from_numpy(launch_order_hint(batch)).to(self.dev)
         self.params = make_params(batch)
@@ -84,10 +83,9 @@ class ClosedLoopRunner:
     def __init__(self, engine: FrenetEngine, dbatch: DeviceBatch, goal_xy: np.ndarray, planner: str = "FOP", fused: bool = True,
                  goal_poly: np.ndarray | None = None, goal_nv: np.ndarray | None = None, goal_intervals: np.ndarray | None = None,
                  rules=()):
-        """rules: any subset of ("envelope", "gates", "boundary", "gaps") - FOP only, and the batch must carry each rule's data (speed
-        profile / gates / corridor / a time gap with a lag above 0).  The cycle then is fp_plan_dense into the runner's own [B][C] tables,
-        the passes asked for in that order (fp_speed_envelope, fp_gate_mask, fp_boundary_mask, fp_gap_mask), each writing best_idx /
-        best_cost, and fp_advance on the last one's winner;
+        """rules: any subset of the names in rules.TABLE - FOP only, and the batch must carry each rule's data (speed profile / gates /
+        corridor / a time gap with a lag above 0).  The cycle then is fp_plan_dense into the runner's own [B][C] tables, the passes asked
+        for in the table's order, whatever the caller's, each writing best_idx / best_cost, and fp_advance on the last one's winner;
         `fused` has no say.  rules=(): the calls below, unchanged.
         fused: an FOP cycle is ONE launch (fp_plan_step: the workgroup that finds an ego's argmin advances the ego); False = the two
         calls fp_plan_dense + fp_advance (same results; the A/B of tests and bench).
@@ -125,8 +123,8 @@ class ClosedLoopRunner:
             self.cost_tbl = dbatch.empty((B, dbatch.C), f64)
             self.flag_tbl = torch.zeros((B, dbatch.C), dtype=i32, device=dbatch.dev)
             self.n_flagged = {r: torch.zeros(B, dtype=i32, device=dbatch.dev) for r in self.rules}
-            if "envelope" in self.rules and "speed_limit" not in dbatch.t:  # (a lateral bound alone: no limit anywhere)
-                dbatch.t["speed_limit"] = torch.full((dbatch.host.F, dbatch.host.NX), float("inf"), dtype=f64, device=dbatch.dev)
+            addr = lambda k: dbatch.t[k].data_ptr()  # noqa: E731  (the addresses are fixed: every pass' struct is built once)
+            self.passes = [(p, p.struct(dbatch.host, addr), self.n_flagged[p.name].data_ptr()) for p in map(_rules.by_name.get, self.rules)]
         if planner != "FOP":
             self.prev = torch.full((B, 3), -1, dtype=i32, device=dbatch.dev)
             self.ijk = dbatch.empty((B, 3), i32)
@@ -142,40 +140,26 @@ class ClosedLoopRunner:
     @staticmethod
     def _check_rules(rules, planner, batch) -> tuple:
         """The rules in the order they run; ValueError for an unknown rule, a planner that is not FOP, or a rule without its data."""
-        rules = (rules,) if isinstance(rules, str) else tuple(rules)
-        for r in rules:
-            if r not in RULES and r not in OBSTACLE_RULES:
-                raise ValueError(f"ClosedLoopRunner: unknown rule {r!r} (rules are a subset of {RULES + OBSTACLE_RULES})")
-        if rules and planner != "FOP":
+        asked = (rules,) if isinstance(rules, str) else tuple(rules)
+        for r in asked:
+            if r not in _rules.by_name:
+                raise ValueError(f"ClosedLoopRunner: unknown rule {r!r} (rules are a subset of {tuple(_rules.by_name)})")
+        if asked and planner != "FOP":
             raise ValueError(f"ClosedLoopRunner: rules are defined for the FOP planner only ({planner} orders candidates by cost before validation)")
-        has = dict(envelope=getattr(batch, "speed_limit", None) is not None or float(getattr(batch, "max_lat_accel", 0.0) or 0.0) > 0.0,
-                   gates=getattr(batch, "gate_s", None) is not None, boundary=getattr(batch, "bound_left", None) is not None,
-                   gaps=_has_time_gap(batch))
-        for r in rules:
-            if not has[r]:
-                raise ValueError(f"ClosedLoopRunner: rule {r!r} needs data the batch does not carry "
-                                 "(envelope: speed_limit / max_lat_accel, gates: gate_s / gate_closed, boundary: bound_left / bound_right, "
-                                 "gaps: gap_follow / gap_lead)")
-        return tuple(r for r in RULES + OBSTACLE_RULES if r in rules)
+        for r in asked:
+            if not _rules.by_name[r].carried(batch):
+                raise _rules.missing(_rules.by_name[r], f"ClosedLoopRunner(rules={r!r})")
+        return tuple(r for r in _rules.by_name if r in asked)
 
     def _step_rules(self, stream: int):
         """fp_plan_dense -> the rule passes -> fp_advance: a linear chain on `stream`."""
         import ctypes as C
 
-        db, h, eng = self.db, self.db.host, self.eng
+        db, eng = self.db, self.eng
         bi, bc, cost, flags = self.best_idx.data_ptr(), self.best_cost.data_ptr(), self.cost_tbl.data_ptr(), self.flag_tbl.data_ptr()
         eng.plan_dense_device(db.params, self.fb, bi, bc, self.stats.data_ptr(), cost_tbl=cost, flag_tbl=flags, stream=stream)
-        for r in self.rules:
-            n = self.n_flagged[r].data_ptr()
-            if r == "envelope":
-                eng.speed_envelope_device(db.params, self.fb, db.t["speed_limit"].data_ptr(), h.limit_front, h.limit_tol, h.max_lat_accel, cost, flags, bi, bc, n, stream)
-            elif r == "gates":
-                eng.gate_mask_device(db.params, self.fb, db.t["gate_s"].data_ptr(), db.t["gate_closed"].data_ptr(), h.gate_s.shape[1], h.gate_closed.shape[1],
-                                     h.gate_front, h.gate_max_decel, cost, flags, bi, bc, n, stream)
-            elif r == "boundary":
-                eng.boundary_mask_device(db.params, self.fb, db.t["bound_left"].data_ptr(), db.t["bound_right"].data_ptr(), h.bound_margin, cost, flags, bi, bc, n, stream)
-            else:
-                eng.gap_mask_device(db.params, self.fb, h.gap_follow, h.gap_lead, h.gap_first, cost, flags, bi, bc, n, stream)
+        for rule, struct, n in self.passes:
+            eng._table_pass_device(rule, db.params, self.fb, struct, cost, flags, bi, bc, n, stream)
         _abi.check(eng._lib.fp_advance(eng._ctx, C.byref(db.params), C.byref(self.fb), bi, None, C.byref(self.io), _abi.FP_MEM_DEVICE, stream or None))
 
     def step(self, stream: int = 0):

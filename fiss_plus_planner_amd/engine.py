@@ -17,8 +17,9 @@ from types import SimpleNamespace
 
 import numpy as np
 
-from . import _abi
+from . import _abi, rules
 from .batch import ProblemBatch
+from .rules import _time_gap  # (its home is the table of rule passes; callers find it here as before)
 
 TRAJ_STRIDE = _abi.FP_DEFAULT_STRIDE
 
@@ -135,25 +136,6 @@ def fiss_rounds(kind, max_refine_iters: int) -> int:
     return int(max_refine_iters) if kind in ("FISS+", _abi.FP_FISS_PLUS) else 0
 
 
-def _has_time_gap(batch) -> bool:
-    """A batch with both lags 0 carries no time gap."""
-    return int(getattr(batch, "gap_follow", 0) or 0) > 0 or int(getattr(batch, "gap_lead", 0) or 0) > 0
-
-
-def _time_gap(follow, lead, first, who: str) -> "_abi.FpTimeGap":
-    """fp_time_gap of three Python ints; a value outside the struct's range raises here (a ctypes field would wrap it silently)."""
-    follow, lead, first = int(follow), int(lead), int(first)
-    if not (0 <= follow <= _abi.FP_MAX_POINTS and 0 <= lead <= _abi.FP_MAX_POINTS):
-        raise ValueError(f"{who}: follow = {follow} / lead = {lead} outside 0 .. FP_MAX_POINTS ({_abi.FP_MAX_POINTS}) steps")
-    if not 1 <= first <= 2**31 - 1:
-        raise ValueError(f"{who}: first = {first} outside 1 .. INT32_MAX")
-    return _abi.FpTimeGap(follow, lead, first, 0)
-
-
-def _has_speed_profile(batch) -> bool:
-    return getattr(batch, "speed_limit", None) is not None or float(getattr(batch, "max_lat_accel", 0.0) or 0.0) > 0.0
-
-
 def _check_out(out: SimpleNamespace, B: int, spec: dict) -> None:
     """Caller-provided output arrays cross the C ABI as bare addresses: every array the call writes must be a writable,
     C-contiguous array of the dtype and shape [B, ...] the engine would have allocated itself (a strided or wrong-dtype array
@@ -243,14 +225,13 @@ class FrenetEngine:
         margin_obs (traj_margins at the batch's check_stride) of the result - [B] for best_idx, or [top_k, B] for rank_idx together with
         top_k; with boundary=True they are taken on the masked result.  envelope=True (the batch must carry a speed profile:
         speed_limit and / or max_lat_accel): the position-dependent speed limits (speed_envelope) run behind the dense call over its
-        tables, before the boundary check when both are asked for; best_idx / best_cost are the argmin among the candidates that obey the
-        envelope (and the corridor), `flags` carry the added FLAG_SPEED / FLAG_ACCEL bits, also n_limited [B]; top_k, margins and
-        winner=True follow the masked result like with boundary=True.  gates=True (the batch must carry gates: gate_s / gate_closed): the
-        stop lines that open and close (gate_mask) run behind the envelope and before the boundary check; `flags` carry the added
-        FLAG_SPEED bits of the candidates that cross a closed gate, also n_gated [B]; everything else follows the masked result likewise.
-        gaps=True (the batch must carry a time gap: gap_follow / gap_lead > 0): the time gap to moving obstacles (gap_mask) runs last,
-        behind envelope, gates and boundary check, so that fewer survivors reach it; `flags` carry the added FLAG_COLLISION bits, also
-        n_close [B].
+        tables; best_idx / best_cost are the argmin among the candidates that obey the envelope (and the other rules asked for), `flags`
+        carry the added FLAG_SPEED / FLAG_ACCEL bits, also n_limited [B]; top_k, margins and winner=True follow the masked result like
+        with boundary=True.  gates=True (the batch must carry gates: gate_s / gate_closed): the stop lines that open and close
+        (gate_mask); `flags` carry the added FLAG_SPEED bits of the candidates that cross a closed gate, also n_gated [B]; everything
+        else follows the masked result likewise.  gaps=True (the batch must carry a time gap: gap_follow / gap_lead > 0): the time gap
+        to moving obstacles (gap_mask); `flags` carry the added FLAG_COLLISION bits, also n_close [B].  The passes asked for run in the
+        order of rules.TABLE, whatever the order of the keywords: every argmin honours the bits set before it.
         """
         if margins:
             out = self.plan_dense(batch, tables, winner, traj_stride, traj_sparse, out, audit, top_k, boundary, envelope=envelope, gates=gates, gaps=gaps)
@@ -260,66 +241,35 @@ class FrenetEngine:
             else:
                 out.margin_dist, out.margin_step, out.margin_obs = np.empty(plans.shape), np.empty(plans.shape, dtype=np.int32), np.empty(plans.shape, dtype=np.int32)
             return out
-        if boundary or envelope or gates or gaps:
-            if boundary and getattr(batch, "bound_left", None) is None:
-                raise ValueError("plan_dense(boundary=True): the batch carries no corridor (ProblemBatch.bound_left / bound_right)")
-            if envelope and not _has_speed_profile(batch):
-                raise ValueError("plan_dense(envelope=True): the batch carries no speed profile (ProblemBatch.speed_limit / max_lat_accel)")
-            if gates and getattr(batch, "gate_s", None) is None:
-                raise ValueError("plan_dense(gates=True): the batch carries no gates (ProblemBatch.gate_s / gate_closed)")
-            if gaps and not _has_time_gap(batch):
-                raise ValueError("plan_dense(gaps=True): the batch carries no time gap (ProblemBatch.gap_follow / gap_lead)")
-            if audit:
+        if boundary or envelope or gates or gaps or top_k:
+            asked = dict(boundary=boundary, envelope=envelope, gates=gates, gaps=gaps)
+            passes = [r for r in rules.TABLE if asked[r.name]]  # (in the table's order, not the keywords': every argmin honours the bits set before it)
+            for r in passes:
+                if not r.carried(batch):
+                    raise rules.missing(r, f"plan_dense({r.name}=True)")
+            if passes and audit:
                 raise ValueError("plan_dense(boundary / envelope / gates / gaps=True, audit=True): the audit bits describe the dense call's own answer, not the masked one")
-            want_tables = tables
+            if top_k and not 1 <= int(top_k) <= _abi.FP_MAX_RANK:
+                raise ValueError(f"top_k={top_k}: 0 (off) or 1 .. FP_MAX_RANK ({_abi.FP_MAX_RANK})")
+            B, want_tables = batch.B, tables
             if out is not None and not tables:  # the caller's arrays hold no tables: the call brings its own
-                out.cost, out.flags = np.empty((batch.B, batch.C)), np.empty((batch.B, batch.C), dtype=np.uint32)
+                out.cost, out.flags = np.empty((B, batch.C)), np.empty((B, batch.C), dtype=np.uint32)
                 out.__dict__.pop("_res", None)
-            out = self.plan_dense(batch, True, winner, traj_stride, traj_sparse, out)
-            if batch.B:
-                if envelope:  # (first: the boundary check's argmin then honours its bits)
-                    _, bi, bc, out.n_limited = self.speed_envelope(batch, out.cost, out.flags, inplace=True)
-                if gates:  # (behind the envelope, ahead of the boundary check: every argmin honours the bits set before it)
-                    _, bi, bc, out.n_gated = self.gate_mask(batch, out.cost, out.flags, inplace=True)
-                if boundary:
-                    _, bi, bc, out.n_masked = self.boundary_mask(batch, out.cost, out.flags, inplace=True)
-                if gaps:  # (last: the geometry is paid only for the candidates the cheaper rules left)
-                    _, bi, bc, out.n_close = self.gap_mask(batch, out.cost, out.flags, inplace=True)
-                out.best_idx[...], out.best_cost[...] = bi, bc
+            out = self.plan_dense(batch, True, winner, traj_stride, traj_sparse, out, audit)
+            for r in passes:
+                if B:
+                    _, bi, bc, n = self._table_pass(r, batch, out.cost, out.flags, None, True)
+                else:
+                    n = np.empty(0, dtype=np.int32)
+                setattr(out, r.count, n)
+            if passes and B:
+                out.best_idx[...], out.best_cost[...] = bi, bc  # (the last pass' argmin)
                 if winner:
                     w = self.winner_trajs(batch, out.best_idx, traj_stride, traj_sparse)
                     out.best_flags[...], out.best_traj[...] = w.best_flags, w.best_traj
-            else:
-                if envelope:
-                    out.n_limited = np.empty(0, dtype=np.int32)
-                if gates:
-                    out.n_gated = np.empty(0, dtype=np.int32)
-                if boundary:
-                    out.n_masked = np.empty(0, dtype=np.int32)
-                if gaps:
-                    out.n_close = np.empty(0, dtype=np.int32)
-            if top_k:
-                if not 1 <= int(top_k) <= _abi.FP_MAX_RANK:
-                    raise ValueError(f"top_k={top_k}: 0 (off) or 1 .. FP_MAX_RANK ({_abi.FP_MAX_RANK})")
-                if batch.B:
-                    out.rank_idx, out.rank_cost, out.n_feasible = self.rank_feasible(batch, out.cost, out.flags, int(top_k))
-                else:
-                    out.rank_idx, out.rank_cost, out.n_feasible = np.empty((int(top_k), 0), dtype=np.int32), np.empty((int(top_k), 0)), np.empty(0, dtype=np.int32)
-            if not want_tables:
-                out.cost = out.flags = None
-                out.__dict__.pop("_res", None)
-            return out
-        if top_k:
-            if not 1 <= int(top_k) <= _abi.FP_MAX_RANK:
-                raise ValueError(f"top_k={top_k}: 0 (off) or 1 .. FP_MAX_RANK ({_abi.FP_MAX_RANK})")
-            want_tables = tables
-            if out is not None and not tables:  # the caller's arrays hold no tables: the call brings its own
-                out.cost, out.flags = np.empty((batch.B, batch.C)), np.empty((batch.B, batch.C), dtype=np.uint32)
-                out.__dict__.pop("_res", None)
-            out = self.plan_dense(batch, True, winner, traj_stride, traj_sparse, out, audit)
-            if batch.B:
+            if top_k and B:
                 out.rank_idx, out.rank_cost, out.n_feasible = self.rank_feasible(batch, out.cost, out.flags, int(top_k))
-            else:
+            elif top_k:
                 out.rank_idx, out.rank_cost, out.n_feasible = np.empty((int(top_k), 0), dtype=np.int32), np.empty((int(top_k), 0)), np.empty(0, dtype=np.int32)
             if not want_tables:
                 out.cost = out.flags = None
@@ -378,30 +328,48 @@ class FrenetEngine:
         _abi.check(self._lib.fp_rank_feasible(self._ctx, C.byref(params), C.byref(fb), cost_tbl or None, flag_tbl or None, int(k), rank_idx or None,
                                               rank_cost or None, n_feasible or None, _abi.FP_MEM_DEVICE, stream or None))
 
+    def _table_pass(self, rule: rules.Rule, batch: ProblemBatch, cost, flags, skip, inplace: bool, struct=None):
+        """One rule pass over host tables -> (flags, best_idx, best_cost, count).  struct None = the rule's own, from the batch, which must
+        carry the rule's data then."""
+        held = {}
+
+        def addr(name):
+            held[name] = rules.array(batch, name)  # (kept alive over the call)
+            return _ptr(held[name])
+
+        if struct is None:
+            if not rule.carried(batch):
+                raise rules.missing(rule, rule.fn)
+            struct = rule.struct(batch, addr)
+        B, Cn = batch.B, batch.C
+        cost = np.ascontiguousarray(cost, dtype=np.float64)
+        if not (inplace and isinstance(flags, np.ndarray) and flags.dtype == np.uint32 and flags.flags.c_contiguous and flags.flags.writeable):
+            flags = np.array(flags, dtype=np.uint32, order="C", copy=True)
+        if cost.shape != (B, Cn) or flags.shape != (B, Cn):
+            raise ValueError(f"{rule.fn}: cost / flags must be [B={B}, C={Cn}] tables, got {cost.shape} / {flags.shape}")
+        best_idx = np.empty(B, dtype=np.int32); best_cost = np.empty(B); count = np.empty(B, dtype=np.int32)
+        p, fb = host_structs(batch)
+        if skip is not None:
+            skip = np.ascontiguousarray(skip, dtype=np.int32)
+            assert skip.shape == (B,)
+            fb.skip = _ptr(skip)
+        _abi.check(getattr(self._lib, rule.fn)(self._ctx, C.byref(p), C.byref(fb), C.byref(struct), _ptr(cost), _ptr(flags), _ptr(best_idx), _ptr(best_cost),
+                                               _ptr(count), _abi.FP_MEM_HOST, None))
+        return flags, best_idx, best_cost, count
+
+    def _table_pass_device(self, rule: rules.Rule, params: _abi.FpParams, fb: _abi.FpBatch, struct, cost_tbl: int, flag_tbl: int, best_idx: int,
+                           best_cost: int, count: int, stream: int):
+        """Enqueue one rule pass over device tables (addresses; count or 0)."""
+        _abi.check(getattr(self._lib, rule.fn)(self._ctx, C.byref(params), C.byref(fb), C.byref(struct), cost_tbl or None, flag_tbl or None, best_idx or None,
+                                               best_cost or None, count or None, _abi.FP_MEM_DEVICE, stream or None))
+
     def boundary_mask(self, batch: ProblemBatch, cost: np.ndarray, flags: np.ndarray, skip: np.ndarray | None = None, inplace: bool = False):
         """The road-boundary check over plan_dense's tables (fp_boundary_mask; the definition: include/frenet_gpu.h): cost [B,C],
         flags [B,C] and the batch's corridor (bound_left / bound_right [F,NX], bound_margin) -> (flags, best_idx, best_cost, n_masked):
         the flag words with FLAG_BOUNDARY written (a copy, unless inplace=True and `flags` is a contiguous uint32 array), the argmin
         among the candidates without a FLAG_INFEASIBLE bit - which includes FLAG_BOUNDARY - and the number of candidates per ego that
         carry the bit.  skip [B] (optional): egos whose rows are neither read nor written (-1 / NaN / 0)."""
-        if getattr(batch, "bound_left", None) is None:
-            raise ValueError("boundary_mask: the batch carries no corridor (ProblemBatch.bound_left / bound_right)")
-        B, Cn = batch.B, batch.C
-        cost = np.ascontiguousarray(cost, dtype=np.float64)
-        if not (inplace and isinstance(flags, np.ndarray) and flags.dtype == np.uint32 and flags.flags.c_contiguous and flags.flags.writeable):
-            flags = np.array(flags, dtype=np.uint32, order="C", copy=True)
-        if cost.shape != (B, Cn) or flags.shape != (B, Cn):
-            raise ValueError(f"boundary_mask: cost / flags must be [B={B}, C={Cn}] tables, got {cost.shape} / {flags.shape}")
-        best_idx = np.empty(B, dtype=np.int32); best_cost = np.empty(B); n_masked = np.empty(B, dtype=np.int32)
-        p, fb = host_structs(batch)
-        if skip is not None:
-            skip = np.ascontiguousarray(skip, dtype=np.int32)
-            assert skip.shape == (B,)
-            fb.skip = _ptr(skip)
-        cor = _abi.FpCorridor(_ptr(batch.bound_left), _ptr(batch.bound_right), float(batch.bound_margin))
-        _abi.check(self._lib.fp_boundary_mask(self._ctx, C.byref(p), C.byref(fb), C.byref(cor), _ptr(cost), _ptr(flags), _ptr(best_idx), _ptr(best_cost),
-                                              _ptr(n_masked), _abi.FP_MEM_HOST, None))
-        return flags, best_idx, best_cost, n_masked
+        return self._table_pass(rules.by_name["boundary"], batch, cost, flags, skip, inplace)
 
     def boundary_mask_device(self, params: _abi.FpParams, fb: _abi.FpBatch, left: int, right: int, margin: float, cost_tbl: int, flag_tbl: int,
                              best_idx: int, best_cost: int, n_masked: int = 0, stream: int = 0):
@@ -409,8 +377,7 @@ class FrenetEngine:
         flag_tbl [B][C] (flag_tbl in/out), best_idx / best_cost [B] out, n_masked [B] or 0.  best_idx is a valid argument of
         winner_trajs_device / fp_advance as it stands."""
         cor = _abi.FpCorridor(left or None, right or None, float(margin))
-        _abi.check(self._lib.fp_boundary_mask(self._ctx, C.byref(params), C.byref(fb), C.byref(cor), cost_tbl or None, flag_tbl or None, best_idx or None,
-                                              best_cost or None, n_masked or None, _abi.FP_MEM_DEVICE, stream or None))
+        self._table_pass_device(rules.by_name["boundary"], params, fb, cor, cost_tbl, flag_tbl, best_idx, best_cost, n_masked, stream)
 
     def speed_envelope(self, batch: ProblemBatch, cost: np.ndarray, flags: np.ndarray, skip: np.ndarray | None = None, inplace: bool = False):
         """Position-dependent speed limits and stop lines over plan_dense's tables (fp_speed_envelope; the definition:
@@ -419,25 +386,7 @@ class FrenetEngine:
         ORed in where a checked point violates (a copy, unless inplace=True and `flags` is a contiguous uint32 array; no bit is ever
         cleared), the argmin among the candidates without a FLAG_INFEASIBLE bit, and the number of candidates per ego that violate in
         this call.  skip [B] (optional): egos whose rows are neither read nor written (-1 / NaN / 0)."""
-        if not _has_speed_profile(batch):
-            raise ValueError("speed_envelope: the batch carries no speed profile (ProblemBatch.speed_limit / max_lat_accel)")
-        B, Cn = batch.B, batch.C
-        cost = np.ascontiguousarray(cost, dtype=np.float64)
-        if not (inplace and isinstance(flags, np.ndarray) and flags.dtype == np.uint32 and flags.flags.c_contiguous and flags.flags.writeable):
-            flags = np.array(flags, dtype=np.uint32, order="C", copy=True)
-        if cost.shape != (B, Cn) or flags.shape != (B, Cn):
-            raise ValueError(f"speed_envelope: cost / flags must be [B={B}, C={Cn}] tables, got {cost.shape} / {flags.shape}")
-        best_idx = np.empty(B, dtype=np.int32); best_cost = np.empty(B); n_limited = np.empty(B, dtype=np.int32)
-        p, fb = host_structs(batch)
-        if skip is not None:
-            skip = np.ascontiguousarray(skip, dtype=np.int32)
-            assert skip.shape == (B,)
-            fb.skip = _ptr(skip)
-        limit = batch.speed_limit if batch.speed_limit is not None else np.full((batch.F, batch.NX), np.inf)
-        prof = _abi.FpSpeedProfile(_ptr(limit), float(batch.limit_front), float(batch.limit_tol), float(batch.max_lat_accel))
-        _abi.check(self._lib.fp_speed_envelope(self._ctx, C.byref(p), C.byref(fb), C.byref(prof), _ptr(cost), _ptr(flags), _ptr(best_idx), _ptr(best_cost),
-                                               _ptr(n_limited), _abi.FP_MEM_HOST, None))
-        return flags, best_idx, best_cost, n_limited
+        return self._table_pass(rules.by_name["envelope"], batch, cost, flags, skip, inplace)
 
     def speed_envelope_device(self, params: _abi.FpParams, fb: _abi.FpBatch, v_limit: int, front: float, tol: float, max_lat_accel: float,
                               cost_tbl: int, flag_tbl: int, best_idx: int, best_cost: int, n_limited: int = 0, stream: int = 0):
@@ -445,8 +394,7 @@ class FrenetEngine:
         [B][C] (flag_tbl in/out), best_idx / best_cost [B] out, n_limited [B] or 0.  best_idx is a valid argument of
         winner_trajs_device / fp_advance as it stands, the tables of boundary_mask_device / rank_feasible_device."""
         prof = _abi.FpSpeedProfile(v_limit or None, float(front), float(tol), float(max_lat_accel))
-        _abi.check(self._lib.fp_speed_envelope(self._ctx, C.byref(params), C.byref(fb), C.byref(prof), cost_tbl or None, flag_tbl or None, best_idx or None,
-                                               best_cost or None, n_limited or None, _abi.FP_MEM_DEVICE, stream or None))
+        self._table_pass_device(rules.by_name["envelope"], params, fb, prof, cost_tbl, flag_tbl, best_idx, best_cost, n_limited, stream)
 
     def gate_mask(self, batch: ProblemBatch, cost: np.ndarray, flags: np.ndarray, skip: np.ndarray | None = None, inplace: bool = False):
         """Stop lines that open and close over plan_dense's tables (fp_gate_mask; the definition: include/frenet_gpu.h): cost [B,C],
@@ -455,25 +403,7 @@ class FrenetEngine:
         is closed at that step (a copy, unless inplace=True and `flags` is a contiguous uint32 array; no bit is ever cleared), the argmin
         among the candidates without a FLAG_INFEASIBLE bit, and the number of candidates per ego that violate in this call.  The step is
         batch.t_now[b] + the point's index.  skip [B] (optional): egos whose rows are neither read nor written (-1 / NaN / 0)."""
-        if getattr(batch, "gate_s", None) is None:
-            raise ValueError("gate_mask: the batch carries no gates (ProblemBatch.gate_s / gate_closed)")
-        B, Cn = batch.B, batch.C
-        cost = np.ascontiguousarray(cost, dtype=np.float64)
-        if not (inplace and isinstance(flags, np.ndarray) and flags.dtype == np.uint32 and flags.flags.c_contiguous and flags.flags.writeable):
-            flags = np.array(flags, dtype=np.uint32, order="C", copy=True)
-        if cost.shape != (B, Cn) or flags.shape != (B, Cn):
-            raise ValueError(f"gate_mask: cost / flags must be [B={B}, C={Cn}] tables, got {cost.shape} / {flags.shape}")
-        best_idx = np.empty(B, dtype=np.int32); best_cost = np.empty(B); n_gated = np.empty(B, dtype=np.int32)
-        p, fb = host_structs(batch)
-        if skip is not None:
-            skip = np.ascontiguousarray(skip, dtype=np.int32)
-            assert skip.shape == (B,)
-            fb.skip = _ptr(skip)
-        g = _abi.FpGates(_ptr(batch.gate_s), _ptr(batch.gate_closed), int(batch.gate_s.shape[1]), int(batch.gate_closed.shape[1]), float(batch.gate_front),
-                         float(batch.gate_max_decel))
-        _abi.check(self._lib.fp_gate_mask(self._ctx, C.byref(p), C.byref(fb), C.byref(g), _ptr(cost), _ptr(flags), _ptr(best_idx), _ptr(best_cost),
-                                          _ptr(n_gated), _abi.FP_MEM_HOST, None))
-        return flags, best_idx, best_cost, n_gated
+        return self._table_pass(rules.by_name["gates"], batch, cost, flags, skip, inplace)
 
     def gate_mask_device(self, params: _abi.FpParams, fb: _abi.FpBatch, gate_s: int, closed: int, gate_stride: int, T_gate: int, front: float,
                          max_decel: float, cost_tbl: int, flag_tbl: int, best_idx: int, best_cost: int, n_gated: int = 0, stream: int = 0):
@@ -482,8 +412,7 @@ class FrenetEngine:
         the kernel runs.  best_idx is a valid argument of winner_trajs_device / fp_advance as it stands, the tables of
         speed_envelope_device / boundary_mask_device / rank_feasible_device."""
         g = _abi.FpGates(gate_s or None, closed or None, int(gate_stride), int(T_gate), float(front), float(max_decel))
-        _abi.check(self._lib.fp_gate_mask(self._ctx, C.byref(params), C.byref(fb), C.byref(g), cost_tbl or None, flag_tbl or None, best_idx or None,
-                                          best_cost or None, n_gated or None, _abi.FP_MEM_DEVICE, stream or None))
+        self._table_pass_device(rules.by_name["gates"], params, fb, g, cost_tbl, flag_tbl, best_idx, best_cost, n_gated, stream)
 
     def gap_mask(self, batch: ProblemBatch, cost: np.ndarray, flags: np.ndarray, skip: np.ndarray | None = None, inplace: bool = False,
                  follow: int | None = None, lead: int | None = None, first: int | None = None):
@@ -496,23 +425,9 @@ class FrenetEngine:
         `first` beyond every pose (any value up to INT32_MAX); lags outside 0 .. FP_MAX_POINTS or a `first` outside 1 .. INT32_MAX raise
         ValueError.
         skip [B] (optional): egos whose rows are neither read nor written (-1 / NaN / 0)."""
-        B, Cn = batch.B, batch.C
-        cost = np.ascontiguousarray(cost, dtype=np.float64)
-        if not (inplace and isinstance(flags, np.ndarray) and flags.dtype == np.uint32 and flags.flags.c_contiguous and flags.flags.writeable):
-            flags = np.array(flags, dtype=np.uint32, order="C", copy=True)
-        if cost.shape != (B, Cn) or flags.shape != (B, Cn):
-            raise ValueError(f"gap_mask: cost / flags must be [B={B}, C={Cn}] tables, got {cost.shape} / {flags.shape}")
-        best_idx = np.empty(B, dtype=np.int32); best_cost = np.empty(B); n_close = np.empty(B, dtype=np.int32)
-        p, fb = host_structs(batch)
-        if skip is not None:
-            skip = np.ascontiguousarray(skip, dtype=np.int32)
-            assert skip.shape == (B,)
-            fb.skip = _ptr(skip)
         g = _time_gap(batch.gap_follow if follow is None else follow, batch.gap_lead if lead is None else lead,
-                      batch.gap_first if first is None else first, "gap_mask")
-        _abi.check(self._lib.fp_gap_mask(self._ctx, C.byref(p), C.byref(fb), C.byref(g), _ptr(cost), _ptr(flags), _ptr(best_idx), _ptr(best_cost),
-                                         _ptr(n_close), _abi.FP_MEM_HOST, None))
-        return flags, best_idx, best_cost, n_close
+                      batch.gap_first if first is None else first, "gap_mask")  # (its own struct: no test for a gap on the batch, both lags 0 flag nothing)
+        return self._table_pass(rules.by_name["gaps"], batch, cost, flags, skip, inplace, g)
 
     def gap_mask_device(self, params: _abi.FpParams, fb: _abi.FpBatch, follow: int, lead: int, first: int, cost_tbl: int, flag_tbl: int,
                         best_idx: int, best_cost: int, n_close: int = 0, stream: int = 0):
@@ -520,8 +435,7 @@ class FrenetEngine:
         [B][C] (flag_tbl in/out), best_idx / best_cost [B] out, n_close [B] or 0.  t_now, ego and the obstacle table are read when the
         kernel runs.  best_idx is a valid argument of winner_trajs_device / fp_advance as it stands."""
         g = _time_gap(follow, lead, first, "gap_mask_device")
-        _abi.check(self._lib.fp_gap_mask(self._ctx, C.byref(params), C.byref(fb), C.byref(g), cost_tbl or None, flag_tbl or None, best_idx or None,
-                                         best_cost or None, n_close or None, _abi.FP_MEM_DEVICE, stream or None))
+        self._table_pass_device(rules.by_name["gaps"], params, fb, g, cost_tbl, flag_tbl, best_idx, best_cost, n_close, stream)
 
     def traj_margins(self, batch: ProblemBatch, best_idx: np.ndarray | None = None, end_state: np.ndarray | None = None, pose_stride: int | None = None,
                      skip: np.ndarray | None = None):

@@ -17,7 +17,7 @@ import time
 
 import numpy as np
 
-from . import _abi, search
+from . import _abi, rules, search
 from .batch import FISS_KINDS, ProblemBatch
 from .engine import TRAJ_STRIDE, FrenetEngine, host_structs, unpack_flags
 from .frenet import FrenetState, FrenetTrajectory
@@ -411,9 +411,10 @@ class FrenetOptimalPlanner:
         if reuse is None:
             reuse = outs[key] = self._engine.dense_outputs(1, batch.C, True, winner, stride)
         # (a corridor / a speed profile / gates / a time gap on the batch: the checks run behind the dense call and decide the winner)
-        out = self._engine.plan_dense(batch, tables=True, winner=winner, traj_stride=stride, out=reuse, boundary=batch.bound_left is not None,
-                                      envelope=batch.speed_limit is not None or batch.max_lat_accel > 0, gates=batch.gate_s is not None,
-                                      gaps=batch.gap_follow > 0 or batch.gap_lead > 0)
+        on = batch.__dict__.get("_rules_on")
+        if on is None:  # asked once per batch: the planner builds a new batch whenever a rule's data changes, and the answers cost a microsecond of the cycle
+            on = batch.__dict__["_rules_on"] = {r.name: r.carried(batch) for r in rules.TABLE}
+        out = self._engine.plan_dense(batch, tables=True, winner=winner, traj_stride=stride, out=reuse, **on)
         self.last_tables = (out.cost[0].copy(), out.flags[0].copy())
         if self.materialize_all:  # visualisation payload (reference :102): every candidate's series in one launch
             m = self._engine.materialize_all(batch, traj_stride=stride)

@@ -253,6 +253,50 @@ def test_plan_dense_with_gaps_is_the_chain_of_calls(engine, oracle):
         engine.plan_dense(batch, gaps=True, audit=True)
 
 
+RULES_ON = dict(envelope=True, gates=True, boundary=True, gaps=True)
+COUNTS = ("n_limited", "n_gated", "n_masked", "n_close")
+
+
+def test_plan_dense_every_rule_into_the_callers_arrays_without_tables(engine):
+    """The caller's arrays hold no tables: the call brings its own, twice into the same arrays, and leaves nothing of them behind."""
+    every = full_batch()
+    want = engine.plan_dense(every, tables=True, top_k=3, **RULES_ON)
+    out = engine.dense_outputs(every.B, every.C, tables=False)
+    for call in range(2):
+        got = engine.plan_dense(every, tables=False, out=out, top_k=3, **RULES_ON)
+        assert got is out and got.cost is None and got.flags is None, call
+        assert np.array_equal(got.best_idx, want.best_idx) and same_bits(got.best_cost, want.best_cost), call
+        for name in COUNTS:
+            assert np.array_equal(getattr(got, name), getattr(want, name)) and getattr(got, name).dtype == np.int32, (call, name)
+        assert np.array_equal(got.rank_idx, want.rank_idx) and same_bits(got.rank_cost, want.rank_cost) and np.array_equal(got.n_feasible, want.n_feasible), call
+    assert want.n_close.sum() > 0  # (the passes have work on this batch)
+    plain, fresh = engine.plan_dense(every, tables=False, out=out), engine.plan_dense(every, tables=False)
+    assert plain.cost is None and np.array_equal(plain.best_idx, fresh.best_idx) and same_bits(plain.best_cost, fresh.best_cost)  # the unmasked winner: no stale fp_result
+
+
+def test_plan_dense_every_rule_on_a_batch_without_egos(engine):
+    every = full_batch()
+    none = dataclasses.replace(every, v_samples=every.v_samples[:0], target_speed=every.target_speed[:0], ego=every.ego[:0], frame_of=every.frame_of[:0],
+                               scene_of=every.scene_of[:0], t_now=every.t_now[:0])  # (frames, scenes and the rules' data stay)
+    assert none.B == 0 and none.F == every.F and none.S == every.S and none.gate_s is every.gate_s
+    out = engine.plan_dense(none, top_k=3, margins=True, **RULES_ON)
+    for name in COUNTS:
+        assert getattr(out, name).shape == (0,) and getattr(out, name).dtype == np.int32, name
+    assert out.rank_idx.shape == (3, 0) and out.rank_cost.shape == (3, 0) and out.n_feasible.shape == (0,)
+    assert out.margin_dist.shape == (3, 0) and out.margin_step.shape == (3, 0) and out.margin_obs.shape == (3, 0)
+    assert out.best_idx.shape == (0,)
+
+
+def test_plan_dense_audit_goes_with_top_k_and_with_no_rule(engine):
+    every = full_batch()
+    out = engine.plan_dense(every, audit=True, top_k=3)
+    assert out.audit.shape == (every.B,) and out.audit.dtype == np.uint32 and out.rank_idx.shape == (3, every.B)
+    assert np.array_equal(out.rank_idx[0], out.best_idx)
+    for name in RULES_ON:
+        with pytest.raises(ValueError):
+            engine.plan_dense(every, audit=True, top_k=3, **{name: True})
+
+
 def test_a_ctx_that_never_asks_pays_nothing(oracle):
     batch, refs = R.case(oracle, "base")
     with FrenetEngine(0) as other:
