@@ -175,7 +175,7 @@ struct fp_ctx {
     int zero_copy_in = 0;          // fp_ctx_set_option("zero_copy_in"): FP_MEM_HOST calls of a handful of egos read inputs from pinned host memory: 0 never (default: even a few hundred bytes read over the link cost every kernel of the call a round trip - measured slower than the copy kernel), 1 the per-ego arrays of a call whose tables are cached (tables_tag), 2 everything
     int lattice_occupancy = 0;     // fp_ctx_set_option("lattice_occupancy"): 0 auto, 2 / 3: at most that many lattice workgroups per CU
     int lattice_tail = 0;          // fp_ctx_set_option("lattice_tail"): 0 auto, 1 never, n >= 2: the last n dispatch slots of a multi-round launch are cut in two workgroups
-    int lattice_group = 0;         // fp_ctx_set_option("lattice_group"): 0 auto, 1 never, n >= 2: up to n slices per barrier interval
+    int lattice_group = 0;         // fp_ctx_set_option("lattice_group"): 0 auto, 1 never, n >= 2: the 1024-thread (grouped) instances where they fit
     int refine_table_kb = 96;      // fp_ctx_set_option("refine_table_kb")
     int fiss_stages = 3;           // fp_ctx_set_option("fiss_stages"): timing diagnostic, 3 = the whole pipeline
     int fiss_jump = 1;             // fp_ctx_set_option("fiss_jump"): FISS+ walk skips ahead to the first feasible sample's level
@@ -694,11 +694,11 @@ int lattice_split_for(fp_ctx* ctx, const fp_params* p, const fp_batch* b, hipStr
     } else if (ctx->lattice_split == 1) {
         parts_per_ego = 1;
     }
-    // Grouped slices (launch_lattice_fused, `group`): when the batch leaves room for no more than TWO workgroups per ego but every
-    // ego can have a CU to itself, one 1024-thread workgroup per ego takes all its slices at once - four barrier intervals
-    // instead of 4 nt, one prologue instead of two, no ticket and no merge.  Measured on MI355X (BASELINE configs[1], 5 x 5 x 5,
-    // 10 obstacles): 256 egos 36.3 us against 37.9 split in two; 128 egos (split in four) 34.5 against 31.3 - so only in that
-    // regime.  Needs the whole lattice's per-slice tables in one workgroup's LDS.
+    // Grouped instances (launch_lattice_fused, `group`): when the batch leaves room for no more than TWO workgroups per ego but every
+    // ego can have a CU to itself, one 1024-thread workgroup per ego takes all its slices - twice the wavefronts on its lon
+    // profiles, one prologue instead of two, no ticket and no merge.  Measured on MI355X (BASELINE configs[1], 5 x 5 x 5,
+    // 10 obstacles; with the kernel organisation of the time): 256 egos 36.3 us against 37.9 split in two; 128 egos (split in
+    // four) 34.5 against 31.3 - so only in that regime.  Needs lattice_group_fit to grant all nt slices.
     const bool obstacles = b->S > 0 && b->n_obs > 0;
     if (ctx->lattice_group >= 2) {
         *group = ctx->lattice_group;
@@ -1081,7 +1081,7 @@ extern "C" {
 int fp_abi_version(void) { return FP_ABI_VERSION; }
 
 // The diagnostic macros this library was compiled with: "" for a production build.  The timing ablations (FP_ABL_*: results are
-// WRONG by design), the instance switches (FP_NO_*, FP_SLICE_LOOP, ...) and the stamp / counter builds (FP_PHASE_STAMPS, FP_COUNTERS,
+// WRONG by design), the instance switches (FP_NO_*, ...) and the stamp / counter builds (FP_PHASE_STAMPS, FP_COUNTERS,
 // FP_TL: series blocks carry clock ticks) all live in the production sources behind #if and build into the same file name under the same
 // ABI version; this is how a caller tells them apart.  Two sources: the Makefile's EXTRA verbatim, and - however the macro got onto the
 // command line - the list below.
@@ -1145,17 +1145,11 @@ const char* fp_build_flags(void)
 #if defined(FP_ABL_NO_SPLINE_COPY)
         FP_FLAG_IF(FP_ABL_NO_SPLINE_COPY)
 #endif
-#if defined(FP_ABL_NO_SLICE_SYNC)
-        FP_FLAG_IF(FP_ABL_NO_SLICE_SYNC)
-#endif
 #if defined(FP_ABL_NO_SCAN)
         FP_FLAG_IF(FP_ABL_NO_SCAN)
 #endif
 #if defined(FP_ABL_NO_DALL)
         FP_FLAG_IF(FP_ABL_NO_DALL)
-#endif
-#if defined(FP_SLICE_LOOP)
-        FP_FLAG_IF(FP_SLICE_LOOP)
 #endif
 #if defined(FP_NO_SHAPES)
         FP_FLAG_IF(FP_NO_SHAPES)

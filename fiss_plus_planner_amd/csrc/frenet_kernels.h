@@ -142,7 +142,7 @@ struct LatticeRequest {
     int nsplit = 1;
     const int* perm = nullptr;     // (nsplit == 1) workgroup i works on ego perm[i]: the launch order
     int* dur = nullptr;            // every workgroup leaves its ego's duration there (10 ns ticks)
-    int group = 1;                 // time-horizon slices per barrier interval, as far as lattice_group_fit allows (<= 1: one)
+    int group = 1;                 // "lattice_group", granted up to lattice_group_fit; above 1: a grouped instance (1024-thread workgroups)
     int tail = 0;                  // (needs part_scratch) cut the last `tail` slots of a multi-round launch in two; < 0: auto for -tail CUs
     const InlineIn* inl = nullptr;  // inline inputs: the fused kernel or nothing
     const FissTail* ft = nullptr;   // the FISS+ search in workgroups appended to the launch (three- / four-per-CU launches)

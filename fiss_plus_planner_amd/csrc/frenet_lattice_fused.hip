@@ -16,15 +16,14 @@
 // ALL slices (a polynomial evaluation each) becomes a circle - centre on the line at the middle of the range, radius = half the
 // range x an upper bound of the spline's parametric speed + ego reach + a closed-form bound of the lateral offsets - and one lane
 // per (row, obstacle) item tests the obstacle against it: ~7 % survive, and only their orientations are turned into (cos, sin).
-// Per time-horizon slice i_T (all candidates that share T):
-//   phase A  one lane per (profile, time point) the collision horizon can touch: spline frames and lateral offsets -> LDS, fan
-//            bounds by LDS atomic max
-//   prep     one lane per (pose row, lon profile): the fan's half-width along the reference normal
-//   B        one lane per (surviving item, lon profile): circle fattened by the largest lateral offset of the slice, separating
-//            axes along the reference normal and tangent
+// Per lon profile (T, v) - the WALK: one wavefront does everything for the profile by itself, with no workgroup barrier:
+//   frames   one lane per time point the collision horizon can touch: spline frame -> the wavefront's LDS table
+//   prep     one lane per pose row: the half-width of the fan of lateral samples along the reference normal
+//   B        one lane per surviving item: circle fattened by the largest lateral offset of the slice, separating axes along the
+//            reference normal and tangent
 //   N        one lane per (hit, lateral sample): exact ego centre + heading, exact circle test, 4-axis separating-axis test
-//            (closed: touching collides).  Survivors of G and B are appended to block-wide LDS lists with ballot / popcount + one
-//            atomic per wavefront.
+//            (closed: touching collides).  Survivors of G are appended to a block-wide LDS list with ballot / popcount + one atomic
+//            per wavefront; those of B are compacted into the wavefront's own hit list.
 // Finally one lane per candidate assembles cost + flag word, a wave/LDS argmin with FOP's "last minimum wins" rule picks the
 // winner, and - when the caller asked for it - one wavefront of the same workgroup writes the winner's series (frenet_winner.h).
 //
@@ -114,12 +113,6 @@ __device__ __forceinline__ bool handover_wait(const int32_t* flag, int32_t* err_
     return true;
 }
 
-#if defined(FP_ABL_NO_SLICE_SYNC)  // timing ablation: the slice loop without its barriers (results are wrong)
-#define SLICE_SYNC() do { } while (0)
-#else
-#define SLICE_SYNC() __syncthreads()
-#endif
-
 struct __attribute__((aligned(16))) Frame {  // reference-line frame of one lon-profile point
     double px, py, tx, ty;
 };
@@ -189,15 +182,18 @@ __device__ __forceinline__ int lut_segment_step(const double* knots, const unsig
 // carve-up folds to immediates and the loop bounds are known.  The <0, ...> instance is the same source with everything read from
 // the arguments.
 //
-// GS: time-horizon slices per barrier interval of the collision stages.  1 = one slice at a time (the throughput instances: their LDS
-// holds one slice's frames); 0 = gs_arg slices at a time (run-time value): a GROUP of g slices is handled like one slice with g * nv
-// lon profiles and g * nd lat profiles - same four barriers, g times the lanes per pass.  Small lattices with few obstacles are bound
-// by the latency of those barrier intervals (a handful of wavefronts of work each), not by arithmetic: with all nt slices in one group
-// an ego costs 4 intervals instead of 4 nt and needs no split over workgroups (no ticket, no merge).
-// NTH: threads per workgroup, 512 or - the grouped latency instances, one workgroup per CU - 1024 (twice the wavefronts per pass).
-// the kernel's parameters as one struct: where InlineIn::bytes sits in the argument segment
+// NTH: threads per workgroup, 512 or - the grouped instances (kGrouped / kPolyGrouped, "lattice_group") - 1024: twice the wavefronts
+// walking the ego's lon profiles, for small batches in which every ego can have a CU to itself.  Small lattices with few obstacles
+// are bound by latency, not by arithmetic: with all slices in one such workgroup an ego needs no split over workgroups (no ticket, no
+// merge).  Nothing else distinguishes a grouped instance from a plain one.
+//
+// The kernel's parameters as one struct: where InlineIn::bytes sits in the argument segment.
+// `reserved` is a slot nothing reads (it held the slices per barrier interval of an organisation that is gone); the launcher passes 0.
+// It stays because the layout of the argument segment is part of the generated code: without it tail_from, epi_from and wcap move by
+// 4 bytes, and the register allocator then came out differently in 14 of the 25 instances (SGPR spills of the four-per-CU instances
+// 38 -> 41, 26 -> 21, 95 -> 104; instruction counts -0.4 % ... +4 %; one three-per-CU instance gained 36 B of scratch).
 struct LatticeKernarg {
-    KernelArgs ka; int rows_max_arg, hp_max_arg, nsplit; Best* part_best; int* part_count; const int* perm; int* dur; int gs_arg, tail_from, epi_from, wcap; FissTail ft; InlineIn inl;
+    KernelArgs ka; int rows_max_arg, hp_max_arg, nsplit; Best* part_best; int* part_count; const int* perm; int* dur; int reserved, tail_from, epi_from, wcap; FissTail ft; InlineIn inl;
 };
 constexpr size_t kInlineOffset = offsetof(LatticeKernarg, inl) + offsetof(InlineIn, bytes);
 
@@ -212,9 +208,9 @@ constexpr size_t kInlineOffset = offsetof(LatticeKernarg, inl) + offsetof(Inline
 // WIN: the instance can keep a WINDOW of the spline's coefficient columns in LDS (wcap < NX, see make_layout) - reference lines too long
 // for a residency's LDS share.  Its own instances: the window's bookkeeping costs the others 10-35 spilled SGPRs each (v_writelane /
 // v_readlane pairs in a kernel that is VALU-issue bound), so the instances without it are exactly what they were.
-template <int ND, int NV, int NT, int STRIDE, int NOBS, int ROWS, int OCC, int GS, int NTH, bool POLY = false, bool FISS = false, bool WIN = false>
+template <int ND, int NV, int NT, int STRIDE, int NOBS, int ROWS, int OCC, int NTH, bool POLY = false, bool FISS = false, bool WIN = false>
 __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, int rows_max_arg, int hp_max_arg, int nsplit_arg, Best* part_best, int* part_count, const int* perm,
-                                                                   int* dur, int gs_arg, int tail_from, int epi_from, int wcap, FissTail ft, InlineIn inl)
+                                                                   int* dur, int reserved, int tail_from, int epi_from, int wcap, FissTail ft, InlineIn inl)
 {
     if constexpr (FISS) {
         if (epi_from >= 0 && (int)blockIdx.x >= epi_from) {  // ---- appended search workgroup: one ego, in launch order
@@ -339,13 +335,10 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
     // (tools/resource_usage.py must show 0 in "VGPRs Spill" for every kernel; tests/test_abi_cpu.py checks it).
     constexpr bool kEgoLds = (ND == 0 && OCC > 4) || OCC > 6;
     constexpr bool kEgoEarly = OCC > 6;  // four per CU (64 VGPRs): from the FIRST barrier on
-    constexpr bool kGroup = GS != 1;
     constexpr int kThreads = NTH, kWaves = NTH / kWave;  // (shadow the file-scope defaults)
-    static_assert(GS == 0 || GS == 1, "GS: 1 or 0 (run-time group size)");
     constexpr int kItemCap = item_cap(OCC);
     constexpr bool kSlim = OCC > 6;  // four workgroups per CU: the 40 KB layout (make_layout)
-    static_assert(!kSlim || (kWalk && !POLY && NTH <= 512 && item_cap(OCC) <= 256), "slim layout: walk, boxes only, 8 wavefronts, 8-bit survivor index");
-    const int gs = kGroup ? gs_arg : 1;
+    static_assert(!kSlim || (!POLY && NTH <= 512 && item_cap(OCC) <= 256), "slim layout: boxes only, 8 wavefronts, 8-bit survivor index");
     const int rows_max = kShape ? ROWS : rows_max_arg;
     const int hp_max = kShape ? (ROWS > 0 ? (ROWS * STRIDE + 1 > FP_MAX_POINTS ? FP_MAX_POINTS : ROWS * STRIDE + 1) : 0) : hp_max_arg;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -394,7 +387,7 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
     // wcap < NX: the coefficient rows in LDS are a WINDOW of wcap segments (make_layout's coef_cols) that starts one segment behind the ego
     const bool windowed = WIN && wcap < bt.NX;
     const int ld = windowed ? wcap : bt.NX;  // row stride of the LDS coefficient table
-    const Layout L = make_layout(bt.NX, n_obs_tab, rows_max, hp_max, nd, nv, nt, kItemCap, gs, kWaves, POLY ? bt.poly_stride : 0, kSlim, wcap);
+    const Layout L = make_layout(bt.NX, n_obs_tab, rows_max, hp_max, nd, nv, nt, kItemCap, kWaves, POLY ? bt.poly_stride : 0, kSlim, wcap);
     double* s_knots = (double*)(smem + L.knots);
     double* s_coef = (double*)(smem + L.coef);
     unsigned short* s_lut = (unsigned short*)(smem + L.lut);
@@ -412,21 +405,18 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
     // poses of the (row, obstacle) items that survive the group test, in the order of the item list: the table itself is read from
     // global memory exactly once (registers -> group test), only the ~7 % the slices can touch are kept
     const SplitTab<ObsPose> s_spose{(double2*)(smem + L.pose), (double2*)(smem + L.pose) + kItemCap};
-    const int n_frames = kWalk ? mul24(kWaves, hp_max) : mul24(mul24(gs, kShape ? NV : p.nv), hp_max);  // records of the frame table
+    const int n_frames = mul24(kWaves, hp_max);  // records of the frame table: [wavefront][point]
     const SplitTab<Frame> s_frames{(double2*)(smem + L.frames), (double2*)(smem + L.frames) + n_frames};
-    double* s_lat = (double*)(smem + L.lat);
-    float* s_dmax2 = (float*)(smem + L.dmax);    // [2][gs][hp_max]
-    float* s_ddmax2 = (float*)(smem + L.ddmax);  // [2][gs][hp_max]
-    using fan_t = typename FanType<kSlim>::type;  // the walk's view of the two: [slice][hp_max]
+    using fan_t = typename FanType<kSlim>::type;  // the lateral fan bounds: [slice][hp_max]
     fan_t* s_fan_d = (fan_t*)(smem + L.dmax);
     fan_t* s_fan_dd = (fan_t*)(smem + L.ddmax);
-    float* s_wfat = (float*)(smem + L.wfat);
+    float* s_wfat = (float*)(smem + L.wfat);  // [wavefront][rows_max]
     ObsDim* s_grp = (ObsDim*)(smem + L.grp);  // reused as {cx, cy, radius, -}
     unsigned short* s_items = (unsigned short*)(smem + L.iqueue);  // item (row r, obstacle j), see kItemShift
-    // A survivor's item in the walk's list: the shaped instances pack it as r << kItemShift | j (kItemShift = bits of NOBS - 1), so that
+    // A survivor's item in the list: the shaped instances pack it as r << kItemShift | j (kItemShift = bits of NOBS - 1), so that
     // B and N take it apart with a shift and a mask; where the shape is a run-time value, or the packed code would not fit the list's
     // 16 bits, it is the table index mul24(r, n_obs) + j and a division takes it apart (kItemShift = 0).
-    constexpr int kItemShift = (kWalk && kShape) ? item_shift(NOBS, ROWS) : 0;
+    constexpr int kItemShift = kShape ? item_shift(NOBS, ROWS) : 0;
     double* s_pows = (double*)(smem + L.pows);
     double* s_ts = (double*)(smem + L.samples);
     double* s_vs = s_ts + nt;
@@ -435,12 +425,11 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
     double* s_lat_sum = (double*)(smem + L.lat_sum);
     int2* s_lon_meta = (int2*)(smem + L.lon_meta);
     double* s_qlon = (double*)(smem + L.qlon);  // [nt][nv][2]
-    double* s_qlat = (double*)(smem + L.qlat);  // [gs][nd][3]
+    double* s_qlat = (double*)(smem + L.qlat);  // [nt][nd][3]
     uint4* s_box = (uint4*)(smem + L.box);      // [rows] {min x, max x, min y, max y} relative to the first knot
-    unsigned char* s_coll = smem + L.coll;
-    uint32_t* s_collmask = (uint32_t*)(smem + L.coll);  // walk: [lon profile][2], bit id = lateral sample id of the profile collides
-    uint32_t* s_hits = (uint32_t*)(smem + L.queue);
-    using hit_t = typename std::conditional<kSlim, uint16_t, uint32_t>::type;  // walk: (point k, survivor index) codes
+    uint32_t* s_collmask = (uint32_t*)(smem + L.coll);  // [lon profile][2], bit id = lateral sample id of the profile collides
+    using hit_t = typename std::conditional<kSlim, uint16_t, uint32_t>::type;  // (point k, survivor index) codes
+    hit_t* s_hits = (hit_t*)(smem + L.queue);  // [wavefront][kWave]
     int* s_cnt = (int*)(smem + L.cnt);
     int* s_nslice = (int*)(smem + L.nslice);
     Best* s_best = (Best*)(smem + L.best);
@@ -539,7 +528,7 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
     {
         const double* gk = bt.knots + (size_t)f * NX;
         const double* gc = bt.coef + (size_t)f * 8 * NX;
-        // [0], [1]: list counters; [2]: slices whose lon profiles need the point-by-point scan; [3]: ticket; [4]: knots closer than a
+        // [0]: counter of the item list ([1]: unused); [2]: slices whose lon profiles need the point-by-point scan; [3]: ticket; [4]: knots closer than a
         // bucket (the segment hint needs its loops); [5], [6]: fp32 bit patterns of the spline's speed bound and of the largest lateral offset
         if (tid < 8) s_cnt[tid] = 0;
 #if defined(FP_PHASE_STAMPS)
@@ -682,16 +671,10 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
         rows = (h + stride - 1) / stride;
         if (rows_stage < rows) rows = rows_stage;
     }
-    if constexpr (kWalk) {
-        for (int c = tid; c < 2 * nt * nv; c += kThreads) s_collmask[c] = 0u;
-    } else {
-        for (int c = tid; c < C; c += kThreads) s_coll[c] = 0;
-    }
+    for (int c = tid; c < 2 * nt * nv; c += kThreads) s_collmask[c] = 0u;
     for (int r = tid; r < rows; r += kThreads) {
         s_box[r] = make_uint4(kOrdPosInf, kOrdNegInf, kOrdPosInf, kOrdNegInf);  // empty
     }
-    if constexpr (!kWalk)
-        for (int i = tid; i < 2 * gs * hp_max; i += kThreads) { s_dmax2[i] = 0.0f; s_ddmax2[i] = 0.0f; }
     // points whose frame the collision stage can touch: 0 .. hp-1 (pose k needs point k+1 for its heading)
     const int pose_limit = rows * stride < horizon_cap ? rows * stride : horizon_cap;  // poses k < pose_limit (and k < M)
     int hp = pose_limit > 0 ? pose_limit + 1 : 0;
@@ -703,7 +686,7 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
     FP_STAMP(1);
 
     const double* v_samples = s_vs;
-    int item_base = 0, hit_base = 0;  // list counters at the start of the current stage (block-uniform)
+    int item_base = 0;  // the item list's counter at the start of the current chunk (block-uniform)
 
     // ---------------------------------------------------------------- phase A0 (once): masks / M / cost sums of every profile
     // (0) lane per lon profile: the boundary-value solve (two divisions), kept for the whole kernel; meta = {N, no flags}.
@@ -874,75 +857,64 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
             o[0] = lat[0]; o[1] = lat[1]; o[2] = lat[2];
         }
     }
-    // lat polynomial coefficients of one slice (a boundary-value solve costs two divisions): nd threads per slice instead of once
-    // per trajectory point
-    const float inv_nd_g = 1.0f / (float)nd;
-    auto fill_group_lat = [&](int it0) {  // the group of slices that starts at it0: [slice in group][lateral sample]
-        if constexpr (kWalk) {  // every slice of this workgroup, [slice][lateral sample] (absolute slice index)
-            for (int e = kThreads - 1 - tid; e < mul24(n_it, nd); e += kThreads) {
-                const int itl = div_small(e, inv_nd_g), id = e - mul24(itl, nd);
-                const Quintic q = quintic_bvp(eD0(), eDd0(), eDdd0(), s_ds[id], 0.0, 0.0, s_ts[it_lo + itl]);
-                double* o = s_qlat + 3 * (mul24(it_lo + itl, nd) + id);
-                o[0] = q.a3; o[1] = q.a4; o[2] = q.a5;
-            }
-            return;
+    // lat polynomial coefficients of every slice of this workgroup, [slice][lateral sample] (absolute slice index): a boundary-value
+    // solve costs two divisions - nd threads per slice (the last ones) instead of once per trajectory point
+    // (A plain loop, in a lambda that is called on the spot: written without the lambda, the same statements come out of the compiler
+    // with other register assignments and SGPR spills (38 600 lines of the 25 instances' assembly differ; with it, none) - and the
+    // instances are to stay exactly as validated.)
+    const float inv_nd = 1.0f / (float)nd;
+    [&] {
+        for (int e = kThreads - 1 - tid; e < mul24(n_it, nd); e += kThreads) {
+            const int itl = div_small(e, inv_nd), id = e - mul24(itl, nd);
+            const Quintic q = quintic_bvp(eD0(), eDd0(), eDdd0(), s_ds[id], 0.0, 0.0, s_ts[it_lo + itl]);
+            double* o = s_qlat + 3 * (mul24(it_lo + itl, nd) + id);
+            o[0] = q.a3; o[1] = q.a4; o[2] = q.a5;
         }
-        const int idg = kThreads - 1 - tid;  // the last threads: they have the least prep work
-        if (idg < mul24(gs, nd)) {
-            const int itl = kGroup ? div_small(idg, inv_nd_g) : 0, id = idg - mul24(itl, nd);
-            if (it0 + itl < it_hi) {
-                const Quintic q = quintic_bvp(eD0(), eDd0(), eDdd0(), s_ds[id], 0.0, 0.0, s_ts[it0 + itl]);
-                s_qlat[3 * idg] = q.a3; s_qlat[3 * idg + 1] = q.a4; s_qlat[3 * idg + 2] = q.a5;
-            }
-        }
-    };
-    fill_group_lat(it_lo);
+    }();
     __syncthreads();
     FP_STAMP(3);
-    if constexpr (kWalk) {
-        // ---- lateral fan bounds of EVERY slice (walk): lane = (slice, point inside the collision horizon): fan half-width max|d| and
-        // largest lateral step max|d(i + 1) - d(i)| over the lateral samples, float_above: never below the fp64 value.  For a fixed
-        // horizon the quintic is AFFINE in its end offset (Hermite form, see the lateral bound above): d(t; d_end) = b(t) + d_end g(t),
-        // so |d| and |d(i + 1) - d(i)| are convex in d_end and their maxima over the samples sit at the smallest and the largest
-        // sample - two profiles are evaluated instead of nd (the rounding of the other samples' own evaluations, ~1e-16 relative,
-        // is far inside float_above's 2^-22).  (The first threads: the circles below take the last ones.)
-        if (n_obs > 0 && hp > 0) {
-            int id_lo = 0, id_hi = 0;  // (any order of d_samples: the reference passes np.linspace, the ABI does not require it)
-            for (int id = 1; id < nd; ++id) {
-                id_lo = s_ds[id] < s_ds[id_lo] ? id : id_lo;
-                id_hi = s_ds[id] > s_ds[id_hi] ? id : id_hi;
-            }
-            bool d_nan = false;
-            for (int id = 0; id < nd; ++id) d_nan = d_nan || !(s_ds[id] == s_ds[id]);
-            const float inv_hp = 1.0f / (float)hp;
-            for (int e = tid; e < mul24(n_it, hp); e += kThreads) {
-                const int itl = div_small(e, inv_hp), i = e - mul24(itl, hp);
-                const int it = it_lo + itl;
-                const int np_i = hp < s_nslice[it] ? hp : s_nslice[it];
-                if (i >= np_i) continue;
-                const double t = (double)i * tick, tn = (double)(i + 1) * tick;
-                float dm = 0.0f, ddm = 0.0f;
+    // ---- lateral fan bounds of EVERY slice: lane = (slice, point inside the collision horizon): fan half-width max|d| and
+    // largest lateral step max|d(i + 1) - d(i)| over the lateral samples, float_above: never below the fp64 value.  For a fixed
+    // horizon the quintic is AFFINE in its end offset (Hermite form, see the lateral bound above): d(t; d_end) = b(t) + d_end g(t),
+    // so |d| and |d(i + 1) - d(i)| are convex in d_end and their maxima over the samples sit at the smallest and the largest
+    // sample - two profiles are evaluated instead of nd (the rounding of the other samples' own evaluations, ~1e-16 relative,
+    // is far inside float_above's 2^-22).  (The first threads: the circles below take the last ones.)
+    if (n_obs > 0 && hp > 0) {
+        int id_lo = 0, id_hi = 0;  // (any order of d_samples: the reference passes np.linspace, the ABI does not require it)
+        for (int id = 1; id < nd; ++id) {
+            id_lo = s_ds[id] < s_ds[id_lo] ? id : id_lo;
+            id_hi = s_ds[id] > s_ds[id_hi] ? id : id_hi;
+        }
+        bool d_nan = false;
+        for (int id = 0; id < nd; ++id) d_nan = d_nan || !(s_ds[id] == s_ds[id]);
+        const float inv_hp = 1.0f / (float)hp;
+        for (int e = tid; e < mul24(n_it, hp); e += kThreads) {
+            const int itl = div_small(e, inv_hp), i = e - mul24(itl, hp);
+            const int it = it_lo + itl;
+            const int np_i = hp < s_nslice[it] ? hp : s_nslice[it];
+            if (i >= np_i) continue;
+            const double t = (double)i * tick, tn = (double)(i + 1) * tick;
+            float dm = 0.0f, ddm = 0.0f;
 #pragma unroll
-                for (int side = 0; side < 2; ++side) {
-                    const double* ql = s_qlat + 3 * (mul24(it, nd) + (side ? id_hi : id_lo));
-                    const double a3 = ql[0], a4 = ql[1], a5 = ql[2];
-                    const double d = fma(fma(fma(fma(fma(a5, t, a4), t, a3), t, eDdd0() * 0.5), t, eDd0()), t, eD0());
-                    const double dn = fma(fma(fma(fma(fma(a5, tn, a4), tn, a3), tn, eDdd0() * 0.5), tn, eDd0()), tn, eD0());
-                    // (a NaN offset poisons the bound: as an unsigned bit pattern NaN is the largest)
-                    const float fd = float_above(fabs(d)), fdd = float_above(fabs(dn - d));
-                    dm = __float_as_uint(fd) > __float_as_uint(dm) ? fd : dm;
-                    ddm = __float_as_uint(fdd) > __float_as_uint(ddm) ? fdd : ddm;
-                }
-                if (d_nan) dm = ddm = __builtin_nanf("");  // a NaN sample: its own profile is NaN everywhere -> every pair passes
-                s_fan_d[mul24(it, hp_max) + i] = FanType<kSlim>::above(dm);
-                s_fan_dd[mul24(it, hp_max) + i] = i + 1 < np_i ? FanType<kSlim>::above(ddm) : (fan_t)0.0f;
+            for (int side = 0; side < 2; ++side) {
+                const double* ql = s_qlat + 3 * (mul24(it, nd) + (side ? id_hi : id_lo));
+                const double a3 = ql[0], a4 = ql[1], a5 = ql[2];
+                const double d = fma(fma(fma(fma(fma(a5, t, a4), t, a3), t, eDdd0() * 0.5), t, eDd0()), t, eD0());
+                const double dn = fma(fma(fma(fma(fma(a5, tn, a4), tn, a3), tn, eDdd0() * 0.5), tn, eDd0()), tn, eD0());
+                // (a NaN offset poisons the bound: as an unsigned bit pattern NaN is the largest)
+                const float fd = float_above(fabs(d)), fdd = float_above(fabs(dn - d));
+                dm = __float_as_uint(fd) > __float_as_uint(dm) ? fd : dm;
+                ddm = __float_as_uint(fdd) > __float_as_uint(ddm) ? fdd : ddm;
             }
+            if (d_nan) dm = ddm = __builtin_nanf("");  // a NaN sample: its own profile is NaN everywhere -> every pair passes
+            s_fan_d[mul24(it, hp_max) + i] = FanType<kSlim>::above(dm);
+            s_fan_dd[mul24(it, hp_max) + i] = i + 1 < np_i ? FanType<kSlim>::above(ddm) : (fan_t)0.0f;
         }
     }
     // ---- ranges -> circles: every reference point of the row lies within  v_max * (half the range)  of the line's point at
     // the middle of the range (v_max >= |P'(s)| everywhere); + ego reach + the largest lateral offset.  One test per
     // (row, obstacle) item then prunes the item for every profile of every slice at once.
-    if (n_obs > 0 && kThreads - 1 - nd - tid >= 0 && kThreads - 1 - nd - tid < rows) {  // (threads next to fill_group_lat's first)
+    if (n_obs > 0 && kThreads - 1 - nd - tid >= 0 && kThreads - 1 - nd - tid < rows) {  // (the threads next to the lat coefficients' first)
         const int r = kThreads - 1 - nd - tid;
         const uint4 bx = s_box[r];
         const double knot0 = s_knots[0], knot_last = s_knots[nx - 1];  // (fresh reads: the prologue's copies need not live this long)
@@ -976,16 +948,17 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
     // ---------------------------------------------------------------- collision
     // Once per ego:   G  lane = (row, obstacle) item against the circle that encloses the row's reference points of ALL lon
     //                    profiles of ALL slices of this workgroup (+ ego reach + the largest lateral offset)     -> s_items
-    // Per slice i_T:  phase A  frames + lateral offsets;  prep  fan half-widths
-    //                 B  lane = (surviving item, lon profile): fattened circle around the reference point + separating axes
-    //                    n_k and t_k of the lateral fan                                                          -> s_hits
-    //                 N  lane = (hit, lateral sample): exact circle + 4-axis separating-axis test                -> s_coll
+    // Per lon profile (one wavefront each, no workgroup barrier - see WALK below):
+    //                 frames, prep  the profile's reference-line frames and fan half-widths       -> the wavefront's s_frames, s_wfat
+    //                 B  lane = surviving item: fattened circle around the reference point + separating axes
+    //                    n_k and t_k of the lateral fan                                            -> the wavefront's s_hits
+    //                 N  lane = (hit, lateral sample): exact circle + 4-axis separating-axis test -> s_collmask
     // The time horizon T moves a profile's first seconds only a little (the end speed spreads them by tens of metres), so one
-    // group test per ego keeps about as few items as one per slice did - at a seventh of the work and one barrier less per slice.
-    // Lists are appended with one LDS atomic per wavefront (ballot + popcount); the two counters only ever grow, each stage works
-    // on [base, counter) and every thread tracks the bases itself, so nothing is reset between stages.  Capacity: the item list is
+    // group test per ego keeps about as few items as one per slice would - at a seventh of the work.
+    // The item list is appended with one LDS atomic per wavefront (ballot + popcount); its counter only ever grows, a chunk works
+    // on [base, counter) and every thread tracks the base itself, so nothing is reset between chunks.  Capacity: the item list is
     // filled optimistically by the whole table; if the survivors do not fit (rare) the table is cut into chunks of kItemCap items
-    // and the slice loop runs once per chunk; the pair range of B is cut into passes of kHitCap pairs.
+    // and the profiles are walked once per chunk.  A wavefront's hit list holds one B round (kWave items): it cannot overflow.
 #if defined(FP_ABL_NO_COLL)
     const bool collide = false;
 #else
@@ -1053,395 +1026,145 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
                 sincos_snapped(s_spose.hi[si].x, sn, cs);
                 s_spose.hi[si] = make_double2(cs, sn);
             }
-            // (the slice loop's first barrier orders these writes before stage B reads them)
-            // No survivor (block-uniform: empty surroundings, obstacles out of reach): nothing can collide, the slices are skipped.
+            // (the walk's barrier below orders these writes before stage B reads them)
+            // No survivor (block-uniform: empty surroundings, obstacles out of reach): nothing can collide, the walk is skipped.
             // (Skipping only the rows without a survivor was tried: a lane that skips its point saves nothing while its wavefront's
             // other lanes work, and the bookkeeping cost 3 % on dense scenes.)
-            if constexpr (kWalk) {
-                // ---- WALK: every wavefront takes lon profiles (slice, end speed) from a counter and handles each one on its own, in four
-                // wave-local steps with no workgroup barrier between them (a wavefront's LDS accesses execute in program order):
-                //   frames   lane = trajectory point inside the collision horizon: reference-line frame -> the wavefront's frame table
-                //   prep     lane = checked pose row: the fan's half-width along the reference normal (fp32, rounded outwards)
-                //   B        lane = surviving item, in list (= time) order, 64 at a time: fattened circle + separating axes n_k, t_k;
-                //            the passing items are compacted into the wavefront's hit list (ballot + popcount, no atomics)
-                //   N        lane = (hit, lateral sample), floor(64 / nd) hits per round: exact circle + 4-axis separating-axis test.
-                // The collision state of the profile's nd candidates is ONE wave-uniform bit mask: a lane skips candidates that have
-                // collided, and the walk of a profile ENDS when all nd have (later items cannot change anything) - items are in time
-                // order, so a blocked profile ends after its first hits instead of testing every pose of the horizon.
-                if (n_surv > 0) {
-                    __syncthreads();  // the survivors' (cos, sin), the item list and the lateral bounds are visible to every wavefront
-                    const SplitTab<Frame> wfr = s_frames.at(mul24(wave, hp_max));
-                    float* wwf = s_wfat + mul24(wave, rows_max > 0 ? rows_max : 1);
-                    hit_t* wh = (hit_t*)s_hits + wave * kWave;
-                    constexpr int kHpwC = ND > 0 ? kWave / ND : 1;
-                    const int hpw = kShape ? kHpwC : kWave / nd;  // hits per narrow-phase round
-                    const int hh_l = div_by<ND, kWave>(lane, inv_ndf), id_l = lane - mul24(hh_l, nd);
-                    const unsigned long long full = nd >= 64 ? ~0ull : ((1ull << nd) - 1ull);
-                    const unsigned long long lt_mask = (1ull << lane) - 1ull;
-                    const int n_prof = mul24(n_it, nv);
-                    const float inv_stride = 1.0f / (float)stride;
-                    // wave-uniform, in scalar registers across the profile loop: whether the segment hint is exact to one step (s_cnt[4], see
-                    // the LUT build), and prep's fp32 ego sizes (the bits of float_above(s_k[4]), (s_k[2]), (s_k[3]))
-                    // (the builtin would not do: the compiler knows these values to be uniform, drops it and keeps them in VECTOR registers
-                    // through the whole walk - this instance has none to spare.  The compiler's hazard recogniser does not look into an asm:
-                    // of gfx950's VALU-writes-SGPR hazards (VMEM reading it as an address: 5 wait states; v_readlane / v_writelane taking it as
-                    // the lane select: 4) neither use exists - the four values only ever feed s_cmp and the constant operand of v_min_f32 /
-                    // v_mul_f32 / v_add_f32, which need none - and the first reader is behind the profile loop's header, LDS waits included.
-                    // Whoever gives them another use pads it.  tools/resource_usage.py after this change: the four-per-CU instances 63 VGPRs
-                    // (shaped) / 64 (run-time shape), 62 - 64 with the appended search, 0 spilled in all 25.)
-                    auto in_sgpr = [](int v) { int r; asm volatile("v_readfirstlane_b32 %0, %1" : "=s"(r) : "v"(v)); return r; };
-                    const int lut_crowded = kShape ? in_sgpr(s_cnt[4]) : 1;  // (run-time shape: the loops, see FRAMES)
-                    // (shaped instances only: the run-time-shape ones have no scalar register left either - held there, the four cost more
-                    // lane operations on spilled SGPRs than they save - and convert per profile as before)
-                    const float r_ego_s = kShape ? __int_as_float(in_sgpr(__float_as_int(float_above(s_k[4])))) : 0.0f;
-                    const float hl_s = kShape ? __int_as_float(in_sgpr(__float_as_int(float_above(s_k[2])))) : 0.0f;
-                    const float hw_s = kShape ? __int_as_float(in_sgpr(__float_as_int(float_above(s_k[3])))) : 0.0f;
-                    // the last pose row a lane can hold: a profile with more points than that has no hit on its own last point
-                    const int k_last = kShape ? mul24(rows - 1, stride) : 0;
-                    // Profiles are dealt to the wavefronts round-robin (wave w takes w, w + 8, ...: a mix of end speeds each); the first
-                    // wavefront to run out waits ~3 of the walk's 24 us for the last one.  Dealing them from a shared LDS counter instead was
-                    // built and measured: no difference (153.1 / 154.4 against 155.1 / 154.1 us per step in same-box runs) - the waiting
-                    // wavefronts cost no issue slots and the CU's other workgroups fill them.  (Its C++ spelling, `if (lane == 0) t =
-                    // atomicAdd(...)` + readfirstlane inside a loop whose only exit is a break, was restructured by the compiler so that lanes
-                    // 1..63 spun on their own - a hang; it took an inline-asm block with EXEC narrowed by hand.)  The loop below has a
-                    // wave-uniform scalar trip count and no divergent branch around a cross-lane operation.
-                    for (int pq = __builtin_amdgcn_readfirstlane(wave); pq < n_prof; pq += kWaves) {
-                        const int itl = div_by<NV, NT * NV>(pq, inv_nvf), iv = pq - mul24(itl, nv);
-                        const int it = it_lo + itl, qg = mul24(it, nv) + iv;
-                        const int M = __builtin_amdgcn_readfirstlane(s_lon_meta[qg].x);  // (M <= N; wave-uniform -> scalar registers)
-                        // a trajectory of fewer than two points has no heading: no pair (M == 1 is the assembly's business)
-                        if (M < 2) continue;
-                        const int n_pts = __builtin_amdgcn_readfirstlane(s_nslice[it]);
-                        const int np = hp < n_pts ? hp : n_pts;
-                        const int npm = np < M ? np : M;
-                        const double a3 = s_qlon[2 * qg], a4 = s_qlon[2 * qg + 1];
+            // ---- WALK: every wavefront takes lon profiles (slice, end speed) round-robin and handles each one on its own, in four
+            // wave-local steps with no workgroup barrier between them (a wavefront's LDS accesses execute in program order):
+            //   frames   lane = trajectory point inside the collision horizon: reference-line frame -> the wavefront's frame table
+            //   prep     lane = checked pose row: the fan's half-width along the reference normal (fp32, rounded outwards)
+            //   B        lane = surviving item, in list (= time) order, 64 at a time: fattened circle + separating axes n_k, t_k;
+            //            the passing items are compacted into the wavefront's hit list (ballot + popcount, no atomics)
+            //   N        lane = (hit, lateral sample), floor(64 / nd) hits per round: exact circle + 4-axis separating-axis test.
+            // The collision state of the profile's nd candidates is ONE wave-uniform bit mask: a lane skips candidates that have
+            // collided, and the walk of a profile ENDS when all nd have (later items cannot change anything) - items are in time
+            // order, so a blocked profile ends after its first hits instead of testing every pose of the horizon.
+            if (n_surv > 0) {
+                __syncthreads();  // the survivors' (cos, sin), the item list and the lateral bounds are visible to every wavefront
+                const SplitTab<Frame> wfr = s_frames.at(mul24(wave, hp_max));
+                float* wwf = s_wfat + mul24(wave, rows_max > 0 ? rows_max : 1);
+                hit_t* wh = s_hits + wave * kWave;
+                constexpr int kHpwC = ND > 0 ? kWave / ND : 1;
+                const int hpw = kShape ? kHpwC : kWave / nd;  // hits per narrow-phase round
+                const int hh_l = div_by<ND, kWave>(lane, inv_ndf), id_l = lane - mul24(hh_l, nd);
+                const unsigned long long full = nd >= 64 ? ~0ull : ((1ull << nd) - 1ull);
+                const unsigned long long lt_mask = (1ull << lane) - 1ull;
+                const int n_prof = mul24(n_it, nv);
+                const float inv_stride = 1.0f / (float)stride;
+                // wave-uniform, in scalar registers across the profile loop: whether the segment hint is exact to one step (s_cnt[4], see
+                // the LUT build), and prep's fp32 ego sizes (the bits of float_above(s_k[4]), (s_k[2]), (s_k[3]))
+                // (the builtin would not do: the compiler knows these values to be uniform, drops it and keeps them in VECTOR registers
+                // through the whole walk - this instance has none to spare.  The compiler's hazard recogniser does not look into an asm:
+                // of gfx950's VALU-writes-SGPR hazards (VMEM reading it as an address: 5 wait states; v_readlane / v_writelane taking it as
+                // the lane select: 4) neither use exists - the four values only ever feed s_cmp and the constant operand of v_min_f32 /
+                // v_mul_f32 / v_add_f32, which need none - and the first reader is behind the profile loop's header, LDS waits included.
+                // Whoever gives them another use pads it.  tools/resource_usage.py after this change: the four-per-CU instances 63 VGPRs
+                // (shaped) / 64 (run-time shape), 62 - 64 with the appended search, 0 spilled in all 25.)
+                auto in_sgpr = [](int v) { int r; asm volatile("v_readfirstlane_b32 %0, %1" : "=s"(r) : "v"(v)); return r; };
+                const int lut_crowded = kShape ? in_sgpr(s_cnt[4]) : 1;  // (run-time shape: the loops, see FRAMES)
+                // (shaped instances only: the run-time-shape ones have no scalar register left either - held there, the four cost more
+                // lane operations on spilled SGPRs than they save - and convert per profile as before)
+                const float r_ego_s = kShape ? __int_as_float(in_sgpr(__float_as_int(float_above(s_k[4])))) : 0.0f;
+                const float hl_s = kShape ? __int_as_float(in_sgpr(__float_as_int(float_above(s_k[2])))) : 0.0f;
+                const float hw_s = kShape ? __int_as_float(in_sgpr(__float_as_int(float_above(s_k[3])))) : 0.0f;
+                // the last pose row a lane can hold: a profile with more points than that has no hit on its own last point
+                const int k_last = kShape ? mul24(rows - 1, stride) : 0;
+                // Profiles are dealt to the wavefronts round-robin (wave w takes w, w + 8, ...: a mix of end speeds each); the first
+                // wavefront to run out waits ~3 of the walk's 24 us for the last one.  Dealing them from a shared LDS counter instead was
+                // built and measured: no difference (153.1 / 154.4 against 155.1 / 154.1 us per step in same-box runs) - the waiting
+                // wavefronts cost no issue slots and the CU's other workgroups fill them.  (Its C++ spelling, `if (lane == 0) t =
+                // atomicAdd(...)` + readfirstlane inside a loop whose only exit is a break, was restructured by the compiler so that lanes
+                // 1..63 spun on their own - a hang; it took an inline-asm block with EXEC narrowed by hand.)  The loop below has a
+                // wave-uniform scalar trip count and no divergent branch around a cross-lane operation.
+                for (int pq = __builtin_amdgcn_readfirstlane(wave); pq < n_prof; pq += kWaves) {
+                    const int itl = div_by<NV, NT * NV>(pq, inv_nvf), iv = pq - mul24(itl, nv);
+                    const int it = it_lo + itl, qg = mul24(it, nv) + iv;
+                    const int M = __builtin_amdgcn_readfirstlane(s_lon_meta[qg].x);  // (M <= N; wave-uniform -> scalar registers)
+                    // a trajectory of fewer than two points has no heading: no pair (M == 1 is the assembly's business)
+                    if (M < 2) continue;
+                    const int n_pts = __builtin_amdgcn_readfirstlane(s_nslice[it]);
+                    const int np = hp < n_pts ? hp : n_pts;
+                    const int npm = np < M ? np : M;
+                    const double a3 = s_qlon[2 * qg], a4 = s_qlon[2 * qg + 1];
     // [section FRAMES]
-                        for (int i = lane; i < npm; i += kWave) {
-                            const double t = (double)i * tick;
-                            const double s = fma(fma(fma(fma(a4, t, a3), t, eSdd0() * 0.5), t, eSd0()), t, eS0());
-                            int seg;
-                            if (kShape && lut_crowded == 0) {  // (the run-time-shape instances keep the loops alone: both lookups in one instance make it larger than it was)
-                                seg = lut_segment_step(s_knots, s_lut, nx, s, s_k[0], s_k[1], n_buckets);
-                            } else {
-    // [section LUTWALK]
-                                seg = lut_segment(s_knots, s_lut, nx, s, s_k[0], s_k[1], n_buckets);
-    // [/section LUTWALK]
-                            }
-                            Frame fr;
-                            frame_at(seg, s - s_knots[seg], fr.px, fr.py, fr.tx, fr.ty);
-                            wfr.set(i, fr.px, fr.py, fr.tx, fr.ty);
-                        }
-    // [/section FRAMES]
-                        wave_lds_sync();
-                        const fan_t* dm = s_fan_d + mul24(it, hp_max);
-                        const fan_t* ddm = s_fan_dd + mul24(it, hp_max);
-                        {   // prep (see the slice loop's comment for the bound): conservative, fp32
-                            const float r_ego_f = kShape ? r_ego_s : float_above(s_k[4]), hl_f = kShape ? hl_s : float_above(s_k[2]), hw_f = kShape ? hw_s : float_above(s_k[3]);
-    // [section PREP]
-                            for (int r = lane; r < rows; r += kWave) {
-                                const int k = mul24(r, stride);
-                                const bool row_ok = k < n_pts && k < hp;
-                                float wl = r_ego_f;
-                                if (k + 1 < M && k + 1 < hp) {
-                                    const Frame f0 = wfr.get(k), f1 = wfr.get(k + 1);
-                                    const double dpx = f1.px - f0.px, dpy = f1.py - f0.py;
-                                    const double a_n = fma(dpy, f0.tx, -dpx * f0.ty);     // dP . n_k,  n_k = (-ty, tx)
-                                    const double a_t = fma(dpx, f0.tx, dpy * f0.ty);      // dP . t_k
-                                    const double nn = fma(f1.tx, f0.tx, f1.ty * f0.ty);   // n_{k+1} . n_k
-                                    const double nt_ = fma(f1.tx, f0.ty, -f1.ty * f0.tx); // n_{k+1} . t_k
-                                    const double dm1 = (double)dm[k + 1];
-                                    const float num = (float)(fabs(a_n) + (double)ddm[k] + dm1 * fabs(1.0 - nn));
-                                    const float den = (float)(fabs(a_t) - dm1 * fabs(nt_));
-                                    if (den > 1e-30f) {  // v_rcp_f32: 1 ulp; the factor covers it and the two roundings to nearest
-                                        const float sigma = vmin_f32(1.0f, num * __builtin_amdgcn_rcpf(den) * (1.0f + 4e-6f) + 1e-9f);
-                                        wl = vmin_f32(r_ego_f, (hl_f * sigma + hw_f) * (1.0f + 1e-6f));
-                                    }
-                                }
-                                wwf[r] = row_ok ? ((float)dm[k] + wl) * (1.0f + 1e-6f) + 1e-9f : 0.0f;
-                            }
-    // [/section PREP]
-                        }
-                        wave_lds_sync();
-                        // candidates of this profile that collided in an earlier item chunk (crowded scenes only; else 0)
-                        unsigned long long coll = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)s_collmask[2 * qg + 1]) << 32) |
-                                                  (uint32_t)__builtin_amdgcn_readfirstlane((int)s_collmask[2 * qg]);
-                        const double* qlat = s_qlat + 3 * mul24(it, nd);
-#if defined(FP_ABL_NO_BN)
-                        const int n_walk = 0;
-#else
-                        const int n_walk = n_surv;
-#endif
-                        for (int c0 = 0; c0 < n_walk && coll != full; c0 += kWave) {
-                            const int si = c0 + lane;
-                            bool pass = false;
-                            uint32_t code = 0;
-    // [section B]
-                            if (si < n_walk) {
-                                const int item = s_items[si];
-                                const int r = kItemShift > 0 ? item >> kItemShift : div_by<NOBS, ROWS * NOBS>(item, inv_nobs);
-                                const int j = kItemShift > 0 ? item & ((1 << kItemShift) - 1) : item - mul24(r, n_obs);
-                                const int k = mul24(r, stride);
-                                const ObsPose op = s_spose.get(si);
-                                const ObsDim od = s_dim.get(j);
-                                const Frame fr = wfr.get(k);  // (stale beyond the profile's M: the test below excludes those poses)
-                                const double r_ego_b = s_k[4];
-                                const double fat = (r_ego_b + od.r + (double)dm[k]) * (1.0 + 1e-12);
-                                const double dx = op.x - fr.px, dy = op.y - fr.py;
-                                // (1) circle around the reference point; (2) separating axis n_k: lateral offset of the obstacle centre
-                                // vs the fan half-width + the obstacle's own reach along n_k; (3) separating axis t_k: every ego centre
-                                // of the fan lies ON the normal line, so along t_k the fan reaches no further than the ego box's
-                                // half-diagonal.  A NaN pose passes all three (-> "collision").
-                                const double w = fma(dy, fr.tx, -dx * fr.ty), u = fma(dx, fr.tx, dy * fr.ty);
-                                const double a_n = fabs(fma(op.s, fr.tx, -op.c * fr.ty)), a_t = fabs(fma(op.c, fr.tx, op.s * fr.ty));
-                                const double reach = fma(od.hl, a_n, od.hw * a_t), reach_t = fma(od.hl, a_t, od.hw * a_n);
-                                pass = k < M && !(fma(dx, dx, dy * dy) > fat * fat) && !(fabs(w) > (double)wwf[r] + reach) &&
-                                       !(fabs(u) > r_ego_b * (1.0 + 1e-12) + reach_t);
-                                code = (uint32_t)k | ((uint32_t)si << 8);  // k < 128, si < 512 (slim: si < 256, 16 bits)
-                            }
-    // [/section B]
-                            const unsigned long long m = __ballot(pass);
-                            if (lane == 0) { FP_COUNT(1, 1); FP_COUNT(2, __popcll(m)); }
-                            if (!m) continue;
-                            const int n_hits = __popcll(m);
-                            if (pass) wh[__popcll(m & lt_mask)] = (hit_t)code;
-                            wave_lds_sync();
-                            // ---- N: exact narrow phase, hpw hits x nd lateral samples per round
-#if defined(FP_ABL_NO_N)
-                            const int n_exact = 0;
-#else
-                            const int n_exact = n_hits;
-#endif
-                            for (int h0 = 0; h0 < n_exact; h0 += hpw) {
-                                const int h = h0 + hh_l;
-                                bool hit = false;
-    // [section N]
-                                if (hh_l < hpw && h < n_exact && !((coll >> id_l) & 1ull)) {
-                                    const uint32_t hc = wh[h];
-                                    const int k = hc & 0xFF, si2 = hc >> 8;
-                                    const int j = kItemShift > 0 ? (int)s_items[si2] & ((1 << kItemShift) - 1)
-                                                                 : (int)s_items[si2] - mul24(div_by<STRIDE, FP_MAX_POINTS>(k, inv_stride), n_obs);  // (table index: row * n_obs + obstacle)
-                                    FP_COUNT(3, 1);
-                                    // heading of pose k: forward difference, or the previous one for the last point (:127-129)
-                                    // (only a profile whose line ends inside the checked rows has such a point: the others take k without the compare and the selects)
-                                    int ka_ = k;
-                                    unsigned long long on_last = 0;  // the round's lanes that stand on their profile's last point
-                                    // (run-time shape: every profile takes the block - one more scalar held through the walk costs those instances more
-                                    // lane operations on spilled SGPRs than the block has instructions)
-                                    if (!kShape || M <= k_last + 1) {  // (scalar: the line ends inside the checked rows)
-    // [section NLAST]
-                                        asm volatile("");  // (nothing is emitted: it keeps this a wave-uniform BRANCH - without it the compiler folds the block into selects that every profile pays)
-                                        on_last = __builtin_amdgcn_ballot_w64(k + 1 >= M);
-                                        ka_ = (k + 1 < M) ? k : k - 1;
-    // [/section NLAST]
-                                    }
-                                    const Frame f0 = wfr.get(ka_), f1 = wfr.get(ka_ + 1);
-                                    const double* ql = qlat + mul24(id_l, 3);
-                                    const double b3 = ql[0], b4 = ql[1], b5 = ql[2];
-                                    const double ta = (double)ka_ * tick, tb = (double)(ka_ + 1) * tick;
-                                    const double da = fma(fma(fma(fma(fma(b5, ta, b4), ta, b3), ta, eDdd0Half()), ta, eDd0()), ta, eD0());
-                                    const double db = fma(fma(fma(fma(fma(b5, tb, b4), tb, b3), tb, eDdd0Half()), tb, eDd0()), tb, eD0());
-                                    double xa, ya, xb, yb;
-                                    frenet_to_cartesian(f0.px, f0.py, f0.tx, f0.ty, da, xa, ya);
-                                    frenet_to_cartesian(f1.px, f1.py, f1.tx, f1.ty, db, xb, yb);
-                                    Obb ego;
-                                    step_heading(xb - xa, yb - ya, ego.c, ego.s);
-                                    ego.x = xa;
-                                    ego.y = ya;
-                                    if (on_last) {
-    // [section NLAST]
-                                        asm volatile("");
-                                        const bool mine = __builtin_amdgcn_inverse_ballot_w64(on_last);
-                                        ego.x = mine ? xb : xa;
-                                        ego.y = mine ? yb : ya;
-    // [/section NLAST]
-                                    }
-                                    ego.hl = s_k[2];
-                                    ego.hw = s_k[3];
-                                    const ObsPose op = s_spose.get(si2);
-                                    const ObsDim od = s_dim.get(j);
-                                    if (!(ego.x == ego.x) || !(ego.y == ego.y) || !(ego.c == ego.c)) {
-                                        hit = true;  // polygon construction fails in the reference -> collision (:178-182)
-                                    } else {
-                                        const double R = (s_k[4] + od.r) * (1.0 + 1e-12);
-                                        const double dx = op.x - ego.x, dy = op.y - ego.y;
-                                        hit = fma(dx, dx, dy * dy) <= R * R && obb_overlap(ego, Obb{op.x, op.y, op.c, op.s, od.hl, od.hw});
-                                        if constexpr (POLY) {
-                                            if (hit) {  // a polygon column: its box was a necessary condition, the ring decides
-                                                const int nvx = ((const int32_t*)(smem + L.nvert))[j];
-                                                if (nvx > 0) hit = ring_overlap(ego, Obb{op.x, op.y, op.c, op.s, od.hl, od.hw}, ring_base + (ring_col0 + j) * 2 * (size_t)bt.poly_stride, nvx, s_dim.rin[j]);
-                                            }
-                                        }
-                                    }
-                                    if (hit) FP_COUNT(5, 1);
-                                }
-    // [/section N]
-                                if (lane == 0) FP_COUNT(6, 1);
-                                unsigned long long hm = __ballot(hit);
-                                // fold the round's hits onto the nd lateral samples (scalar arithmetic on the ballot)
-                                if (nd >= kWave) coll |= hm;
-                                else
-                                    for (; hm; hm >>= nd) coll |= hm & full;
-                                if (coll == full) {
-#if defined(FP_COUNTERS)  // when a blocked profile dies: the pose index of the last hit of the deciding round, in bins of 8 steps (slots 10..15)
-                                    if (lane == 0) {
-                                        FP_COUNT(7, 1);
-                                        const int hl = (h0 + hpw < n_exact ? h0 + hpw : n_exact) - 1;
-                                        const int kd = (int)(wh[hl] & 0xFF) >> 3;
-                                        FP_COUNT(10 + (kd > 5 ? 5 : kd), 1);
-                                    }
-#endif
-                                    break;
-                                }
-                            }
-                        }
-                        if (lane == 0) { s_collmask[2 * qg] = (uint32_t)coll; s_collmask[2 * qg + 1] = (uint32_t)(coll >> 32); }
-                    }
-#if defined(FP_PHASE_STAMPS)  // when the first and the last wavefront finished their profiles (columns 11, 12): the walk's imbalance
-                    if (lane == 0) { atomicMin(&s_walk_t[0], (unsigned int)(wall_clock64() - t_begin)); atomicMax(&s_walk_t[1], (unsigned int)(wall_clock64() - t_begin)); }
-#endif
-                    // every wavefront's collision masks are visible to the assembly (and every wavefront is done with this chunk's item
-                    // list before G overwrites it: crowded scenes walk the profiles again over the next chunk's survivors)
-                    __syncthreads();
-#if defined(FP_PHASE_STAMPS)
-                    if (threadIdx.x == 0 && ka.r.best_traj && (perm || blockIdx.x % nsplit == 0)) {
-                        double* row = ka.r.best_traj + ((size_t)(perm ? perm[blockIdx.x] : blockIdx.x / nsplit) * FP_ARR_COUNT + 15) * (ka.r.traj_stride > 0 ? ka.r.traj_stride : FP_DEFAULT_STRIDE) + 112;
-                        row[11] = (double)s_walk_t[0]; row[12] = (double)s_walk_t[1];
-                    }
-#endif
-                }
-                i0 = i1;
-                continue;
-            }
-            int par = 0;  // which of the two fan-bound buffers this group fills (the other one is zeroed meanwhile)
-            for (int it0 = it_lo; n_surv > 0 && it0 < it_hi; it0 += gs) {
-                // ---- a GROUP of g slices (g = 1 in the throughput instances): profile index q = (slice in group) * nv + iv and
-                // idg = (slice in group) * nd + id; the lon tables ([nt][nv]) are contiguous over a group, so q indexes them from it0 * nv
-                const int g = kGroup ? (it_hi - it0 < gs ? it_hi - it0 : gs) : 1;
-                const int nvg = mul24(g, nv), ndg = mul24(g, nd);
-                const int q0 = mul24(it0, nv);
-                float* s_dmax = s_dmax2 + mul24(par, mul24(gs, hp_max));    // [g][hp_max] (zeroed during the previous group)
-                float* s_ddmax = s_ddmax2 + mul24(par, mul24(gs, hp_max));
-                // ---------------------------------------------------- phase A (per group): one lane per (profile, point)
-                // reference-line frames of the points the collision horizon can touch (i < hp), lateral offsets, fan bounds
-                int n_max = s_nslice[it0];  // points per slice, len(np.arange(0, T, tick)); the longest slice of the group sizes the passes
-                if constexpr (kGroup)
-                    for (int j = 1; j < g; ++j) n_max = s_nslice[it0 + j] > n_max ? s_nslice[it0 + j] : n_max;
-                const int np = hp < n_max ? hp : n_max;
-                const float inv_np = 1.0f / (float)np;
-    // [section FRAMES]
-                for (int e = tid; e < mul24(nvg, np); e += kThreads) {
-                    const int q = div_small(e, inv_np), i = e - mul24(q, np);
-                    const int M = s_lon_meta[q0 + q].x;
-                    if (i < M) {  // the point is on the spline (M <= the slice's N)
-                        const Quartic ql{eS0(), eSd0(), eSdd0() * 0.5, s_qlon[2 * (q0 + q)], s_qlon[2 * (q0 + q) + 1]};
+                    for (int i = lane; i < npm; i += kWave) {
                         const double t = (double)i * tick;
-                        const double s = fma(fma(fma(fma(ql.a4, t, ql.a3), t, ql.a2), t, ql.a1), t, ql.a0);
-                        const int seg = lut_segment(s_knots, s_lut, nx, s, s_k[0], s_k[1], n_buckets);
+                        const double s = fma(fma(fma(fma(a4, t, a3), t, eSdd0() * 0.5), t, eSd0()), t, eS0());
+                        int seg;
+                        if (kShape && lut_crowded == 0) {  // (the run-time-shape instances keep the loops alone: both lookups in one instance make it larger than it was)
+                            seg = lut_segment_step(s_knots, s_lut, nx, s, s_k[0], s_k[1], n_buckets);
+                        } else {
+    // [section LUTWALK]
+                            seg = lut_segment(s_knots, s_lut, nx, s, s_k[0], s_k[1], n_buckets);
+    // [/section LUTWALK]
+                        }
                         Frame fr;
                         frame_at(seg, s - s_knots[seg], fr.px, fr.py, fr.tx, fr.ty);
-                        s_frames.set(mul24(q, hp_max) + i, fr.px, fr.py, fr.tx, fr.ty);
+                        wfr.set(i, fr.px, fr.py, fr.tx, fr.ty);
                     }
-                }
     // [/section FRAMES]
-    // [section LAT]
-                for (int e = tid; e < mul24(ndg, np); e += kThreads) {
-                    const int idg = div_small(e, inv_np), i = e - mul24(idg, np);
-                    const int itl = kGroup ? div_small(idg, inv_nd_g) : 0;
-                    int np_i = np;  // this slice's points inside the horizon
-                    if constexpr (kGroup) {
-                        np_i = s_nslice[it0 + itl];
-                        np_i = hp < np_i ? hp : np_i;
-                        if (i >= np_i) continue;
-                    }
-                    const double* ql = s_qlat + mul24(idg, 3);
-                    const Quintic q{eD0(), eDd0(), eDdd0() * 0.5, ql[0], ql[1], ql[2]};
-                    const double t = (double)i * tick;
-                    const double d = fma(fma(fma(fma(fma(q.a5, t, q.a4), t, q.a3), t, q.a2), t, q.a1), t, q.a0);
-                    s_lat[mul24(idg, hp_max) + i] = d;
-                    // fan half-width max|d| and largest lateral step max|d(i+1) - d(i)| over the lateral samples: LDS atomic max on
-                    // the bit patterns (non-negative floats order like unsigned integers); float_above: never below the fp64 value
-                    atomicMax((unsigned int*)&s_dmax[mul24(itl, hp_max) + i], __float_as_uint(float_above(fabs(d))));
-                    if (i + 1 < np_i) {
-                        const double tn = (double)(i + 1) * tick;
-                        const double dn = fma(fma(fma(fma(fma(q.a5, tn, q.a4), tn, q.a3), tn, q.a2), tn, q.a1), tn, q.a0);
-                        atomicMax((unsigned int*)&s_ddmax[mul24(itl, hp_max) + i], __float_as_uint(float_above(fabs(dn - d))));
-                    }
-                }
-            // [/section LAT]
-                SLICE_SYNC();
-                if (it0 == it_lo + (kGroup ? 0 : 3)) FP_STAMP(11);
-                // ---- prep: wfat = lateral half-width of the whole fan along the reference normal n_k, per checked pose (row r, lon
-                // profile q): every ego centre is P_k + d n_k with |d| <= dmax[k];  the ego box, whose heading deviates from the
-                // reference tangent by alpha, reaches hw cos(alpha) + hl |sin(alpha)| <= min(r_ego, hw + hl sigma) along n_k, where
-                // sigma >= |sin(alpha)| for every lateral sample follows from the heading vector
-                //   h = (P_{k+1} - P_k) + d_{k+1} n_{k+1} - d_k n_k:  |h.n_k| <= |dP.n_k| + max|d_{k+1} - d_k| + max|d_{k+1}| |1 - n_{k+1}.n_k|,
-                //   |h| >= |h.t_k| >= |dP.t_k| - max|d_{k+1}| |n_{k+1}.t_k|.   n_k then serves as a (conservative) separating axis.
-                {
-                    float* z_dmax = s_dmax2 + mul24(par ^ 1, mul24(gs, hp_max));   // zero the other buffer for the next group
-                    float* z_ddmax = s_ddmax2 + mul24(par ^ 1, mul24(gs, hp_max));
-                    for (int i = tid; i < mul24(gs, hp_max); i += kThreads) { z_dmax[i] = 0.0f; z_ddmax[i] = 0.0f; }
-                    fill_group_lat(it0 + gs);  // phase A of this group is done with the table (barrier above)
+                    wave_lds_sync();
+                    const fan_t* dm = s_fan_d + mul24(it, hp_max);
+                    const fan_t* ddm = s_fan_dd + mul24(it, hp_max);
+                    // ---- prep: wfat = lateral half-width of the whole fan along the reference normal n_k, per checked pose row r of this
+                    // profile: every ego centre is P_k + d n_k with |d| <= dm[k];  the ego box, whose heading deviates from the
+                    // reference tangent by alpha, reaches hw cos(alpha) + hl |sin(alpha)| <= min(r_ego, hw + hl sigma) along n_k, where
+                    // sigma >= |sin(alpha)| for every lateral sample follows from the heading vector
+                    //   h = (P_{k+1} - P_k) + d_{k+1} n_{k+1} - d_k n_k:  |h.n_k| <= |dP.n_k| + max|d_{k+1} - d_k| + max|d_{k+1}| |1 - n_{k+1}.n_k|,
+                    //   |h| >= |h.t_k| >= |dP.t_k| - max|d_{k+1}| |n_{k+1}.t_k|.   n_k then serves as a (conservative) separating axis.
                     // A conservative bound, so it is computed in fp32 (the ratio is a reciprocal instead of an fp64 division).
-                    const float r_ego_f = float_above(s_k[4]), hl_f = float_above(s_k[2]), hw_f = float_above(s_k[3]);
-                    const float inv_nv = 1.0f / (float)nv, inv_rows_p = 1.0f / (float)(rows > 0 ? rows : 1);
+                    {
+                        const float r_ego_f = kShape ? r_ego_s : float_above(s_k[4]), hl_f = kShape ? hl_s : float_above(s_k[2]), hw_f = kShape ? hw_s : float_above(s_k[3]);
     // [section PREP]
-                    for (int e = tid; e < mul24(g, mul24(rows, nv)); e += kThreads) {
-                        // e = ((slice in group) * rows + r) * nv + iv
-                        const int rr = div_by<NV, (NT > 0 ? NT : 1) * ROWS * NV>(e, inv_nv), iv = e - mul24(rr, nv);
-                        const int itl = kGroup ? div_small(rr, inv_rows_p) : 0, r = rr - mul24(itl, rows);
-                        const int q = mul24(itl, nv) + iv;
-                        const int k = mul24(r, stride);
-                        const bool row_ok = k < (kGroup ? s_nslice[it0 + itl] : n_max) && k < hp;
-                        const int M = s_lon_meta[q0 + q].x;  // (M <= N)
-                        const float* dm = s_dmax + mul24(itl, hp_max);
-                        float wl = r_ego_f;
-                        if (k + 1 < M && k + 1 < hp) {
-                            const Frame f0 = s_frames.get(mul24(q, hp_max) + k), f1 = s_frames.get(mul24(q, hp_max) + k + 1);
-                            const double dpx = f1.px - f0.px, dpy = f1.py - f0.py;
-                            const double a_n = fma(dpy, f0.tx, -dpx * f0.ty);     // dP . n_k,  n_k = (-ty, tx)
-                            const double a_t = fma(dpx, f0.tx, dpy * f0.ty);      // dP . t_k
-                            const double nn = fma(f1.tx, f0.tx, f1.ty * f0.ty);   // n_{k+1} . n_k
-                            const double nt_ = fma(f1.tx, f0.ty, -f1.ty * f0.tx); // n_{k+1} . t_k
-                            const double dm1 = (double)dm[k + 1];
-                            const float num = (float)(fabs(a_n) + (double)s_ddmax[mul24(itl, hp_max) + k] + dm1 * fabs(1.0 - nn));
-                            const float den = (float)(fabs(a_t) - dm1 * fabs(nt_));
-                            if (den > 1e-30f) {  // v_rcp_f32: 1 ulp; the factor covers it and the two roundings to nearest
-                                const float sigma = vmin_f32(1.0f, num * __builtin_amdgcn_rcpf(den) * (1.0f + 4e-6f) + 1e-9f);
-                                wl = vmin_f32(r_ego_f, (hl_f * sigma + hw_f) * (1.0f + 1e-6f));
+                        for (int r = lane; r < rows; r += kWave) {
+                            const int k = mul24(r, stride);
+                            const bool row_ok = k < n_pts && k < hp;
+                            float wl = r_ego_f;
+                            if (k + 1 < M && k + 1 < hp) {
+                                const Frame f0 = wfr.get(k), f1 = wfr.get(k + 1);
+                                const double dpx = f1.px - f0.px, dpy = f1.py - f0.py;
+                                const double a_n = fma(dpy, f0.tx, -dpx * f0.ty);     // dP . n_k,  n_k = (-ty, tx)
+                                const double a_t = fma(dpx, f0.tx, dpy * f0.ty);      // dP . t_k
+                                const double nn = fma(f1.tx, f0.tx, f1.ty * f0.ty);   // n_{k+1} . n_k
+                                const double nt_ = fma(f1.tx, f0.ty, -f1.ty * f0.tx); // n_{k+1} . t_k
+                                const double dm1 = (double)dm[k + 1];
+                                const float num = (float)(fabs(a_n) + (double)ddm[k] + dm1 * fabs(1.0 - nn));
+                                const float den = (float)(fabs(a_t) - dm1 * fabs(nt_));
+                                if (den > 1e-30f) {  // v_rcp_f32: 1 ulp; the factor covers it and the two roundings to nearest
+                                    const float sigma = vmin_f32(1.0f, num * __builtin_amdgcn_rcpf(den) * (1.0f + 4e-6f) + 1e-9f);
+                                    wl = vmin_f32(r_ego_f, (hl_f * sigma + hw_f) * (1.0f + 1e-6f));
+                                }
                             }
+                            wwf[r] = row_ok ? ((float)dm[k] + wl) * (1.0f + 1e-6f) + 1e-9f : 0.0f;
                         }
-                        s_wfat[mul24(q, hp_max) + k] = row_ok ? (dm[k] + wl) * (1.0f + 1e-6f) + 1e-9f : 0.0f;
+    // [/section PREP]
                     }
-        // [/section PREP]
-                }
-                SLICE_SYNC();
-                if (it0 == it_lo + (kGroup ? 0 : 3)) FP_STAMP(12);
-                const float inv_nvg = 1.0f / (float)nvg;
+                    wave_lds_sync();
+                    // candidates of this profile that collided in an earlier item chunk (crowded scenes only; else 0)
+                    unsigned long long coll = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)s_collmask[2 * qg + 1]) << 32) |
+                                              (uint32_t)__builtin_amdgcn_readfirstlane((int)s_collmask[2 * qg]);
+                    const double* qlat = s_qlat + 3 * mul24(it, nd);
 #if defined(FP_ABL_NO_BN)
-                const int n_pairs = 0;
+                    const int n_walk = 0;
 #else
-                const int n_pairs = mul24(n_surv, nvg);
+                    const int n_walk = n_surv;
 #endif
-                for (int p0 = 0; p0 < n_pairs; p0 += kHitCap) {
-                    const int p1 = p0 + kHitCap < n_pairs ? p0 + kHitCap : n_pairs;
-                    for (int qq0 = p0 + wave * kWave; qq0 < p1; qq0 += kThreads) {
-                        const int pr = qq0 + lane;
+                    for (int c0 = 0; c0 < n_walk && coll != full; c0 += kWave) {
+                        const int si = c0 + lane;
                         bool pass = false;
                         uint32_t code = 0;
-                        if (pr < p1) {
-                            const int si = kGroup ? div_small(pr, inv_nvg) : div_by<NV, kItemCapMax * NV>(pr, inv_nvf), q = pr - mul24(si, nvg);
-                            const int itl = kGroup ? div_small(q, inv_nvf) : 0;
+    // [section B]
+                        if (si < n_walk) {
                             const int item = s_items[si];
-                            const int r = div_by<NOBS, ROWS * NOBS>(item, inv_nobs), j = item - mul24(r, n_obs);
+                            const int r = kItemShift > 0 ? item >> kItemShift : div_by<NOBS, ROWS * NOBS>(item, inv_nobs);
+                            const int j = kItemShift > 0 ? item & ((1 << kItemShift) - 1) : item - mul24(r, n_obs);
                             const int k = mul24(r, stride);
                             const ObsPose op = s_spose.get(si);
                             const ObsDim od = s_dim.get(j);
-                            const Frame fr = s_frames.get(mul24(q, hp_max) + k);
-                            // Poses beyond a profile's M hold stale frames, and a trajectory of fewer than two points has no heading: no
-                            // pair (the narrow phase relies on it)
-                            const int Mp = s_lon_meta[q0 + q].x;
+                            const Frame fr = wfr.get(k);  // (stale beyond the profile's M: the test below excludes those poses)
                             const double r_ego_b = s_k[4];
-                            const double fat = (r_ego_b + od.r + (double)s_dmax[mul24(itl, hp_max) + k]) * (1.0 + 1e-12);
+                            const double fat = (r_ego_b + od.r + (double)dm[k]) * (1.0 + 1e-12);
                             const double dx = op.x - fr.px, dy = op.y - fr.py;
                             // (1) circle around the reference point; (2) separating axis n_k: lateral offset of the obstacle centre
                             // vs the fan half-width + the obstacle's own reach along n_k; (3) separating axis t_k: every ego centre
@@ -1450,88 +1173,122 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
                             const double w = fma(dy, fr.tx, -dx * fr.ty), u = fma(dx, fr.tx, dy * fr.ty);
                             const double a_n = fabs(fma(op.s, fr.tx, -op.c * fr.ty)), a_t = fabs(fma(op.c, fr.tx, op.s * fr.ty));
                             const double reach = fma(od.hl, a_n, od.hw * a_t), reach_t = fma(od.hl, a_t, od.hw * a_n);
-                            pass = k < Mp && Mp >= 2 && !(fma(dx, dx, dy * dy) > fat * fat) && !(fabs(w) > (double)s_wfat[mul24(q, hp_max) + k] + reach) &&
+                            pass = k < M && !(fma(dx, dx, dy * dy) > fat * fat) && !(fabs(w) > (double)wwf[r] + reach) &&
                                    !(fabs(u) > r_ego_b * (1.0 + 1e-12) + reach_t);
-                            code = (uint32_t)q | ((uint32_t)k << 8) | ((uint32_t)si << 16);  // q <= 255, k < 128, si < 512
+                            code = (uint32_t)k | ((uint32_t)si << 8);  // k < 128, si < 512 (slim: si < 256, 16 bits)
                         }
+    // [/section B]
                         const unsigned long long m = __ballot(pass);
                         if (lane == 0) { FP_COUNT(1, 1); FP_COUNT(2, __popcll(m)); }
-                        if (m) {
-                            const int first = __ffsll((long long)m) - 1;
-                            int base = 0;
-                            if (lane == first) base = atomicAdd(&s_cnt[1], __popcll(m));
-                            const int pos = __builtin_amdgcn_readlane(base, first) - hit_base + __popcll(m & ((1ull << lane) - 1ull));
-                            if (pass) s_hits[pos] = code;  // at most kHitCap pairs per pass: always fits
-                        }
-                    }
-                    SLICE_SYNC();
-                    if (it0 == it_lo + (kGroup ? 0 : 3)) FP_STAMP(13);
-                    const int hit_end = s_cnt[1];
-                    const int n_hits = hit_end - hit_base;
-                    hit_base = hit_end;
-                    // ---- N: exact narrow phase
+                        if (!m) continue;
+                        const int n_hits = __popcll(m);
+                        if (pass) wh[__popcll(m & lt_mask)] = (hit_t)code;
+                        wave_lds_sync();
+                        // ---- N: exact narrow phase, hpw hits x nd lateral samples per round
 #if defined(FP_ABL_NO_N)
-                    const int n_exact = 0;
+                        const int n_exact = 0;
 #else
-                    const int n_exact = n_hits * nd;
+                        const int n_exact = n_hits;
 #endif
-                    for (int x = tid; x < n_exact; x += kThreads) {
-                        const int h = div_by<ND, kHitCap * ND>(x, inv_ndf), id = x - mul24(h, nd);
-                        // everything the filter needs rides in the hit word: one LDS read, then the candidate's collision byte
-                        const uint32_t code = s_hits[h];
-                        const int q = code & 0xFF, k = (code >> 8) & 0xFF, si = code >> 16;
-                        const int itl = kGroup ? div_small(q, inv_nvf) : 0;
-                        const int cand = mul24(mul24(id, nt), nv) + q0 + q;  // (id * nt + it) * nv + iv with it * nv + iv = q0 + q
-                        FP_COUNT(3, 1);
-                        if (s_coll[cand]) FP_COUNT(4, 1);
-                        if (!s_coll[cand]) {
-                            const int j = (int)s_items[si] - mul24(div_by<STRIDE, FP_MAX_POINTS>(k, 1.0f / (float)stride), n_obs);  // item = row * n_obs + obstacle, k = row * stride
-                            const int M = s_lon_meta[q0 + q].x;
-                            // heading of pose k: forward difference, or the previous one for the last point (:127-129)
-                            const int ka_ = (k + 1 < M) ? k : k - 1;
-                            const Frame f0 = s_frames.get(mul24(q, hp_max) + ka_), f1 = s_frames.get(mul24(q, hp_max) + ka_ + 1);
-                            const double* lt = s_lat + mul24(mul24(itl, nd) + id, hp_max) + ka_;
-                            const double da = lt[0], db = lt[1];
-                            double xa, ya, xb, yb;
-                            frenet_to_cartesian(f0.px, f0.py, f0.tx, f0.ty, da, xa, ya);
-                            frenet_to_cartesian(f1.px, f1.py, f1.tx, f1.ty, db, xb, yb);
-                            Obb ego;
-                            step_heading(xb - xa, yb - ya, ego.c, ego.s);
-                            ego.x = (ka_ == k) ? xa : xb;
-                            ego.y = (ka_ == k) ? ya : yb;
-                            ego.hl = s_k[2];
-                            ego.hw = s_k[3];
-                            const ObsPose op = s_spose.get(si);
-                            const ObsDim od = s_dim.get(j);
-                            bool hit;
-                            if (!(ego.x == ego.x) || !(ego.y == ego.y) || !(ego.c == ego.c)) {
-                                hit = true;  // polygon construction fails in the reference -> collision (:178-182)
-                            } else {
-                                const double R = (s_k[4] + od.r) * (1.0 + 1e-12);
-                                const double dx = op.x - ego.x, dy = op.y - ego.y;
-                                hit = fma(dx, dx, dy * dy) <= R * R && obb_overlap(ego, Obb{op.x, op.y, op.c, op.s, od.hl, od.hw});
-                                        if constexpr (POLY) {
-                                            if (hit) {  // a polygon column: its box was a necessary condition, the ring decides
-                                                const int nvx = ((const int32_t*)(smem + L.nvert))[j];
-                                                if (nvx > 0) hit = ring_overlap(ego, Obb{op.x, op.y, op.c, op.s, od.hl, od.hw}, ring_base + (ring_col0 + j) * 2 * (size_t)bt.poly_stride, nvx, s_dim.rin[j]);
-                                            }
+                        for (int h0 = 0; h0 < n_exact; h0 += hpw) {
+                            const int h = h0 + hh_l;
+                            bool hit = false;
+    // [section N]
+                            if (hh_l < hpw && h < n_exact && !((coll >> id_l) & 1ull)) {
+                                const uint32_t hc = wh[h];
+                                const int k = hc & 0xFF, si2 = hc >> 8;
+                                const int j = kItemShift > 0 ? (int)s_items[si2] & ((1 << kItemShift) - 1)
+                                                             : (int)s_items[si2] - mul24(div_by<STRIDE, FP_MAX_POINTS>(k, inv_stride), n_obs);  // (table index: row * n_obs + obstacle)
+                                FP_COUNT(3, 1);
+                                // heading of pose k: forward difference, or the previous one for the last point (:127-129)
+                                // (only a profile whose line ends inside the checked rows has such a point: the others take k without the compare and the selects)
+                                int ka_ = k;
+                                unsigned long long on_last = 0;  // the round's lanes that stand on their profile's last point
+                                // (run-time shape: every profile takes the block - one more scalar held through the walk costs those instances more
+                                // lane operations on spilled SGPRs than the block has instructions)
+                                if (!kShape || M <= k_last + 1) {  // (scalar: the line ends inside the checked rows)
+    // [section NLAST]
+                                    asm volatile("");  // (nothing is emitted: it keeps this a wave-uniform BRANCH - without it the compiler folds the block into selects that every profile pays)
+                                    on_last = __builtin_amdgcn_ballot_w64(k + 1 >= M);
+                                    ka_ = (k + 1 < M) ? k : k - 1;
+    // [/section NLAST]
+                                }
+                                const Frame f0 = wfr.get(ka_), f1 = wfr.get(ka_ + 1);
+                                const double* ql = qlat + mul24(id_l, 3);
+                                const double b3 = ql[0], b4 = ql[1], b5 = ql[2];
+                                const double ta = (double)ka_ * tick, tb = (double)(ka_ + 1) * tick;
+                                const double da = fma(fma(fma(fma(fma(b5, ta, b4), ta, b3), ta, eDdd0Half()), ta, eDd0()), ta, eD0());
+                                const double db = fma(fma(fma(fma(fma(b5, tb, b4), tb, b3), tb, eDdd0Half()), tb, eDd0()), tb, eD0());
+                                double xa, ya, xb, yb;
+                                frenet_to_cartesian(f0.px, f0.py, f0.tx, f0.ty, da, xa, ya);
+                                frenet_to_cartesian(f1.px, f1.py, f1.tx, f1.ty, db, xb, yb);
+                                Obb ego;
+                                step_heading(xb - xa, yb - ya, ego.c, ego.s);
+                                ego.x = xa;
+                                ego.y = ya;
+                                if (on_last) {
+    // [section NLAST]
+                                    asm volatile("");
+                                    const bool mine = __builtin_amdgcn_inverse_ballot_w64(on_last);
+                                    ego.x = mine ? xb : xa;
+                                    ego.y = mine ? yb : ya;
+    // [/section NLAST]
+                                }
+                                ego.hl = s_k[2];
+                                ego.hw = s_k[3];
+                                const ObsPose op = s_spose.get(si2);
+                                const ObsDim od = s_dim.get(j);
+                                if (!(ego.x == ego.x) || !(ego.y == ego.y) || !(ego.c == ego.c)) {
+                                    hit = true;  // polygon construction fails in the reference -> collision (:178-182)
+                                } else {
+                                    const double R = (s_k[4] + od.r) * (1.0 + 1e-12);
+                                    const double dx = op.x - ego.x, dy = op.y - ego.y;
+                                    hit = fma(dx, dx, dy * dy) <= R * R && obb_overlap(ego, Obb{op.x, op.y, op.c, op.s, od.hl, od.hw});
+                                    if constexpr (POLY) {
+                                        if (hit) {  // a polygon column: its box was a necessary condition, the ring decides
+                                            const int nvx = ((const int32_t*)(smem + L.nvert))[j];
+                                            if (nvx > 0) hit = ring_overlap(ego, Obb{op.x, op.y, op.c, op.s, od.hl, od.hw}, ring_base + (ring_col0 + j) * 2 * (size_t)bt.poly_stride, nvx, s_dim.rin[j]);
                                         }
+                                    }
+                                }
+                                if (hit) FP_COUNT(5, 1);
                             }
-                            if (hit) { s_coll[cand] = 1; FP_COUNT(5, 1); FP_COUNT(8 + (k >> 3), 1); }
+    // [/section N]
+                            if (lane == 0) FP_COUNT(6, 1);
+                            unsigned long long hm = __ballot(hit);
+                            // fold the round's hits onto the nd lateral samples (scalar arithmetic on the ballot)
+                            if (nd >= kWave) coll |= hm;
+                            else
+                                for (; hm; hm >>= nd) coll |= hm & full;
+                            if (coll == full) {
+#if defined(FP_COUNTERS)  // when a blocked profile dies: the pose index of the last hit of the deciding round, in bins of 8 steps (slots 10..15)
+                                if (lane == 0) {
+                                    FP_COUNT(7, 1);
+                                    const int hl = (h0 + hpw < n_exact ? h0 + hpw : n_exact) - 1;
+                                    const int kd = (int)(wh[hl] & 0xFF) >> 3;
+                                    FP_COUNT(10 + (kd > 5 ? 5 : kd), 1);
+                                }
+#endif
+                                break;
+                            }
                         }
                     }
-                    if (p1 < n_pairs) SLICE_SYNC();  // the next pass overwrites the hit list
+                    if (lane == 0) { s_collmask[2 * qg] = (uint32_t)coll; s_collmask[2 * qg + 1] = (uint32_t)(coll >> 32); }
                 }
-                SLICE_SYNC();  // frames / lat / dmax are rewritten by the next group
-                if (it0 == it_lo + (kGroup ? 0 : 3)) FP_STAMP(14);
-                par ^= 1;
+#if defined(FP_PHASE_STAMPS)  // when the first and the last wavefront finished their profiles (columns 11, 12): the walk's imbalance
+                if (lane == 0) { atomicMin(&s_walk_t[0], (unsigned int)(wall_clock64() - t_begin)); atomicMax(&s_walk_t[1], (unsigned int)(wall_clock64() - t_begin)); }
+#endif
+                // every wavefront's collision masks are visible to the assembly (and every wavefront is done with this chunk's item
+                // list before G overwrites it: crowded scenes walk the profiles again over the next chunk's survivors)
+                __syncthreads();
+#if defined(FP_PHASE_STAMPS)
+                if (threadIdx.x == 0 && ka.r.best_traj && (perm || blockIdx.x % nsplit == 0)) {
+                    double* row = ka.r.best_traj + ((size_t)(perm ? perm[blockIdx.x] : blockIdx.x / nsplit) * FP_ARR_COUNT + 15) * (ka.r.traj_stride > 0 ? ka.r.traj_stride : FP_DEFAULT_STRIDE) + 112;
+                    row[11] = (double)s_walk_t[0]; row[12] = (double)s_walk_t[1];
+                }
+#endif
             }
             i0 = i1;
-            if (i0 < n_items) {  // another item chunk: its slice loop starts over (rare: crowded scenes)
-                for (int i = tid; i < 2 * mul24(gs, hp_max); i += kThreads) { s_dmax2[i] = 0.0f; s_ddmax2[i] = 0.0f; }
-                fill_group_lat(it_lo);
-                __syncthreads();
-            }
         }
     }
 
@@ -1564,9 +1321,7 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
         const int2 meta = s_lon_meta[mul24(it, nv) + iv];
         const int M = meta.x;
         uint32_t flags = (uint32_t)meta.y;
-        bool hit;
-        if constexpr (kWalk) hit = (s_collmask[2 * (mul24(it, nv) + iv) + (id >> 5)] >> (id & 31)) & 1u;
-        else hit = s_coll[c] != 0;
+        bool hit = (s_collmask[2 * (mul24(it, nv) + iv) + (id >> 5)] >> (id & 31)) & 1u;
         if (n_obs > 0 && M == 1 && horizon_cap >= 1) hit = true;  // traj.yaw is empty -> IndexError -> collision (:178-182)
         if (hit) flags |= FP_FLAG_COLLISION;
         if (M < N) flags |= FP_FLAG_TRUNCATED;
@@ -1739,7 +1494,7 @@ constexpr LatticeFn lattice_kernel_of()
     constexpr bool grouped = k.family == kGrouped || k.family == kPolyGrouped;
     constexpr bool poly = k.family == kPoly || k.family == kPolyGrouped || k.family == kPolyWindow;
     constexpr bool win = k.family == kWindow || k.family == kPolyWindow;
-    return lattice_fused_kernel<d.nd, d.nv, d.nt, d.stride, d.n_obs, d.rows, 2 * k.per_cu, grouped ? 0 : 1, grouped ? FP_GROUP_THREADS : kThreads, poly,
+    return lattice_fused_kernel<d.nd, d.nv, d.nt, d.stride, d.n_obs, d.rows, 2 * k.per_cu, grouped ? FP_GROUP_THREADS : kThreads, poly,
                                 k.family == kSearch, win>;
 }
 struct LatticeInstance {
@@ -1764,7 +1519,7 @@ static hipError_t launch_lattice_fused(const KernelArgs& ka, hipStream_t stream,
     KernelArgs kx = ka;  // (epilogue workgroups offered but not taken: the caller's winner_traj_kernel writes the series)
     if (ka.epi_flag && !pl.epilogue) { kx.r.best_traj = nullptr; kx.epi_flag = nullptr; }
     if (rq.provisional) { kx.r.best_traj = nullptr; kx.epi_flag = nullptr; kx.has_loop = 0; }  // (as planned: tables and a provisional argmin only)
-    int rows = pl.rows, hp = pl.hp, nsplit = pl.nsplit, gs = pl.gs, tail_from = pl.tail_from, epi_from = pl.epi_from, wcap = pl.wcap;
+    int rows = pl.rows, hp = pl.hp, nsplit = pl.nsplit, reserved = 0, tail_from = pl.tail_from, epi_from = pl.epi_from, wcap = pl.wcap;
     // part_scratch: [ticket counters: kTicketBytes, zero between launches][partial argmins: Best x B x nsplit]
     int* part_count = (int*)rq.part_scratch;
     Best* part_best = rq.part_scratch ? (Best*)((char*)rq.part_scratch + kTicketBytes) : nullptr;
@@ -1774,7 +1529,7 @@ static hipError_t launch_lattice_fused(const KernelArgs& ka, hipStream_t stream,
     if (pl.search) { fx = *rq.ft; fx.NB = kAppendedSearchNB; }
     static const InlineIn kNoInline{};
     const InlineIn* in = rq.inl ? rq.inl : &kNoInline;
-    void* args[] = {&kx, &rows, &hp, &nsplit, &part_best, &part_count, &perm, &dur, &gs, &tail_from, &epi_from, &wcap, &fx, (void*)in};
+    void* args[] = {&kx, &rows, &hp, &nsplit, &part_best, &part_count, &perm, &dur, &reserved, &tail_from, &epi_from, &wcap, &fx, (void*)in};
     LatticeInstance& inst = lattice_instance_at(pl.instance, std::make_index_sequence<kLatticeInstanceCount>());
     hipError_t e = ensure_dynamic_lds((const void*)inst.kernel, pl.lds, inst.lds_slot);
     if (e != hipSuccess) return e;

@@ -14,7 +14,6 @@ constexpr int kThreads = 512;
 #ifndef FP_GROUP_THREADS
 #define FP_GROUP_THREADS 1024  // threads per workgroup of the grouped instances
 #endif
-constexpr int kHitCap = 1024;    // block-wide list of (lon profile, row, obstacle) hits of one B pass  // block-wide list of live narrow-phase items (pair, lateral sample) of one B pass: 24 KB
 // block-wide list of (row, obstacle) items that pass the group test (+ their poses, 32 B each).  Two kernel variants: OCC = 4 waves per
 // SIMD (two workgroups per CU, up to 128 VGPRs, winner epilogue inside) and OCC = 6 (THREE workgroups per CU: 80 VGPRs - a few spill
 // - and at most 53 KB of LDS, so a shorter list; no winner epilogue, the batches it serves get theirs from winner_traj_kernel or from the
@@ -35,22 +34,14 @@ static_assert(item_shift(1, 25) == 0 && item_shift(2, 25) == 1 && item_shift(409
 
 // LDS carve-up (all offsets in bytes, 16-byte aligned)
 struct Layout {
-    int knots, coef, lut, dim, pose, frames, lat, dmax, ddmax, wfat, grp, iqueue, pows, samples, lon_sum, lat_sum, lon_meta, qlon, qlat, box, coll, queue, cnt, nslice, best, konst, nvert, poly, total;
+    int knots, coef, lut, dim, pose, frames, dmax, ddmax, wfat, grp, iqueue, pows, samples, lon_sum, lat_sum, lon_meta, qlon, qlat, box, coll, queue, cnt, nslice, best, konst, nvert, poly, total;
 };
 
 __host__ __device__ inline int align16(int v) { return (v + 15) & ~15; }
 
-// Two organisations of the collision stages share the kernel's prologue (FP_SLICE_LOOP selects the older one for A/B runs):
-//   walk (default)  every wavefront takes one lon profile (T, v) at a time and does everything for it by itself - frames, fan
-//                   half-widths, broad phase, narrow phase - with NO workgroup barrier; the per-slice tables (frames, half-widths,
-//                   hit list) are per WAVEFRONT, the lateral bounds and coefficients of all slices are computed once per ego
-//   slice loop      all wavefronts work on one time-horizon slice (or a group of gs slices) per barrier interval
-#if defined(FP_SLICE_LOOP)
-constexpr bool kWalk = false;
-#else
-constexpr bool kWalk = true;
-#endif
-// gs = time-horizon slices the collision stages work on per barrier interval (1: one at a time; the per-slice tables are gs deep)
+// The collision stages are a WALK: every wavefront takes one lon profile (T, v) at a time and does everything for it by itself - frames,
+// fan half-widths, broad phase, narrow phase - with NO workgroup barrier.  So the per-profile tables (frames, half-widths, hit list) are
+// per WAVEFRONT (nwaves of each); the lateral bounds and coefficients of all slices are computed once per ego.
 // Polygon columns (POLY instances): the vertex counts always sit in LDS, the rings when they are small (kPolyLdsMax: a few KB keep the
 // three-workgroups-per-CU instance inside its 52 KB; 9.6 KB of 12-gons pushed config-3-sized scenes to two per CU: 208 -> 234 us) - a
 // narrow-phase lane reads another obstacle than its neighbour, and from global memory a ring costs it two dependent L2 round trips
@@ -63,42 +54,33 @@ __host__ __device__ inline int poly_lds_verts(int n_obs, int poly_stride) { retu
 // coef_cols: columns (segments) of the spline's coefficient rows the workgroup keeps in LDS: all nx_max of them (default), or a WINDOW
 // of that many segments placed at the ego's position (the kernel's `wcap`): 64 of the 76 bytes a knot costs.  Long reference lines
 // (200+ knots) then still fit the three- / four-per-CU layouts; a point whose segment lies outside the window reads global memory.
-__host__ __device__ inline Layout make_layout(int nx_max, int n_obs, int rows, int hp, int nd, int nv, int nt, int kItemCap, int gs, int nwaves, int poly_stride = 0, bool slim = false,
+__host__ __device__ inline Layout make_layout(int nx_max, int n_obs, int rows, int hp, int nd, int nv, int nt, int kItemCap, int nwaves, int poly_stride = 0, bool slim = false,
                                               int coef_cols = -1)
 {
-    // slim (the four-per-CU instance, kWalk, no polygon columns): the same tables in 40 KB - no inner radii, fp16 fan bounds, 16-bit
+    // slim (the four-per-CU instance, no polygon columns): the same tables in 40 KB - no inner radii, fp16 fan bounds, 16-bit
     // hit codes, the row boxes inside the power sums' / hit lists' bytes (they are read for the last time before the first hit is written)
     Layout L;
     int o = 0;
     L.dim = o;      o = align16(o + (slim ? 24 : 32) * n_obs);
     L.pose = o;     o = align16(o + 32 * kItemCap);  // poses of the group test's survivors (x, y, cos, sin), in list order
-    if (kWalk) {
-        L.frames = o;   o = align16(o + 32 * nwaves * hp);   // [wavefront][point]: the profile the wavefront is working on
-        L.lat = o;
-        L.dmax = o;     o = align16(o + (slim ? 2 : 4) * nt * hp);   // [slice][point] float (slim: half), rounded up: max |d| over the lateral samples
-        L.ddmax = o;    o = align16(o + (slim ? 2 : 4) * nt * hp);   // max |d(i + 1) - d(i)|
-        L.wfat = o;     o = align16(o + 4 * nwaves * (rows > 0 ? rows : 1));  // [wavefront][row] float, rounded up
-    } else {
-        L.frames = o;   o = align16(o + 32 * gs * nv * hp);
-        L.lat = o;      o = align16(o + 8 * gs * nd * hp);
-        L.dmax = o;     o = align16(o + 2 * 4 * gs * hp);   // float, rounded up; two buffers (group parity): LDS atomic max in phase A
-        L.ddmax = o;    o = align16(o + 2 * 4 * gs * hp);
-        L.wfat = o;     o = align16(o + 4 * gs * nv * hp);  // float, rounded up
-    }
-    L.grp = o;      o = align16(o + 32 * (rows > 0 ? rows : 1));       // per checked pose row: circle enclosing all lon profiles' points
+    L.frames = o;   o = align16(o + 32 * nwaves * hp);   // [wavefront][point]: the profile the wavefront is working on
+    L.dmax = o;     o = align16(o + (slim ? 2 : 4) * nt * hp);   // [slice][point] float (slim: half), rounded up: max |d| over the lateral samples
+    L.ddmax = o;    o = align16(o + (slim ? 2 : 4) * nt * hp);   // max |d(i + 1) - d(i)|
+    L.wfat = o;     o = align16(o + 4 * nwaves * (rows > 0 ? rows : 1));  // [wavefront][row] float, rounded up
+    L.grp = o;      o =align16(o + 32 * (rows > 0 ? rows : 1));       // per checked pose row: circle enclosing all lon profiles' points
     L.iqueue = o;   o = align16(o + 2 * kItemCap);                           // (row, obstacle) items that pass the group test
     L.samples = o;  o = align16(o + 8 * (nt + nv + nd));  // t / v / d sample grids (read all over the kernel: keep them out of HBM latency)
     L.lon_sum = o;  o = align16(o + 24 * nt * nv);   // sum_v, sum_as, sum_js
     L.lat_sum = o;  o = align16(o + 24 * nd * nt);   // sum_ad, sum_jd, sum_d
     L.lon_meta = o; o = align16(o + 8 * nt * nv);    // int M, uint flags
     L.qlon = o;     o = align16(o + 16 * nt * nv);   // a3, a4 of every lon profile (a0..a2 are the ego state)
-    L.qlat = o;     o = align16(o + 24 * (kWalk ? nt : gs) * nd);   // a3, a4, a5 of the lat profiles (walk: of every slice; else of the CURRENT slices)
-    L.box = o;      if (!slim) o = align16(o + 16 * (rows > 0 ? rows : 1));  // per checked pose row: bounding box of the slice's reference points (ordered-uint fp32)
-    L.coll = o;     o = align16(o + (kWalk ? 8 * nt * nv : nd * nv * nt));  // walk: one bit per lateral sample, a 64-bit word per lon profile; else a byte per candidate
-    // per-wave hit queues; before the slice loop the same bytes hold the power sums S_k(N) = sum_i (i*tick - c)^k, k = 0..10, per slice
+    L.qlat = o;     o = align16(o + 24 * nt * nd);   // a3, a4, a5 of the lat profiles of every slice
+    L.box = o;      if (!slim) o = align16(o + 16 * (rows > 0 ? rows : 1));  // per checked pose row: bounding box of the row's reference points (ordered-uint fp32)
+    L.coll = o;     o = align16(o + 8 * nt * nv);  // one bit per lateral sample, a 64-bit word per lon profile
+    // per-wavefront hit lists; before the walk the same bytes hold the power sums S_k(N) = sum_i (i*tick - c)^k, k = 0..10, per slice
     L.queue = o;    L.pows = o;
     {
-        const int q = kWalk ? (slim ? 2 : 4) * 64 * nwaves : 4 * kHitCap;
+        const int q = (slim ? 2 : 4) * 64 * nwaves;
         int pw = align16(88 * nt);
         if (slim) { L.box = o + pw; pw += 16 * (rows > 0 ? rows : 1); }
         o = align16(o + (q > pw ? q : pw));
@@ -152,21 +134,21 @@ inline bool fused_shape(const fp_params& p, const fp_batch& b, int* rows_out, in
     return true;
 }
 
-// Largest number of time-horizon slices one workgroup can hold at once (the grouped instances, GS = 0): LDS budget and the 8-bit
-// profile index of the hit word.  0 when the problem does not fit the fused kernel at all.
+// The largest "lattice_group" a problem gets: nt, capped at 256 / nv; 0 when the problem does not fit the fused kernel or the layout
+// of a 1024-thread workgroup does not fit the LDS budget.  Above 1 the launch takes a grouped instance (plan_lattice, step 2).  The
+// cap g * nv <= 256 was the 8-bit profile index of a kernel organisation that is gone (several slices per barrier interval); it is
+// kept because it still decides which launches get the 1024-thread instances - tests/test_gpu_edges.py pins nv = 128 (two: grouped)
+// against nv = 129 (one: plain) - and a refactor does not move that line.
 inline int group_fit(const fp_params& p, const fp_batch& b)
 {
     int rows = 0, hp = 0;
     if (!fused_shape(p, b, &rows, &hp)) return 0;
-    int gs = 0;
-    for (int g = 1; g <= p.nt; ++g) {
-        if (g * p.nv > 256 || make_layout(b.NX, b.n_obs, rows, hp, p.nd, p.nv, p.nt, item_cap(4), g, FP_GROUP_THREADS / kWave, b.obs_nvert ? b.poly_stride : 0).total > kLdsLimit) break;
-        gs = g;
-    }
-    return gs;
+    if (make_layout(b.NX, b.n_obs, rows, hp, p.nd, p.nv, p.nt, item_cap(4), FP_GROUP_THREADS / kWave, b.obs_nvert ? b.poly_stride : 0).total > kLdsLimit) return 0;
+    const int by_index = 256 / p.nv;  // (lattice sizes are at least 1: the ABI refuses anything else)
+    return p.nt < by_index ? p.nt : by_index;
 }
 
-// The instances of lattice_fused_kernel - family (grouped: GS = 0; poly: POLY; search: FISS; window: WIN) x workgroups per CU x compile-time
+// The instances of lattice_fused_kernel - family (grouped: 1024 threads; poly: POLY; search: FISS; window: WIN) x workgroups per CU x compile-time
 // shape (BASELINE.json's two; else run-time sizes).  frenet_lattice_fused.hip instantiates exactly these; a plan names one by index.
 enum LatticeFamily { kPlain, kGrouped, kPoly, kPolyGrouped, kSearch, kWindow, kPolyWindow };
 enum LatticeShape { kShapeRuntime, kShape997, kShape555 };
@@ -194,7 +176,7 @@ inline int lattice_instance(LatticeFamily family, int per_cu, LatticeShape shape
 struct LatticePlan {
     bool fits = false;       // false: the problem does not fit the fused kernel (index widths, LDS budget) - nothing below is set
     int rows = 0, hp = 0;    // checked pose rows, the time points they span
-    int gs = 1;              // time-horizon slices per barrier interval
+    int gs = 1;              // "lattice_group" as granted (group_fit); > 1: a grouped instance - 1024-thread workgroups, two per CU, no window, no tail
     int nsplit = 1;          // workgroups per ego (latency mode)
     int per_cu = 2;          // lattice workgroups per CU the instance is built for (2 / 3 / 4)
     int wcap = 0;            // spline coefficient columns in LDS: NX (the whole table) unless the instance keeps a window
@@ -209,7 +191,7 @@ struct LatticePlan {
     int instance = -1;       // index into kLatticeInstances
 };
 
-// The launch plan.  Decided in dependency order - shape, slices per interval, the window of each occupancy, occupancy and offers, LDS,
+// The launch plan.  Decided in dependency order - shape, grouped or not, the window of each occupancy, occupancy and offers, LDS,
 // tail, grid - and nothing is undone later: a launch whose plan comes out windowed is planned as if no search had been offered (no
 // instance has both; the search then follows in its own launch, and neither the occupancy nor the LDS is gated on it).
 inline LatticePlan plan_lattice(const KernelArgs& ka, const LatticeRequest& rq)
@@ -248,7 +230,10 @@ inline LatticePlan plan_lattice(const KernelArgs& ka, const LatticeRequest& rq)
     const int pstride = poly ? b.poly_stride : 0;  // (polygon columns: their counts - and rings, when they fit - live in LDS)
     const bool inl = rq.inl && rq.inl->on;
     pl.nsplit = !rq.part_scratch || rq.nsplit < 1 ? 1 : rq.nsplit > p.nt ? p.nt : rq.nsplit;
-    // 2. slices per barrier interval (the grouped instances): as asked for, as far as one workgroup's LDS holds them
+    // 2. grouped or not: "lattice_group" as asked for, clamped to [1, group_fit].  Its value only matters as 1 / more than 1: above 1 the
+    // launch takes a grouped instance - workgroups of 1024 threads (twice the wavefronts walking an ego's lon profiles: the latency
+    // instances, for batches that leave every ego a CU to itself) - never three or four per CU, never a coefficient window, never a
+    // tail split (all gated on gs == 1 below).  The host's automatic choice asks for it together with one workgroup per ego (no split).
     int gs = rq.group < 1 ? 1 : (rq.group > p.nt ? p.nt : rq.group);
     if (gs > 1) {
         const int fit = group_fit(p, b);
@@ -257,16 +242,16 @@ inline LatticePlan plan_lattice(const KernelArgs& ka, const LatticeRequest& rq)
     pl.gs = gs;
     pl.threads = gs > 1 ? FP_GROUP_THREADS : kThreads;
     // 3. the coefficient window of each occupancy: when the whole spline does not fit a residency's LDS share, the largest window that
-    // does - if it is at least kWinMin segments (0: not even a useful window fits); no WIN instance with grouped slices
+    // does - if it is at least kWinMin segments (0: not even a useful window fits); no grouped instance has a window
     auto window_for = [&](int cap_bytes, int occ, int ps, bool slim) {
-        const int base = make_layout(b.NX, b.n_obs, rows, hp, p.nd, p.nv, p.nt, item_cap(occ), 1, kThreads / kWave, ps, slim, 0).total;
+        const int base = make_layout(b.NX, b.n_obs, rows, hp, p.nd, p.nv, p.nt, item_cap(occ), kThreads / kWave, ps, slim, 0).total;
         const int w = (cap_bytes - base - 16) / 64;
         if (w >= b.NX) return b.NX;
         return gs == 1 && w >= kWinMin ? w : b.NX;
     };
     const int w6 = window_for(kLdsThird, 6, pstride, false), w8 = window_for(kLdsQuarter, 8, 0, true);
-    const Layout L6 = make_layout(b.NX, b.n_obs, rows, hp, p.nd, p.nv, p.nt, item_cap(6), 1, kThreads / kWave, pstride, false, w6);
-    const Layout L8 = make_layout(b.NX, b.n_obs, rows, hp, p.nd, p.nv, p.nt, item_cap(8), 1, kThreads / kWave, 0, true, w8);
+    const Layout L6 = make_layout(b.NX, b.n_obs, rows, hp, p.nd, p.nv, p.nt, item_cap(6), kThreads / kWave, pstride, false, w6);
+    const Layout L8 = make_layout(b.NX, b.n_obs, rows, hp, p.nd, p.nv, p.nt, item_cap(8), kThreads / kWave, 0, true, w8);
     // 4. occupancy and the offers.  Three workgroups per CU (OCC = 6) when the launch has more egos than two per CU hold at once,
     // nobody needs the series from this kernel (series asked of it pin it to two per CU; series offered to the epilogue workgroups do
     // not) and a workgroup's LDS fits a third of the CU; never for inline inputs (read by the two-per-CU instances only) or a CU with
@@ -292,7 +277,7 @@ inline LatticePlan plan_lattice(const KernelArgs& ka, const LatticeRequest& rq)
     pl.wcap = four ? w8 : three ? w6 : b.NX;  // (two per CU: the whole table)
     pl.series = ka.r.best_traj && (pl.epilogue || (!three && !ka.epi_flag));
     // 5. LDS, tail, grid
-    const Layout L = four ? L8 : three ? L6 : make_layout(b.NX, b.n_obs, rows, hp, p.nd, p.nv, p.nt, item_cap(4), gs, pl.threads / kWave, pstride);
+    const Layout L = four ? L8 : three ? L6 : make_layout(b.NX, b.n_obs, rows, hp, p.nd, p.nv, p.nt, item_cap(4), pl.threads / kWave, pstride);
     if (L.total > kLdsLimit) return LatticePlan{};
     pl.lds = L.total;
     if (pl.epilogue && pl.lds < epi_lds) pl.lds = epi_lds;  // (every workgroup of a launch gets the same dynamic LDS)

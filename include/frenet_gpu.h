@@ -263,10 +263,11 @@ int fp_ctx_destroy(fp_ctx* ctx);
  * "lattice_split": 0 = auto (default: an ego's time-horizon slices are spread over as many workgroups - at most one per
  * slice - as keep ALL workgroups of the launch resident at once, 2 per compute unit: latency mode for small batches), 1 = never,
  * 2 = always one workgroup per slice.  Identical results either way.
- * "lattice_group": time-horizon slices one workgroup's collision stages take per barrier interval.  0 = auto (default: one at a
- * time, except for batches of at most one ego per compute unit that "lattice_split" could only cut in two: one 1024-thread
- * workgroup per ego then takes all nt slices at once, when its LDS holds their tables), 1 = always one at a time, n >= 2 = up to n
- * at a time (as many as fit).  Identical results.
+ * "lattice_group": whether an ego's workgroups have 1024 threads instead of 512 (twice the wavefronts working through its lon
+ * profiles).  0 = auto (default: 512, except for batches of at most one ego per compute unit that "lattice_split" could only cut in
+ * two: one 1024-thread workgroup per ego then takes all nt slices, when its tables fit the LDS), 1 = always 512, n >= 2 = 1024
+ * where its tables fit and the lattice has at least two slices of at most 128 end speeds each; n beyond 2 changes nothing.
+ * Identical results.
  * "lattice_tail": 0 = auto (default: a launch with more one-workgroup egos than stay resident cuts the LAST quarter round of its
  * dispatch slots in two workgroups each - slices split, ticket + merge as in latency mode - so that it does not end on whole egos
  * that started last), 1 = never, n >= 2 = the last n slots.  Identical results.

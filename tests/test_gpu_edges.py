@@ -312,8 +312,8 @@ def test_speed_samples_8bit_profile_index(oracle, engine):
 
 
 def test_grouped_slices_profile_index(oracle, engine):
-    """lattice_group = 99: g slices per barrier interval while g * nv <= 256 - nv = 128 groups two slices, nv = 129 one; both through the
-    fused kernel (it does not refuse: the group shrinks) and equal to the oracle."""
+    """lattice_group = 99: granted as g while g * nv <= 256 (group_fit) - nv = 128 gets two and with it the 1024-thread instance, nv = 129
+    one and the plain instance; both through the fused kernel (it does not refuse: the group shrinks) and equal to the oracle."""
     for nv in (128, 129):
         batch = synth.make_batch(2, 3, nv, 4, 8, 50, True, 3800 + nv)
         ref = [p.fop_plan() for p in oracle.problems_from_batch(batch)]

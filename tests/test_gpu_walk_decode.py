@@ -1,4 +1,4 @@
-"""GPU: the walk's per-profile shortcuts (csrc/frenet_lattice_fused.hip, `if constexpr (kWalk)`), each on the inputs at which it switches.
+"""GPU: the walk's per-profile shortcuts (csrc/frenet_lattice_fused.hip, "WALK"), each on the inputs at which it switches.
 
 * item codes   the shaped instances pack a survivor as row << bits | obstacle (item_shift, frenet_lattice_plan.h); the run-time-shape
                instances keep the table index row * n_obs + obstacle and take it apart by division.  Both, at obstacle counts around the

@@ -46,6 +46,11 @@ CASES = [
     ("grouped", "B=256 nd=5 nv=5 nt=5 obs=10 T_obs=100 group=5"),
     ("grouped_997", "B=256 group=7"),
     ("grouped_runtime", "B=256 nd=5 nv=5 nt=5 obs=12 T_obs=100 group=5"),
+    # lattice_group = 99 takes the 1024-thread instance while two slices' lon profiles number at most 256 (nv = 128 against 129, as in
+    # tests/test_gpu_edges.py) and that instance's layout fits a workgroup's LDS
+    ("grouped_nv128", "B=2 nd=3 nv=128 nt=4 obs=8 group=99"),
+    ("grouped_nv129", "B=2 nd=3 nv=129 nt=4 obs=8 group=99"),
+    ("grouped_lds", "B=256 NX=1250 group=99"),
     ("no_obstacles", "obs=0 S=0"),
     ("no_obstacles_tail", "obs=0 S=0 parts tail=-256"),
     ("knots200", "NX=200"),
@@ -164,6 +169,9 @@ latency_split_clamped plain/2/997 rows=25 hp=51 gs=1 nsplit=7 wcap=81 epi=0 sear
 grouped grouped/2/555 rows=50 hp=101 gs=5 nsplit=1 wcap=81 epi=0 search=0 series=0 tail_from=-1 epi_from=-1 grid=256 lds=92560 threads=1024
 grouped_997 grouped/2/997 rows=25 hp=51 gs=7 nsplit=1 wcap=81 epi=0 search=0 series=0 tail_from=-1 epi_from=-1 grid=256 lds=68288 threads=1024
 grouped_runtime grouped/2/rt rows=50 hp=101 gs=5 nsplit=1 wcap=81 epi=0 search=0 series=0 tail_from=-1 epi_from=-1 grid=256 lds=92624 threads=1024
+grouped_nv128 grouped/2/rt rows=25 hp=51 gs=2 nsplit=1 wcap=81 epi=0 search=0 series=0 tail_from=-1 epi_from=-1 grid=2 lds=89216 threads=1024
+grouped_nv129 plain/2/rt rows=25 hp=51 gs=1 nsplit=1 wcap=81 epi=0 search=0 series=0 tail_from=-1 epi_from=-1 grid=2 lds=73536 threads=512
+grouped_lds plain/2/997 rows=25 hp=51 gs=1 nsplit=1 wcap=1250 epi=0 search=0 series=0 tail_from=-1 epi_from=-1 grid=256 lds=141216 threads=512
 no_obstacles plain/4/rt rows=0 hp=0 gs=1 nsplit=1 wcap=81 epi=0 search=0 series=0 tail_from=-1 epi_from=-1 grid=2048 lds=23056 threads=512
 no_obstacles_tail plain/4/rt rows=0 hp=0 gs=1 nsplit=1 wcap=81 epi=0 search=0 series=0 tail_from=-1 epi_from=-1 grid=2048 lds=23056 threads=512
 knots200 window/4/997 rows=25 hp=51 gs=1 nsplit=1 wcap=61 epi=0 search=0 series=0 tail_from=-1 epi_from=-1 grid=2048 lds=40432 threads=512

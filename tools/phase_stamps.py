@@ -17,7 +17,7 @@ NAMES = ("d_samples", "t_samples", "v_samples", "target_speed", "ego", "frame_of
          "obs_pose", "obs_dims", "final_time_step")
 PHASES = ["scalars + spline tables + obstacle sizes", "LUT + speed bound + lateral extremes", "A0 boundary-value solves + proofs + lateral bound",
           "power sums + point scans + arclength ranges", "cost sums + row circles", "group test G (scene table read) + sincos",
-          "slices: frames / lat / prep / B / N", "assembly + argmin", "results"]
+          "walk: frames / prep / B / N per lon profile", "assembly + argmin", "results"]
 STAMPS = [0, 1, 2, 3, 4, 7, 8, 9, 10]
 
 # usage: phase_stamps.py [config | "b1"] [lattice_split] [lattice_group];  b1 = one ego, 5 x 5 x 5, 27 obstacles (the plan-cycle case)
@@ -52,12 +52,6 @@ print(f"sum of workgroup durations / 512 slots = {stamps[:, -1].sum() / 512:.1f}
 # the walk's imbalance: when the first / the last wavefront of the workgroup ran out of profiles (columns 11, 12)
 print("walk: first wavefront done at {:.2f} us, last at {:.2f} us after the workgroup's start (medians); G ended at {:.2f}: the walk takes {:.2f}, of which {:.2f} is waiting for the slowest wavefront".format(
     np.median(raw[:, 11]), np.median(raw[:, 12]), np.median(raw[:, 7]), np.median(raw[:, 12] - raw[:, 7]), np.median(raw[:, 12] - raw[:, 11])))
-# (slice-loop builds, -DFP_SLICE_LOOP) inside the 4th slice of the workgroup: stamps 11..14 after the frames / prep / B / N barriers
-sl = raw[:, 11:15]
-print("one slice (the 4th):  prep {:.2f}  B {:.2f}  N {:.2f} us (medians);  frames + lat = slice total - these".format(
-    np.median(sl[:, 1] - sl[:, 0]), np.median(sl[:, 2] - sl[:, 1]), np.median(sl[:, 3] - sl[:, 2])))
-print("absolute stamps of that slice / group (us since the workgroup started): after frames+lat {:.2f}, prep {:.2f}, B {:.2f}, N {:.2f}; G ended at {:.2f}".format(
-    *(np.median(sl[:, i]) for i in range(4)), np.median(raw[:, 7])))
 
 # occupancy of the launch over time: workgroups running at every instant (absolute starts in column 15)
 t0 = raw[:, 15] - raw[:, 15].min()
