@@ -32,7 +32,7 @@ _up = C.POINTER(C.c_uint32)
 
 # every symbol include/frenet_gpu.h declares (tests check the library exports all of them)
 EXPORTED_SYMBOLS = ("fp_abi_version", "fp_build_flags", "fp_build_compiler", "fp_last_error", "fp_device_count", "fp_device_info", "fp_ctx_create", "fp_ctx_destroy", "fp_ctx_set_option", "fp_ctx_get_option", "fp_ctx_join",
-                    "fp_plan_dense", "fp_winner_trajs", "fp_rank_feasible", "fp_boundary_mask", "fp_speed_envelope", "fp_gate_mask", "fp_gap_mask", "fp_traj_margins", "fp_obstacles_predict", "fp_eval_trajs", "fp_plan_fiss", "fp_advance", "fp_plan_step", "fp_plan_fiss_step", "fp_loop_record", "fp_frames_build", "fp_from_state", "fp_materialize_all",
+                    "fp_plan_dense", "fp_winner_trajs", "fp_rank_feasible", "fp_boundary_mask", "fp_speed_envelope", "fp_gate_mask", "fp_gap_mask", "fp_rules_eval", "fp_traj_margins", "fp_obstacles_predict", "fp_eval_trajs", "fp_plan_fiss", "fp_advance", "fp_plan_step", "fp_plan_fiss_step", "fp_loop_record", "fp_frames_build", "fp_from_state", "fp_materialize_all",
                     "fp_group_create", "fp_group_destroy", "fp_group_submit", "fp_group_wait")
 
 
@@ -81,6 +81,16 @@ class FpGates(C.Structure):
 class FpTimeGap(C.Structure):
     """A time gap to moving obstacles, in steps of tick_t (fp_gap_mask)."""
     _fields_ = [("lag_follow", C.c_int32), ("lag_lead", C.c_int32), ("first", C.c_int32), ("reserved0", C.c_int32)]
+
+
+# fp_rules_eval: which rule an explicit end state violates (rule_bits), and the columns of its per-ego counts (log2 of the bit)
+RULE_LIMIT, RULE_LATERAL, RULE_GATE, RULE_BOUNDARY, RULE_GAP = 1, 2, 4, 8, 16
+FP_RULE_COUNT = 5
+
+
+class FpRuleSet(C.Structure):
+    """The rules fp_rules_eval evaluates: a pointer to each rule's own struct, NULL = that rule is off."""
+    _fields_ = [("envelope", C.POINTER(FpSpeedProfile)), ("gates", C.POINTER(FpGates)), ("boundary", C.POINTER(FpCorridor)), ("gaps", C.POINTER(FpTimeGap))]
 
 
 FP_TRACK_NONE, FP_TRACK_LANE, FP_TRACK_ARC = 0, 1, 2  # fp_tracks.model (fp_obstacles_predict)
@@ -195,6 +205,9 @@ def load() -> C.CDLL:
     if hasattr(L, "fp_gap_mask"):  # (likewise)
         L.fp_gap_mask.argtypes = [C.c_void_p, C.POINTER(FpParams), C.POINTER(FpBatch), C.POINTER(FpTimeGap), C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    if hasattr(L, "fp_rules_eval"):  # (likewise)
+        L.fp_rules_eval.argtypes = [C.c_void_p, C.POINTER(FpParams), C.POINTER(FpBatch), C.POINTER(FpRuleSet), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_int, C.c_void_p]
     L.fp_traj_margins.argtypes = [C.c_void_p, C.POINTER(FpParams), C.POINTER(FpBatch), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_int, C.c_void_p]
     L.fp_obstacles_predict.argtypes = [C.c_void_p, C.POINTER(FpParams), C.POINTER(FpBatch), C.POINTER(FpTracks), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]

@@ -198,6 +198,7 @@ struct fp_ctx {
     int envelope_launches = 0;     // fp_ctx_get_option("envelope_launches"): launches of the speed-envelope kernel (fp_speed_envelope)
     int gate_launches = 0;         // fp_ctx_get_option("gate_launches"): launches of the gate kernel (fp_gate_mask)
     int gap_launches = 0;          // fp_ctx_get_option("gap_launches"): launches of the time-gap kernel (fp_gap_mask)
+    int rules_eval_launches = 0;   // fp_ctx_get_option("rules_eval_launches"): launches of the rules kernel (fp_rules_eval)
     int margin_launches = 0;       // fp_ctx_get_option("margin_launches"): launches of the plan-margin kernel (fp_traj_margins)
     int predict_launches = 0;      // fp_ctx_get_option("predict_launches"): launches of the obstacle prediction kernel (fp_obstacles_predict)
     int from_state_launches = 0;   // fp_ctx_get_option("from_state_launches"): launches of the projection kernel (fp_from_state)
@@ -379,12 +380,12 @@ int check_frames_host(const fp_batch* b)
 }
 
 // ... and everything else a planning call reads
-int check_batch_host(const fp_params* p, const fp_batch* b)
+int check_batch_host(const fp_params* p, const fp_batch* b, bool past_ok = false)  // (past_ok: the call reads a clock before step 0 like fp_gate_mask)
 {
     FP_TRY(check_frames_host(b));
     for (int i = 0; i < b->B; ++i) {
         if (b->scene_of[i] >= b->S) return fail(FP_EINVAL, "scene_of[%d]=%d out of range", i, b->scene_of[i]);
-        if (b->t_now[i] < 0) return fail(FP_EINVAL, "t_now[%d]=%d is negative", i, b->t_now[i]);
+        if (b->t_now[i] < 0 && !past_ok) return fail(FP_EINVAL, "t_now[%d]=%d is negative", i, b->t_now[i]);
     }
     for (int k = 0; k < p->nt; ++k) {
         const double n = b->t_samples[k] / p->tick_t;
@@ -429,6 +430,59 @@ void stage_samples(StageList& sl, const fp_params* p, const fp_batch* b, const d
     sl.in(b->d_samples, (size_t)p->nd, d_samples);
     sl.in(b->t_samples, (size_t)p->nt, t_samples);
     sl.in(b->v_samples, (size_t)b->B * p->nv, v_samples);
+}
+
+// The argument checks of the four rules, shared by each rule's own pass and fp_rules_eval: the same conditions, the same messages.
+// The *_host halves look into the arrays, which only a FP_MEM_HOST call can.
+int check_corridor(const fp_corridor* corridor)
+{
+    if (!corridor || !corridor->left || !corridor->right) return fail(FP_EINVAL, "fp_boundary_mask: corridor / left / right must not be NULL");
+    if (!finite_nonneg(corridor->margin)) return fail(FP_EINVAL, "fp_boundary_mask: margin must be finite and >= 0");
+    return FP_OK;
+}
+int check_corridor_host(const fp_corridor* corridor, const fp_batch* batch)
+{
+    for (int f = 0; f < batch->F; ++f)
+        for (int k = 0; k < batch->nx[f]; ++k) {
+            const double l = corridor->left[(size_t)f * batch->NX + k], r = corridor->right[(size_t)f * batch->NX + k];
+            if (!(l == l) || !(r == r)) return fail(FP_EINVAL, "fp_boundary_mask: corridor has a NaN at frame %d, knot %d (+-inf says \"no edge\")", f, k);
+        }
+    return FP_OK;
+}
+int check_speed_profile(const fp_speed_profile* profile, const fp_batch* batch)
+{
+    if (!profile || !profile->v_limit) return fail(FP_EINVAL, "fp_speed_envelope: profile / v_limit must not be NULL");
+    if (!finite_nonneg(profile->front)) return fail(FP_EINVAL, "fp_speed_envelope: front must be finite and >= 0");
+    if (!finite_nonneg(profile->tol)) return fail(FP_EINVAL, "fp_speed_envelope: tol must be finite and >= 0");
+    if (!finite_nonneg(profile->max_lat_accel)) return fail(FP_EINVAL, "fp_speed_envelope: max_lat_accel must be finite and >= 0 (0 = off)");
+    if (profile->max_lat_accel > 0 && !batch->coef) return fail(FP_EINVAL, "fp_speed_envelope: max_lat_accel > 0 needs batch->coef");
+    return FP_OK;
+}
+int check_speed_profile_host(const fp_speed_profile* profile, const fp_batch* batch)
+{
+    for (int f = 0; f < batch->F; ++f)
+        for (int k = 0; k + 1 < batch->nx[f]; ++k) {
+            const double l = profile->v_limit[(size_t)f * batch->NX + k];
+            if (!(l >= 0)) return fail(FP_EINVAL, "fp_speed_envelope: v_limit is %g at frame %d, knot %d (+inf says \"no limit\", 0 \"stop\")", l, f, k);
+        }
+    return FP_OK;
+}
+int check_gates(const fp_gates* gates)
+{
+    if (!gates || !gates->gate_s || !gates->closed) return fail(FP_EINVAL, "fp_gate_mask: gates / gate_s / closed must not be NULL");
+    if (gates->gate_stride < 1 || gates->gate_stride > FP_MAX_GATES) return fail(FP_EINVAL, "fp_gate_mask: gate_stride=%d outside 1..FP_MAX_GATES", gates->gate_stride);
+    if (gates->T_gate < 1) return fail(FP_EINVAL, "fp_gate_mask: T_gate=%d must be >= 1", gates->T_gate);
+    if (!finite_nonneg(gates->front)) return fail(FP_EINVAL, "fp_gate_mask: front must be finite and >= 0");
+    if (!finite_nonneg(gates->max_decel)) return fail(FP_EINVAL, "fp_gate_mask: max_decel must be finite and >= 0 (0 = off)");
+    return FP_OK;
+}
+int check_time_gap(const fp_time_gap* gap)
+{
+    if (!gap) return fail(FP_EINVAL, "fp_gap_mask: gap must not be NULL");
+    if (gap->lag_follow < 0 || gap->lag_follow > FP_MAX_POINTS) return fail(FP_EINVAL, "fp_gap_mask: lag_follow=%d outside 0..FP_MAX_POINTS", gap->lag_follow);
+    if (gap->lag_lead < 0 || gap->lag_lead > FP_MAX_POINTS) return fail(FP_EINVAL, "fp_gap_mask: lag_lead=%d outside 0..FP_MAX_POINTS", gap->lag_lead);
+    if (gap->first < 1) return fail(FP_EINVAL, "fp_gap_mask: first=%d must be >= 1", gap->first);
+    return FP_OK;
 }
 
 // The argument block the table passes behind the dense pass share (fp::TablePassArgs), holding the caller's arrays as they were given:
@@ -1414,7 +1468,7 @@ int fp_ctx_get_option(fp_ctx* ctx, const char* name, int* value)
     const struct { const char* n; int v; } tab[] = {
         {"lattice_kernel", ctx->lattice_kernel}, {"lattice_split", ctx->lattice_split}, {"lattice_group", ctx->lattice_group}, {"lattice_tail", ctx->lattice_tail}, {"lattice_occupancy", ctx->lattice_occupancy}, {"resident_groups", ctx->resident_groups}, {"zero_copy_in", ctx->zero_copy_in}, {"stage_kernel", ctx->stage_kernel}, {"inline_inputs", ctx->inline_inputs}, {"lattice_order", ctx->lattice_order},
         {"refine_table_kb", ctx->refine_table_kb}, {"fiss_stages", ctx->fiss_stages}, {"fiss_jump", ctx->fiss_jump}, {"validate", ctx->validate}, {"lattice_winner", ctx->lattice_winner}, {"fiss_fused", ctx->fiss_fused}, {"appended_workgroups", ctx->appended_ok ? 1 : 0}, {"handover_failed", ctx->hand_err ? *(volatile int32_t*)ctx->hand_err : 0}, {"overlap", ctx->overlap}, {"overlapped_calls", ctx->overlapped_calls}, {"clearance_launches", ctx->clearance_launches + (ctx->twin ? ctx->twin->clearance_launches : 0)}, {"lattice_launches", ctx->lattice_launches + (ctx->twin ? ctx->twin->lattice_launches : 0)},
-        {"looplog_launches", ctx->looplog_launches}, {"rank_launches", ctx->rank_launches}, {"boundary_launches", ctx->boundary_launches}, {"envelope_launches", ctx->envelope_launches}, {"gate_launches", ctx->gate_launches}, {"gap_launches", ctx->gap_launches}, {"margin_launches", ctx->margin_launches}, {"predict_launches", ctx->predict_launches}, {"from_state_launches", ctx->from_state_launches}, {"lattice_ordered_launches", ctx->lattice_ordered_launches + (ctx->twin ? ctx->twin->lattice_ordered_launches : 0)},
+        {"looplog_launches", ctx->looplog_launches}, {"rank_launches", ctx->rank_launches}, {"boundary_launches", ctx->boundary_launches}, {"envelope_launches", ctx->envelope_launches}, {"gate_launches", ctx->gate_launches}, {"gap_launches", ctx->gap_launches}, {"margin_launches", ctx->margin_launches}, {"rules_eval_launches", ctx->rules_eval_launches}, {"predict_launches", ctx->predict_launches}, {"from_state_launches", ctx->from_state_launches}, {"lattice_ordered_launches", ctx->lattice_ordered_launches + (ctx->twin ? ctx->twin->lattice_ordered_launches : 0)},
         {"lattice_launches_2", (int)fp::lattice_launches_per_cu(0)}, {"lattice_launches_3", (int)fp::lattice_launches_per_cu(1)}, {"lattice_launches_4", (int)fp::lattice_launches_per_cu(2)}};
     for (const auto& t : tab)
         if (strcmp(name, t.n) == 0) { *value = t.v; return FP_OK; }
@@ -1601,9 +1655,9 @@ int fp_boundary_mask(fp_ctx* ctx, const fp_params* params, const fp_batch* batch
                      uint32_t* flag_tbl, int32_t* best_idx, double* best_cost, int32_t* n_masked, int mem, void* stream)
 {
     FP_TRY(common_checks(ctx, params, batch, mem, stream));
-    if (!corridor || !corridor->left || !corridor->right) return fail(FP_EINVAL, "fp_boundary_mask: corridor / left / right must not be NULL");
+    if (!corridor || !corridor->left || !corridor->right) return check_corridor(corridor);
     if (!cost_tbl || !flag_tbl || !best_idx || !best_cost) return fail(FP_EINVAL, "fp_boundary_mask: cost_tbl/flag_tbl/best_idx/best_cost must not be NULL");
-    if (!finite_nonneg(corridor->margin)) return fail(FP_EINVAL, "fp_boundary_mask: margin must be finite and >= 0");
+    FP_TRY(check_corridor(corridor));
     if (batch->B == 0) return FP_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     fp::BoundaryArgs a;
@@ -1616,11 +1670,7 @@ int fp_boundary_mask(fp_ctx* ctx, const fp_params* params, const fp_batch* batch
         return FP_OK;
     }
     FP_TRY(check_frames_host(batch));
-    for (int f = 0; f < batch->F; ++f)
-        for (int k = 0; k < batch->nx[f]; ++k) {
-            const double l = corridor->left[(size_t)f * batch->NX + k], r = corridor->right[(size_t)f * batch->NX + k];
-            if (!(l == l) || !(r == r)) return fail(FP_EINVAL, "fp_boundary_mask: corridor has a NaN at frame %d, knot %d (+-inf says \"no edge\")", f, k);
-        }
+    FP_TRY(check_corridor_host(corridor, batch));
     const size_t fn = (size_t)batch->F * batch->NX;
     HostStage hs(ctx);
     StageList sl;
@@ -1639,13 +1689,10 @@ int fp_speed_envelope(fp_ctx* ctx, const fp_params* params, const fp_batch* batc
                       uint32_t* flag_tbl, int32_t* best_idx, double* best_cost, int32_t* n_limited, int mem, void* stream)
 {
     FP_TRY(common_checks(ctx, params, batch, mem, stream, /*need_coef=*/false));  // (coef is read by the lateral check alone: see below)
-    if (!profile || !profile->v_limit) return fail(FP_EINVAL, "fp_speed_envelope: profile / v_limit must not be NULL");
+    if (!profile || !profile->v_limit) return check_speed_profile(profile, batch);
     if (!cost_tbl || !flag_tbl || !best_idx || !best_cost) return fail(FP_EINVAL, "fp_speed_envelope: cost_tbl/flag_tbl/best_idx/best_cost must not be NULL");
-    if (!finite_nonneg(profile->front)) return fail(FP_EINVAL, "fp_speed_envelope: front must be finite and >= 0");
-    if (!finite_nonneg(profile->tol)) return fail(FP_EINVAL, "fp_speed_envelope: tol must be finite and >= 0");
-    if (!finite_nonneg(profile->max_lat_accel)) return fail(FP_EINVAL, "fp_speed_envelope: max_lat_accel must be finite and >= 0 (0 = off)");
+    FP_TRY(check_speed_profile(profile, batch));
     const bool lateral = profile->max_lat_accel > 0;
-    if (lateral && !batch->coef) return fail(FP_EINVAL, "fp_speed_envelope: max_lat_accel > 0 needs batch->coef");
     if (batch->B == 0) return FP_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     fp::EnvelopeArgs a;
@@ -1658,11 +1705,7 @@ int fp_speed_envelope(fp_ctx* ctx, const fp_params* params, const fp_batch* batc
         return FP_OK;
     }
     FP_TRY(check_frames_host(batch));
-    for (int f = 0; f < batch->F; ++f)
-        for (int k = 0; k + 1 < batch->nx[f]; ++k) {
-            const double l = profile->v_limit[(size_t)f * batch->NX + k];
-            if (!(l >= 0)) return fail(FP_EINVAL, "fp_speed_envelope: v_limit is %g at frame %d, knot %d (+inf says \"no limit\", 0 \"stop\")", l, f, k);
-        }
+    FP_TRY(check_speed_profile_host(profile, batch));
     const size_t fn = (size_t)batch->F * batch->NX;
     HostStage hs(ctx);
     StageList sl;
@@ -1680,12 +1723,9 @@ int fp_gate_mask(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, co
                  int32_t* best_idx, double* best_cost, int32_t* n_gated, int mem, void* stream)
 {
     FP_TRY(common_checks(ctx, params, batch, mem, stream, /*need_coef=*/false));  // (the line's coefficients are not read)
-    if (!gates || !gates->gate_s || !gates->closed) return fail(FP_EINVAL, "fp_gate_mask: gates / gate_s / closed must not be NULL");
+    if (!gates || !gates->gate_s || !gates->closed) return check_gates(gates);
     if (!cost_tbl || !flag_tbl || !best_idx || !best_cost) return fail(FP_EINVAL, "fp_gate_mask: cost_tbl/flag_tbl/best_idx/best_cost must not be NULL");
-    if (gates->gate_stride < 1 || gates->gate_stride > FP_MAX_GATES) return fail(FP_EINVAL, "fp_gate_mask: gate_stride=%d outside 1..FP_MAX_GATES", gates->gate_stride);
-    if (gates->T_gate < 1) return fail(FP_EINVAL, "fp_gate_mask: T_gate=%d must be >= 1", gates->T_gate);
-    if (!finite_nonneg(gates->front)) return fail(FP_EINVAL, "fp_gate_mask: front must be finite and >= 0");
-    if (!finite_nonneg(gates->max_decel)) return fail(FP_EINVAL, "fp_gate_mask: max_decel must be finite and >= 0 (0 = off)");
+    FP_TRY(check_gates(gates));
     if (batch->B == 0) return FP_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     fp::GateArgs a;
@@ -1720,11 +1760,9 @@ int fp_gap_mask(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, con
                 int32_t* best_idx, double* best_cost, int32_t* n_close, int mem, void* stream)
 {
     FP_TRY(common_checks(ctx, params, batch, mem, stream));
-    if (!gap) return fail(FP_EINVAL, "fp_gap_mask: gap must not be NULL");
+    if (!gap) return check_time_gap(gap);
     if (!cost_tbl || !flag_tbl || !best_idx || !best_cost) return fail(FP_EINVAL, "fp_gap_mask: cost_tbl/flag_tbl/best_idx/best_cost must not be NULL");
-    if (gap->lag_follow < 0 || gap->lag_follow > FP_MAX_POINTS) return fail(FP_EINVAL, "fp_gap_mask: lag_follow=%d outside 0..FP_MAX_POINTS", gap->lag_follow);
-    if (gap->lag_lead < 0 || gap->lag_lead > FP_MAX_POINTS) return fail(FP_EINVAL, "fp_gap_mask: lag_lead=%d outside 0..FP_MAX_POINTS", gap->lag_lead);
-    if (gap->first < 1) return fail(FP_EINVAL, "fp_gap_mask: first=%d must be >= 1", gap->first);
+    FP_TRY(check_time_gap(gap));
     if (batch->B == 0) return FP_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t B = (size_t)batch->B, C = (size_t)params->nd * params->nv * params->nt;
@@ -1758,6 +1796,85 @@ int fp_gap_mask(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, con
     FP_TRY(hs.commit(sl, rg));
     LAUNCH_TRY(fp::launch_gap_mask(ka, g, ctx->stream), "time-gap kernel");
     ++ctx->gap_launches;
+    return hs.fetch_out();
+}
+
+int fp_rules_eval(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, const fp_rule_set* rules, int32_t K, const double* end_states,
+                  uint32_t* flags, uint32_t* rule_bits, int32_t* counts, int mem, void* stream)
+{
+    FP_TRY(common_checks(ctx, params, batch, mem, stream));
+    if (K < 1) return fail(FP_EINVAL, "fp_rules_eval: K=%d must be >= 1", K);
+    if (!rules || !end_states || !flags) return fail(FP_EINVAL, "fp_rules_eval: rules / end_states / flags must not be NULL");
+    if (!rules->envelope && !rules->gates && !rules->boundary && !rules->gaps) return fail(FP_EINVAL, "fp_rules_eval: every rule of the set is NULL");
+    if (rules->envelope) FP_TRY(check_speed_profile(rules->envelope, batch));
+    if (rules->gates) FP_TRY(check_gates(rules->gates));
+    if (rules->boundary) FP_TRY(check_corridor(rules->boundary));
+    if (rules->gaps) FP_TRY(check_time_gap(rules->gaps));
+    if (batch->B == 0) return FP_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t B = (size_t)batch->B, BK = B * (size_t)K;
+    fp::KernelArgs ka;
+    ka.p = *params;
+    ka.r = no_result();
+    fp::RulesEvalArgs a;
+    a.K = K;
+    if (const fp_speed_profile* e = rules->envelope) {
+        a.on |= FP_RULE_LIMIT | (e->max_lat_accel > 0 ? FP_RULE_LATERAL : 0u);
+        a.env_front = e->front; a.env_tol = e->tol; a.max_lat_accel = e->max_lat_accel; a.v_limit = e->v_limit;
+    }
+    if (const fp_gates* g = rules->gates) {
+        a.on |= FP_RULE_GATE;
+        a.gate_front = g->front; a.max_decel = g->max_decel; a.gate_stride = g->gate_stride; a.T_gate = g->T_gate;
+        a.gate_s = g->gate_s; a.closed = g->closed;
+    }
+    if (const fp_corridor* c = rules->boundary) {
+        a.on |= FP_RULE_BOUNDARY;
+        a.margin = c->margin; a.left = c->left; a.right = c->right;
+    }
+    if (const fp_time_gap* t = rules->gaps) {
+        a.on |= FP_RULE_GAP;
+        a.lag_follow = t->lag_follow; a.lag_lead = t->lag_lead;
+        a.first = t->first < FP_MAX_POINTS ? t->first : FP_MAX_POINTS;  // (points are 0 .. FP_MAX_POINTS - 1: anything above is "beyond every pose")
+    }
+    if (mem == FP_MEM_DEVICE) {
+        ka.b = *batch;
+        if (!(batch->S > 0 && batch->n_obs > 0)) ka.b.n_obs = 0;
+        a.end_states = end_states; a.flags = flags; a.rule_bits = rule_bits; a.counts = counts; a.perm = batch->launch_order;
+        LAUNCH_TRY(fp::launch_rules_eval(ka, a, (hipStream_t)stream), "rules kernel");
+        ++ctx->rules_eval_launches;
+        return FP_OK;
+    }
+    FP_TRY(check_batch_host(params, batch, /*past_ok=*/true));  // (a negative t_now reads the gates' first state; no obstacle has a state before step 0)
+    if (rules->envelope) FP_TRY(check_speed_profile_host(rules->envelope, batch));
+    if (rules->boundary) FP_TRY(check_corridor_host(rules->boundary, batch));
+    for (size_t i = 0; i < BK; ++i) {
+        const double n = end_states[3 * i + 2] / params->tick_t;
+        if (n != n || (batch->skip && batch->skip[i / (size_t)K])) continue;  // NaN end state = "no trajectory"
+        if (!(n > 0) || n > FP_MAX_POINTS)
+            return fail(FP_ELIMIT, "fp_rules_eval: end_states of ego %zu, trajectory %zu: T=%g needs 1..FP_MAX_POINTS points", i / (size_t)K, i % (size_t)K, end_states[3 * i + 2]);
+    }
+    ka.p.points_max = host_points_max(params, batch, end_states + 2, BK, 3);
+    const size_t fn = (size_t)batch->F * batch->NX, F = (size_t)batch->F;
+    HostStage hs(ctx);
+    StageList sl;
+    StageRegime rg;  // (throughput)
+    FP_TRY(stage_batch(ctx, sl, rg, params, batch, &ka.b));
+    if (rules->envelope) sl.in(a.v_limit, fn, &a.v_limit);
+    if (rules->gates) {
+        sl.in(a.gate_s, F * a.gate_stride, &a.gate_s);
+        sl.in(a.closed, F * a.T_gate, &a.closed);
+    }
+    if (rules->boundary) {
+        sl.in(a.left, fn, &a.left);
+        sl.in(a.right, fn, &a.right);
+    }
+    sl.in(end_states, BK * 3, &a.end_states);
+    sl.in_mut(flags, BK, &a.flags);
+    sl.out(rule_bits, BK, &a.rule_bits);
+    if (counts) sl.in_mut(counts, B * FP_RULE_COUNT, &a.counts);
+    FP_TRY(hs.commit(sl, rg));
+    LAUNCH_TRY(fp::launch_rules_eval(ka, a, ctx->stream), "rules kernel");
+    ++ctx->rules_eval_launches;
     return hs.fetch_out();
 }
 

@@ -23,6 +23,7 @@
 #include "frenet_device.h"
 #include "frenet_kernels.h"
 #include "frenet_project.h"
+#include "frenet_rules.h"
 
 namespace fp {
 
@@ -56,19 +57,7 @@ __global__ __launch_bounds__(kBoundThreads) void boundary_mask_kernel(BoundaryAr
     const double* gk = a.knots + (size_t)f * a.NX;
     const double* gl = a.left + (size_t)f * a.NX;
     const double* gr = a.right + (size_t)f * a.NX;
-    for (int i = tid; i < nx; i += kBoundThreads) {
-        const double k0 = gk[i];
-        knots[i] = k0;
-        if (i + 1 < nx) {
-            const double inv = 1.0 / (gk[i + 1] - k0);
-            const double la = gl[i], lb = gl[i + 1], ra = gr[i], rb = gr[i + 1];
-            const bool lfin = finite_f64(la) && finite_f64(lb), rfin = finite_f64(ra) && finite_f64(rb);
-            l0[i] = lfin ? la : __builtin_inf();
-            l1[i] = lfin ? (lb - la) * inv : 0.0;
-            r0[i] = rfin ? ra : -__builtin_inf();
-            r1[i] = rfin ? (rb - ra) * inv : 0.0;
-        }
-    }
+    stage_corridor(gk, gl, gr, nx, knots, l0, l1, r0, r1, tid, kBoundThreads);
     const double* eg = a.ego + (size_t)b * 6;
     const double s0 = eg[0], s_d0 = eg[1], s_dd0 = eg[2], d0 = eg[3], d_d0 = eg[4], d_dd0 = eg[5];
     const double* vs = a.v_samples + (size_t)b * nv;
@@ -129,18 +118,7 @@ __global__ __launch_bounds__(kBoundThreads) void boundary_mask_kernel(BoundaryAr
             for (int i0 = 1; i0 < M; i0 += kWave) {
                 const int i = i0 + lane;
                 bool viol = false;
-                if (i < M) {
-                    const double t = (double)i * tick;
-                    double s, s_d, d, d_d, unused_a, unused_j;
-                    quartic_eval(lon, t, s, s_d, unused_a, unused_j);
-                    quintic_eval(lat, t, d, d_d, unused_a, unused_j);
-                    const int k = spline_segment_clamped(sp, s, guess_scale);  // (a point below M lies on the line)
-                    const double ds = s - knots[k];
-                    const double L = fma(l1[k], ds, l0[k]), R = fma(r1[k], ds, r0[k]);
-                    const double r = hypot(s_d, d_d);
-                    const double h = r == 0.0 ? hw : (hw * fabs(s_d) + hl * fabs(d_d)) / r;
-                    viol = (d + h) + margin > L || (d - h) - margin < R;
-                }
+                if (i < M) viol = boundary_point(sp, l0, l1, r0, r1, guess_scale, lon, lat, (double)i * tick, hw, hl, margin);
                 if (__ballot(viol)) {  // one violation decides the candidate
                     out = true;
                     break;

@@ -23,6 +23,7 @@
 // No atomics, no scratch, every reduction a fixed tree or a ballot: two runs give the same bits.
 #include "frenet_device.h"
 #include "frenet_kernels.h"
+#include "frenet_rules.h"
 
 namespace fp {
 
@@ -79,24 +80,7 @@ __global__ __launch_bounds__(kEnvThreads) void speed_envelope_kernel(EnvelopeArg
             for (int i0 = 1; i0 < M; i0 += kWave) {
                 const int i = i0 + lane;
                 bool fast = false, lat = false;
-                if (i < M) {
-                    double s, s_d, unused_a, unused_j;
-                    quartic_eval(lon, (double)i * tick, s, s_d, unused_a, unused_j);
-                    const double s_q = s + front;
-                    int k = spline_segment_clamped(sp, s_q, guess_scale);
-                    fast = s_d > lim[k] + tol;  // (+inf, and a NaN, compare false: no limit there)
-                    if (lateral) {
-                        k = spline_segment_clamped(sp, s, guess_scale);
-                        const double dx = s - knots[k];
-                        const double* c = coef + k;
-                        const double bx = c[nx], cx = c[2 * nx], dx3 = c[3 * nx], by = c[5 * nx], cy = c[6 * nx], dy3 = c[7 * nx];
-                        const double gx = fma(fma(3.0 * dx3, dx, 2.0 * cx), dx, bx), gy = fma(fma(3.0 * dy3, dx, 2.0 * cy), dx, by);
-                        const double hx = fma(6.0 * dx3, dx, 2.0 * cx), hy = fma(6.0 * dy3, dx, 2.0 * cy);
-                        const double g2 = fma(gx, gx, gy * gy);
-                        const double kappa = fma(gx, hy, -(gy * hx)) / (g2 * sqrt(g2));
-                        lat = s_d * s_d * fabs(kappa) > max_lat;
-                    }
-                }
+                if (i < M) envelope_point(sp, lim, guess_scale, lon, (double)i * tick, front, tol, lateral, max_lat, fast, lat);
                 if (__ballot(fast)) bits |= FP_FLAG_SPEED;
                 if (__ballot(lat)) bits |= FP_FLAG_ACCEL;
                 if (bits == want) break;  // every bit the profile can get is found

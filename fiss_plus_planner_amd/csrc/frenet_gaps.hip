@@ -24,6 +24,7 @@
 #include "frenet_device.h"
 #include "frenet_kernels.h"
 #include "frenet_ego.h"
+#include "frenet_rules.h"
 
 namespace fp {
 
@@ -46,9 +47,6 @@ __device__ __forceinline__ float f32_up(double v)
     const float f = (float)v;
     return (double)f < v ? nextafterf(f, __builtin_inff()) : f;
 }
-// centre distance beyond which an ego box of circumradius r_e and column j cannot touch, widened past any rounding of the compare
-__device__ __forceinline__ double gap_reach(const EgoCtx& e, double r_e, int j) { return (r_e + e.obs_dim[4 * j + 2]) * (1.0 + 1e-9) + 1e-9; }
-
 __global__ __launch_bounds__(kGapThreads) void gap_mask_kernel(KernelArgs ka, GapArgs g, int lds_doubles)
 {
     extern __shared__ __attribute__((aligned(16))) double lds[];
@@ -73,17 +71,7 @@ __global__ __launch_bounds__(kGapThreads) void gap_mask_kernel(KernelArgs ka, Ga
     const double inf = __builtin_inf();
     const double hl = 0.5 * p.veh_l, hw = 0.5 * p.veh_w;
     const double r_e = sqrt(fma(hl, hl, hw * hw));
-    // grid poses q = i / cs the ego's horizon and table hold (stage_ego's row count): q < G <=> q cs < final_time_step - t_now, the
-    // call's points and T_obs - t_now
-    int G = 0;
-    if (n_obs > 0) {
-        int hmax = e.horizon_cap < points_cap(p) ? e.horizon_cap : points_cap(p);
-        if (hmax < 0) hmax = 0;
-        G = (hmax + cs - 1) / cs;
-        const int in_table = e.T_obs - e.t_now;
-        const int rows_tab = in_table > 0 ? (in_table + cs - 1) / cs : 0;
-        if (rows_tab < G) G = rows_tab;
-    }
+    const int G = gap_grid_poses(p, e);  // grid poses q = i / cs the ego's horizon and table hold
     const bool active = G > 0 && (Lf > 0 || Ll > 0);  // (block-uniform)
     // ---- cull table [G][n_obs]: x_min, y_min, x_max, y_max of where the ego's centre can be and still reach the column at a paired row
     const float4* bound = nullptr;
@@ -157,27 +145,7 @@ __global__ __launch_bounds__(kGapThreads) void gap_mask_kernel(KernelArgs ka, Ga
                     bool hit = false;
                     Obb ego;
                     if (q < n_pose && a + e.t_now >= 0 && checked_pose(p, e.sp, guess_scale, lon, lat, a, M, ego)) {
-                        const int lo = q - Lf > 0 ? q - Lf : 0, hi = q + Ll < n_pose - 1 ? q + Ll : n_pose - 1;
-                        for (int j = sub; j < n_obs && !hit; j += split) {
-                            if (bound) {
-                                const float4 bb = bound[q * n_obs + j];
-                                if (!(ego.x >= (double)bb.x && ego.x <= (double)bb.z && ego.y >= (double)bb.y && ego.y <= (double)bb.w)) continue;
-                            }
-                            const double R = gap_reach(e, r_e, j);
-                            for (int qr = lo; qr <= hi; ++qr) {
-                                if (qr == q) continue;  // lag 0 is the collision check's
-                                const double* row = obs_row(e, qr * cs, cs);
-                                double ox, oy, oc, os;
-                                if (!row || !obs_centre(e, row, j, ox, oy)) continue;
-                                const double dx = ox - ego.x, dy = oy - ego.y;
-                                if (!(fma(dx, dx, dy * dy) <= R * R)) continue;
-                                obs_heading(e, row, j, oc, os);
-                                const int nvert = obs_nvert(ka, e, j);
-                                hit = nvert > 0 ? poly_overlap(ego, ox, oy, oc, os, obs_ring(ka, e, j), nvert)
-                                                : obb_overlap(ego, Obb{ox, oy, oc, os, e.obs_dim[4 * j], e.obs_dim[4 * j + 1]});
-                                if (hit) break;
-                            }
-                        }
+                        hit = gap_pose_hit(ka, e, ego, q, n_pose, Lf, Ll, sub, split, bound, r_e, cs, n_obs);
                     }
                     if (__ballot(hit)) {
                         flagged = true;

@@ -20,6 +20,7 @@
 // No atomics, no scratch, every reduction a fixed tree or a ballot: two runs give the same bits.
 #include "frenet_device.h"
 #include "frenet_kernels.h"
+#include "frenet_rules.h"
 
 namespace fp {
 
@@ -55,15 +56,14 @@ __global__ __launch_bounds__(kGateThreads) void gate_mask_kernel(GateArgs a)
         if (lane < a.gate_stride) {
             g = a.gate_s[(size_t)f * a.gate_stride + lane];
             // the dilemma zone: the ego is in front of the line and cannot stop there any more
-            if (a.max_decel > 0.0 && s_d0 > 0.0 && q0 <= g && q0 + s_d0 * s_d0 / (2.0 * a.max_decel) > g) g = __builtin_nan("");
+            if (gate_waived(a.max_decel, s_d0, q0, g)) g = __builtin_nan("");
         }
         if (lane < FP_MAX_GATES) line[lane] = g;
         const unsigned long long live = __ballot(g == g);
         if (lane == 0) s_live = (uint32_t)live;
     }
     for (int i = tid; i < cap; i += kGateThreads) {
-        const long long t = tn + 1 + i;
-        word[i] = closed[t < 0 ? 0 : (t > t_last ? t_last : (int)t)];  // (the first / the last known state holds)
+        word[i] = gate_word(closed, tn + 1 + i, t_last);  // (the first / the last known state holds)
     }
     __syncthreads();
     const uint32_t live = s_live;
@@ -84,19 +84,10 @@ __global__ __launch_bounds__(kGateThreads) void gate_mask_kernel(GateArgs a)
                     if (i <= cap) {
                         w = word[i - 1];
                     } else {  // (a caller that announced fewer points than its flag words carry: the same word, from memory)
-                        const long long t = tn + i;
-                        w = closed[t < 0 ? 0 : (t > t_last ? t_last : (int)t)];
+                        w = gate_word(closed, tn + i, t_last);
                     }
                     w &= live;
-                    if (w) {
-                        const double q_prev = i == 1 ? q0 : quartic_pos(lon, (double)(i - 1) * tick) + front;
-                        const double q = quartic_pos(lon, (double)i * tick) + front;
-                        while (w) {
-                            const double g = line[__builtin_ctz(w)];
-                            w &= w - 1u;
-                            hit = hit || (q_prev <= g && g < q);
-                        }
-                    }
+                    if (w) hit = gate_point(lon, i, tick, front, q0, w, line);
                 }
                 if (__ballot(hit)) {
                     bits = FP_FLAG_SPEED;

@@ -273,6 +273,32 @@ struct GapArgs {
     int32_t* count = nullptr;
 };
 hipError_t launch_gap_mask(const KernelArgs& ka, GapArgs g, hipStream_t stream);
+// The four rules on K explicit end states per ego (frenet_rules_eval.hip, fp_rules_eval): one workgroup per ego, in the order of perm
+// (optional).  on = the FP_RULE_* bits of the rules that run (FP_RULE_LATERAL only beside FP_RULE_LIMIT); each rule's scalars and
+// arrays as its own pass takes them (a rule that is off leaves them unset).  Device addresses; end_states [B][K][3], flags [B][K]
+// in/out, rule_bits [B][K] or nullptr, counts [B][FP_RULE_COUNT] or nullptr.  The off_* fields are filled in by the launcher: where
+// the rules' own tables start in LDS behind stage_ego's layout, in doubles.
+struct RulesEvalArgs {
+    int K = 0;
+    uint32_t on = 0u;
+    double env_front = 0.0, env_tol = 0.0, max_lat_accel = 0.0;
+    const double* v_limit = nullptr;
+    double gate_front = 0.0, max_decel = 0.0;
+    int gate_stride = 0, T_gate = 0;
+    const double* gate_s = nullptr;
+    const uint32_t* closed = nullptr;
+    double margin = 0.0;
+    const double* left = nullptr;
+    const double* right = nullptr;
+    int lag_follow = 0, lag_lead = 0, first = 1;
+    int off_lim = 0, off_edge = 0, off_gate = 0;
+    const double* end_states = nullptr;
+    uint32_t* flags = nullptr;
+    uint32_t* rule_bits = nullptr;
+    int32_t* counts = nullptr;
+    const int32_t* perm = nullptr;
+};
+hipError_t launch_rules_eval(const KernelArgs& ka, RulesEvalArgs a, hipStream_t stream);
 // The obstacle margin of K chosen plans per ego (frenet_margins.hip, fp_traj_margins): one workgroup per ego, in the order of perm
 // (optional).  ka.p.check_stride is the call's pose_stride; ka.r is not read.  Device addresses; exactly one of best_idx [K][B] /
 // end_state [K][B][3] set; the outputs are [K][B].

@@ -8,6 +8,8 @@ speed envelope, the gates, the road-boundary check and the time gap to moving ob
 rules.TABLE, and decide which candidate the ego follows.
 With record=True the driven trajectory of every ego - what the reference's loop returns as state_list - is written on the device by
 fp_loop_record behind every step and read back once.
+With audit=(...) a FISS / FISS+ cycle is [plan -> rule verdict of the returned end state -> advance] (fp_rules_eval, K = 1): the plan is
+not changed, the violations are counted per ego and rule on the device.
 """
 from __future__ import annotations
 
@@ -82,16 +84,24 @@ class ClosedLoopRunner:
 
     def __init__(self, engine: FrenetEngine, dbatch: DeviceBatch, goal_xy: np.ndarray, planner: str = "FOP", fused: bool = True,
                  goal_poly: np.ndarray | None = None, goal_nv: np.ndarray | None = None, goal_intervals: np.ndarray | None = None,
-                 rules=()):
+                 rules=(), audit=()):
         """rules: any subset of the names in rules.TABLE - FOP only, and the batch must carry each rule's data (speed profile / gates /
         corridor / a time gap with a lag above 0).  The cycle then is fp_plan_dense into the runner's own [B][C] tables, the passes asked
         for in the table's order, whatever the caller's, each writing best_idx / best_cost, and fp_advance on the last one's winner;
         `fused` has no say.  rules=(): the calls below, unchanged.
+        audit: any subset of the names in rules.TABLE - FISS / FISS+ only (FOP enforces its rules with rules=), and the batch must carry
+        each rule's data.  The cycle then is fp_plan_fiss (asking for best_flags, which its series writer fills beside best_traj) ->
+        fp_rules_eval (K = 1 on end_state, counts = self.violations) -> fp_advance(end_state): the verdict is taken before the hand-over
+        moves ego / t_now, the plan is the one the loop drives without audit, and `fused` has no say.  self.violations [B, 5] int32 counts,
+        per ego and FP_RULE_* bit (column log2 of the bit), the cycles whose plan violated; run / run_graph return them as
+        `violations` (rule name -> [B]; the envelope's entry adds its two columns) and `violation_counts` [B, 5].  audit=(): the calls
+        below, unchanged.
         fused: an FOP cycle is ONE launch (fp_plan_step: the workgroup that finds an ego's argmin advances the ego); False = the two
         calls fp_plan_dense + fp_advance (same results; the A/B of tests and bench).
         goal_poly [B, V, 2] + goal_nv [B] (+ goal_intervals [B, 6] = time_step / velocity / orientation lo, hi; NaN = undefined): the
         goal region of goal_region.is_reached() (planning.py:150-153), see fp_loop_io in include/frenet_gpu.h."""
         self.rules = self._check_rules(rules, planner, dbatch.host)  # (first: the argument errors need no device)
+        self.audit = self._check_audit(audit, planner, dbatch.host)
         torch = dbatch.torch
         self.eng, self.db, self.planner, self.fused = engine, dbatch, planner, fused
         B = dbatch.B
@@ -136,6 +146,14 @@ class ClosedLoopRunner:
             f.prev_best_idx, f.best_ijk, f.best_cost, f.end_state = self.prev.data_ptr(), self.ijk.data_ptr(), self.best_cost.data_ptr(), self.end_state.data_ptr()
             f.refined, f.stats, f.trace, f.best_flags, f.best_traj = self.refined.data_ptr(), self.stats.data_ptr(), None, None, None
             self.fio = f
+        if self.audit:  # the plan's flag word (fp_plan_fiss writes best_flags with the series), the rule set on device addresses, the counts
+            stride = max(_abi.FP_DEFAULT_STRIDE, int(dbatch.params.points_max))
+            self.best_flags = torch.zeros(B, dtype=i32, device=dbatch.dev)
+            self.best_traj = dbatch.empty((B, 16, stride), f64)
+            self.fio.best_flags, self.fio.best_traj = self.best_flags.data_ptr(), self.best_traj.data_ptr()
+            self.fio.traj_stride, self.fio.traj_sparse = stride, 1
+            self.violations = torch.zeros((B, _abi.FP_RULE_COUNT), dtype=i32, device=dbatch.dev)
+            self.rule_set, self._rule_structs = _rules.rule_set(dbatch.host, lambda k: dbatch.t[k].data_ptr(), self.audit)
 
     @staticmethod
     def _check_rules(rules, planner, batch) -> tuple:
@@ -150,6 +168,25 @@ class ClosedLoopRunner:
             if not _rules.by_name[r].carried(batch):
                 raise _rules.missing(_rules.by_name[r], f"ClosedLoopRunner(rules={r!r})")
         return tuple(r for r in _rules.by_name if r in asked)
+
+    @staticmethod
+    def _check_audit(audit, planner, batch) -> tuple:
+        """The audited rules in the order they run; ValueError for an unknown rule, the FOP planner, or a rule without its data."""
+        asked = (audit,) if isinstance(audit, str) else tuple(audit)
+        names = _rules.check_names(asked, batch, "ClosedLoopRunner(audit=...)")
+        if asked and planner == "FOP":
+            raise ValueError("ClosedLoopRunner: audit is for the FISS / FISS+ planners (FOP enforces its rules with rules=...)")
+        return names
+
+    def _step_audit(self, stream: int):
+        """fp_plan_fiss -> fp_rules_eval (K = 1) -> fp_advance: a linear chain on `stream`."""
+        import ctypes as C
+
+        db, eng = self.db, self.eng
+        eng.plan_fiss_device(db.params, self.fb, self.fopts, self.fio, stream=stream)
+        eng.rules_eval_device(db.params, self.fb, self.rule_set, 1, self.end_state.data_ptr(), self.best_flags.data_ptr(), 0, self.violations.data_ptr(), stream)
+        _abi.check(eng._lib.fp_advance(eng._ctx, C.byref(db.params), C.byref(self.fb), None, self.end_state.data_ptr(), C.byref(self.io),
+                                       _abi.FP_MEM_DEVICE, stream or None))
 
     def _step_rules(self, stream: int):
         """fp_plan_dense -> the rule passes -> fp_advance: a linear chain on `stream`."""
@@ -168,6 +205,8 @@ class ClosedLoopRunner:
 
         if self.rules:
             return self._step_rules(stream)
+        if self.audit:
+            return self._step_audit(stream)
         lib, ctx = self.eng._lib, self.eng._ctx
         if self.planner == "FOP" and self.fused:
             self.eng.plan_step_device(self.db.params, self.fb, self.io, self.best_idx.data_ptr(), self.best_cost.data_ptr(), self.stats.data_ptr(), stream=stream)
@@ -222,6 +261,10 @@ class ClosedLoopRunner:
                               t_now=self.db.t["t_now"].cpu().numpy(), cart=self.cart.cpu().numpy(), trace=rows)
         if record:
             out.log = self.log_fetch()
+        if self.audit:
+            out.violation_counts = self.violations.cpu().numpy()
+            cols = lambda bits: [i for i in range(_abi.FP_RULE_COUNT) if bits >> i & 1]  # noqa: E731
+            out.violations = {n: out.violation_counts[:, cols(_rules.BITS[n])].sum(axis=1) for n in self.audit}
         return out
 
     def run_graph(self, max_cycles: int, record: bool = False):

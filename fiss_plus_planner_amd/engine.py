@@ -18,6 +18,7 @@ from types import SimpleNamespace
 import numpy as np
 
 from . import _abi, rules
+from . import rules as rules_mod  # (`rules` is an argument name of rules_eval / plan_fiss)
 from .batch import ProblemBatch
 from .rules import _time_gap  # (its home is the table of rule passes; callers find it here as before)
 
@@ -437,6 +438,58 @@ class FrenetEngine:
         g = _time_gap(follow, lead, first, "gap_mask_device")
         self._table_pass_device(rules.by_name["gaps"], params, fb, g, cost_tbl, flag_tbl, best_idx, best_cost, n_close, stream)
 
+    def rules_eval(self, batch: ProblemBatch, end_states: np.ndarray, flags: np.ndarray | None = None, rules=None, counts: np.ndarray | None = None,
+                   skip: np.ndarray | None = None):
+        """The rule verdicts of explicit end states (fp_rules_eval; the definition: include/frenet_gpu.h): end_states [B, K, 3] = (d, v,
+        T) as eval_trajs takes them, flags [B, K] their flag words (None: eval_trajs runs first and supplies them), rules = names of
+        rules.TABLE (None: every rule the batch carries data for; a named rule without data raises rules.missing), counts [B, 5] int32
+        to accumulate into (None: zeros) -> namespace(flags [B, K] - a copy with the rules' bits: FLAG_SPEED / FLAG_ACCEL ORed in by the
+        envelope, FLAG_SPEED by the gates, FLAG_BOUNDARY written by the corridor, FLAG_COLLISION ORed in by the time gap -, rule_bits
+        [B, K] - the _abi.RULE_* each trajectory violates in this call -, counts [B, 5] - per ego and rule (column log2 of the RULE_* bit)
+        the violating trajectories, added to what `counts` held).  The rules run in the order of rules.TABLE, the time gap only on
+        trajectories still feasible after the others.  skip [B] (optional): egos whose trajectories are not evaluated."""
+        es = np.ascontiguousarray(end_states, dtype=np.float64)
+        B = batch.B
+        if es.ndim != 3 or es.shape[0] != B or es.shape[1] < 1 or es.shape[2] != 3:
+            raise ValueError(f"rules_eval: end_states must be [B={B}, K >= 1, 3], got {es.shape}")
+        K = es.shape[1]
+        names = rules_mod.carried_names(batch) if rules is None else rules_mod.check_names(rules, batch, "rules_eval")
+        if not names:
+            raise ValueError("rules_eval: no rule to evaluate (the batch carries data for none)" if rules is None else "rules_eval: rules is empty")
+        if flags is not None and np.shape(flags) != (B, K):
+            raise ValueError(f"rules_eval: flags must be [B={B}, K={K}], got {np.shape(flags)}")
+        if counts is not None and np.shape(counts) != (B, _abi.FP_RULE_COUNT):
+            raise ValueError(f"rules_eval: counts must be [B={B}, {_abi.FP_RULE_COUNT}], got {np.shape(counts)}")
+        if flags is None:
+            flags = self.eval_trajs(batch, es).flags if B else np.empty((B, K), dtype=np.uint32)
+        flags = np.array(flags, dtype=np.uint32, order="C", copy=True)
+        counts = np.zeros((B, _abi.FP_RULE_COUNT), dtype=np.int32) if counts is None else np.array(counts, dtype=np.int32, order="C", copy=True)
+        rule_bits = np.zeros((B, K), dtype=np.uint32)
+        held = {}
+
+        def addr(name):
+            held[name] = np.ascontiguousarray(rules_mod.array(batch, name))  # (kept alive over the call)
+            return _ptr(held[name])
+
+        rs, structs = rules_mod.rule_set(batch, addr, names)
+        p, fb = host_structs(batch)
+        if skip is not None:
+            skip = np.ascontiguousarray(skip, dtype=np.int32)
+            assert skip.shape == (B,)
+            fb.skip = _ptr(skip)
+        _abi.check(self._lib.fp_rules_eval(self._ctx, C.byref(p), C.byref(fb), C.byref(rs), K, _ptr(es), _ptr(flags), _ptr(rule_bits), _ptr(counts),
+                                           _abi.FP_MEM_HOST, None))
+        return SimpleNamespace(flags=flags, rule_bits=rule_bits, counts=counts)
+
+    def rules_eval_device(self, params: _abi.FpParams, fb: _abi.FpBatch, rule_set: _abi.FpRuleSet, K: int, end_states: int, flags: int, rule_bits: int = 0,
+                          counts: int = 0, stream: int = 0):
+        """Enqueue the rule verdicts of explicit end states (device addresses; rule_set from rules.rule_set with device addresses):
+        end_states [B][K][3], flags [B][K] in/out (eval_trajs_device's words, or plan_fiss_device's best_flags with K = 1), rule_bits
+        [B][K] or 0, counts [B][5] int32 in/out or 0.  One launch, nothing allocated, nothing waited for; t_now, ego, the gate phases and
+        the obstacle table are read when the kernel runs."""
+        _abi.check(self._lib.fp_rules_eval(self._ctx, C.byref(params), C.byref(fb), C.byref(rule_set), int(K), end_states or None, flags or None,
+                                           rule_bits or None, counts or None, _abi.FP_MEM_DEVICE, stream or None))
+
     def traj_margins(self, batch: ProblemBatch, best_idx: np.ndarray | None = None, end_state: np.ndarray | None = None, pose_stride: int | None = None,
                      skip: np.ndarray | None = None):
         """The obstacle margin of chosen plans (fp_traj_margins; the definition: include/frenet_gpu.h): best_idx [B] or [K, B] flat FOP
@@ -588,14 +641,19 @@ class FrenetEngine:
 
     def plan_fiss(self, batch: ProblemBatch, kind: str = "FISS+", prev_best_idx: np.ndarray | None = None, w_heuristic: float = 10.0,
                   max_refine_iters: int = 3, decaying_factor: float = 0.5, winner: bool = False, trace: bool = False,
-                  traj_stride: int = TRAJ_STRIDE, traj_sparse: bool = False, out: SimpleNamespace | None = None):
+                  traj_stride: int = TRAJ_STRIDE, traj_sparse: bool = False, out: SimpleNamespace | None = None, rules=()):
         """FissPlanner.plan / FissPlusPlanner.plan for every ego of the batch, entirely on the device (fp_plan_fiss):
         dense tables -> per-ego search walk -> (FISS+) refinement -> optional winner series.
 
         batch.d_samples must be the FISS lattice (max_road_width - w + 0.3) and batch.samp_min/max/res must be set.
         prev_best_idx [B,3] (-1 = None) is not modified; the updated copy is returned.
+        rules: names of rules.TABLE the batch carries data for - the returned end state is audited by rules_eval (K = 1): also rule_bits
+        [B], the _abi.RULE_* the plan violates (0 for an ego without a plan).  The plan itself is the one the call returns without
+        `rules`: the walks do not look at the verdict.  The flag word comes from the call's best_flags when winner=True (the series
+        writer fills it), else from eval_trajs on the end state.
         """
         B = batch.B
+        audit = rules_mod.check_names(rules, batch, "plan_fiss(rules=...)") if rules else ()
         plus = kind in ("FISS+", _abi.FP_FISS_PLUS)
         R = fiss_rounds(kind, max_refine_iters)
         if out is None:
@@ -607,6 +665,8 @@ class FrenetEngine:
         out.prev_best_idx[...] = -1 if prev_best_idx is None else np.asarray(prev_best_idx, dtype=np.int32)
         prev = out.prev_best_idx
         if B == 0:
+            if audit:
+                out.rule_bits = np.zeros(0, dtype=np.uint32)
             return out
         okey = (plus, R, w_heuristic, decaying_factor)
         ocached = out.__dict__.get("_opts")
@@ -632,6 +692,8 @@ class FrenetEngine:
             out.__dict__["_io"] = (key, io, batch.samp_min, batch.samp_max, batch.samp_res)  # (the arrays kept alive: their ids are the key)
         p, fb = host_structs(batch)
         _abi.check(self._lib.fp_plan_fiss(self._ctx, C.byref(p), C.byref(fb), C.byref(opts), C.byref(io), _abi.FP_MEM_HOST, None))
+        if audit:
+            out.rule_bits = self.rules_eval(batch, out.end_state[:, None, :], out.best_flags[:, None] if winner else None, audit).rule_bits[:, 0]
         return out
 
     def materialize_all(self, batch: ProblemBatch, traj_stride: int = TRAJ_STRIDE, traj_sparse: bool = False):

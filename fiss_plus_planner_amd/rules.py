@@ -65,6 +65,41 @@ TABLE = (
          lambda b, addr: _time_gap(b.gap_follow, b.gap_lead, b.gap_first, "gaps")),
 )
 by_name = {r.name: r for r in TABLE}
+# fp_rules_eval: the FP_RULE_* bits each rule can report for an explicit end state (rule_bits), and the fp_rule_set field it fills
+BITS = {"envelope": _abi.RULE_LIMIT | _abi.RULE_LATERAL, "gates": _abi.RULE_GATE, "boundary": _abi.RULE_BOUNDARY, "gaps": _abi.RULE_GAP}
+assert tuple(BITS) == tuple(by_name) == tuple(n for n, _ in _abi.FpRuleSet._fields_)
+
+
+def carried_names(batch) -> tuple:
+    """The rules the batch carries data for, in the order they run."""
+    return tuple(r.name for r in TABLE if r.carried(batch))
+
+
+def check_names(names, batch, who: str) -> tuple:
+    """`names` (a rule name or an iterable of them) in the order the rules run; ValueError for an unknown name or a rule the batch
+    carries no data for."""
+    asked = (names,) if isinstance(names, str) else tuple(names)
+    for n in asked:
+        if n not in by_name:
+            raise ValueError(f"{who}: unknown rule {n!r} (rules are a subset of {tuple(by_name)})")
+    for n in asked:
+        if not by_name[n].carried(batch):
+            raise missing(by_name[n], f"{who}, rule {n!r}")
+    return tuple(n for n in by_name if n in asked)
+
+
+def rule_set(batch, addr, names=None):
+    """The fp_rule_set of `names` (None: every rule the batch carries) from TABLE's struct builders -> (FpRuleSet, {name: struct}).  The
+    set holds pointers into the structs: keep the dict alive as long as the set is used.  addr(name) = the address of array(batch, name)
+    in the caller's memory space."""
+    import ctypes as C
+
+    names = carried_names(batch) if names is None else check_names(names, batch, "rule_set")
+    structs = {n: by_name[n].struct(batch, addr) for n in names}
+    rs = _abi.FpRuleSet()
+    for n, st in structs.items():
+        setattr(rs, n, C.pointer(st))
+    return rs, structs
 
 
 def missing(rule: Rule, who: str) -> ValueError:

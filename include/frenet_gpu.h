@@ -316,7 +316,7 @@ int fp_ctx_destroy(fp_ctx* ctx);
 int fp_ctx_set_option(fp_ctx* ctx, const char* name, int value);
 /* Reads an option back, or one of the read-only counters "clearance_launches" (launches of the clearance rescoring kernel,
  * fp_params.w_obstacle > 0, of this ctx so far), "looplog_launches" (launches of fp_loop_record's kernel), "rank_launches" (launches of
- * fp_rank_feasible's kernel), "boundary_launches" (launches of fp_boundary_mask's kernel), "envelope_launches" (launches of fp_speed_envelope's kernel), "gate_launches" (launches of fp_gate_mask's kernel), "margin_launches" (launches of fp_traj_margins' kernel), "predict_launches" (launches of
+ * fp_rank_feasible's kernel), "boundary_launches" (launches of fp_boundary_mask's kernel), "envelope_launches" (launches of fp_speed_envelope's kernel), "gate_launches" (launches of fp_gate_mask's kernel), "margin_launches" (launches of fp_traj_margins' kernel), "rules_eval_launches" (launches of fp_rules_eval's kernel), "predict_launches" (launches of
  * fp_obstacles_predict's kernel), "from_state_launches" (launches of fp_from_state's kernel), "lattice_launches" (dense lattice launches of this ctx so far) and
  * "lattice_ordered_launches" (those dispatched in a feedback order or in the order of fp_batch.launch_order) - bench.py reports when an
  * order took effect -, "lattice_launches_2" / "_3" / "_4" (PROCESS-wide: fused lattice launches so far by workgroups per compute unit). */
@@ -623,6 +623,73 @@ typedef struct {
 
 int fp_gap_mask(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, const fp_time_gap* gap, const double* cost_tbl,
                 uint32_t* flag_tbl, int32_t* best_idx, double* best_cost, int32_t* n_close, int mem, void* stream);
+
+/* ---- the rules on explicit end states (added WITHIN ABI 18: detect it by looking the symbol up, e.g. dlsym) -------------------------
+ * fp_speed_envelope, fp_gate_mask, fp_boundary_mask and fp_gap_mask are table passes: a trajectory has a rule verdict only as a lattice
+ * candidate of a dense call.  What fp_plan_fiss hands back - an end state (d, v, T) that refinement has moved off the lattice - and
+ * every trajectory a caller makes itself (fp_eval_trajs, fp_traj_margins, fp_advance take them) has none.  fp_rules_eval evaluates the
+ * same four definitions on K explicit end states per ego.  It prices nothing and chooses nothing.
+ *
+ * Definition, for every ego b that is not skipped and every trajectory k < K:
+ *   trajectory       the one fp_eval_trajs builds for end_states[b][k] = (d, v, T).
+ *   N, M             from flags[b][k] ON ENTRY - fp_eval_trajs' flag word of the same end state (or fp_plan_fiss' best_flags, K = 1) -,
+ *                    as the passes take them from the table's flag word.
+ *   rules            the rules whose pointer in fp_rule_set is not NULL, in the passes' order: envelope, gates, boundary, gaps.  Each
+ *                    is its own pass' definition above, word for word (checked points, thresholds, the gates' waiver from the ego's
+ *                    present state, the gaps' pose set and pairs), with "candidate" read as "trajectory".
+ *   the bits         envelope: ORs FP_FLAG_SPEED (violation A) / FP_FLAG_ACCEL (violation B).  gates: OR FP_FLAG_SPEED.  boundary:
+ *                    WRITES FP_FLAG_BOUNDARY, set or cleared.  gaps: OR FP_FLAG_COLLISION, and only a trajectory whose word carries no
+ *                    FP_FLAG_INFEASIBLE bit after the rules before it IN THIS CALL is evaluated (fp_gap_mask's entry condition behind
+ *                    the other passes).  No other bit changes.
+ *   equivalence      on the lattice's own end states (d_samples[i_d], v_samples[b][i_v], t_samples[i_t]) and their flag words the call
+ *                    leaves the words the chain fp_speed_envelope -> fp_gate_mask -> fp_boundary_mask -> fp_gap_mask leaves in a
+ *                    dense call's table: the kernels share the predicates (same arithmetic, same bits).
+ *   rule_bits        NULL or [B][K] out: the FP_RULE_* of the rules the trajectory violates in THIS call, whatever bits it carried
+ *                    before.  The flag bits are shared - FP_FLAG_SPEED comes from the envelope or from a gate -: a report needs the rule.
+ *   counts           NULL or [B][FP_RULE_COUNT] in/out: entry log2(FP_RULE_x) of row b grows by the trajectories of ego b that violate
+ *                    rule x in this call.  A loop that passes the same array every cycle accumulates violations per ego and rule.
+ *   nothing checked  a NaN in the end state, M <= 1, or batch->skip[b] != 0: the word is unchanged, rule_bits is 0, nothing is counted.
+ * A second call on the words the first one left changes no word: the boundary bit is written to the same value, the OR bits stay; the
+ * gaps no longer evaluate their own violators, so that call's rule_bits lack FP_RULE_GAP for them.  Two calls on the same inputs give
+ * the same bits; the result depends neither on batch->launch_order nor on the memory space.  The rounding notes of the four passes hold
+ * here too.
+ *
+ * FP_MEM_DEVICE: one kernel is enqueued (one workgroup per ego, in the order of batch->launch_order when there is one) - no
+ * allocation, no wait; it can be captured behind fp_plan_fiss in a linear chain (fp_plan_fiss -> fp_rules_eval -> fp_advance: the
+ * verdict is taken before the hand-over moves ego / t_now).  t_now, ego, the gate phases and the obstacle table are read when the kernel
+ * runs.  A row of `counts` is read, added to and stored by the ego's workgroup alone (no atomics).  K has no compiled-in cap.
+ * params->points_max announces the points per trajectory as for every FP_MEM_DEVICE call.
+ * FP_MEM_HOST stages the batch, the arrays of the rules that are on, end_states, flags (in/out), rule_bits (out) and counts (in/out)
+ * through the ctx and waits, like fp_gap_mask.
+ * Errors: K < 1, a NULL rules / end_states / flags, or all four rules NULL: FP_EINVAL; for every rule that is on, its own pass' argument
+ * errors with the pass' messages; (FP_MEM_HOST only) an end state of an ego that is not skipped whose T needs more than FP_MAX_POINTS
+ * points: FP_ELIMIT - FP_MEM_DEVICE treats such a trajectory (and one that needs more points than the call is sized for) as having
+ * none: nothing is checked.
+ * Also read-only in fp_ctx_get_option: "rules_eval_launches" = launches of the kernel on this ctx so far (0 for a caller that never asks).
+ *
+ * Deliberately not done: fp_plan_fiss does not call it - where a verdict belongs INSIDE the FISS walks remains the separate decision the
+ * passes name, and this call is what it needs first -; fp_shard_call has no slot for it; there is no lattice-index input (an index has
+ * no flag word outside a table: a caller with tables runs the passes). */
+#define FP_RULE_LIMIT    1u   /* fp_speed_envelope violation A */
+#define FP_RULE_LATERAL  2u   /* fp_speed_envelope violation B */
+#define FP_RULE_GATE     4u
+#define FP_RULE_BOUNDARY 8u
+#define FP_RULE_GAP      16u
+#define FP_RULE_COUNT    5
+
+typedef struct {              /* each NULL = that rule is off; all four NULL: FP_EINVAL */
+    const fp_speed_profile* envelope;
+    const fp_gates*         gates;
+    const fp_corridor*      boundary;
+    const fp_time_gap*      gaps;
+} fp_rule_set;
+
+int fp_rules_eval(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, const fp_rule_set* rules, int32_t K,
+                  const double* end_states,  /* [B][K][3] = (d, v, T): fp_eval_trajs' layout */
+                  uint32_t* flags,           /* [B][K] in/out: fp_eval_trajs' flag words (N, M and the bits so far) */
+                  uint32_t* rule_bits,       /* NULL or [B][K] out: FP_RULE_* violated in THIS call */
+                  int32_t* counts,           /* NULL or [B][FP_RULE_COUNT] in/out */
+                  int mem, void* stream);
 
 /* ---- the obstacle margin of chosen plans (added WITHIN ABI 18: detect it by looking the symbol up, e.g. dlsym) ------------
  * fp_rank_feasible hands a behaviour layer K alternatives per ego as an index and a cost.  How close each of them comes to anything,
