@@ -202,7 +202,8 @@ struct fp_ctx {
     int margin_launches = 0;       // fp_ctx_get_option("margin_launches"): launches of the plan-margin kernel (fp_traj_margins)
     int predict_launches = 0;      // fp_ctx_get_option("predict_launches"): launches of the obstacle prediction kernel (fp_obstacles_predict)
     int from_state_launches = 0;   // fp_ctx_get_option("from_state_launches"): launches of the projection kernel (fp_from_state)
-    OrderSet order_lattice, order_refine;
+    int fiss_rules_calls = 0;      // fp_ctx_get_option("fiss_rules_calls"): calls of fp_plan_fiss_rules that passed their argument checks
+    OrderSet order_lattice, order_refine, order_refine_rules;  // (the rule instances of the refinement learn their own order: two workgroups per CU, other durations)
     DeviceBuf idx_shadow;          // [B] device copy of best_idx for the winner kernel of a dense call (KernelArgs::idx_shadow)
     DeviceBuf epi_flags;           // [B] hand-over flags of the epilogue workgroups appended to a multi-round lattice launch (KernelArgs::epi_flag); zero between launches
     DeviceBuf curv_buf;            // [B][C] curvature flag bytes of the lattice (fp_params.curvature_mask), written ahead of the fused kernel
@@ -1337,6 +1338,7 @@ int fp_ctx_destroy(fp_ctx* ctx)
     if (ctx->epi_flags.base) (void)hipFree(ctx->epi_flags.base);
     ctx->order_lattice.release();
     ctx->order_refine.release();
+    ctx->order_refine_rules.release();
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
     if (ctx->hand_err) (void)hipHostFree(ctx->hand_err);
     if (ctx->validate_host) (void)hipHostFree(ctx->validate_host);
@@ -1355,7 +1357,7 @@ int fp_ctx_set_option(fp_ctx* ctx, const char* name, int value)
     if (strcmp(name, "lattice_order") == 0) {
         if (value < 0 || value > 1) return fail(FP_EINVAL, "lattice_order must be 0 or 1");
         ctx->lattice_order = value;
-        ctx->order_lattice.forget(); ctx->order_refine.forget();
+        ctx->order_lattice.forget(); ctx->order_refine.forget(); ctx->order_refine_rules.forget();
         return FP_OK;
     }
     if (strcmp(name, "refine_table_kb") == 0) {
@@ -1468,7 +1470,7 @@ int fp_ctx_get_option(fp_ctx* ctx, const char* name, int* value)
     const struct { const char* n; int v; } tab[] = {
         {"lattice_kernel", ctx->lattice_kernel}, {"lattice_split", ctx->lattice_split}, {"lattice_group", ctx->lattice_group}, {"lattice_tail", ctx->lattice_tail}, {"lattice_occupancy", ctx->lattice_occupancy}, {"resident_groups", ctx->resident_groups}, {"zero_copy_in", ctx->zero_copy_in}, {"stage_kernel", ctx->stage_kernel}, {"inline_inputs", ctx->inline_inputs}, {"lattice_order", ctx->lattice_order},
         {"refine_table_kb", ctx->refine_table_kb}, {"fiss_stages", ctx->fiss_stages}, {"fiss_jump", ctx->fiss_jump}, {"validate", ctx->validate}, {"lattice_winner", ctx->lattice_winner}, {"fiss_fused", ctx->fiss_fused}, {"appended_workgroups", ctx->appended_ok ? 1 : 0}, {"handover_failed", ctx->hand_err ? *(volatile int32_t*)ctx->hand_err : 0}, {"overlap", ctx->overlap}, {"overlapped_calls", ctx->overlapped_calls}, {"clearance_launches", ctx->clearance_launches + (ctx->twin ? ctx->twin->clearance_launches : 0)}, {"lattice_launches", ctx->lattice_launches + (ctx->twin ? ctx->twin->lattice_launches : 0)},
-        {"looplog_launches", ctx->looplog_launches}, {"rank_launches", ctx->rank_launches}, {"boundary_launches", ctx->boundary_launches}, {"envelope_launches", ctx->envelope_launches}, {"gate_launches", ctx->gate_launches}, {"gap_launches", ctx->gap_launches}, {"margin_launches", ctx->margin_launches}, {"rules_eval_launches", ctx->rules_eval_launches}, {"predict_launches", ctx->predict_launches}, {"from_state_launches", ctx->from_state_launches}, {"lattice_ordered_launches", ctx->lattice_ordered_launches + (ctx->twin ? ctx->twin->lattice_ordered_launches : 0)},
+        {"looplog_launches", ctx->looplog_launches}, {"rank_launches", ctx->rank_launches}, {"boundary_launches", ctx->boundary_launches}, {"envelope_launches", ctx->envelope_launches}, {"gate_launches", ctx->gate_launches}, {"gap_launches", ctx->gap_launches}, {"margin_launches", ctx->margin_launches}, {"rules_eval_launches", ctx->rules_eval_launches}, {"fiss_rules_calls", ctx->fiss_rules_calls}, {"predict_launches", ctx->predict_launches}, {"from_state_launches", ctx->from_state_launches}, {"lattice_ordered_launches", ctx->lattice_ordered_launches + (ctx->twin ? ctx->twin->lattice_ordered_launches : 0)},
         {"lattice_launches_2", (int)fp::lattice_launches_per_cu(0)}, {"lattice_launches_3", (int)fp::lattice_launches_per_cu(1)}, {"lattice_launches_4", (int)fp::lattice_launches_per_cu(2)}};
     for (const auto& t : tab)
         if (strcmp(name, t.n) == 0) { *value = t.v; return FP_OK; }
@@ -2064,8 +2066,10 @@ int fp_materialize_all(fp_ctx* ctx, const fp_params* params, const fp_batch* bat
 namespace {
 
 // fp_plan_fiss, and - with `loop` (FP_MEM_DEVICE only) - fp_plan_fiss_step: the pipeline plus the egos' hand-over to their next states.
+// rules (fp_plan_fiss_rules, its arguments checked there): the dense tables are masked by the table passes of the rules that are on before
+// the search reads them, and the refinement runs its rule instances; rejected [B] in / out or nullptr.
 int plan_fiss_impl(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, const fp_fiss_opts* opts, const fp_fiss_io* io, const fp_loop_io* loop,
-                   int mem, void* stream_v)
+                   int mem, void* stream_v, const fp_rule_set* rules = nullptr, int32_t* rejected = nullptr)
 {
     FP_TRY(common_checks(ctx, params, batch, mem, stream_v));
     if (!opts || !io) return fail(FP_EINVAL, "opts/io is NULL");
@@ -2090,8 +2094,10 @@ int plan_fiss_impl(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, 
     if (mem == FP_MEM_HOST && ctx->appended_ok && ctx->fiss_fused && B > (size_t)ctx->resident_groups) prev_in.assign(io->prev_best_idx, io->prev_best_idx + B * 3);
 
     // dense tables + per-ego dense results live in the scratch buffer in both modes
+    // (with rules: the passes' best_idx / best_cost / count outputs behind them)
     const size_t scratch_need = align_up(sizeof(double) * B * C) + align_up(sizeof(uint32_t) * B * C) + align_up(sizeof(int32_t) * B) +
-                                align_up(sizeof(double) * B) + 4 * kAlign;
+                                align_up(sizeof(double) * B) + 4 * kAlign +
+                                (rules ? 2 * align_up(sizeof(int32_t) * B) + align_up(sizeof(double) * B) + 3 * kAlign : 0);
     if (scratch_need > ctx->scratch.cap) HIP_TRY(hipStreamSynchronize(stream));  // the buffer may be reallocated: drain its users
     FP_TRY(ctx->scratch.reserve(scratch_need));
     char* sp = ctx->scratch.base;
@@ -2108,6 +2114,51 @@ int plan_fiss_impl(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, 
     fa.ka.r.best_idx = (int32_t*)sp;
     sp += align_up(sizeof(int32_t) * B);
     fa.ka.r.best_cost = (double*)sp;
+    sp += align_up(sizeof(double) * B);
+    int32_t* pass_idx = (int32_t*)sp;
+    sp += rules ? align_up(sizeof(int32_t) * B) : 0;
+    double* pass_cost = (double*)sp;
+    sp += rules ? align_up(sizeof(double) * B) : 0;
+    int32_t* pass_count = (int32_t*)sp;
+    int32_t* rejected_dev = rejected;  // (a host call: the staged copy's address at commit)
+    // the rule set as the rules kernel takes it (fp_rules_eval builds the same block); a host call's arrays get their device addresses at commit
+    fp::RulesEvalArgs ra;
+    if (rules) {
+        if (const fp_speed_profile* e = rules->envelope) {
+            ra.on |= FP_RULE_LIMIT | (e->max_lat_accel > 0 ? FP_RULE_LATERAL : 0u);
+            ra.env_front = e->front; ra.env_tol = e->tol; ra.max_lat_accel = e->max_lat_accel; ra.v_limit = e->v_limit;
+        }
+        if (const fp_gates* g = rules->gates) {
+            ra.on |= FP_RULE_GATE;
+            ra.gate_front = g->front; ra.max_decel = g->max_decel; ra.gate_stride = g->gate_stride; ra.T_gate = g->T_gate;
+            ra.gate_s = g->gate_s; ra.closed = g->closed;
+        }
+        if (const fp_corridor* c = rules->boundary) {
+            ra.on |= FP_RULE_BOUNDARY;
+            ra.margin = c->margin; ra.left = c->left; ra.right = c->right;
+        }
+        if (const fp_time_gap* t = rules->gaps) {
+            ra.on |= FP_RULE_GAP;
+            ra.lag_follow = t->lag_follow; ra.lag_lead = t->lag_lead;
+            ra.first = t->first < FP_MAX_POINTS ? t->first : FP_MAX_POINTS;  // (points are 0 .. FP_MAX_POINTS - 1: anything above is "beyond every pose")
+        }
+    }
+    int gate_points_cap = big_points(*params) ? params->points_max : FP_FAST_POINTS;  // (the passes' own sizing: see fp_gate_mask / fp_gap_mask)
+    int gap_points_max = params->points_max;
+    // the rule instances of the refinement hold the rules' tables in LDS beside the refinement's own: a call that does not fit is refused
+    auto refine_fits = [&](const fp_params& p_sized) -> int {
+        if (!rules || R <= 0) return FP_OK;
+        fp::FissArgs probe;
+        probe.ka.p = p_sized;
+        probe.ka.b = *batch;
+        if (!(batch->S > 0 && batch->n_obs > 0)) probe.ka.b.n_obs = 0;
+        int base = 0, own = 0;
+        fp::fiss_refine_rules_lds(probe, ra.on, ctx->refine_table_kb, &base, &own);
+        if (base + own > fp::kRefineRulesLdsMax)
+            return fail(FP_ELIMIT, "fp_plan_fiss_rules: the refinement needs %d bytes of LDS and the rules' tables %d (NX=%d, %d gate slots, %d points, n_obs=%d): more than the %d a workgroup has",
+                        base, own, batch->NX, (ra.on & FP_RULE_GATE) ? FP_MAX_GATES : 0, p_sized.points_max > FP_FAST_POINTS ? (p_sized.points_max < FP_MAX_POINTS ? p_sized.points_max : FP_MAX_POINTS) : FP_FAST_POINTS, probe.ka.b.n_obs, fp::kRefineRulesLdsMax);
+        return FP_OK;
+    };
     fa.cost_tbl = fa.ka.r.cost_tbl;
     fa.flag_tbl = fa.ka.r.flag_tbl;
     int stride;
@@ -2124,12 +2175,20 @@ int plan_fiss_impl(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, 
         if (!(batch->S > 0 && batch->n_obs > 0)) fa.ka.b.n_obs = 0;
         fa.io = *io;
         if (!trace_doubles) fa.io.trace = nullptr;
+        FP_TRY(refine_fits(fa.ka.p));
     } else {
         FP_TRY(check_batch_host(params, batch));
+        if (rules && rules->envelope) FP_TRY(check_speed_profile_host(rules->envelope, batch));
+        if (rules && rules->boundary) FP_TRY(check_corridor_host(rules->boundary, batch));
         for (size_t i = 0; R > 0 && i < B; ++i)  // (a refinement probe beyond FP_MAX_POINTS would come back as NaN cost: a silently different walk)
             if (ceil(io->samp_max[3 * i + 2] / params->tick_t) > FP_MAX_POINTS)
                 return fail(FP_ELIMIT, "samp_max[%zu].T=%g needs more than FP_MAX_POINTS points (FISS+ refinement)", i, io->samp_max[3 * i + 2]);
         fa.ka.p.points_max = host_points_max(params, batch, R > 0 ? io->samp_max + 2 : nullptr, R > 0 ? B : 0, 3);  // (refined trajectories reach T = samp_max)
+        FP_TRY(refine_fits(fa.ka.p));
+        if (rules) {  // (what the host calls of the passes work out from the time samples)
+            gap_points_max = host_points_max(params, batch, nullptr, 0, 0);
+            gate_points_cap = gap_points_max > FP_FAST_POINTS ? gap_points_max : FP_FAST_POINTS;
+        }
         if (io->best_traj) {
             for (size_t i = 0; i < B; ++i)  // refined trajectories reach T = samp_max of their ego
                 if (ceil(io->samp_max[3 * i + 2] / params->tick_t) > stride) return fail(FP_EINVAL, "traj_stride=%d is smaller than the points of samp_max[%zu].T=%g", stride, i, io->samp_max[3 * i + 2]);
@@ -2140,7 +2199,7 @@ int plan_fiss_impl(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, 
         // inside the lattice kernel's argument block, which also leaves them in a device mirror for the search and refinement
         // kernels - no copy kernel, no dependency in front of the lattice kernel (a single-ego FISS+ cycle: ~5 us of ~80).
         fa.io = *io;
-        const bool try_inline = ctx->inline_inputs && B <= 8 && !params->curvature_mask && ctx->lattice_kernel != 1 && !big_points(fa.ka.p) &&
+        const bool try_inline = !rules && ctx->inline_inputs && B <= 8 && !params->curvature_mask && ctx->lattice_kernel != 1 && !big_points(fa.ka.p) &&
                                 fp::lattice_group_fit(*params, *batch) >= 1;
         const InlineExtra ex[3] = {{io->samp_min, sizeof(double) * B * 3, (const void**)&fa.io.samp_min},
                                    {io->samp_max, sizeof(double) * B * 3, (const void**)&fa.io.samp_max},
@@ -2150,6 +2209,19 @@ int plan_fiss_impl(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, 
             sl.in(io->samp_min, B * 3, &fa.io.samp_min);
             sl.in(io->samp_max, B * 3, &fa.io.samp_max);
             sl.in(io->samp_res, B * 3, &fa.io.samp_res);
+        }
+        if (rules) {  // the rule arrays, as the host call of fp_rules_eval declares them
+            const size_t fn = (size_t)batch->F * batch->NX, F = (size_t)batch->F;
+            if (rules->envelope) sl.in(ra.v_limit, fn, &ra.v_limit);
+            if (rules->gates) {
+                sl.in(ra.gate_s, F * ra.gate_stride, &ra.gate_s);
+                sl.in(ra.closed, F * ra.T_gate, &ra.closed);
+            }
+            if (rules->boundary) {
+                sl.in(ra.left, fn, &ra.left);
+                sl.in(ra.right, fn, &ra.right);
+            }
+            if (rejected) sl.in_mut(rejected, B, &rejected_dev);
         }
         sl.in_mut(io->prev_best_idx, B * 3, &fa.io.prev_best_idx);
         sl.out(io->best_ijk, B * 3, &fa.io.best_ijk);
@@ -2172,26 +2244,76 @@ int plan_fiss_impl(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, 
     if (inl.on) kl.b = lat_b;
     fp::FissTail ft;
     ft.opts = fa.opts; ft.io = fa.io; ft.walk_jump = ctx->fiss_jump;
-    ft.flag = (!inl.on && ctx->fiss_fused && ctx->appended_ok && ctx->fiss_stages >= 3 && opts->kind == FP_FISS_PLUS) ? epi_flags_for(ctx, B, stream) : nullptr;
+    ft.flag = (!rules && !inl.on && ctx->fiss_fused && ctx->appended_ok && ctx->fiss_stages >= 3 && opts->kind == FP_FISS_PLUS) ? epi_flags_for(ctx, B, stream) : nullptr;
     fp::LatticeResult lr;
     FP_TRY(lattice_step(ctx, params, batch, kl, stream, inl.on ? 2 : ctx->lattice_kernel, mem == FP_MEM_DEVICE ? batch->launch_order : nullptr,
                         inl.on ? &inl : nullptr, ft.flag ? &ft : nullptr, &lr));
     if (ctx->fiss_stages < 2) return mem == FP_MEM_HOST ? hs.fetch_out() : FP_OK;  // timing diagnostic: outputs are not produced
     fa.walk_jump = ctx->fiss_jump;
+    if (rules) {
+        // the table passes of the rules that are on, in the order they run (rules.TABLE): the launches a dense call's caller makes behind
+        // it, over the same tables - the search reads the words the FOP chain leaves
+        const fp_batch& db = fa.ka.b;
+        const int32_t* perm = mem == FP_MEM_DEVICE ? batch->launch_order : nullptr;
+        auto pass_args = [&](fp::TablePassArgs* a) {
+            table_pass_args(a, params, &db, fa.cost_tbl, fa.ka.r.flag_tbl, pass_idx, pass_cost, pass_count);
+            a->perm = perm;
+        };
+        if (ra.on & FP_RULE_LIMIT) {
+            fp::EnvelopeArgs a;
+            pass_args(&a);
+            a.front = ra.env_front; a.tol = ra.env_tol; a.max_lat_accel = ra.max_lat_accel;
+            a.coef = (ra.on & FP_RULE_LATERAL) ? db.coef : nullptr; a.v_limit = ra.v_limit;
+            LAUNCH_TRY(fp::launch_speed_envelope(a, stream), "speed-envelope kernel");
+            ++ctx->envelope_launches;
+        }
+        if (ra.on & FP_RULE_GATE) {
+            fp::GateArgs a;
+            pass_args(&a);
+            a.front = ra.gate_front; a.max_decel = ra.max_decel; a.gate_stride = ra.gate_stride; a.T_gate = ra.T_gate;
+            a.t_now = db.t_now; a.gate_s = ra.gate_s; a.closed = ra.closed;
+            a.points_cap = gate_points_cap;
+            LAUNCH_TRY(fp::launch_gate_mask(a, stream), "gate kernel");
+            ++ctx->gate_launches;
+        }
+        if (ra.on & FP_RULE_BOUNDARY) {
+            fp::BoundaryArgs a;
+            pass_args(&a);
+            a.veh_l = params->veh_l; a.veh_w = params->veh_w; a.margin = ra.margin;
+            a.d_samples = db.d_samples; a.left = ra.left; a.right = ra.right;
+            LAUNCH_TRY(fp::launch_boundary_mask(a, stream), "road-boundary kernel");
+            ++ctx->boundary_launches;
+        }
+        if (ra.on & FP_RULE_GAP) {
+            fp::KernelArgs kg;
+            kg.p = *params;
+            kg.p.points_max = gap_points_max;
+            kg.b = db;
+            kg.r = no_result();
+            kg.r.cost_tbl = fa.ka.r.cost_tbl; kg.r.flag_tbl = fa.ka.r.flag_tbl; kg.r.best_idx = pass_idx; kg.r.best_cost = pass_cost;
+            fp::GapArgs g;
+            g.lag_follow = ra.lag_follow; g.lag_lead = ra.lag_lead; g.first = ra.first;
+            g.perm = perm; g.count = pass_count;
+            LAUNCH_TRY(fp::launch_gap_mask(kg, g, stream), "time-gap kernel");
+            ++ctx->gap_launches;
+        }
+    }
     if (!lr.search_done) LAUNCH_TRY(fp::launch_fiss_search(fa, stream), "search kernel");
     bool handed_over = false;
     if (R > 0 && ctx->fiss_stages >= 3) {
         // three refinement workgroups per CU are resident at once (fiss_refine_kernel: 168 VGPRs, ~52 KB LDS)
         const int* rperm; int* rdur;
         LaunchOrder* oslot_r = nullptr;
-        FP_TRY(launch_order_before(ctx, ctx->order_refine, ctx->resident_groups / 2 * 3, batch, 1, stream, &rperm, &rdur, nullptr, &oslot_r));
+        if (rules) FP_TRY(launch_order_before(ctx, ctx->order_refine_rules, ctx->resident_groups, batch, 1, stream, &rperm, &rdur, nullptr, &oslot_r));  // (two per CU)
+        else FP_TRY(launch_order_before(ctx, ctx->order_refine, ctx->resident_groups / 2 * 3, batch, 1, stream, &rperm, &rdur, nullptr, &oslot_r));
         fp::FissArgs fr = fa;
         if (loop) {  // fp_plan_fiss_step: the refinement workgroup that settles an ego's trajectory hands the ego over itself
             fr.ka.loop = *loop;
             fr.ka.has_loop = 1;
             handed_over = true;
         }
-        LAUNCH_TRY(fp::launch_fiss_refine(fr, stream, ctx->refine_table_kb, rperm, rdur), "refinement kernel");
+        if (rules) LAUNCH_TRY(fp::launch_fiss_refine_rules(fr, ra, rejected_dev, stream, ctx->refine_table_kb, rperm, rdur), "refinement kernel (rule instance)");
+        else LAUNCH_TRY(fp::launch_fiss_refine(fr, stream, ctx->refine_table_kb, rperm, rdur), "refinement kernel");
         FP_TRY(launch_order_after(oslot_r, batch, rdur, stream));
     }
     if (fa.io.best_traj && R <= 0) {  // with refinement rounds the refinement kernel writes the series itself
@@ -2208,7 +2330,7 @@ int plan_fiss_impl(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, 
     if (handover_failed(ctx)) {  // (see fp_plan_dense)
         (void)handover_recover(ctx, ctx->stream);
         if (!prev_in.empty()) memcpy(io->prev_best_idx, prev_in.data(), prev_in.size() * sizeof(int32_t));
-        return plan_fiss_impl(ctx, params, batch, opts, io, loop, mem, stream_v);
+        return plan_fiss_impl(ctx, params, batch, opts, io, loop, mem, stream_v, rules, rejected);
     }
     return FP_OK;
 }
@@ -2241,6 +2363,25 @@ int fp_plan_fiss_step(fp_ctx* ctx, const fp_params* params, const fp_batch* batc
         return fp_advance(ctx, params, batch, nullptr, io->end_state, loop, mem, stream);
     }
     return plan_fiss_impl(ctx, params, batch, opts, io, loop, mem, stream);
+}
+
+int fp_plan_fiss_rules(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, const fp_fiss_opts* opts, const fp_fiss_io* io,
+                       const fp_rule_set* rules, const fp_loop_io* loop, int32_t* rejected, int mem, void* stream)
+{
+    FP_TRY(common_checks(ctx, params, batch, mem, stream));
+    if (!rules) return fail(FP_EINVAL, "fp_plan_fiss_rules: rules must not be NULL");
+    if (!rules->envelope && !rules->gates && !rules->boundary && !rules->gaps) return fail(FP_EINVAL, "fp_plan_fiss_rules: every rule of the set is NULL");
+    if (rules->envelope) FP_TRY(check_speed_profile(rules->envelope, batch));
+    if (rules->gates) FP_TRY(check_gates(rules->gates));
+    if (rules->boundary) FP_TRY(check_corridor(rules->boundary));
+    if (rules->gaps) FP_TRY(check_time_gap(rules->gaps));
+    if (loop) {
+        if (mem != FP_MEM_DEVICE) return fail(FP_EINVAL, "fp_plan_fiss_rules: loop needs FP_MEM_DEVICE (a host caller plans with loop = NULL and calls fp_advance)");
+        if (!loop->ego || !loop->t_now || !loop->done || !loop->cycles || !loop->goal_xy) return fail(FP_EINVAL, "fp_loop_io has a NULL mandatory array");
+        if (loop->goal_poly && (!loop->goal_nv || loop->goal_max_vertices < 3)) return fail(FP_EINVAL, "fp_loop_io.goal_poly needs goal_nv and goal_max_vertices >= 3");
+    }
+    ++ctx->fiss_rules_calls;
+    return plan_fiss_impl(ctx, params, batch, opts, io, loop, mem, stream, rules, rejected);
 }
 
 int fp_advance(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, const int32_t* best_idx, const double* end_state,

@@ -126,7 +126,9 @@ constexpr int kMisc = 256;  // bytes of counters / per-wave extremes / jump stat
 // CMAX: the most samples the instance is launched for (sizes the per-thread register copies of the jump's relaxation).
 // COHERENT: the dense tables were written by ANOTHER workgroup of the SAME launch (the fused lattice + search launch): they are read
 // with agent-scope loads (the writer used agent-scope stores; an XCD's L2 is not coherent with the others' inside a launch).
-template <int W, int NW, int CMAX, bool COHERENT = false>
+// BOUNDARY: FP_FLAG_BOUNDARY counts as a constraint bit (the stand-alone launch, whose tables fp_plan_fiss_rules may have masked with
+// fp_boundary_mask; the appended search never sees such a table).
+template <int W, int NW, int CMAX, bool COHERENT = false, bool BOUNDARY = false>
 __device__ __forceinline__ void fissplus_search_ego(const FissArgs& fa, int NB, int b, unsigned char* smem)
 {
     constexpr int T = W * kWave;
@@ -199,8 +201,9 @@ __device__ __forceinline__ void fissplus_search_ego(const FissArgs& fa, int NB, 
         X[q] = finite ? cost : __builtin_inf();  // NaN and +-inf: never queued, ranked behind every finite key by raster index
         if (finite) { kmin = fmin(kmin, cost); kmax = fmax(kmax, cost); }
         feasible += (f & FP_FLAG_INFEASIBLE) == 0;
-        pass_constraints += (f & FP_FLAG_CONSTRAINTS) == 0;
-        rank[q] = (uint16_t)(((uint32_t)q << 3) | ((f & FP_FLAG_CONSTRAINTS) ? kPayCfail : 0u) | ((f & FP_FLAG_COLLISION) ? kPayColl : 0u) |
+        constexpr uint32_t kConstraintBits = FP_FLAG_CONSTRAINTS | (BOUNDARY ? FP_FLAG_BOUNDARY : 0u);
+        pass_constraints += (f & kConstraintBits) == 0;
+        rank[q] = (uint16_t)(((uint32_t)q << 3) | ((f & kConstraintBits) ? kPayCfail : 0u) | ((f & FP_FLAG_COLLISION) ? kPayColl : 0u) |
                              (cost != cost ? kPayNan : 0u));  // (the payload, parked here until the scatter)
     }
     // No feasible candidate anywhere in the lattice: the walk would generate and validate every sample, one per outer

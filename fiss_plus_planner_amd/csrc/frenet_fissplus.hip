@@ -10,7 +10,7 @@ template <int W, int NW, int CMAX>
 __global__ __launch_bounds__(W * kWave, W >= 8 ? 8 : 1) void fissplus_search_kernel(FissArgs fa, int NB)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    fsp::fissplus_search_ego<W, NW, CMAX>(fa, NB, (int)blockIdx.x, smem);
+    fsp::fissplus_search_ego<W, NW, CMAX, false, true>(fa, NB, (int)blockIdx.x, smem);
 }
 
 #ifndef FP_SEARCH_WAVES

@@ -299,6 +299,22 @@ struct RulesEvalArgs {
     const int32_t* perm = nullptr;
 };
 hipError_t launch_rules_eval(const KernelArgs& ka, RulesEvalArgs a, hipStream_t stream);
+// fp_plan_fiss_rules: the refinement whose popped candidates are also checked against the enforced rules (fiss_refine_rules_kernel,
+// frenet_fiss.hip).  rules = the rule set as launch_rules_eval takes it (K, end_states, flags, rule_bits, counts, perm
+// and the off_* fields are not read); rejected [B] in/out or nullptr; rules_off = where the rules' tables start in LDS, in bytes
+// (filled in by the launcher).
+struct FissRulesArgs : FissArgs {
+    RulesEvalArgs rules;
+    int32_t* rejected = nullptr;
+    int rules_off = 0;
+};
+// LDS of one workgroup of that launch: the refinement's own layout (*base_bytes) and the rules' tables behind it (*rule_bytes) - the limit
+// per segment, the corridor's edge and slope per segment and side, the gate lines and closed words, the obstacle sizes (the gaps).
+// kRefineRulesLdsMax is what a workgroup may use; a call that needs more is refused (FP_ELIMIT).
+constexpr int kRefineRulesLdsMax = 160 * 1024;
+void fiss_refine_rules_lds(const FissArgs& fa, uint32_t on, int table_kb, int* base_bytes, int* rule_bytes);
+hipError_t launch_fiss_refine_rules(const FissArgs& fa, const RulesEvalArgs& rules, int32_t* rejected, hipStream_t stream, int table_kb,
+                                    const int* perm = nullptr, int* dur = nullptr);
 // The obstacle margin of K chosen plans per ego (frenet_margins.hip, fp_traj_margins): one workgroup per ego, in the order of perm
 // (optional).  ka.p.check_stride is the call's pose_stride; ka.r is not read.  Device addresses; exactly one of best_idx [K][B] /
 // end_state [K][B][3] set; the outputs are [K][B].

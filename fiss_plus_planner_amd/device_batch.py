@@ -10,6 +10,8 @@ With record=True the driven trajectory of every ego - what the reference's loop 
 fp_loop_record behind every step and read back once.
 With audit=(...) a FISS / FISS+ cycle is [plan -> rule verdict of the returned end state -> advance] (fp_rules_eval, K = 1): the plan is
 not changed, the violations are counted per ego and rule on the device.
+With enforce=(...) a FISS / FISS+ cycle is ONE fp_plan_fiss_rules call with the loop's hand-over: the walks obey the rules (their validation
+sees the rules' verdicts, the visiting order stays cost-only); audit=(...) may follow it (plan, verdict, advance).
 """
 from __future__ import annotations
 
@@ -84,7 +86,7 @@ class ClosedLoopRunner:
 
     def __init__(self, engine: FrenetEngine, dbatch: DeviceBatch, goal_xy: np.ndarray, planner: str = "FOP", fused: bool = True,
                  goal_poly: np.ndarray | None = None, goal_nv: np.ndarray | None = None, goal_intervals: np.ndarray | None = None,
-                 rules=(), audit=()):
+                 rules=(), audit=(), enforce=()):
         """rules: any subset of the names in rules.TABLE - FOP only, and the batch must carry each rule's data (speed profile / gates /
         corridor / a time gap with a lag above 0).  The cycle then is fp_plan_dense into the runner's own [B][C] tables, the passes asked
         for in the table's order, whatever the caller's, each writing best_idx / best_cost, and fp_advance on the last one's winner;
@@ -96,12 +98,17 @@ class ClosedLoopRunner:
         per ego and FP_RULE_* bit (column log2 of the bit), the cycles whose plan violated; run / run_graph return them as
         `violations` (rule name -> [B]; the envelope's entry adds its two columns) and `violation_counts` [B, 5].  audit=(): the calls
         below, unchanged.
+        enforce: any subset of the names in rules.TABLE - FISS / FISS+ only (FOP enforces with rules=), and the batch must carry each
+        rule's data.  Each cycle is one fp_plan_fiss_rules call with the loop's fp_loop_io (FISS+: the refinement's rule instance hands the
+        ego over; FISS: the advance kernel follows); with audit= as well it is fp_plan_fiss_rules (loop = NULL) -> fp_rules_eval ->
+        fp_advance.  self.rejected [B] int32 sums, per ego, the refined candidates a rule alone rejected; run / run_graph return it.
         fused: an FOP cycle is ONE launch (fp_plan_step: the workgroup that finds an ego's argmin advances the ego); False = the two
         calls fp_plan_dense + fp_advance (same results; the A/B of tests and bench).
         goal_poly [B, V, 2] + goal_nv [B] (+ goal_intervals [B, 6] = time_step / velocity / orientation lo, hi; NaN = undefined): the
         goal region of goal_region.is_reached() (planning.py:150-153), see fp_loop_io in include/frenet_gpu.h."""
         self.rules = self._check_rules(rules, planner, dbatch.host)  # (first: the argument errors need no device)
         self.audit = self._check_audit(audit, planner, dbatch.host)
+        self.enforce = self._check_enforce(enforce, planner, dbatch.host, self.rules)
         torch = dbatch.torch
         self.eng, self.db, self.planner, self.fused = engine, dbatch, planner, fused
         B = dbatch.B
@@ -154,6 +161,9 @@ class ClosedLoopRunner:
             self.fio.traj_stride, self.fio.traj_sparse = stride, 1
             self.violations = torch.zeros((B, _abi.FP_RULE_COUNT), dtype=i32, device=dbatch.dev)
             self.rule_set, self._rule_structs = _rules.rule_set(dbatch.host, lambda k: dbatch.t[k].data_ptr(), self.audit)
+        if self.enforce:  # the enforced set on device addresses, and the per-ego count of rule-rejected refined candidates
+            self.rejected = torch.zeros(B, dtype=i32, device=dbatch.dev)
+            self.enforce_set, self._enforce_structs = _rules.rule_set(dbatch.host, lambda k: dbatch.t[k].data_ptr(), self.enforce)
 
     @staticmethod
     def _check_rules(rules, planner, batch) -> tuple:
@@ -170,6 +180,17 @@ class ClosedLoopRunner:
         return tuple(r for r in _rules.by_name if r in asked)
 
     @staticmethod
+    def _check_enforce(enforce, planner, batch, rules) -> tuple:
+        """The enforced rules in the order they run; ValueError for an unknown rule, the FOP planner, rules= beside it, or a rule without
+        its data."""
+        asked = (enforce,) if isinstance(enforce, str) else tuple(enforce)
+        if asked and rules:
+            raise ValueError("ClosedLoopRunner: enforce= (FISS / FISS+) and rules= (FOP) do not combine")
+        if asked and planner == "FOP":
+            raise ValueError("ClosedLoopRunner: enforce is for the FISS / FISS+ planners (FOP enforces its rules with rules=...)")
+        return _rules.check_names(asked, batch, "ClosedLoopRunner(enforce=...)")
+
+    @staticmethod
     def _check_audit(audit, planner, batch) -> tuple:
         """The audited rules in the order they run; ValueError for an unknown rule, the FOP planner, or a rule without its data."""
         asked = (audit,) if isinstance(audit, str) else tuple(audit)
@@ -183,7 +204,10 @@ class ClosedLoopRunner:
         import ctypes as C
 
         db, eng = self.db, self.eng
-        eng.plan_fiss_device(db.params, self.fb, self.fopts, self.fio, stream=stream)
+        if self.enforce:
+            eng.plan_fiss_rules_device(db.params, self.fb, self.fopts, self.fio, self.enforce_set, None, self.rejected.data_ptr(), stream)
+        else:
+            eng.plan_fiss_device(db.params, self.fb, self.fopts, self.fio, stream=stream)
         eng.rules_eval_device(db.params, self.fb, self.rule_set, 1, self.end_state.data_ptr(), self.best_flags.data_ptr(), 0, self.violations.data_ptr(), stream)
         _abi.check(eng._lib.fp_advance(eng._ctx, C.byref(db.params), C.byref(self.fb), None, self.end_state.data_ptr(), C.byref(self.io),
                                        _abi.FP_MEM_DEVICE, stream or None))
@@ -207,6 +231,8 @@ class ClosedLoopRunner:
             return self._step_rules(stream)
         if self.audit:
             return self._step_audit(stream)
+        if self.enforce:  # one call: the rules' passes, the walks, the hand-over
+            return self.eng.plan_fiss_rules_device(self.db.params, self.fb, self.fopts, self.fio, self.enforce_set, self.io, self.rejected.data_ptr(), stream)
         lib, ctx = self.eng._lib, self.eng._ctx
         if self.planner == "FOP" and self.fused:
             self.eng.plan_step_device(self.db.params, self.fb, self.io, self.best_idx.data_ptr(), self.best_cost.data_ptr(), self.stats.data_ptr(), stream=stream)
@@ -261,6 +287,8 @@ class ClosedLoopRunner:
                               t_now=self.db.t["t_now"].cpu().numpy(), cart=self.cart.cpu().numpy(), trace=rows)
         if record:
             out.log = self.log_fetch()
+        if self.enforce:
+            out.rejected = self.rejected.cpu().numpy()
         if self.audit:
             out.violation_counts = self.violations.cpu().numpy()
             cols = lambda bits: [i for i in range(_abi.FP_RULE_COUNT) if bits >> i & 1]  # noqa: E731

@@ -641,7 +641,7 @@ class FrenetEngine:
 
     def plan_fiss(self, batch: ProblemBatch, kind: str = "FISS+", prev_best_idx: np.ndarray | None = None, w_heuristic: float = 10.0,
                   max_refine_iters: int = 3, decaying_factor: float = 0.5, winner: bool = False, trace: bool = False,
-                  traj_stride: int = TRAJ_STRIDE, traj_sparse: bool = False, out: SimpleNamespace | None = None, rules=()):
+                  traj_stride: int = TRAJ_STRIDE, traj_sparse: bool = False, out: SimpleNamespace | None = None, rules=(), enforce=()):
         """FissPlanner.plan / FissPlusPlanner.plan for every ego of the batch, entirely on the device (fp_plan_fiss):
         dense tables -> per-ego search walk -> (FISS+) refinement -> optional winner series.
 
@@ -651,9 +651,14 @@ class FrenetEngine:
         [B], the _abi.RULE_* the plan violates (0 for an ego without a plan).  The plan itself is the one the call returns without
         `rules`: the walks do not look at the verdict.  The flag word comes from the call's best_flags when winner=True (the series
         writer fills it), else from eval_trajs on the end state.
+        enforce: names of rules.TABLE the batch carries data for - the walks OBEY them (fp_plan_fiss_rules): the dense tables are masked
+        by those rules' passes before the search reads them, and a refined candidate that violates one is rejected when it is popped;
+        also `rejected` [B], the consumed refined candidates per ego that only a rule rejected.  The visiting order stays cost-only.
+        May be combined with rules= (the audit of what is returned).
         """
         B = batch.B
         audit = rules_mod.check_names(rules, batch, "plan_fiss(rules=...)") if rules else ()
+        enforced = rules_mod.check_names(enforce, batch, "plan_fiss(enforce=...)") if enforce else ()
         plus = kind in ("FISS+", _abi.FP_FISS_PLUS)
         R = fiss_rounds(kind, max_refine_iters)
         if out is None:
@@ -664,6 +669,8 @@ class FrenetEngine:
                                     best_flags=("uint32", ()) if winner else None, best_traj=("float64", (16, traj_stride)) if winner else None))
         out.prev_best_idx[...] = -1 if prev_best_idx is None else np.asarray(prev_best_idx, dtype=np.int32)
         prev = out.prev_best_idx
+        if enforced:
+            out.rejected = np.zeros(B, dtype=np.int32)
         if B == 0:
             if audit:
                 out.rule_bits = np.zeros(0, dtype=np.uint32)
@@ -691,7 +698,18 @@ class FrenetEngine:
             io.traj_stride, io.traj_sparse = int(traj_stride), int(traj_sparse)
             out.__dict__["_io"] = (key, io, batch.samp_min, batch.samp_max, batch.samp_res)  # (the arrays kept alive: their ids are the key)
         p, fb = host_structs(batch)
-        _abi.check(self._lib.fp_plan_fiss(self._ctx, C.byref(p), C.byref(fb), C.byref(opts), C.byref(io), _abi.FP_MEM_HOST, None))
+        if enforced:
+            held = {}
+
+            def addr(name):
+                held[name] = np.ascontiguousarray(rules_mod.array(batch, name))  # (kept alive over the call)
+                return _ptr(held[name])
+
+            rs, structs = rules_mod.rule_set(batch, addr, enforced)
+            _abi.check(self._lib.fp_plan_fiss_rules(self._ctx, C.byref(p), C.byref(fb), C.byref(opts), C.byref(io), C.byref(rs), None, _ptr(out.rejected),
+                                                    _abi.FP_MEM_HOST, None))
+        else:
+            _abi.check(self._lib.fp_plan_fiss(self._ctx, C.byref(p), C.byref(fb), C.byref(opts), C.byref(io), _abi.FP_MEM_HOST, None))
         if audit:
             out.rule_bits = self.rules_eval(batch, out.end_state[:, None, :], out.best_flags[:, None] if winner else None, audit).rule_bits[:, 0]
         return out
@@ -787,6 +805,14 @@ class FrenetEngine:
     def plan_fiss_device(self, params: _abi.FpParams, fb: _abi.FpBatch, opts: _abi.FpFissOpts, io: _abi.FpFissIo, stream: int = 0):
         """Enqueue the whole FISS / FISS+ pipeline (lattice, search, refinement, winner series); device addresses in `io`."""
         _abi.check(self._lib.fp_plan_fiss(self._ctx, C.byref(params), C.byref(fb), C.byref(opts), C.byref(io), _abi.FP_MEM_DEVICE, stream or None))
+
+    def plan_fiss_rules_device(self, params: _abi.FpParams, fb: _abi.FpBatch, opts: _abi.FpFissOpts, io: _abi.FpFissIo, rule_set: _abi.FpRuleSet,
+                               loop: _abi.FpLoopIo | None = None, rejected: int = 0, stream: int = 0):
+        """Enqueue the FISS / FISS+ pipeline that obeys `rule_set` (fp_plan_fiss_rules; rule_set from rules.rule_set with device
+        addresses): the rules' table passes between the lattice and the search, the refinement's rule instances; with `loop` the
+        hand-over of fp_plan_fiss_step follows.  rejected [B] int32 in / out or 0.  A linear chain of launches, nothing waited for."""
+        _abi.check(self._lib.fp_plan_fiss_rules(self._ctx, C.byref(params), C.byref(fb), C.byref(opts), C.byref(io), C.byref(rule_set),
+                                                None if loop is None else C.byref(loop), rejected or None, _abi.FP_MEM_DEVICE, stream or None))
 
     def eval_trajs_device(self, params: _abi.FpParams, fb: _abi.FpBatch, K: int, end_states: int, cost: int, flags: int,
                           traj: int = 0, stream: int = 0, traj_stride: int = TRAJ_STRIDE, traj_sparse: bool = False):

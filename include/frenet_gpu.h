@@ -943,6 +943,38 @@ int fp_plan_step(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, co
 int fp_plan_fiss_step(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, const fp_fiss_opts* opts, const fp_fiss_io* io,
                       const fp_loop_io* loop, int mem, void* stream);
 
+/* ---- FISS / FISS+ that obey the road rules: fp_plan_fiss_rules (added within ABI 18: one new symbol, found by looking it up) -------
+ * fp_plan_fiss (loop = NULL) or fp_plan_fiss_step (loop set, FP_MEM_DEVICE only) whose cost-ordered VALIDATION sees the verdicts of the
+ * rules in `rules` (as fp_rules_eval: a NULL member = that rule is off, all four NULL = FP_EINVAL).  The visiting order, the frontier and
+ * the gradient rounds stay cost-only (fiss_planner.py:229-258, fiss_plus_planner.py:120-146, :301-323 are the only places either walk
+ * consults feasibility).
+ *  1. Lattice stage.  The call's dense tables (ctx scratch) are masked by the table passes of the rules that are on, in the order
+ *     fp_speed_envelope, fp_gate_mask, fp_boundary_mask, fp_gap_mask - the launches a dense call's caller makes behind it, so the table
+ *     the search reads is bit for bit the one that chain leaves.  The search runs in its own launch (no appended search, no inline inputs).
+ *  2. Search.  The unchanged walk, with FP_FLAG_BOUNDARY counting as a constraint bit (the stand-alone search kernels test
+ *     FP_FLAG_CONSTRAINTS | FP_FLAG_BOUNDARY; no other entry point puts bit 128 into their table).  Stats keep their meaning on the masked
+ *     words: validated = pops, collision_checks = pops without a constraint or boundary bit; "nothing feasible" is C + 1, C, C,
+ *     pass_constraints.
+ *  3. Refinement (FP_FISS_PLUS, max_refine_iters > 0).  Rounds, candidate list, pop order (cost, then generation index) and the end test
+ *     `cost > coarse cost` are unchanged.  A popped candidate's word is the trajectory's own; if it has no FP_FLAG_INFEASIBLE bit the
+ *     enforced rules are evaluated on it in the order above, exactly as fp_rules_eval defines them for an end state whose word on entry is
+ *     that word (the gaps only when the word is still feasible after the other three), and the loop consumes the result - again with
+ *     FP_FLAG_BOUNDARY as a constraint bit.  rejected [B] (in / out, or NULL) is increased by the number of CONSUMED pops that were feasible
+ *     by their own word and got a rule bit.  If no refined candidate survives, the coarse winner - rule-clean by 1 - stands.
+ *  4. Everything else - skipped egos, egos without a coarse winner, prev_best_idx, trace, best_flags / best_traj (the trajectory's own
+ *     word: it is feasible, the rules add nothing), the refusals, the hand-over with `loop` - is fp_plan_fiss' / fp_plan_fiss_step's.
+ *     FP_MEM_HOST stages the rule arrays as fp_rules_eval's host call does and checks them the same way (a clock before step 0 stays
+ *     refused: the lattice stage plans from it).  FP_MEM_DEVICE is a linear chain of launches on the caller's stream: it waits for
+ *     nothing, allocates nothing after the first call of a size, and can be captured into a graph.
+ *  5. With a rule set that cannot speak on the batch (limits +inf, a corridor wider than any footprint, gates never closed, lags with no
+ *     obstacle near) every output equals fp_plan_fiss' bit for bit, Stats included.
+ * Limit: the refinement's rule instances hold the rules' tables in LDS beside the refinement's own layout - NX doubles (limits), 4 NX
+ * (corridor), FP_MAX_GATES + points / 2 (gates), 4 n_obs (gaps).  A call with refinement rounds whose total exceeds 160 KB is refused
+ * with FP_ELIMIT in both memory modes (the message names the sizes).
+ * fp_ctx_get_option("fiss_rules_calls") counts the calls that passed their argument checks. */
+int fp_plan_fiss_rules(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, const fp_fiss_opts* opts, const fp_fiss_io* io,
+                       const fp_rule_set* rules, const fp_loop_io* loop, int32_t* rejected, int mem, void* stream);
+
 /* ---- the driven trajectory of a device-resident loop (ABI 17) ---------------------------------------------------
  * The reference's loop returns `state_list` - one row per driven cycle: time step, position, orientation, velocity, velocity_y
  * (planners/benchmark/planning.py:135-148) - beside the summed Stats and goal_reached (:129, :150-161).  fp_loop_record keeps that
