@@ -328,6 +328,26 @@ struct MarginArgs {
     int32_t* min_obs = nullptr;
 };
 hipError_t launch_traj_margins(const KernelArgs& ka, const MarginArgs& m, hipStream_t stream);
+// A stopping manoeuvre for the egos without a plan (frenet_fallback.hip, fp_fallback_stop): one workgroup per ego, in the order of perm
+// (optional).  Device addresses; best_idx [B] or nullptr, end_state [B][3] in/out, cand [B][n_d * n_stop] or nullptr, counts [B][4]
+// in/out or nullptr, the other outputs [B].
+struct FallbackArgs {
+    int n_d = 0, n_stop = 0;
+    const double* d_targets = nullptr;
+    const double* stop_T = nullptr;
+    double max_decel = 0.0;
+    const int32_t* best_idx = nullptr;
+    double* end_state = nullptr;
+    int32_t* status = nullptr;
+    int32_t* fb_idx = nullptr;
+    int32_t* hit_step = nullptr;
+    int32_t* hit_obs = nullptr;
+    double* hit_speed = nullptr;
+    int32_t* cand = nullptr;
+    int32_t* counts = nullptr;
+    const int32_t* perm = nullptr;
+};
+hipError_t launch_fallback_stop(const KernelArgs& ka, const FallbackArgs& a, hipStream_t stream);
 // The obstacle pose table from tracks (frenet_predict.hip, fp_obstacles_predict): rows max(t0, 0) .. min(T_obs, t0 + n_rows) - 1 of
 // every scene of obs_pose [S][T_obs][n_obs][4].  Device addresses; nx / knots / coef / frame_of_scene may be NULL (LANE columns then
 // have no pose).  compact: the output is [S][span][n_obs][4], span = min(T_obs, n_rows), and a scene's first written row lands in

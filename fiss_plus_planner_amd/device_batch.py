@@ -86,7 +86,7 @@ class ClosedLoopRunner:
 
     def __init__(self, engine: FrenetEngine, dbatch: DeviceBatch, goal_xy: np.ndarray, planner: str = "FOP", fused: bool = True,
                  goal_poly: np.ndarray | None = None, goal_nv: np.ndarray | None = None, goal_intervals: np.ndarray | None = None,
-                 rules=(), audit=(), enforce=()):
+                 rules=(), audit=(), enforce=(), fallback=None):
         """rules: any subset of the names in rules.TABLE - FOP only, and the batch must carry each rule's data (speed profile / gates /
         corridor / a time gap with a lag above 0).  The cycle then is fp_plan_dense into the runner's own [B][C] tables, the passes asked
         for in the table's order, whatever the caller's, each writing best_idx / best_cost, and fp_advance on the last one's winner;
@@ -102,6 +102,13 @@ class ClosedLoopRunner:
         rule's data.  Each cycle is one fp_plan_fiss_rules call with the loop's fp_loop_io (FISS+: the refinement's rule instance hands the
         ego over; FISS: the advance kernel follows); with audit= as well it is fp_plan_fiss_rules (loop = NULL) -> fp_rules_eval ->
         fp_advance.  self.rejected [B] int32 sums, per ego, the refined candidates a rule alone rejected; run / run_graph return it.
+        fallback: a FallbackStop - FOP (with or without rules=) and FISS / FISS+ (with or without enforce=).  The cycle then is the plan
+        without a fused hand-over (fp_plan_dense + the rule passes, fp_plan_fiss, or fp_plan_fiss_rules with loop = NULL) ->
+        fp_fallback_stop -> fp_advance(end_state): an ego whose plan call found nothing brakes to a stop along the lane instead of ending
+        with FP_DONE_NO_SOLUTION, and plans again in the next cycle; `fused` has no say.  self.fallback_counts [B, 4] int32 counts, per ego,
+        the cycles by fallback status (_abi.FALLBACK_*: column 0 = the ego had a plan or was finished); run / run_graph return it.  With
+        record=True the log is written from end_state for FOP too: its FP_LOG_BEST_IDX column is then -1 in every row.  fallback= with
+        audit= is not done (ValueError).  fallback=None: the calls below, unchanged.
         fused: an FOP cycle is ONE launch (fp_plan_step: the workgroup that finds an ego's argmin advances the ego); False = the two
         calls fp_plan_dense + fp_advance (same results; the A/B of tests and bench).
         goal_poly [B, V, 2] + goal_nv [B] (+ goal_intervals [B, 6] = time_step / velocity / orientation lo, hi; NaN = undefined): the
@@ -109,6 +116,9 @@ class ClosedLoopRunner:
         self.rules = self._check_rules(rules, planner, dbatch.host)  # (first: the argument errors need no device)
         self.audit = self._check_audit(audit, planner, dbatch.host)
         self.enforce = self._check_enforce(enforce, planner, dbatch.host, self.rules)
+        if fallback is not None and self.audit:
+            raise ValueError("ClosedLoopRunner: fallback= with audit= is not done (the audit's verdict is taken on the planner's own end state)")
+        self.fallback = fallback
         torch = dbatch.torch
         self.eng, self.db, self.planner, self.fused = engine, dbatch, planner, fused
         B = dbatch.B
@@ -161,6 +171,23 @@ class ClosedLoopRunner:
             self.fio.traj_stride, self.fio.traj_sparse = stride, 1
             self.violations = torch.zeros((B, _abi.FP_RULE_COUNT), dtype=i32, device=dbatch.dev)
             self.rule_set, self._rule_structs = _rules.rule_set(dbatch.host, lambda k: dbatch.t[k].data_ptr(), self.audit)
+        if fallback is not None:  # the family on device addresses, the call's outputs, and the per-ego counts by status
+            if planner == "FOP":
+                self.end_state = torch.full((B, 3), float("nan"), dtype=f64, device=dbatch.dev)
+            self._fb_arrays = {}
+
+            def fb_addr(name, a):
+                self._fb_arrays[name] = torch.from_numpy(a).to(dbatch.dev)
+                return self._fb_arrays[name].data_ptr()
+
+            self.fb_struct = fallback.struct(dbatch.host, fb_addr)
+            self.fb_status, self.fb_idx, self.fb_hit_step, self.fb_hit_obs = (torch.zeros(B, dtype=i32, device=dbatch.dev) for _ in range(4))
+            self.fb_hit_speed = torch.full((B,), float("nan"), dtype=f64, device=dbatch.dev)
+            self.fallback_counts = torch.zeros((B, 4), dtype=i32, device=dbatch.dev)
+            # (the fallback's own calls are sized for its longest stop time; the plan calls keep the batch's params)
+            self.fb_params = _abi.FpParams.from_buffer_copy(dbatch.params)
+            pts = max(fallback.points_max(dbatch.host.tick_t), int(dbatch.params.points_max))
+            self.fb_params.points_max = min(pts, _abi.FP_MAX_POINTS) if pts > _abi.FP_FAST_POINTS else 0
         if self.enforce:  # the enforced set on device addresses, and the per-ego count of rule-rejected refined candidates
             self.rejected = torch.zeros(B, dtype=i32, device=dbatch.dev)
             self.enforce_set, self._enforce_structs = _rules.rule_set(dbatch.host, lambda k: dbatch.t[k].data_ptr(), self.enforce)
@@ -223,10 +250,37 @@ class ClosedLoopRunner:
             eng._table_pass_device(rule, db.params, self.fb, struct, cost, flags, bi, bc, n, stream)
         _abi.check(eng._lib.fp_advance(eng._ctx, C.byref(db.params), C.byref(self.fb), bi, None, C.byref(self.io), _abi.FP_MEM_DEVICE, stream or None))
 
+    def _step_fallback(self, stream: int):
+        """plan (no fused hand-over) -> fp_fallback_stop -> fp_advance(end_state): a linear chain on `stream`."""
+        import ctypes as C
+
+        db, eng = self.db, self.eng
+        bi = 0
+        if self.planner == "FOP":
+            bi, bc = self.best_idx.data_ptr(), self.best_cost.data_ptr()
+            if self.rules:
+                cost, flags = self.cost_tbl.data_ptr(), self.flag_tbl.data_ptr()
+                eng.plan_dense_device(db.params, self.fb, bi, bc, self.stats.data_ptr(), cost_tbl=cost, flag_tbl=flags, stream=stream)
+                for rule, struct, n in self.passes:
+                    eng._table_pass_device(rule, db.params, self.fb, struct, cost, flags, bi, bc, n, stream)
+            else:
+                eng.plan_dense_device(db.params, self.fb, bi, bc, self.stats.data_ptr(), stream=stream)
+        elif self.enforce:
+            eng.plan_fiss_rules_device(db.params, self.fb, self.fopts, self.fio, self.enforce_set, None, self.rejected.data_ptr(), stream)
+        else:
+            eng.plan_fiss_device(db.params, self.fb, self.fopts, self.fio, stream=stream)
+        eng.fallback_stop_device(self.fb_params, self.fb, self.fb_struct, self.end_state.data_ptr(), self.fb_status.data_ptr(), self.fb_idx.data_ptr(),
+                                 self.fb_hit_step.data_ptr(), self.fb_hit_obs.data_ptr(), self.fb_hit_speed.data_ptr(), best_idx=bi,
+                                 counts=self.fallback_counts.data_ptr(), stream=stream)
+        _abi.check(eng._lib.fp_advance(eng._ctx, C.byref(self.fb_params), C.byref(self.fb), None, self.end_state.data_ptr(), C.byref(self.io),
+                                       _abi.FP_MEM_DEVICE, stream or None))
+
     def step(self, stream: int = 0):
         """One plan cycle for every running ego + the state hand-over, enqueued on `stream`."""
         import ctypes as C
 
+        if self.fallback is not None:
+            return self._step_fallback(stream)
         if self.rules:
             return self._step_rules(stream)
         if self.audit:
@@ -272,8 +326,8 @@ class ClosedLoopRunner:
         """fp_loop_record behind the step just enqueued on `stream`: every running ego's new state goes to its next log row."""
         import ctypes as C
 
-        fop = self.planner == "FOP"
-        _abi.check(self.eng._lib.fp_loop_record(self.eng._ctx, C.byref(self.db.params), C.byref(self.fb), C.byref(self.io),
+        fop = self.planner == "FOP" and self.fallback is None  # (with a fallback the driven plan is end_state for every planner)
+        _abi.check(self.eng._lib.fp_loop_record(self.eng._ctx, C.byref(self.db.params if self.fallback is None else self.fb_params), C.byref(self.fb), C.byref(self.io),
                                                 self.best_idx.data_ptr() if fop else None, None if fop else self.end_state.data_ptr(),
                                                 self.best_cost.data_ptr(), self.stats.data_ptr(), C.byref(self.flog), _abi.FP_MEM_DEVICE, stream or None))
 
@@ -289,6 +343,8 @@ class ClosedLoopRunner:
             out.log = self.log_fetch()
         if self.enforce:
             out.rejected = self.rejected.cpu().numpy()
+        if self.fallback is not None:
+            out.fallback_counts = self.fallback_counts.cpu().numpy()
         if self.audit:
             out.violation_counts = self.violations.cpu().numpy()
             cols = lambda bits: [i for i in range(_abi.FP_RULE_COUNT) if bits >> i & 1]  # noqa: E731

@@ -209,7 +209,7 @@ class FrenetEngine:
 
     def plan_dense(self, batch: ProblemBatch, tables: bool = True, winner: bool = False, traj_stride: int = TRAJ_STRIDE, traj_sparse: bool = False,
                    out: SimpleNamespace | None = None, audit: bool = False, top_k: int = 0, boundary: bool = False, margins: bool = False,
-                   envelope: bool = False, gates: bool = False, gaps: bool = False):
+                   envelope: bool = False, gates: bool = False, gaps: bool = False, fallback=None):
         """FrenetOptimalPlanner.plan() for every ego of the batch (reference frenet_optimal_planner.py:247-270).
 
         Returns best_idx [B] (flat (i_d*nt+i_T)*nv+i_v, -1 = none), best_cost [B], stats [B,4] and, with
@@ -233,7 +233,14 @@ class FrenetEngine:
         else follows the masked result likewise.  gaps=True (the batch must carry a time gap: gap_follow / gap_lead > 0): the time gap
         to moving obstacles (gap_mask); `flags` carry the added FLAG_COLLISION bits, also n_close [B].  The passes asked for run in the
         order of rules.TABLE, whatever the order of the keywords: every argmin honours the bits set before it.
+        fallback=FallbackStop(...): behind the last pass asked for, the egos whose best_idx is -1 get a stopping manoeuvre
+        (fallback_stop): also `fallback`, its namespace - fallback.end_state [B, 3] is the plan every ego drives.  best_idx, the tables
+        and everything taken on them (winner, top_k, margins) are the call's own answer without it.
         """
+        if fallback is not None:
+            out = self.plan_dense(batch, tables, winner, traj_stride, traj_sparse, out, audit, top_k, boundary, margins, envelope, gates, gaps)
+            out.fallback = self.fallback_stop(batch, fallback, best_idx=out.best_idx)
+            return out
         if margins:
             out = self.plan_dense(batch, tables, winner, traj_stride, traj_sparse, out, audit, top_k, boundary, envelope=envelope, gates=gates, gaps=gaps)
             plans = out.rank_idx if top_k else out.best_idx
@@ -535,6 +542,61 @@ class FrenetEngine:
                                              int(params.check_stride if pose_stride is None else pose_stride), min_dist or None, min_step or None, min_obs or None,
                                              _abi.FP_MEM_DEVICE, stream or None))
 
+    def fallback_stop(self, batch: ProblemBatch, fallback, best_idx: np.ndarray | None = None, end_state: np.ndarray | None = None, cand: bool = False,
+                      skip: np.ndarray | None = None, counts: np.ndarray | None = None):
+        """A stopping manoeuvre for the egos without a plan (fp_fallback_stop; the definition: include/frenet_gpu.h).  fallback: a
+        FallbackStop.  best_idx [B] (plan_dense's or a rule pass' argmin, < 0 = needs a fallback), or end_state [B, 3] (plan_fiss'
+        end_state, NaN = needs one) - exactly one of the two; the caller's arrays are not modified.  Returns a namespace: end_state
+        [B, 3] (the plan every ego drives: the lattice sample's or the untouched (d, v, T) of an ego with a plan, the chosen (d, 0, T) of
+        one without, NaN where nothing is admissible), status [B] (_abi.FALLBACK_*), fb_idx [B], hit_step / hit_obs / hit_speed [B],
+        counts [B, 4] (the caller's array plus one per ego in its status' column) and, with cand=True, cand [B, F] (-2 inadmissible,
+        -1 clear, else the first hit step; -3 in the rows of the egos that need none).  skip [B] (optional): egos that are not planned."""
+        if (best_idx is None) == (end_state is None):
+            raise ValueError("fallback_stop: exactly one of best_idx / end_state")
+        B = batch.B
+        if best_idx is not None:
+            bi = np.ascontiguousarray(best_idx, dtype=np.int32)
+            if bi.shape != (B,):
+                raise ValueError(f"fallback_stop: best_idx must be [B={B}], got {bi.shape}")
+            es = np.full((B, 3), np.nan)
+        else:
+            bi = None
+            es = np.array(end_state, dtype=np.float64, order="C")
+            if es.shape != (B, 3):
+                raise ValueError(f"fallback_stop: end_state must be [B={B}, 3], got {es.shape}")
+        held = {}
+
+        def addr(name, a):
+            held[name] = a
+            return _ptr(a)
+
+        fs = fallback.struct(batch, addr)
+        F = fs.n_d * fs.n_stop
+        out = SimpleNamespace(end_state=es, status=np.empty(B, dtype=np.int32), fb_idx=np.empty(B, dtype=np.int32), hit_step=np.empty(B, dtype=np.int32),
+                              hit_obs=np.empty(B, dtype=np.int32), hit_speed=np.empty(B), cand=np.full((B, F), -3, dtype=np.int32) if cand else None,
+                              counts=np.zeros((B, 4), dtype=np.int32) if counts is None else np.array(counts, dtype=np.int32, order="C"))
+        if out.counts.shape != (B, 4):
+            raise ValueError(f"fallback_stop: counts must be [B={B}, 4], got {out.counts.shape}")
+        p, fb = host_structs(batch)
+        if skip is not None:
+            skip = np.ascontiguousarray(skip, dtype=np.int32)
+            assert skip.shape == (B,)
+            fb.skip = _ptr(skip)
+        # (B == 0 still crosses the ABI: the argument checks are the library's)
+        _abi.check(self._lib.fp_fallback_stop(self._ctx, C.byref(p), C.byref(fb), C.byref(fs), _ptr(bi) if bi is not None else None, _ptr(es), _ptr(out.status),
+                                              _ptr(out.fb_idx), _ptr(out.hit_step), _ptr(out.hit_obs), _ptr(out.hit_speed), _ptr(out.cand) if cand else None,
+                                              _ptr(out.counts), _abi.FP_MEM_HOST, None))
+        return out
+
+    def fallback_stop_device(self, params: _abi.FpParams, fb: _abi.FpBatch, fallback: _abi.FpFallback, end_state: int, status: int, fb_idx: int, hit_step: int,
+                             hit_obs: int, hit_speed: int, best_idx: int = 0, cand: int = 0, counts: int = 0, stream: int = 0):
+        """Enqueue the fallback behind a plan call (device addresses; `fallback` holds device addresses too): best_idx [B] or 0 (then
+        end_state [B][3] says who needs one), cand [B][F] / counts [B][4] or 0.  params.points_max must cover the longest stop time.
+        One launch, nothing allocated, nothing waited for."""
+        _abi.check(self._lib.fp_fallback_stop(self._ctx, C.byref(params), C.byref(fb), C.byref(fallback), best_idx or None, end_state or None, status or None,
+                                              fb_idx or None, hit_step or None, hit_obs or None, hit_speed or None, cand or None, counts or None,
+                                              _abi.FP_MEM_DEVICE, stream or None))
+
     def predict_obstacles(self, batch, model, state, frame_of_scene=None, t0=0, n_rows: int | None = None, out: np.ndarray | None = None):
         """The obstacle pose table of `batch` predicted from tracks (fp_obstacles_predict through FP_MEM_HOST; the definition:
         include/frenet_gpu.h): model [S, n_obs] FP_TRACK_*, state [S, n_obs, 6], frame_of_scene [S] or None, t0 an int or [S],
@@ -641,7 +703,7 @@ class FrenetEngine:
 
     def plan_fiss(self, batch: ProblemBatch, kind: str = "FISS+", prev_best_idx: np.ndarray | None = None, w_heuristic: float = 10.0,
                   max_refine_iters: int = 3, decaying_factor: float = 0.5, winner: bool = False, trace: bool = False,
-                  traj_stride: int = TRAJ_STRIDE, traj_sparse: bool = False, out: SimpleNamespace | None = None, rules=(), enforce=()):
+                  traj_stride: int = TRAJ_STRIDE, traj_sparse: bool = False, out: SimpleNamespace | None = None, rules=(), enforce=(), fallback=None):
         """FissPlanner.plan / FissPlusPlanner.plan for every ego of the batch, entirely on the device (fp_plan_fiss):
         dense tables -> per-ego search walk -> (FISS+) refinement -> optional winner series.
 
@@ -655,6 +717,9 @@ class FrenetEngine:
         by those rules' passes before the search reads them, and a refined candidate that violates one is rejected when it is popped;
         also `rejected` [B], the consumed refined candidates per ego that only a rule rejected.  The visiting order stays cost-only.
         May be combined with rules= (the audit of what is returned).
+        fallback=FallbackStop(...): behind the walks (enforce= included), the egos whose end_state is NaN get a stopping manoeuvre
+        (fallback_stop): also `fallback`, its namespace - fallback.end_state [B, 3] is the plan every ego drives.  end_state, rule_bits
+        and the series are the call's own answer without it.
         """
         B = batch.B
         audit = rules_mod.check_names(rules, batch, "plan_fiss(rules=...)") if rules else ()
@@ -674,6 +739,8 @@ class FrenetEngine:
         if B == 0:
             if audit:
                 out.rule_bits = np.zeros(0, dtype=np.uint32)
+            if fallback is not None:
+                out.fallback = self.fallback_stop(batch, fallback, end_state=out.end_state)
             return out
         okey = (plus, R, w_heuristic, decaying_factor)
         ocached = out.__dict__.get("_opts")
@@ -712,6 +779,8 @@ class FrenetEngine:
             _abi.check(self._lib.fp_plan_fiss(self._ctx, C.byref(p), C.byref(fb), C.byref(opts), C.byref(io), _abi.FP_MEM_HOST, None))
         if audit:
             out.rule_bits = self.rules_eval(batch, out.end_state[:, None, :], out.best_flags[:, None] if winner else None, audit).rule_bits[:, 0]
+        if fallback is not None:
+            out.fallback = self.fallback_stop(batch, fallback, end_state=out.end_state)
         return out
 
     def materialize_all(self, batch: ProblemBatch, traj_stride: int = TRAJ_STRIDE, traj_sparse: bool = False):

@@ -103,6 +103,8 @@ _TRAJ_DEFAULTS = dict(lane_id=-1, lane_type=None, is_generated=False, is_searche
 class FrenetTrajectory:
     """Result object of ``plan()``; filled from a [16, stride] device dump."""
 
+    is_fallback = False  # True on the stopping manoeuvre plan() returns when it found nothing and set_fallback() is on
+
     def __init__(self):
         self.idx = np.array([-1, -1, -1])
         self.lane_id = -1

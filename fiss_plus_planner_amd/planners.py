@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import itertools
 import time
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -256,6 +257,34 @@ class FrenetOptimalPlanner:
             raise ValueError(f"set_time_gap: a grace of {grace_s} s is more than INT32_MAX steps of {tick} s")
         self._time_gap = (float(follow_s), float(lead_s), float(grace_s)) if follow_s > 0 or lead_s > 0 else None
 
+    def set_fallback(self, fallback):
+        """A stopping manoeuvre for the cycles in which plan() finds nothing: fallback = a FallbackStop (fallback.py), None removes it.
+        plan() of every planner class then returns, instead of what it returns today for "no solution" (FOP: its previous best_traj,
+        the others None), the FrenetTrajectory fp_fallback_stop chooses for the start state - the ego brakes to v = 0 along the lane, a
+        stop without contact first, else the latest contact (include/frenet_gpu.h) - with `is_fallback` True and the series of
+        fp_eval_trajs; `planner.fallback_info` carries status (_abi.FALLBACK_*), fb_idx, hit_step, hit_obs and hit_speed.  When no
+        candidate of the family is admissible (status FALLBACK_NONE) plan() returns what it returns today.  best_traj, prev_best_idx
+        and the Stats are the planner's own: the fallback changes none of them.  The fallback obeys no rule pass."""
+        self._fallback_stop = fallback
+
+    def _fallback(self, batch: ProblemBatch, none):
+        """What plan() returns when it found nothing: `none` (today's answer) without set_fallback or without an admissible stop."""
+        fb = getattr(self, "_fallback_stop", None)
+        if fb is None:
+            return none
+        r = self._engine.fallback_stop(batch, fb, best_idx=np.array([-1], dtype=np.int32))
+        self.fallback_info = SimpleNamespace(status=int(r.status[0]), fb_idx=int(r.fb_idx[0]), hit_step=int(r.hit_step[0]), hit_obs=int(r.hit_obs[0]),
+                                             hit_speed=float(r.hit_speed[0]))
+        if self.fallback_info.status == _abi.FALLBACK_NONE:
+            return none
+        es = r.end_state[0]
+        n = int(np.ceil(es[2] / self.settings.tick_t))
+        out = self._engine.eval_trajs(batch, es[None, None], dump=True, traj_stride=max(self._stride(), (n + 15) // 16 * 16))
+        _, N, M = unpack_flags(out.flags[0])
+        traj = FrenetTrajectory.from_dump(out.traj[0, 0], int(N[0]), int(M[0]), float(out.cost[0, 0]), FrenetState(t=es[2], s=0.0, s_d=es[1], d=es[0]))
+        traj.is_fallback = True
+        return traj
+
     # ------------------------------------------------------------------ problem marshalling
     def _predicted_table(self, tracks: ObstacleTracks, time_step_now: int) -> ObstacleTable:
         """The pose table of an ObstacleTracks against this planner's own frame: the track states are valid at time_step_now and
@@ -300,6 +329,7 @@ class FrenetOptimalPlanner:
         changed - the speed samples are rewritten in place."""
         if self.cubic_spline is None:
             raise RuntimeError("generate_frenet_frame() must be called before plan()")
+        self.__dict__.pop("fallback_info", None)  # (every plan() call builds its batch here: the info describes the last call only)
         st = self.settings
         tab = self._obstacle_table(obstacles, time_step_now)
         sp = self.cubic_spline
@@ -446,7 +476,7 @@ class FrenetOptimalPlanner:
         else:
             self.__dict__.pop("alternatives", None)
         self._margins(batch, self.best_traj if best >= 0 else None)
-        return self.best_traj
+        return self.best_traj if best >= 0 else self._fallback(batch, self.best_traj)
 
     def _margins(self, batch: ProblemBatch, traj):
         """settings.report_margins: best_margin of the trajectory this plan() call found (None: it found none) and, beside
@@ -503,7 +533,7 @@ class FopPlusPlanner(FrenetOptimalPlanner):
         self.stats = Stats(*st)
         if best is None:
             self._margins(batch, None)
-            return None
+            return self._fallback(batch, None)
         es, _ = self._end_state_of_flat(batch, best)
         trajs, _ = self._materialize(batch, es[None])
         self.best_traj = trajs[0]
@@ -587,7 +617,7 @@ class FissPlanner(FrenetOptimalPlanner):
             self.sampling_res = self.sampling_res * st.decaying_factor ** R  # decays in place in the reference (:282)
         if not found:
             self._margins(batch, None)
-            return None
+            return self._fallback(batch, None)
         self.prev_best_idx = out.prev_best_idx[0].copy()
         fl = int(out.best_flags[0])  # N and M ride in the flag word (FP_FLAG_N_SHIFT / FP_FLAG_M_SHIFT)
         es = out.end_state[0].tolist()
@@ -626,7 +656,7 @@ class FissPlanner(FrenetOptimalPlanner):
         batch, idx = self._coarse(frenet_state, max_target_speed, obstacles, time_step_now)
         if idx is None:
             self._margins(batch, None)
-            return None
+            return self._fallback(batch, None)
         es = np.array([batch.d_samples[idx[0]], batch.v_samples[0, idx[1]], batch.t_samples[idx[2]]])
         trajs, _ = self._materialize(batch, es[None], [np.array(idx)])
         self.best_traj = trajs[0]
@@ -648,7 +678,7 @@ class FissPlusPlanner(FissPlanner):
         batch, idx = self._coarse(frenet_state, max_target_speed, obstacles, time_step_now)
         if idx is None:
             self._margins(batch, None)
-            return None
+            return self._fallback(batch, None)
         x = np.array([batch.d_samples[idx[0]], batch.v_samples[0, idx[1]], batch.t_samples[idx[2]]])
         coarse_cost = float(self.last_tables[0][(idx[0] * batch.nt + idx[2]) * batch.nv + idx[1]])
         self.prev_best_idx = np.array(idx)  # stays the coarse index even if a refined trajectory wins (:140)

@@ -316,7 +316,7 @@ int fp_ctx_destroy(fp_ctx* ctx);
 int fp_ctx_set_option(fp_ctx* ctx, const char* name, int value);
 /* Reads an option back, or one of the read-only counters "clearance_launches" (launches of the clearance rescoring kernel,
  * fp_params.w_obstacle > 0, of this ctx so far), "looplog_launches" (launches of fp_loop_record's kernel), "rank_launches" (launches of
- * fp_rank_feasible's kernel), "boundary_launches" (launches of fp_boundary_mask's kernel), "envelope_launches" (launches of fp_speed_envelope's kernel), "gate_launches" (launches of fp_gate_mask's kernel), "margin_launches" (launches of fp_traj_margins' kernel), "rules_eval_launches" (launches of fp_rules_eval's kernel), "predict_launches" (launches of
+ * fp_rank_feasible's kernel), "boundary_launches" (launches of fp_boundary_mask's kernel), "envelope_launches" (launches of fp_speed_envelope's kernel), "gate_launches" (launches of fp_gate_mask's kernel), "margin_launches" (launches of fp_traj_margins' kernel), "fallback_launches" (launches of fp_fallback_stop's kernel), "rules_eval_launches" (launches of fp_rules_eval's kernel), "predict_launches" (launches of
  * fp_obstacles_predict's kernel), "from_state_launches" (launches of fp_from_state's kernel), "lattice_launches" (dense lattice launches of this ctx so far) and
  * "lattice_ordered_launches" (those dispatched in a feedback order or in the order of fp_batch.launch_order) - bench.py reports when an
  * order took effect -, "lattice_launches_2" / "_3" / "_4" (PROCESS-wide: fused lattice launches so far by workgroups per compute unit). */
@@ -737,6 +737,80 @@ int fp_traj_margins(fp_ctx* ctx, const fp_params* params, const fp_batch* batch,
                     int32_t* min_step,           /* [K][B] */
                     int32_t* min_obs,            /* [K][B] */
                     int mem, void* stream);
+
+/* ---- a stopping manoeuvre for the egos without a plan (added WITHIN ABI 18: detect it by looking the symbol up, e.g. dlsym) ------
+ * Every planner here answers "no solution" with best_idx = -1 / a NaN end state, and fp_advance then ends the ego with
+ * FP_DONE_NO_SOLUTION: its next state is never computed.  Every rule pass removes more candidates, so in a resident closed loop an
+ * ego whose candidates are all flagged leaves the simulation at full speed.  fp_fallback_stop gives such an ego a degraded answer: it
+ * brakes to a stop along the lane; if contact can no longer be avoided the contact comes as late as possible; and it keeps planning,
+ * so the ego drives on when the road clears.  The egos that have a plan pay one early return.
+ *
+ * need(b)      batch->skip[b] == 0 and: best_idx given and best_idx[b] < 0; or best_idx NULL and end_state[b][0] is NaN (what
+ *              fp_plan_fiss leaves for an ego without a trajectory).
+ * family       candidate f = i_d * n_stop + i_T is the explicit end state (d_targets[i_d], or the ego's own d0 when that entry is NaN;
+ *              v = 0; stop_T[i_T]) - exactly the trajectory fp_eval_trajs builds for it: a longitudinal quartic to v = 0, s_dd = 0 at T,
+ *              a lateral quintic to the offset with zero end derivatives, N = len(arange(0, T, tick_t)) series points, M = the first
+ *              point off the reference line.
+ * admissible   N <= the points the call is sized for (FP_FAST_POINTS, or params->points_max) and M >= 2 and, at every series point
+ *              i < N, s_d[i] >= -FP_FALLBACK_REVERSE_TOL (the ego never reverses: v0 = 5, a0 = -4, T = 6 passes through -0.5 m/s) and
+ *              -s_dd[i] <= max_decel.
+ * first contact  over the collision check's own pose set, i = 0, check_stride, ... < min(M, final_time_step - t_now) with
+ *              0 <= i + t_now < T_obs: hit_step = the smallest i at which the footprint intersects a valid column, hit_obs = the smallest
+ *              such column at that pose, hit_speed = s_d[hit_step]; -1, -1, NaN without contact.  The predicate is the collision check's
+ *              own: fp_traj_margins(end_state, pose_stride = check_stride) has min_dist == 0 exactly when there is a hit, and names the
+ *              same step and column; fp_eval_trajs sets FP_FLAG_COLLISION exactly then.
+ * choice       among the admissible candidates only; every key is an integer or one exact IEEE operation on inputs, so two
+ *              implementations of the definition agree bit for bit:
+ *                1. a candidate without contact beats one with contact;
+ *                2. among candidates without contact the larger i_T wins (the gentlest stop);
+ *                3. among candidates with contact the larger hit_step wins (the latest contact), then the smaller i_T (brake hardest);
+ *                4. then the smaller fabs(d_end - d0);  5. then the smaller i_d.
+ * outputs, need(b):  status[b] = FP_FALLBACK_CLEAR / _CONTACT / _NONE (no admissible candidate); fb_idx[b] = f, or -1 for NONE;
+ *              end_state[b] = the chosen (d, 0, T), or three NaN for NONE; hit_step / hit_obs / hit_speed as above;
+ *              cand[b][f] = -2 inadmissible, -1 clear, else the candidate's first hit step; counts[b][status] += 1.
+ * outputs, no need:  status 0, fb_idx -1, hit_step / hit_obs / hit_speed -1, -1, NaN, cand untouched, counts[b][0] += 1.  With best_idx
+ *              given, end_state[b] becomes the lattice sample's (d_samples[i_d], v_samples[b][i_v], t_samples[i_T]), decoded as
+ *              fp_advance decodes it; with best_idx NULL it is untouched.
+ * outputs, skipped ego:  status 0 and the "none" values (counts[b][0] += 1); end_state becomes NaN when best_idx is given and is
+ *              untouched otherwise.  None of its rows is read.
+ * After the call end_state is "the plan every ego drives": a valid argument of fp_advance, fp_loop_record, fp_eval_trajs,
+ * fp_traj_margins and fp_rules_eval.
+ *
+ * FP_MEM_DEVICE: one kernel is enqueued (one workgroup per ego, in the order of batch->launch_order when there is one) - nothing is
+ * allocated, nothing waited for, the call can be captured.  The result does not depend on launch_order, and two runs give the same
+ * bits.  FP_MEM_HOST stages the batch and the call's arrays through the ctx and waits, like fp_traj_margins.
+ * Errors, all before any launch: a NULL fallback / d_targets / stop_T / end_state / status / fb_idx / hit_step / hit_obs / hit_speed,
+ * n_d < 1, n_stop < 1: FP_EINVAL; n_d * n_stop > FP_MAX_FALLBACK: FP_ELIMIT; max_decel not positive or NaN: FP_EINVAL.  FP_MEM_HOST
+ * also refuses a stop_T entry that is not finite, not positive or not above its predecessor (FP_EINVAL, the entry named), one that
+ * needs more than FP_MAX_POINTS points (FP_ELIMIT; on the device such a candidate is inadmissible) and a best_idx >= nd*nv*nt of an
+ * ego that is not skipped (FP_EINVAL, as fp_advance answers; on the device such an ego gets a NaN end state).
+ * Also read-only in fp_ctx_get_option: "fallback_launches" = launches of the kernel on this ctx so far (0 for a caller that never asks).
+ * Deliberately not done:
+ *   - the fallback obeys no rule pass: a stop may end across a stop line;
+ *   - the footprint's heading is the series' own yaw, the difference quotient of calc_global_paths: an ego that stands from the first
+ *     point has yaw 0, as every lattice candidate at v = 0 already has in every entry point - changing that is a change to all of them;
+ *   - no fp_shard_call slot, nothing inside fp_plan_step / fp_plan_fiss_step (a loop enqueues plan, fp_fallback_stop, fp_advance),
+ *     no per-row marker in the loop log. */
+#define FP_MAX_FALLBACK 256          /* n_d * n_stop */
+#define FP_FALLBACK_REVERSE_TOL 1e-6 /* m/s */
+enum { FP_FALLBACK_NOT_NEEDED = 0, FP_FALLBACK_CLEAR = 1, FP_FALLBACK_CONTACT = 2, FP_FALLBACK_NONE = 3 };
+
+typedef struct {
+    int32_t n_d, n_stop;
+    const double* d_targets;  /* [n_d]    lateral end offsets; a NaN entry = the ego's own d0 (stay where you are) */
+    const double* stop_T;     /* [n_stop] stop times in seconds, strictly ascending, > 0 */
+    double max_decel;         /* > 0, +inf = no limit */
+} fp_fallback;
+
+int fp_fallback_stop(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, const fp_fallback* fallback,
+                     const int32_t* best_idx,   /* NULL or [B] */
+                     double* end_state,         /* [B][3] in/out */
+                     int32_t* status,           /* [B] */
+                     int32_t* fb_idx,           /* [B] */
+                     int32_t* hit_step, int32_t* hit_obs, double* hit_speed,   /* [B] each */
+                     int32_t* cand,             /* NULL or [B][n_d * n_stop] */
+                     int32_t* counts,           /* NULL or [B][4] in/out */
+                     int mem, void* stream);
 
 /* ---- obstacle pose tables from tracks (added WITHIN ABI 18: detect it by looking the symbol up, e.g. dlsym) --------------
  * The reference has no predictor: it reads CommonRoad's recorded trajectories through `state_at_time` and skips an obstacle that has no
