@@ -376,6 +376,14 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
     const int tid = threadIdx.x;
     const int lane = tid & (kWave - 1);
     const int wave = tid / kWave;
+    // The prologue's cuts: phases entered on a scalar test of the wavefront's number, the cost sums dealt by kind, one boundary-value solve
+    // per lat profile, the ends of d_samples found once, G with a column per lane - each described where it stands.  In the shaped
+    // rectangle instances only: the run-time-shape instances have no scalar register to spare and came out larger with them, and the two
+    // shaped polygon instances (80 VGPRs, all in use) spill a VGPR with them; both keep the statements they had.
+    constexpr bool kCut = kShape && !POLY;
+    // the same number in a scalar register (kCut): a phase that belongs to some of the wavefronts is entered on a scalar
+    // compare and a branch - on `wave` every wavefront pays the vector compare and the EXEC round trip of a phase that is not its own
+    const int wave_s = kCut ? __builtin_amdgcn_readfirstlane(wave) : wave;
     const int nd = kShape ? ND : p.nd, nv = kShape ? NV : p.nv, nt = kShape ? NT : p.nt;
     const int C = nd * nv * nt;
     const int it_lo = part * nt / nsplit, it_hi = (part + 1) * nt / nsplit;  // this workgroup's slices
@@ -491,6 +499,7 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
         }
         return;
     }
+    // [section STAGE]
     // ---------------------------------------------------------------- stage: ego, spline, obstacle rows
     // Global reads cost 1-2 us each, so everything that depends only on the scalars above is requested at once.  The obstacle
     // table is NOT staged: the group test reads it once, straight from global memory, and keeps the poses of its survivors
@@ -528,7 +537,7 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
     {
         const double* gk = bt.knots + (size_t)f * NX;
         const double* gc = bt.coef + (size_t)f * 8 * NX;
-        // [0]: counter of the item list ([1]: unused); [2]: slices whose lon profiles need the point-by-point scan; [3]: ticket; [4]: knots closer than a
+        // [0]: counter of the item list; [1]: kCut instances: the ends of d_samples, packed (see the cost sums); [2]: slices whose lon profiles need the point-by-point scan; [3]: ticket; [4]: knots closer than a
         // bucket (the segment hint needs its loops); [5], [6]: fp32 bit patterns of the spline's speed bound and of the largest lateral offset
         if (tid < 8) s_cnt[tid] = 0;
 #if defined(FP_PHASE_STAMPS)
@@ -590,6 +599,7 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
             spline_frame(SplineLds{bt.knots + (size_t)fg * bt.NX, bt.coef + (size_t)fg * 8 * bt.NX, nx, bt.NX}, seg, dxs, px, py, tx, ty);
         }
     };
+    // [/section STAGE]
     if (kEgoEarly && tid == 8) { s_k[5] = s0; s_k[6] = s_d0; s_k[7] = s_dd0; s_k[8] = d0; s_k[9] = d_d0; s_k[10] = d_dd0; s_k[11] = d_dd0 * 0.5; }
     __syncthreads();
     FP_STAMP(0);
@@ -600,12 +610,19 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
     auto pD0 = [&]() -> double { if constexpr (kEgoEarly) return s_k[8]; else return d0; };
     auto pDd0 = [&]() -> double { if constexpr (kEgoEarly) return s_k[9]; else return d_d0; };
     auto pDdd0 = [&]() -> double { if constexpr (kEgoEarly) return s_k[10]; else return d_dd0; };
+    // [section LUT]
     // Arclength buckets -> segment hint: lut[b] = bisect_right(knots, k0 + b*width) - 1, 2*nx buckets.  A point then
     // needs one table read plus a short walk instead of a log2(nx) search (knots may be non-uniform: the walk fixes it).
     const int n_buckets = 2 * nx;
     const double knot0 = s_knots[0], knot_last = s_knots[nx - 1];
-    const double bucket_w = (knot_last - knot0) / (double)n_buckets;
-    const double inv_bucket_w = bucket_w > 0.0 ? 1.0 / bucket_w : 0.0;
+    // The bucket width and its reciprocal are two fp64 divisions.  They are read by the wavefronts that fill the table, by those that
+    // check the knot spacing below (fewer: nx - 1 segments against 2 nx + 1 buckets) and by thread 0 (s_k[1]): in the kCut instances
+    // the others branch around them on a scalar test.
+    double bucket_w = 0.0, inv_bucket_w = 0.0;
+    if (!kCut || wave_s * kWave <= n_buckets) {
+        bucket_w = (knot_last - knot0) / (double)n_buckets;
+        inv_bucket_w = bucket_w > 0.0 ? 1.0 / bucket_w : 0.0;
+    }
     for (int bkt = tid; bkt <= n_buckets; bkt += kThreads) {
         const double sb = knot0 + (double)bkt * bucket_w;
         int lo = 0, hi = nx;
@@ -617,6 +634,8 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
         seg = seg < 0 ? 0 : (seg > nx - 2 ? nx - 2 : seg);
         s_lut[bkt] = (unsigned short)seg;
     }
+    // [/section LUT]
+    // [section VBOUND]
 #if defined(FP_ABL_NO_VMAX)
     if (tid == 0) s_cnt[4] = 1;  // (the knot spacing is checked in the loop below)
     if (false) {
@@ -662,6 +681,7 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
             if (lane == 0) atomicMax((unsigned int*)&s_cnt[5], bits);
         }
     }
+    // [/section VBOUND]
     int horizon_cap = 0;  // final_time_step - time_step_now (:173-174)
     int rows = 0;         // obstacle rows the collision horizon can touch: rows of the table below final_time_step
     if (n_obs > 0) {
@@ -679,8 +699,12 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
     const int pose_limit = rows * stride < horizon_cap ? rows * stride : horizon_cap;  // poses k < pose_limit (and k < M)
     int hp = pose_limit > 0 ? pose_limit + 1 : 0;
     if (hp > hp_max) hp = hp_max;
-    const double veh_hl = 0.5 * p.veh_l, veh_hw = 0.5 * p.veh_w;
-    const double r_ego = sqrt(fma(veh_hl, veh_hl, veh_hw * veh_hw));
+    // (thread 0 leaves them in s_k below: in the kCut instances the other wavefronts branch around the square root)
+    double veh_hl = 0.0, veh_hw = 0.0, r_ego = 0.0;
+    if (!kCut || wave_s == 0) {
+        veh_hl = 0.5 * p.veh_l; veh_hw = 0.5 * p.veh_w;
+        r_ego = sqrt(fma(veh_hl, veh_hl, veh_hw * veh_hw));
+    }
     // (no barrier: phase A0 below needs only what the staging barrier made visible - the LUT / speed bound above and the solves below
     // are independent and share one barrier interval; the solves go to the LAST threads, the LUT to the first)
     FP_STAMP(1);
@@ -699,6 +723,7 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
     //     sum_i p(t_i)^2 = sum_k c_k S_k with c = p (*) p (coefficient convolution) - no per-point work and no reductions.
     //     Conditioning is benign on t in [0, 10] (terms ~1e2..1e4 against sums ~1e1..1e3: ~1e-12 absolute), far inside the
     //     1e-6 cost bar, and the expressions are even in the lateral boundary data, so mirrored candidates still tie bit-exactly.
+    // [section SOLVE]
     for (int e = kThreads - 1 - tid; e < n_it * nv; e += kThreads) {
         const int eq = div_by<NV, NT * NV>(e, 1.0f / (float)nv);
         const int it = it_lo + eq, iv = e - mul24(eq, nv);
@@ -739,6 +764,8 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
             if (!proven) atomicOr((unsigned int*)&s_cnt[2], 1u << ((it - it_lo) & 31));
         }
     }
+    // [/section SOLVE]
+    // [section DALL]
     // bound of |d(t)| over ALL slices and lateral samples (the once-per-ego group test needs it), by the wavefronts the solves above
     // leave idle.  In the Hermite form of the quintic with a resting end state,
     //   d(t) = d_end + (d0 - d_end) h0 + d_d0 T h1 + d_dd0 T^2 h2  (tau = t / T),  h0 = 1 - 10 tau^3 + 15 tau^4 - 6 tau^5 in [0, 1],
@@ -770,12 +797,15 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
             if (lane == 0 && bits) atomicMax((unsigned int*)&s_cnt[6], bits);
         }
     }
+    // [/section DALL]
     if (tid == 0) { s_k[0] = knot0; s_k[1] = inv_bucket_w; s_k[2] = veh_hl; s_k[3] = veh_hw; s_k[4] = r_ego; }
     if (kEgoLds && !kEgoEarly && tid == 1) { s_k[5] = s0; s_k[6] = s_d0; s_k[7] = s_dd0; s_k[8] = d0; s_k[9] = d_d0; s_k[10] = d_dd0; s_k[11] = d_dd0 * 0.5; }
+    // [section POWS]
     {   // power sums of every slice (they need nothing but the time samples): a few threads of the middle
         const int i = tid - kThreads / 2;
         if (i >= 0 && i < n_it) power_sums_closed(arange_len(s_ts[it_lo + i], tick), tick, s_pows + (it_lo + i) * 11);
     }
+    // [/section POWS]
     __syncthreads();
     FP_STAMP(2);
     auto eS0 = [&]() -> double { if constexpr (kEgoLds) return s_k[5]; else return s0; };
@@ -785,6 +815,7 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
     auto eDd0 = [&]() -> double { if constexpr (kEgoLds) return s_k[9]; else return d_d0; };
     auto eDdd0 = [&]() -> double { if constexpr (kEgoLds) return s_k[10]; else return d_dd0; };
     auto eDdd0Half = [&]() -> double { if constexpr (kEgoLds) return s_k[11]; else return d_dd0 * 0.5; };  // (the walk's N: the product, ready)
+    // [section RANGES]
     if (n_obs > 0 && pose_limit > 0) {
         // ---- arclength range of every checked pose row over the lon profiles of ALL slices of this workgroup: lane = (row, slice),
         // loop over the end-speed samples, then LDS atomic min / max on order-preserving fp32 bit patterns (relative to the first knot).
@@ -809,6 +840,7 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
             else if (lo <= hi) { atomicMin(bx + 0, f32_ordered((float)lo)); atomicMax(bx + 1, f32_ordered((float)hi)); }
         }
     }
+    // [/section RANGES]
     // [section MASKS]
 #if defined(FP_ABL_NO_SCAN)  // timing ablation: no point-by-point mask scan (results are wrong)
     const uint32_t scan_mask = 0u;
@@ -834,36 +866,84 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
         }
     }
     // [/section MASKS]
-    for (int e0 = (kWaves - 1 - wave) * kWave; e0 < n_it * (nv + nd); e0 += kThreads) {  // (the last wavefronts: the ranges above keep the first busy)  // (whole wavefronts: the row maxima below are wave reductions)
-        const int e = e0 + lane;
-        const bool live = e < n_it * (nv + nd);
-        const int eq = live ? div_by<NV + ND, NT * (NV + ND)>(e, 1.0f / (float)(nv + nd)) : 0;
-        const int it = it_lo + eq, sub = live ? e - mul24(eq, nv + nd) : 0;
-        const double T = s_ts[it];
-        const double* S = s_pows + it * 11;
-        if (!live) {
-        } else if (sub < nv) {
-            const Quartic q{eS0(), eSd0(), eSdd0() * 0.5, s_qlon[2 * (mul24(it, nv) + sub)], s_qlon[2 * (mul24(it, nv) + sub) + 1]};
-            double lon[3];
-            lon_cost_sums(q, target_speed, S, lon);
-            double* o = s_lon_sum + 3 * (mul24(it, nv) + sub);
-            o[0] = lon[0]; o[1] = lon[1]; o[2] = lon[2];
-        } else {
-            const int id = sub - nv;
-            const Quintic q = quintic_bvp(eD0(), eDd0(), eDdd0(), s_ds[id], 0.0, 0.0, T);
-            double lat[3];
-            lat_cost_sums(q, S, lat);
-            double* o = s_lat_sum + 3 * (mul24(id, nt) + it);
-            o[0] = lat[0]; o[1] = lat[1]; o[2] = lat[2];
+    // [section SUMS]
+    if constexpr (kCut) {
+        // kCut instances: the lon profiles go to the last wavefront and the lat profiles to the one before it, each entered on a scalar
+        // test - dealt nv + nd lanes per slice as in the loop below, both wavefronts execute both branches.  The lat lane also keeps the
+        // coefficients of its boundary-value solve for the fan bounds and the walk (QLAT below solves every one a second time), and the
+        // wavefront before those two finds the ends of d_samples ONCE (s_cnt[1] = id_lo | id_hi << 8 | NaN << 16; nd <= 64) instead of
+        // all eight in front of the fan bounds.  Every value is the expression it was; only the lane that evaluates it changed.
+        for (int e0 = (kWaves - 1 - wave_s) * kWave; e0 < n_it * nv; e0 += kThreads) {
+            const int e = e0 + lane;
+            if (e < n_it * nv) {
+                const int eq = div_by<NV, NT * NV>(e, 0.0f);
+                const int it = it_lo + eq, iv = e - mul24(eq, nv);
+                const Quartic q{eS0(), eSd0(), eSdd0() * 0.5, s_qlon[2 * (mul24(it, nv) + iv)], s_qlon[2 * (mul24(it, nv) + iv) + 1]};
+                double lon[3];
+                lon_cost_sums(q, target_speed, s_pows + it * 11, lon);
+                double* o = s_lon_sum + 3 * (mul24(it, nv) + iv);
+                o[0] = lon[0]; o[1] = lon[1]; o[2] = lon[2];
+            }
+        }
+        for (int e0 = ((kWaves - 2 - wave_s) & (kWaves - 1)) * kWave; e0 < n_it * nd; e0 += kThreads) {
+            const int e = e0 + lane;
+            if (e < n_it * nd) {
+                const int eq = div_by<ND, NT * ND>(e, 0.0f);
+                const int it = it_lo + eq, id = e - mul24(eq, nd);
+                const Quintic q = quintic_bvp(eD0(), eDd0(), eDdd0(), s_ds[id], 0.0, 0.0, s_ts[it]);
+                double lat[3];
+                lat_cost_sums(q, s_pows + it * 11, lat);
+                double* o = s_lat_sum + 3 * (mul24(id, nt) + it);
+                o[0] = lat[0]; o[1] = lat[1]; o[2] = lat[2];
+                double* oq = s_qlat + 3 * (mul24(it, nd) + id);
+                oq[0] = q.a3; oq[1] = q.a4; oq[2] = q.a5;
+            }
+        }
+        if (wave_s == kWaves - 3) {
+            int id_lo = 0, id_hi = 0;  // (the loops of the run-time-shape instances' fan bounds)
+            for (int id = 1; id < nd; ++id) {
+                id_lo = s_ds[id] < s_ds[id_lo] ? id : id_lo;
+                id_hi = s_ds[id] > s_ds[id_hi] ? id : id_hi;
+            }
+            bool d_nan = false;
+            for (int id = 0; id < nd; ++id) d_nan = d_nan || !(s_ds[id] == s_ds[id]);
+            if (lane == 0) s_cnt[1] = id_lo | (id_hi << 8) | ((int)d_nan << 16);
+        }
+    } else {
+        for (int e0 = (kWaves - 1 - wave) * kWave; e0 < n_it * (nv + nd); e0 += kThreads) {  // (the last wavefronts: the ranges above keep the first busy)  // (whole wavefronts: the row maxima below are wave reductions)
+            const int e = e0 + lane;
+            const bool live = e < n_it * (nv + nd);
+            const int eq = live ? div_by<NV + ND, NT * (NV + ND)>(e, 1.0f / (float)(nv + nd)) : 0;
+            const int it = it_lo + eq, sub = live ? e - mul24(eq, nv + nd) : 0;
+            const double T = s_ts[it];
+            const double* S = s_pows + it * 11;
+            if (!live) {
+            } else if (sub < nv) {
+                const Quartic q{eS0(), eSd0(), eSdd0() * 0.5, s_qlon[2 * (mul24(it, nv) + sub)], s_qlon[2 * (mul24(it, nv) + sub) + 1]};
+                double lon[3];
+                lon_cost_sums(q, target_speed, S, lon);
+                double* o = s_lon_sum + 3 * (mul24(it, nv) + sub);
+                o[0] = lon[0]; o[1] = lon[1]; o[2] = lon[2];
+            } else {
+                const int id = sub - nv;
+                const Quintic q = quintic_bvp(eD0(), eDd0(), eDdd0(), s_ds[id], 0.0, 0.0, T);
+                double lat[3];
+                lat_cost_sums(q, S, lat);
+                double* o = s_lat_sum + 3 * (mul24(id, nt) + it);
+                o[0] = lat[0]; o[1] = lat[1]; o[2] = lat[2];
+            }
         }
     }
+    // [/section SUMS]
+    // [section QLAT]
     // lat polynomial coefficients of every slice of this workgroup, [slice][lateral sample] (absolute slice index): a boundary-value
     // solve costs two divisions - nd threads per slice (the last ones) instead of once per trajectory point
     // (A plain loop, in a lambda that is called on the spot: written without the lambda, the same statements come out of the compiler
     // with other register assignments and SGPR spills (38 600 lines of the 25 instances' assembly differ; with it, none) - and the
     // instances are to stay exactly as validated.)
     const float inv_nd = 1.0f / (float)nd;
-    [&] {
+    // (kCut instances: written by the lat lanes of the sums above)
+    if constexpr (!kCut) [&] {
         for (int e = kThreads - 1 - tid; e < mul24(n_it, nd); e += kThreads) {
             const int itl = div_small(e, inv_nd), id = e - mul24(itl, nd);
             const Quintic q = quintic_bvp(eD0(), eDd0(), eDdd0(), s_ds[id], 0.0, 0.0, s_ts[it_lo + itl]);
@@ -871,8 +951,10 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
             o[0] = q.a3; o[1] = q.a4; o[2] = q.a5;
         }
     }();
+    // [/section QLAT]
     __syncthreads();
     FP_STAMP(3);
+    // [section FAN]
     // ---- lateral fan bounds of EVERY slice: lane = (slice, point inside the collision horizon): fan half-width max|d| and
     // largest lateral step max|d(i + 1) - d(i)| over the lateral samples, float_above: never below the fp64 value.  For a fixed
     // horizon the quintic is AFFINE in its end offset (Hermite form, see the lateral bound above): d(t; d_end) = b(t) + d_end g(t),
@@ -880,13 +962,18 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
     // sample - two profiles are evaluated instead of nd (the rounding of the other samples' own evaluations, ~1e-16 relative,
     // is far inside float_above's 2^-22).  (The first threads: the circles below take the last ones.)
     if (n_obs > 0 && hp > 0) {
-        int id_lo = 0, id_hi = 0;  // (any order of d_samples: the reference passes np.linspace, the ABI does not require it)
-        for (int id = 1; id < nd; ++id) {
-            id_lo = s_ds[id] < s_ds[id_lo] ? id : id_lo;
-            id_hi = s_ds[id] > s_ds[id_hi] ? id : id_hi;
-        }
+        int id_lo = 0, id_hi = 0;
         bool d_nan = false;
-        for (int id = 0; id < nd; ++id) d_nan = d_nan || !(s_ds[id] == s_ds[id]);
+        if constexpr (kCut) {  // (found once per ego, see the sums above)
+            const int ends = __builtin_amdgcn_readfirstlane(s_cnt[1]);
+            id_lo = ends & 0xFF; id_hi = (ends >> 8) & 0xFF; d_nan = (ends >> 16) != 0;
+        } else {  // (any order of d_samples: the reference passes np.linspace, the ABI does not require it)
+            for (int id = 1; id < nd; ++id) {
+                id_lo = s_ds[id] < s_ds[id_lo] ? id : id_lo;
+                id_hi = s_ds[id] > s_ds[id_hi] ? id : id_hi;
+            }
+            for (int id = 0; id < nd; ++id) d_nan = d_nan || !(s_ds[id] == s_ds[id]);
+        }
         const float inv_hp = 1.0f / (float)hp;
         for (int e = tid; e < mul24(n_it, hp); e += kThreads) {
             const int itl = div_small(e, inv_hp), i = e - mul24(itl, hp);
@@ -911,6 +998,8 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
             s_fan_dd[mul24(it, hp_max) + i] = i + 1 < np_i ? FanType<kSlim>::above(ddm) : (fan_t)0.0f;
         }
     }
+    // [/section FAN]
+    // [section CIRCLES]
     // ---- ranges -> circles: every reference point of the row lies within  v_max * (half the range)  of the line's point at
     // the middle of the range (v_max >= |P'(s)| everywhere); + ego reach + the largest lateral offset.  One test per
     // (row, obstacle) item then prunes the item for every profile of every slice at once.
@@ -942,6 +1031,7 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
         s_grp[r].hw = cy;
         s_grp[r].r = rad;
     }
+    // [/section CIRCLES]
     __syncthreads();  // the final assembly reads the sums (with no obstacles there is no other barrier in between)
     FP_STAMP(4);
 
@@ -971,44 +1061,97 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
         const int n_items = rows * n_obs;
 #endif
         const float inv_nobs = 1.0f / (float)n_obs, inv_nvf = 1.0f / (float)nv, inv_ndf = 1.0f / (float)nd;
+        // items of a chunk of the redo: at most kItemCap, so that its survivors always fit; kCut instances: whole rows (see G)
+        constexpr int kChunk = kCut ? kItemCap / (NOBS > 0 ? NOBS : 1) * NOBS : kItemCap;
+        static_assert(kChunk > 0 && (!kCut || NOBS <= kThreads), "a chunk of the redo and a pass of the workgroup hold at least one row");
         int chunk = n_items;
         for (int i0 = 0; i0 < n_items;) {
             // ---- G (once per ego and item chunk): the poses come straight from the scene table (L2 for all but the first ego of a
             // scene), kPoseFlight reads in flight per lane.  x = NaN / valid = 0: no state at this step (state_at_time -> None).
             // A survivor's pose goes to the list with its orientation still an angle.
+    // [section G]
             const int i1 = i0 + chunk < n_items ? i0 + chunk : n_items;
-            for (int b0 = i0; b0 < i1; b0 += kPoseFlight * kThreads) {
-                double4 ps[kPoseFlight];
-                fetch_poses(b0, ps);
+            if constexpr (kCut) {
+                // kCut instances: a lane keeps ONE obstacle column and steps through the rows - a pass of the workgroup is kRowsPass whole
+                // rows, a lane's items of one trip are kRowsPass rows apart.  One division per lane and chunk (item = pass * kThreads +
+                // tid cost two per item, and a third for a survivor's code).  Pass u still covers the band of rows it covered -
+                // [u kRowsPass, (u + 1) kRowsPass) against items [u kThreads, (u + 1) kThreads) - so the list stays in time order pass by
+                // pass, which is what ends a blocked profile's walk early.  A chunk of the redo is whole rows (kChunk).
+                // A lane without an item (the kThreads % NOBS last threads hold no column; rows behind the chunk) reads the chunk's LAST row
+                // instead - a valid address, its neighbours' cache lines - and its pose is never looked at: no zeroed registers, no
+                // branch around the reads.
+                // (The opaque copy of tid keeps the lane's row and column INSIDE the chunk loop: hoisted out of it they would live
+                // through the walk, in an instance with one VGPR to spare.)
+                constexpr int kRowsPass = kThreads / NOBS;
+                int tl = tid;
+                asm volatile("" : "+v"(tl));
+                const int r0 = div_by<NOBS, kThreads>(tl, 0.0f), j = tl - mul24(r0, NOBS);  // (j < NOBS for every thread)
+                const int r_end = div_by<NOBS, ROWS * NOBS>(i1, 0.0f);  // (uniform; i0 and i1 are multiples of NOBS; 0 <= i0 < i1: r_end >= 1)
+                for (int rb = div_by<NOBS, ROWS * NOBS>(i0, 0.0f); rb < r_end; rb += kPoseFlight * kRowsPass) {
+                    double4 ps[kPoseFlight];
 #pragma unroll
-                for (int u = 0; u < kPoseFlight; ++u) {
-                    const int e = b0 + u * kThreads + tid;
-                    bool keep = false;
-                    if (e < i1) {
-                        const int r = div_by<NOBS, ROWS * NOBS>(e, inv_nobs), j = e - mul24(r, n_obs);
-                        const int k = mul24(r, stride);
-                        const ObsDim g = s_grp[r];
-                        const double dx = ps[u].x - g.hl, dy = ps[u].y - g.hw, R = g.r + s_dim.rad[j];
-                        keep = k < pose_limit && ps[u].w != 0.0 && (ps[u].x == ps[u].x) && !(g.r < 0.0) && !(fma(dx, dx, dy * dy) > R * R);
+                    for (int u = 0; u < kPoseFlight; ++u) {
+                        const int r = rb + u * kRowsPass + r0, r_ld = r < r_end ? r : r_end - 1;  // (r_end <= rows <= rows_stage: inside the table)
+                        ps[u] = *(const double4*)(gp + ((size_t)(mul24(r_ld, STRIDE) + t_now) * NOBS + j) * 4);
                     }
-                    const unsigned long long m = __ballot(keep);
-                    if (m) {
-                        const int first = __ffsll((long long)m) - 1;
-                        int base = 0;
-                        if (lane == first) base = atomicAdd(&s_cnt[0], __popcll(m));
-                        const int pos = __builtin_amdgcn_readlane(base, first) - item_base + __popcll(m & ((1ull << lane) - 1ull));
-                        if (keep && pos < kItemCap) {
-                            if constexpr (kItemShift > 0) {  // (taken apart again here: a survivor is rare, a register held across the ballot is not free)
-                                const int r_e = div_by<NOBS, ROWS * NOBS>(e, inv_nobs);
-                                s_items[pos] = (unsigned short)((r_e << kItemShift) | (e - mul24(r_e, n_obs)));
-                            } else {
-                                s_items[pos] = (unsigned short)e;
+#pragma unroll
+                    for (int u = 0; u < kPoseFlight; ++u) {
+                        const int r = rb + u * kRowsPass + r0;
+                        bool keep = false;
+                        if (r0 < kRowsPass && r < r_end) {
+                            const int k = mul24(r, STRIDE);
+                            const ObsDim g = s_grp[r];
+                            const double dx = ps[u].x - g.hl, dy = ps[u].y - g.hw, R = g.r + s_dim.rad[j];
+                            keep = k < pose_limit && ps[u].w != 0.0 && (ps[u].x == ps[u].x) && !(g.r < 0.0) && !(fma(dx, dx, dy * dy) > R * R);
+                        }
+                        const unsigned long long m = __ballot(keep);
+                        if (m) {
+                            const int first = __ffsll((long long)m) - 1;
+                            int base = 0;
+                            if (lane == first) base = atomicAdd(&s_cnt[0], __popcll(m));
+                            const int pos = __builtin_amdgcn_readlane(base, first) - item_base + __popcll(m & ((1ull << lane) - 1ull));
+                            if (keep && pos < kItemCap) {
+                                s_items[pos] = (unsigned short)(kItemShift > 0 ? (r << kItemShift) | j : mul24(r, NOBS) + j);
+                                s_spose.set(pos, ps[u].x, ps[u].y, ps[u].z, 0.0);
                             }
-                            s_spose.set(pos, ps[u].x, ps[u].y, ps[u].z, 0.0);
+                        }
+                    }
+                }
+            } else {
+                for (int b0 = i0; b0 < i1; b0 += kPoseFlight * kThreads) {
+                    double4 ps[kPoseFlight];
+                    fetch_poses(b0, ps);
+#pragma unroll
+                    for (int u = 0; u < kPoseFlight; ++u) {
+                        const int e = b0 + u * kThreads + tid;
+                        bool keep = false;
+                        if (e < i1) {
+                            const int r = div_by<NOBS, ROWS * NOBS>(e, inv_nobs), j = e - mul24(r, n_obs);
+                            const int k = mul24(r, stride);
+                            const ObsDim g = s_grp[r];
+                            const double dx = ps[u].x - g.hl, dy = ps[u].y - g.hw, R = g.r + s_dim.rad[j];
+                            keep = k < pose_limit && ps[u].w != 0.0 && (ps[u].x == ps[u].x) && !(g.r < 0.0) && !(fma(dx, dx, dy * dy) > R * R);
+                        }
+                        const unsigned long long m = __ballot(keep);
+                        if (m) {
+                            const int first = __ffsll((long long)m) - 1;
+                            int base = 0;
+                            if (lane == first) base = atomicAdd(&s_cnt[0], __popcll(m));
+                            const int pos = __builtin_amdgcn_readlane(base, first) - item_base + __popcll(m & ((1ull << lane) - 1ull));
+                            if (keep && pos < kItemCap) {
+                                if constexpr (kItemShift > 0) {  // (taken apart again here: a survivor is rare, a register held across the ballot is not free)
+                                    const int r_e = div_by<NOBS, ROWS * NOBS>(e, inv_nobs);
+                                    s_items[pos] = (unsigned short)((r_e << kItemShift) | (e - mul24(r_e, n_obs)));
+                                } else {
+                                    s_items[pos] = (unsigned short)e;
+                                }
+                                s_spose.set(pos, ps[u].x, ps[u].y, ps[u].z, 0.0);
+                            }
                         }
                     }
                 }
             }
+    // [/section G]
             __syncthreads();
     FP_STAMP(7);
             const int item_end = s_cnt[0];
@@ -1016,16 +1159,18 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
             item_base = item_end;
             if (tid == 0) FP_COUNT(0, n_surv);
             if (n_surv > kItemCap) {  // block-uniform: does not fit, redo [i0, ...) in chunks whose survivors always fit
-                chunk = kItemCap;
+                chunk = kChunk;
                 __syncthreads();  // every thread has read s_cnt[0] before the redone pass adds to it again
                 continue;
             }
+    // [section SINCOS]
             // the survivors' orientations -> (cos, sin), with shapely's snap (frenet_device.h); every item belongs to one chunk
             for (int si = tid; si < n_surv; si += kThreads) {
                 double sn, cs;
                 sincos_snapped(s_spose.hi[si].x, sn, cs);
                 s_spose.hi[si] = make_double2(cs, sn);
             }
+    // [/section SINCOS]
             // (the walk's barrier below orders these writes before stage B reads them)
             // No survivor (block-uniform: empty surroundings, obstacles out of reach): nothing can collide, the walk is skipped.
             // (Skipping only the rows without a survivor was tried: a lane that skips its point saves nothing while its wavefront's
@@ -1347,10 +1492,13 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
         __atomic_signal_fence(__ATOMIC_SEQ_CST);
     }
     // [/section ASM]
+    // [section ARGMIN]
     mine = wave_best(mine);
     if (lane == 0) s_best[wave] = mine;
     __syncthreads();
     FP_STAMP(9);
+    // [/section ARGMIN]
+    // [section RESULTS]
     if (nsplit > 1) {
         // Latency mode: this workgroup holds the argmin of its slices.  The LAST workgroup of the ego to arrive (ticket counter;
         // the partial argmins travel as device-coherent atomic stores / loads) merges the partial argmins in part order - the result does not depend on
@@ -1437,6 +1585,7 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
     }
     // 10 ns ticks: feeds the next launches' order (a tail ego leaves twice its last part's time: about what it would take whole)
     if (tid == 0 && la.dur && (nsplit == 1 || in_tail)) la.dur[b] = (int)(wall_clock64() - t_begin) * nsplit;
+    // [/section RESULTS]
     if (nsplit > 1) FP_STAMP_LAST(10); else FP_STAMP(10);
 #if defined(FP_PHASE_STAMPS)  // column 15: the workgroup's absolute start (10 ns ticks, low 40 bits) - the launch's occupancy over time
     if (threadIdx.x == 0 && ka.r.best_traj && (perm || blockIdx.x % nsplit == 0)) ka.r.best_traj[((size_t)b * FP_ARR_COUNT + 15) * (ka.r.traj_stride > 0 ? ka.r.traj_stride : FP_DEFAULT_STRIDE) + 112 + 15] = (double)(t_begin & 0xFFFFFFFFFFll);

@@ -14,6 +14,7 @@ import argparse, csv, os, re, shutil, subprocess, sys, tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "fiss_plus_planner_amd", "csrc", "frenet_lattice_fused.hip")
+REPEATABLE = ("MASKS", "FRAMES", "LUTWALK", "PREP", "B", "N", "NLAST", "ASM")
 
 
 def patched(text, name, rep):
@@ -43,7 +44,9 @@ def main():
     ap.add_argument("--config", type=int, default=3)
     args = ap.parse_args()
     original = open(SRC).read()
-    names = re.findall(r"// \[section (\w+)\]", original)
+    # (the walk's sections and the assembly can run again with the same result; the prologue's marks - STAGE .. G, ARGMIN, RESULTS - are
+    # there for tools/isa_lines.py and tools/nonwalk_census.py: G appends to a list, others declare what later code reads)
+    names = [n for n in dict.fromkeys(re.findall(r"// \[section (\w+)\]", original)) if n in REPEATABLE]
     try:
         base = None
         for name in [None] + names:
