@@ -25,6 +25,7 @@
 
 #include "frenet_kernels.h"
 #include "frenet_project.h"
+#include "frenet_rule_calls.h"
 #include "frenet_stage_plan.h"
 
 // Toolchain pin.  The kernels were validated on ROCm 7.2.0's clang 22 (AMD clang 22.0.0git roc-7.2.0): no kernel may spill a VGPR
@@ -486,6 +487,36 @@ int check_time_gap(const fp_time_gap* gap)
     if (gap->first < 1) return fail(FP_EINVAL, "fp_gap_mask: first=%d must be >= 1", gap->first);
     return FP_OK;
 }
+// A rule set (fp_rules_eval, fp_plan_fiss_rules: `fn` names the entry point): some rule is on, and every rule that is on passes its checks
+int check_rule_set(const char* fn, const fp_rule_set* rules, const fp_batch* batch)
+{
+    if (!rules->envelope && !rules->gates && !rules->boundary && !rules->gaps) return fail(FP_EINVAL, "%s: every rule of the set is NULL", fn);
+    if (rules->envelope) FP_TRY(check_speed_profile(rules->envelope, batch));
+    if (rules->gates) FP_TRY(check_gates(rules->gates));
+    if (rules->boundary) FP_TRY(check_corridor(rules->boundary));
+    return rules->gaps ? check_time_gap(rules->gaps) : FP_OK;
+}
+int check_rule_set_host(const fp_rule_set* rules, const fp_batch* batch)
+{
+    if (rules->envelope) FP_TRY(check_speed_profile_host(rules->envelope, batch));
+    return rules->boundary ? check_corridor_host(rules->boundary, batch) : FP_OK;
+}
+
+// The loop state of a closed-loop call.  need_goal: the call decides arrivals (fp_loop_record only copies the states).
+int check_loop_io(const fp_loop_io* io, bool need_goal)
+{
+    if (!io || !io->ego || !io->t_now || !io->done || !io->cycles || (need_goal && !io->goal_xy)) return fail(FP_EINVAL, "fp_loop_io has a NULL mandatory array");
+    if (need_goal && io->goal_poly && (!io->goal_nv || io->goal_max_vertices < 3)) return fail(FP_EINVAL, "fp_loop_io.goal_poly needs goal_nv and goal_max_vertices >= 3");
+    return FP_OK;
+}
+
+// The batch as the kernels of an FP_MEM_DEVICE call see it: a batch without scenes or obstacle columns has no obstacles
+fp_batch device_batch(const fp_batch* batch)
+{
+    fp_batch b = *batch;
+    if (!(batch->S > 0 && batch->n_obs > 0)) b.n_obs = 0;
+    return b;
+}
 
 // The argument block the table passes behind the dense pass share (fp::TablePassArgs), holding the caller's arrays as they were given:
 // all an FP_MEM_DEVICE call needs
@@ -893,6 +924,32 @@ int clearance_step(fp_ctx* ctx, const fp::KernelArgs& ka, const int32_t* launch_
 {
     LAUNCH_TRY(fp::launch_clearance_rescore(ka, launch_order, stream), "clearance rescoring kernel");
     ++ctx->clearance_launches;
+    return FP_OK;
+}
+
+// The launch of each rule's table pass and its counter: the pass's entry point (both memory modes) and plan_fiss_impl go through here
+int envelope_pass(fp_ctx* ctx, const fp::EnvelopeArgs& a, hipStream_t stream)
+{
+    LAUNCH_TRY(fp::launch_speed_envelope(a, stream), "speed-envelope kernel");
+    ++ctx->envelope_launches;
+    return FP_OK;
+}
+int gate_pass(fp_ctx* ctx, const fp::GateArgs& a, hipStream_t stream)
+{
+    LAUNCH_TRY(fp::launch_gate_mask(a, stream), "gate kernel");
+    ++ctx->gate_launches;
+    return FP_OK;
+}
+int boundary_pass(fp_ctx* ctx, const fp::BoundaryArgs& a, hipStream_t stream)
+{
+    LAUNCH_TRY(fp::launch_boundary_mask(a, stream), "road-boundary kernel");
+    ++ctx->boundary_launches;
+    return FP_OK;
+}
+int gap_pass(fp_ctx* ctx, const fp::KernelArgs& ka, const fp::GapArgs& g, hipStream_t stream)
+{
+    LAUNCH_TRY(fp::launch_gap_mask(ka, g, stream), "time-gap kernel");
+    ++ctx->gap_launches;
     return FP_OK;
 }
 
@@ -1520,8 +1577,7 @@ static int plan_dense_impl(fp_ctx* ctx, const fp_params* params, const fp_batch*
     StageList sl;
     fp::InlineIn inl;
     if (mem == FP_MEM_DEVICE) {
-        ka.b = *batch;
-        if (!(batch->S > 0 && batch->n_obs > 0)) ka.b.n_obs = 0;
+        ka.b = device_batch(batch);
         ka.r = *result;
     } else {  // host buffers: checked, staged into device buffers, fetched below
         FP_TRY(check_batch_host(params, batch));
@@ -1665,13 +1721,8 @@ int fp_boundary_mask(fp_ctx* ctx, const fp_params* params, const fp_batch* batch
     HIP_TRY(hipSetDevice(ctx->device));
     fp::BoundaryArgs a;
     table_pass_args(&a, params, batch, cost_tbl, flag_tbl, best_idx, best_cost, n_masked);
-    a.veh_l = params->veh_l; a.veh_w = params->veh_w; a.margin = corridor->margin;
-    a.d_samples = batch->d_samples; a.left = corridor->left; a.right = corridor->right;
-    if (mem == FP_MEM_DEVICE) {
-        LAUNCH_TRY(fp::launch_boundary_mask(a, (hipStream_t)stream), "road-boundary kernel");
-        ++ctx->boundary_launches;
-        return FP_OK;
-    }
+    fp::boundary_args(&a, fp::rule_args(fp_rule_set{nullptr, nullptr, corridor, nullptr}), *params, batch->d_samples);
+    if (mem == FP_MEM_DEVICE) return boundary_pass(ctx, a, (hipStream_t)stream);
     FP_TRY(check_frames_host(batch));
     FP_TRY(check_corridor_host(corridor, batch));
     const size_t fn = (size_t)batch->F * batch->NX;
@@ -1683,8 +1734,7 @@ int fp_boundary_mask(fp_ctx* ctx, const fp_params* params, const fp_batch* batch
         l.in(a.right, fn, &a.right);
     });
     FP_TRY(hs.commit(sl));
-    LAUNCH_TRY(fp::launch_boundary_mask(a, ctx->stream), "road-boundary kernel");
-    ++ctx->boundary_launches;
+    FP_TRY(boundary_pass(ctx, a, ctx->stream));
     return hs.fetch_out();
 }
 
@@ -1695,30 +1745,23 @@ int fp_speed_envelope(fp_ctx* ctx, const fp_params* params, const fp_batch* batc
     if (!profile || !profile->v_limit) return check_speed_profile(profile, batch);
     if (!cost_tbl || !flag_tbl || !best_idx || !best_cost) return fail(FP_EINVAL, "fp_speed_envelope: cost_tbl/flag_tbl/best_idx/best_cost must not be NULL");
     FP_TRY(check_speed_profile(profile, batch));
-    const bool lateral = profile->max_lat_accel > 0;
     if (batch->B == 0) return FP_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     fp::EnvelopeArgs a;
     table_pass_args(&a, params, batch, cost_tbl, flag_tbl, best_idx, best_cost, n_limited);
-    a.front = profile->front; a.tol = profile->tol; a.max_lat_accel = profile->max_lat_accel;
-    a.coef = lateral ? batch->coef : nullptr; a.v_limit = profile->v_limit;  // (coef is read by the lateral check alone)
-    if (mem == FP_MEM_DEVICE) {
-        LAUNCH_TRY(fp::launch_speed_envelope(a, (hipStream_t)stream), "speed-envelope kernel");
-        ++ctx->envelope_launches;
-        return FP_OK;
-    }
+    fp::envelope_args(&a, fp::rule_args(fp_rule_set{profile, nullptr, nullptr, nullptr}), batch->coef);
+    if (mem == FP_MEM_DEVICE) return envelope_pass(ctx, a, (hipStream_t)stream);
     FP_TRY(check_frames_host(batch));
     FP_TRY(check_speed_profile_host(profile, batch));
     const size_t fn = (size_t)batch->F * batch->NX;
     HostStage hs(ctx);
     StageList sl;
     table_pass_stage(sl, &a, batch->F, [&](StageList& l) {
-        if (lateral) l.in(a.coef, fn * 8, &a.coef);
+        if (a.coef) l.in(a.coef, fn * 8, &a.coef);  // (set when the lateral bound is on: check_speed_profile has seen batch->coef then)
         l.in(a.v_limit, fn, &a.v_limit);
     });
     FP_TRY(hs.commit(sl));
-    LAUNCH_TRY(fp::launch_speed_envelope(a, ctx->stream), "speed-envelope kernel");
-    ++ctx->envelope_launches;
+    FP_TRY(envelope_pass(ctx, a, ctx->stream));
     return hs.fetch_out();
 }
 
@@ -1733,18 +1776,10 @@ int fp_gate_mask(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, co
     HIP_TRY(hipSetDevice(ctx->device));
     fp::GateArgs a;
     table_pass_args(&a, params, batch, cost_tbl, flag_tbl, best_idx, best_cost, n_gated);
-    a.front = gates->front; a.max_decel = gates->max_decel;
-    a.gate_stride = gates->gate_stride; a.T_gate = gates->T_gate;
-    a.t_now = batch->t_now; a.gate_s = gates->gate_s; a.closed = gates->closed;
-    a.points_cap = big_points(*params) ? params->points_max : FP_FAST_POINTS;
-    if (mem == FP_MEM_DEVICE) {
-        LAUNCH_TRY(fp::launch_gate_mask(a, (hipStream_t)stream), "gate kernel");
-        ++ctx->gate_launches;
-        return FP_OK;
-    }
+    fp::gate_args(&a, fp::rule_args(fp_rule_set{nullptr, gates, nullptr, nullptr}), batch->t_now, fp::gate_points_cap(*params, false, 0));
+    if (mem == FP_MEM_DEVICE) return gate_pass(ctx, a, (hipStream_t)stream);
     FP_TRY(check_frames_host(batch));
-    const int pts = host_points_max(params, batch, nullptr, 0, 0);  // (host calls look at their time samples themselves)
-    a.points_cap = pts > FP_FAST_POINTS ? pts : FP_FAST_POINTS;
+    a.points_cap = fp::gate_points_cap(*params, true, host_points_max(params, batch, nullptr, 0, 0));  // (host calls look at their time samples themselves)
     const size_t F = (size_t)batch->F;
     HostStage hs(ctx);
     StageList sl;
@@ -1754,8 +1789,7 @@ int fp_gate_mask(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, co
         l.in(a.closed, F * a.T_gate, &a.closed);
     });
     FP_TRY(hs.commit(sl));
-    LAUNCH_TRY(fp::launch_gate_mask(a, ctx->stream), "gate kernel");
-    ++ctx->gate_launches;
+    FP_TRY(gate_pass(ctx, a, ctx->stream));
     return hs.fetch_out();
 }
 
@@ -1772,21 +1806,16 @@ int fp_gap_mask(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, con
     fp::KernelArgs ka;
     ka.p = *params;
     ka.r = no_result();
-    fp::GapArgs g;
-    g.lag_follow = gap->lag_follow; g.lag_lead = gap->lag_lead;
-    g.first = gap->first < FP_MAX_POINTS ? gap->first : FP_MAX_POINTS;  // (points are 0 .. FP_MAX_POINTS - 1: anything above is "beyond every pose")
-    if (mem == FP_MEM_DEVICE) {
-        ka.b = *batch;
-        if (!(batch->S > 0 && batch->n_obs > 0)) ka.b.n_obs = 0;
+    const bool host = mem != FP_MEM_DEVICE;  // (a host call has no launch order, and its count is staged)
+    fp::GapArgs g = fp::gap_args(fp::rule_args(fp_rule_set{nullptr, nullptr, nullptr, gap}), host ? nullptr : batch->launch_order, host ? nullptr : n_close);
+    if (!host) {
+        ka.b = device_batch(batch);
         ka.r.cost_tbl = const_cast<double*>(cost_tbl);  // (read only)
         ka.r.flag_tbl = flag_tbl; ka.r.best_idx = best_idx; ka.r.best_cost = best_cost;
-        g.perm = batch->launch_order; g.count = n_close;
-        LAUNCH_TRY(fp::launch_gap_mask(ka, g, (hipStream_t)stream), "time-gap kernel");
-        ++ctx->gap_launches;
-        return FP_OK;
+        return gap_pass(ctx, ka, g, (hipStream_t)stream);
     }
     FP_TRY(check_batch_host(params, batch));
-    ka.p.points_max = host_points_max(params, batch, nullptr, 0, 0);  // (host calls look at their time samples themselves)
+    ka.p.points_max = fp::gap_points_max(*params, true, host_points_max(params, batch, nullptr, 0, 0));  // (host calls look at their time samples themselves)
     HostStage hs(ctx);
     StageList sl;
     StageRegime rg;  // (throughput)
@@ -1797,8 +1826,7 @@ int fp_gap_mask(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, con
     sl.out(best_cost, B, &ka.r.best_cost);
     sl.out(n_close, B, &g.count);
     FP_TRY(hs.commit(sl, rg));
-    LAUNCH_TRY(fp::launch_gap_mask(ka, g, ctx->stream), "time-gap kernel");
-    ++ctx->gap_launches;
+    FP_TRY(gap_pass(ctx, ka, g, ctx->stream));
     return hs.fetch_out();
 }
 
@@ -1808,48 +1836,24 @@ int fp_rules_eval(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, c
     FP_TRY(common_checks(ctx, params, batch, mem, stream));
     if (K < 1) return fail(FP_EINVAL, "fp_rules_eval: K=%d must be >= 1", K);
     if (!rules || !end_states || !flags) return fail(FP_EINVAL, "fp_rules_eval: rules / end_states / flags must not be NULL");
-    if (!rules->envelope && !rules->gates && !rules->boundary && !rules->gaps) return fail(FP_EINVAL, "fp_rules_eval: every rule of the set is NULL");
-    if (rules->envelope) FP_TRY(check_speed_profile(rules->envelope, batch));
-    if (rules->gates) FP_TRY(check_gates(rules->gates));
-    if (rules->boundary) FP_TRY(check_corridor(rules->boundary));
-    if (rules->gaps) FP_TRY(check_time_gap(rules->gaps));
+    FP_TRY(check_rule_set("fp_rules_eval", rules, batch));
     if (batch->B == 0) return FP_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t B = (size_t)batch->B, BK = B * (size_t)K;
     fp::KernelArgs ka;
     ka.p = *params;
     ka.r = no_result();
-    fp::RulesEvalArgs a;
+    fp::RulesEvalArgs a = fp::rule_args(*rules);
     a.K = K;
-    if (const fp_speed_profile* e = rules->envelope) {
-        a.on |= FP_RULE_LIMIT | (e->max_lat_accel > 0 ? FP_RULE_LATERAL : 0u);
-        a.env_front = e->front; a.env_tol = e->tol; a.max_lat_accel = e->max_lat_accel; a.v_limit = e->v_limit;
-    }
-    if (const fp_gates* g = rules->gates) {
-        a.on |= FP_RULE_GATE;
-        a.gate_front = g->front; a.max_decel = g->max_decel; a.gate_stride = g->gate_stride; a.T_gate = g->T_gate;
-        a.gate_s = g->gate_s; a.closed = g->closed;
-    }
-    if (const fp_corridor* c = rules->boundary) {
-        a.on |= FP_RULE_BOUNDARY;
-        a.margin = c->margin; a.left = c->left; a.right = c->right;
-    }
-    if (const fp_time_gap* t = rules->gaps) {
-        a.on |= FP_RULE_GAP;
-        a.lag_follow = t->lag_follow; a.lag_lead = t->lag_lead;
-        a.first = t->first < FP_MAX_POINTS ? t->first : FP_MAX_POINTS;  // (points are 0 .. FP_MAX_POINTS - 1: anything above is "beyond every pose")
-    }
     if (mem == FP_MEM_DEVICE) {
-        ka.b = *batch;
-        if (!(batch->S > 0 && batch->n_obs > 0)) ka.b.n_obs = 0;
+        ka.b = device_batch(batch);
         a.end_states = end_states; a.flags = flags; a.rule_bits = rule_bits; a.counts = counts; a.perm = batch->launch_order;
         LAUNCH_TRY(fp::launch_rules_eval(ka, a, (hipStream_t)stream), "rules kernel");
         ++ctx->rules_eval_launches;
         return FP_OK;
     }
     FP_TRY(check_batch_host(params, batch, /*past_ok=*/true));  // (a negative t_now reads the gates' first state; no obstacle has a state before step 0)
-    if (rules->envelope) FP_TRY(check_speed_profile_host(rules->envelope, batch));
-    if (rules->boundary) FP_TRY(check_corridor_host(rules->boundary, batch));
+    FP_TRY(check_rule_set_host(rules, batch));
     for (size_t i = 0; i < BK; ++i) {
         const double n = end_states[3 * i + 2] / params->tick_t;
         if (n != n || (batch->skip && batch->skip[i / (size_t)K])) continue;  // NaN end state = "no trajectory"
@@ -1857,20 +1861,11 @@ int fp_rules_eval(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, c
             return fail(FP_ELIMIT, "fp_rules_eval: end_states of ego %zu, trajectory %zu: T=%g needs 1..FP_MAX_POINTS points", i / (size_t)K, i % (size_t)K, end_states[3 * i + 2]);
     }
     ka.p.points_max = host_points_max(params, batch, end_states + 2, BK, 3);
-    const size_t fn = (size_t)batch->F * batch->NX, F = (size_t)batch->F;
     HostStage hs(ctx);
     StageList sl;
     StageRegime rg;  // (throughput)
     FP_TRY(stage_batch(ctx, sl, rg, params, batch, &ka.b));
-    if (rules->envelope) sl.in(a.v_limit, fn, &a.v_limit);
-    if (rules->gates) {
-        sl.in(a.gate_s, F * a.gate_stride, &a.gate_s);
-        sl.in(a.closed, F * a.T_gate, &a.closed);
-    }
-    if (rules->boundary) {
-        sl.in(a.left, fn, &a.left);
-        sl.in(a.right, fn, &a.right);
-    }
+    fp::stage_rule_arrays(sl, &a, batch->F, batch->NX);
     sl.in(end_states, BK * 3, &a.end_states);
     sl.in_mut(flags, BK, &a.flags);
     sl.out(rule_bits, BK, &a.rule_bits);
@@ -1899,8 +1894,7 @@ int fp_traj_margins(fp_ctx* ctx, const fp_params* params, const fp_batch* batch,
     fp::MarginArgs m;
     m.K = K;
     if (mem == FP_MEM_DEVICE) {
-        ka.b = *batch;
-        if (!(batch->S > 0 && batch->n_obs > 0)) ka.b.n_obs = 0;
+        ka.b = device_batch(batch);
         m.best_idx = best_idx; m.end_state = end_state; m.perm = batch->launch_order;
         m.min_dist = min_dist; m.min_step = min_step; m.min_obs = min_obs;
         LAUNCH_TRY(fp::launch_traj_margins(ka, m, (hipStream_t)stream), "plan-margin kernel");
@@ -1960,8 +1954,7 @@ int fp_fallback_stop(fp_ctx* ctx, const fp_params* params, const fp_batch* batch
     fp::FallbackArgs a;
     a.n_d = fallback->n_d; a.n_stop = fallback->n_stop; a.max_decel = fallback->max_decel;
     if (mem == FP_MEM_DEVICE) {
-        ka.b = *batch;
-        if (!(batch->S > 0 && batch->n_obs > 0)) ka.b.n_obs = 0;
+        ka.b = device_batch(batch);
         a.d_targets = fallback->d_targets; a.stop_T = fallback->stop_T; a.best_idx = best_idx; a.end_state = end_state;
         a.status = status; a.fb_idx = fb_idx; a.hit_step = hit_step; a.hit_obs = hit_obs; a.hit_speed = hit_speed;
         a.cand = cand; a.counts = counts; a.perm = batch->launch_order;
@@ -2187,37 +2180,16 @@ int plan_fiss_impl(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, 
     sp += rules ? align_up(sizeof(double) * B) : 0;
     int32_t* pass_count = (int32_t*)sp;
     int32_t* rejected_dev = rejected;  // (a host call: the staged copy's address at commit)
-    // the rule set as the rules kernel takes it (fp_rules_eval builds the same block); a host call's arrays get their device addresses at commit
-    fp::RulesEvalArgs ra;
-    if (rules) {
-        if (const fp_speed_profile* e = rules->envelope) {
-            ra.on |= FP_RULE_LIMIT | (e->max_lat_accel > 0 ? FP_RULE_LATERAL : 0u);
-            ra.env_front = e->front; ra.env_tol = e->tol; ra.max_lat_accel = e->max_lat_accel; ra.v_limit = e->v_limit;
-        }
-        if (const fp_gates* g = rules->gates) {
-            ra.on |= FP_RULE_GATE;
-            ra.gate_front = g->front; ra.max_decel = g->max_decel; ra.gate_stride = g->gate_stride; ra.T_gate = g->T_gate;
-            ra.gate_s = g->gate_s; ra.closed = g->closed;
-        }
-        if (const fp_corridor* c = rules->boundary) {
-            ra.on |= FP_RULE_BOUNDARY;
-            ra.margin = c->margin; ra.left = c->left; ra.right = c->right;
-        }
-        if (const fp_time_gap* t = rules->gaps) {
-            ra.on |= FP_RULE_GAP;
-            ra.lag_follow = t->lag_follow; ra.lag_lead = t->lag_lead;
-            ra.first = t->first < FP_MAX_POINTS ? t->first : FP_MAX_POINTS;  // (points are 0 .. FP_MAX_POINTS - 1: anything above is "beyond every pose")
-        }
-    }
-    int gate_points_cap = big_points(*params) ? params->points_max : FP_FAST_POINTS;  // (the passes' own sizing: see fp_gate_mask / fp_gap_mask)
-    int gap_points_max = params->points_max;
+    // the rule set as the rules kernel takes it; a host call's arrays get their device addresses at commit
+    fp::RulesEvalArgs ra = fp::rule_args(rules ? *rules : fp_rule_set{});
+    const bool host = mem == FP_MEM_HOST;
+    int pass_points = 0;  // (a host call: what the host calls of the passes work out from the time samples)
     // the rule instances of the refinement hold the rules' tables in LDS beside the refinement's own: a call that does not fit is refused
     auto refine_fits = [&](const fp_params& p_sized) -> int {
         if (!rules || R <= 0) return FP_OK;
         fp::FissArgs probe;
         probe.ka.p = p_sized;
-        probe.ka.b = *batch;
-        if (!(batch->S > 0 && batch->n_obs > 0)) probe.ka.b.n_obs = 0;
+        probe.ka.b = device_batch(batch);
         int base = 0, own = 0;
         fp::fiss_refine_rules_lds(probe, ra.on, ctx->refine_table_kb, &base, &own);
         if (base + own > fp::kRefineRulesLdsMax)
@@ -2236,25 +2208,20 @@ int plan_fiss_impl(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, 
     fp::InlineIn inl;   // (host entry, latency regime: see below)
     fp_batch lat_b;     // the batch as the lattice kernel addresses it (byte offsets into inl.bytes when inl.on)
     if (mem == FP_MEM_DEVICE) {
-        fa.ka.b = *batch;
+        fa.ka.b = device_batch(batch);
         if (loop) fa.ka.b.skip = loop->done;
-        if (!(batch->S > 0 && batch->n_obs > 0)) fa.ka.b.n_obs = 0;
         fa.io = *io;
         if (!trace_doubles) fa.io.trace = nullptr;
         FP_TRY(refine_fits(fa.ka.p));
     } else {
         FP_TRY(check_batch_host(params, batch));
-        if (rules && rules->envelope) FP_TRY(check_speed_profile_host(rules->envelope, batch));
-        if (rules && rules->boundary) FP_TRY(check_corridor_host(rules->boundary, batch));
+        if (rules) FP_TRY(check_rule_set_host(rules, batch));
         for (size_t i = 0; R > 0 && i < B; ++i)  // (a refinement probe beyond FP_MAX_POINTS would come back as NaN cost: a silently different walk)
             if (ceil(io->samp_max[3 * i + 2] / params->tick_t) > FP_MAX_POINTS)
                 return fail(FP_ELIMIT, "samp_max[%zu].T=%g needs more than FP_MAX_POINTS points (FISS+ refinement)", i, io->samp_max[3 * i + 2]);
         fa.ka.p.points_max = host_points_max(params, batch, R > 0 ? io->samp_max + 2 : nullptr, R > 0 ? B : 0, 3);  // (refined trajectories reach T = samp_max)
         FP_TRY(refine_fits(fa.ka.p));
-        if (rules) {  // (what the host calls of the passes work out from the time samples)
-            gap_points_max = host_points_max(params, batch, nullptr, 0, 0);
-            gate_points_cap = gap_points_max > FP_FAST_POINTS ? gap_points_max : FP_FAST_POINTS;
-        }
+        if (rules) pass_points = host_points_max(params, batch, nullptr, 0, 0);
         if (io->best_traj) {
             for (size_t i = 0; i < B; ++i)  // refined trajectories reach T = samp_max of their ego
                 if (ceil(io->samp_max[3 * i + 2] / params->tick_t) > stride) return fail(FP_EINVAL, "traj_stride=%d is smaller than the points of samp_max[%zu].T=%g", stride, i, io->samp_max[3 * i + 2]);
@@ -2276,19 +2243,8 @@ int plan_fiss_impl(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, 
             sl.in(io->samp_max, B * 3, &fa.io.samp_max);
             sl.in(io->samp_res, B * 3, &fa.io.samp_res);
         }
-        if (rules) {  // the rule arrays, as the host call of fp_rules_eval declares them
-            const size_t fn = (size_t)batch->F * batch->NX, F = (size_t)batch->F;
-            if (rules->envelope) sl.in(ra.v_limit, fn, &ra.v_limit);
-            if (rules->gates) {
-                sl.in(ra.gate_s, F * ra.gate_stride, &ra.gate_s);
-                sl.in(ra.closed, F * ra.T_gate, &ra.closed);
-            }
-            if (rules->boundary) {
-                sl.in(ra.left, fn, &ra.left);
-                sl.in(ra.right, fn, &ra.right);
-            }
-            if (rejected) sl.in_mut(rejected, B, &rejected_dev);
-        }
+        fp::stage_rule_arrays(sl, &ra, batch->F, batch->NX);
+        if (rules && rejected) sl.in_mut(rejected, B, &rejected_dev);
         sl.in_mut(io->prev_best_idx, B * 3, &fa.io.prev_best_idx);
         sl.out(io->best_ijk, B * 3, &fa.io.best_ijk);
         sl.out(io->best_cost, B, &fa.io.best_cost);
@@ -2320,7 +2276,7 @@ int plan_fiss_impl(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, 
         // the table passes of the rules that are on, in the order they run (rules.TABLE): the launches a dense call's caller makes behind
         // it, over the same tables - the search reads the words the FOP chain leaves
         const fp_batch& db = fa.ka.b;
-        const int32_t* perm = mem == FP_MEM_DEVICE ? batch->launch_order : nullptr;
+        const int32_t* perm = host ? nullptr : batch->launch_order;
         auto pass_args = [&](fp::TablePassArgs* a) {
             table_pass_args(a, params, &db, fa.cost_tbl, fa.ka.r.flag_tbl, pass_idx, pass_cost, pass_count);
             a->perm = perm;
@@ -2328,40 +2284,29 @@ int plan_fiss_impl(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, 
         if (ra.on & FP_RULE_LIMIT) {
             fp::EnvelopeArgs a;
             pass_args(&a);
-            a.front = ra.env_front; a.tol = ra.env_tol; a.max_lat_accel = ra.max_lat_accel;
-            a.coef = (ra.on & FP_RULE_LATERAL) ? db.coef : nullptr; a.v_limit = ra.v_limit;
-            LAUNCH_TRY(fp::launch_speed_envelope(a, stream), "speed-envelope kernel");
-            ++ctx->envelope_launches;
+            fp::envelope_args(&a, ra, db.coef);
+            FP_TRY(envelope_pass(ctx, a, stream));
         }
         if (ra.on & FP_RULE_GATE) {
             fp::GateArgs a;
             pass_args(&a);
-            a.front = ra.gate_front; a.max_decel = ra.max_decel; a.gate_stride = ra.gate_stride; a.T_gate = ra.T_gate;
-            a.t_now = db.t_now; a.gate_s = ra.gate_s; a.closed = ra.closed;
-            a.points_cap = gate_points_cap;
-            LAUNCH_TRY(fp::launch_gate_mask(a, stream), "gate kernel");
-            ++ctx->gate_launches;
+            fp::gate_args(&a, ra, db.t_now, fp::gate_points_cap(*params, host, pass_points));
+            FP_TRY(gate_pass(ctx, a, stream));
         }
         if (ra.on & FP_RULE_BOUNDARY) {
             fp::BoundaryArgs a;
             pass_args(&a);
-            a.veh_l = params->veh_l; a.veh_w = params->veh_w; a.margin = ra.margin;
-            a.d_samples = db.d_samples; a.left = ra.left; a.right = ra.right;
-            LAUNCH_TRY(fp::launch_boundary_mask(a, stream), "road-boundary kernel");
-            ++ctx->boundary_launches;
+            fp::boundary_args(&a, ra, *params, db.d_samples);
+            FP_TRY(boundary_pass(ctx, a, stream));
         }
         if (ra.on & FP_RULE_GAP) {
             fp::KernelArgs kg;
             kg.p = *params;
-            kg.p.points_max = gap_points_max;
+            kg.p.points_max = fp::gap_points_max(*params, host, pass_points);
             kg.b = db;
             kg.r = no_result();
             kg.r.cost_tbl = fa.ka.r.cost_tbl; kg.r.flag_tbl = fa.ka.r.flag_tbl; kg.r.best_idx = pass_idx; kg.r.best_cost = pass_cost;
-            fp::GapArgs g;
-            g.lag_follow = ra.lag_follow; g.lag_lead = ra.lag_lead; g.first = ra.first;
-            g.perm = perm; g.count = pass_count;
-            LAUNCH_TRY(fp::launch_gap_mask(kg, g, stream), "time-gap kernel");
-            ++ctx->gap_launches;
+            FP_TRY(gap_pass(ctx, kg, fp::gap_args(ra, perm, pass_count), stream));
         }
     }
     if (!lr.search_done) LAUNCH_TRY(fp::launch_fiss_search(fa, stream), "search kernel");
@@ -2419,8 +2364,7 @@ int fp_plan_fiss(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, co
 int fp_plan_fiss_step(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, const fp_fiss_opts* opts, const fp_fiss_io* io,
                       const fp_loop_io* loop, int mem, void* stream)
 {
-    if (!loop || !loop->ego || !loop->t_now || !loop->done || !loop->cycles || !loop->goal_xy) return fail(FP_EINVAL, "fp_loop_io has a NULL mandatory array");
-    if (loop->goal_poly && (!loop->goal_nv || loop->goal_max_vertices < 3)) return fail(FP_EINVAL, "fp_loop_io.goal_poly needs goal_nv and goal_max_vertices >= 3");
+    FP_TRY(check_loop_io(loop, /*need_goal=*/true));
     if (mem != FP_MEM_DEVICE) {  // host buffers: the two staged calls (every array travels anyway)
         if (!batch || !io) return fail(FP_EINVAL, "batch/io is NULL");
         fp_batch bb = *batch;
@@ -2436,15 +2380,10 @@ int fp_plan_fiss_rules(fp_ctx* ctx, const fp_params* params, const fp_batch* bat
 {
     FP_TRY(common_checks(ctx, params, batch, mem, stream));
     if (!rules) return fail(FP_EINVAL, "fp_plan_fiss_rules: rules must not be NULL");
-    if (!rules->envelope && !rules->gates && !rules->boundary && !rules->gaps) return fail(FP_EINVAL, "fp_plan_fiss_rules: every rule of the set is NULL");
-    if (rules->envelope) FP_TRY(check_speed_profile(rules->envelope, batch));
-    if (rules->gates) FP_TRY(check_gates(rules->gates));
-    if (rules->boundary) FP_TRY(check_corridor(rules->boundary));
-    if (rules->gaps) FP_TRY(check_time_gap(rules->gaps));
+    FP_TRY(check_rule_set("fp_plan_fiss_rules", rules, batch));
     if (loop) {
         if (mem != FP_MEM_DEVICE) return fail(FP_EINVAL, "fp_plan_fiss_rules: loop needs FP_MEM_DEVICE (a host caller plans with loop = NULL and calls fp_advance)");
-        if (!loop->ego || !loop->t_now || !loop->done || !loop->cycles || !loop->goal_xy) return fail(FP_EINVAL, "fp_loop_io has a NULL mandatory array");
-        if (loop->goal_poly && (!loop->goal_nv || loop->goal_max_vertices < 3)) return fail(FP_EINVAL, "fp_loop_io.goal_poly needs goal_nv and goal_max_vertices >= 3");
+        FP_TRY(check_loop_io(loop, /*need_goal=*/true));
     }
     ++ctx->fiss_rules_calls;
     return plan_fiss_impl(ctx, params, batch, opts, io, loop, mem, stream, rules, rejected);
@@ -2455,8 +2394,7 @@ int fp_advance(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, cons
 {
     FP_TRY(common_checks(ctx, params, batch, mem, stream));
     if ((best_idx == nullptr) == (end_state == nullptr)) return fail(FP_EINVAL, "exactly one of best_idx / end_state must be given");
-    if (!io || !io->ego || !io->t_now || !io->done || !io->cycles || !io->goal_xy) return fail(FP_EINVAL, "fp_loop_io has a NULL mandatory array");
-    if (io->goal_poly && (!io->goal_nv || io->goal_max_vertices < 3)) return fail(FP_EINVAL, "fp_loop_io.goal_poly needs goal_nv and goal_max_vertices >= 3");
+    FP_TRY(check_loop_io(io, /*need_goal=*/true));
     if (batch->B == 0) return FP_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t B = (size_t)batch->B;
@@ -2508,7 +2446,7 @@ int fp_loop_record(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, 
 {
     FP_TRY(common_checks(ctx, params, batch, mem, stream));
     if ((best_idx == nullptr) == (end_state == nullptr)) return fail(FP_EINVAL, "exactly one of best_idx / end_state must be given");
-    if (!io || !io->ego || !io->t_now || !io->done || !io->cycles) return fail(FP_EINVAL, "fp_loop_io has a NULL mandatory array");
+    FP_TRY(check_loop_io(io, /*need_goal=*/false));
     if (!io->cart_state) return fail(FP_EINVAL, "fp_loop_record: fp_loop_io.cart_state is mandatory (the rows' x, y, yaw)");
     if (!best_cost) return fail(FP_EINVAL, "fp_loop_record: best_cost is NULL");
     if (!log || !log->rows || !log->n_rows || !log->sealed) return fail(FP_EINVAL, "fp_loop_log has a NULL mandatory array (rows / n_rows / sealed)");
@@ -2565,8 +2503,7 @@ int fp_plan_step(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, co
     if (!result || !result->best_idx || !result->best_cost) return fail(FP_EINVAL, "result.best_idx/best_cost must not be NULL");
     if (result->best_traj && !result->best_flags) return fail(FP_EINVAL, "result.best_traj requires result.best_flags");
     if (result->fopplus || result->audit) return fail(FP_EINVAL, "fp_plan_step: result.fopplus / result.audit must be NULL (use fp_plan_dense + fp_advance)");
-    if (!io || !io->ego || !io->t_now || !io->done || !io->cycles || !io->goal_xy) return fail(FP_EINVAL, "fp_loop_io has a NULL mandatory array");
-    if (io->goal_poly && (!io->goal_nv || io->goal_max_vertices < 3)) return fail(FP_EINVAL, "fp_loop_io.goal_poly needs goal_nv and goal_max_vertices >= 3");
+    FP_TRY(check_loop_io(io, /*need_goal=*/true));
     if (batch->B == 0) return FP_OK;
     if (mem != FP_MEM_DEVICE) {
         // host buffers: the two staged calls (every array travels anyway; the fused launch is for resident loops)
@@ -2581,9 +2518,8 @@ int fp_plan_step(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, co
     fp::KernelArgs ka;
     ka.p = *params;
     ctx_lattice_args(ctx, &ka);
-    ka.b = *batch;
+    ka.b = device_batch(batch);
     ka.b.skip = io->done;
-    if (!(batch->S > 0 && batch->n_obs > 0)) ka.b.n_obs = 0;
     ka.r = *result;
     // the hand-over is offered to the lattice launch unless that launch cannot write the series it is asked for itself (the standalone
     // epilogue reads the ego's state, so it has to run BEFORE the state moves on)
@@ -2692,8 +2628,7 @@ int fp_eval_trajs(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, i
     ka.p = *params;
     ka.r = no_result();
     if (mem == FP_MEM_DEVICE) {
-        ka.b = *batch;
-        if (!(batch->S > 0 && batch->n_obs > 0)) ka.b.n_obs = 0;
+        ka.b = device_batch(batch);
         LAUNCH_TRY(fp::launch_eval_trajs(ka, K, end_states, cost, flags, traj, stride, traj_sparse, (hipStream_t)stream), "eval kernel");
         return FP_OK;
     }

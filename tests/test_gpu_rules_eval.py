@@ -1,7 +1,8 @@
 """GPU: fp_rules_eval (the four road rules on explicit end states) - on the lattice's own end states against the table passes it
 restates (fp_speed_envelope, fp_gate_mask, fp_boundary_mask, fp_gap_mask) and their references, one rule at a time and all four; off
 the lattice against tests/rules_eval_ref.py; the counts, the two memory spaces, a launch order, a second call on its own output;
-FrenetEngine.plan_fiss(rules=...), ClosedLoopRunner(audit=...) and the error codes of the C ABI."""
+FrenetEngine.plan_fiss(rules=...), ClosedLoopRunner(audit=...) and the error codes of the C ABI; a rule's bad argument refused with
+one code and one text by the rule's own pass, fp_rules_eval and fp_plan_fiss_rules, and a bad fp_loop_io by every closed-loop entry point."""
 import ctypes as C
 import dataclasses
 
@@ -325,3 +326,118 @@ def test_errors(engine, oracle):
         engine.rules_eval(dataclasses.replace(batch, bound_margin=-1.0), es, words, rules=("boundary",))
     assert engine.get_option("rules_eval_launches") == n0 and np.array_equal(w, words) and not bits.any() and not counts.any()  # nothing launched, nothing written
     assert raw_call(engine, batch, None, R.OFF_K, es, w, bits, counts) == 0 and engine.get_option("rules_eval_launches") == n0 + 1
+
+
+# ---------------------------------------------------------------- 8. one refusal, whichever entry point carries the rule
+NAN, INF = float("nan"), float("inf")
+# (rule, what is wrong, the text of fp_last_error as the rule's checks in csrc/frenet_abi.hip word it); every row is FP_EINVAL.  "field"
+# rows change the rule's struct, "array" rows an entry of the array the field points to (only a host call can look there)
+BAD_ARGUMENTS = [
+    ("envelope", ("field", "front", -1.0), "fp_speed_envelope: front must be finite and >= 0"),
+    ("envelope", ("field", "tol", NAN), "fp_speed_envelope: tol must be finite and >= 0"),
+    ("envelope", ("field", "max_lat_accel", INF), "fp_speed_envelope: max_lat_accel must be finite and >= 0 (0 = off)"),
+    ("envelope", ("field", "v_limit", None), "fp_speed_envelope: profile / v_limit must not be NULL"),
+    ("gates", ("field", "gate_stride", 0), "fp_gate_mask: gate_stride=0 outside 1..FP_MAX_GATES"),
+    ("gates", ("field", "gate_stride", _abi.FP_MAX_GATES + 1), f"fp_gate_mask: gate_stride={_abi.FP_MAX_GATES + 1} outside 1..FP_MAX_GATES"),
+    ("gates", ("field", "T_gate", 0), "fp_gate_mask: T_gate=0 must be >= 1"),
+    ("gates", ("field", "max_decel", NAN), "fp_gate_mask: max_decel must be finite and >= 0 (0 = off)"),
+    ("gates", ("field", "closed", None), "fp_gate_mask: gates / gate_s / closed must not be NULL"),
+    ("boundary", ("field", "margin", NAN), "fp_boundary_mask: margin must be finite and >= 0"),
+    ("boundary", ("field", "left", None), "fp_boundary_mask: corridor / left / right must not be NULL"),
+    ("gaps", ("field", "lag_follow", -1), "fp_gap_mask: lag_follow=-1 outside 0..FP_MAX_POINTS"),
+    ("gaps", ("field", "lag_lead", _abi.FP_MAX_POINTS + 1), f"fp_gap_mask: lag_lead={_abi.FP_MAX_POINTS + 1} outside 0..FP_MAX_POINTS"),
+    ("gaps", ("field", "first", 0), "fp_gap_mask: first=0 must be >= 1"),
+    ("envelope", ("array", "speed_limit", -1.0), 'fp_speed_envelope: v_limit is -1 at frame 0, knot 0 (+inf says "no limit", 0 "stop")'),
+    ("boundary", ("array", "bound_right", NAN), 'fp_boundary_mask: corridor has a NaN at frame 0, knot 0 (+-inf says "no edge")'),
+]
+LAUNCH_COUNTERS = ("envelope_launches", "gate_launches", "boundary_launches", "gap_launches", "rules_eval_launches", "lattice_launches")
+
+
+def last_error(engine):
+    return engine._lib.fp_last_error().decode()
+
+
+def test_one_refusal_in_the_pass_the_rules_kernel_and_the_fiss_call(engine):
+    from test_gpu_fiss_rules import raw_call as fiss_raw_call
+
+    batch = R.all_rules_batch()
+    B, Cn = batch.B, batch.C
+    p, fb = host_structs(batch)
+    es = np.ascontiguousarray(R.lattice_end_states(batch)[:, :1])
+    cost, words = np.zeros((B, Cn)), np.zeros((B, Cn), dtype=np.uint32)
+    idx, best, count = np.zeros(B, dtype=np.int32), np.zeros(B), np.zeros(B, dtype=np.int32)
+    w1, bits, counts = np.zeros((B, 1), dtype=np.uint32), np.zeros((B, 1), dtype=np.uint32), np.zeros((B, 5), dtype=np.int32)
+    before = [engine.get_option(k) for k in LAUNCH_COUNTERS]
+
+    def own_pass(rule, struct, tables=True):
+        ptr = lambda a: a.ctypes.data if tables else None  # noqa: E731
+        return getattr(engine._lib, rules.by_name[rule].fn)(engine._ctx, C.byref(p), C.byref(fb), C.byref(struct), ptr(cost), ptr(words), ptr(idx), ptr(best),
+                                                            count.ctypes.data, _abi.FP_MEM_HOST, None)
+
+    for rule, (kind, name, value), text in BAD_ARGUMENTS:
+        held = {}
+
+        def addr(k):
+            held[k] = np.array(rules.array(batch, k), order="C", copy=True)
+            return held[k].ctypes.data
+
+        rs, structs = rules.rule_set(batch, addr, (rule,))
+        if kind == "field":
+            setattr(structs[rule], name, value)
+        else:
+            held[name][0, 0] = value  # (knot 0 of frame 0 is used: every line has two knots or more)
+        got = [(own_pass(rule, structs[rule]), last_error(engine)),
+               (raw_call(engine, batch, None, 1, es, w1, bits, counts, rule_set=rs), last_error(engine)),
+               (fiss_raw_call(engine, batch, rs), last_error(engine))]
+        assert got == [(-1, text)] * 3, (rule, name, value, got)
+    # the empty set names the entry point it was handed to
+    assert raw_call(engine, batch, None, 1, es, w1, bits, counts, rule_set=_abi.FpRuleSet()) == -1
+    assert last_error(engine) == "fp_rules_eval: every rule of the set is NULL"
+    assert fiss_raw_call(engine, batch, _abi.FpRuleSet()) == -1 and last_error(engine) == "fp_plan_fiss_rules: every rule of the set is NULL"
+    # a pass looks at its tables before it looks at the rule's scalars
+    held = {}
+    rs, structs = rules.rule_set(batch, lambda k: held.setdefault(k, np.ascontiguousarray(rules.array(batch, k))).ctypes.data, ("boundary",))
+    structs["boundary"].margin = NAN
+    assert own_pass("boundary", structs["boundary"], tables=False) == -1
+    assert last_error(engine) == "fp_boundary_mask: cost_tbl/flag_tbl/best_idx/best_cost must not be NULL"
+    assert [engine.get_option(k) for k in LAUNCH_COUNTERS] == before and not words.any() and not w1.any() and not bits.any() and not counts.any()
+
+
+def test_loop_io_refusals(engine):
+    batch = R.all_rules_batch()
+    B = batch.B
+    p, fb = host_structs(batch)
+    lib, ctx, HOST = engine._lib, engine._ctx, _abi.FP_MEM_HOST
+    arr = dict(ego=np.array(batch.ego, dtype=np.float64), t_now=np.zeros(B, dtype=np.int32), done=np.zeros(B, dtype=np.int32), cycles=np.zeros(B, dtype=np.int32),
+               goal_xy=np.full((B, 2), 1e6), cart_state=np.zeros((B, 3)), goal_poly=np.zeros((B, 4, 2)))
+    idx, best = np.zeros(B, dtype=np.int32), np.zeros(B)
+    res = _abi.FpResult()
+    res.best_idx, res.best_cost = idx.ctypes.data, best.ctypes.data
+    out = engine.fiss_outputs(B, 0)
+    fio = _abi.FpFissIo()
+    fio.samp_min, fio.samp_max, fio.samp_res = (np.ascontiguousarray(getattr(batch, k)).ctypes.data for k in ("samp_min", "samp_max", "samp_res"))
+    for k in ("prev_best_idx", "best_ijk", "best_cost", "end_state", "refined", "stats"):
+        setattr(fio, k, getattr(out, k).ctypes.data)
+    opts = _abi.FpFissOpts(_abi.FP_FISS, 0, 10.0, 0.5)
+
+    def loop_io(*names, goal_max_vertices=0):
+        io = _abi.FpLoopIo()
+        for k in names:
+            setattr(io, k, arr[k].ctypes.data)
+        io.goal_max_vertices = goal_max_vertices
+        return io
+
+    calls = {
+        "fp_advance": lambda io: lib.fp_advance(ctx, C.byref(p), C.byref(fb), idx.ctypes.data, None, C.byref(io), HOST, None),
+        "fp_plan_step": lambda io: lib.fp_plan_step(ctx, C.byref(p), C.byref(fb), C.byref(res), C.byref(io), HOST, None),
+        "fp_plan_fiss_step": lambda io: lib.fp_plan_fiss_step(ctx, C.byref(p), C.byref(fb), C.byref(opts), C.byref(fio), C.byref(io), HOST, None),
+        "fp_loop_record": lambda io: lib.fp_loop_record(ctx, C.byref(p), C.byref(fb), C.byref(io), idx.ctypes.data, None, best.ctypes.data, None, None, HOST, None),
+    }
+    n0 = engine.get_option("lattice_launches")
+    no_ego = loop_io("t_now", "done", "cycles", "goal_xy", "cart_state")
+    for fn, call in calls.items():
+        assert call(no_ego) == -1 and last_error(engine) == "fp_loop_io has a NULL mandatory array", fn
+    no_nv = loop_io("ego", "t_now", "done", "cycles", "goal_xy", "cart_state", "goal_poly", goal_max_vertices=4)
+    for fn in ("fp_advance", "fp_plan_step", "fp_plan_fiss_step"):
+        assert calls[fn](no_nv) == -1 and last_error(engine) == "fp_loop_io.goal_poly needs goal_nv and goal_max_vertices >= 3", fn
+    assert engine.get_option("lattice_launches") == n0 and (arr["t_now"] == 0).all() and (arr["cycles"] == 0).all()
