@@ -21,6 +21,9 @@ from types import SimpleNamespace
 
 import numpy as np
 
+import rule_ref_common as common
+from rule_ref_common import argmin
+
 FLAG_BOUNDARY = 128
 FLAG_INFEASIBLE = 1 | 2 | 4 | 16 | 32 | 64 | FLAG_BOUNDARY  # FP_FLAG_CONSTRAINTS | FP_FLAG_COLLISION | FP_FLAG_BOUNDARY
 UNDECIDED_TOL = 1e-9                                         # FP_AUDIT_GAP_TOL (include/frenet_gpu.h)
@@ -88,7 +91,7 @@ def ego_mask(O, batch, b, tables=None):
     """The check for ego b of a batch that carries a corridor.  tables = (cost [C], flags [C]) to mask (default: the oracle's dense
     tables; the clearance term's re-priced tables come from tests/clearance_ref.py).  Returns a namespace:
     cost [C], flags_in [C], flags [C] (bit written), bit [C], slack [C], hi [C] / lo [C] (largest d + h / smallest d - h over the
-    checked points, NaN when none), undecided [C], best_idx, best_cost, n_masked."""
+    checked points, NaN when none), undecided [C], best_idx, best_cost (the masked winner), best_in (the winner of flags_in), n_masked."""
     prob = O.problems_from_batch(batch, egos=[b])[0]
     cost, flags_in = prob.dense_tables() if tables is None else (np.asarray(tables[0], dtype=np.float64), np.asarray(tables[1], dtype=np.uint32))
     f = int(batch.frame_of[b])
@@ -113,12 +116,9 @@ def ego_mask(O, batch, b, tables=None):
         slack[c] = gaps.min() if gaps.size else np.inf
         hi[c], lo[c] = up.max(), dn.min()
     flags = (flags_in & np.uint32(~FLAG_BOUNDARY & 0xFFFFFFFF)) | np.where(bit, FLAG_BOUNDARY, 0).astype(np.uint32)
-    best_idx, best_cost = -1, np.nan
-    for c in range(Cn):  # `min_cost >= cost`: the last minimum wins; a NaN cost never does (frenet_optimal_planner.py:264-268)
-        if not (int(flags[c]) & FLAG_INFEASIBLE) and cost[c] == cost[c] and (best_idx < 0 or best_cost >= cost[c]):
-            best_idx, best_cost = c, float(cost[c])
+    best_idx, best_cost = argmin(cost, flags)
     return SimpleNamespace(cost=cost, flags_in=flags_in, flags=flags, bit=bit, slack=slack, hi=hi, lo=lo, undecided=slack < UNDECIDED_TOL,
-                           best_idx=best_idx, best_cost=best_cost, n_masked=int(bit.sum()))
+                           best_idx=best_idx, best_cost=best_cost, best_in=argmin(cost, flags_in)[0], n_masked=int(bit.sum()))
 
 
 def batch_mask(O, batch, tables=None, egos=None):
@@ -129,25 +129,12 @@ def batch_mask(O, batch, tables=None, egos=None):
 
 def check_caps(refs, what=""):
     """The caps the tests rely on: at most 0.5 % of the batch's candidates undecided, at most one ego excluded for having one."""
-    total = sum(len(r.bit) for r in refs)
-    und = sum(int(r.undecided.sum()) for r in refs)
-    egos = sum(1 for r in refs if r.undecided.any())
-    assert und <= MAX_UNDECIDED_SHARE * total, (what, und, total)
-    assert egos <= MAX_EXCLUDED_EGOS, (what, egos)
-    return und, egos
+    return common.check_caps(refs, MAX_UNDECIDED_SHARE, MAX_EXCLUDED_EGOS, what)
 
 
 # ---------------------------------------------------------------------------
 # the test batches (shared by tests/test_boundary_cpu.py, which checks the caps on the reference alone, and tests/test_gpu_boundary.py)
 # ---------------------------------------------------------------------------
-def _line_ends():
-    b = widened(base_batch())
-    ego = b.ego.copy()
-    ego[1, 0] = b.knots[1, -1] - 40.0  # within 40 m of the end of its line: fast candidates leave it (M < N)
-    ego[3, 0] = b.knots[3, -1] + 5.0   # past the end: M = 0 for every candidate, nothing is checked
-    return with_corridor(b, left=b.bound_left, right=b.bound_right, ego=ego)
-
-
 def _unbounded():
     b = base_batch()
     left = b.bound_left.copy()
@@ -172,7 +159,8 @@ CASES = {
     "wide": lambda: widened(base_batch()),                   # the same, both edges 0.35 m further out
     "tick005": lambda: base_batch(tick_t=0.05),              # N up to 200 (needs points_max): four lane rounds
     "tick005_wide": lambda: widened(base_batch(tick_t=0.05)),
-    "line_ends": _line_ends,                                 # M < N and M <= 1
+    # M < N and M <= 1
+    "line_ends": lambda: common._line_ends(widened(base_batch()), lambda b, ego: with_corridor(b, left=b.bound_left, right=b.bound_right, ego=ego)),
     "unbounded": _unbounded,                                 # +inf on knots 20 .. 40 of the left side, no right edge at all
     "obstacles": _obstacles,                                 # w_obstacle = 0.1 against 6 obstacles: re-priced tables
     "chunks": _lattice(9, 9, 7),                             # C = 567: three chunks of 256 candidates, the last one partly filled

@@ -26,6 +26,9 @@ from types import SimpleNamespace
 
 import numpy as np
 
+import rule_ref_common as common
+from rule_ref_common import argmin, plain_batch  # noqa: F401  (the tests reach plain_batch through this module too)
+
 FLAG_SPEED, FLAG_ACCEL, FLAG_BOUNDARY = 1, 2, 128
 FLAG_INFEASIBLE = 1 | 2 | 4 | 16 | 32 | 64 | FLAG_BOUNDARY  # FP_FLAG_CONSTRAINTS | FP_FLAG_COLLISION | FP_FLAG_BOUNDARY
 UNDECIDED_TOL = 1e-9                                         # FP_AUDIT_GAP_TOL (include/frenet_gpu.h)
@@ -60,14 +63,6 @@ def with_profile(batch, limit="wavy", front=None, tol=TOL, max_lat_accel=0.0, **
         lim = np.broadcast_to(np.asarray(limit, dtype=np.float64), knots.shape).copy()
     return dataclasses.replace(batch, speed_limit=lim, limit_front=0.5 * batch.veh_l if front is None else front, limit_tol=tol,
                                max_lat_accel=max_lat_accel, **kw)
-
-
-def plain_batch(B=5, nd=5, nv=4, nt=3, seed=SEED):
-    """The smallest shape that still exercises every loop: 5 egos x 5 x 4 x 3 (C = 60: no multiple of the wave or of the workgroup,
-    12 profiles for 4 wavefronts), N = 80 .. 100 (two lane rounds), 81 knots, no obstacles."""
-    from fiss_plus_planner_amd import synth
-
-    return synth.make_batch(B, nd, nv, nt, 0, 20, False, seed)
 
 
 def _segment(knots, s):
@@ -133,15 +128,6 @@ def ego_envelope(O, batch, b, tables=None):
                            best_in=argmin(cost, flags_in)[0], n_limited=int((bit_a | bit_b).sum()))
 
 
-def argmin(cost, flags):
-    """`min_cost >= cost`: the last minimum wins; a NaN cost never does (frenet_optimal_planner.py:264-268)."""
-    best_idx, best_cost = -1, np.nan
-    for c in range(len(cost)):
-        if not (int(flags[c]) & FLAG_INFEASIBLE) and cost[c] == cost[c] and (best_idx < 0 or best_cost >= cost[c]):
-            best_idx, best_cost = c, float(cost[c])
-    return best_idx, best_cost
-
-
 def batch_envelope(O, batch, tables=None, egos=None):
     """ego_envelope for the egos asked for (all by default) -> list; tables = (cost [B, C], flags [B, C]) or None."""
     egos = range(batch.B) if egos is None else egos
@@ -150,12 +136,7 @@ def batch_envelope(O, batch, tables=None, egos=None):
 
 def check_caps(refs, what=""):
     """The caps the tests rely on: at most 0.5 % of the batch's candidates undecided, at most one ego excluded for having one."""
-    total = sum(len(r.slack) for r in refs)
-    und = sum(int(r.undecided.sum()) for r in refs)
-    egos = sum(1 for r in refs if r.undecided.any())
-    assert und <= MAX_UNDECIDED_SHARE * total, (what, und, total)
-    assert egos <= MAX_EXCLUDED_EGOS, (what, egos)
-    return und, egos
+    return common.check_caps(refs, MAX_UNDECIDED_SHARE, MAX_EXCLUDED_EGOS, what)
 
 
 def limited_share(refs):
@@ -184,14 +165,6 @@ def _stop():
     return with_profile(b, limit=stop_limit(b)[0])
 
 
-def _line_ends():
-    b = plain_batch()
-    ego = b.ego.copy()
-    ego[1, 0] = b.knots[1, -1] - 40.0  # within 40 m of the end of its line: fast candidates leave it (M < N)
-    ego[3, 0] = b.knots[3, -1] + 5.0   # past the end: M = 0 for every candidate, nothing is checked
-    return with_profile(b, max_lat_accel=MAX_LAT_ACCEL, ego=ego)
-
-
 def stop_egos(O):
     """The egos of the stop case whose unmasked winner runs the red light while a masked winner exists."""
     _, refs = case(O, "stop")
@@ -204,7 +177,7 @@ CASES = {
     "both": lambda: with_profile(plain_batch(), max_lat_accel=MAX_LAT_ACCEL),                 # limits and lateral together
     "stop": _stop,                                                                            # a red light ~50 m ahead of every ego
     "tick005": lambda: with_profile(plain_batch(), max_lat_accel=MAX_LAT_ACCEL, tick_t=0.05),  # N up to 200 (needs points_max): four lane rounds
-    "line_ends": _line_ends,                                                                  # M < N and M <= 1
+    "line_ends": lambda: common._line_ends(plain_batch(), lambda b, ego: with_profile(b, max_lat_accel=MAX_LAT_ACCEL, ego=ego)),  # M < N and M <= 1
     "chunks": lambda: with_profile(plain_batch(2, 9, 9, 7), max_lat_accel=MAX_LAT_ACCEL),     # C = 567: three chunks of the row pass, 63 profiles
     "unlimited": lambda: with_profile(plain_batch(), limit=None),                             # all +inf, lateral off: nothing may change
 }

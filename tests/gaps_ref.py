@@ -25,6 +25,9 @@ from types import SimpleNamespace
 
 import numpy as np
 
+import rule_ref_common as common
+from rule_ref_common import argmin
+
 FLAG_COLLISION = 4
 FLAG_INFEASIBLE = 1 | 2 | 4 | 16 | 32 | 64 | 128  # FP_FLAG_CONSTRAINTS | FP_FLAG_COLLISION | FP_FLAG_BOUNDARY
 UNDECIDED_TOL = 1e-9                              # FP_AUDIT_GAP_TOL (include/frenet_gpu.h)
@@ -33,15 +36,6 @@ MAX_EXCLUDED_EGOS = 1                             # per test batch
 NEAR = 0.5                                        # m: pairs further apart than the circumradii + NEAR are not looked at
 X, Y, YAW = 9, 10, 11                             # rows of a [16, stride] dump (FP_ARR_X / _Y / _YAW)
 SEED = 33055                                      # the seed of every test batch (the other rule passes' batches use the same one)
-
-
-def argmin(cost, flags):
-    """`min_cost >= cost`: the last minimum wins; a NaN cost never does (frenet_optimal_planner.py:264-268)."""
-    best_idx, best_cost = -1, np.nan
-    for c in range(len(cost)):
-        if not (int(flags[c]) & FLAG_INFEASIBLE) and cost[c] == cost[c] and (best_idx < 0 or best_cost >= cost[c]):
-            best_idx, best_cost = c, float(cost[c])
-    return best_idx, best_cost
 
 
 def pose_set(M, horizon, t_now, T_obs, cs):
@@ -155,12 +149,7 @@ def batch_gaps(O, batch, tables=None, egos=None, **kw):
 
 def check_caps(refs, what=""):
     """The caps the tests rely on: at most 0.5 % of the batch's candidates undecided, at most one ego excluded for having one."""
-    total = sum(len(r.slack) for r in refs)
-    und = sum(int(r.undecided.sum()) for r in refs)
-    egos = sum(1 for r in refs if r.undecided.any())
-    assert und <= MAX_UNDECIDED_SHARE * total, (what, und, total)
-    assert egos <= MAX_EXCLUDED_EGOS, (what, egos)
-    return und, egos
+    return common.check_caps(refs, MAX_UNDECIDED_SHARE, MAX_EXCLUDED_EGOS, what)
 
 
 def close_share(refs):
@@ -215,14 +204,6 @@ def lds_plan(batch):
     return full <= LDS_BUDGET, False
 
 
-def _line_ends():
-    b = moving_batch()
-    ego = b.ego.copy()
-    ego[1, 0] = b.knots[1, -1] - 40.0  # within 40 m of the end of its line: fast candidates leave it (M < N)
-    ego[3, 0] = b.knots[3, -1] + 5.0   # past the end: M = 0 for every candidate, nothing is checked
-    return with_gap(b, ego=ego)
-
-
 def _short_table():
     """The table ends inside the horizon (T_obs = 30 rows, N up to 50) and the scenario one step earlier for two of the scenes."""
     b = moving_batch(T_obs=30)
@@ -274,7 +255,7 @@ CASES = {
     "no_lds": lambda: _table_rows(100, 104),                                            # neither fits: no cull table at all
     "polygons": _polygons,                                                              # convex rings among the columns
     "short_table": _short_table,                                                        # the table / the scenario end inside the horizon
-    "line_ends": _line_ends,                                                            # M < N and M <= 1
+    "line_ends": lambda: common._line_ends(moving_batch(), lambda b, ego: with_gap(b, ego=ego)),  # M < N and M <= 1
     "lead": lead_batch,                                                                 # lag_follow = 0: the lead direction alone
 }
 # every case is meant to flag something: the floor on the violating share of its candidates (the follow cases of the base batch flagged

@@ -24,6 +24,9 @@ from types import SimpleNamespace
 
 import numpy as np
 
+import rule_ref_common as common
+from rule_ref_common import argmin, plain_batch  # noqa: F401  (the tests reach plain_batch through this module too)
+
 FLAG_SPEED = 1
 FLAG_INFEASIBLE = 1 | 2 | 4 | 16 | 32 | 64 | 128  # FP_FLAG_CONSTRAINTS | FP_FLAG_COLLISION | FP_FLAG_BOUNDARY
 UNDECIDED_TOL = 1e-9                              # FP_AUDIT_GAP_TOL (include/frenet_gpu.h)
@@ -32,15 +35,6 @@ MAX_EXCLUDED_EGOS = 1                             # per test batch
 S = 1                                             # row of a [16, stride] dump (FP_ARR_S)
 
 SEED = 33055  # the seed of every test batch (the envelope's and the boundary check's batches use the same one)
-
-
-def argmin(cost, flags):
-    """`min_cost >= cost`: the last minimum wins; a NaN cost never does (frenet_optimal_planner.py:264-268)."""
-    best_idx, best_cost = -1, np.nan
-    for c in range(len(cost)):
-        if not (int(flags[c]) & FLAG_INFEASIBLE) and cost[c] == cost[c] and (best_idx < 0 or best_cost >= cost[c]):
-            best_idx, best_cost = c, float(cost[c])
-    return best_idx, best_cost
 
 
 def waived_gates(batch, b):
@@ -101,12 +95,7 @@ def batch_gates(O, batch, tables=None, egos=None):
 
 def check_caps(refs, what=""):
     """The caps the tests rely on: at most 0.5 % of the batch's candidates undecided, at most one ego excluded for having one."""
-    total = sum(len(r.slack) for r in refs)
-    und = sum(int(r.undecided.sum()) for r in refs)
-    egos = sum(1 for r in refs if r.undecided.any())
-    assert und <= MAX_UNDECIDED_SHARE * total, (what, und, total)
-    assert egos <= MAX_EXCLUDED_EGOS, (what, egos)
-    return und, egos
+    return common.check_caps(refs, MAX_UNDECIDED_SHARE, MAX_EXCLUDED_EGOS, what)
 
 
 def gated_share(refs):
@@ -119,14 +108,6 @@ def gated_share(refs):
 AHEAD = (25.0, 60.0)  # m: the two lines of every frame, ahead of the frame's ego
 T_GATE = 128          # steps of the phase tables (the base batches' horizon is N <= 100)
 MAX_DECEL = 2.0       # m/s^2 of the waiver case: the egos faster than ~9.5 m/s cannot stop in front of the line 25 m ahead
-
-
-def plain_batch(B=5, nd=5, nv=4, nt=3, seed=SEED):
-    """The smallest shape that still exercises every loop: 5 egos x 5 x 4 x 3 (C = 60: no multiple of the wave or of the workgroup,
-    12 profiles for 4 wavefronts), N = 80 .. 100 (two lane rounds), 81 knots, no obstacles."""
-    from fiss_plus_planner_amd import synth
-
-    return synth.make_batch(B, nd, nv, nt, 0, 20, False, seed)
 
 
 def phases(F, T, G, period=(23, 31), offset=7):
@@ -153,14 +134,6 @@ def with_gates(batch, ahead=AHEAD, T_gate=T_GATE, closed=None, front=None, max_d
                                gate_max_decel=max_decel, **kw)
 
 
-def _line_ends():
-    b = plain_batch()
-    ego = b.ego.copy()
-    ego[1, 0] = b.knots[1, -1] - 40.0  # within 40 m of the end of its line: fast candidates leave it (M < N)
-    ego[3, 0] = b.knots[3, -1] + 5.0   # past the end: M = 0 for every candidate, nothing is checked
-    return with_gates(b, ahead=(10.0, 25.0), ego=ego)
-
-
 def _stride32():
     ahead = tuple(4.0 + 2.5 * g for g in range(32))  # a line every 2.5 m from 4 m to 81.5 m ahead, every slot used
     b = plain_batch()
@@ -173,7 +146,7 @@ CASES = {
     "hold_last": lambda: with_gates(plain_batch(), T_gate=30),                                          # the table ends before the horizon
     "before_zero": lambda: with_gates(plain_batch(), t_now=[-50, -5, -120, -1, -30]),                   # t_now + i < 0: row 0 holds
     "tick005": lambda: with_gates(plain_batch(), tick_t=0.05, T_gate=2 * T_GATE),                       # N up to 200 (needs points_max)
-    "line_ends": _line_ends,                                                                            # M < N and M <= 1
+    "line_ends": lambda: common._line_ends(plain_batch(), lambda b, ego: with_gates(b, ahead=(10.0, 25.0), ego=ego)),  # M < N and M <= 1
     "chunks": lambda: with_gates(plain_batch(2, 9, 9, 7)),                                              # C = 567: three chunks, 63 profiles
     "stride32": _stride32,                                                                              # gate_stride = 32, every slot used
     "open": lambda: with_gates(plain_batch(), closed=np.zeros((5, T_GATE, 2), dtype=bool)),             # no bit closed: nothing may change

@@ -3,135 +3,44 @@ flag words exact on every candidate the reference decides by more than 1e-9 m, e
 argmin and the masked count exact, through both memory spaces, with a launch order and a skipped ego; long trajectories, line ends,
 unbounded stretches, edges 1 um either side of a candidate's reach, the bit written rather than OR-ed, the entry points that take its
 outputs, graph capture, the error codes and the planner class."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import boundary_ref as R
+import rule_pass as RP
 from conftest import assert_series_close
 from fiss_plus_planner_amd import _abi, synth
-from fiss_plus_planner_amd.engine import FrenetEngine, host_structs
+from rule_pass import same_bits
 
 pytestmark = pytest.mark.gpu
+RULE = "boundary"
 BOUNDARY = np.uint32(R.FLAG_BOUNDARY)
 
 
-def same_bits(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(np.ascontiguousarray(a).view(np.uint8), np.ascontiguousarray(b).view(np.uint8))
-
-
-def check_against(refs, dense, got, what, skip=None):
-    """got = (flags, best_idx, best_cost, n_masked) of a mask call over the tables of `dense` (cost, flags)."""
-    flags, bi, bc, nm = got
-    cost_in, flags_in = dense
-    und, excluded = R.check_caps(refs, what)
-    for b, r in enumerate(refs):
-        if skip is not None and skip[b]:
-            assert bi[b] == -1 and np.isnan(bc[b]) and nm[b] == 0, (what, b)
-            assert np.array_equal(flags[b], flags_in[b]), (what, b)  # rows neither read nor written
-            continue
-        assert np.array_equal(flags_in[b], r.flags_in), (what, b)  # (the dense call's own parity with the oracle)
-        assert np.array_equal(flags[b] & ~BOUNDARY, flags_in[b]), (what, b)
-        ok = ~r.undecided
-        assert np.array_equal((flags[b] & BOUNDARY != 0)[ok], r.bit[ok]), (what, b, np.nonzero((flags[b] & BOUNDARY != 0) != r.bit)[0][:8].tolist())
-        assert nm[b] == int(np.count_nonzero(flags[b] & BOUNDARY)), (what, b)
-        if not r.undecided.any():
-            assert nm[b] == r.n_masked and bi[b] == r.best_idx, (what, b, int(bi[b]), r.best_idx)
-        if bi[b] >= 0:
-            assert same_bits(bc[b:b + 1], cost_in[b, bi[b]:bi[b] + 1]) and not (flags[b, bi[b]] & _abi.FLAG_INFEASIBLE), (what, b)
-        else:
-            assert np.isnan(bc[b]), (what, b)
-
-
-def dense_and_mask(engine, batch, skip=None):
-    out = engine.plan_dense(batch, tables=True)
-    cost0, flags0 = out.cost.copy(), out.flags.copy()
-    got = engine.boundary_mask(batch, out.cost, out.flags, skip=skip)
-    assert same_bits(out.cost, cost0) and np.array_equal(out.flags, flags0)  # the caller's tables are copies here
-    return out, got
-
-
-class Resident:
-    """A batch and its corridor in device memory, the dense call and the mask behind it on one stream."""
-
-    def __init__(self, engine, batch, order=None, skip=None):
-        import torch
-
-        from fiss_plus_planner_amd.device_batch import DeviceBatch
-
-        self.torch, self.engine, self.db = torch, engine, DeviceBatch(batch, 0, order_hint=False)
-        db, B, Cn = self.db, batch.B, batch.C
-        self.fb = _abi.FpBatch.from_buffer_copy(db.fb)
-        if order is not None:
-            self.order = torch.from_numpy(np.ascontiguousarray(order, dtype=np.int32)).to(db.dev)
-            self.fb.launch_order = self.order.data_ptr()
-        if skip is not None:
-            self.skip = torch.from_numpy(np.ascontiguousarray(skip, dtype=np.int32)).to(db.dev)
-            self.fb.skip = self.skip.data_ptr()
-        self.margin = float(batch.bound_margin)
-        self.bi0, self.bc0 = db.empty(B, torch.int32), db.empty(B, torch.float64)
-        self.bi, self.bc, self.nm = db.empty(B, torch.int32), db.empty(B, torch.float64), db.empty(B, torch.int32)
-        self.cost, self.flags = torch.zeros((B, Cn), dtype=torch.float64, device=db.dev), torch.zeros((B, Cn), dtype=torch.int32, device=db.dev)
-
-    def pair(self, stream=0):
-        db = self.db
-        self.engine.plan_dense_device(db.params, self.fb, self.bi0.data_ptr(), self.bc0.data_ptr(), cost_tbl=self.cost.data_ptr(), flag_tbl=self.flags.data_ptr(), stream=stream)
-        self.mask(stream)
-
-    def mask(self, stream=0, left=None, right=None):
-        db = self.db
-        self.engine.boundary_mask_device(db.params, self.fb, (left if left is not None else db.t["bound_left"]).data_ptr(),
-                                         (right if right is not None else db.t["bound_right"]).data_ptr(), self.margin, self.cost.data_ptr(),
-                                         self.flags.data_ptr(), self.bi.data_ptr(), self.bc.data_ptr(), self.nm.data_ptr(), stream=stream)
-
-    def fetch(self):
-        self.torch.cuda.synchronize(self.db.dev)
-        return self.flags.cpu().numpy().view(np.uint32), self.bi.cpu().numpy(), self.bc.cpu().numpy(), self.nm.cpu().numpy()
+def dense_and_mask(engine, batch):
+    return RP.dense_and_pass(engine, RULE, batch)
 
 
 # ---------------------------------------------------------------- 1 .. 4: parity
 @pytest.mark.parametrize("name", ["base", "wide", "chunks", "unstaged"])
 def test_parity_host(engine, oracle, name):
-    batch, refs = R.case(oracle, name)
-    out, got = dense_and_mask(engine, batch)
-    check_against(refs, (out.cost, out.flags), got, name)
-    if name in ("base", "wide"):  # a skipped ego: -1 / NaN / 0, its rows untouched
-        skip = np.zeros(batch.B, dtype=np.int32)
-        skip[2] = 1
-        out.flags[2] = 0xFFFFFFFF  # (a row that WOULD fault or count if it were read)
-        got = engine.boundary_mask(batch, out.cost, out.flags, skip=skip)
-        assert (got[0][2] == 0xFFFFFFFF).all()
-        out.flags[2] = refs[2].flags_in
-        got[0][2] = refs[2].flags_in
-        check_against(refs, (out.cost, out.flags), got, name + " skip", skip)
+    RP.host_parity(engine, oracle, RULE, name, skip_ego=2 if name in ("base", "wide") else None)
 
 
 @pytest.mark.parametrize("name", ["base", "wide"])
 def test_parity_device_with_order_and_skip(engine, oracle, name):
-    batch, refs = R.case(oracle, name)
-    host = engine.plan_dense(batch, tables=True)
-    res = Resident(engine, batch)
-    res.pair()
-    plain = res.fetch()
-    check_against(refs, (host.cost, host.flags), plain, name + " device")
-    skip = np.zeros(batch.B, dtype=np.int32)
-    skip[2] = 1
-    res = Resident(engine, batch, order=np.arange(batch.B)[::-1], skip=skip)
-    res.pair()
-    got = res.fetch()
-    tables = (host.cost.copy(), host.flags.copy())
-    tables[1][2] = 0  # (the dense call wrote no rows for the skipped ego: the zeros the arrays were made with)
-    check_against(refs, tables, got, name + " device, reversed order, skip", skip)
-    keep = skip == 0
-    assert np.array_equal(got[0][keep], plain[0][keep]) and np.array_equal(got[1][keep], plain[1][keep]) and same_bits(got[2][keep], plain[2][keep])
+    RP.device_parity(engine, oracle, RULE, name)
+
+
+def test_idempotence(engine, oracle):
+    assert len(list(RP.idempotence(engine, oracle, RULE, ("base", "wide")))) == 2
 
 
 @pytest.mark.parametrize("name", ["tick005", "tick005_wide", "line_ends", "unbounded"])
 def test_long_trajectories_line_ends_and_unbounded_stretches(engine, oracle, name):
     batch, refs = R.case(oracle, name)
     out, got = dense_and_mask(engine, batch)
-    check_against(refs, (out.cost, out.flags), got, name)
+    RP.check_against(RULE, refs, (out.cost, out.flags), got, name)
     if name == "line_ends":  # past the end: M <= 1, nothing is checked, no bit
         assert (out.flags[3] >> 20 <= 1).all() and not (got[0][3] & BOUNDARY).any() and got[3][3] == 0
     if name == "unbounded":  # no violation can come from the unbounded stretch: a candidate that stays on it carries no bit
@@ -162,7 +71,7 @@ def test_an_edge_one_micrometre_either_side_of_a_candidates_reach(engine, oracle
         ref = R.batch_mask(oracle, batch)
         assert ref[b].bit[c] == (eps < 0) and abs(ref[b].slack[c] - 1e-6) < 1e-9
         out, got = dense_and_mask(engine, batch)
-        check_against(ref, (out.cost, out.flags), got, f"{side} {eps:+g}")
+        RP.check_against(RULE, ref, (out.cost, out.flags), got, f"{side} {eps:+g}")
         assert bool(got[0][b, c] & BOUNDARY) == (eps < 0), (side, eps)
 
 
@@ -222,24 +131,10 @@ def test_dense_and_mask_replay_from_a_graph(engine, oracle):
     import torch
 
     batch, _ = R.case(oracle, "wide")
-    res = Resident(engine, batch)
+    res, graph, _, n0 = RP.graph_replay(engine, oracle, RULE, "wide")
     dev = res.db.dev
-    n0 = engine.get_option("boundary_launches")
-    res.pair(torch.cuda.current_stream(dev).cuda_stream)  # eager (also the warm-up of the capture)
-    first = res.fetch()
-    assert engine.get_option("boundary_launches") == n0 + 1
-    free = torch.cuda.mem_get_info()[0]
-    res.pair(torch.cuda.current_stream(dev).cuda_stream)
-    torch.cuda.synchronize(dev)
-    assert torch.cuda.mem_get_info()[0] == free  # enqueue only: a second call allocates nothing
-    side = torch.cuda.Stream(dev)
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph, stream=side):
-        res.pair(side.cuda_stream)  # a linear chain: the mask directly behind the dense call
-    torch.cuda.synchronize(dev)
-    assert engine.get_option("boundary_launches") == n0 + 3
     rng = np.random.default_rng(5)
-    seen = [first[1].tolist()]
+    seen = [res.fetch()[1].tolist()]
     for step in range(3):  # changed ego states in the same device arrays
         ego = batch.ego.copy()
         ego[:, 0] += rng.uniform(-3, 25, batch.B)
@@ -247,7 +142,7 @@ def test_dense_and_mask_replay_from_a_graph(engine, oracle):
         res.db.t["ego"].copy_(torch.from_numpy(ego))
         res.pair(torch.cuda.current_stream(dev).cuda_stream)
         eager = res.fetch()
-        res.flags.zero_(); res.bi.fill_(-9); res.bc.fill_(-9.0); res.nm.fill_(-9)
+        res.clobber()
         graph.replay()
         replay = res.fetch()
         for a, b in zip(eager, replay):
@@ -258,42 +153,26 @@ def test_dense_and_mask_replay_from_a_graph(engine, oracle):
             assert same_bits(a, b), step
         seen.append(replay[1].tolist())
     assert len({tuple(s) for s in seen}) > 1  # (the states did change the answer)
-    assert engine.get_option("boundary_launches") == n0 + 3 + 2 * 3  # eager device + host calls; a replay is not a call
-    with FrenetEngine(0) as other:  # a ctx that never asks pays nothing
-        o = other.plan_dense(batch, tables=True)
-        assert other.get_option("boundary_launches") == 0 and other.get_option("lattice_launches") == 1
-        assert not (o.flags & BOUNDARY).any()
+    assert RP.launches(engine, RULE) == n0 + 3 + 2 * 3  # eager device + host calls; a replay is not a call
+
+
+def test_a_ctx_that_never_asks_pays_nothing(oracle):
+    assert not (RP.never_asks(oracle, RULE, "wide").flags & BOUNDARY).any()
 
 
 # ---------------------------------------------------------------- 9: errors
 def test_errors(engine, oracle):
     batch, _ = R.case(oracle, "base")
-    out = engine.plan_dense(batch, tables=True)
-    p, fb = host_structs(batch)
-    B = batch.B
-    bi, bc, nm = np.empty(B, dtype=np.int32), np.empty(B), np.empty(B, dtype=np.int32)
-    flags = out.flags.copy()
-
-    def call(cor, params=p, cost=out.cost, fl=flags, idx=bi):
-        return engine._lib.fp_boundary_mask(engine._ctx, C.byref(params), C.byref(fb), C.byref(cor) if cor is not None else None, cost.ctypes.data if cost is not None else None,
-                                            fl.ctypes.data, idx.ctypes.data if idx is not None else None, bc.ctypes.data, nm.ctypes.data, _abi.FP_MEM_HOST, None)
-
     L, Rr = batch.bound_left.copy(), batch.bound_right.copy()
     good = lambda m=0.05, left=L, right=Rr: _abi.FpCorridor(left.ctypes.data if left is not None else None, right.ctypes.data, m)  # noqa: E731
-    assert call(good()) == 0
-    assert call(None) == -1
-    assert call(good(left=None)) == -1
-    assert call(good(m=-1.0)) == -1
+    call = RP.host_error_codes(engine, RULE, batch, [good(left=None), good(m=-1.0), good(m=float("nan")), good(m=float("inf"))])
+    n1, masked = RP.launches(engine, RULE), call.flags.copy()
     assert call(good(m=float("nan"))) == -1 and b"margin" in engine._lib.fp_last_error()
-    assert call(good(m=float("inf"))) == -1
-    assert call(good(), cost=None) == -1 and call(good(), idx=None) == -1
     bad = L.copy()
     bad[1, 7] = np.nan
     assert call(good(left=bad)) == -1 and b"NaN" in engine._lib.fp_last_error()
-    assert np.array_equal(flags, engine.boundary_mask(batch, out.cost, out.flags)[0])  # (a refused call wrote nothing)
-    big = _abi.FpParams.from_buffer_copy(p)
-    big.nd, big.nv, big.nt = 129, 128, 1  # C = 16 512 > FP_MAX_CAND
-    assert call(good(), params=big) == -4
+    assert RP.launches(engine, RULE) == n1 and np.array_equal(call.flags, masked)  # (a refused call launched and wrote nothing)
+    RP.device_error_codes(engine, RULE, batch, [dict(left=0), dict(right=0), dict(margin=-1.0), dict(margin=float("nan"))])
     # rows k >= nx[f] are ignored: a frame table with padding, NaN in the padded corridor rows
     padded = R.with_corridor(synth.make_batch(2, 5, 4, 3, 0, 20, False, R.SEED, n_knots=61), margin=0.05)
     NX = 64

@@ -10,102 +10,25 @@ import numpy as np
 import pytest
 
 import gaps_ref as R
+import rule_pass as RP
 from fiss_plus_planner_amd import _abi, synth
-from fiss_plus_planner_amd.engine import FrenetEngine, host_structs
+from rule_pass import same_bits
 
 pytestmark = pytest.mark.gpu
+RULE = "gaps"
 COLLISION = np.uint32(R.FLAG_COLLISION)
 INT32_MAX = 2**31 - 1
 POS_TOL = 1e-8  # the six ego numbers of a hand-over (tests/test_gpu_advance.py)
 
 
-def same_bits(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(np.ascontiguousarray(a).view(np.uint8), np.ascontiguousarray(b).view(np.uint8))
-
-
-def check_against(refs, dense, got, what, skip=None):
-    """got = (flags, best_idx, best_cost, n_close) of a gap call over the tables of `dense` (cost, flags)."""
-    flags, bi, bc, nc = got
-    cost_in, flags_in = dense
-    R.check_caps(refs, what)
-    for b, r in enumerate(refs):
-        if skip is not None and skip[b]:
-            assert bi[b] == -1 and np.isnan(bc[b]) and nc[b] == 0, (what, b)
-            assert np.array_equal(flags[b], flags_in[b]), (what, b)  # rows neither read nor written
-            continue
-        assert np.array_equal(flags_in[b], r.flags_in), (what, b)  # (the dense call's own parity with the oracle)
-        assert np.array_equal(flags[b] & ~COLLISION, flags_in[b] & ~COLLISION), (what, b)  # no other bit moves
-        assert np.array_equal(flags[b] & flags_in[b], flags_in[b]), (what, b)              # bits are only ever added
-        ok = ~r.undecided
-        assert np.array_equal(flags[b][ok], r.flags[ok]), (what, b, np.nonzero(flags[b] != r.flags)[0][:8].tolist())
-        assert nc[b] == np.count_nonzero(flags[b] != flags_in[b]), (what, b)  # violators are survivors: every one of them gains the bit
-        if not r.undecided.any():
-            assert nc[b] == r.n_close and bi[b] == r.best_idx, (what, b, int(bi[b]), r.best_idx, int(nc[b]), r.n_close)
-        if bi[b] >= 0:
-            assert same_bits(bc[b:b + 1], cost_in[b, bi[b]:bi[b] + 1]) and not (flags[b, bi[b]] & _abi.FLAG_INFEASIBLE), (what, b)
-        else:
-            assert np.isnan(bc[b]), (what, b)
-
-
-def dense_and_gaps(engine, batch, skip=None, **kw):
-    out = engine.plan_dense(batch, tables=True)
-    cost0, flags0 = out.cost.copy(), out.flags.copy()
-    got = engine.gap_mask(batch, out.cost, out.flags, skip=skip, **kw)
-    assert same_bits(out.cost, cost0) and np.array_equal(out.flags, flags0)  # the caller's tables are copies here; cost is never written
-    return out, got
-
-
-class Resident:
-    """A batch in device memory, the dense call and the gap pass behind it on one stream."""
-
-    def __init__(self, engine, batch, order=None, skip=None, poison=None):
-        import torch
-
-        from fiss_plus_planner_amd.device_batch import DeviceBatch
-
-        self.torch, self.engine, self.db, self.batch = torch, engine, DeviceBatch(batch, 0, order_hint=False), batch
-        db, B, Cn = self.db, batch.B, batch.C
-        self.fb = _abi.FpBatch.from_buffer_copy(db.fb)
-        if order is not None:
-            self.order = torch.from_numpy(np.ascontiguousarray(order, dtype=np.int32)).to(db.dev)
-            self.fb.launch_order = self.order.data_ptr()
-        if skip is not None:
-            self.skip = torch.from_numpy(np.ascontiguousarray(skip, dtype=np.int32)).to(db.dev)
-            self.fb.skip = self.skip.data_ptr()
-        self.bi0, self.bc0 = db.empty(B, torch.int32), db.empty(B, torch.float64)
-        self.bi, self.bc, self.nc = db.empty(B, torch.int32), db.empty(B, torch.float64), db.empty(B, torch.int32)
-        self.cost, self.flags = torch.zeros((B, Cn), dtype=torch.float64, device=db.dev), torch.zeros((B, Cn), dtype=torch.int32, device=db.dev)
-        if poison is not None:
-            self.flags[poison] = -1  # 0xFFFFFFFF: a row that WOULD count if it were read
-
-    def dense(self, stream=0):
-        db = self.db
-        self.engine.plan_dense_device(db.params, self.fb, self.bi0.data_ptr(), self.bc0.data_ptr(), cost_tbl=self.cost.data_ptr(), flag_tbl=self.flags.data_ptr(), stream=stream)
-
-    def gaps(self, stream=0, **kw):
-        b = self.batch
-        a = dict(follow=b.gap_follow, lead=b.gap_lead, first=b.gap_first, cost_tbl=self.cost.data_ptr(), flag_tbl=self.flags.data_ptr(), best_idx=self.bi.data_ptr(),
-                 best_cost=self.bc.data_ptr(), n_close=self.nc.data_ptr())
-        a.update(kw)
-        self.engine.gap_mask_device(self.db.params, self.fb, stream=stream, **a)
-
-    def pair(self, stream=0):
-        self.dense(stream)
-        self.gaps(stream)
-
-    def fetch(self):
-        self.torch.cuda.synchronize(self.db.dev)
-        return self.flags.cpu().numpy().view(np.uint32), self.bi.cpu().numpy(), self.bc.cpu().numpy(), self.nc.cpu().numpy()
+def dense_and_gaps(engine, batch):
+    return RP.dense_and_pass(engine, RULE, batch)
 
 
 # ---------------------------------------------------------------- parity
 @pytest.mark.parametrize("name", list(R.CASES))
 def test_parity_host(engine, oracle, name):
-    batch, refs = R.case(oracle, name)
-    n0 = engine.get_option("gap_launches")
-    out, got = dense_and_gaps(engine, batch)
-    assert engine.get_option("gap_launches") == n0 + 1  # one launch
-    check_against(refs, (out.cost, out.flags), got, name)
+    batch, refs, out, got = RP.host_parity(engine, oracle, RULE, name, skip_ego=2 if name in R.BASE_CASES else None)
     assert got[3].sum() > 0, name
     if name == "line_ends":  # past the end: M <= 1, nothing is checked, no bit
         assert (out.flags[3] >> 20 <= 1).all() and np.array_equal(got[0][3], out.flags[3]) and got[3][3] == 0
@@ -114,54 +37,15 @@ def test_parity_host(engine, oracle, name):
         assert got[1][b] == -1 and np.isnan(got[2][b]) and got[3][b] == refs[b].survivors
     if name == "lead":  # lag_follow = 0: the lead direction alone
         assert batch.gap_follow == 0 and got[3][0] == refs[0].n_close >= 1
-    if name in R.BASE_CASES:  # a skipped ego: -1 / NaN / 0, its rows untouched
-        skip = np.zeros(batch.B, dtype=np.int32)
-        skip[2] = 1
-        out.flags[2] = 0xFFFFFFFF  # (a row that WOULD count if it were read)
-        got = engine.gap_mask(batch, out.cost, out.flags, skip=skip)
-        assert (got[0][2] == 0xFFFFFFFF).all()
-        out.flags[2] = refs[2].flags_in
-        got[0][2] = refs[2].flags_in
-        check_against(refs, (out.cost, out.flags), got, name + " skip", skip)
 
 
 @pytest.mark.parametrize("name", ["base", "t_now", "chunks", "cull_only", "no_lds", "polygons"])
 def test_parity_device_with_order_and_skip(engine, oracle, name):
-    """HOST and DEVICE give the same bits, and so do two runs; a launch order and a skipped ego are honoured."""
-    batch, refs = R.case(oracle, name)
-    host_out, host = dense_and_gaps(engine, batch)
-    res = Resident(engine, batch)
-    res.pair()
-    plain = res.fetch()
-    check_against(refs, (host_out.cost, host_out.flags), plain, name + " device")
-    for a, b in zip(host, plain):
-        assert same_bits(a, b), name
-    res = Resident(engine, batch)
-    res.pair()
-    for a, b in zip(plain, res.fetch()):
-        assert same_bits(a, b), name  # two runs, identical bits
-    skip = np.zeros(batch.B, dtype=np.int32)
-    skip[batch.B - 1] = 1
-    res = Resident(engine, batch, order=np.arange(batch.B)[::-1], skip=skip, poison=batch.B - 1)
-    res.pair()
-    got = res.fetch()
-    assert (got[0][batch.B - 1] == 0xFFFFFFFF).all()  # the poisoned rows of the skipped ego come back untouched
-    tables = (host_out.cost.copy(), host_out.flags.copy())
-    tables[1][batch.B - 1] = 0xFFFFFFFF
-    check_against(refs, tables, got, name + " device, reversed order, skip", skip)
-    keep = skip == 0
-    for a, b in zip(got, plain):
-        assert same_bits(a[keep], b[keep])
+    RP.device_parity(engine, oracle, RULE, name, skip_ego=R.case(oracle, name)[0].B - 1)  # (the last ego: the chunks and table cases have two)
 
 
 def test_idempotence_and_rank(engine, oracle):
-    for name in ("base", "dense24"):
-        batch, _ = R.case(oracle, name)
-        out, first = dense_and_gaps(engine, batch)
-        second = engine.gap_mask(batch, out.cost, first[0])  # on the masked tables: the violators are no longer evaluated
-        assert first[3].sum() > 0 and (second[3] == 0).all()
-        for a, b in zip(first[:3], second[:3]):
-            assert same_bits(a, b), name
+    for batch, out, first in RP.idempotence(engine, oracle, RULE, ("base", "dense24")):  # (on the masked tables the violators are no longer evaluated: 0)
         flags, bi, bc, _ = first
         ri, rc, nf = engine.rank_feasible(batch, out.cost, flags, 4)  # plane 0 of the ranking on the masked tables
         assert np.array_equal(ri[0], bi) and same_bits(np.where(bi < 0, 0.0, rc[0]), np.where(bi < 0, 0.0, bc)) and np.array_equal(np.isnan(rc[0]), bi < 0)
@@ -181,9 +65,9 @@ def test_outcomes_that_follow_from_the_definition(engine, oracle):
                dict(first=INT32_MAX), dict(follow=1, lead=1)):
         flags, bi, bc, nc = engine.gap_mask(batch, out.cost, out.flags, **kw)
         assert np.array_equal(flags, out.flags) and np.array_equal(bi, out.best_idx) and same_bits(bc, out.best_cost) and (nc == 0).all(), kw
-    res = Resident(engine, batch)  # ... and through FP_MEM_DEVICE, and at check_stride 1 (another rounding of first to the grid)
+    res = RP.Resident(engine, RULE, batch)  # ... and through FP_MEM_DEVICE, and at check_stride 1 (another rounding of first to the grid)
     res.dense()
-    res.gaps(first=INT32_MAX)
+    res.call(first=INT32_MAX)
     got = res.fetch()
     assert np.array_equal(got[0], out.flags) and np.array_equal(got[1], out.best_idx) and same_bits(got[2], out.best_cost) and (got[3] == 0).all()
     dense1 = dataclasses.replace(batch, check_stride=1)
@@ -194,7 +78,7 @@ def test_outcomes_that_follow_from_the_definition(engine, oracle):
         assert np.array_equal(flags, o1.flags) and np.array_equal(bi, o1.best_idx) and same_bits(bc, o1.best_cost) and (nc == 0).all(), first
     # a `first` one step short of the last pose looks at that pose alone: the reference's verdicts
     last = [R.ego_gaps(oracle, batch, b, first=horizon - 2) for b in range(batch.B)]
-    check_against(last, (out.cost, out.flags), engine.gap_mask(batch, out.cost, out.flags, first=horizon - 2), "first = horizon - 2")
+    RP.check_against(RULE, last, (out.cost, out.flags), engine.gap_mask(batch, out.cost, out.flags, first=horizon - 2), "first = horizon - 2")
     for kw in (dict(follow=-1), dict(lead=_abi.FP_MAX_POINTS + 1), dict(first=0), dict(first=INT32_MAX + 1), dict(first=2**32 + 2), dict(follow=2**32 + 20)):
         with pytest.raises(ValueError):  # (a ctypes field would wrap these silently)
             engine.gap_mask(batch, out.cost, out.flags, **kw)
@@ -203,7 +87,7 @@ def test_outcomes_that_follow_from_the_definition(engine, oracle):
     for a, b in zip(full, more):
         assert same_bits(a, b)  # lags longer than the horizon
     want = [R.ego_gaps(oracle, batch, b, follow=horizon, lead=horizon) for b in range(batch.B)]
-    check_against(want, (out.cost, out.flags), full, "lag = horizon")
+    RP.check_against(RULE, want, (out.cost, out.flags), full, "lag = horizon")
     no_scene = dataclasses.replace(batch, scene_of=np.full(batch.B, -1))
     o2, got = dense_and_gaps(engine, no_scene)
     assert np.array_equal(got[0], o2.flags) and np.array_equal(got[1], o2.best_idx) and same_bits(got[2], o2.best_cost) and (got[3] == 0).all()
@@ -297,15 +181,12 @@ def test_plan_dense_audit_goes_with_top_k_and_with_no_rule(engine):
             engine.plan_dense(every, audit=True, top_k=3, **{name: True})
 
 
+def test_dense_and_gaps_replay_from_a_graph(engine, oracle):
+    RP.graph_replay(engine, oracle, RULE, "base")
+
+
 def test_a_ctx_that_never_asks_pays_nothing(oracle):
-    batch, refs = R.case(oracle, "base")
-    with FrenetEngine(0) as other:
-        o = other.plan_dense(batch, tables=True)
-        assert other.get_option("gap_launches") == 0 and other.get_option("lattice_launches") == 1
-        for b, r in enumerate(refs):  # the bits of the dense call alone: the oracle's tables
-            assert np.array_equal(o.flags[b], r.flags_in) and o.best_idx[b] == r.best_in
-        other.gap_mask(batch, o.cost, o.flags)
-        assert other.get_option("gap_launches") == 1 and other.get_option("lattice_launches") == 1 and other.get_option("clearance_launches") == 0
+    RP.never_asks(oracle, RULE, "base")
 
 
 # ---------------------------------------------------------------- the planner class
@@ -338,46 +219,21 @@ def test_planner_class(engine, oracle):
 # ---------------------------------------------------------------- errors
 def test_host_error_codes(engine, oracle):
     batch, _ = R.case(oracle, "base")
-    out = engine.plan_dense(batch, tables=True)
-    p, fb = host_structs(batch)
-    B = batch.B
-    bi, bc, nc = np.empty(B, dtype=np.int32), np.empty(B), np.empty(B, dtype=np.int32)
-    flags = out.flags.copy()
-
-    def call(g, params=p, cost=out.cost, fl=flags, idx=bi, best=bc):
-        ptr = lambda a: a.ctypes.data if a is not None else None  # noqa: E731
-        return engine._lib.fp_gap_mask(engine._ctx, C.byref(params), C.byref(fb), C.byref(g) if g is not None else None, ptr(cost), ptr(fl), ptr(idx), ptr(best),
-                                       nc.ctypes.data, _abi.FP_MEM_HOST, None)
 
     def good(follow=20, lead=10, first=2):
         return _abi.FpTimeGap(follow, lead, first, 0)
 
-    n0 = engine.get_option("gap_launches")
-    for g in (None, good(follow=-1), good(lead=-1), good(follow=_abi.FP_MAX_POINTS + 1), good(lead=_abi.FP_MAX_POINTS + 1), good(first=0), good(first=-3)):
-        assert call(g) == -1
-    assert call(good(), cost=None) == -1 and call(good(), fl=None) == -1 and call(good(), idx=None) == -1 and call(good(), best=None) == -1
-    big = _abi.FpParams.from_buffer_copy(p)
-    big.nd, big.nv, big.nt = 129, 128, 1  # C = 16 512 > FP_MAX_CAND
-    assert call(good(), params=big) == -4
-    assert engine.get_option("gap_launches") == n0 and np.array_equal(flags, out.flags)  # (a refused call launched and wrote nothing)
-    assert call(good()) == 0 and engine.get_option("gap_launches") == n0 + 1
-    want = engine.gap_mask(batch, out.cost, out.flags)
-    assert np.array_equal(flags, want[0]) and np.array_equal(bi, want[1]) and np.array_equal(nc, want[3])
+    RP.host_error_codes(engine, RULE, batch, [good(follow=-1), good(lead=-1), good(follow=_abi.FP_MAX_POINTS + 1), good(lead=_abi.FP_MAX_POINTS + 1), good(first=0),
+                                              good(first=-3)])
 
 
 def test_device_error_codes(engine, oracle):
     batch, _ = R.case(oracle, "base")
-    res = Resident(engine, batch)
-    res.pair()
+    res, n = RP.device_error_codes(engine, RULE, batch, [])
     first = res.fetch()
-    n0 = engine.get_option("gap_launches")
-    for kw in (dict(cost_tbl=0), dict(flag_tbl=0), dict(best_idx=0), dict(best_cost=0)):
-        with pytest.raises(_abi.FrenetGpuError) as err:
-            res.gaps(**kw)
-        assert err.value.code == -1, kw
     for kw in (dict(follow=-1), dict(lead=-2), dict(follow=_abi.FP_MAX_POINTS + 1), dict(lead=_abi.FP_MAX_POINTS + 1), dict(first=0), dict(first=2**31)):
         with pytest.raises(ValueError):  # the binding refuses what the struct cannot hold or the library would refuse
-            res.gaps(**kw)
+            res.call(**kw)
     for g in (_abi.FpTimeGap(-1, 0, 1, 0), _abi.FpTimeGap(0, -2, 1, 0), _abi.FpTimeGap(_abi.FP_MAX_POINTS + 1, 0, 1, 0), _abi.FpTimeGap(0, _abi.FP_MAX_POINTS + 1, 1, 0),
               _abi.FpTimeGap(20, 10, 0, 0), _abi.FpTimeGap(20, 10, -5, 0)):  # ... and so does the library itself
         rc = engine._lib.fp_gap_mask(engine._ctx, C.byref(res.db.params), C.byref(res.fb), C.byref(g), res.cost.data_ptr(), res.flags.data_ptr(), res.bi.data_ptr(),
@@ -386,29 +242,12 @@ def test_device_error_codes(engine, oracle):
     rc = engine._lib.fp_gap_mask(engine._ctx, C.byref(res.db.params), C.byref(res.fb), None, res.cost.data_ptr(), res.flags.data_ptr(), res.bi.data_ptr(),
                                  res.bc.data_ptr(), None, _abi.FP_MEM_DEVICE, None)
     assert rc == -1
-    big = _abi.FpParams.from_buffer_copy(res.db.params)
-    big.nd, big.nv, big.nt = 129, 128, 1
-    g = _abi.FpTimeGap(20, 10, 2, 0)
-    rc = engine._lib.fp_gap_mask(engine._ctx, C.byref(big), C.byref(res.fb), C.byref(g), res.cost.data_ptr(), res.flags.data_ptr(), res.bi.data_ptr(),
-                                 res.bc.data_ptr(), None, _abi.FP_MEM_DEVICE, None)
-    assert rc == -4
-    assert engine.get_option("gap_launches") == n0
-    res.gaps(n_close=0)  # n_close is optional; on the masked tables nothing changes
-    again = res.fetch()
-    for a, b in zip(first[:3], again[:3]):
+    assert RP.launches(engine, RULE) == n  # (none of them launched or wrote)
+    for a, b in zip(first, res.fetch()):
         assert same_bits(a, b)
-    assert engine.get_option("gap_launches") == n0 + 1
 
 
 # ---------------------------------------------------------------- the closed loop
-def run_loop(engine, batch, cycles, graph, rules=("gaps",)):
-    from fiss_plus_planner_amd.device_batch import ClosedLoopRunner, DeviceBatch
-
-    runner = ClosedLoopRunner(engine, DeviceBatch(batch, 0), np.full((batch.B, 2), 1e9), rules=rules)
-    out = runner.run_graph(cycles, record=True) if graph else runner.run(cycles, record=True)
-    return runner, out
-
-
 def logged_ego(rows):
     return rows[:, [_abi.LOG_S, _abi.LOG_VELOCITY, _abi.LOG_S_DD, _abi.LOG_D, _abi.LOG_VELOCITY_Y, _abi.LOG_D_DD]]
 
@@ -421,7 +260,7 @@ def test_closed_loop_keeps_the_gap(engine, oracle, graph):
     batch, rows = R.loop_case(oracle)
     assert not any(r.undecided for r in rows)  # (state-exact on every cycle: none is undecided)
     n0 = {k: engine.get_option(k) for k in ("gap_launches", "lattice_launches", "gate_launches")}
-    runner, out = run_loop(engine, batch, cycles, graph)
+    runner, out = RP.run_loop(engine, batch, cycles, graph, rules=(RULE,))
     calls = 2 if graph else cycles  # (a graph: the warm-up and the capture; a replay is not a call)
     assert engine.get_option("gap_launches") == n0["gap_launches"] + calls and engine.get_option("gate_launches") == n0["gate_launches"]
     log = out.log
@@ -442,21 +281,21 @@ def test_closed_loop_without_the_rule_closes_in(engine, oracle):
     cycles = R.LOOP_CYCLES
     batch, free = R.loop_case(oracle, gaps=False)
     n0 = engine.get_option("gap_launches")
-    runner, out = run_loop(engine, batch, cycles, graph=False, rules=())
+    runner, out = RP.run_loop(engine, batch, cycles, graph=False, rules=())
     assert engine.get_option("gap_launches") == n0 and not hasattr(runner, "cost_tbl")
     got = out.log.rows[0, :cycles]
     assert np.array_equal(got[:, _abi.LOG_BEST_IDX], [r.best_idx for r in free])
     steps = np.arange(1, cycles + 1)
     came = R.bumper_distance(batch, got[:, _abi.LOG_S], steps)
-    kept = R.bumper_distance(batch, run_loop(engine, batch, cycles, graph=False)[1].log.rows[0, :cycles, _abi.LOG_S], steps)
+    kept = R.bumper_distance(batch, RP.run_loop(engine, batch, cycles, graph=False, rules=(RULE,))[1].log.rows[0, :cycles, _abi.LOG_S], steps)
     assert came < batch.veh_l < R.LOOP_FOLLOW * batch.tick_t * R.LEAD_V < kept, (came, kept)
 
 
 def test_closed_loop_with_all_four_rules_replays_from_a_graph(engine, oracle):
     batch, cycles = full_batch(), 4
-    runner, out = run_loop(engine, batch, cycles, graph=False, rules=("gaps", "boundary", "envelope", "gates"))
+    runner, out = RP.run_loop(engine, batch, cycles, graph=False, rules=("gaps", "boundary", "envelope", "gates"))
     assert runner.rules == ("envelope", "gates", "boundary", "gaps")
-    graphed = run_loop(engine, batch, cycles, graph=True, rules=runner.rules)[1]
+    graphed = RP.run_loop(engine, batch, cycles, graph=True, rules=runner.rules)[1]
     assert same_bits(out.ego, graphed.ego) and np.array_equal(out.t_now, graphed.t_now) and np.array_equal(out.done, graphed.done)
     assert np.array_equal(out.cycles, graphed.cycles) and same_bits(out.cart, graphed.cart)
     for b in range(batch.B):

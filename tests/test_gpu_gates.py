@@ -10,158 +10,38 @@ import numpy as np
 import pytest
 
 import gates_ref as R
+import rule_pass as RP
 from fiss_plus_planner_amd import _abi, synth
-from fiss_plus_planner_amd.engine import FrenetEngine, host_structs
+from rule_pass import same_bits
 
 pytestmark = pytest.mark.gpu
+RULE = "gates"
 OPEN_AT, LOOP_CYCLES, check_loop_invariants = R.OPEN_STEPS, R.LOOP_CYCLES, R.check_loop_invariants
 SPEED = np.uint32(R.FLAG_SPEED)
 POS_TOL = 1e-8  # the six ego numbers and x, y of a hand-over (tests/test_gpu_advance.py)
 
 
-def same_bits(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(np.ascontiguousarray(a).view(np.uint8), np.ascontiguousarray(b).view(np.uint8))
-
-
-def check_against(refs, dense, got, what, skip=None):
-    """got = (flags, best_idx, best_cost, n_gated) of a gate call over the tables of `dense` (cost, flags)."""
-    flags, bi, bc, ng = got
-    cost_in, flags_in = dense
-    R.check_caps(refs, what)
-    for b, r in enumerate(refs):
-        if skip is not None and skip[b]:
-            assert bi[b] == -1 and np.isnan(bc[b]) and ng[b] == 0, (what, b)
-            assert np.array_equal(flags[b], flags_in[b]), (what, b)  # rows neither read nor written
-            continue
-        assert np.array_equal(flags_in[b], r.flags_in), (what, b)  # (the dense call's own parity with the oracle)
-        assert np.array_equal(flags[b] & ~SPEED, flags_in[b] & ~SPEED), (what, b)
-        assert np.array_equal(flags[b] & flags_in[b], flags_in[b]), (what, b)  # bits are only ever added
-        ok = ~r.undecided
-        assert np.array_equal(flags[b][ok], r.flags[ok]), (what, b, np.nonzero(flags[b] != r.flags)[0][:8].tolist())
-        added = np.count_nonzero(flags[b] != flags_in[b])
-        assert added <= ng[b] <= np.count_nonzero(flags[b] & SPEED), (what, b)  # (a violating candidate may have carried the bit already)
-        if not r.undecided.any():
-            assert ng[b] == r.n_gated and bi[b] == r.best_idx, (what, b, int(bi[b]), r.best_idx, int(ng[b]), r.n_gated)
-        if bi[b] >= 0:
-            assert same_bits(bc[b:b + 1], cost_in[b, bi[b]:bi[b] + 1]) and not (flags[b, bi[b]] & _abi.FLAG_INFEASIBLE), (what, b)
-        else:
-            assert np.isnan(bc[b]), (what, b)
-
-
-def dense_of(engine, batch):
-    """The dense call's tables (a host planning call refuses a negative t_now; without obstacles its tables do not depend on t_now)."""
-    assert batch.n_obs == 0
-    return engine.plan_dense(dataclasses.replace(batch, t_now=np.maximum(batch.t_now, 0)), tables=True)
-
-
-def dense_and_gates(engine, batch, skip=None):
-    out = dense_of(engine, batch)
-    cost0, flags0 = out.cost.copy(), out.flags.copy()
-    got = engine.gate_mask(batch, out.cost, out.flags, skip=skip)
-    assert same_bits(out.cost, cost0) and np.array_equal(out.flags, flags0)  # the caller's tables are copies here; cost is never written
-    return out, got
-
-
-class Resident:
-    """A batch and its gates in device memory, the dense call and the gate pass behind it on one stream."""
-
-    def __init__(self, engine, batch, order=None, skip=None, poison=None):
-        import torch
-
-        from fiss_plus_planner_amd.device_batch import DeviceBatch
-
-        self.torch, self.engine, self.db, self.batch = torch, engine, DeviceBatch(batch, 0, order_hint=False), batch
-        db, B, Cn = self.db, batch.B, batch.C
-        self.fb = _abi.FpBatch.from_buffer_copy(db.fb)
-        if order is not None:
-            self.order = torch.from_numpy(np.ascontiguousarray(order, dtype=np.int32)).to(db.dev)
-            self.fb.launch_order = self.order.data_ptr()
-        if skip is not None:
-            self.skip = torch.from_numpy(np.ascontiguousarray(skip, dtype=np.int32)).to(db.dev)
-            self.fb.skip = self.skip.data_ptr()
-        self.bi0, self.bc0 = db.empty(B, torch.int32), db.empty(B, torch.float64)
-        self.bi, self.bc, self.ng = db.empty(B, torch.int32), db.empty(B, torch.float64), db.empty(B, torch.int32)
-        self.cost, self.flags = torch.zeros((B, Cn), dtype=torch.float64, device=db.dev), torch.zeros((B, Cn), dtype=torch.int32, device=db.dev)
-        if poison is not None:
-            self.flags[poison] = -1  # 0xFFFFFFFF: a row that WOULD count (M = 4095, every bit set) if it were read
-
-    def dense(self, stream=0):
-        db = self.db
-        self.engine.plan_dense_device(db.params, self.fb, self.bi0.data_ptr(), self.bc0.data_ptr(), cost_tbl=self.cost.data_ptr(), flag_tbl=self.flags.data_ptr(), stream=stream)
-
-    def gates(self, stream=0, **kw):
-        db, b = self.db, self.batch
-        a = dict(gate_s=db.t["gate_s"].data_ptr(), closed=db.t["gate_closed"].data_ptr(), gate_stride=b.gate_s.shape[1], T_gate=b.gate_closed.shape[1],
-                 front=b.gate_front, max_decel=b.gate_max_decel, cost_tbl=self.cost.data_ptr(), flag_tbl=self.flags.data_ptr(), best_idx=self.bi.data_ptr(),
-                 best_cost=self.bc.data_ptr(), n_gated=self.ng.data_ptr())
-        a.update(kw)
-        self.engine.gate_mask_device(db.params, self.fb, stream=stream, **a)
-
-    def pair(self, stream=0):
-        self.dense(stream)
-        self.gates(stream)
-
-    def fetch(self):
-        self.torch.cuda.synchronize(self.db.dev)
-        return self.flags.cpu().numpy().view(np.uint32), self.bi.cpu().numpy(), self.bc.cpu().numpy(), self.ng.cpu().numpy()
+def dense_and_gates(engine, batch):
+    return RP.dense_and_pass(engine, RULE, batch)
 
 
 # ---------------------------------------------------------------- parity
 @pytest.mark.parametrize("name", list(R.CASES))
 def test_parity_host(engine, oracle, name):
-    batch, refs = R.case(oracle, name)
-    n0 = engine.get_option("gate_launches")
-    out, got = dense_and_gates(engine, batch)
-    assert engine.get_option("gate_launches") == n0 + 1  # one launch
-    check_against(refs, (out.cost, out.flags), got, name)
+    batch, refs, out, got = RP.host_parity(engine, oracle, RULE, name, skip_ego=2 if name in R.BASE_CASES else None)
     if name == "open":  # no bit closed: no bit may change, the winner is the dense call's
         assert np.array_equal(got[0], out.flags) and np.array_equal(got[1], out.best_idx) and same_bits(got[2], out.best_cost) and (got[3] == 0).all()
     if name == "line_ends":  # past the end: M <= 1, nothing is checked, no bit
         assert (out.flags[3] >> 20 <= 1).all() and np.array_equal(got[0][3], out.flags[3]) and got[3][3] == 0
-    if name in R.BASE_CASES:  # a skipped ego: -1 / NaN / 0, its rows untouched
-        skip = np.zeros(batch.B, dtype=np.int32)
-        skip[2] = 1
-        out.flags[2] = 0xFFFFFFFF  # (a row that WOULD count if it were read)
-        got = engine.gate_mask(batch, out.cost, out.flags, skip=skip)
-        assert (got[0][2] == 0xFFFFFFFF).all()
-        out.flags[2] = refs[2].flags_in
-        got[0][2] = refs[2].flags_in
-        check_against(refs, (out.cost, out.flags), got, name + " skip", skip)
 
 
 @pytest.mark.parametrize("name", ["base", "t_now", "tick005", "stride32"])
 def test_parity_device_with_order_and_skip(engine, oracle, name):
-    """HOST and DEVICE give the same bits; a launch order and a skipped ego are honoured."""
-    batch, refs = R.case(oracle, name)
-    host_out, host = dense_and_gates(engine, batch)
-    res = Resident(engine, batch)
-    res.pair()
-    plain = res.fetch()
-    check_against(refs, (host_out.cost, host_out.flags), plain, name + " device")
-    for a, b in zip(host, plain):
-        assert same_bits(a, b), name
-    skip = np.zeros(batch.B, dtype=np.int32)
-    skip[2] = 1
-    res = Resident(engine, batch, order=np.arange(batch.B)[::-1], skip=skip, poison=2)
-    res.pair()
-    got = res.fetch()
-    assert (got[0][2] == 0xFFFFFFFF).all()  # the poisoned rows of the skipped ego come back untouched
-    tables = (host_out.cost.copy(), host_out.flags.copy())
-    tables[1][2] = 0xFFFFFFFF
-    check_against(refs, tables, got, name + " device, reversed order, skip", skip)
-    keep = skip == 0
-    for a, b in zip(got, plain):
-        assert same_bits(a[keep], b[keep])
+    RP.device_parity(engine, oracle, RULE, name)
 
 
 def test_idempotence_and_rank(engine, oracle):
-    for name in ("base", "waiver"):
-        batch, _ = R.case(oracle, name)
-        out, first = dense_and_gates(engine, batch)
-        second = engine.gate_mask(batch, out.cost, first[0])
-        for a, b in zip(first, second):
-            assert same_bits(a, b), name
-        assert first[3].sum() > 0
+    for batch, out, first in RP.idempotence(engine, oracle, RULE, ("base", "waiver")):
         flags, bi, bc, _ = first
         ri, rc, nf = engine.rank_feasible(batch, out.cost, flags, 4)  # plane 0 of the ranking on the masked tables
         assert np.array_equal(ri[0], bi) and same_bits(np.where(bi < 0, 0.0, rc[0]), np.where(bi < 0, 0.0, bc)) and np.array_equal(np.isnan(rc[0]), bi < 0)
@@ -249,52 +129,18 @@ def test_envelope_gates_and_boundary_compose(engine, oracle):
 
 # ---------------------------------------------------------------- capture
 def test_dense_and_gates_replay_from_a_graph(engine, oracle):
-    import torch
-
-    batch, refs = R.case(oracle, "t_now")
-    res = Resident(engine, batch)
-    dev = res.db.dev
-    n0 = engine.get_option("gate_launches")
-    res.pair(torch.cuda.current_stream(dev).cuda_stream)  # eager (also the warm-up of the capture)
-    eager = res.fetch()
-    assert engine.get_option("gate_launches") == n0 + 1
-    free = torch.cuda.mem_get_info()[0]
-    res.pair(torch.cuda.current_stream(dev).cuda_stream)
-    torch.cuda.synchronize(dev)
-    assert torch.cuda.mem_get_info()[0] == free  # enqueue only: a second call allocates nothing
-    side = torch.cuda.Stream(dev)
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph, stream=side):
-        res.pair(side.cuda_stream)  # a linear chain on one stream: the gates directly behind the dense call
-    torch.cuda.synchronize(dev)
-    assert engine.get_option("gate_launches") == n0 + 3
-    for step in range(2):
-        res.flags.zero_(); res.bi.fill_(-9); res.bc.fill_(-9.0); res.ng.fill_(-9)
-        graph.replay()
-        replay = res.fetch()
-        for a, b in zip(eager, replay):
-            assert same_bits(a, b), step
-    host = engine.plan_dense(batch, tables=True)
-    check_against(refs, (host.cost, host.flags), replay, "replay")
+    res, graph, host, n0 = RP.graph_replay(engine, oracle, RULE, "t_now")
     # t_now is read when the kernel runs: the replayed graph follows the clocks the base case has
     res.db.t["t_now"].zero_()
     graph.replay()
     _, base = R.case(oracle, "base")
-    check_against(base, (host.cost, host.flags), res.fetch(), "replay on another clock")
-    assert engine.get_option("gate_launches") == n0 + 3  # a replay is not a call
+    RP.check_against(RULE, base, (host.cost, host.flags), res.fetch(), "replay on another clock")
+    assert RP.launches(engine, RULE) == n0 + 3  # a replay is not a call
 
 
 # ---------------------------------------------------------------- off unless called
 def test_a_ctx_that_never_asks_pays_nothing(oracle):
-    batch, refs = R.case(oracle, "base")
-    with FrenetEngine(0) as other:
-        o = other.plan_dense(batch, tables=True)
-        assert other.get_option("gate_launches") == 0 and other.get_option("lattice_launches") == 1
-        assert other.get_option("envelope_launches") == 0 and other.get_option("boundary_launches") == 0 and other.get_option("rank_launches") == 0
-        for b, r in enumerate(refs):  # the bits of the dense call alone: the oracle's tables
-            assert np.array_equal(o.flags[b], r.flags_in) and o.best_idx[b] == r.best_in
-        other.gate_mask(batch, o.cost, o.flags)
-        assert other.get_option("gate_launches") == 1 and other.get_option("lattice_launches") == 1 and other.get_option("envelope_launches") == 0
+    RP.never_asks(oracle, RULE, "base")
 
 
 # ---------------------------------------------------------------- the planner class
@@ -323,75 +169,28 @@ def test_planner_class(engine, oracle):
 # ---------------------------------------------------------------- errors
 def test_host_error_codes(engine, oracle):
     batch, _ = R.case(oracle, "base")
-    out = engine.plan_dense(batch, tables=True)
-    p, fb = host_structs(batch)
-    B = batch.B
-    bi, bc, ng = np.empty(B, dtype=np.int32), np.empty(B), np.empty(B, dtype=np.int32)
-    flags = out.flags.copy()
-
-    def call(g, params=p, cost=out.cost, fl=flags, idx=bi, best=bc):
-        ptr = lambda a: a.ctypes.data if a is not None else None  # noqa: E731
-        return engine._lib.fp_gate_mask(engine._ctx, C.byref(params), C.byref(fb), C.byref(g) if g is not None else None, ptr(cost), ptr(fl), ptr(idx), ptr(best),
-                                        ng.ctypes.data, _abi.FP_MEM_HOST, None)
 
     def good(s=batch.gate_s, c=batch.gate_closed, stride=2, T=R.T_GATE, front=2.0, decel=0.0):
         return _abi.FpGates(s.ctypes.data if s is not None else None, c.ctypes.data if c is not None else None, stride, T, front, decel)
 
-    n0 = engine.get_option("gate_launches")
-    for g in (None, good(s=None), good(c=None), good(stride=0), good(stride=33), good(stride=-1), good(T=0), good(T=-3), good(front=-1.0), good(front=float("nan")),
-              good(front=float("inf")), good(decel=-0.1), good(decel=float("nan")), good(decel=float("inf"))):
-        assert call(g) == -1
-    assert call(good(), cost=None) == -1 and call(good(), fl=None) == -1 and call(good(), idx=None) == -1 and call(good(), best=None) == -1
-    big = _abi.FpParams.from_buffer_copy(p)
-    big.nd, big.nv, big.nt = 129, 128, 1  # C = 16 512 > FP_MAX_CAND
-    assert call(good(), params=big) == -4
-    assert engine.get_option("gate_launches") == n0 and np.array_equal(flags, out.flags)  # (a refused call launched and wrote nothing)
-    assert call(good(front=batch.gate_front)) == 0 and engine.get_option("gate_launches") == n0 + 1
-    want = engine.gate_mask(batch, out.cost, out.flags)
-    assert np.array_equal(flags, want[0]) and np.array_equal(bi, want[1]) and np.array_equal(ng, want[3])
+    RP.host_error_codes(engine, RULE, batch, [good(s=None), good(c=None), good(stride=0), good(stride=33), good(stride=-1), good(T=0), good(T=-3), good(front=-1.0),
+                                              good(front=float("nan")), good(front=float("inf")), good(decel=-0.1), good(decel=float("nan")), good(decel=float("inf"))])
 
 
 def test_device_error_codes(engine, oracle):
     batch, _ = R.case(oracle, "base")
-    res = Resident(engine, batch)
-    res.pair()
-    first = res.fetch()
-    n0 = engine.get_option("gate_launches")
-    for kw in (dict(gate_s=0), dict(closed=0), dict(cost_tbl=0), dict(flag_tbl=0), dict(best_idx=0), dict(best_cost=0), dict(gate_stride=0), dict(gate_stride=33),
-               dict(T_gate=0), dict(front=-1.0), dict(front=float("nan")), dict(max_decel=-1.0), dict(max_decel=float("inf"))):
-        with pytest.raises(_abi.FrenetGpuError) as err:
-            res.gates(**kw)
-        assert err.value.code == -1, kw
-    big = _abi.FpParams.from_buffer_copy(res.db.params)
-    big.nd, big.nv, big.nt = 129, 128, 1
-    g = _abi.FpGates(res.db.t["gate_s"].data_ptr(), res.db.t["gate_closed"].data_ptr(), 2, R.T_GATE, 1.0, 0.0)
-    rc = engine._lib.fp_gate_mask(engine._ctx, C.byref(big), C.byref(res.fb), C.byref(g), res.cost.data_ptr(), res.flags.data_ptr(), res.bi.data_ptr(),
-                                  res.bc.data_ptr(), None, _abi.FP_MEM_DEVICE, None)
-    assert rc == -4
-    assert engine.get_option("gate_launches") == n0
-    res.gates(n_gated=0)  # n_gated is optional
-    again = res.fetch()
-    for a, b in zip(first, again):
-        assert same_bits(a, b)
-    assert engine.get_option("gate_launches") == n0 + 1
+    RP.device_error_codes(engine, RULE, batch, [dict(gate_s=0), dict(closed=0), dict(gate_stride=0), dict(gate_stride=33), dict(T_gate=0), dict(front=-1.0),
+                                                dict(front=float("nan")), dict(max_decel=-1.0), dict(max_decel=float("inf"))])
 
 
 # ---------------------------------------------------------------- the closed loop
-def run_loop(engine, batch, cycles, graph, rules=("gates",)):
-    from fiss_plus_planner_amd.device_batch import ClosedLoopRunner, DeviceBatch
-
-    runner = ClosedLoopRunner(engine, DeviceBatch(batch, 0), np.full((batch.B, 2), 1e9), rules=rules)
-    out = runner.run_graph(cycles, record=True) if graph else runner.run(cycles, record=True)
-    return runner, out
-
-
 @pytest.mark.parametrize("graph", [False, True], ids=["eager", "graph"])
 def test_closed_loop_waits_for_the_gate(engine, oracle, graph):
     """The scenario of tests/test_gates_cpu.py, four egos with four opening steps: every cycle's winner is the reference loop's, the
     logged state its state, and the two invariants hold on the logged rows."""
     batch, loops = R.loop_case(oracle, OPEN_AT, LOOP_CYCLES)
     n0 = {k: engine.get_option(k) for k in ("gate_launches", "lattice_launches", "looplog_launches", "envelope_launches", "boundary_launches")}
-    runner, out = run_loop(engine, batch, LOOP_CYCLES, graph)
+    runner, out = RP.run_loop(engine, batch, LOOP_CYCLES, graph, rules=(RULE,))
     calls = 2 if graph else LOOP_CYCLES  # (a graph: the warm-up and the capture; a replay is not a call)
     assert engine.get_option("gate_launches") == n0["gate_launches"] + calls and engine.get_option("looplog_launches") == n0["looplog_launches"] + calls
     assert engine.get_option("envelope_launches") == n0["envelope_launches"] and engine.get_option("boundary_launches") == n0["boundary_launches"]
@@ -417,7 +216,7 @@ def test_closed_loop_without_rules_runs_the_light(engine, oracle):
     cycles = 70
     batch, free = R.loop_case(oracle, OPEN_AT, cycles, gates=False)
     n0 = engine.get_option("gate_launches")
-    runner, out = run_loop(engine, batch, cycles, graph=False, rules=())
+    runner, out = RP.run_loop(engine, batch, cycles, graph=False, rules=())
     assert engine.get_option("gate_launches") == n0 and not hasattr(runner, "cost_tbl")
     for b in (0, 2, 3):
         got = out.log.rows[b, :cycles]
@@ -435,9 +234,9 @@ def test_closed_loop_with_every_rule_equals_the_calls_made_one_by_one(engine, or
     from fiss_plus_planner_amd.device_batch import DeviceBatch
 
     batch, cycles = full_batch(), 4
-    runner, out = run_loop(engine, batch, cycles, graph=False, rules=("boundary", "envelope", "gates"))
+    runner, out = RP.run_loop(engine, batch, cycles, graph=False, rules=("boundary", "envelope", "gates"))
     assert runner.rules == ("envelope", "gates", "boundary")
-    graphed = run_loop(engine, batch, cycles, graph=True, rules=runner.rules)[1]
+    graphed = RP.run_loop(engine, batch, cycles, graph=True, rules=runner.rules)[1]
     # the same cycle by hand on a fresh resident batch
     db = DeviceBatch(batch, 0)
     B, Cn, dev = batch.B, batch.C, db.dev

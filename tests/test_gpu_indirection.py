@@ -25,14 +25,11 @@ import gaps_ref as PR
 import gates_ref as GR
 import indirection as IX
 import margins_ref as MR
+import rule_pass as RP
 import rules_eval_ref as R
-import test_gpu_boundary as TB
 import test_gpu_clearance as TC
-import test_gpu_envelope as TE
 import test_gpu_fallback as TF
 import test_gpu_fiss_rules as TFR
-import test_gpu_gaps as TP
-import test_gpu_gates as TG
 import test_gpu_margins as TM
 import test_gpu_rules_eval as TR
 from fiss_plus_planner_amd import rules
@@ -40,8 +37,7 @@ from fiss_plus_planner_amd.fallback import FallbackStop
 
 pytestmark = pytest.mark.gpu
 NAMES = R.RULE_NAMES
-PASSES = {"envelope": (ER, TE, "batch_envelope", "speed_envelope"), "gates": (GR, TG, "batch_gates", "gate_mask"),
-          "boundary": (BR, TB, "batch_mask", "boundary_mask"), "gaps": (PR, TP, "batch_gaps", "gap_mask")}
+PASSES = {"envelope": (ER, "batch_envelope"), "gates": (GR, "batch_gates"), "boundary": (BR, "batch_mask"), "gaps": (PR, "batch_gaps")}
 LOOP_CYCLES = 6
 SHAPES = pytest.mark.parametrize("shapes", [False, True], ids=["rectangles", "polygon columns"])  # (the fixture with_shapes() went over first)
 
@@ -90,12 +86,12 @@ def test_twins_dense_chain_and_fallback_host(engine, shapes):
 @SHAPES
 @pytest.mark.parametrize("rule", list(PASSES))
 def test_twins_one_pass_host_and_device(engine, rule, shapes):
-    _, suite, _, method = PASSES[rule]
+    method = RP.PASSES[rule].method
 
     def run(b):
         dense = engine.plan_dense(b, tables=True)
         host = getattr(engine, method)(b, dense.cost, dense.flags)
-        res = suite.Resident(engine, b)
+        res = RP.Resident(engine, rule, b)
         res.pair()
         dev = res.fetch()
         for h, d in zip(host, dev):
@@ -197,7 +193,7 @@ def test_twins_clearance_rescoring_host_and_device(engine, shapes):
         n0 = engine.get_option("clearance_launches")
         h = engine.plan_dense(b, tables=True, winner=True)
         assert engine.get_option("clearance_launches") == n0 + 1
-        res = TP.Resident(engine, b)
+        res = RP.Resident(engine, "gaps", b)
         res.dense()
         flags = res.fetch()[0]
         assert same_bits(flags, h.flags) and same_bits(res.cost.cpu().numpy(), h.cost) and same_bits(res.bi0.cpu().numpy(), h.best_idx)
@@ -237,13 +233,13 @@ def ref_words(oracle, batch, es):
 
 @pytest.mark.parametrize("rule", list(PASSES))
 def test_one_pass_against_its_reference(engine, oracle, rule):
-    mod, suite, fn, method = PASSES[rule]
+    (mod, fn), method = PASSES[rule], RP.PASSES[rule].method
     for sharing, nx, shapes in ((2, 0, False), (0, 1, False)) + (((2, 0, True),) if rule == "gaps" else ()):
         batch = IX.rules_batch(sharing, nx, shapes)
         refs = getattr(mod, fn)(oracle, batch)
         dense = engine.plan_dense(batch, tables=True)
         got = getattr(engine, method)(batch, dense.cost, dense.flags)
-        suite.check_against(refs, (dense.cost, dense.flags), got, f"{rule}, sharing {sharing}, nx list {nx}, polygon columns {shapes}")
+        RP.check_against(rule, refs, (dense.cost, dense.flags), got, f"{rule}, sharing {sharing}, nx list {nx}, polygon columns {shapes}")
         assert got[3].sum() > 0, rule
 
 
