@@ -381,6 +381,9 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
     // rectangle instances only: the run-time-shape instances have no scalar register to spare and came out larger with them, and the two
     // shaped polygon instances (80 VGPRs, all in use) spill a VGPR with them; both keep the statements they had.
     constexpr bool kCut = kShape && !POLY;
+    // The argmin by one wavefront (ARGMIN below): every instance comes out smaller with it but the shaped polygon instance without a
+    // window (80 VGPRs, all in use), which spills two VGPRs with it and keeps the statements it had.
+    constexpr bool kArgWave = !(kShape && POLY && !WIN);
     // the same number in a scalar register (kCut): a phase that belongs to some of the wavefronts is entered on a scalar
     // compare and a branch - on `wave` every wavefront pays the vector compare and the EXEC round trip of a phase that is not its own
     const int wave_s = kCut ? __builtin_amdgcn_readfirstlane(wave) : wave;
@@ -538,7 +541,8 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
         const double* gk = bt.knots + (size_t)f * NX;
         const double* gc = bt.coef + (size_t)f * 8 * NX;
         // [0]: counter of the item list; [1]: kCut instances: the ends of d_samples, packed (see the cost sums); [2]: slices whose lon profiles need the point-by-point scan; [3]: ticket; [4]: knots closer than a
-        // bucket (the segment hint needs its loops); [5], [6]: fp32 bit patterns of the spline's speed bound and of the largest lateral offset
+        // bucket (the segment hint needs its loops); [5], [6]: fp32 bit patterns of the spline's speed bound and of the largest lateral offset;
+        // [7]: kCut instances: the ends of the ego's v_samples, packed like [1] (see the row ranges)
         if (tid < 8) s_cnt[tid] = 0;
 #if defined(FP_PHASE_STAMPS)
         if (tid == 0) { s_walk_t[0] = 0xFFFFFFFFu; s_walk_t[1] = 0u; }
@@ -724,6 +728,8 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
     //     Conditioning is benign on t in [0, 10] (terms ~1e2..1e4 against sums ~1e1..1e3: ~1e-12 absolute), far inside the
     //     1e-6 cost bar, and the expressions are even in the lateral boundary data, so mirrored candidates still tie bit-exactly.
     // [section SOLVE]
+    // (kCut instances: the wavefronts that hold no solve branch around the loop on a scalar test; likewise DALL, POWS and CIRCLES below)
+    if (!kCut || (wave_s + 1) * kWave + n_it * nv > kThreads)
     for (int e = kThreads - 1 - tid; e < n_it * nv; e += kThreads) {
         const int eq = div_by<NV, NT * NV>(e, 1.0f / (float)nv);
         const int it = it_lo + eq, iv = e - mul24(eq, nv);
@@ -776,9 +782,9 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
 #if defined(FP_ABL_NO_DALL)
     if (false) {
 #else
-    if (n_obs > 0 && wave >= 1) {
+    if (n_obs > 0 && wave_s >= 1) {
 #endif
-        for (int e0 = (wave - 1) * kWave; e0 < n_it * nd; e0 += (kWaves - 1) * kWave) {
+        for (int e0 = (wave_s - 1) * kWave; e0 < n_it * nd; e0 += (kWaves - 1) * kWave) {
             const int e = e0 + lane;
             uint32_t bits = 0u;
             if (e < n_it * nd) {
@@ -803,9 +809,26 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
     // [section POWS]
     {   // power sums of every slice (they need nothing but the time samples): a few threads of the middle
         const int i = tid - kThreads / 2;
-        if (i >= 0 && i < n_it) power_sums_closed(arange_len(s_ts[it_lo + i], tick), tick, s_pows + (it_lo + i) * 11);
+        if ((!kCut || wave_s == kWaves / 2) && i >= 0 && i < n_it) power_sums_closed(arange_len(s_ts[it_lo + i], tick), tick, s_pows + (it_lo + i) * 11);
     }
     // [/section POWS]
+    // [section VENDS]
+    // kCut instances: the ends of the ego's v_samples for the row ranges below (s_cnt[7] = iv_lo | iv_hi << 8 | NaN << 16; nv <= 255),
+    // found once by a wavefront that has nothing else in this interval (the solves take the last one, the power sums the middle one,
+    // the LUT, the speed bound and the lateral bound the first ones).  Any order of v_samples, as for d_samples below.
+    if constexpr (kCut) {
+        if (wave_s == kWaves - 2) {
+            int iv_lo = 0, iv_hi = 0;
+            for (int iv = 1; iv < nv; ++iv) {
+                iv_lo = s_vs[iv] < s_vs[iv_lo] ? iv : iv_lo;
+                iv_hi = s_vs[iv] > s_vs[iv_hi] ? iv : iv_hi;
+            }
+            bool v_nan = false;
+            for (int iv = 0; iv < nv; ++iv) v_nan = v_nan || !(s_vs[iv] == s_vs[iv]);
+            if (lane == 0) s_cnt[7] = iv_lo | (iv_hi << 8) | ((int)v_nan << 16);
+        }
+    }
+    // [/section VENDS]
     __syncthreads();
     FP_STAMP(2);
     auto eS0 = [&]() -> double { if constexpr (kEgoLds) return s_k[5]; else return s0; };
@@ -821,6 +844,44 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
         // loop over the end-speed samples, then LDS atomic min / max on order-preserving fp32 bit patterns (relative to the first knot).
         // (The truncation index M is still being reduced in this phase: poses off the spline count too, the circle clamps the range.)
         const float inv_rows = 1.0f / (float)(rows > 0 ? rows : 1);
+        if constexpr (kCut) {
+            // kCut instances: TWO profiles instead of nv.  quartic_bvp makes a3 and a4 affine in the end speed v:
+            //   s(t; v) = base(t) + v g(t),  g(t) = t^3 / T^2 (1 - t / (2 T)) >= 0 for 0 <= t <= 2 T
+            // (every point looked at has k < s_nslice[it], t <= T), so s is monotone in v and its ends over the samples sit at the
+            // smallest and the largest sample (s_cnt[7], found once per ego).  Those two are the parent's expressions on the parent's
+            // operands, bit for bit; what is gone is the comparison with the samples between them.  How far can the COMPUTED s of a
+            // middle sample - the number the walk's frames use - lie outside the two computed ends?  With u = 2^-53, X = |v| + |s_d0|,
+            // Y = |a2| T, |V| <= X + 2 Y:  a3 carries at most u (9 X + 20 Y) / T^2 of absolute rounding (the operations of quartic_bvp,
+            // one by one, cancellation in V and in 3 V - A T included), a4 at most u (8 X + 16 Y) / T^3, so a3 t^3 + a4 t^4 is off
+            // by at most 36 u (X + Y) t; the Horner chain's four roundings add 4 u sum|term|, sum|term| <= |s0| + |s_d0| t + |a2| t^2
+            // + |a3| t^3 + |a4| t^4 <= 5.2 Q with  Q = |s0| + t (|s_d0| + max|v| + |a2| T).  Each value is within 60 u Q of the
+            // exact affine one, two values within 120 u Q < 2^-46 Q of their exact order.  That is NOT inside the slack of CIRCLES
+            // at any magnitude (its absolute part is 1e-6: an |s0| of 1e9 m uses it up), so the range is widened HERE, where Q is
+            // known, by E = 2^-44 Q on each side (four times the bound; 6e-11 m at s0 = 1 km); the subtraction of knot0 is monotone,
+            // its rounding and that of lo - E are relative to the ends (2^-53, inside the 6e-8 the relative slack has to spare).
+            // max|v| is at an end.  A NaN sample, a NaN end or an E that is not finite (an infinite sample makes its own end NaN
+            // already: inf t - inf) keeps everything, as a NaN did before.
+            const int ends = __builtin_amdgcn_readfirstlane(s_cnt[7]);
+            const int iv_lo = ends & 0xFF, iv_hi = (ends >> 8) & 0xFF;
+            const bool v_nan = (ends >> 16) != 0;
+            const double v_abs = fmax(fabs(s_vs[iv_lo]), fabs(s_vs[iv_hi]));
+            for (int e = tid; e < mul24(n_it, rows); e += kThreads) {
+                const int itl = div_small(e, inv_rows), r = e - mul24(itl, rows);
+                const int it = it_lo + itl;
+                const int k = mul24(r, stride);
+                if (k >= pose_limit || k >= s_nslice[it]) continue;
+                const double t = (double)k * tick;
+                const double* qa = s_qlon + 2 * (mul24(it, nv) + iv_lo);
+                const double* qb = s_qlon + 2 * (mul24(it, nv) + iv_hi);
+                const double sa = fma(fma(fma(fma(qa[1], t, qa[0]), t, eSdd0() * 0.5), t, eSd0()), t, eS0()) - knot0;
+                const double sb = fma(fma(fma(fma(qb[1], t, qb[0]), t, eSdd0() * 0.5), t, eSd0()), t, eS0()) - knot0;
+                const double E = fma(t, fabs(eSd0()) + v_abs + fabs(eSdd0() * 0.5) * s_ts[it], fabs(eS0())) * 0x1p-44;
+                const bool bad = v_nan || !(sa == sa) || !(sb == sb) || !(E < __builtin_inf());
+                uint32_t* bx = (uint32_t*)&s_box[r];
+                if (bad) { atomicMin(bx + 0, kOrdNegInf); atomicMax(bx + 1, kOrdPosInf); }  // NaN: keep everything
+                else { atomicMin(bx + 0, f32_ordered((float)(fmin(sa, sb) - E))); atomicMax(bx + 1, f32_ordered((float)(fmax(sa, sb) + E))); }
+            }
+        } else
         for (int e = tid; e < mul24(n_it, rows); e += kThreads) {
             const int itl = div_small(e, inv_rows), r = e - mul24(itl, rows);
             const int it = it_lo + itl;
@@ -1003,7 +1064,8 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
     // ---- ranges -> circles: every reference point of the row lies within  v_max * (half the range)  of the line's point at
     // the middle of the range (v_max >= |P'(s)| everywhere); + ego reach + the largest lateral offset.  One test per
     // (row, obstacle) item then prunes the item for every profile of every slice at once.
-    if (n_obs > 0 && kThreads - 1 - nd - tid >= 0 && kThreads - 1 - nd - tid < rows) {  // (the threads next to the lat coefficients' first)
+    if (n_obs > 0 && (!kCut || (wave_s * kWave <= kThreads - 1 - nd && wave_s * kWave + kWave - 1 >= kThreads - nd - rows)) && kThreads - 1 - nd - tid >= 0 &&
+        kThreads - 1 - nd - tid < rows) {  // (the threads next to the lat coefficients' first)
         const int r = kThreads - 1 - nd - tid;
         const uint4 bx = s_box[r];
         const double knot0 = s_knots[0], knot_last = s_knots[nx - 1];  // (fresh reads: the prologue's copies need not live this long)
@@ -1493,9 +1555,27 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
     }
     // [/section ASM]
     // [section ARGMIN]
-    mine = wave_best(mine);
-    if (lane == 0) s_best[wave] = mine;
-    __syncthreads();
+    if constexpr (kArgWave) {
+        // ONE wavefront reduces the workgroup: every lane leaves its `mine` in LDS, the first wavefront merges kWaves of them per lane
+        // and runs the exchange chain once (it ran on all kWaves, and thread 0 merged their partials).  best_merge is a total order
+        // on (cost, index) among feasible candidates with a cost that is a number - all ASM lets through - so any reduction tree
+        // ends on the same winner.  The bytes are the survivors' pose table: nothing reads it after the walk's last barrier (the
+        // series of the two-per-CU instances read the spline, the sample grids and s_best), and it exists in every layout.
+        static_assert(sizeof(Best) == 16 && 32 * kItemCap >= (int)sizeof(Best) * kThreads, "every thread's partial argmin fits the pose table");
+        Best* s_arg = (Best*)(smem + L.pose);
+        s_arg[tid] = mine;
+        __syncthreads();
+        if (wave == 0) {  // (not wave_s: a scalar held through the walk costs the four-per-CU instances spilled SGPRs at the kernel's entry)
+            mine = s_arg[lane];
+#pragma unroll
+            for (int w = 1; w < kWaves; ++w) mine = best_merge(mine, s_arg[w * kWave + lane]);
+            mine = wave_best(mine);
+        }
+    } else {
+        mine = wave_best(mine);
+        if (lane == 0) s_best[wave] = mine;
+        __syncthreads();
+    }
     FP_STAMP(9);
     // [/section ARGMIN]
     // [section RESULTS]
@@ -1504,8 +1584,11 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
         // the partial argmins travel as device-coherent atomic stores / loads) merges the partial argmins in part order - the result does not depend on
         // the arrival order - and carries on as the ego's only workgroup: results, epilogue.  No merge launch.
         if (tid == 0) {
-            Best r = s_best[0];
-            for (int w = 1; w < kWaves; ++w) r = best_merge(r, s_best[w]);
+            Best r = mine;  // (kArgWave: the workgroup's argmin already)
+            if constexpr (!kArgWave) {
+                r = s_best[0];
+                for (int w = 1; w < kWaves; ++w) r = best_merge(r, s_best[w]);
+            }
             // device-coherent (agent scope) stores, acknowledged before the ticket is taken: no whole-L2 write-back fence
             // Ordering: relaxed agent-scope atomics go to the device-coherent L2 in program order per wavefront; s_waitcnt(0) holds
             // the ticket back until both stores are acknowledged by L2, and the merging workgroup reads the partials with
@@ -1543,8 +1626,11 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
         }
         __syncthreads();
     } else if (tid == 0) {
-        Best r = s_best[0];
-        for (int w = 1; w < kWaves; ++w) r = best_merge(r, s_best[w]);
+        Best r = mine;
+        if constexpr (!kArgWave) {
+            r = s_best[0];
+            for (int w = 1; w < kWaves; ++w) r = best_merge(r, s_best[w]);
+        }
         s_best[0] = r;
     }
     if (tid == 0) {

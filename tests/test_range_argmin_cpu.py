@@ -1,0 +1,154 @@
+"""CPU: the cases of tests/range_argmin_cases.py are what their names say, by the oracle alone.  Every case with obstacles has a
+colliding and a free candidate (a cull that drops a needed item flips a flag); the cases without obstacles have none by construction
+and prove their argmin property instead."""
+import math
+
+import numpy as np
+import pytest
+
+import adversarial as A
+import prologue_cases as P
+import range_argmin_cases as R
+from fiss_plus_planner_amd import synth
+from fiss_plus_planner_amd.engine import make_params
+
+INFEASIBLE = 1 | 2 | 4 | 16 | 32 | 64 | 128  # FP_FLAG_INFEASIBLE (include/frenet_gpu.h)
+ALL = {**R.RANGE_CASES, **R.ARGMIN_CASES}
+
+
+@pytest.fixture(scope="module")
+def plans(oracle):
+    cache = {}
+
+    def get(name, batch=None):
+        if name not in cache:
+            batch = ALL[name]() if batch is None else batch
+            cache[name] = (batch, [p.fop_plan() for p in oracle.problems_from_batch(batch)])
+        return cache[name]
+    return get
+
+
+def rows_of(batch):
+    cap = make_params(batch).points_max or 128
+    return min(math.ceil(cap / batch.check_stride), math.ceil(batch.T_obs / batch.check_stride))
+
+
+def feasible(r):
+    return ((r.flags & INFEASIBLE) == 0) & ~np.isnan(r.cost)
+
+
+@pytest.mark.parametrize("name", list(ALL))
+def test_every_case_decides_something(plans, name):
+    batch, ref = plans(name)
+    assert 8 <= batch.B <= 16
+    coll = np.concatenate([(r.flags & 4) != 0 for r in ref])
+    if name in R.NO_OBSTACLES:
+        assert batch.n_obs == 0 and not coll.any()
+    else:
+        assert coll.any() and (~coll).any(), (name, int(coll.sum()), coll.size)
+    if name != "no feasible candidate":
+        assert any(r.best_idx >= 0 for r in ref), name
+
+
+@pytest.mark.parametrize("name", sorted(R.SHAPED_997 | R.SHAPED_555))
+def test_shaped_cases_have_a_compiled_in_shape(name):
+    b = ALL[name]()
+    assert (b.nd, b.nv, b.nt, b.check_stride, b.n_obs, rows_of(b)) == (R.SHAPE_997 if name in R.SHAPED_997 else R.SHAPE_555)
+
+
+def test_v_samples_are_ordered_as_the_names_say():
+    for shape, n in (("9 x 9 x 7", 9), ("5 x 5 x 5", 5)):
+        v = {how: R.RANGE_CASES[f"{shape}, v_samples {how}"]().v_samples for how in
+             ("ascending", "descending", "permuted", "equal extremes", "negative smallest", "nan middle", "nan end", "inf largest")}
+        assert (np.diff(v["ascending"], axis=1) > 0).all() and (np.diff(v["descending"], axis=1) < 0).all()
+        for how in ("permuted", "negative smallest", "inf largest"):
+            lo, hi = np.argmin(v[how], axis=1), np.argmax(v[how], axis=1)
+            assert ((lo > 0) & (lo < n - 1) & (hi > 0) & (hi < n - 1)).all(), how
+        assert (np.sort(v["permuted"], axis=1) == v["ascending"]).all()
+        e = v["equal extremes"]
+        assert ((e == e.min(axis=1, keepdims=True)).sum(axis=1) == 2).all() and ((e == e.max(axis=1, keepdims=True)).sum(axis=1) == 2).all()
+        assert (v["negative smallest"].min(axis=1) < 0).all()
+        assert np.isnan(v["nan middle"][:, n // 2]).all() and np.isnan(v["nan middle"]).sum(axis=1).max() == 1
+        assert np.isnan(v["nan end"][:, n - 1]).all() and np.isnan(v["nan end"]).sum(axis=1).max() == 1
+        assert (v["inf largest"].max(axis=1) == np.inf).all() and np.isinf(v["inf largest"]).sum(axis=1).max() == 1
+    assert R.RANGE_CASES["nv = 1"]().nv == 1
+    b = R.RANGE_CASES["nv != nd (4 x 7 x 3)"]()
+    assert (b.nd, b.nv) == (4, 7)
+    b = R.RANGE_CASES["permuted, t_now odd"]()
+    assert (b.t_now % 2 == 1).all() and b.check_stride == 2
+    assert R.RANGE_CASES["permuted, 220 knots (coefficient window)"]().NX == 220
+
+
+def test_only_the_extreme_profiles_reach_their_obstacles_and_the_first_and_last_index_do_not_span_them(oracle, plans):
+    """The two obstacles of every other ego exist at step 48 alone.  By the oracle, taking them away changes collision flags - of the
+    fastest (index 2) and of the slowest (index 4) end speed and of no other - so a range taken from the samples' first and last index
+    (6.0 and 5.8 m/s) must not cull them: they lie further from that range's circle than the circle reaches."""
+    name = "permuted, obstacles only the fastest and only the slowest profile reach"
+    batch, ref = plans(name)
+    v = batch.v_samples[0]
+    i_hi, i_lo = int(np.argmax(v)), int(np.argmin(v))
+    assert 0 < i_hi < batch.nv - 1 and 0 < i_lo < batch.nv - 1
+    pose = batch.obs_pose.copy()
+    egos = list(range(0, batch.B, 2))
+    for b in egos:
+        pose[int(batch.scene_of[b]), :, :2, 3] = 0.0
+    _, without = plans(name + " / without them", A._copy(batch, obs_pose=pose))
+    for b in range(batch.B):
+        changed = ((ref[b].flags ^ without[b].flags) & 4).reshape(batch.nd, batch.nt, batch.nv) != 0
+        if b not in egos:
+            assert not changed.any()
+            continue
+        assert changed[:, :, i_hi].any() and changed[:, :, i_lo].any(), b
+        assert not np.delete(changed, [i_hi, i_lo], axis=2).any(), b
+        # the reading "first and last index": the range of those two end speeds over every slice, its circle on the line
+        s = P.lon_positions(batch, b)[:, R.K_LATE].reshape(batch.nt, batch.nv)
+        wrong = s[:, [0, batch.nv - 1]]
+        lo, hi = np.nanmin(wrong), np.nanmax(wrong)
+        f, sc = int(batch.frame_of[b]), int(batch.scene_of[b])
+        cx, cy, _ = synth.sample_frames(batch.knots[f:f + 1], batch.coef[f:f + 1], np.array([[0.5 * (lo + hi)]]))
+        reach = 1.2 * 0.5 * (hi - lo) + R.group_reach(batch, b, (1.0, 1.0))  # (|P'| < 1.2 on these lines)
+        for j in (0, 1):
+            dist = math.hypot(batch.obs_pose[sc, R.K_LATE, j, 0] - cx[0, 0], batch.obs_pose[sc, R.K_LATE, j, 1] - cy[0, 0])
+            assert dist > reach + 0.5, (b, j, dist, reach)
+
+
+# ---------------------------------------------------------------- argmin
+def test_the_winner_visits_every_wavefronts_share(plans):
+    shares = {R.share_of(r.best_idx) for name in R.WINNER_SHARES for r in plans(name)[1] if r.best_idx >= 0}
+    assert {w for w, trip in shares if trip == 0} == set(range(8)), sorted(shares)
+    assert any(trip == 1 for _, trip in shares), sorted(shares)  # an index >= 512: the assembly loop's second trip
+
+
+def test_one_feasible_candidate_first_and_last(plans):
+    for name, want in (("the only feasible candidate is index 0", 0), ("the only feasible candidate is index C - 1", -1)):
+        batch, ref = plans(name)
+        want = want % batch.C
+        for r in ref:
+            assert np.flatnonzero(feasible(r)).tolist() == [want] and r.best_idx == want, name
+
+
+def test_no_feasible_candidate(plans):
+    _, ref = plans("no feasible candidate")
+    assert all(r.best_idx == -1 and not feasible(r).any() for r in ref)
+
+
+def test_small_lattice(plans):
+    batch, ref = plans("C < 64 (3 x 3 x 3)")
+    assert batch.C == 27 and any(r.best_idx >= 0 for r in ref)
+
+
+@pytest.mark.parametrize("name,same", [("mirror tie inside one wavefront's share (5 x 5 x 5)", True), ("mirror tie across two wavefronts' shares (9 x 9 x 7)", False)])
+def test_mirror_ties(plans, name, same):
+    batch, ref = plans(name)
+    nd, per = batch.nd, batch.nt * batch.nv
+    seen = 0
+    for r in ref:
+        hi = r.best_idx
+        d = batch.d_samples
+        id_hi = hi // per
+        id_lo = int(np.flatnonzero(d == -d[id_hi])[0])
+        assert hi >= 0 and id_lo < id_hi and abs(d[id_hi]) == np.nanmin(np.abs(d))  # the higher of the two innermost samples
+        lo = hi - (id_hi - id_lo) * per
+        assert r.cost[lo] == r.cost[hi] and feasible(r)[lo] and (r.cost[feasible(r)] >= r.cost[hi]).all()
+        seen += (R.share_of(lo) == R.share_of(hi)) == same
+    assert seen == len(ref), (name, seen)

@@ -13,9 +13,12 @@ sections and the appended series workgroups are not modelled and are part of tha
 
 What the model is and is not.  A section's static count is taken as ONE execution of it by a wavefront that does its work; a loop
 inside a section counts once (the bisection of LUT and the end-speed loop of RANGES carry their trip counts below, as a factor on
-the whole section - an over-estimate of their headers).  A wavefront that only tests and skips a section is charged SKIP
+the whole section - an over-estimate of their headers; --unrolled names the sections whose loop the compiler unrolled, so that the
+static count is every trip already: RANGES wherever nv is a template argument).  A wavefront that only tests and skips a section is charged SKIP
 instructions when the test is a vector compare, none when it is scalar (--scalar-skip names those sections: the kCut instances
-enter LUT's divisions, the square root of `r_ego`, the cost sums and the ends of d_samples on a scalar test).  MASKS runs only for slices with an
+enter LUT's divisions, the square root of `r_ego`, the cost sums, the ends of d_samples and of v_samples (VENDS) and the one-wavefront
+argmin on a scalar test).  --two-ends names the sections that have the form of the instances with the two-profile RANGES and the
+one-wavefront ARGMIN: RANGES then has no end-speed loop, ARGMIN runs once and only its store (--uniform ARGMIN=9) on every wavefront.  MASKS runs only for slices with an
 unproven profile (0.05 of 7 on the headline workload) and is charged its share.
 """
 import argparse
@@ -40,6 +43,10 @@ ap.add_argument("--tail", type=float, default=128 / 2048, help="share of the ego
 ap.add_argument("--scalar-skip", default="", help="comma list of sections whose idle wavefronts skip on a scalar test (the kCut instances: LUT,SUMS)")
 ap.add_argument("--uniform", default="", help="NAME=count[@wavefronts],...: instructions of a section that are no part of its dealt work and run once on that many wavefronts, "
                 "all by default (parent: FAN=38,LUT=28 - the ends of d_samples, the bucket width's divisions; kCut instances: LUT=28@3)")
+ap.add_argument("--two-ends", default="", help="comma list of RANGES, ARGMIN: the section has the form of the instances that take the row ranges from the two extreme end "
+                "speeds (no end-speed loop: one trip per lane) / reduce the argmin on one wavefront (the store of every lane's candidate stays on all: --uniform ARGMIN=9)")
+ap.add_argument("--unrolled", default="", help="comma list of sections whose inner loop the compiler unrolled (the static count holds every trip already): RANGES in the shaped "
+                "instances, where nv is a constant - the counter showed it: taking seven of nine evaluations out removed 0.2 k per ego, not 1.0 k")
 ap.add_argument("--counter", type=float, help="SQ_INSTS_VALU per launch")
 ap.add_argument("--egos", type=int, default=2048)
 a = ap.parse_args()
@@ -60,6 +67,8 @@ v = dict(W=W, nd=a.nd, nv=a.nv, nt=a.nt, rows=a.rows, n_obs=a.n_obs, nx=a.nx, hp
          flight=a.flight, threads=a.threads, ceil=math.ceil, log2=math.log2, scan=a.scan_slices)
 SKIP = 4  # a vector compare, the EXEC save / restore moves around a section a wavefront has no lane in
 scalar = set(filter(None, a.scalar_skip.split(",")))
+two_ends = set(filter(None, a.two_ends.split(",")))
+unrolled = set(filter(None, a.unrolled.split(",")))
 uniform = {k: (int(c.split("@")[0]), int(c.split("@")[1]) if "@" in c else W) for k, c in (kv.split("=") for kv in filter(None, a.uniform.split(",")))}
 # section -> (wavefronts x trips that execute it, as a formula of the shape)
 WEIGHT = {
@@ -69,7 +78,8 @@ WEIGHT = {
     "SOLVE": "ceil(nt * nv / 64)",
     "DALL": "ceil(nt * nd / 64)",
     "POWS": "1",
-    "RANGES": "ceil(nt * rows / 64) * (1 + (nv - 1) / 4)",   # (a quarter of the section is the end-speed loop's body)
+    "VENDS": "1",
+    "RANGES": "ceil(nt * rows / 64) * (1 + (nv - 1) / 4)" if "RANGES" not in two_ends | unrolled else "ceil(nt * rows / 64)",   # (a quarter of the section is the end-speed loop's body; two ends, unrolled: no loop)
     "MASKS": "W * scan / nt",
     "SUMS": "ceil(nt * nv / 64) + ceil(nt * nd / 64)" if "SUMS" not in scalar else "1",   # (both branches in each; dealt by kind: each wavefront one of them)
     "QLAT": "ceil(nt * nd / 64)",
@@ -78,7 +88,7 @@ WEIGHT = {
     "G": "W * ceil(rows * n_obs / (flight * threads))",
     "SINCOS": "ceil(surv / 64)",
     "ASM": "ceil(C / 64)",
-    "ARGMIN": "W",
+    "ARGMIN": "W" if "ARGMIN" not in two_ends else "1",
     "RESULTS": "1",
 }
 rows_out, total = [], 0.0
