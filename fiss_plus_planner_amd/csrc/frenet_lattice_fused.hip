@@ -83,6 +83,12 @@ __device__ __forceinline__ int div_by(int e, float inv_d)
     }
 }
 
+// bits of a ballot below the calling lane: __popcll(m & ((1ull << lane) - 1)) as the hardware counts it (v_mbcnt_lo / v_mbcnt_hi)
+__device__ __forceinline__ int lanes_below(unsigned long long m)
+{
+    return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+}
+
 // Orders the LDS accesses of ONE wavefront for the compiler (the hardware executes a wavefront's LDS instructions in program order):
 // what lanes wrote before it, other lanes of the same wavefront read after it.  No instruction is emitted.
 __device__ __forceinline__ void wave_lds_sync()
@@ -212,6 +218,7 @@ template <int ND, int NV, int NT, int STRIDE, int NOBS, int ROWS, int OCC, int N
 __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, int rows_max_arg, int hp_max_arg, int nsplit_arg, Best* part_best, int* part_count, const int* perm,
                                                                    int* dur, int reserved, int tail_from, int epi_from, int wcap, FissTail ft, InlineIn inl)
 {
+    // [section APPSEARCH]
     if constexpr (FISS) {
         if (epi_from >= 0 && (int)blockIdx.x >= epi_from) {  // ---- appended search workgroup: one ego, in launch order
             extern __shared__ __attribute__((aligned(16))) unsigned char fsm[];
@@ -254,6 +261,7 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
             return;
         }
     }
+    // [/section APPSEARCH]
     // ---------------------------------------------------------------- appended epilogue workgroups (blockIdx >= epi_from)
     // The three-workgroups-per-CU instances cannot write the winner's series themselves (the slot time of a one-wavefront dependent
     // chain, and 125 registers), and a winner_traj_kernel behind the launch costs ~9.5 us of a ~155 us step in which the last ~25 us
@@ -268,6 +276,7 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
     // observed, not documented: the host offers appended workgroups only on the architectures it was verified on (gfx942 / gfx950,
     // fp_ctx_create), and should it ever not hold the wait gives up after 2 s WITHOUT a trap (handover_wait): the slot falls free,
     // the launch completes, and the next call on the ctx reports the failed hand-over and falls back to winner_traj_kernel.
+    // [section APPSERIES]
     if constexpr (OCC > 4) {
         if (epi_from >= 0 && (int)blockIdx.x >= epi_from) {
             extern __shared__ __attribute__((aligned(16))) unsigned char esm[];
@@ -319,13 +328,22 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
             return;
         }
     }
+    // [/section APPSERIES]
+    // [section ENTRY]
     // Dispatch slot -> (ego, part).  Uniform split (latency mode): slot = blockIdx / nsplit.  Tail split (tail_from >= 0, nsplit_arg
     // == 1): the slots from tail_from on - the workgroups that start when the launch's last round is already draining - are cut in
     // two like a latency-mode ego, so the launch does not end on whole egos that started last (see launch_lattice_fused).
     const bool in_tail = tail_from >= 0 && (int)blockIdx.x >= tail_from;
-    const int nsplit = in_tail ? 2 : nsplit_arg;
-    const int slot = in_tail ? tail_from + (((int)blockIdx.x - tail_from) >> 1) : (int)blockIdx.x / nsplit_arg;
-    const int part_of_slot = in_tail ? (((int)blockIdx.x - tail_from) & 1) : (int)blockIdx.x - slot * nsplit_arg;
+    // Three and four per CU are only ever launched with ONE workgroup per ego outside the tail (plan_lattice grants them to launches with
+    // nsplit == 1 alone; launch_lattice_fused refuses anything else): nsplit is 1 or 2 there, and the three scalar divisions of the
+    // uniform split - blockIdx / nsplit here, part nt / nsplit twice below, five vector instructions each on every wavefront for the
+    // reciprocal - are a shift by nsplit - 1.  Three instances keep the divisions: the two shaped polygon instances (80 VGPRs, all in
+    // use) spill two VGPRs without them, and the plain run-time-shape four-per-CU instance comes out LARGER (4595 -> 4673 vector
+    // instructions, 94 -> 111 spilled SGPRs: another register assignment, not less work).
+    constexpr bool kOnePart = OCC > 4 && !(ND > 0 && POLY) && !(ND == 0 && OCC > 6 && !POLY && !FISS && !WIN);
+    const int nsplit = in_tail ? 2 : (kOnePart ? 1 : nsplit_arg);
+    const int slot = in_tail ? tail_from + (((int)blockIdx.x - tail_from) >> 1) : (kOnePart ? (int)blockIdx.x : (int)blockIdx.x / nsplit_arg);
+    const int part_of_slot = in_tail ? (((int)blockIdx.x - tail_from) & 1) : (kOnePart ? 0 : (int)blockIdx.x - slot * nsplit_arg);
     constexpr bool kShape = ND > 0;  // (all six are set together)
     // The run-time-shape three-per-CU instances have no register to spare (80 VGPRs, run-time sizes in place of immediates): from the
     // prologue's second barrier on they re-read the ego's start state from LDS (s_k[5..10]) where it is used instead of holding twelve
@@ -380,6 +398,9 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
     // per lat profile, the ends of d_samples found once, G with a column per lane - each described where it stands.  In the shaped
     // rectangle instances only: the run-time-shape instances have no scalar register to spare and came out larger with them, and the two
     // shaped polygon instances (80 VGPRs, all in use) spill a VGPR with them; both keep the statements they had.
+    // (Also kCut: the appends' lane count by v_mbcnt - lanes_below - and the fold of an N round's hits by halving, both in the walk.)
+    // Every statement of the kernel stands in a `// [section NAME]` pair - the bodies, and since the last census also the entry, the glue
+    // between sections, the profile loop's own statements and the appended workgroups - so that tools/nonwalk_census.py can weigh all of it.
     constexpr bool kCut = kShape && !POLY;
     // The argmin by one wavefront (ARGMIN below): every instance comes out smaller with it but the shaped polygon instance without a
     // window (80 VGPRs, all in use), which spills two VGPRs with it and keeps the statements it had.
@@ -389,7 +410,8 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
     const int wave_s = kCut ? __builtin_amdgcn_readfirstlane(wave) : wave;
     const int nd = kShape ? ND : p.nd, nv = kShape ? NV : p.nv, nt = kShape ? NT : p.nt;
     const int C = nd * nv * nt;
-    const int it_lo = part * nt / nsplit, it_hi = (part + 1) * nt / nsplit;  // this workgroup's slices
+    // this workgroup's slices (kOnePart: nsplit is 1 or 2 and the products are not negative - the same quotients)
+    const int it_lo = kOnePart ? (part * nt) >> (nsplit - 1) : part * nt / nsplit, it_hi = kOnePart ? ((part + 1) * nt) >> (nsplit - 1) : (part + 1) * nt / nsplit;
     const int n_it = it_hi - it_lo;
     const int stride = kShape ? STRIDE : p.check_stride;
     const int n_obs_tab = kShape ? NOBS : bt.n_obs;  // obstacles per scene of the table
@@ -474,6 +496,7 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
     const double target_speed = in_ts[b];
     const double* eg = in_ego + (size_t)b * 6;
     const double s0 = eg[0], s_d0 = eg[1], s_dd0 = eg[2], d0 = eg[3], d_d0 = eg[4], d_dd0 = eg[5];
+    // [section SKIPPED]
     if (skip_flag) {  // finished ego of a closed-loop batch (block-uniform exit)
         if (part == 0) {
             if (tid == 0 && dur) dur[b] = 0;
@@ -502,6 +525,8 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
         }
         return;
     }
+    // [/section SKIPPED]
+    // [/section ENTRY]
     // [section STAGE]
     // ---------------------------------------------------------------- stage: ego, spline, obstacle rows
     // Global reads cost 1-2 us each, so everything that depends only on the scalars above is requested at once.  The obstacle
@@ -604,6 +629,7 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
         }
     };
     // [/section STAGE]
+    // [section GLUE]
     if (kEgoEarly && tid == 8) { s_k[5] = s0; s_k[6] = s_d0; s_k[7] = s_dd0; s_k[8] = d0; s_k[9] = d_d0; s_k[10] = d_dd0; s_k[11] = d_dd0 * 0.5; }
     __syncthreads();
     FP_STAMP(0);
@@ -614,6 +640,7 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
     auto pD0 = [&]() -> double { if constexpr (kEgoEarly) return s_k[8]; else return d0; };
     auto pDd0 = [&]() -> double { if constexpr (kEgoEarly) return s_k[9]; else return d_d0; };
     auto pDdd0 = [&]() -> double { if constexpr (kEgoEarly) return s_k[10]; else return d_dd0; };
+    // [/section GLUE]
     // [section LUT]
     // Arclength buckets -> segment hint: lut[b] = bisect_right(knots, k0 + b*width) - 1, 2*nx buckets.  A point then
     // needs one table read plus a short walk instead of a log2(nx) search (knots may be non-uniform: the walk fixes it).
@@ -686,6 +713,7 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
         }
     }
     // [/section VBOUND]
+    // [section GLUE]
     int horizon_cap = 0;  // final_time_step - time_step_now (:173-174)
     int rows = 0;         // obstacle rows the collision horizon can touch: rows of the table below final_time_step
     if (n_obs > 0) {
@@ -727,6 +755,7 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
     //     sum_i p(t_i)^2 = sum_k c_k S_k with c = p (*) p (coefficient convolution) - no per-point work and no reductions.
     //     Conditioning is benign on t in [0, 10] (terms ~1e2..1e4 against sums ~1e1..1e3: ~1e-12 absolute), far inside the
     //     1e-6 cost bar, and the expressions are even in the lateral boundary data, so mirrored candidates still tie bit-exactly.
+    // [/section GLUE]
     // [section SOLVE]
     // (kCut instances: the wavefronts that hold no solve branch around the loop on a scalar test; likewise DALL, POWS and CIRCLES below)
     if (!kCut || (wave_s + 1) * kWave + n_it * nv > kThreads)
@@ -804,8 +833,10 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
         }
     }
     // [/section DALL]
+    // [section GLUE]
     if (tid == 0) { s_k[0] = knot0; s_k[1] = inv_bucket_w; s_k[2] = veh_hl; s_k[3] = veh_hw; s_k[4] = r_ego; }
     if (kEgoLds && !kEgoEarly && tid == 1) { s_k[5] = s0; s_k[6] = s_d0; s_k[7] = s_dd0; s_k[8] = d0; s_k[9] = d_d0; s_k[10] = d_dd0; s_k[11] = d_dd0 * 0.5; }
+    // [/section GLUE]
     // [section POWS]
     {   // power sums of every slice (they need nothing but the time samples): a few threads of the middle
         const int i = tid - kThreads / 2;
@@ -829,6 +860,7 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
         }
     }
     // [/section VENDS]
+    // [section GLUE]
     __syncthreads();
     FP_STAMP(2);
     auto eS0 = [&]() -> double { if constexpr (kEgoLds) return s_k[5]; else return s0; };
@@ -838,6 +870,7 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
     auto eDd0 = [&]() -> double { if constexpr (kEgoLds) return s_k[9]; else return d_d0; };
     auto eDdd0 = [&]() -> double { if constexpr (kEgoLds) return s_k[10]; else return d_dd0; };
     auto eDdd0Half = [&]() -> double { if constexpr (kEgoLds) return s_k[11]; else return d_dd0 * 0.5; };  // (the walk's N: the product, ready)
+    // [/section GLUE]
     // [section RANGES]
     if (n_obs > 0 && pose_limit > 0) {
         // ---- arclength range of every checked pose row over the lon profiles of ALL slices of this workgroup: lane = (row, slice),
@@ -1013,8 +1046,10 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
         }
     }();
     // [/section QLAT]
+    // [section GLUE]
     __syncthreads();
     FP_STAMP(3);
+    // [/section GLUE]
     // [section FAN]
     // ---- lateral fan bounds of EVERY slice: lane = (slice, point inside the collision horizon): fan half-width max|d| and
     // largest lateral step max|d(i + 1) - d(i)| over the lateral samples, float_above: never below the fp64 value.  For a fixed
@@ -1094,6 +1129,7 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
         s_grp[r].r = rad;
     }
     // [/section CIRCLES]
+    // [section GLUE]
     __syncthreads();  // the final assembly reads the sums (with no obstacles there is no other barrier in between)
     FP_STAMP(4);
 
@@ -1131,6 +1167,7 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
             // ---- G (once per ego and item chunk): the poses come straight from the scene table (L2 for all but the first ego of a
             // scene), kPoseFlight reads in flight per lane.  x = NaN / valid = 0: no state at this step (state_at_time -> None).
             // A survivor's pose goes to the list with its orientation still an angle.
+    // [/section GLUE]
     // [section G]
             const int i1 = i0 + chunk < n_items ? i0 + chunk : n_items;
             if constexpr (kCut) {
@@ -1171,7 +1208,9 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
                             const int first = __ffsll((long long)m) - 1;
                             int base = 0;
                             if (lane == first) base = atomicAdd(&s_cnt[0], __popcll(m));
-                            const int pos = __builtin_amdgcn_readlane(base, first) - item_base + __popcll(m & ((1ull << lane) - 1ull));
+                            // (the survivors in the lanes below this one: v_mbcnt counts them in two instructions - the mask (1 << lane) - 1,
+                            // two ands and two popcounts were eight)
+                            const int pos = __builtin_amdgcn_readlane(base, first) - item_base + lanes_below(m);
                             if (keep && pos < kItemCap) {
                                 s_items[pos] = (unsigned short)(kItemShift > 0 ? (r << kItemShift) | j : mul24(r, NOBS) + j);
                                 s_spose.set(pos, ps[u].x, ps[u].y, ps[u].z, 0.0);
@@ -1214,6 +1253,7 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
                 }
             }
     // [/section G]
+    // [section GLUE]
             __syncthreads();
     FP_STAMP(7);
             const int item_end = s_cnt[0];
@@ -1225,6 +1265,7 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
                 __syncthreads();  // every thread has read s_cnt[0] before the redone pass adds to it again
                 continue;
             }
+    // [/section GLUE]
     // [section SINCOS]
             // the survivors' orientations -> (cos, sin), with shapely's snap (frenet_device.h); every item belongs to one chunk
             for (int si = tid; si < n_surv; si += kThreads) {
@@ -1233,6 +1274,7 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
                 s_spose.hi[si] = make_double2(cs, sn);
             }
     // [/section SINCOS]
+    // [section WSETUP]
             // (the walk's barrier below orders these writes before stage B reads them)
             // No survivor (block-uniform: empty surroundings, obstacles out of reach): nothing can collide, the walk is skipped.
             // (Skipping only the rows without a survivor was tried: a lane that skips its point saves nothing while its wavefront's
@@ -1284,9 +1326,14 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
                 // atomicAdd(...)` + readfirstlane inside a loop whose only exit is a break, was restructured by the compiler so that lanes
                 // 1..63 spun on their own - a hang; it took an inline-asm block with EXEC narrowed by hand.)  The loop below has a
                 // wave-uniform scalar trip count and no divergent branch around a cross-lane operation.
+    // [/section WSETUP]
+    // [section PQ]
                 for (int pq = __builtin_amdgcn_readfirstlane(wave); pq < n_prof; pq += kWaves) {
+    // [section PQDEC]
                     const int itl = div_by<NV, NT * NV>(pq, inv_nvf), iv = pq - mul24(itl, nv);
                     const int it = it_lo + itl, qg = mul24(it, nv) + iv;
+    // [/section PQDEC]
+    // [section PQFETCH]
                     const int M = __builtin_amdgcn_readfirstlane(s_lon_meta[qg].x);  // (M <= N; wave-uniform -> scalar registers)
                     // a trajectory of fewer than two points has no heading: no pair (M == 1 is the assembly's business)
                     if (M < 2) continue;
@@ -1294,6 +1341,7 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
                     const int np = hp < n_pts ? hp : n_pts;
                     const int npm = np < M ? np : M;
                     const double a3 = s_qlon[2 * qg], a4 = s_qlon[2 * qg + 1];
+    // [/section PQFETCH]
     // [section FRAMES]
                     for (int i = lane; i < npm; i += kWave) {
                         const double t = (double)i * tick;
@@ -1311,9 +1359,11 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
                         wfr.set(i, fr.px, fr.py, fr.tx, fr.ty);
                     }
     // [/section FRAMES]
+    // [section PQPTR]
                     wave_lds_sync();
                     const fan_t* dm = s_fan_d + mul24(it, hp_max);
                     const fan_t* ddm = s_fan_dd + mul24(it, hp_max);
+    // [/section PQPTR]
                     // ---- prep: wfat = lateral half-width of the whole fan along the reference normal n_k, per checked pose row r of this
                     // profile: every ego centre is P_k + d n_k with |d| <= dm[k];  the ego box, whose heading deviates from the
                     // reference tangent by alpha, reaches hw cos(alpha) + hl |sin(alpha)| <= min(r_ego, hw + hl sigma) along n_k, where
@@ -1346,6 +1396,7 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
                             wwf[r] = row_ok ? ((float)dm[k] + wl) * (1.0f + 1e-6f) + 1e-9f : 0.0f;
                         }
     // [/section PREP]
+    // [section PQFETCH]
                     }
                     wave_lds_sync();
                     // candidates of this profile that collided in an earlier item chunk (crowded scenes only; else 0)
@@ -1357,10 +1408,13 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
 #else
                     const int n_walk = n_surv;
 #endif
+    // [/section PQFETCH]
+    // [section ROUNDB]
                     for (int c0 = 0; c0 < n_walk && coll != full; c0 += kWave) {
                         const int si = c0 + lane;
                         bool pass = false;
                         uint32_t code = 0;
+    // [/section ROUNDB]
     // [section B]
                         if (si < n_walk) {
                             const int item = s_items[si];
@@ -1385,11 +1439,12 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
                             code = (uint32_t)k | ((uint32_t)si << 8);  // k < 128, si < 512 (slim: si < 256, 16 bits)
                         }
     // [/section B]
+    // [section ROUNDB]
                         const unsigned long long m = __ballot(pass);
                         if (lane == 0) { FP_COUNT(1, 1); FP_COUNT(2, __popcll(m)); }
                         if (!m) continue;
                         const int n_hits = __popcll(m);
-                        if (pass) wh[__popcll(m & lt_mask)] = (hit_t)code;
+                        if (pass) wh[kCut ? lanes_below(m) : __popcll(m & lt_mask)] = (hit_t)code;
                         wave_lds_sync();
                         // ---- N: exact narrow phase, hpw hits x nd lateral samples per round
 #if defined(FP_ABL_NO_N)
@@ -1397,9 +1452,12 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
 #else
                         const int n_exact = n_hits;
 #endif
+    // [/section ROUNDB]
+    // [section ROUNDN]
                         for (int h0 = 0; h0 < n_exact; h0 += hpw) {
                             const int h = h0 + hh_l;
                             bool hit = false;
+    // [/section ROUNDN]
     // [section N]
                             if (hh_l < hpw && h < n_exact && !((coll >> id_l) & 1ull)) {
                                 const uint32_t hc = wh[h];
@@ -1461,11 +1519,21 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
                                 if (hit) FP_COUNT(5, 1);
                             }
     // [/section N]
+    // [section ROUNDN]
                             if (lane == 0) FP_COUNT(6, 1);
                             unsigned long long hm = __ballot(hit);
                             // fold the round's hits onto the nd lateral samples (scalar arithmetic on the ballot)
+                            // (kCut instances: the round's kHpwC groups of nd bits are ORed onto the first by halving - three or four
+                            // scalar shift / or pairs.  The loop's test `hm != 0` of a 64-bit scalar has no scalar compare: it came out as
+                            // v_mov_b64 + v_cmp_gt_u64 per trip, up to seven trips per round, which no static count weighs.  The shaped
+                            // polygon instances come out seven instructions larger with it and keep the loop.)
                             if (nd >= kWave) coll |= hm;
-                            else
+                            else if constexpr (kCut) {
+#pragma unroll
+                                for (int g = 32; g >= 1; g >>= 1)
+                                    if (g < kHpwC) hm |= hm >> (g * ND);
+                                coll |= hm & full;
+                            } else
                                 for (; hm; hm >>= nd) coll |= hm & full;
                             if (coll == full) {
 #if defined(FP_COUNTERS)  // when a blocked profile dies: the pose index of the last hit of the deciding round, in bins of 8 steps (slots 10..15)
@@ -1480,8 +1548,13 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
                             }
                         }
                     }
+    // [/section ROUNDN]
+    // [section PQEND]
                     if (lane == 0) { s_collmask[2 * qg] = (uint32_t)coll; s_collmask[2 * qg + 1] = (uint32_t)(coll >> 32); }
                 }
+    // [/section PQEND]
+    // [/section PQ]
+    // [section POSTWALK]
 #if defined(FP_PHASE_STAMPS)  // when the first and the last wavefront finished their profiles (columns 11, 12): the walk's imbalance
                 if (lane == 0) { atomicMin(&s_walk_t[0], (unsigned int)(wall_clock64() - t_begin)); atomicMax(&s_walk_t[1], (unsigned int)(wall_clock64() - t_begin)); }
 #endif
@@ -1516,6 +1589,7 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
     const fp_params& pa = la.ka.p;
     Best mine{0.0, -1};
     const float inv_nv_a = 1.0f / (float)nv, inv_nt_a = 1.0f / (float)nt;
+    // [/section POSTWALK]
     // [section ASM]
     for (int c = tid; c < C; c += kThreads) {
         // c = (id * nt + it) * nv + iv
@@ -1672,6 +1746,7 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
     // 10 ns ticks: feeds the next launches' order (a tail ego leaves twice its last part's time: about what it would take whole)
     if (tid == 0 && la.dur && (nsplit == 1 || in_tail)) la.dur[b] = (int)(wall_clock64() - t_begin) * nsplit;
     // [/section RESULTS]
+    // [section SERIES]
     if (nsplit > 1) FP_STAMP_LAST(10); else FP_STAMP(10);
 #if defined(FP_PHASE_STAMPS)  // column 15: the workgroup's absolute start (10 ns ticks, low 40 bits) - the launch's occupancy over time
     if (threadIdx.x == 0 && ka.r.best_traj && (perm || blockIdx.x % nsplit == 0)) ka.r.best_traj[((size_t)b * FP_ARR_COUNT + 15) * (ka.r.traj_stride > 0 ? ka.r.traj_stride : FP_DEFAULT_STRIDE) + 112 + 15] = (double)(t_begin & 0xFFFFFFFFFFll);
@@ -1711,6 +1786,7 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
     }
     FP_STAMP_LAST(6);
     if (ka.has_loop && tid == 0) advance_ego(ka, b, win, nullptr, ka.loop);
+    // [/section SERIES]
 }
 
 
@@ -1754,6 +1830,7 @@ static hipError_t launch_lattice_fused(const KernelArgs& ka, hipStream_t stream,
     KernelArgs kx = ka;  // (epilogue workgroups offered but not taken: the caller's winner_traj_kernel writes the series)
     if (ka.epi_flag && !pl.epilogue) { kx.r.best_traj = nullptr; kx.epi_flag = nullptr; }
     if (rq.provisional) { kx.r.best_traj = nullptr; kx.epi_flag = nullptr; kx.has_loop = 0; }  // (as planned: tables and a provisional argmin only)
+    if (pl.per_cu > 2 && pl.nsplit != 1) return hipErrorInvalidValue;  // (internal: those instances read nsplit as 1, see kOnePart)
     int rows = pl.rows, hp = pl.hp, nsplit = pl.nsplit, reserved = 0, tail_from = pl.tail_from, epi_from = pl.epi_from, wcap = pl.wcap;
     // part_scratch: [ticket counters: kTicketBytes, zero between launches][partial argmins: Best x B x nsplit]
     int* part_count = (int*)rq.part_scratch;

@@ -17,7 +17,7 @@ main file above the kernel's own first line - goes to its outermost call site in
 innermost `// [section NAME]` ... `// [/section NAME]` pair (read from the source: --src, or the path in the .file directive) around
 that line.  A section nested in another (a branch that only some inputs take) is reported on its own, not inside the outer one.
 
-Prints the section totals (VALU split into fp64 / fp32 / int / mov+select / lane / other, then SALU, LDS, VMEM, branches, waits), the
+Prints the section totals (VALU split into fp64 / fp32 / int / mov+select / lane / lane operations on spilled SGPRs / other, then SALU, LDS, VMEM, branches, waits), the
 totals of [lo, hi] when given, and with --lines every line.  Static counts - loops are not weighted - but inside one loop body they are
 the per-iteration mix.
 """
@@ -44,12 +44,17 @@ INT = re.compile(r"^v_(add|sub|subrev|mul|mad|lshl|lshr|ashr|and|or|xor|not|bfe|
 F32 = re.compile(r"^v_\w+_f(32|16)(_|$)|^v_cvt_")  # (what F64 did not take: single and half precision, and the conversions among them and integers)
 MOV = re.compile(r"^v_(mov|cndmask|swap|accvgpr)")
 LANE = re.compile(r"^v_(readlane|readfirstlane|writelane|permlane)|^v_\w+_dpp")
+# a lane operation on a spilled SGPR: v_writelane_b32 / v_readlane_b32 whose lane select is an immediate (the register allocator's
+# spill slots; a lane the program chooses - __builtin_amdgcn_readlane(x, first) - arrives in a scalar register or m0)
+SPILL = re.compile(r"^v_(readlane|writelane)_b32\s+[^,]+,\s*[^,]+,\s*\d+\s*(;.*)?$")
 
-VALU = ["f64", "f32", "int", "movsel", "lane", "vother"]
+VALU = ["f64", "f32", "int", "movsel", "lane", "spill", "vother"]
 COLS = VALU + ["salu", "lds", "vmem", "branch", "wait"]
 
 
-def classify(op):
+def classify(op, text=""):
+    if SPILL.match(text):
+        return "spill"
     if op.startswith("s_"):
         if op.startswith("s_waitcnt") or op.startswith("s_nop") or op.startswith("s_barrier"):
             return "wait"
@@ -157,7 +162,7 @@ for line in open(path):
         continue
     if cur is None:
         continue
-    cls = classify(s.split()[0])
+    cls = classify(s.split()[0], s)
     per[cur][cls] += 1
     if where is not None:
         helper[(section_of(cur), os.path.basename(where))][cls] += 1
