@@ -1243,6 +1243,9 @@ const char* fp_build_flags(void)
 #if defined(FP_ABL_NO_BN)
         FP_FLAG_IF(FP_ABL_NO_BN)
 #endif
+#if defined(FP_ABL_NO_SURE)
+        FP_FLAG_IF(FP_ABL_NO_SURE)
+#endif
 #if defined(FP_ABL_NO_GBN)
         FP_FLAG_IF(FP_ABL_NO_GBN)
 #endif

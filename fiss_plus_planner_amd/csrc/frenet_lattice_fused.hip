@@ -402,6 +402,20 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
     // Every statement of the kernel stands in a `// [section NAME]` pair - the bodies, and since the last census also the entry, the glue
     // between sections, the profile loop's own statements and the appended workgroups - so that tools/nonwalk_census.py can weigh all of it.
     constexpr bool kCut = kShape && !POLY;
+    // The walk's stage S (a blocked profile ends on one SURE hit, before prep, B and N - see the walk): kCut instances, three and four per CU.  Never a
+    // POLY instance: a ring lies inside its box, so a sure hit on the box proves nothing about the ring.
+    // -DFP_ABL_NO_SURE compiles the stage out: one source gives both sides of an A/B.
+#if defined(FP_ABL_NO_SURE)
+    constexpr bool kSure = false;
+#else
+    // (the four-per-CU instances with the appended search or the coefficient window - 63 of 64 VGPRs before - spill one VGPR with
+    // the stage and keep the statements they had; the plain four-per-CU instance, the headline's, holds it in 64)
+    // The two-per-CU instances (OCC 4: small batches, latency mode, the grouped 1024-thread launches) do not get it either: their
+    // launches leave the device underfilled and last as long as one profile's dependent chain, which S lengthens for every profile
+    // it does not end, while the issue slots it saves are not what bounds them - config 2 (5 x 5 x 5, 256 egos) measured 6 % slower
+    // with it although S ended three in four of its profiles (EXPERIMENTS.md).  S stands where launches run in rounds: three and four per CU.
+    constexpr bool kSure = kCut && OCC > 4 && !(OCC > 6 && (FISS || WIN));
+#endif
     // The argmin by one wavefront (ARGMIN below): every instance comes out smaller with it but the shaped polygon instance without a
     // window (80 VGPRs, all in use), which spills two VGPRs with it and keeps the statements it had.
     constexpr bool kArgWave = !(kShape && POLY && !WIN);
@@ -835,6 +849,17 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
     // [/section DALL]
     // [section GLUE]
     if (tid == 0) { s_k[0] = knot0; s_k[1] = inv_bucket_w; s_k[2] = veh_hl; s_k[3] = veh_hw; s_k[4] = r_ego; }
+    if constexpr (kSure) {
+        // stage S's threshold, squared: thr = rho (1 - 1e-9) - 1e-6 with rho = min(half length, half width), the radius of the disk
+        // inside the ego box at any heading (see the walk).  It stands in the unused fourth word of the first row circle (s_grp[0].pad:
+        // CIRCLES writes the other three, G reads past it; the row exists also with no rows) - s_k's twelve words are taken and one more
+        // would move every table behind it.  A thr that is not > 0 (a NaN size included) leaves -1: no squared distance is <= -1, S is silent.
+        // (entered on the scalar test, like the square root above: the other wavefronts pay no vector compare for it)
+        if (wave_s == 0 && tid == 0) {
+            const double thr = (veh_hl < veh_hw ? veh_hl : veh_hw) * (1.0 - 1e-9) - 1e-6, both = veh_hl + veh_hw;  // (fmin would drop a NaN)
+            s_grp[0].pad = thr > 0.0 && both == both ? thr * thr : -1.0;
+        }
+    }
     if (kEgoLds && !kEgoEarly && tid == 1) { s_k[5] = s0; s_k[6] = s_d0; s_k[7] = s_dd0; s_k[8] = d0; s_k[9] = d_d0; s_k[10] = d_dd0; s_k[11] = d_dd0 * 0.5; }
     // [/section GLUE]
     // [section POWS]
@@ -1124,6 +1149,9 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
             // (coefficient window: v_max bounds |P'| over the window's segments only - a range that leaves them keeps every obstacle)
             if (windowed && (!(s_lo >= s_knots[w0]) || !(s_hi <= s_knots[w0 + wcap < nx - 1 ? w0 + wcap : nx - 1]))) rad = __builtin_inf();
         }
+        // (field by field, never the whole record: with stage S the fourth word of row 0, s_grp[0].pad, holds S's squared threshold -
+        // written once per ego beside s_k - and a store of the whole ObsDim here would wipe it)
+        static_assert(sizeof(ObsDim) == 4 * sizeof(double) && offsetof(ObsDim, pad) == 3 * sizeof(double), "s_grp[0].pad is the record's fourth word (stage S's threshold)");
         s_grp[r].hl = cx;
         s_grp[r].hw = cy;
         s_grp[r].r = rad;
@@ -1364,6 +1392,80 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
                     const fan_t* dm = s_fan_d + mul24(it, hp_max);
                     const fan_t* ddm = s_fan_dd + mul24(it, hp_max);
     // [/section PQPTR]
+    // [section PQFETCH]
+                    // candidates of this profile that collided in an earlier item chunk (crowded scenes only; else 0)
+                    // (read here by the instances with stage S, which may end the profile at once; by the others behind prep, as before)
+                    auto coll_so_far = [&]() {
+                        return ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)s_collmask[2 * qg + 1]) << 32) |
+                               (uint32_t)__builtin_amdgcn_readfirstlane((int)s_collmask[2 * qg]);
+                    };
+#if defined(FP_ABL_NO_BN)
+                    const int n_walk = 0;
+#else
+                    const int n_walk = n_surv;
+#endif
+                    unsigned long long coll = 0;
+                    // ---- S: a SURE hit ends a blocked profile before prep, B and N.  lane = surviving item, in list (= time) order, 64 at a
+                    // time.  Three in four lon profiles of the headline batches are blocked - all nd lateral samples collide - and paid
+                    // prep, a B round and an N round (two quintics, two Frenet-to-Cartesian conversions, a heading and a 4-axis test per
+                    // (hit, lateral sample)) to learn it.  The proof here needs no heading, no quintic and no separating axis:
+                    //   (a) A box of half extents (hl, hw) contains, at ANY heading, the disk of radius rho = min(hl, hw) about its centre.
+                    //   (b) At pose k every one of the profile's nd ego centres is P_k + d n_k with |d| <= dm[k] (the fan bound B reads: the
+                    //       largest |d| over the lateral samples, rounded UP to fp32 / fp16, which only lengthens the segment), n_k = (-ty, tx):
+                    //       they lie on the segment between E- = P_k - dm n_k and E+ = P_k + dm n_k.
+                    //   (c) The distance from a point to a convex set - the obstacle's box - is a convex function of the point, so on a
+                    //       segment it is largest at an end.
+                    //   So if dist(E-, box) and dist(E+, box) are both <= thr = rho (1 - 1e-9) - 1e-6, then every centre of the fan is closer
+                    //   than rho to the box: its disk, hence its ego box, whatever its heading, meets the obstacle's box - the profile's nd
+                    //   candidates all collide at pose k, which is what N would find one pair at a time (its circle test holds a fortiori:
+                    //   the centres are closer than rho + the obstacle's radius).  coll = full, and the profile goes to PQEND as it does
+                    //   when N fills the mask.
+                    // |n_k| = 1 up to the frame's own rounding (spline_frame normalises the tangent: a few ulp), and N builds its centres from
+                    // the same frame.  What the 1e-6 m absorbs: the reference's and the kernel's centres differ by less than 1e-12 m; the
+                    // rounding of this stage's own dozen operations on coordinates of 1e3..1e5 m (below 1e-10 m); the relative 1e-9 is for
+                    // rho's.  The obstacle's (cos, sin) are the snapped ones N uses (SINCOS), its box the one N tests.
+                    // Every comparison fails on a NaN: the squared distances (frame, fan - d_nan -, pose) and the sum `fin` (sizes: max(NaN, 0)
+                    // would be 0) leave `sure` false, thr <= 0 or NaN is -1 in LDS.  Poses k >= M are never judged (their frames are stale).
+                    // A profile S does not end takes prep, B and N exactly as before.  The trip count is wave-uniform (scalar n_walk, coll)
+                    // and the ballot stands under no divergent branch (see WSETUP on the hang).
+                    if constexpr (kSure) {
+                        coll = coll_so_far();
+    // [/section PQFETCH]
+    // [section ROUNDS]
+                        for (int c0 = 0; c0 < n_walk && coll != full; c0 += kWave) {
+                            const int si = c0 + lane;
+                            bool sure = false;
+    // [/section ROUNDS]
+    // [section S]
+                            if (si < n_walk) {
+                                const int item = s_items[si];
+                                const int r = kItemShift > 0 ? item >> kItemShift : div_by<NOBS, ROWS * NOBS>(item, 1.0f / (float)n_obs);
+                                const int j = kItemShift > 0 ? item & ((1 << kItemShift) - 1) : item - mul24(r, n_obs);
+                                const int k = mul24(r, stride);
+                                const ObsPose op = s_spose.get(si);
+                                const double2 ohw = s_dim.hlw[j];
+                                const Frame fr = wfr.get(k);  // (stale beyond the profile's M: the test below excludes those poses)
+                                const double dmk = (double)dm[k], thr2 = s_grp[0].pad;
+                                const double ex = dmk * fr.ty, ey = dmk * fr.tx;  // E+- = (px -+ ex, py +- ey)
+                                const double dxp = (fr.px - ex) - op.x, dyp = (fr.py + ey) - op.y;
+                                const double dxm = (fr.px + ex) - op.x, dym = (fr.py - ey) - op.y;
+                                // in the obstacle's axes: u along its length, w along its width; q = the part of each outside the box
+                                const double ap = fabs(fma(dxp, op.c, dyp * op.s)) - ohw.x, bp = fabs(fma(dyp, op.c, -dxp * op.s)) - ohw.y;
+                                const double am = fabs(fma(dxm, op.c, dym * op.s)) - ohw.x, bm = fabs(fma(dym, op.c, -dxm * op.s)) - ohw.y;
+                                const double qxp = fmax(ap, 0.0), qyp = fmax(bp, 0.0), qxm = fmax(am, 0.0), qym = fmax(bm, 0.0);
+                                const double fin = ap + bp;  // (NaN if any input is: the frame, the fan and the pose enter both ends)
+                                sure = k < M && fma(qxp, qxp, qyp * qyp) <= thr2 && fma(qxm, qxm, qym * qym) <= thr2 && fin == fin;
+                            }
+    // [/section S]
+    // [section ROUNDS]
+                            if (lane == 0) FP_COUNT(4, 1);
+                            if (__ballot(sure)) {
+                                coll = full;
+                                if (lane == 0) FP_COUNT(8, 1);
+                            }
+                        }
+    // [/section ROUNDS]
+                    }
                     // ---- prep: wfat = lateral half-width of the whole fan along the reference normal n_k, per checked pose row r of this
                     // profile: every ego centre is P_k + d n_k with |d| <= dm[k];  the ego box, whose heading deviates from the
                     // reference tangent by alpha, reaches hw cos(alpha) + hl |sin(alpha)| <= min(r_ego, hw + hl sigma) along n_k, where
@@ -1374,6 +1476,8 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
                     {
                         const float r_ego_f = kShape ? r_ego_s : float_above(s_k[4]), hl_f = kShape ? hl_s : float_above(s_k[2]), hw_f = kShape ? hw_s : float_above(s_k[3]);
     // [section PREP]
+                        // (a profile S ended - or one that an earlier chunk blocked - needs no half-widths: a scalar test)
+                        if (!kSure || coll != full)
                         for (int r = lane; r < rows; r += kWave) {
                             const int k = mul24(r, stride);
                             const bool row_ok = k < n_pts && k < hp;
@@ -1399,15 +1503,8 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
     // [section PQFETCH]
                     }
                     wave_lds_sync();
-                    // candidates of this profile that collided in an earlier item chunk (crowded scenes only; else 0)
-                    unsigned long long coll = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)s_collmask[2 * qg + 1]) << 32) |
-                                              (uint32_t)__builtin_amdgcn_readfirstlane((int)s_collmask[2 * qg]);
+                    if constexpr (!kSure) coll = coll_so_far();
                     const double* qlat = s_qlat + 3 * mul24(it, nd);
-#if defined(FP_ABL_NO_BN)
-                    const int n_walk = 0;
-#else
-                    const int n_walk = n_surv;
-#endif
     // [/section PQFETCH]
     // [section ROUNDB]
                     for (int c0 = 0; c0 < n_walk && coll != full; c0 += kWave) {

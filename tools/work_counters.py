@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Work statistics of lattice_fused_kernel's collision stages per ego (build with EXTRA=-DFP_COUNTERS; run on the GPU box):
 items that survive the group test, rounds and hits of stage B, lane tests and rounds of the narrow phase, how many found a
-collision, and how many lon profiles ended their walk early."""
+collision, how many lon profiles ended their walk early in N, and the rounds of stage S and the profiles it ended."""
 import os
 os.environ.setdefault("FP_ALLOW_DIAGNOSTIC_BUILD", "1")  # runs against a library built with EXTRA=-DFP_...
 import sys
@@ -37,11 +37,12 @@ eng.plan_dense_device(params, fb, bi.data_ptr(), bc.data_ptr(), stream=st.cuda_s
                       traj_stride=128, traj_sparse=True)
 torch.cuda.synchronize()
 c = bt[:, 14, 112:128].cpu().numpy()
-names = ["G survivors (items)", "B wave rounds (64 items of one profile each)", "B pairs passed (hits)", "N lane tests (live candidates only)", "(slot 4: unused)",
-         "N lane tests that found a collision", "N wave rounds (floor(64 / nd) hits each)", "profiles whose walk ended early (all nd collided)"]
+names = ["G survivors (items)", "B wave rounds (64 items of one profile each)", "B pairs passed (hits)", "N lane tests (live candidates only)", "S wave rounds (64 items of one profile each)",
+         "N lane tests that found a collision", "N wave rounds (floor(64 / nd) hits each)", "profiles whose walk ended early in N (all nd collided)",
+         "profiles ended by S (a sure hit: before prep, B and N)"]
 print(f"config {config}, layout {layout}: per ego, {B} egos")
 for k, n in enumerate(names):
-    print(f"  {n:40s} mean {c[:, k].mean():9.1f}  median {np.median(c[:, k]):9.1f}  p90 {np.percentile(c[:, k], 90):9.1f}  max {c[:, k].max():9.0f}")
+    print(f"  {n:56s} mean {c[:, k].mean():9.1f}  median {np.median(c[:, k]):9.1f}  p90 {np.percentile(c[:, k], 90):9.1f}  max {c[:, k].max():9.0f}")
 print("  blocked profiles by the pose index at which the last lateral sample collided (bins of 8 steps = 0.8 s): " +
       "  ".join(f"k<{8 * (i + 1)}: {c[:, 10 + i].mean():.1f}" if i < 5 else f"k>=40: {c[:, 15].mean():.1f}" for i in range(6)) + "   (mean per ego)")
 print("  slices whose lon profiles needed the point-by-point mask scan: mean", round(float(c[:, 9].mean()), 2), "of", batch.nt)
