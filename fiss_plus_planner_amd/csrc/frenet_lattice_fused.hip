@@ -52,6 +52,9 @@ namespace {
 // emulation of the directed-rounding conversion (~15 instructions) where only a conservative bound is needed.
 __device__ __forceinline__ float float_above(double x) { return (float)x * 1.00000024f; }
 
+// the counterpart of frenet_device.h's vmin_f64: v_max_f64 without the canonicalising instruction in front of each fmax operand
+__device__ __forceinline__ double vmax_f64(double a, double b) { double r; asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+
 // monotone map fp32 -> uint32 (and back), so that LDS integer atomic min / max order floats of either sign
 __device__ __forceinline__ uint32_t f32_ordered(float f)
 {
@@ -381,8 +384,8 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
     __shared__ unsigned int s_walk_t[2];  // when the first / the last wavefront of the workgroup finished its profiles
 #endif
 #if defined(FP_COUNTERS)  // work statistics (tools/work_counters.py): LDS counters, left in row 14, columns 112.. of the winner block
-    __shared__ int s_dbg[16];
-    if (threadIdx.x < 16) s_dbg[threadIdx.x] = 0;
+    __shared__ int s_dbg[20];  // (16..19: stage V's groups ended, profiles that entered the walk, S rounds no lane's first end passed, the ended groups' bits)
+    if (threadIdx.x < 20) s_dbg[threadIdx.x] = 0;
 #define FP_COUNT(k, v) atomicAdd(&s_dbg[k], (int)(v))
 #else
 #define FP_COUNT(k, v) do { } while (0)
@@ -415,6 +418,22 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
     // it does not end, while the issue slots it saves are not what bounds them - config 2 (5 x 5 x 5, 256 egos) measured 6 % slower
     // with it although S ended three in four of its profiles (EXPERIMENTS.md).  S stands where launches run in rounds: three and four per CU.
     constexpr bool kSure = kCut && OCC > 4 && !(OCC > 6 && (FISS || WIN));
+#endif
+    // Stage V (whole end-speed GROUPS end on a sure hit before the walk - see VCIRC and VTEST): the instances with stage S.  It needs
+    // S's threshold and the speed bound of VBOUND.  -DFP_ABL_NO_GROUP compiles it out.
+    // Not the instance with the coefficient window (three per CU; the four-per-CU one has no S): with the stage its FRAMES - the path of
+    // a profile V does NOT end - came out ten vector instructions larger (75 > 85) and it spilled 16 SGPRs where it spilled none, so
+    // it keeps the statements it had.
+    // The same rule was knowingly NOT applied to the plain four-per-CU instance, the headline's, which also came out larger there
+    // (FRAMES 62 > 65, PREP 47 > 51, the loop's own statements +5, spilled SGPRs 15 > 31: about 12 vector instructions per walked
+    // profile, 0.3 k per ego) - it is the instance the stage was made for, V takes 38 of its 63 profiles out of the walk, and with
+    // that cost included it measured 15.8 % fewer vector instructions and 8 % less time (profiles/group_hit_valu_count.txt).  The
+    // cause is another register assignment around the mask read at the loop's head; reading only the mask's low word where nd <= 32
+    // was tried to shorten it (EXPERIMENTS.md).
+#if defined(FP_ABL_NO_GROUP) || defined(FP_ABL_NO_VMAX)
+    constexpr bool kGroup = false;
+#else
+    constexpr bool kGroup = kSure && !WIN;
 #endif
     // The argmin by one wavefront (ARGMIN below): every instance comes out smaller with it but the shaped polygon instance without a
     // window (80 VGPRs, all in use), which spills two VGPRs with it and keeps the statements it had.
@@ -480,6 +499,16 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
     int* s_cnt = (int*)(smem + L.cnt);
     int* s_nslice = (int*)(smem + L.nslice);
     Best* s_best = (Best*)(smem + L.best);
+    // Stage V's tables.  The group circles [end speed][row]{cx, cy, (thr - rad)^2, -} stand in the walk's frame tables, which are dead until
+    // the walk's barrier and again from its last barrier to the next item chunk's walk: VCIRC rebuilds them for every item chunk.
+    // The bound of |P''| (fp32 bits, a wave maximum like s_cnt[5]) stands in s_best[1]: s_cnt's eight words are taken, and a kArgWave
+    // instance - every kGroup instance is one - writes s_best[0] alone, after the last walk.
+    double* s_vcirc = (double*)(smem + L.frames);
+    uint32_t* s_vword = (uint32_t*)&s_best[1];
+    if constexpr (kGroup) {
+        constexpr int kHpMaxC = ROWS * STRIDE + 1 > FP_MAX_POINTS ? FP_MAX_POINTS : ROWS * STRIDE + 1;
+        static_assert(kArgWave && 32 * NV * ROWS <= 32 * kWaves * kHpMaxC && ND <= 64, "stage V: s_best[1] is free and the circles fit the frame tables");
+    }
     // {first knot, bucket width reciprocal, ego half length, half width, half diagonal; [5..10] ego start state, [11] d_dd0 / 2}: uniform FP64 values live in VECTOR registers
     // (the scalar unit has no FP64); kept in registers from the prologue to the last slice they cost the three-workgroup variant spills
     double* s_k = (double*)(smem + L.konst);
@@ -583,6 +612,7 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
         // bucket (the segment hint needs its loops); [5], [6]: fp32 bit patterns of the spline's speed bound and of the largest lateral offset;
         // [7]: kCut instances: the ends of the ego's v_samples, packed like [1] (see the row ranges)
         if (tid < 8) s_cnt[tid] = 0;
+        if (kGroup && tid == 8) s_vword[0] = 0u;
 #if defined(FP_PHASE_STAMPS)
         if (tid == 0) { s_walk_t[0] = 0xFFFFFFFFu; s_walk_t[1] = 0u; }
 #endif
@@ -702,11 +732,11 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
         if (tid == 0 && (windowed || !(inv_bucket_w > 0.0) || !(fmax(fabs(s_knots[0]), fabs(s_knots[nx - 1])) * inv_bucket_w < 1e-6 * 0x1p50))) s_cnt[4] = 1;
         for (int i0 = w0 + wave * kWave; i0 < seg_end; i0 += kThreads) {
             const int i = i0 + lane;
-            uint32_t bits = 0u;
+            uint32_t bits = 0u, bits2 = 0u;
             if (i < seg_end) {
                 const double h = s_knots[i + 1] - s_knots[i];
                 if (!(h * inv_bucket_w >= 1.0 + 1e-6)) atomicOr((unsigned int*)&s_cnt[4], 1u);
-                double m2 = 0.0;
+                double m2 = 0.0, w2 = 0.0;
 #pragma unroll
                 for (int ax = 0; ax < 2; ++ax) {
                     const double b1 = sp.coef[(4 * ax + 1) * ld + i], c2 = 2.0 * sp.coef[(4 * ax + 2) * ld + i], d3 = 3.0 * sp.coef[(4 * ax + 3) * ld + i];
@@ -715,8 +745,22 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
                     if (uv > 0.0 && uv < h) m = fmax(m, fabs(fma(fma(d3, uv, c2), uv, b1)));
                     if (!(m == m) || !(h == h)) m = __builtin_nan("");
                     m2 = fma(m, m, m2);
+                    if constexpr (kGroup) {  // stage V: |P''| - g'(u) = c2 + 2 d3 u is linear, extreme at the segment's ends
+                        double w = fmax(fabs(c2), fabs(fma(2.0 * d3, h, c2)));
+                        if (!(c2 == c2) || !(d3 == d3) || !(h == h)) w = __builtin_nan("");
+                        w2 = fma(w, w, w2);
+                    }
                 }
                 bits = __float_as_uint(float_above(sqrt(m2)) * 1.0000005f);
+                if constexpr (kGroup) bits2 = __float_as_uint(float_above(sqrt(w2)) * 1.0000005f);
+            }
+            if constexpr (kGroup) {  // (a NaN is the largest pattern: VCIRC then leaves every circle silent)
+#pragma unroll
+                for (int off = kWave / 2; off > 0; off >>= 1) {
+                    const uint32_t o2 = (uint32_t)__shfl_xor((int)bits2, off, kWave);
+                    bits2 = o2 > bits2 ? o2 : bits2;
+                }
+                if (lane == 0) atomicMax(&s_vword[0], bits2);
             }
 #pragma unroll
             for (int off = kWave / 2; off > 0; off >>= 1) {
@@ -740,6 +784,9 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
     for (int c = tid; c < 2 * nt * nv; c += kThreads) s_collmask[c] = 0u;
     for (int r = tid; r < rows; r += kThreads) {
         s_box[r] = make_uint4(kOrdPosInf, kOrdNegInf, kOrdPosInf, kOrdNegInf);  // empty
+        // stage V: the row's range of lateral offsets over every slice and lateral sample, two ordered fp32 words in the unused fourth
+        // word of the row's circle record (FAN fills them; row 0's word holds S's threshold, and at t = 0 every offset is d0)
+        if (kGroup && r >= 1) *(uint2*)&s_grp[r].pad = make_uint2(kOrdPosInf, kOrdNegInf);
     }
     // points whose frame the collision stage can touch: 0 .. hp-1 (pose k needs point k+1 for its heading)
     const int pose_limit = rows * stride < horizon_cap ? rows * stride : horizon_cap;  // poses k < pose_limit (and k < M)
@@ -1111,6 +1158,13 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
                 const double dn = fma(fma(fma(fma(fma(a5, tn, a4), tn, a3), tn, eDdd0() * 0.5), tn, eDd0()), tn, eD0());
                 // (a NaN offset poisons the bound: as an unsigned bit pattern NaN is the largest)
                 const float fd = float_above(fabs(d)), fdd = float_above(fabs(dn - d));
+                if constexpr (kGroup) {  // stage V: the signed range at the checked rows (to nearest: VCIRC adds the half ulp back; a NaN stays one)
+                    const int r_i = div_by<STRIDE, FP_MAX_POINTS>(i, 0.0f);
+                    if (i > 0 && i == mul24(r_i, STRIDE) && r_i < rows) {
+                        uint32_t* w = (uint32_t*)&s_grp[r_i].pad;
+                        atomicMin(w, f32_ordered((float)d)); atomicMax(w + 1, f32_ordered((float)d));
+                    }
+                }
                 dm = __float_as_uint(fd) > __float_as_uint(dm) ? fd : dm;
                 ddm = __float_as_uint(fdd) > __float_as_uint(ddm) ? fdd : ddm;
             }
@@ -1196,6 +1250,105 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
             // scene), kPoseFlight reads in flight per lane.  x = NaN / valid = 0: no state at this step (state_at_time -> None).
             // A survivor's pose goes to the list with its orientation still an angle.
     // [/section GLUE]
+    // [section VCIRC]
+            // ---- V, first half (once per ego and item chunk): one circle per (end speed iv, checked row r) that encloses the ego CENTRES of
+            // the whole end-speed GROUP at pose k = r stride - the lon profiles (it, iv) of every slice `it` of this workgroup, times every
+            // lateral sample.  VTEST (behind SINCOS) then tests each survivor of G against the nv circles of its row: a circle that lies
+            // within S's sure-hit distance `thr` of an obstacle's box ends the n_it profiles of the group before any frame of theirs.
+            // The horizon T moves a profile's first seconds by centimetres, the end speed by metres: the group is the tight unit.
+            //   Centre of candidate (it, iv, id), as N computes it:  C = P(s) + d n(s),  s = s_it(t_k),  d = d_{it,id}(t_k),  n = (-ty, tx).
+            //   [s_lo, s_hi]: range of the n_it values s - the expression FRAMES evaluates, operand for operand - with middle s_m and
+            //   half width hs;  [d_lo, d_hi]: range of d over the slices and the two EXTREME lateral samples (d is affine in its end offset
+            //   for a fixed horizon, see FAN), middle d_m, half width hd - the same for every end speed, so FAN, which evaluates those
+            //   offsets anyway, leaves it once per ego and row in s_grp[r].pad.  Circle centre  C0 = P(s_m) + d_m n(s_m).
+            //   C - C0 = (P(s) - P(s_m)) + (d - d_m) n(s) + d_m (n(s) - n(s_m)), hence
+            //   |C - C0| <= v_max hs + hd + |d_m| |n(s) - n(s_m)|          (v_max >= |P'| everywhere, VBOUND)
+            //   |n(s) - n(s_m)| = |T(s) - T(s_m)| <= |P'(s) - P'(s_m)| / min(|P'(s)|, |P'(s_m)|) <= A2 hs / (g - A2 hs)
+            //   with T = P' / |P'|, A2 >= |P''| everywhere (VBOUND; P' is continuous across knots), g = |P'(s_m)|: |u/|u| - v/|v|| <=
+            //   2 |u - v| / (|u| + |v|) for any two vectors, and |P'(s)| >= g - A2 hs.  A group whose g - A2 hs is not > 0 stays silent.
+            // Rounding: the middle samples' computed d can leave [d_lo, d_hi] by ~1e-15 m, FAN's fp32 ends are widened by their half ulp
+            // here, the frames are good to ~1e-12 m, v_max, A2 and the fp32 reciprocal of g - A2 hs are rounded up; the factors 1 + 1e-9 and the 1e-6 m below cover it as they do in CIRCLES, and thr carries S's own 1e-6.
+            // The row must be a pose of EVERY profile of the group: k < pose_limit (final_time_step, the table's rows) and k < the
+            // smallest M of the group, which must be >= 2 (a profile with M < 2 is never walked and must not be marked).  Every comparison
+            // fails on a NaN (a NaN sample, state, coefficient or size): the word stays -1 and VTEST is silent.  (No instance with a coefficient
+            // window has the stage - see kGroup; one that gets it must keep a range that leaves the window silent, as CIRCLES does.)
+            if constexpr (kGroup) {
+                const int n_circ = mul24(nv, rows);
+                if (wave_s * kWave < n_circ) {
+                    const int ends = s_cnt[1];
+                    const float inv_rows_v = 1.0f / (float)(rows > 0 ? rows : 1);
+                    // (the opaque copies of tid keep the lanes' addresses INSIDE the chunk loop, as in G: hoisted out of it they live through
+                    // the walk and spill four VGPRs of the four-per-CU instance)
+                    int tv = tid;
+                    asm volatile("" : "+v"(tv));
+                    for (int e = tv; e < n_circ; e += kThreads) {
+                        const int iv = div_small(e, inv_rows_v), r = e - mul24(iv, rows);
+                        const int k = mul24(r, stride);
+                        const double t = (double)k * tick;
+                        double s_lo = __builtin_inf(), s_hi = -__builtin_inf();
+                        int m_min = 0x7FFFFFFF;
+                        bool ok = (ends >> 16) == 0 && k < pose_limit;
+#pragma unroll 1
+                        for (int it = it_lo; it < it_hi; ++it) {
+                            const int qg = mul24(it, nv) + iv;
+                            const int Mq = s_lon_meta[qg].x;
+                            m_min = Mq < m_min ? Mq : m_min;
+                            const double a3 = s_qlon[2 * qg], a4 = s_qlon[2 * qg + 1];
+                            const double s = fma(fma(fma(fma(a4, t, a3), t, eSdd0() * 0.5), t, eSd0()), t, eS0());
+                            ok = ok && s == s;  // (fmin / fmax drop a NaN)
+                            s_lo = vmin_f64(s_lo, s); s_hi = vmax_f64(s_hi, s);
+                        }
+                        // the lateral range of the row: FAN's two words (rounded to nearest fp32: half an ulp each, covered by the slack)
+                        double d_lo = eD0(), d_hi = d_lo;
+                        if (r > 0) {
+                            const uint2 w = *(const uint2*)&s_grp[r].pad;
+                            const float lo_f = f32_from_ordered(w.x), hi_f = f32_from_ordered(w.y);
+                            const double slack = ((double)fabsf(lo_f) + (double)fabsf(hi_f)) * 1.2e-7 + 1e-9;
+                            d_lo = (double)lo_f - slack; d_hi = (double)hi_f + slack;
+                        }
+                        ok = ok && d_hi >= d_lo && d_hi - d_lo < 1e30;  // (an empty or a NaN range fails)
+                        ok = ok && m_min >= 2 && k < m_min;
+                        // (the ranges go through the circle's own record and the frame is a second pass of the same lane over it: held in
+                        // registers across the frame's coefficient reads they spill four VGPRs of the four-per-CU instance)
+                        const double s_m = 0.5 * (s_lo + s_hi), d_m = 0.5 * (d_lo + d_hi);
+                        double* o = s_vcirc + 4 * (mul24(iv, rows_max) + r);
+                        o[0] = s_m; o[1] = ok ? fmax(s_hi - s_m, s_m - s_lo) : -1.0; o[2] = d_m; o[3] = fmax(d_hi - d_m, d_m - d_lo);
+                    }
+                    wave_lds_sync();
+                    asm volatile("" : "+v"(tv));
+                    for (int e = tv; e < n_circ; e += kThreads) {
+                        const int iv = div_small(e, inv_rows_v), r = e - mul24(iv, rows);
+                        double* o = s_vcirc + 4 * (mul24(iv, rows_max) + r);
+                        const double s_m = o[0], hs = o[1];
+                        double cx = 0.0, cy = 0.0, t2 = -1.0;
+                        if (hs >= 0.0) {
+                            const int seg = s_cnt[4] == 0 ? lut_segment_step(s_knots, s_lut, nx, s_m, s_k[0], s_k[1], n_buckets)
+                                                          : lut_segment(s_knots, s_lut, nx, s_m, s_k[0], s_k[1], n_buckets);
+                            {
+                                const double u = s_m - s_knots[seg];
+                                const double* c = sp.coef + seg;
+                                // (spline_frame's expressions; the derivative's length g is needed beside the unit tangent)
+                                const double gx = fma(fma(3.0 * c[3 * ld], u, 2.0 * c[2 * ld]), u, c[ld]), gy = fma(fma(3.0 * c[7 * ld], u, 2.0 * c[6 * ld]), u, c[5 * ld]);
+                                const double g2 = fma(gx, gx, gy * gy), inv = rsqrt_nr(g2);
+                                const double v_max = (double)__uint_as_float((uint32_t)s_cnt[5]), A2 = (double)__uint_as_float(s_vword[0]);
+                                const double g = g2 * inv * (1.0 - 1e-9);
+                                const double bend = A2 * hs * (1.0 + 1e-9), m = g - bend;
+                                const double d_m = o[2], hd = o[3];
+                                // (1 / m from above in fp32, as PREP's sigma: v_rcp_f32 is good to 1 ulp, the factor covers it and the rounding of m)
+                                const double turn = bend * (double)(__builtin_amdgcn_rcpf((float)m) * (1.0f + 4e-6f));
+                                const double rad = (v_max * hs * (1.0 + 1e-9) + hd + fabs(d_m) * turn) * (1.0 + 1e-9) + 1e-6;
+                                const double thr = (s_k[2] < s_k[3] ? s_k[2] : s_k[3]) * (1.0 - 1e-9) - 1e-6;  // S's threshold (fmin would drop a NaN)
+                                const double room = thr - rad;
+                                cx = fma(-d_m, gy * inv, fma(fma(fma(c[3 * ld], u, c[2 * ld]), u, c[ld]), u, c[0]));
+                                cy = fma(d_m, gx * inv, fma(fma(fma(c[7 * ld], u, c[6 * ld]), u, c[5 * ld]), u, c[4 * ld]));
+                                if (m > 1e-30 && room > 0.0 && s_k[2] + s_k[3] == s_k[2] + s_k[3] && cx == cx && cy == cy) t2 = room * room;
+                            }
+                        }
+                        o[0] = cx; o[1] = cy; o[2] = t2;
+                    }
+                }
+            }
+    // [/section VCIRC]
     // [section G]
             const int i1 = i0 + chunk < n_items ? i0 + chunk : n_items;
             if constexpr (kCut) {
@@ -1300,8 +1453,42 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
                 double sn, cs;
                 sincos_snapped(s_spose.hi[si].x, sn, cs);
                 s_spose.hi[si] = make_double2(cs, sn);
-            }
     // [/section SINCOS]
+    // [section VTEST]
+                // ---- V, second half: the lane that snapped a survivor's orientation tests its box against the nv group circles of its row -
+                // the squared point-to-box distance of the circle's centre exactly as S computes it for a fan end (same pose, same
+                // half extents, same snapped (cos, sin)), against (thr - rad)^2.  dist(C0, box) <= thr - rad puts every ego centre of the
+                // group within thr < rho of the box: all n_it x nd candidates of the group collide at this pose (S's argument (a)).
+                // A survivor is a pose the table holds at a row below pose_limit; the circle is silent (-1) unless the row is a pose of
+                // every profile of the group.  Every comparison fails on a NaN.  A passing lane fills the collision masks of the group's
+                // profiles (the same words from every passing lane); the profile loop skips a full mask at its head.  No extra
+                // barrier: the circles were written before G's, the masks are read behind the walk's.  With item chunks the masks accumulate.
+                if constexpr (kGroup) {
+                    const int item = s_items[si];
+                    const int r = kItemShift > 0 ? item >> kItemShift : div_by<NOBS, ROWS * NOBS>(item, 1.0f / (float)n_obs);
+                    const int j = kItemShift > 0 ? item & ((1 << kItemShift) - 1) : item - mul24(r, n_obs);
+                    const double2 oxy = s_spose.lo[si], ohw = s_dim.hlw[j];
+                    const unsigned long long full_v = nd >= 64 ? ~0ull : ((1ull << nd) - 1ull);
+#pragma unroll 1
+                    for (int iv = 0; iv < nv; ++iv) {
+                        const double* c = s_vcirc + 4 * (mul24(iv, rows_max) + r);
+                        const double dx = c[0] - oxy.x, dy = c[1] - oxy.y;
+                        const double a = fabs(fma(dx, cs, dy * sn)) - ohw.x, bq = fabs(fma(dy, cs, -dx * sn)) - ohw.y;
+                        const double qx = fmax(a, 0.0), qy = fmax(bq, 0.0);
+                        const double fin = a + bq;
+                        if (fma(qx, qx, qy * qy) <= c[2] && fin == fin) {
+#if defined(FP_COUNTERS)  // (slot 19: one bit per end speed V ended, whichever chunk and however many lanes - slot 16 reports their number)
+                            atomicOr((unsigned int*)&s_dbg[19], 1u << (iv & 31));
+#endif
+                            for (int it = it_lo; it < it_hi; ++it) {
+                                const int qg = mul24(it, nv) + iv;
+                                s_collmask[2 * qg] = (uint32_t)full_v; s_collmask[2 * qg + 1] = (uint32_t)(full_v >> 32);
+                            }
+                        }
+                    }
+                }
+            }
+    // [/section VTEST]
     // [section WSETUP]
             // (the walk's barrier below orders these writes before stage B reads them)
             // No survivor (block-uniform: empty surroundings, obstacles out of reach): nothing can collide, the walk is skipped.
@@ -1362,6 +1549,20 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
                     const int it = it_lo + itl, qg = mul24(it, nv) + iv;
     // [/section PQDEC]
     // [section PQFETCH]
+                    // candidates of this profile that collided in an earlier item chunk (crowded scenes only; else 0) - or, stage V, whose
+                    // whole end-speed group VTEST ended: the mask is full and the profile is skipped here, on a scalar test, before its
+                    // frames.  (Profiles are dealt pq = wave, wave + kWaves, ... with iv = pq mod nv: an ended end speed thins every
+                    // wavefront's share alike.)
+                    auto coll_so_far = [&]() {
+                        return ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)s_collmask[2 * qg + 1]) << 32) |
+                               (uint32_t)__builtin_amdgcn_readfirstlane((int)s_collmask[2 * qg]);
+                    };
+                    unsigned long long coll = 0;
+                    if constexpr (kGroup) {
+                        coll = coll_so_far();
+                        if (coll == full) continue;
+                        if (lane == 0) FP_COUNT(17, 1);
+                    }
                     const int M = __builtin_amdgcn_readfirstlane(s_lon_meta[qg].x);  // (M <= N; wave-uniform -> scalar registers)
                     // a trajectory of fewer than two points has no heading: no pair (M == 1 is the assembly's business)
                     if (M < 2) continue;
@@ -1393,18 +1594,13 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
                     const fan_t* ddm = s_fan_dd + mul24(it, hp_max);
     // [/section PQPTR]
     // [section PQFETCH]
-                    // candidates of this profile that collided in an earlier item chunk (crowded scenes only; else 0)
-                    // (read here by the instances with stage S, which may end the profile at once; by the others behind prep, as before)
-                    auto coll_so_far = [&]() {
-                        return ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)s_collmask[2 * qg + 1]) << 32) |
-                               (uint32_t)__builtin_amdgcn_readfirstlane((int)s_collmask[2 * qg]);
-                    };
+                    // (the mask of the earlier item chunks is read here by the instances with stage S, which may end the profile at once -
+                    // those with stage V have it from the loop's head - and by the others behind prep, as before)
 #if defined(FP_ABL_NO_BN)
                     const int n_walk = 0;
 #else
                     const int n_walk = n_surv;
 #endif
-                    unsigned long long coll = 0;
                     // ---- S: a SURE hit ends a blocked profile before prep, B and N.  lane = surviving item, in list (= time) order, 64 at a
                     // time.  Three in four lon profiles of the headline batches are blocked - all nd lateral samples collide - and paid
                     // prep, a B round and an N round (two quintics, two Frenet-to-Cartesian conversions, a heading and a 4-axis test per
@@ -1429,12 +1625,15 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
                     // A profile S does not end takes prep, B and N exactly as before.  The trip count is wave-uniform (scalar n_walk, coll)
                     // and the ballot stands under no divergent branch (see WSETUP on the hang).
                     if constexpr (kSure) {
-                        coll = coll_so_far();
+                        if constexpr (!kGroup) coll = coll_so_far();
     // [/section PQFETCH]
     // [section ROUNDS]
                         for (int c0 = 0; c0 < n_walk && coll != full; c0 += kWave) {
                             const int si = c0 + lane;
                             bool sure = false;
+#if defined(FP_COUNTERS)
+                            bool first_end = false;  // (the E- end alone: a round in which no lane passes it skips the second end's instructions)
+#endif
     // [/section ROUNDS]
     // [section S]
                             if (si < n_walk) {
@@ -1455,10 +1654,16 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
                                 const double qxp = fmax(ap, 0.0), qyp = fmax(bp, 0.0), qxm = fmax(am, 0.0), qym = fmax(bm, 0.0);
                                 const double fin = ap + bp;  // (NaN if any input is: the frame, the fan and the pose enter both ends)
                                 sure = k < M && fma(qxp, qxp, qyp * qyp) <= thr2 && fma(qxm, qxm, qym * qym) <= thr2 && fin == fin;
+#if defined(FP_COUNTERS)
+                                first_end = k < M && fma(qxp, qxp, qyp * qyp) <= thr2;
+#endif
                             }
     // [/section S]
     // [section ROUNDS]
                             if (lane == 0) FP_COUNT(4, 1);
+#if defined(FP_COUNTERS)
+                            if (!__ballot(first_end) && lane == 0) FP_COUNT(18, 1);
+#endif
                             if (__ballot(sure)) {
                                 coll = full;
                                 if (lane == 0) FP_COUNT(8, 1);
@@ -1673,6 +1878,7 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
 #if defined(FP_COUNTERS)
     __syncthreads();
     if (tid < 16 && ka.r.best_traj) ka.r.best_traj[((size_t)b * FP_ARR_COUNT + 14) * (ka.r.traj_stride > 0 ? ka.r.traj_stride : FP_DEFAULT_STRIDE) + 112 + tid] = (double)s_dbg[tid];
+    if (tid >= 16 && tid < 20 && ka.r.best_traj) ka.r.best_traj[((size_t)b * FP_ARR_COUNT + 13) * (ka.r.traj_stride > 0 ? ka.r.traj_stride : FP_DEFAULT_STRIDE) + 112 + tid - 16] = (double)(tid == 16 ? __popc((unsigned int)s_dbg[19]) : s_dbg[tid]);  // (row 13: row 14 is full; 16 = groups ended by V, counted from slot 19's bits)
 #endif
     // ---------------------------------------------------------------- per-candidate assembly + argmin
     // From here on the kernel's arguments are read through `la`: for the four-per-CU instances (80 SGPRs) a view of the argument segment the
