@@ -8,8 +8,6 @@ import numpy as np
 import adversarial as A
 from fiss_plus_planner_amd import synth
 
-SHAPE_997 = (9, 9, 7, 2, 50, 25)
-
 
 def base997(seed, B=12, **kw):
     return synth.make_batch(B, 9, 9, 7, 50, 50, True, seed, layout="survey8d", **kw)

@@ -12,13 +12,9 @@ import numpy as np
 import adversarial as A
 import prologue_cases as P
 from fiss_plus_planner_amd import synth
+from prologue_cases import base997
 
-SHAPE_997, SHAPE_555 = (9, 9, 7, 2, 50, 25), (5, 5, 5, 2, 10, 50)
 K_LATE = 48  # the last checked step of the 9 x 9 x 7 shape (25 rows, stride 2)
-
-
-def base997(seed, B=12, **kw):
-    return synth.make_batch(B, 9, 9, 7, 50, 50, True, seed, layout="survey8d", **kw)
 
 
 def base555(seed, B=12):

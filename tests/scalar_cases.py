@@ -13,7 +13,6 @@ import adversarial as A
 import prologue_cases as P
 from fiss_plus_planner_amd import synth
 
-SHAPE_997, SHAPE_555 = (9, 9, 7, 2, 50, 25), (5, 5, 5, 2, 10, 50)
 B = 8
 T_NOW_SHORT = 25   # 50-step table, stride 2: ceil((50 - 25) / 2) = 13 rows staged of the 25 compiled in
 HORIZON_CAP = 21   # final_time_step - t_now: ceil(21 / 2) = 11 rows checked, pose_limit 21, hp 22

@@ -6,9 +6,8 @@ and its proof-or-scan speed / acceleration / range masks (1e-9 margins, phase A0
 the reference finds; a proof that is not a proof clears a candidate the reference rejects.  The reference semantics are
 planners/frenet_optimal_planner.py:140-160 (constraints), :168-208 (collision), :106-138 (truncation).
 
-The multi-round instances (three / four workgroups per compute unit: 80 / 64 VGPRs, the slim 40 KB layout with fp16 fan bounds) only
-run on batches of more than 512 / 768 egos on a whole MI355X; fp_ctx_set_option("resident_groups", 2) models a one-CU device, so a
-handful of egos - what the oracle can check in seconds - takes exactly those instances (asserted through the launch counters).
+Every scene runs through tests/lattice_paths.py's MODES (the multi-round instances - three / four workgroups per compute unit: 80 / 64
+VGPRs, the slim 40 KB layout with fp16 fan bounds - on a handful of egos, asserted through the launch counters); cost within 1e-6.
 """
 import os
 
@@ -16,41 +15,11 @@ import numpy as np
 import pytest
 
 import adversarial as A
+import lattice_paths as L
 from fiss_plus_planner_amd import synth
 
 pytestmark = pytest.mark.gpu
 SEEDS = int(os.environ.get("FP_ADVERSARIAL_SEEDS", "12"))
-
-# (label, ctx options, which per-CU launch counter must move)
-MODES = [
-    ("two per CU, latency split", {"lattice_kernel": 2}, "lattice_launches_2"),
-    ("two per CU, one workgroup per ego", {"lattice_kernel": 2, "lattice_split": 1}, "lattice_launches_2"),
-    ("three per CU", {"lattice_kernel": 2, "resident_groups": 2, "lattice_occupancy": 3}, "lattice_launches_3"),
-    ("four per CU (slim layout; three when the 40 KB layout does not hold the shape)", {"lattice_kernel": 2, "resident_groups": 2}, "lattice_launches_4|lattice_launches_3"),
-    ("lane per candidate", {"lattice_kernel": 1}, None),
-]
-RESET = {"lattice_kernel": 0, "lattice_split": 0, "resident_groups": 0, "lattice_occupancy": 0}
-
-
-def run_modes(engine, batch, ref, what, modes=MODES, winner=True):
-    try:
-        for label, opts, counter in modes:
-            for k, v in {**RESET, **opts}.items():
-                engine.set_option(k, v)
-            before = sum(engine.get_option(c) for c in counter.split("|")) if counter else 0
-            out = engine.plan_dense(batch, winner=winner)
-            if counter:
-                assert sum(engine.get_option(c) for c in counter.split("|")) > before, f"{what}: '{label}' did not take its instance"
-            for e, r in enumerate(ref):
-                bad = np.nonzero(out.flags[e] != r.flags)[0]
-                assert bad.size == 0, (f"{what} [{label}] ego {e}: {bad.size} flag words differ, first candidate {bad[0]}: "
-                                       f"got {out.flags[e][bad[0]]:#x} want {r.flags[bad[0]]:#x}")
-                np.testing.assert_allclose(out.cost[e], r.cost, rtol=0, atol=1e-6, err_msg=f"{what} [{label}] ego {e}")
-                assert out.best_idx[e] == r.best_idx, (what, label, e)
-    finally:
-        for k, v in RESET.items():
-            engine.set_option(k, v)
-
 
 def shapes(seed):
     """BASELINE's dense shape (the shaped instances), an odd one (the run-time-shape instances) and, every sixth seed, BASELINE's shape on
@@ -67,14 +36,13 @@ def test_obstacles_within_a_millimetre_of_contact(oracle, engine, seed):
     base = shapes(seed)
     gaps = (1e-6, 1e-5, 1e-4, 1e-3) if seed % 3 else (1e-6, 3e-6)
     batch, placed = A.contact_scene(oracle, base, 100 + seed, gaps=gaps)
-    ref = [p.fop_plan() for p in oracle.problems_from_batch(batch)]
+    ref = L.reference(oracle, batch)
     # the generator did what it says: most placements decide their candidate's collision bit by the sign of the gap
     decisive = sum(bool(ref[e].flags[c] & 4) == (eps < 0) for e, c, _k, _j, eps in placed)
     assert len(placed) >= batch.B and decisive >= 0.4 * len(placed), (len(placed), decisive)   # (a sanity check of the generator, not of the kernels)
-    n_coll = sum(int(((r.flags & 4) != 0).sum()) for r in ref)
-    assert 0 < n_coll < batch.B * batch.C
+    assert 0 < L.colliding(ref) < batch.B * batch.C
     before4 = engine.get_option("lattice_launches_4")
-    run_modes(engine, batch, ref, f"contact scene seed {seed}")
+    L.through_modes(ref, engine, batch, f"contact scene seed {seed}", L.MODES, cost="abs1e-6")
     if seed % 2 == 0:  # BASELINE's dense shape (81-knot lines, or 220 knots through the WIN instance): the slim four-per-CU layout (fp16 fan bounds) was attacked
         assert engine.get_option("lattice_launches_4") > before4
 
@@ -87,11 +55,10 @@ def test_polygon_obstacles_within_a_millimetre_of_contact(oracle, engine, seed):
     base = shapes(seed)
     batch, placed = A.contact_scene(oracle, base, 1100 + seed, polygons=0.7, gaps=(1e-6, 1e-5, 1e-4, 1e-3) if seed % 2 else (1e-6, 2e-6))
     assert batch.obs_nvert is not None and (batch.obs_nvert > 0).sum() >= batch.B // 2
-    ref = [p.fop_plan() for p in oracle.problems_from_batch(batch)]
+    ref = L.reference(oracle, batch)
     decisive = sum(bool(ref[e].flags[c] & 4) == (eps < 0) for e, c, _k, _j, eps in placed)
     assert decisive >= 0.35 * len(placed), (len(placed), decisive)
-    poly_modes = [m for m in MODES if "four per CU" not in m[0]] + [("three per CU (no cap)", {"lattice_kernel": 2, "resident_groups": 2}, "lattice_launches_3")]
-    run_modes(engine, batch, ref, f"polygon contact scene seed {seed}", modes=poly_modes)
+    L.through_modes(ref, engine, batch, f"polygon contact scene seed {seed}", L.POLY_MODES, cost="abs1e-6")
 
 
 @pytest.mark.parametrize("seed", range(max(2, SEEDS // 2)))
@@ -103,25 +70,25 @@ def test_contact_at_the_edge_of_the_fan_with_t_now_and_short_horizons(oracle, en
     base = A._copy(base, t_now=rng.integers(0, 12, base.B), final_time_step=rng.integers(base.T_obs - 14, base.T_obs + 3, len(base.final_time_step)).astype(np.int32),
                    check_stride=int(rng.choice([1, 3])))
     batch, placed = A.contact_scene(oracle, base, 300 + seed)
-    ref = [p.fop_plan() for p in oracle.problems_from_batch(batch)]
+    ref = L.reference(oracle, batch)
     assert len(placed) >= batch.B // 2
-    run_modes(engine, batch, ref, f"contact scene (t_now, stride {batch.check_stride}) seed {seed}")
+    L.through_modes(ref, engine, batch, f"contact scene (t_now, stride {batch.check_stride}) seed {seed}", L.MODES, cost="abs1e-6")
 
 
 @pytest.mark.parametrize("seed", range(max(2, SEEDS // 2)))
 def test_limits_at_a_candidates_own_extreme(oracle, engine, seed):
     base = shapes(seed)
     for batch, what in A.limit_batch(oracle, base, 500 + seed):
-        ref = [p.fop_plan() for p in oracle.problems_from_batch(batch)]
-        run_modes(engine, batch, ref, what, modes=MODES[1:], winner=False)
+        ref = L.reference(oracle, batch)
+        L.through_modes(ref, engine, batch, what, L.MODES[1:], winner=False, cost="abs1e-6")
 
 
 @pytest.mark.parametrize("seed", range(max(2, SEEDS // 2)))
 def test_egos_at_the_ends_of_the_reference_line(oracle, engine, seed):
     base = synth.make_batch(24, 9, 9, 7, 50, 50, True, 7100 + seed, layout="survey8d") if seed % 2 == 0 else synth.make_batch(24, 5, 6, 3, 12, 40, True, 7100 + seed)
     batch = A.spline_end_batch(base, 700 + seed)
-    ref = [p.fop_plan() for p in oracle.problems_from_batch(batch)]
+    ref = L.reference(oracle, batch)
     M = np.concatenate([(r.flags >> 20) for r in ref])
     N = np.concatenate([(r.flags >> 8) & 0xFFF for r in ref])
     assert (M == 0).any() and (M == 1).any() and ((M > 1) & (M < N)).any() and (M == N).any()  # every truncation case is in the batch
-    run_modes(engine, batch, ref, f"spline ends seed {seed}")
+    L.through_modes(ref, engine, batch, f"spline ends seed {seed}", L.MODES, cost="abs1e-6")

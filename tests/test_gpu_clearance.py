@@ -1,5 +1,5 @@
 """GPU: the obstacle-clearance cost term (fp_params.w_obstacle) against its independent restatement (tests/clearance_ref.py: oracle
-tables + brute-force distances).  Costs within the project's bar (|d| <= 1e-9 max(1, |ref|), tests/test_gpu_edges.py::cost_close),
+tables + brute-force distances).  Costs within the project's bar (|d| <= 1e-9 max(1, |ref|), tests/lattice_paths.py: cost_close),
 flags and Stats exact, best_idx exact for every ego.  tests/test_clearance_cpu.py shows that the cases could not pass by returning the
 plain winner.
 
@@ -18,7 +18,7 @@ from conftest import assert_series_close, load_golden
 from fiss_plus_planner_amd import _abi, synth
 from fiss_plus_planner_amd.engine import host_structs
 from test_clearance_cpu import CASES, W_TEST
-from test_gpu_edges import cost_close
+from lattice_paths import cost_close
 
 pytestmark = pytest.mark.gpu
 

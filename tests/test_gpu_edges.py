@@ -12,17 +12,13 @@ import numpy as np
 import pytest
 
 import exact_cost as X
+import lattice_paths as L
 from conftest import assert_series_close
 from fiss_plus_planner_amd import _abi, synth
 from fiss_plus_planner_amd.batch import ProblemBatch
 from fiss_plus_planner_amd.engine import make_params
-from test_gpu_adversarial import MODES, run_modes
 
 pytestmark = pytest.mark.gpu
-# the instances every row's shapes take: with one ego, or a scene whose layout does not fit a third / quarter of the CU's LDS, the three- and
-# four-per-CU requests run two per CU (their counters do not move), so the rows below use these three and the lane-per-candidate kernel
-EDGE_MODES = [MODES[0], MODES[1], MODES[4]]
-RESET = {"lattice_kernel": 0, "lattice_split": 0, "resident_groups": 0, "lattice_occupancy": 0, "lattice_group": 0, "lattice_winner": 0}
 
 
 def horizon(N, tick=0.1):
@@ -62,32 +58,8 @@ def with_horizons(batch, Ts, ego_kick=False, seed=0):
     return ProblemBatch(**kw, meta=dict(batch.meta, horizons=[float(t) for t in Ts]))
 
 
-def set_opts(engine, opts):
-    for k, v in {**RESET, **opts}.items():
-        engine.set_option(k, v)
-
-
-def reset(engine):
-    for k, v in RESET.items():
-        engine.set_option(k, v)
-
-
-def cost_close(got, want, what):
-    """Costs within 1e-9 of the oracle's (relative beyond magnitude 1: a one-point trajectory's jerk term reaches 1e10); NaN where NaN."""
-    got, want = np.asarray(got), np.asarray(want)
-    assert np.array_equal(np.isnan(got), np.isnan(want)), what
-    m = ~np.isnan(want)
-    bad = np.abs(got[m] - want[m]) > 1e-9 * np.maximum(1.0, np.abs(want[m]))
-    assert not bad.any(), f"{what}: {got[m][bad][:4]} vs {want[m][bad][:4]}"
-
-
 def check_dense(out, ref, what):
-    for e, r in enumerate(ref):
-        bad = np.nonzero(out.flags[e] != r.flags)[0]
-        assert bad.size == 0, f"{what} ego {e}: {bad.size} flag words differ, first {bad[0]}: {out.flags[e][bad[0]]:#x} vs {r.flags[bad[0]]:#x}"
-        cost_close(out.cost[e], r.cost, f"{what} ego {e}")
-        assert out.best_idx[e] == r.best_idx, (what, e)
-        np.testing.assert_array_equal(out.stats[e], r.stats, err_msg=f"{what} ego {e}")
+    L.compare(out, ref, what, cost="relative")
 
 
 def exact_costs(batch, egos=None, cands=None):
@@ -145,31 +117,28 @@ def test_points_per_trajectory_dense(oracle, engine, Ns, label):
     exact = exact_costs(batch, egos=range(4))
     # the oracle meets the bar the kernels are held to
     assert_exact(np.stack([r.cost for r in ref]), exact, f"oracle ({label})")
-    if min(Ns) > 2:  # (run_modes' absolute 1e-6 bar: one- and two-point trajectories cost ~1e10, checked relatively below)
-        run_modes(engine, batch, ref, f"points {Ns}", modes=EDGE_MODES, winner=False)
-    try:
-        for opts, what in (({"lattice_kernel": 2}, "fused"), ({"lattice_kernel": 2, "lattice_split": 1}, "fused, one workgroup per ego"),
-                           ({"lattice_kernel": 1}, "lattice_percand"), ({}, "default")):
-            set_opts(engine, opts)
+    if min(Ns) > 2:  # (the absolute 1e-6 bar: one- and two-point trajectories cost ~1e10, checked relatively below)
+        L.through_modes(ref, engine, batch, f"points {Ns}", L.EDGE_MODES, winner=False, cost="abs1e-6")
+    for opts, what in (({"lattice_kernel": 2}, "fused"), ({"lattice_kernel": 2, "lattice_split": 1}, "fused, one workgroup per ego"),
+                       ({"lattice_kernel": 1}, "lattice_percand"), ({}, "default")):
+        with L.options(engine, opts):
             out = engine.plan_dense(batch)
-            check_dense(out, ref, f"{what} {Ns}")
-            w = assert_exact(out.cost, exact, f"{what} {Ns}")
-            assert w <= X.REL_BAR
-        stride = 256
-        for lw in (1, 2):
-            set_opts(engine, {"lattice_winner": lw})
+        check_dense(out, ref, f"{what} {Ns}")
+        w = assert_exact(out.cost, exact, f"{what} {Ns}")
+        assert w <= X.REL_BAR
+    stride = 256
+    for lw in (1, 2):
+        with L.options(engine, {"lattice_winner": lw}):
             wo = engine.plan_dense(batch, tables=False, winner=True, traj_stride=stride)
-            assert np.array_equal(wo.best_idx, [r.best_idx for r in ref])
-            assert series_check(oracle, batch, wo.best_idx, wo.best_traj, stride, f"winner series (lattice_winner {lw}) {Ns}") >= 1
-    finally:
-        reset(engine)
+        assert np.array_equal(wo.best_idx, [r.best_idx for r in ref])
+        assert series_check(oracle, batch, wo.best_idx, wo.best_traj, stride, f"winner series (lattice_winner {lw}) {Ns}") >= 1
     # eval_trajs: every candidate of two egos as explicit end states; costs exact to the bar, N / M / flags as the oracle's
     es = np.array([[[batch.d_samples[c // (batch.nv * batch.nt)], batch.v_samples[e, c % batch.nv], batch.t_samples[(c // batch.nv) % batch.nt]]
                     for c in range(batch.C)] for e in range(batch.B)])
     ev = engine.eval_trajs(batch, es, dump=True, traj_stride=stride)
     for e, r in enumerate(ref):
         np.testing.assert_array_equal(ev.flags[e], r.flags, err_msg=f"eval_trajs ego {e}")
-        cost_close(ev.cost[e], r.cost, f"eval_trajs ego {e}")
+        L.cost_close(ev.cost[e], r.cost, f"eval_trajs ego {e}")
     assert_exact(ev.cost, exact, f"eval_trajs {Ns}")
     for e in (0, 1):
         for c in range(0, batch.C, 7):
@@ -195,15 +164,12 @@ def test_points_a_horizon_just_below_an_integer_number_of_ticks(oracle, engine):
     assert all(n == round(T / 0.1) + 1 for T, n in above)
     Ts = sorted({below[0][0], below[-1][0], above[-1][0]})
     batch = with_horizons(synth.make_batch(3, 3, 3, len(Ts), 6, 260, True, 3200), Ts)
-    ref = [p.fop_plan() for p in oracle.problems_from_batch(batch)]
+    ref = L.reference(oracle, batch)
     for T in Ts:
         assert math.ceil(T / 0.1) == len(np.arange(0.0, T, 0.1))
-    try:
-        for opts in ({"lattice_kernel": 2}, {"lattice_kernel": 1}):
-            set_opts(engine, opts)
+    for opts in ({"lattice_kernel": 2}, {"lattice_kernel": 1}):
+        with L.options(engine, opts):
             check_dense(engine.plan_dense(batch), ref, f"T just below / above k ticks {opts}")
-    finally:
-        reset(engine)
 
 
 def test_points_past_the_limit_are_refused(engine):
@@ -238,7 +204,7 @@ def test_fiss_refinement_up_to_256_points(oracle, engine):
             assert np.isnan(out.best_cost[e]) == np.isnan(r.best_cost)
             if np.isnan(r.best_cost):
                 continue
-            cost_close(out.best_cost[e], r.best_cost, f"{kind} ego {e}")
+            L.cost_close(out.best_cost[e], r.best_cost, f"{kind} ego {e}")
             es = out.end_state[e]
             ex = X.cost_total(fb.ego[e], es[0], es[1], es[2], fb.tick_t, fb.target_speed[e])
             assert X.rel_err(out.best_cost[e], ex) <= X.REL_BAR, (kind, e, out.best_cost[e], float(ex))
@@ -258,21 +224,14 @@ def test_fiss_refinement_up_to_256_points(oracle, engine):
 
 # ---------------------------------------------------------------------------------------------------- dense-pass limits
 def _fused_refuses(engine, batch):
-    engine.set_option("lattice_kernel", 2)
-    try:
-        with pytest.raises(_abi.FrenetGpuError):
-            engine.plan_dense(batch)
-    finally:
-        reset(engine)
+    with L.options(engine, {"lattice_kernel": 2}), pytest.raises(_abi.FrenetGpuError):
+        engine.plan_dense(batch)
 
 
-def _fused_takes(oracle, engine, batch, ref, what, modes=EDGE_MODES):
-    run_modes(engine, batch, ref, what, modes=modes, winner=False)
-    set_opts(engine, {"lattice_kernel": 2})
-    try:
+def _fused_takes(oracle, engine, batch, ref, what, modes=L.EDGE_MODES):
+    L.through_modes(ref, engine, batch, what, modes, winner=False, cost="abs1e-6")
+    with L.options(engine, {"lattice_kernel": 2}):
         out = engine.plan_dense(batch)
-    finally:
-        reset(engine)
     check_dense(out, ref, what)
     return out
 
@@ -286,8 +245,8 @@ def test_largest_dense_lattice(oracle, engine):
     """C = 64 x 16 x 16 = FP_MAX_CAND = 16384 (nd = 64: one lane per lateral sample), every mode; 16385 = 5 x 29 x 113: FP_ELIMIT."""
     batch = synth.make_batch(1, 64, 16, 16, 6, 50, True, 3500)
     assert batch.C == _abi.FP_MAX_CAND
-    ref = [p.fop_plan() for p in oracle.problems_from_batch(batch)]
-    _fused_takes(oracle, engine, batch, ref, "C = FP_MAX_CAND", modes=EDGE_MODES)
+    ref = L.reference(oracle, batch)
+    _fused_takes(oracle, engine, batch, ref, "C = FP_MAX_CAND")
     past = synth.make_batch(1, 5, 29, 113, 6, 50, True, 3501)
     assert past.C == _abi.FP_MAX_CAND + 1
     with pytest.raises(_abi.FrenetGpuError, match="FP_MAX_CAND") as ex:
@@ -316,13 +275,10 @@ def test_grouped_slices_profile_index(oracle, engine):
     one and the plain instance; both through the fused kernel (it does not refuse: the group shrinks) and equal to the oracle."""
     for nv in (128, 129):
         batch = synth.make_batch(2, 3, nv, 4, 8, 50, True, 3800 + nv)
-        ref = [p.fop_plan() for p in oracle.problems_from_batch(batch)]
+        ref = L.reference(oracle, batch)
         for opts in ({"lattice_kernel": 2, "lattice_group": 99}, {"lattice_kernel": 2, "lattice_group": 99, "lattice_split": 1}):
-            set_opts(engine, opts)
-            try:
+            with L.options(engine, opts):
                 out = engine.plan_dense(batch)
-            finally:
-                reset(engine)
             check_dense(out, ref, f"grouped nv = {nv} {opts}")
 
 
@@ -340,7 +296,7 @@ def test_obstacle_count(oracle, engine):
         batch = _scene(1, n_obs, 30, 3900 + n_obs)
         rows = min(math.ceil(128 / 2), math.ceil(batch.T_obs / 2))
         assert rows * n_obs <= 65535
-        ref = [p.fop_plan() for p in oracle.problems_from_batch(batch)]
+        ref = L.reference(oracle, batch)
         assert any(((r.flags & 4) != 0).any() for r in ref)
         _fallback(oracle, engine, batch, ref, f"n_obs = {n_obs}")
 
@@ -354,9 +310,9 @@ def test_row_obstacle_pairs_16bit(oracle, engine):
         assert cap == 256
         rows = min(math.ceil(cap / batch.check_stride), math.ceil(batch.T_obs / batch.check_stride))
         assert rows * n_obs == (65535 if fused else 65536)
-        ref = [p.fop_plan() for p in oracle.problems_from_batch(batch)]
+        ref = L.reference(oracle, batch)
         if fused:
-            _fused_takes(oracle, engine, batch, ref, f"rows x n_obs = {rows} x {n_obs}", modes=[MODES[0], MODES[4]])
+            _fused_takes(oracle, engine, batch, ref, f"rows x n_obs = {rows} x {n_obs}", modes=[L.MODES[0], L.MODES[4]])
         else:
             _fallback(oracle, engine, batch, ref, f"rows x n_obs = {rows} x {n_obs}")
 
@@ -387,14 +343,11 @@ def test_polygon_ring_vertices(oracle, engine):
 
     batch = shaped(128)
     assert batch.obs_poly.shape[2] == _abi.FP_MAX_POLY_VERTS and set(batch.obs_nvert.ravel().tolist()) == {0, 3, 4, 128}
-    ref = [p.fop_plan() for p in oracle.problems_from_batch(batch)]
+    ref = L.reference(oracle, batch)
     assert any(((r.flags & 4) != 0).any() for r in ref)
     for opts in ({"lattice_kernel": 2}, {"lattice_kernel": 1}, {}):
-        set_opts(engine, opts)
-        try:
+        with L.options(engine, opts):
             check_dense(engine.plan_dense(batch), ref, f"poly rings {opts}")
-        finally:
-            reset(engine)
     past = shaped(129)
     with pytest.raises(_abi.FrenetGpuError, match="FP_MAX_POLY_VERTS") as ex:
         engine.plan_dense(past)
@@ -416,7 +369,7 @@ def test_device_search_walk_at_its_limit(oracle, engine):
             r = pr.fissplus_plan() if kind == "FISS+" else pr.fiss_plan()
             np.testing.assert_array_equal(out.stats[e], r.stats, err_msg=f"{kind} ego {e}")
             np.testing.assert_array_equal(out.best_ijk[e], r.best_ijk, err_msg=f"{kind} ego {e}")
-            cost_close(out.best_cost[e], r.best_cost, f"{kind} ego {e}")
+            L.cost_close(out.best_cost[e], r.best_cost, f"{kind} ego {e}")
     assert P.FissPlusPlanner(P.FissPlusPlannerSettings(16, 16, 16), Vehicle(), None, engine=engine)._device_walk()
     past = synth.make_batch(1, 10, 10, 41, 10, 50, True, 4201, kind="FISS+")
     assert past.C > _abi.FP_MAX_CAND_SEARCH
@@ -437,7 +390,7 @@ def test_device_calls_size_themselves_from_points_max(oracle, engine):
 
     for pm, n_ok, n_past in ((0, 128, 129), (200, 200, 201)):
         batch = with_horizons(synth.make_batch(4, 3, 3, 2, 6, 260, True, 4300 + pm), [horizon(n_ok), horizon(n_past)])
-        ref = [p.fop_plan() for p in oracle.problems_from_batch(batch)]
+        ref = L.reference(oracle, batch)
         db = DeviceBatch(batch, 0)
         params = make_params(batch)
         params.points_max = pm
@@ -451,7 +404,7 @@ def test_device_calls_size_themselves_from_points_max(oracle, engine):
         for e, r in enumerate(ref):
             fit = it == 0
             np.testing.assert_array_equal(flags[e, fit], r.flags[fit], err_msg=f"points_max {pm} ego {e}")
-            cost_close(cost[e, fit], r.cost[fit], f"points_max {pm} ego {e}")
+            L.cost_close(cost[e, fit], r.cost[fit], f"points_max {pm} ego {e}")
             assert np.isnan(cost[e, ~fit]).all(), (pm, e)
             assert ((flags[e, ~fit] & _abi.FLAG_INFEASIBLE) != 0).all(), (pm, e)
         es = torch.tensor([[[0.0, 5.0, horizon(n_ok)], [0.0, 5.0, horizon(n_past)]]] * B, dtype=torch.float64, device=db.dev)

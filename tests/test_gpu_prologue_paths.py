@@ -13,12 +13,12 @@ code that deals their work to lanes and wavefronts can go wrong (tests/prologue_
 * uniforms       values only some wavefronts compute: a line with all knots in one place (bucket width 0), a windowed launch on a
                  220-knot line, veh_l == veh_w.
 
-Every case runs through the two-, three- and four-per-CU instances (tests/test_gpu_adversarial.py's MODES, launch counters asserted)
-and is compared with the oracle: flag words, Stats and the selected index exact, cost within 1e-9 (test_gpu_walk_decode.check)."""
+Every case runs through the two-, three- and four-per-CU instances (tests/lattice_paths.py's MODES, launch counters asserted)
+and is compared with the oracle: flag words, Stats and the selected index exact, cost within 1e-9 (lattice_paths.shaped_case)."""
 import pytest
 
+import lattice_paths as L
 import prologue_cases as P
-from test_gpu_walk_decode import assert_compiled_in_shape, check, colliding
 
 pytestmark = pytest.mark.gpu
 
@@ -27,10 +27,4 @@ pytestmark = pytest.mark.gpu
 def test_prologue_case_through_every_instance(oracle, engine, name):
     batch = P.CASES[name]()
     assert 8 <= batch.B <= 16
-    if name in P.SHAPED:
-        assert_compiled_in_shape(batch, P.SHAPE_997)
-    before4 = engine.get_option("lattice_launches_4")
-    ref = check(oracle, engine, batch, name)
-    assert 0 < colliding(ref) < batch.B * batch.C
-    if name in P.SHAPED:  # (BASELINE's dense shape: the slim four-per-CU layout holds it, also behind a coefficient window)
-        assert engine.get_option("lattice_launches_4") > before4
+    L.shaped_case(oracle, engine, batch, name, L.SHAPE_997 if name in P.SHAPED else None, L.MODES)

@@ -13,44 +13,30 @@ inputs of tests/range_argmin_cases.py.
                wins), no obstacles (the smallest layout), the 1024-thread grouped instances.
 
 Every case runs through the two-per-CU instances in latency mode (the partial argmins of several workgroups) and with one workgroup per
-ego, the three- and four-per-CU instances in rounds with a split tail (tests/test_gpu_adversarial.py's MODES, launch counters asserted)
+ego, the three- and four-per-CU instances in rounds with a split tail (tests/lattice_paths.py's MODES, launch counters asserted)
 and the lane-per-candidate kernel, and is compared with the oracle: flag words, Stats and the selected index exact, cost within 1e-9
-(test_gpu_walk_decode.check)."""
+(lattice_paths.through_modes)."""
 import pytest
 
+import lattice_paths as L
 import range_argmin_cases as R
-from test_gpu_adversarial import MODES
-from test_gpu_walk_decode import assert_compiled_in_shape, check, colliding
 
 pytestmark = pytest.mark.gpu
-# (the 5 x 5 x 5 shape's 50 rows of frames do not fit a third of a CU's LDS: its shaped instances run two per CU)
-MODES_555 = [m for m in MODES if m[2] in ("lattice_launches_2", None)]
-GROUPED = [("grouped, 1024 threads", {"lattice_kernel": 2, "lattice_group": 99}, "lattice_launches_2"),
-           ("grouped, one workgroup per ego", {"lattice_kernel": 2, "lattice_group": 99, "lattice_split": 1}, "lattice_launches_2")]
 
 
 @pytest.mark.parametrize("name", list(R.RANGE_CASES))
 def test_row_range_case_through_every_instance(oracle, engine, name):
     batch = R.RANGE_CASES[name]()
-    if name in R.SHAPED_997:
-        assert_compiled_in_shape(batch, R.SHAPE_997)
-    elif name in R.SHAPED_555:
-        assert_compiled_in_shape(batch, R.SHAPE_555)
-    before4 = engine.get_option("lattice_launches_4")
-    ref = check(oracle, engine, batch, name, MODES_555 if name in R.SHAPED_555 else MODES)
-    assert 0 < colliding(ref) < batch.B * batch.C
-    if name in R.SHAPED_997:
-        assert engine.get_option("lattice_launches_4") > before4
+    shape = L.SHAPE_997 if name in R.SHAPED_997 else L.SHAPE_555 if name in R.SHAPED_555 else None
+    L.shaped_case(oracle, engine, batch, name, shape, L.modes_for(batch, tail=False))
 
 
 @pytest.mark.parametrize("name", list(R.ARGMIN_CASES))
 def test_argmin_case_through_every_instance(oracle, engine, name):
     batch = R.ARGMIN_CASES[name]()
-    ref = check(oracle, engine, batch, name, MODES_555 if batch.nd == 5 else MODES)
+    ref = L.shaped_case(oracle, engine, batch, name, None, L.modes_for(batch, tail=False), decides=name not in R.NO_OBSTACLES)
     if name in R.NO_OBSTACLES:
-        assert colliding(ref) == 0
-    else:
-        assert 0 < colliding(ref) < batch.B * batch.C
+        assert L.colliding(ref) == 0
 
 
 @pytest.mark.parametrize("name", ["9 x 9 x 7, v_samples permuted", "mirror tie across two wavefronts' shares (9 x 9 x 7)",
@@ -60,7 +46,4 @@ def test_grouped_launch(oracle, engine, name):
     pose table's 16 KB).  That such a launch takes a grouped instance is pinned where launches are decided: rows `grouped_997` and
     `grouped_runtime` of tests/test_lattice_plan_cpu.py (a batch without obstacles has the run-time shape)."""
     batch = {**R.RANGE_CASES, **R.ARGMIN_CASES}[name]()
-    try:
-        check(oracle, engine, batch, name, GROUPED)
-    finally:
-        engine.set_option("lattice_group", 0)
+    L.through_modes(oracle, engine, batch, name, L.GROUPED, winner=False)

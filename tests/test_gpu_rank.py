@@ -11,7 +11,8 @@ import rank_ref as R
 from conftest import load_golden, batch_from_golden
 from fiss_plus_planner_amd import _abi, synth
 from fiss_plus_planner_amd.engine import host_structs
-from test_gpu_edges import cost_close, series_check
+from lattice_paths import cost_close
+from test_gpu_edges import series_check
 from test_rank_cpu import FIXTURES, oracle_tables, tie_batch
 
 pytestmark = pytest.mark.gpu

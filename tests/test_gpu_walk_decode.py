@@ -17,7 +17,7 @@
                uniform lines, lines with several knots inside one bucket, the ego exactly on a knot and exactly on a bucket edge, and
                arclengths so large (1e10 m) that the spacing margin no longer covers their rounding: those take the loops too.
 
-Every case runs through the two-, three- and four-per-CU instances (tests/test_gpu_adversarial.py's MODES: "resident_groups" 2 models
+Every case runs through the two-, three- and four-per-CU instances (tests/lattice_paths.py's MODES: "resident_groups" 2 models
 a one-CU device, so a dozen egos take them; asserted through the launch counters) and is compared with the oracle: flag words, Stats and
 the selected index exact, cost within 1e-9."""
 import numpy as np
@@ -26,56 +26,16 @@ import pytest
 import math
 
 import adversarial as A
+import lattice_paths as L
 from fiss_plus_planner_amd import synth
 from fiss_plus_planner_amd.engine import make_params
 from fiss_plus_planner_amd.spline import build_frames
-from test_gpu_adversarial import MODES, RESET
 
 pytestmark = pytest.mark.gpu
-COST_TOL = 1e-9
 
 
-def check(oracle, engine, batch, what, modes=MODES):
-    ref = [p.fop_plan() for p in oracle.problems_from_batch(batch)]
-    try:
-        for label, opts, counter in modes:
-            for k, v in {**RESET, **opts}.items():
-                engine.set_option(k, v)
-            before = sum(engine.get_option(c) for c in counter.split("|")) if counter else 0
-            out = engine.plan_dense(batch)
-            if counter:
-                assert sum(engine.get_option(c) for c in counter.split("|")) > before, f"{what}: '{label}' did not take its instance"
-            for e, r in enumerate(ref):
-                np.testing.assert_array_equal(out.flags[e], r.flags, err_msg=f"{what} [{label}] ego {e}: flag words")
-                np.testing.assert_array_equal(out.stats[e], r.stats, err_msg=f"{what} [{label}] ego {e}: Stats")
-                np.testing.assert_allclose(out.cost[e], r.cost, rtol=0, atol=COST_TOL, err_msg=f"{what} [{label}] ego {e}")
-                assert out.best_idx[e] == r.best_idx, (what, label, e)
-    finally:
-        for k, v in RESET.items():
-            engine.set_option(k, v)
-    return ref
-
-
-def rows_of(batch):
-    """Checked pose rows, by the host's own formula (fused_shape, frenet_lattice_plan.h)."""
-    from fiss_plus_planner_amd import _abi
-
-    cap = make_params(batch).points_max or _abi.FP_FAST_POINTS  # (0: no trajectory of the batch has more than the fast path's points)
-    return min(math.ceil(cap / batch.check_stride), math.ceil(batch.T_obs / batch.check_stride))
-
-
-def assert_compiled_in_shape(batch, shape):
-    """The batch has one of the two shapes the kernel is instantiated for (kLatticeShapes): the launch planner then names the shaped
-    instance of whichever family and occupancy it picks, and with it the packed item code."""
-    got = (batch.nd, batch.nv, batch.nt, batch.check_stride, batch.n_obs, rows_of(batch))
-    assert got == shape, got
-
-
-SHAPE_997, SHAPE_555 = (9, 9, 7, 2, 50, 25), (5, 5, 5, 2, 10, 50)
-
-
-def colliding(ref):
-    return sum(int(((r.flags & 4) != 0).sum()) for r in ref)
+def check(oracle, engine, batch, what, modes=L.MODES):
+    return L.through_modes(oracle, engine, batch, what, modes, winner=False)
 
 
 # ---------------------------------------------------------------- item codes
@@ -84,13 +44,7 @@ def test_packed_item_codes_of_the_shaped_instances(oracle, engine, shape):
     """BASELINE's two compiled-in shapes: 25 rows x 50 obstacles (6 bits of obstacle) and 50 rows x 10 obstacles (4 bits)."""
     batch = (synth.make_batch(12, 9, 9, 7, 50, 50, True, 8101, layout="survey8d") if shape == "997" else
              synth.make_batch(12, 5, 5, 5, 10, 100, True, 8102))
-    assert_compiled_in_shape(batch, SHAPE_997 if shape == "997" else SHAPE_555)
-    before = engine.get_option("lattice_launches_4")
-    # (the 5 x 5 x 5 shape's 50 rows of frames do not fit a third of a CU's LDS with these lines: its shaped instance runs two per CU)
-    ref = check(oracle, engine, batch, f"shaped {shape}", MODES if shape == "997" else [m for m in MODES if m[2] in ("lattice_launches_2", None)])
-    assert 0 < colliding(ref) < batch.B * batch.C
-    if shape == "997":
-        assert engine.get_option("lattice_launches_4") > before
+    L.shaped_case(oracle, engine, batch, f"shaped {shape}", L.SHAPE_997 if shape == "997" else L.SHAPE_555, L.modes_for(batch, tail=False))
 
 
 @pytest.mark.parametrize("n_obs,stride", [(1, 2), (31, 1), (32, 2), (33, 3), (63, 1), (64, 2), (65, 3)])
@@ -99,7 +53,7 @@ def test_item_codes_around_the_powers_of_two(oracle, engine, n_obs, stride):
     batch = A._copy(base, check_stride=stride)
     ref = check(oracle, engine, batch, f"{n_obs} obstacles, stride {stride}")
     if n_obs > 1:
-        assert colliding(ref) > 0
+        assert L.colliding(ref) > 0
 
 
 @pytest.mark.parametrize("stride", [1, 2, 3])
@@ -113,21 +67,21 @@ def test_a_single_checked_row(oracle, engine, stride):
         pose[int(base.scene_of[b]), :, ::2, 0], pose[int(base.scene_of[b]), :, ::2, 1], pose[int(base.scene_of[b]), :, ::2, 2] = px[0, 0], py[0, 0], yaw[0, 0]
     batch = A._copy(base, check_stride=stride, obs_pose=pose, final_time_step=np.full(len(base.final_time_step), 1, dtype=np.int32))
     ref = check(oracle, engine, batch, f"one row, stride {stride}")
-    assert colliding(ref) > 0
+    assert L.colliding(ref) > 0
 
 
 @pytest.mark.parametrize("stride", [2, 3])
 def test_the_most_rows_a_stride_allows(oracle, engine, stride):
     """256 points per trajectory and a 256-step pose table: 128 rows at stride 2, 86 at stride 3, with 511 / 762 obstacles - the row x
     obstacle table within a row of its 65535 entries.  One ego, a layout of ~100 KB: two per CU and the lane-per-candidate kernel."""
-    from test_gpu_edges import EDGE_MODES, _scene, horizon
+    from test_gpu_edges import _scene, horizon
 
     rows_want = math.ceil(256 / stride)
     n_obs = 65535 // rows_want
     batch = _scene(1, n_obs, 256, 8350 + stride, stride=stride, Ts=[horizon(200), horizon(256)])
-    assert make_params(batch).points_max == 256 and rows_of(batch) == rows_want and 65535 - rows_want < rows_want * n_obs <= 65535
-    ref = check(oracle, engine, batch, f"{rows_want} rows x {n_obs} obstacles, stride {stride}", EDGE_MODES)
-    assert colliding(ref) > 0
+    assert make_params(batch).points_max == 256 and L.rows_of(batch) == rows_want and 65535 - rows_want < rows_want * n_obs <= 65535
+    ref = check(oracle, engine, batch, f"{rows_want} rows x {n_obs} obstacles, stride {stride}", L.EDGE_MODES)
+    assert L.colliding(ref) > 0
 
 
 # ---------------------------------------------------------------- last point
@@ -156,8 +110,8 @@ def test_an_obstacle_on_the_last_point_of_a_line_that_ends_early(oracle, engine,
     assert (M == 2).any() and (M == 3).any() and ((M > 3) & (M < N) & (M % 2 == 0)).any() and ((M > 3) & (M < N) & (M % 2 == 1)).any() and (M == N).any()
     assert (coll & (M >= 2) & (M < N)).any() and (~coll & (M == N)).any()
     if shaped:
-        assert_compiled_in_shape(batch, SHAPE_997)
-    k_last = (rows_of(batch) - 1) * batch.check_stride  # a profile with M <= k_last + 1 can have a checked pose on its last point
+        L.assert_compiled_in_shape(batch, L.SHAPE_997)
+    k_last = (L.rows_of(batch) - 1) * batch.check_stride  # a profile with M <= k_last + 1 can have a checked pose on its last point
     mixed = [e for e, r in enumerate(ref) if ((r.flags >> 20 >= 2) & (r.flags >> 20 <= k_last + 1)).any() and (r.flags >> 20 > k_last + 1).any()]
     assert mixed, "no ego whose profiles end both inside and behind the checked rows"
     for e in mixed:  # ... spread over the end speeds, so that each of the 8 wavefronts (profile pq = slice * nv + end speed, dealt pq % 8) gets both
@@ -193,7 +147,7 @@ def test_segment_hint_on_uniform_and_on_crowded_knots(oracle, engine, shaped, kn
     base = (synth.make_batch(12, 9, 9, 7, 50, 50, True, 8501, layout="survey8d") if shaped else
             synth.make_batch(12, 5, 6, 3, 12, 40, True, 8502, layout="survey8d"))
     if shaped:
-        assert_compiled_in_shape(base, SHAPE_997)
+        L.assert_compiled_in_shape(base, L.SHAPE_997)
     NX = base.NX
     uniform = np.linspace(0.0, 400.0, NX)
     rng = np.random.default_rng(8503)
@@ -215,7 +169,7 @@ def test_segment_hint_on_uniform_and_on_crowded_knots(oracle, engine, shaped, kn
     crowded = (np.diff(batch.knots, axis=1) < w_b[:, None]).any(axis=1)
     assert crowded.all() == (knots == "clustered") and crowded.any() == (knots != "uniform")
     ref = check(oracle, engine, batch, f"{knots} knots ({'shaped' if shaped else 'run-time shape'})")
-    assert 0 < colliding(ref) < batch.B * batch.C
+    assert 0 < L.colliding(ref) < batch.B * batch.C
 
 
 @pytest.mark.parametrize("shaped", [True, False])
@@ -226,7 +180,7 @@ def test_segment_hint_far_from_the_arclength_origin(oracle, engine, shaped):
     base = (synth.make_batch(12, 9, 9, 7, 50, 50, True, 8601, layout="survey8d") if shaped else
             synth.make_batch(12, 5, 6, 3, 12, 40, True, 8602, layout="survey8d"))
     if shaped:
-        assert_compiled_in_shape(base, SHAPE_997)
+        L.assert_compiled_in_shape(base, L.SHAPE_997)
     knots, ego = base.knots.copy(), base.ego.copy()
     far = np.arange(base.B) % 2 == 0
     knots[base.frame_of[far]] += 1e10
@@ -236,4 +190,4 @@ def test_segment_hint_far_from_the_arclength_origin(oracle, engine, shaped):
     assert (np.abs(batch.knots[base.frame_of[far]]).max(axis=1) * 2.0 ** -50 > 1e-6 * w_b[base.frame_of[far]]).all()
     assert (np.abs(batch.knots[base.frame_of[~far]]).max(axis=1) * 2.0 ** -50 < 1e-6 * w_b[base.frame_of[~far]]).all()
     ref = check(oracle, engine, batch, f"arclength offset 1e10 ({'shaped' if shaped else 'run-time shape'})")
-    assert any(((r.flags & 4) != 0).any() for r, f in zip(ref, far) if f) and 0 < colliding(ref) < batch.B * batch.C
+    assert any(((r.flags & 4) != 0).any() for r, f in zip(ref, far) if f) and 0 < L.colliding(ref) < batch.B * batch.C

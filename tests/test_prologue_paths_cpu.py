@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 import prologue_cases as P
-from fiss_plus_planner_amd.engine import make_params
+from lattice_paths import SHAPE_997, coll_of, rows_of, shape_of
 
 
 @pytest.fixture(scope="module")
@@ -21,16 +21,11 @@ def plans(oracle):
     return get
 
 
-def rows_of(batch):
-    cap = make_params(batch).points_max or 128
-    return min(math.ceil(cap / batch.check_stride), math.ceil(batch.T_obs / batch.check_stride))
-
-
 @pytest.mark.parametrize("name", list(P.CASES))
 def test_every_case_has_a_colliding_and_a_free_candidate(plans, name):
     batch, ref = plans(name)
     assert 8 <= batch.B <= 16
-    coll = np.concatenate([(r.flags & 4) != 0 for r in ref])
+    coll = coll_of(ref)
     assert coll.any() and (~coll).any(), (name, int(coll.sum()), coll.size)
     assert any(r.best_idx >= 0 for r in ref), name
 
@@ -38,7 +33,7 @@ def test_every_case_has_a_colliding_and_a_free_candidate(plans, name):
 @pytest.mark.parametrize("name", sorted(P.SHAPED))
 def test_shaped_cases_have_the_compiled_in_shape(name):
     batch = P.CASES[name]()
-    assert (batch.nd, batch.nv, batch.nt, batch.check_stride, batch.n_obs, rows_of(batch)) == P.SHAPE_997
+    assert shape_of(batch) == SHAPE_997
 
 
 def test_run_time_tables_are_no_multiple_of_a_pass():

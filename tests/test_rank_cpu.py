@@ -15,7 +15,7 @@ FIXTURES = {"5x5x5": lambda: synth.make_batch(64, 5, 5, 5, 10, 100, True, 101),
             "9x9x7": lambda: synth.make_batch(64, 9, 9, 7, 50, 100, True, 7),
             "9x9x7 free": lambda: synth.make_batch(32, 9, 9, 7, 0, 100, True, 11)}
 K_ALL = _abi.FP_MAX_RANK + 1  # "the first 65": every position a K = 64 list can hold and the one behind it
-NEAR = 2e-9  # twice the project's 1e-9 cost bar (tests/test_gpu_edges.py::cost_close), once per side
+NEAR = 2e-9  # twice the project's 1e-9 cost bar (tests/lattice_paths.py: cost_close), once per side
 
 
 def oracle_tables(oracle, batch):

@@ -8,7 +8,7 @@ import pytest
 
 import prologue_cases as P
 import scalar_cases as S
-from fiss_plus_planner_amd.engine import make_params
+from lattice_paths import SHAPE_555, SHAPE_997, coll_of, rows_of, shape_of
 
 
 @pytest.fixture(scope="module")
@@ -23,19 +23,6 @@ def plans(oracle):
     return get
 
 
-def rows_of(batch):
-    cap = make_params(batch).points_max or 128
-    return min(math.ceil(cap / batch.check_stride), math.ceil(batch.T_obs / batch.check_stride))
-
-
-def shape_of(batch):
-    return (batch.nd, batch.nv, batch.nt, batch.check_stride, batch.n_obs, rows_of(batch))
-
-
-def coll_of(ref):
-    return np.stack([(r.flags & 4) != 0 for r in ref])
-
-
 @pytest.mark.parametrize("name", list(S.CASES))
 def test_every_case_decides_something(plans, name):
     batch, ref = plans(name)
@@ -43,8 +30,8 @@ def test_every_case_decides_something(plans, name):
     coll = coll_of(ref)
     assert coll.any() and (~coll).any(), (name, int(coll.sum()), coll.size)
     assert any(r.best_idx >= 0 for r in ref), name
-    want = S.SHAPE_997 if name in S.SHAPED_997 else S.SHAPE_555 if name in S.SHAPED_555 else None
-    assert (shape_of(batch) == want) if want else (shape_of(batch) not in (S.SHAPE_997, S.SHAPE_555) and batch.nv != batch.nd)
+    want = SHAPE_997 if name in S.SHAPED_997 else SHAPE_555 if name in S.SHAPED_555 else None
+    assert (shape_of(batch) == want) if want else (shape_of(batch) not in (SHAPE_997, SHAPE_555) and batch.nv != batch.nd)
 
 
 def _staged(batch):
