@@ -1249,6 +1249,9 @@ const char* fp_build_flags(void)
 #if defined(FP_ABL_NO_GROUP)
         FP_FLAG_IF(FP_ABL_NO_GROUP)
 #endif
+#if defined(FP_ABL_NO_WHOLE)
+        FP_FLAG_IF(FP_ABL_NO_WHOLE)
+#endif
 #if defined(FP_ABL_NO_GBN)
         FP_FLAG_IF(FP_ABL_NO_GBN)
 #endif

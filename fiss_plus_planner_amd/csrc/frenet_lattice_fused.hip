@@ -384,8 +384,8 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
     __shared__ unsigned int s_walk_t[2];  // when the first / the last wavefront of the workgroup finished its profiles
 #endif
 #if defined(FP_COUNTERS)  // work statistics (tools/work_counters.py): LDS counters, left in row 14, columns 112.. of the winner block
-    __shared__ int s_dbg[20];  // (16..19: stage V's groups ended, profiles that entered the walk, S rounds no lane's first end passed, the ended groups' bits)
-    if (threadIdx.x < 20) s_dbg[threadIdx.x] = 0;
+    __shared__ int s_dbg[22];  // (16..19: stage V's groups ended, profiles that entered the walk, S rounds no lane's first end passed, the ended groups' bits; 20, 21: stage W - workgroups that took WEXIT, and those of them whose assembly was skipped too)
+    if (threadIdx.x < 22) s_dbg[threadIdx.x] = 0;
 #define FP_COUNT(k, v) atomicAdd(&s_dbg[k], (int)(v))
 #else
 #define FP_COUNT(k, v) do { } while (0)
@@ -434,6 +434,18 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
     constexpr bool kGroup = false;
 #else
     constexpr bool kGroup = kSure && !WIN;
+#endif
+    // Stage W (a WHOLE ego ends: every candidate of the workgroup's slices collides - see WEXIT): the instances with stage V, whose full
+    // masks are the verdict, less the one with the appended search.  -DFP_ABL_NO_WHOLE compiles it out.
+    // Not a FISS instance: W skips the argmin WITH its workgroup barrier, and in those instances that barrier is part of the hand-over
+    // to the ego's search workgroup - every thread's table stores are acknowledged (s_waitcnt) BEFORE it, thread 0 raises the flag
+    // BEHIND it (see the template's comment).  Without it thread 0 could raise the flag while other wavefronts still store their rows.
+    // Those instances always write the tables, so W could only ever take the argmin off them; they keep the parent's statements.
+    // (In the other instances the tables are read by later kernels or the host, behind the kernel's end.)
+#if defined(FP_ABL_NO_WHOLE)
+    constexpr bool kWhole = false;
+#else
+    constexpr bool kWhole = kGroup && !FISS;
 #endif
     // The argmin by one wavefront (ARGMIN below): every instance comes out smaller with it but the shaped polygon instance without a
     // window (80 VGPRs, all in use), which spills two VGPRs with it and keeps the statements it had.
@@ -1873,12 +1885,43 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
             i0 = i1;
         }
     }
+    // [/section POSTWALK]
+    // [section WEXIT]
+    // ---- W: a WHOLE ego has its answer when every collision mask of the workgroup's slices is full - VTEST ended all nv end-speed groups,
+    // or S and N filled what it left.  The assembly flags every candidate of these slices as colliding whatever else it finds, none can
+    // reach the argmin: this workgroup's answer is "none", Best{., -1}.  Each wavefront reads the n_it nv mask words for itself, one
+    // lane per lon profile (contiguous: qg = it_lo nv + pq), behind the last walk's closing barrier - nothing stores a mask after it,
+    // so the verdict is the same in every wavefront, the branches on it are block-uniform and no barrier is added.  An ego with no
+    // survivor of G, or a profile V never marks (M < 2) and the walk never enters, has an open mask and goes the way it went.
+    bool whole = false;
+    if constexpr (kWhole) {
+        if (collide) {
+            const unsigned long long full_w = nd >= 64 ? ~0ull : ((1ull << nd) - 1ull);
+            const int n_prof_w = mul24(n_it, nv);
+            bool open = false;  // some profile of the slices has a candidate that is not known to collide
+            for (int e0 = 0; e0 < n_prof_w; e0 += kWave) {
+                const int e = e0 + lane;
+                bool lane_open = false;
+                if (e < n_prof_w) {
+                    const uint2 m = ((const uint2*)s_collmask)[mul24(it_lo, nv) + e];
+                    lane_open = m.x != (uint32_t)full_w || m.y != (uint32_t)(full_w >> 32);
+                }
+                open = open || __ballot(lane_open) != 0ull;
+            }
+            whole = !open;
+#if defined(FP_COUNTERS)
+            if (tid == 0 && whole) { FP_COUNT(20, 1); FP_COUNT(21, !ka.r.cost_tbl && !ka.r.flag_tbl); }
+#endif
+        }
+    }
+    // [/section WEXIT]
+    // [section POSTWALK]
 
     FP_STAMP(8);
 #if defined(FP_COUNTERS)
     __syncthreads();
     if (tid < 16 && ka.r.best_traj) ka.r.best_traj[((size_t)b * FP_ARR_COUNT + 14) * (ka.r.traj_stride > 0 ? ka.r.traj_stride : FP_DEFAULT_STRIDE) + 112 + tid] = (double)s_dbg[tid];
-    if (tid >= 16 && tid < 20 && ka.r.best_traj) ka.r.best_traj[((size_t)b * FP_ARR_COUNT + 13) * (ka.r.traj_stride > 0 ? ka.r.traj_stride : FP_DEFAULT_STRIDE) + 112 + tid - 16] = (double)(tid == 16 ? __popc((unsigned int)s_dbg[19]) : s_dbg[tid]);  // (row 13: row 14 is full; 16 = groups ended by V, counted from slot 19's bits)
+    if (tid >= 16 && tid < 22 && ka.r.best_traj) ka.r.best_traj[((size_t)b * FP_ARR_COUNT + 13) * (ka.r.traj_stride > 0 ? ka.r.traj_stride : FP_DEFAULT_STRIDE) + 112 + tid - 16] = (double)(tid == 16 ? __popc((unsigned int)s_dbg[19]) : s_dbg[tid]);  // (row 13: row 14 is full; 16 = groups ended by V, counted from slot 19's bits)
 #endif
     // ---------------------------------------------------------------- per-candidate assembly + argmin
     // From here on the kernel's arguments are read through `la`: for the four-per-CU instances (80 SGPRs) a view of the argument segment the
@@ -1893,7 +1936,18 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
     Best mine{0.0, -1};
     const float inv_nv_a = 1.0f / (float)nv, inv_nt_a = 1.0f / (float)nt;
     // [/section POSTWALK]
+    // [section WEXIT]
+    // A whole-blocked ego (the verdict above) with no table requested: the assembly's only outputs would be the tables, and no
+    // candidate of these slices can reach the argmin - both are skipped and RESULTS is entered with Best{., -1}, this workgroup's
+    // "none" (the tail split's ticket and merge, the hand-over flags, Stats and `dur` are RESULTS' as before).  With tables the
+    // assembly runs as it is - its flag words and costs are outputs - and only the argmin, which has nothing to reduce, is skipped:
+    // with it goes its workgroup barrier, which orders nothing in a kWhole instance (no search workgroup reads the tables inside
+    // the launch, RESULTS' thread 0 reads its own `mine`, a split ego's ticket has barriers of its own).
+    // (`whole` is false wherever kWhole is.)
+    const bool whole_quiet = whole && !kb.r.cost_tbl && !kb.r.flag_tbl;
+    // [/section WEXIT]
     // [section ASM]
+    if (!whole_quiet)
     for (int c = tid; c < C; c += kThreads) {
         // c = (id * nt + it) * nv + iv
         const int q1 = div_by<NV, ND * NV * NT>(c, inv_nv_a), iv = c - mul24(q1, nv);
@@ -1932,6 +1986,8 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
     }
     // [/section ASM]
     // [section ARGMIN]
+    // (a whole-blocked ego - block-uniform - has nothing to reduce: every thread's `mine` is Best{., -1} still, thread 0's is what RESULTS reads)
+    if (!whole) {
     if constexpr (kArgWave) {
         // ONE wavefront reduces the workgroup: every lane leaves its `mine` in LDS, the first wavefront merges kWaves of them per lane
         // and runs the exchange chain once (it ran on all kWaves, and thread 0 merged their partials).  best_merge is a total order
@@ -1952,6 +2008,7 @@ __global__ __launch_bounds__(NTH, OCC) void lattice_fused_kernel(KernelArgs ka, 
         mine = wave_best(mine);
         if (lane == 0) s_best[wave] = mine;
         __syncthreads();
+    }
     }
     FP_STAMP(9);
     // [/section ARGMIN]

@@ -20,7 +20,8 @@ instructions when the test is a vector compare, none when it is scalar (--scalar
 enter LUT's divisions, the square root of `r_ego`, the cost sums, the ends of d_samples and of v_samples (VENDS) and the one-wavefront
 argmin on a scalar test).  --two-ends names the sections that have the form of the instances with the two-profile RANGES and the
 one-wavefront ARGMIN: RANGES then has no end-speed loop, ARGMIN runs once and only its store (--uniform ARGMIN=9) on every wavefront.  MASKS runs only for slices with an
-unproven profile (0.05 of 7 on the headline workload) and is charged its share.
+unproven profile (0.05 of 7 on the headline workload) and is charged its share.  --whole is the share of the egos stage W ends with no
+table requested: they skip ASM and ARGMIN and are not charged them (WEXIT, the mask read behind the walk, is charged to every ego).
 
 The whole kernel is weighed when the source carries the marks for it: ENTRY (slot decode, the ego's scalars), GLUE (what stands between
 the prologue's sections), WSETUP (the block in front of the profile loop) and POSTWALK on all wavefronts; the profile loop's own
@@ -55,6 +56,8 @@ ap.add_argument("--s-rounds", type=float, default=0.0, help="work_counters: roun
 ap.add_argument("--s-ended", type=float, default=0.0, help="work_counters: lon profiles per ego that stage S ended (they skip PREP; their B and N rounds are not in the counters)")
 ap.add_argument("--walked", type=float, help="work_counters: lon profiles per ego that entered the walk (stage V skips the others at the loop's head, "
                 "where they pay the loop's own statements but no FRAMES); default: all nt nv")
+ap.add_argument("--whole", type=float, default=0.0, help="work_counters: share of the egos stage W ended with no table requested (every collision mask full behind the walk): "
+                "they are not charged ASM and ARGMIN; WEXIT itself - the mask read - runs on every wavefront of every ego")
 ap.add_argument("--scan-slices", type=float, default=0.05, help="work_counters: slices that needed the mask scan")
 ap.add_argument("--tail", type=float, default=128 / 2048, help="share of the egos the tail split runs as two workgroups")
 ap.add_argument("--scalar-skip", default="", help="comma list of sections whose idle wavefronts skip on a scalar test (the kCut instances: LUT,SUMS)")
@@ -83,7 +86,7 @@ for line in out.splitlines():
 
 W = a.threads // 64
 v = dict(W=W, nd=a.nd, nv=a.nv, nt=a.nt, rows=a.rows, n_obs=a.n_obs, nx=a.nx, hp=a.rows * a.stride + 1, C=a.nd * a.nv * a.nt, surv=a.surv,
-         flight=a.flight, threads=a.threads, ceil=math.ceil, log2=math.log2, scan=a.scan_slices)
+         flight=a.flight, threads=a.threads, ceil=math.ceil, log2=math.log2, scan=a.scan_slices, whole=a.whole)
 SKIP = 4  # a vector compare, the EXEC save / restore moves around a section a wavefront has no lane in
 scalar = set(filter(None, a.scalar_skip.split(",")))
 two_ends = set(filter(None, a.two_ends.split(",")))
@@ -111,8 +114,9 @@ WEIGHT = {
     "SINCOS": "ceil(surv / 64)",
     "WSETUP": "W",
     "POSTWALK": "W",
-    "ASM": "ceil(C / 64)",
-    "ARGMIN": "W" if "ARGMIN" not in two_ends else "1",
+    "WEXIT": "W",
+    "ASM": "ceil(C / 64) * (1 - whole)",
+    "ARGMIN": "W * (1 - whole)" if "ARGMIN" not in two_ends else "1 - whole",
     "RESULTS": "1",
     "SERIES": "0",
     "APPSEARCH": "0",
@@ -122,9 +126,10 @@ for name, formula in WEIGHT.items():
     if name not in static:
         continue
     w = eval(formula, {}, v)
-    idle = max(0.0, W - min(W, math.ceil(w))) if name not in ("MASKS", "SKIPPED", "SERIES", "APPSEARCH") else 0.0
+    w_all = eval(formula, {}, {**v, "whole": 0.0})  # (the wavefronts that hold the section's work in an ego W does not end)
+    idle = max(0.0, W - min(W, math.ceil(w_all))) if name not in ("MASKS", "SKIPPED", "SERIES", "APPSEARCH") else 0.0
     uni, uni_w = uniform.get(name, (0, W))
-    n = (static[name] - uni) * w + uni * uni_w + (0 if name in scalar else SKIP * idle)
+    n = (static[name] - uni) * w + uni * uni_w * ((1 - a.whole) if name in ("ASM", "ARGMIN") else 1) + (0 if name in scalar else SKIP * idle)
     rows_out.append((name, static[name], spill[name], spill[name] * w, f"{formula}" + (f"; {uni} of them once on {uni_w} wavefronts" if uni else "") + ("" if name in scalar or not idle else f"; + {SKIP} x {idle:.0f} idle"), n))
     total += n
     total_spill += spill[name] * w

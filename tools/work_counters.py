@@ -2,7 +2,8 @@
 """Work statistics of lattice_fused_kernel's collision stages per ego (build with EXTRA=-DFP_COUNTERS; run on the GPU box):
 items that survive the group test, rounds and hits of stage B, lane tests and rounds of the narrow phase, how many found a
 collision, how many lon profiles ended their walk early in N, the rounds of stage S and the profiles it ended, and stage V's
-end-speed groups ended before the walk and the profiles that still entered it."""
+end-speed groups ended before the walk and the profiles that still entered it, and stage W's workgroups that found every collision mask
+of their slices full (one workgroup per ego here: egos) and skipped the argmin - with no table requested also the assembly."""
 import os
 os.environ.setdefault("FP_ALLOW_DIAGNOSTIC_BUILD", "1")  # runs against a library built with EXTRA=-DFP_...
 import sys
@@ -46,9 +47,12 @@ for k, n in enumerate(names):
     print(f"  {n:56s} mean {c[:, k].mean():9.1f}  median {np.median(c[:, k]):9.1f}  p90 {np.percentile(c[:, k], 90):9.1f}  max {c[:, k].max():9.0f}")
 print("  blocked profiles by the pose index at which the last lateral sample collided (bins of 8 steps = 0.8 s): " +
       "  ".join(f"k<{8 * (i + 1)}: {c[:, 10 + i].mean():.1f}" if i < 5 else f"k>=40: {c[:, 15].mean():.1f}" for i in range(6)) + "   (mean per ego)")
-v = bt[:, 13, 112:116].cpu().numpy()  # (row 14 is full: stage V's slots and the split of S's rounds stand in row 13)
+v = bt[:, 13, 112:118].cpu().numpy()  # (row 14 is full: stage V's slots and the split of S's rounds stand in row 13)
 for k, n in enumerate(["end-speed groups ended by V (each once, whichever item chunk)", "profiles that entered the walk (not skipped at the loop's head)",
                        "S wave rounds in which no lane passed the first end"]):
     print(f"  {n:56s} mean {v[:, k].mean():9.1f}  median {np.median(v[:, k]):9.1f}  p90 {np.percentile(v[:, k], 90):9.1f}  max {v[:, k].max():9.0f}")
 print(f"  egos with every group ended by V: {100.0 * np.mean(v[:, 0] >= batch.nv):.1f} %")
+print(f"  egos stage W ended (every mask full behind the walk: no argmin): {100.0 * np.mean(v[:, 4] > 0):.1f} %   of them ended by V before the walk: "
+      f"{100.0 * np.mean((v[:, 4] > 0) & (v[:, 0] >= batch.nv)):.1f} %, filled by S, B and N: {100.0 * np.mean((v[:, 4] > 0) & (v[:, 0] < batch.nv)):.1f} %   "
+      f"with no table requested (no assembly either): {100.0 * np.mean(v[:, 5] > 0):.1f} %")
 print("  slices whose lon profiles needed the point-by-point mask scan: mean", round(float(c[:, 9].mean()), 2), "of", batch.nt)
