@@ -202,6 +202,7 @@ struct fp_ctx {
     int rules_eval_launches = 0;   // fp_ctx_get_option("rules_eval_launches"): launches of the rules kernel (fp_rules_eval)
     int margin_launches = 0;       // fp_ctx_get_option("margin_launches"): launches of the plan-margin kernel (fp_traj_margins)
     int fallback_launches = 0;     // fp_ctx_get_option("fallback_launches"): launches of the fallback kernel (fp_fallback_stop)
+    int fallback_rules_launches = 0;  // fp_ctx_get_option("fallback_rules_launches"): launches of its rule instance (fp_fallback_stop_rules)
     int predict_launches = 0;      // fp_ctx_get_option("predict_launches"): launches of the obstacle prediction kernel (fp_obstacles_predict)
     int from_state_launches = 0;   // fp_ctx_get_option("from_state_launches"): launches of the projection kernel (fp_from_state)
     int fiss_rules_calls = 0;      // fp_ctx_get_option("fiss_rules_calls"): calls of fp_plan_fiss_rules that passed their argument checks
@@ -1537,7 +1538,7 @@ int fp_ctx_get_option(fp_ctx* ctx, const char* name, int* value)
     const struct { const char* n; int v; } tab[] = {
         {"lattice_kernel", ctx->lattice_kernel}, {"lattice_split", ctx->lattice_split}, {"lattice_group", ctx->lattice_group}, {"lattice_tail", ctx->lattice_tail}, {"lattice_occupancy", ctx->lattice_occupancy}, {"resident_groups", ctx->resident_groups}, {"zero_copy_in", ctx->zero_copy_in}, {"stage_kernel", ctx->stage_kernel}, {"inline_inputs", ctx->inline_inputs}, {"lattice_order", ctx->lattice_order},
         {"refine_table_kb", ctx->refine_table_kb}, {"fiss_stages", ctx->fiss_stages}, {"fiss_jump", ctx->fiss_jump}, {"validate", ctx->validate}, {"lattice_winner", ctx->lattice_winner}, {"fiss_fused", ctx->fiss_fused}, {"appended_workgroups", ctx->appended_ok ? 1 : 0}, {"handover_failed", ctx->hand_err ? *(volatile int32_t*)ctx->hand_err : 0}, {"overlap", ctx->overlap}, {"overlapped_calls", ctx->overlapped_calls}, {"clearance_launches", ctx->clearance_launches + (ctx->twin ? ctx->twin->clearance_launches : 0)}, {"lattice_launches", ctx->lattice_launches + (ctx->twin ? ctx->twin->lattice_launches : 0)},
-        {"looplog_launches", ctx->looplog_launches}, {"rank_launches", ctx->rank_launches}, {"boundary_launches", ctx->boundary_launches}, {"envelope_launches", ctx->envelope_launches}, {"gate_launches", ctx->gate_launches}, {"gap_launches", ctx->gap_launches}, {"margin_launches", ctx->margin_launches}, {"fallback_launches", ctx->fallback_launches}, {"rules_eval_launches", ctx->rules_eval_launches}, {"fiss_rules_calls", ctx->fiss_rules_calls}, {"predict_launches", ctx->predict_launches}, {"from_state_launches", ctx->from_state_launches}, {"lattice_ordered_launches", ctx->lattice_ordered_launches + (ctx->twin ? ctx->twin->lattice_ordered_launches : 0)},
+        {"looplog_launches", ctx->looplog_launches}, {"rank_launches", ctx->rank_launches}, {"boundary_launches", ctx->boundary_launches}, {"envelope_launches", ctx->envelope_launches}, {"gate_launches", ctx->gate_launches}, {"gap_launches", ctx->gap_launches}, {"margin_launches", ctx->margin_launches}, {"fallback_launches", ctx->fallback_launches}, {"fallback_rules_launches", ctx->fallback_rules_launches}, {"rules_eval_launches", ctx->rules_eval_launches}, {"fiss_rules_calls", ctx->fiss_rules_calls}, {"predict_launches", ctx->predict_launches}, {"from_state_launches", ctx->from_state_launches}, {"lattice_ordered_launches", ctx->lattice_ordered_launches + (ctx->twin ? ctx->twin->lattice_ordered_launches : 0)},
         {"lattice_launches_2", (int)fp::lattice_launches_per_cu(0)}, {"lattice_launches_3", (int)fp::lattice_launches_per_cu(1)}, {"lattice_launches_4", (int)fp::lattice_launches_per_cu(2)}};
     for (const auto& t : tab)
         if (strcmp(name, t.n) == 0) { *value = t.v; return FP_OK; }
@@ -1942,53 +1943,69 @@ int fp_traj_margins(fp_ctx* ctx, const fp_params* params, const fp_batch* batch,
     return hs.fetch_out();
 }
 
-int fp_fallback_stop(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, const fp_fallback* fallback, const int32_t* best_idx, double* end_state,
-                     int32_t* status, int32_t* fb_idx, int32_t* hit_step, int32_t* hit_obs, double* hit_speed, int32_t* cand, int32_t* counts, int mem,
-                     void* stream)
+// fp_fallback_stop and fp_fallback_stop_rules: one body.  fn names the entry point in the messages; with_rules: the rule instance
+// (rules, rule_bits mandatory; cand_rules, rule_counts optional), else the three are not read.
+static int fallback_call(const char* fn, bool with_rules, fp_ctx* ctx, const fp_params* params, const fp_batch* batch, const fp_fallback* fallback,
+                         const fp_rule_set* rules, const int32_t* best_idx, double* end_state, int32_t* status, int32_t* fb_idx, int32_t* hit_step,
+                         int32_t* hit_obs, double* hit_speed, int32_t* cand, uint32_t* cand_rules, uint32_t* rule_bits, int32_t* counts, int32_t* rule_counts,
+                         int mem, void* stream)
 {
     FP_TRY(common_checks(ctx, params, batch, mem, stream));
-    if (!fallback || !fallback->d_targets || !fallback->stop_T) return fail(FP_EINVAL, "fp_fallback_stop: fallback / d_targets / stop_T must not be NULL");
+    if (!fallback || !fallback->d_targets || !fallback->stop_T) return fail(FP_EINVAL, "%s: fallback / d_targets / stop_T must not be NULL", fn);
     if (!end_state || !status || !fb_idx || !hit_step || !hit_obs || !hit_speed)
-        return fail(FP_EINVAL, "fp_fallback_stop: end_state/status/fb_idx/hit_step/hit_obs/hit_speed must not be NULL");
-    if (fallback->n_d < 1 || fallback->n_stop < 1) return fail(FP_EINVAL, "fp_fallback_stop: n_d=%d, n_stop=%d must be >= 1", fallback->n_d, fallback->n_stop);
+        return fail(FP_EINVAL, "%s: end_state/status/fb_idx/hit_step/hit_obs/hit_speed must not be NULL", fn);
+    if (fallback->n_d < 1 || fallback->n_stop < 1) return fail(FP_EINVAL, "%s: n_d=%d, n_stop=%d must be >= 1", fn, fallback->n_d, fallback->n_stop);
     if ((long long)fallback->n_d * fallback->n_stop > FP_MAX_FALLBACK)
-        return fail(FP_ELIMIT, "fp_fallback_stop: n_d * n_stop = %lld exceeds FP_MAX_FALLBACK (%d)", (long long)fallback->n_d * fallback->n_stop, FP_MAX_FALLBACK);
-    if (!(fallback->max_decel > 0)) return fail(FP_EINVAL, "fp_fallback_stop: max_decel=%g must be > 0 (+inf = no limit)", fallback->max_decel);
+        return fail(FP_ELIMIT, "%s: n_d * n_stop = %lld exceeds FP_MAX_FALLBACK (%d)", fn, (long long)fallback->n_d * fallback->n_stop, FP_MAX_FALLBACK);
+    if (!(fallback->max_decel > 0)) return fail(FP_EINVAL, "%s: max_decel=%g must be > 0 (+inf = no limit)", fn, fallback->max_decel);
+    if (with_rules) {
+        if (!rules || !rule_bits) return fail(FP_EINVAL, "%s: rules / rule_bits must not be NULL", fn);
+        FP_TRY(check_rule_set(fn, rules, batch));
+    }
     if (batch->B == 0) return FP_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t B = (size_t)batch->B, F = (size_t)fallback->n_d * fallback->n_stop;
     fp::KernelArgs ka;
     ka.p = *params;
     ka.r = no_result();
-    fp::FallbackArgs a;
+    fp::FallbackRulesArgs a;  // (fp_fallback_stop launches with its FallbackArgs part)
     a.n_d = fallback->n_d; a.n_stop = fallback->n_stop; a.max_decel = fallback->max_decel;
+    if (with_rules) a.rules = fp::rule_args(*rules);
     if (mem == FP_MEM_DEVICE) {
         ka.b = device_batch(batch);
         a.d_targets = fallback->d_targets; a.stop_T = fallback->stop_T; a.best_idx = best_idx; a.end_state = end_state;
         a.status = status; a.fb_idx = fb_idx; a.hit_step = hit_step; a.hit_obs = hit_obs; a.hit_speed = hit_speed;
         a.cand = cand; a.counts = counts; a.perm = batch->launch_order;
-        LAUNCH_TRY(fp::launch_fallback_stop(ka, a, (hipStream_t)stream), "fallback kernel");
-        ++ctx->fallback_launches;
+        if (with_rules) {
+            a.cand_rules = cand_rules; a.rule_bits = rule_bits; a.rule_counts = rule_counts;
+            LAUNCH_TRY(fp::launch_fallback_stop_rules(ka, a, (hipStream_t)stream), "fallback rules kernel");
+            ++ctx->fallback_rules_launches;
+        } else {
+            LAUNCH_TRY(fp::launch_fallback_stop(ka, a, (hipStream_t)stream), "fallback kernel");
+            ++ctx->fallback_launches;
+        }
         return FP_OK;
     }
     FP_TRY(check_batch_host(params, batch));
+    if (with_rules) FP_TRY(check_rule_set_host(rules, batch));
     for (int i = 0; i < fallback->n_stop; ++i) {
         const double T = fallback->stop_T[i];
         if (!finite_pos(T) || (i > 0 && !(T > fallback->stop_T[i - 1])))
-            return fail(FP_EINVAL, "fp_fallback_stop: stop_T[%d]=%g must be finite, > 0 and above stop_T[%d]", i, T, i - 1);
-        if (ceil(T / params->tick_t) > FP_MAX_POINTS) return fail(FP_ELIMIT, "fp_fallback_stop: stop_T[%d]=%g needs more than FP_MAX_POINTS points", i, T);
+            return fail(FP_EINVAL, "%s: stop_T[%d]=%g must be finite, > 0 and above stop_T[%d]", fn, i, T, i - 1);
+        if (ceil(T / params->tick_t) > FP_MAX_POINTS) return fail(FP_ELIMIT, "%s: stop_T[%d]=%g needs more than FP_MAX_POINTS points", fn, i, T);
     }
     if (best_idx) {
         const int C = params->nd * params->nv * params->nt;
         for (size_t b = 0; b < B; ++b)
             if (best_idx[b] >= C && !(batch->skip && batch->skip[b]))
-                return fail(FP_EINVAL, "fp_fallback_stop: best_idx of ego %zu = %d is outside the lattice (nd*nv*nt = %d)", b, best_idx[b], C);
+                return fail(FP_EINVAL, "%s: best_idx of ego %zu = %d is outside the lattice (nd*nv*nt = %d)", fn, b, best_idx[b], C);
     }
     ka.p.points_max = host_points_max(params, batch, fallback->stop_T, (size_t)fallback->n_stop, 1);
     HostStage hs(ctx);
     StageList sl;
     StageRegime rg;  // (throughput)
     FP_TRY(stage_batch(ctx, sl, rg, params, batch, &ka.b));
+    if (with_rules) fp::stage_rule_arrays(sl, &a.rules, batch->F, batch->NX);
     sl.in(fallback->d_targets, (size_t)fallback->n_d, &a.d_targets);
     sl.in(fallback->stop_T, (size_t)fallback->n_stop, &a.stop_T);
     if (best_idx) sl.in(best_idx, B, &a.best_idx);
@@ -2000,10 +2017,36 @@ int fp_fallback_stop(fp_ctx* ctx, const fp_params* params, const fp_batch* batch
     sl.out(hit_speed, B, &a.hit_speed);
     if (cand) sl.in_mut(cand, B * F, &a.cand);
     if (counts) sl.in_mut(counts, B * 4, &a.counts);
+    if (with_rules) {
+        if (cand_rules) sl.in_mut(cand_rules, B * F, &a.cand_rules);
+        sl.out(rule_bits, B, &a.rule_bits);
+        if (rule_counts) sl.in_mut(rule_counts, B * FP_RULE_COUNT, &a.rule_counts);
+    }
     FP_TRY(hs.commit(sl, rg));
-    LAUNCH_TRY(fp::launch_fallback_stop(ka, a, ctx->stream), "fallback kernel");
-    ++ctx->fallback_launches;
+    if (with_rules) {
+        LAUNCH_TRY(fp::launch_fallback_stop_rules(ka, a, ctx->stream), "fallback rules kernel");
+        ++ctx->fallback_rules_launches;
+    } else {
+        LAUNCH_TRY(fp::launch_fallback_stop(ka, a, ctx->stream), "fallback kernel");
+        ++ctx->fallback_launches;
+    }
     return hs.fetch_out();
+}
+
+int fp_fallback_stop(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, const fp_fallback* fallback, const int32_t* best_idx, double* end_state,
+                     int32_t* status, int32_t* fb_idx, int32_t* hit_step, int32_t* hit_obs, double* hit_speed, int32_t* cand, int32_t* counts, int mem,
+                     void* stream)
+{
+    return fallback_call("fp_fallback_stop", false, ctx, params, batch, fallback, nullptr, best_idx, end_state, status, fb_idx, hit_step, hit_obs, hit_speed, cand,
+                         nullptr, nullptr, counts, nullptr, mem, stream);
+}
+
+int fp_fallback_stop_rules(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, const fp_fallback* fallback, const fp_rule_set* rules,
+                           const int32_t* best_idx, double* end_state, int32_t* status, int32_t* fb_idx, int32_t* hit_step, int32_t* hit_obs, double* hit_speed,
+                           int32_t* cand, uint32_t* cand_rules, uint32_t* rule_bits, int32_t* counts, int32_t* rule_counts, int mem, void* stream)
+{
+    return fallback_call("fp_fallback_stop_rules", true, ctx, params, batch, fallback, rules, best_idx, end_state, status, fb_idx, hit_step, hit_obs, hit_speed, cand,
+                         cand_rules, rule_bits, counts, rule_counts, mem, stream);
 }
 
 int fp_obstacles_predict(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, const fp_tracks* tracks, double* obs_pose,

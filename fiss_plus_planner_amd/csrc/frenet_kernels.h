@@ -348,6 +348,16 @@ struct FallbackArgs {
     const int32_t* perm = nullptr;
 };
 hipError_t launch_fallback_stop(const KernelArgs& ka, const FallbackArgs& a, hipStream_t stream);
+// fp_fallback_stop_rules: the fallback whose clear candidates are also ranked by the rule set (fallback_kernel<true>, frenet_fallback.hip).
+// rules = the rule set as launch_rules_eval takes it (K, end_states, flags, rule_bits, counts and perm are not read; the off_* fields are
+// filled in by the launcher); cand_rules [B][F] or nullptr, rule_bits [B], rule_counts [B][FP_RULE_COUNT] in/out or nullptr.
+struct FallbackRulesArgs : FallbackArgs {
+    RulesEvalArgs rules;
+    uint32_t* cand_rules = nullptr;
+    uint32_t* rule_bits = nullptr;
+    int32_t* rule_counts = nullptr;
+};
+hipError_t launch_fallback_stop_rules(const KernelArgs& ka, FallbackRulesArgs a, hipStream_t stream);
 // The obstacle pose table from tracks (frenet_predict.hip, fp_obstacles_predict): rows max(t0, 0) .. min(T_obs, t0 + n_rows) - 1 of
 // every scene of obs_pose [S][T_obs][n_obs][4].  Device addresses; nx / knots / coef / frame_of_scene may be NULL (LANE columns then
 // have no pose).  compact: the output is [S][span][n_obs][4], span = min(T_obs, n_rows), and a scene's first written row lands in

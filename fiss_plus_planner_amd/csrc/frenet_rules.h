@@ -146,4 +146,181 @@ __device__ __forceinline__ bool gap_pose_hit(const KernelArgs& ka, const EgoCtx&
     return hit;
 }
 
+// ---- the four rules on one explicit trajectory, evaluated by a whole wavefront (rules_eval_kernel per end state, the fallback
+// kernel's rule instance per candidate): the tables a workgroup stages once per ego, the call's constants, and the evaluation.
+constexpr int kRulesSplit = 8;  // at most this many lanes share one pose's columns (the gaps)
+
+// The rules' own tables in LDS, behind stage_ego's layout at a.off_lim / off_edge / off_gate (doubles): limits [NX] | l0, l1, r0, r1
+// [NX] each | gate lines [FP_MAX_GATES], closed words [points_cap].  closed = the frame's words in global memory (a point beyond the cap).
+struct RuleTables {
+    const double *lim, *l0, *l1, *r0, *r1, *line;
+    const uint32_t *word, *closed;
+};
+// doubles the tables of the rules in `on` take
+inline long rule_table_doubles(uint32_t on, const fp_params& p, int NX)
+{
+    long own = 0;
+    if (on & FP_RULE_LIMIT) own += NX;
+    if (on & FP_RULE_BOUNDARY) own += 4L * NX;
+    if (on & FP_RULE_GATE) own += FP_MAX_GATES + (points_cap(p) + 1) / 2;
+    return own;
+}
+// where each table starts when the layout before them ends at `off` doubles
+inline void rule_table_offsets(RulesEvalArgs& a, int off, int NX)
+{
+    a.off_lim = off;
+    if (a.on & FP_RULE_LIMIT) off += NX;
+    a.off_edge = off;
+    if (a.on & FP_RULE_BOUNDARY) off += 4 * NX;
+    a.off_gate = off;
+}
+// Stage them with the workgroup's nth threads (after stage_ego; the caller's barrier follows): the limit of every segment, the
+// corridor (stage_corridor), the gate lines with the waiver folded in - taken from the ego's present state -, the mask of the live
+// slots (*s_live, one LDS word, written by wavefront 0) and the closed words of the steps t_now + 1 .. t_now + points_cap.
+__device__ __forceinline__ RuleTables stage_rule_tables(const KernelArgs& ka, const RulesEvalArgs& a, int b, const EgoCtx& e, double* lds, uint32_t* s_live,
+                                                        int tid, int wave, int lane, int nth)
+{
+    const int f = ka.b.frame_of[b], nx = e.sp.nx, NX = ka.b.NX;
+    const int cap = points_cap(ka.p), t_last = a.T_gate - 1;
+    const long long tn = e.t_now;
+    double* lim = lds + a.off_lim;
+    double* l0 = lds + a.off_edge;
+    double* l1 = l0 + NX;
+    double* r0 = l1 + NX;
+    double* r1 = r0 + NX;
+    double* line = lds + a.off_gate;
+    uint32_t* word = (uint32_t*)(line + FP_MAX_GATES);
+    const bool gates = a.on & FP_RULE_GATE;
+    const uint32_t* closed = gates ? a.closed + (size_t)f * a.T_gate : nullptr;
+    if (a.on & FP_RULE_LIMIT) {
+        const double* gl = a.v_limit + (size_t)f * NX;
+        for (int i = tid; i < nx; i += nth) lim[i] = i + 1 < nx ? gl[i] : __builtin_inf();  // (the last knot starts no segment)
+    }
+    if (a.on & FP_RULE_BOUNDARY) stage_corridor(ka.b.knots + (size_t)f * NX, a.left + (size_t)f * NX, a.right + (size_t)f * NX, nx, nullptr, l0, l1, r0, r1, tid, nth);
+    if (gates) {
+        if (wave == 0) {
+            double g = __builtin_nan("");
+            if (lane < a.gate_stride) {
+                g = a.gate_s[(size_t)f * a.gate_stride + lane];
+                if (gate_waived(a.max_decel, e.s_d0, e.s0 + a.gate_front, g)) g = __builtin_nan("");
+            }
+            if (lane < FP_MAX_GATES) line[lane] = g;
+            const unsigned long long live = __ballot(g == g);
+            if (lane == 0) *s_live = (uint32_t)live;
+        }
+        for (int i = tid; i < cap; i += nth) word[i] = gate_word(closed, tn + 1 + i, t_last);
+    }
+    return RuleTables{lim, l0, l1, r0, r1, line, word, closed};
+}
+
+// What the evaluation needs beside the tables and does not depend on the trajectory (after the barrier behind stage_rule_tables)
+struct RuleConsts {
+    uint32_t live, env_want;
+    double guess_scale, hl, hw, r_e, q0;
+    int lateral, cap, t_last, cs, Lf, Ll, G, q_first;
+    bool gaps_active;
+};
+__device__ __forceinline__ RuleConsts rule_consts(const KernelArgs& ka, const RulesEvalArgs& a, const EgoCtx& e, const uint32_t* s_live)
+{
+    const fp_params& p = ka.p;
+    RuleConsts c;
+    const int nx = e.sp.nx;
+    c.live = (a.on & FP_RULE_GATE) ? *s_live : 0u;
+    c.lateral = (a.on & FP_RULE_LATERAL) ? 1 : 0;
+    c.env_want = FP_FLAG_SPEED | (c.lateral ? FP_FLAG_ACCEL : 0u);
+    c.guess_scale = (double)(nx - 1) / (e.sp.knots[nx - 1] - e.sp.knots[0]);
+    c.hl = 0.5 * p.veh_l; c.hw = 0.5 * p.veh_w;
+    c.r_e = sqrt(fma(c.hl, c.hl, c.hw * c.hw));
+    c.q0 = e.s0 + a.gate_front;
+    c.cap = points_cap(p); c.t_last = a.T_gate - 1;
+    c.cs = p.check_stride;
+    c.Lf = a.lag_follow / c.cs; c.Ll = a.lag_lead / c.cs;  // the lags in grid steps: only pairs on the grid exist
+    c.G = (a.on & FP_RULE_GAP) ? gap_grid_poses(p, e) : 0;
+    c.gaps_active = c.G > 0 && (c.Lf > 0 || c.Ll > 0);
+    c.q_first = (a.first - 1) / c.cs + 1 < c.G ? (a.first - 1) / c.cs + 1 : c.G;
+    return c;
+}
+
+// The trajectory (lon, lat) with points 1 .. M - 1 (2 <= M <= N <= points_cap) and flag word word_in -> the word the rules leave;
+// spoke = the FP_RULE_* bits violated.  The rules run in the passes' order; every rule gives the lanes the points 1 + lane, 65 + lane,
+// ... < M (the gaps: the grid poses, split like gap_mask_kernel's), __ballot is the verdict and a rule ends on its first hit; the gaps
+// run only when the word carries no FP_FLAG_INFEASIBLE bit after the three rules before them.  Wave-uniform in, wave-uniform out.
+__device__ __forceinline__ uint32_t wave_rules_eval(const KernelArgs& ka, const RulesEvalArgs& a, const EgoCtx& e, const RuleTables& t, const RuleConsts& c,
+                                                    const Quartic& lon, const Quintic& lat, int M, uint32_t word_in, int lane, uint32_t& spoke)
+{
+    const fp_params& p = ka.p;
+    const double tick = p.tick_t;
+    const long long tn = e.t_now;
+    uint32_t word_new = word_in;
+    spoke = 0u;
+    if (a.on & FP_RULE_LIMIT) {
+        uint32_t bits = 0u;
+        for (int i0 = 1; i0 < M; i0 += kWave) {
+            const int i = i0 + lane;
+            bool fast = false, lat_v = false;
+            if (i < M) envelope_point(e.sp, t.lim, c.guess_scale, lon, (double)i * tick, a.env_front, a.env_tol, c.lateral, a.max_lat_accel, fast, lat_v);
+            if (__ballot(fast)) bits |= FP_FLAG_SPEED;
+            if (__ballot(lat_v)) bits |= FP_FLAG_ACCEL;
+            if (bits == c.env_want) break;  // every bit the rule can give is found
+        }
+        word_new |= bits;
+        if (bits & FP_FLAG_SPEED) spoke |= FP_RULE_LIMIT;
+        if (bits & FP_FLAG_ACCEL) spoke |= FP_RULE_LATERAL;
+    }
+    if ((a.on & FP_RULE_GATE) && c.live != 0u) {
+        for (int i0 = 1; i0 < M; i0 += kWave) {
+            const int i = i0 + lane;
+            bool hit = false;
+            if (i < M) {
+                const uint32_t w = (i <= c.cap ? t.word[i - 1] : gate_word(t.closed, tn + i, c.t_last)) & c.live;
+                if (w) hit = gate_point(lon, i, tick, a.gate_front, c.q0, w, t.line);
+            }
+            if (__ballot(hit)) {
+                word_new |= FP_FLAG_SPEED;
+                spoke |= FP_RULE_GATE;
+                break;
+            }
+        }
+    }
+    if (a.on & FP_RULE_BOUNDARY) {
+        bool out = false;
+        for (int i0 = 1; i0 < M; i0 += kWave) {
+            const int i = i0 + lane;
+            bool viol = false;
+            if (i < M) viol = boundary_point(e.sp, t.l0, t.l1, t.r0, t.r1, c.guess_scale, lon, lat, (double)i * tick, c.hw, c.hl, a.margin);
+            if (__ballot(viol)) {  // one violation decides the trajectory
+                out = true;
+                break;
+            }
+        }
+        word_new = (word_new & ~FP_FLAG_BOUNDARY) | (out ? FP_FLAG_BOUNDARY : 0u);
+        if (out) spoke |= FP_RULE_BOUNDARY;
+    }
+    if (c.gaps_active && !(word_new & FP_FLAG_INFEASIBLE)) {
+        // poses i = 0, cs, 2 cs, ... < min(M, final_time_step - t_now) inside the table: grid poses q < n_pose
+        const int cs = c.cs;
+        const int limit = M < e.horizon_cap ? M : e.horizon_cap;
+        int n_pose = limit > 0 ? (limit + cs - 1) / cs : 0;
+        if (c.G < n_pose) n_pose = c.G;
+        if (c.q_first < n_pose) {
+            int split = 1;
+            while (split < kRulesSplit && (n_pose - c.q_first) * split * 2 <= kWave) split *= 2;
+            const int per_round = kWave / split, sub = lane & (split - 1);
+            for (int qb = c.q_first; qb < n_pose; qb += per_round) {
+                const int q = qb + lane / split, i = q * cs;
+                bool hit = false;
+                Obb ego;
+                if (q < n_pose && i + e.t_now >= 0 && checked_pose(p, e.sp, c.guess_scale, lon, lat, i, M, ego))
+                    hit = gap_pose_hit(ka, e, ego, q, n_pose, c.Lf, c.Ll, sub, split, nullptr, c.r_e, cs, e.n_obs);
+                if (__ballot(hit)) {
+                    word_new |= FP_FLAG_COLLISION;
+                    spoke |= FP_RULE_GAP;
+                    break;  // the one bit the rule can give is found
+                }
+            }
+        }
+    }
+    return word_new;
+}
+
 }  // namespace fp

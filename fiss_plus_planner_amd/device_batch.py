@@ -108,7 +108,11 @@ class ClosedLoopRunner:
         with FP_DONE_NO_SOLUTION, and plans again in the next cycle; `fused` has no say.  self.fallback_counts [B, 4] int32 counts, per ego,
         the cycles by fallback status (_abi.FALLBACK_*: column 0 = the ego had a plan or was finished); run / run_graph return it.  With
         record=True the log is written from end_state for FOP too: its FP_LOG_BEST_IDX column is then -1 in every row.  fallback= with
-        audit= is not done (ValueError).  fallback=None: the calls below, unchanged.
+        audit= is not done (ValueError).  fallback=None: the calls below, unchanged.  A fallback with obey=(...) (any subset of the
+        names in rules.TABLE; the batch must carry each rule's data, whichever rules= / enforce= name) makes the middle call
+        fp_fallback_stop_rules: the clear stops are ranked by those rules - an ego in front of a closed gate stops before the line.
+        self.fallback_rule_counts [B, 5] int32 counts, per ego and FP_RULE_* bit (column log2 of the bit), the cycles whose chosen stop
+        violated the rule; run / run_graph return it.
         fused: an FOP cycle is ONE launch (fp_plan_step: the workgroup that finds an ego's argmin advances the ego); False = the two
         calls fp_plan_dense + fp_advance (same results; the A/B of tests and bench).
         goal_poly [B, V, 2] + goal_nv [B] (+ goal_intervals [B, 6] = time_step / velocity / orientation lo, hi; NaN = undefined): the
@@ -119,6 +123,7 @@ class ClosedLoopRunner:
         if fallback is not None and self.audit:
             raise ValueError("ClosedLoopRunner: fallback= with audit= is not done (the audit's verdict is taken on the planner's own end state)")
         self.fallback = fallback
+        self.obey = fallback.rules_for(dbatch.host, "ClosedLoopRunner(fallback=FallbackStop") if fallback is not None and getattr(fallback, "obey", ()) else ()
         torch = dbatch.torch
         self.eng, self.db, self.planner, self.fused = engine, dbatch, planner, fused
         B = dbatch.B
@@ -184,6 +189,10 @@ class ClosedLoopRunner:
             self.fb_status, self.fb_idx, self.fb_hit_step, self.fb_hit_obs = (torch.zeros(B, dtype=i32, device=dbatch.dev) for _ in range(4))
             self.fb_hit_speed = torch.full((B,), float("nan"), dtype=f64, device=dbatch.dev)
             self.fallback_counts = torch.zeros((B, 4), dtype=i32, device=dbatch.dev)
+            if self.obey:  # the obeyed set on device addresses (DeviceBatch has uploaded the arrays of every rule the batch carries), the verdicts, the counts
+                self.fb_rule_bits = torch.zeros(B, dtype=i32, device=dbatch.dev)
+                self.fallback_rule_counts = torch.zeros((B, _abi.FP_RULE_COUNT), dtype=i32, device=dbatch.dev)
+                self.obey_set, self._obey_structs = _rules.rule_set(dbatch.host, lambda k: dbatch.t[k].data_ptr(), self.obey)
             # (the fallback's own calls are sized for its longest stop time; the plan calls keep the batch's params)
             self.fb_params = _abi.FpParams.from_buffer_copy(dbatch.params)
             pts = max(fallback.points_max(dbatch.host.tick_t), int(dbatch.params.points_max))
@@ -251,7 +260,7 @@ class ClosedLoopRunner:
         _abi.check(eng._lib.fp_advance(eng._ctx, C.byref(db.params), C.byref(self.fb), bi, None, C.byref(self.io), _abi.FP_MEM_DEVICE, stream or None))
 
     def _step_fallback(self, stream: int):
-        """plan (no fused hand-over) -> fp_fallback_stop -> fp_advance(end_state): a linear chain on `stream`."""
+        """plan (no fused hand-over) -> fp_fallback_stop (with obey: fp_fallback_stop_rules) -> fp_advance(end_state): a linear chain on `stream`."""
         import ctypes as C
 
         db, eng = self.db, self.eng
@@ -269,9 +278,15 @@ class ClosedLoopRunner:
             eng.plan_fiss_rules_device(db.params, self.fb, self.fopts, self.fio, self.enforce_set, None, self.rejected.data_ptr(), stream)
         else:
             eng.plan_fiss_device(db.params, self.fb, self.fopts, self.fio, stream=stream)
-        eng.fallback_stop_device(self.fb_params, self.fb, self.fb_struct, self.end_state.data_ptr(), self.fb_status.data_ptr(), self.fb_idx.data_ptr(),
-                                 self.fb_hit_step.data_ptr(), self.fb_hit_obs.data_ptr(), self.fb_hit_speed.data_ptr(), best_idx=bi,
-                                 counts=self.fallback_counts.data_ptr(), stream=stream)
+        if self.obey:
+            eng.fallback_stop_rules_device(self.fb_params, self.fb, self.fb_struct, self.obey_set, self.end_state.data_ptr(), self.fb_status.data_ptr(),
+                                           self.fb_idx.data_ptr(), self.fb_hit_step.data_ptr(), self.fb_hit_obs.data_ptr(), self.fb_hit_speed.data_ptr(),
+                                           self.fb_rule_bits.data_ptr(), best_idx=bi, counts=self.fallback_counts.data_ptr(),
+                                           rule_counts=self.fallback_rule_counts.data_ptr(), stream=stream)
+        else:
+            eng.fallback_stop_device(self.fb_params, self.fb, self.fb_struct, self.end_state.data_ptr(), self.fb_status.data_ptr(), self.fb_idx.data_ptr(),
+                                     self.fb_hit_step.data_ptr(), self.fb_hit_obs.data_ptr(), self.fb_hit_speed.data_ptr(), best_idx=bi,
+                                     counts=self.fallback_counts.data_ptr(), stream=stream)
         _abi.check(eng._lib.fp_advance(eng._ctx, C.byref(self.fb_params), C.byref(self.fb), None, self.end_state.data_ptr(), C.byref(self.io),
                                        _abi.FP_MEM_DEVICE, stream or None))
 
@@ -345,6 +360,8 @@ class ClosedLoopRunner:
             out.rejected = self.rejected.cpu().numpy()
         if self.fallback is not None:
             out.fallback_counts = self.fallback_counts.cpu().numpy()
+            if self.obey:
+                out.fallback_rule_counts = self.fallback_rule_counts.cpu().numpy()
         if self.audit:
             out.violation_counts = self.violations.cpu().numpy()
             cols = lambda bits: [i for i in range(_abi.FP_RULE_COUNT) if bits >> i & 1]  # noqa: E731

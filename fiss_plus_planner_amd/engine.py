@@ -235,9 +235,13 @@ class FrenetEngine:
         order of rules.TABLE, whatever the order of the keywords: every argmin honours the bits set before it.
         fallback=FallbackStop(...): behind the last pass asked for, the egos whose best_idx is -1 get a stopping manoeuvre
         (fallback_stop): also `fallback`, its namespace - fallback.end_state [B, 3] is the plan every ego drives.  best_idx, the tables
-        and everything taken on them (winner, top_k, margins) are the call's own answer without it.
+        and everything taken on them (winner, top_k, margins) are the call's own answer without it.  A fallback with obey=... ranks its
+        clear stops by those rules (fp_fallback_stop_rules; fallback.rule_bits [B] = what the chosen stop violates) - whichever passes
+        the keywords above switched on.
         """
         if fallback is not None:
+            if getattr(fallback, "obey", ()):
+                fallback.rules_for(batch, "plan_dense(fallback=...)")  # (a rule without data: refused before anything runs)
             out = self.plan_dense(batch, tables, winner, traj_stride, traj_sparse, out, audit, top_k, boundary, margins, envelope, gates, gaps)
             out.fallback = self.fallback_stop(batch, fallback, best_idx=out.best_idx)
             return out
@@ -543,14 +547,21 @@ class FrenetEngine:
                                              _abi.FP_MEM_DEVICE, stream or None))
 
     def fallback_stop(self, batch: ProblemBatch, fallback, best_idx: np.ndarray | None = None, end_state: np.ndarray | None = None, cand: bool = False,
-                      skip: np.ndarray | None = None, counts: np.ndarray | None = None):
+                      skip: np.ndarray | None = None, counts: np.ndarray | None = None, rule_counts: np.ndarray | None = None):
         """A stopping manoeuvre for the egos without a plan (fp_fallback_stop; the definition: include/frenet_gpu.h).  fallback: a
         FallbackStop.  best_idx [B] (plan_dense's or a rule pass' argmin, < 0 = needs a fallback), or end_state [B, 3] (plan_fiss'
         end_state, NaN = needs one) - exactly one of the two; the caller's arrays are not modified.  Returns a namespace: end_state
         [B, 3] (the plan every ego drives: the lattice sample's or the untouched (d, v, T) of an ego with a plan, the chosen (d, 0, T) of
         one without, NaN where nothing is admissible), status [B] (_abi.FALLBACK_*), fb_idx [B], hit_step / hit_obs / hit_speed [B],
         counts [B, 4] (the caller's array plus one per ego in its status' column) and, with cand=True, cand [B, F] (-2 inadmissible,
-        -1 clear, else the first hit step; -3 in the rows of the egos that need none).  skip [B] (optional): egos that are not planned."""
+        -1 clear, else the first hit step; -3 in the rows of the egos that need none).  skip [B] (optional): egos that are not planned.
+        With fallback.obey set the call is fp_fallback_stop_rules: the clear stops are ranked by the obeyed rules (the batch must carry
+        each one's data: rules.missing otherwise) and the namespace also has rule_bits [B] (the _abi.RULE_* the chosen stop violates, 0 =
+        clean), rule_counts [B, 5] (the caller's `rule_counts` plus one per bit of rule_bits) and, with cand=True, cand_rules [B, F]
+        uint32 (the verdict of every admissible, clear candidate; 0 elsewhere)."""
+        obey = fallback.rules_for(batch, "fallback_stop") if getattr(fallback, "obey", ()) else ()
+        if rule_counts is not None and not obey:
+            raise ValueError("fallback_stop: rule_counts needs a fallback with obey=...")
         if (best_idx is None) == (end_state is None):
             raise ValueError("fallback_stop: exactly one of best_idx / end_state")
         B = batch.B
@@ -583,9 +594,26 @@ class FrenetEngine:
             assert skip.shape == (B,)
             fb.skip = _ptr(skip)
         # (B == 0 still crosses the ABI: the argument checks are the library's)
-        _abi.check(self._lib.fp_fallback_stop(self._ctx, C.byref(p), C.byref(fb), C.byref(fs), _ptr(bi) if bi is not None else None, _ptr(es), _ptr(out.status),
-                                              _ptr(out.fb_idx), _ptr(out.hit_step), _ptr(out.hit_obs), _ptr(out.hit_speed), _ptr(out.cand) if cand else None,
-                                              _ptr(out.counts), _abi.FP_MEM_HOST, None))
+        if not obey:
+            _abi.check(self._lib.fp_fallback_stop(self._ctx, C.byref(p), C.byref(fb), C.byref(fs), _ptr(bi) if bi is not None else None, _ptr(es), _ptr(out.status),
+                                                  _ptr(out.fb_idx), _ptr(out.hit_step), _ptr(out.hit_obs), _ptr(out.hit_speed), _ptr(out.cand) if cand else None,
+                                                  _ptr(out.counts), _abi.FP_MEM_HOST, None))
+            return out
+        out.rule_bits = np.zeros(B, dtype=np.uint32)
+        out.cand_rules = np.zeros((B, F), dtype=np.uint32) if cand else None
+        out.rule_counts = np.zeros((B, _abi.FP_RULE_COUNT), dtype=np.int32) if rule_counts is None else np.array(rule_counts, dtype=np.int32, order="C")
+        if out.rule_counts.shape != (B, _abi.FP_RULE_COUNT):
+            raise ValueError(f"fallback_stop: rule_counts must be [B={B}, {_abi.FP_RULE_COUNT}], got {out.rule_counts.shape}")
+
+        def rule_addr(name):
+            held[name] = np.ascontiguousarray(rules_mod.array(batch, name))  # (kept alive over the call)
+            return _ptr(held[name])
+
+        rs, structs = rules_mod.rule_set(batch, rule_addr, obey)
+        _abi.check(self._lib.fp_fallback_stop_rules(self._ctx, C.byref(p), C.byref(fb), C.byref(fs), C.byref(rs), _ptr(bi) if bi is not None else None, _ptr(es),
+                                                    _ptr(out.status), _ptr(out.fb_idx), _ptr(out.hit_step), _ptr(out.hit_obs), _ptr(out.hit_speed),
+                                                    _ptr(out.cand) if cand else None, _ptr(out.cand_rules) if cand else None, _ptr(out.rule_bits),
+                                                    _ptr(out.counts), _ptr(out.rule_counts), _abi.FP_MEM_HOST, None))
         return out
 
     def fallback_stop_device(self, params: _abi.FpParams, fb: _abi.FpBatch, fallback: _abi.FpFallback, end_state: int, status: int, fb_idx: int, hit_step: int,
@@ -596,6 +624,16 @@ class FrenetEngine:
         _abi.check(self._lib.fp_fallback_stop(self._ctx, C.byref(params), C.byref(fb), C.byref(fallback), best_idx or None, end_state or None, status or None,
                                               fb_idx or None, hit_step or None, hit_obs or None, hit_speed or None, cand or None, counts or None,
                                               _abi.FP_MEM_DEVICE, stream or None))
+
+    def fallback_stop_rules_device(self, params: _abi.FpParams, fb: _abi.FpBatch, fallback: _abi.FpFallback, rule_set: _abi.FpRuleSet, end_state: int, status: int,
+                                   fb_idx: int, hit_step: int, hit_obs: int, hit_speed: int, rule_bits: int, best_idx: int = 0, cand: int = 0, cand_rules: int = 0,
+                                   counts: int = 0, rule_counts: int = 0, stream: int = 0):
+        """Enqueue the fallback that obeys the rules behind a plan call (fp_fallback_stop_rules; device addresses, rule_set from
+        rules.rule_set with device addresses): as fallback_stop_device, plus rule_bits [B], cand_rules [B][F] or 0 and rule_counts [B][5]
+        in/out or 0.  One launch, nothing allocated, nothing waited for."""
+        _abi.check(self._lib.fp_fallback_stop_rules(self._ctx, C.byref(params), C.byref(fb), C.byref(fallback), C.byref(rule_set), best_idx or None, end_state or None,
+                                                    status or None, fb_idx or None, hit_step or None, hit_obs or None, hit_speed or None, cand or None,
+                                                    cand_rules or None, rule_bits or None, counts or None, rule_counts or None, _abi.FP_MEM_DEVICE, stream or None))
 
     def predict_obstacles(self, batch, model, state, frame_of_scene=None, t0=0, n_rows: int | None = None, out: np.ndarray | None = None):
         """The obstacle pose table of `batch` predicted from tracks (fp_obstacles_predict through FP_MEM_HOST; the definition:
@@ -719,9 +757,12 @@ class FrenetEngine:
         May be combined with rules= (the audit of what is returned).
         fallback=FallbackStop(...): behind the walks (enforce= included), the egos whose end_state is NaN get a stopping manoeuvre
         (fallback_stop): also `fallback`, its namespace - fallback.end_state [B, 3] is the plan every ego drives.  end_state, rule_bits
-        and the series are the call's own answer without it.
+        and the series are the call's own answer without it.  A fallback with obey=... ranks its clear stops by those rules
+        (fp_fallback_stop_rules; fallback.rule_bits [B] = what the chosen stop violates), whatever rules= / enforce= name.
         """
         B = batch.B
+        if fallback is not None and getattr(fallback, "obey", ()):
+            fallback.rules_for(batch, "plan_fiss(fallback=...)")  # (a rule without data: refused before anything runs)
         audit = rules_mod.check_names(rules, batch, "plan_fiss(rules=...)") if rules else ()
         enforced = rules_mod.check_names(enforce, batch, "plan_fiss(enforce=...)") if enforce else ()
         plus = kind in ("FISS+", _abi.FP_FISS_PLUS)

@@ -1,7 +1,8 @@
 """The family of stopping manoeuvres fp_fallback_stop chooses from, described once (the definition: include/frenet_gpu.h).
 
-FallbackStop holds the stop times, the lateral end offsets and the deceleration bound, validates them without a device and builds the
-call's ctypes struct for either memory space, like the rule descriptions in rules.py.
+FallbackStop holds the stop times, the lateral end offsets, the deceleration bound and the road rules the stop obeys (`obey`: then the
+call is fp_fallback_stop_rules), validates them without a device and builds the call's ctypes struct for either memory space, like the
+rule descriptions in rules.py.
 """
 from __future__ import annotations
 
@@ -10,14 +11,22 @@ import math
 import numpy as np
 
 from . import _abi
+from . import rules as _rules
 
 
 class FallbackStop:
-    """FallbackStop(stop_times, d_targets=None, max_decel=inf): candidate f = i_d * n_stop + i_T brakes to v = 0 within stop_times[i_T]
-    and ends at lateral offset d_targets[i_d] (NaN = the ego's own d0: stay where you are).  d_targets=None means
-    [nan, *batch.d_samples], resolved per batch by targets()."""
+    """FallbackStop(stop_times, d_targets=None, max_decel=inf, obey=()): candidate f = i_d * n_stop + i_T brakes to v = 0 within
+    stop_times[i_T] and ends at lateral offset d_targets[i_d] (NaN = the ego's own d0: stay where you are).  d_targets=None means
+    [nan, *batch.d_samples], resolved per batch by targets().  obey: any subset of the names in rules.TABLE - the clear stops are then
+    ranked by those rules (fp_fallback_stop_rules: a clean stop before a violating one, the gentlest clean stop, else the fewest rules
+    broken and the hardest brake); the batch must carry each rule's data when the call is made (rules_for).  obey=(): fp_fallback_stop."""
 
-    def __init__(self, stop_times, d_targets=None, max_decel: float = math.inf):
+    def __init__(self, stop_times, d_targets=None, max_decel: float = math.inf, obey=()):
+        asked = () if obey is None else (obey,) if isinstance(obey, str) else tuple(obey)
+        for n in asked:
+            if n not in _rules.by_name:
+                raise ValueError(f"FallbackStop: unknown rule {n!r} in obey (rules are a subset of {tuple(_rules.by_name)})")
+        self.obey = tuple(n for n in _rules.by_name if n in asked)  # (the order the rules run in)
         t = np.atleast_1d(np.asarray(stop_times, dtype=np.float64))
         if t.ndim != 1 or t.size < 1:
             raise ValueError("FallbackStop: stop_times must be a non-empty 1-d sequence")
@@ -51,6 +60,10 @@ class FallbackStop:
 
     def n_candidates(self, batch) -> int:
         return int(self.targets(batch).size * self.stop_times.size)
+
+    def rules_for(self, batch, who: str = "FallbackStop") -> tuple:
+        """The obeyed rules in the order they run; ValueError (rules.missing) for a rule `batch` carries no data for."""
+        return _rules.check_names(self.obey, batch, f"{who}(obey=...)")
 
     def points_max(self, tick_t: float) -> int:
         """The series points the longest stop time needs (what fp_params.points_max must cover on a device call)."""

@@ -264,7 +264,11 @@ class FrenetOptimalPlanner:
         stop without contact first, else the latest contact (include/frenet_gpu.h) - with `is_fallback` True and the series of
         fp_eval_trajs; `planner.fallback_info` carries status (_abi.FALLBACK_*), fb_idx, hit_step, hit_obs and hit_speed.  When no
         candidate of the family is admissible (status FALLBACK_NONE) plan() returns what it returns today.  best_traj, prev_best_idx
-        and the Stats are the planner's own: the fallback changes none of them.  The fallback obeys no rule pass."""
+        and the Stats are the planner's own: the fallback changes none of them.  FallbackStop(..., obey=(...)) ranks the clear stops
+        by those road rules (fp_fallback_stop_rules; the rule's data must have been set - set_road_boundary / set_speed_profile / set_gates
+        / set_time_gap - when plan() needs the fallback: a rule without data raises rules.missing from that plan() call.  Those four setters
+        are FrenetOptimalPlanner's alone, so FOP+, FISS and FISS+ take obey=() only in practice); `fallback_info.rule_bits` is then what
+        the chosen stop violates (0 = clean, and 0 without obey)."""
         self._fallback_stop = fallback
 
     def _fallback(self, batch: ProblemBatch, none):
@@ -274,7 +278,7 @@ class FrenetOptimalPlanner:
             return none
         r = self._engine.fallback_stop(batch, fb, best_idx=np.array([-1], dtype=np.int32))
         self.fallback_info = SimpleNamespace(status=int(r.status[0]), fb_idx=int(r.fb_idx[0]), hit_step=int(r.hit_step[0]), hit_obs=int(r.hit_obs[0]),
-                                             hit_speed=float(r.hit_speed[0]))
+                                             hit_speed=float(r.hit_speed[0]), rule_bits=int(r.rule_bits[0]) if getattr(fb, "obey", ()) else 0)
         if self.fallback_info.status == _abi.FALLBACK_NONE:
             return none
         es = r.end_state[0]

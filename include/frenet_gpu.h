@@ -316,7 +316,7 @@ int fp_ctx_destroy(fp_ctx* ctx);
 int fp_ctx_set_option(fp_ctx* ctx, const char* name, int value);
 /* Reads an option back, or one of the read-only counters "clearance_launches" (launches of the clearance rescoring kernel,
  * fp_params.w_obstacle > 0, of this ctx so far), "looplog_launches" (launches of fp_loop_record's kernel), "rank_launches" (launches of
- * fp_rank_feasible's kernel), "boundary_launches" (launches of fp_boundary_mask's kernel), "envelope_launches" (launches of fp_speed_envelope's kernel), "gate_launches" (launches of fp_gate_mask's kernel), "margin_launches" (launches of fp_traj_margins' kernel), "fallback_launches" (launches of fp_fallback_stop's kernel), "rules_eval_launches" (launches of fp_rules_eval's kernel), "predict_launches" (launches of
+ * fp_rank_feasible's kernel), "boundary_launches" (launches of fp_boundary_mask's kernel), "envelope_launches" (launches of fp_speed_envelope's kernel), "gate_launches" (launches of fp_gate_mask's kernel), "margin_launches" (launches of fp_traj_margins' kernel), "fallback_launches" (launches of fp_fallback_stop's kernel), "fallback_rules_launches" (launches of fp_fallback_stop_rules' kernel), "rules_eval_launches" (launches of fp_rules_eval's kernel), "predict_launches" (launches of
  * fp_obstacles_predict's kernel), "from_state_launches" (launches of fp_from_state's kernel), "lattice_launches" (dense lattice launches of this ctx so far) and
  * "lattice_ordered_launches" (those dispatched in a feedback order or in the order of fp_batch.launch_order) - bench.py reports when an
  * order took effect -, "lattice_launches_2" / "_3" / "_4" (PROCESS-wide: fused lattice launches so far by workgroups per compute unit). */
@@ -785,8 +785,9 @@ int fp_traj_margins(fp_ctx* ctx, const fp_params* params, const fp_batch* batch,
  * needs more than FP_MAX_POINTS points (FP_ELIMIT; on the device such a candidate is inadmissible) and a best_idx >= nd*nv*nt of an
  * ego that is not skipped (FP_EINVAL, as fp_advance answers; on the device such an ego gets a NaN end state).
  * Also read-only in fp_ctx_get_option: "fallback_launches" = launches of the kernel on this ctx so far (0 for a caller that never asks).
+ * The rules: fp_fallback_stop itself looks at no rule pass - a stop may end across a stop line.  fp_fallback_stop_rules (below) is the
+ * call that ranks the clear stops by the rule set.
  * Deliberately not done:
- *   - the fallback obeys no rule pass: a stop may end across a stop line;
  *   - the footprint's heading is the series' own yaw, the difference quotient of calc_global_paths: an ego that stands from the first
  *     point has yaw 0, as every lattice candidate at v = 0 already has in every entry point - changing that is a change to all of them;
  *   - no fp_shard_call slot, nothing inside fp_plan_step / fp_plan_fiss_step (a loop enqueues plan, fp_fallback_stop, fp_advance),
@@ -811,6 +812,60 @@ int fp_fallback_stop(fp_ctx* ctx, const fp_params* params, const fp_batch* batch
                      int32_t* cand,             /* NULL or [B][n_d * n_stop] */
                      int32_t* counts,           /* NULL or [B][4] in/out */
                      int mem, void* stream);
+
+/* ---- the stopping manoeuvre that obeys the road rules (added WITHIN ABI 18: detect it by looking the symbol up, e.g. dlsym) ----------
+ * The rule passes are the main producer of egos without a plan: an ego whose every candidate is flagged by fp_speed_envelope,
+ * fp_gate_mask, fp_boundary_mask, fp_gap_mask or the enforced FISS walks gets best_idx = -1, and fp_fallback_stop then prefers the
+ * gentlest clear stop - the one most likely to roll over the line the gate has just closed.  fp_fallback_stop_rules is
+ * fp_fallback_stop with one more key in its choice: the verdict of the rule set on every clear candidate.
+ *
+ * Unchanged: need(b), the family, admissibility and the first contact are fp_fallback_stop's, word for word.
+ * rule verdict  of a candidate, taken only for an admissible candidate without contact: the rule_bits fp_rules_eval defines for the
+ *              end state (d, 0, T) when the flag word on entry carries the candidate's M (M << FP_FLAG_M_SHIFT) and no FP_FLAG_* bit.
+ *              The rules are those whose pointer in `rules` is not NULL; they run in the passes' order, the gaps only if the three
+ *              rules before them left the word feasible; the gates' waiver is taken from the ego's present state with the gates' own
+ *              max_decel.  An inadmissible candidate and a candidate with contact have verdict 0: no rule is evaluated for them.
+ *              cand_rules[b][f] = that verdict.
+ * choice       among the admissible candidates only, smaller first; every key is an integer or one exact IEEE operation on inputs:
+ *                1. a candidate without contact beats one with contact;
+ *                2. among candidates without contact a clean verdict (0) beats a violating one;
+ *                3. among clean candidates the larger i_T wins (the gentlest stop);
+ *                4. among violating candidates the smaller number of FP_RULE_* bits set wins, then the smaller i_T (it brakes hardest
+ *                   and overshoots least);
+ *                5. among candidates with contact the larger hit_step wins, then the smaller i_T;
+ *                6. then the smaller fabs(d_end - d0), then the smaller i_d.
+ * outputs      status keeps its four values (FP_FALLBACK_CLEAR still says "no contact").  rule_bits[b] = the chosen candidate's verdict: 0
+ *              = clean; 0 also for NOT_NEEDED, NONE, CONTACT and skipped egos.  rule_counts[b][log2 bit] += 1 for every bit of
+ *              rule_bits[b] (accumulated by the ego's own workgroup without atomics, like fp_rules_eval's counts).  Everything else is
+ *              as fp_fallback_stop writes it, end_state of the egos that have a plan included; cand_rules, like cand, is untouched in
+ *              the rows of the egos that need no fallback.
+ * Equivalence: with a rule set that cannot speak on the batch - limits +inf, gates never closed, a corridor wider than any footprint,
+ * lags with no obstacle near - every output shared with fp_fallback_stop equals that call's bit for bit.
+ *
+ * FP_MEM_DEVICE: one kernel (the fallback kernel's rule instance), nothing allocated, nothing waited for, capturable.  FP_MEM_HOST
+ * stages the batch, the family and the rule arrays through the ctx and waits, as fp_rules_eval's host call does.  The rules' tables
+ * share the kernel's LDS budget with the obstacle rows: a batch whose rows just fit fp_fallback_stop's launch reads them from the scene
+ * table here - the result is the same.
+ * Errors, all before any launch: fp_fallback_stop's own; a NULL rules, a set whose four members are all NULL, a NULL rule_bits:
+ * FP_EINVAL; every rule that is on raises its own pass' argument errors with that pass' messages (FP_MEM_HOST: also what the pass
+ * finds in its arrays).
+ * Also read-only in fp_ctx_get_option: "fallback_rules_launches" = launches of the rule instance on this ctx so far;
+ * "fallback_launches" does not move for this call.
+ * Deliberately not done: no fp_shard_call slot; nothing inside fp_plan_step / fp_plan_fiss_step (a loop enqueues plan,
+ * fp_fallback_stop_rules, fp_advance); no per-row marker in the loop log; a closed loop that audits (fp_rules_eval on the planner's own
+ * end state) beside a fallback stays refused by the Python runner. */
+int fp_fallback_stop_rules(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, const fp_fallback* fallback,
+                           const fp_rule_set* rules,
+                           const int32_t* best_idx,   /* NULL or [B] */
+                           double* end_state,         /* [B][3] in/out */
+                           int32_t* status, int32_t* fb_idx,
+                           int32_t* hit_step, int32_t* hit_obs, double* hit_speed,   /* [B] each */
+                           int32_t* cand,             /* NULL or [B][n_d * n_stop], as fp_fallback_stop */
+                           uint32_t* cand_rules,      /* NULL or [B][n_d * n_stop] out */
+                           uint32_t* rule_bits,       /* [B] out: FP_RULE_* the chosen stop violates, 0 = clean */
+                           int32_t* counts,           /* NULL or [B][4] in/out, as fp_fallback_stop */
+                           int32_t* rule_counts,      /* NULL or [B][FP_RULE_COUNT] in/out */
+                           int mem, void* stream);
 
 /* ---- obstacle pose tables from tracks (added WITHIN ABI 18: detect it by looking the symbol up, e.g. dlsym) --------------
  * The reference has no predictor: it reads CommonRoad's recorded trajectories through `state_at_time` and skips an obstacle that has no
