@@ -32,7 +32,7 @@ _up = C.POINTER(C.c_uint32)
 
 # every symbol include/frenet_gpu.h declares (tests check the library exports all of them)
 EXPORTED_SYMBOLS = ("fp_abi_version", "fp_build_flags", "fp_build_compiler", "fp_last_error", "fp_device_count", "fp_device_info", "fp_ctx_create", "fp_ctx_destroy", "fp_ctx_set_option", "fp_ctx_get_option", "fp_ctx_join",
-                    "fp_plan_dense", "fp_winner_trajs", "fp_rank_feasible", "fp_boundary_mask", "fp_speed_envelope", "fp_gate_mask", "fp_gap_mask", "fp_rules_eval", "fp_traj_margins", "fp_fallback_stop", "fp_fallback_stop_rules", "fp_obstacles_predict", "fp_eval_trajs", "fp_plan_fiss", "fp_advance", "fp_plan_step", "fp_plan_fiss_step", "fp_plan_fiss_rules", "fp_loop_record", "fp_frames_build", "fp_from_state", "fp_materialize_all",
+                    "fp_plan_dense", "fp_winner_trajs", "fp_rank_feasible", "fp_boundary_mask", "fp_speed_envelope", "fp_gate_mask", "fp_gap_mask", "fp_rules_eval", "fp_traj_margins", "fp_fallback_stop", "fp_fallback_stop_rules", "fp_obstacles_predict", "fp_obstacles_from_plans", "fp_eval_trajs", "fp_plan_fiss", "fp_advance", "fp_plan_step", "fp_plan_fiss_step", "fp_plan_fiss_rules", "fp_loop_record", "fp_frames_build", "fp_from_state", "fp_materialize_all",
                     "fp_group_create", "fp_group_destroy", "fp_group_submit", "fp_group_wait")
 
 
@@ -109,6 +109,15 @@ FP_TRACK_NONE, FP_TRACK_LANE, FP_TRACK_ARC = 0, 1, 2  # fp_tracks.model (fp_obst
 class FpTracks(C.Structure):
     """The obstacle tracks a pose table is predicted from (fp_obstacles_predict)."""
     _fields_ = [("model", C.c_void_p), ("state", C.c_void_p), ("frame_of_scene", C.c_void_p), ("t0", C.c_void_p), ("n_rows", C.c_int32)]
+
+
+FP_TAIL_NONE, FP_TAIL_HOLD, FP_TAIL_COAST = 0, 1, 2  # fp_agents.tail (fp_obstacles_from_plans)
+
+
+class FpAgents(C.Structure):
+    """The groups of egos that see each other's plans (fp_obstacles_from_plans)."""
+    _fields_ = [("G", C.c_int32), ("n_members", C.c_int32), ("group_ptr", C.c_void_p), ("members", C.c_void_p), ("col_base", C.c_int32),
+                ("n_rows", C.c_int32), ("tail", C.c_int32), ("reserved0", C.c_int32)]
 
 
 AUDIT_NEAR_TIE, AUDIT_CONTACT, AUDIT_REORDERED, AUDIT_TIES_OVERFLOW = 1, 2, 4, 8
@@ -228,6 +237,9 @@ def load() -> C.CDLL:
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_int, C.c_void_p]
     L.fp_obstacles_predict.argtypes = [C.c_void_p, C.POINTER(FpParams), C.POINTER(FpBatch), C.POINTER(FpTracks), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    if hasattr(L, "fp_obstacles_from_plans"):  # (likewise)
+        L.fp_obstacles_from_plans.argtypes = [C.c_void_p, C.POINTER(FpParams), C.POINTER(FpBatch), C.POINTER(FpAgents), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_int, C.c_void_p]
     L.fp_eval_trajs.argtypes = [C.c_void_p, C.POINTER(FpParams), C.POINTER(FpBatch), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.c_int32, C.c_int32, C.c_int, C.c_void_p]
     L.fp_plan_fiss.argtypes = [C.c_void_p, C.POINTER(FpParams), C.POINTER(FpBatch), C.POINTER(FpFissOpts), C.POINTER(FpFissIo), C.c_int, C.c_void_p]

@@ -203,6 +203,7 @@ struct fp_ctx {
     int margin_launches = 0;       // fp_ctx_get_option("margin_launches"): launches of the plan-margin kernel (fp_traj_margins)
     int fallback_launches = 0;     // fp_ctx_get_option("fallback_launches"): launches of the fallback kernel (fp_fallback_stop)
     int fallback_rules_launches = 0;  // fp_ctx_get_option("fallback_rules_launches"): launches of its rule instance (fp_fallback_stop_rules)
+    int from_plans_launches = 0;   // fp_ctx_get_option("from_plans_launches"): launches of the shared-plans kernel (fp_obstacles_from_plans)
     int predict_launches = 0;      // fp_ctx_get_option("predict_launches"): launches of the obstacle prediction kernel (fp_obstacles_predict)
     int from_state_launches = 0;   // fp_ctx_get_option("from_state_launches"): launches of the projection kernel (fp_from_state)
     int fiss_rules_calls = 0;      // fp_ctx_get_option("fiss_rules_calls"): calls of fp_plan_fiss_rules that passed their argument checks
@@ -1538,7 +1539,7 @@ int fp_ctx_get_option(fp_ctx* ctx, const char* name, int* value)
     const struct { const char* n; int v; } tab[] = {
         {"lattice_kernel", ctx->lattice_kernel}, {"lattice_split", ctx->lattice_split}, {"lattice_group", ctx->lattice_group}, {"lattice_tail", ctx->lattice_tail}, {"lattice_occupancy", ctx->lattice_occupancy}, {"resident_groups", ctx->resident_groups}, {"zero_copy_in", ctx->zero_copy_in}, {"stage_kernel", ctx->stage_kernel}, {"inline_inputs", ctx->inline_inputs}, {"lattice_order", ctx->lattice_order},
         {"refine_table_kb", ctx->refine_table_kb}, {"fiss_stages", ctx->fiss_stages}, {"fiss_jump", ctx->fiss_jump}, {"validate", ctx->validate}, {"lattice_winner", ctx->lattice_winner}, {"fiss_fused", ctx->fiss_fused}, {"appended_workgroups", ctx->appended_ok ? 1 : 0}, {"handover_failed", ctx->hand_err ? *(volatile int32_t*)ctx->hand_err : 0}, {"overlap", ctx->overlap}, {"overlapped_calls", ctx->overlapped_calls}, {"clearance_launches", ctx->clearance_launches + (ctx->twin ? ctx->twin->clearance_launches : 0)}, {"lattice_launches", ctx->lattice_launches + (ctx->twin ? ctx->twin->lattice_launches : 0)},
-        {"looplog_launches", ctx->looplog_launches}, {"rank_launches", ctx->rank_launches}, {"boundary_launches", ctx->boundary_launches}, {"envelope_launches", ctx->envelope_launches}, {"gate_launches", ctx->gate_launches}, {"gap_launches", ctx->gap_launches}, {"margin_launches", ctx->margin_launches}, {"fallback_launches", ctx->fallback_launches}, {"fallback_rules_launches", ctx->fallback_rules_launches}, {"rules_eval_launches", ctx->rules_eval_launches}, {"fiss_rules_calls", ctx->fiss_rules_calls}, {"predict_launches", ctx->predict_launches}, {"from_state_launches", ctx->from_state_launches}, {"lattice_ordered_launches", ctx->lattice_ordered_launches + (ctx->twin ? ctx->twin->lattice_ordered_launches : 0)},
+        {"looplog_launches", ctx->looplog_launches}, {"rank_launches", ctx->rank_launches}, {"boundary_launches", ctx->boundary_launches}, {"envelope_launches", ctx->envelope_launches}, {"gate_launches", ctx->gate_launches}, {"gap_launches", ctx->gap_launches}, {"margin_launches", ctx->margin_launches}, {"fallback_launches", ctx->fallback_launches}, {"fallback_rules_launches", ctx->fallback_rules_launches}, {"rules_eval_launches", ctx->rules_eval_launches}, {"fiss_rules_calls", ctx->fiss_rules_calls}, {"predict_launches", ctx->predict_launches}, {"from_plans_launches", ctx->from_plans_launches}, {"from_state_launches", ctx->from_state_launches}, {"lattice_ordered_launches", ctx->lattice_ordered_launches + (ctx->twin ? ctx->twin->lattice_ordered_launches : 0)},
         {"lattice_launches_2", (int)fp::lattice_launches_per_cu(0)}, {"lattice_launches_3", (int)fp::lattice_launches_per_cu(1)}, {"lattice_launches_4", (int)fp::lattice_launches_per_cu(2)}};
     for (const auto& t : tab)
         if (strcmp(name, t.n) == 0) { *value = t.v; return FP_OK; }
@@ -2131,6 +2132,105 @@ int fp_obstacles_predict(fp_ctx* ctx, const fp_params* params, const fp_batch* b
         src = sc_src; dst = sc_dst; run = count;
     }
     if (run) HIP_TRY(hipMemcpyAsync(dst, src, run * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    return hs.fetch_out();
+}
+
+int fp_obstacles_from_plans(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, const fp_agents* agents, const int32_t* best_idx,
+                            const double* end_state, double* obs_pose, int32_t* final_time_step, int mem, void* stream)
+{
+    if (!ctx) return fail(FP_EINVAL, "ctx is NULL");
+    if (mem != FP_MEM_HOST && mem != FP_MEM_DEVICE) return fail(FP_EINVAL, "mem must be FP_MEM_HOST or FP_MEM_DEVICE");
+    if (!params || !batch || !agents || !obs_pose) return fail(FP_EINVAL, "fp_obstacles_from_plans: params / batch / agents / obs_pose must not be NULL");
+    // (the table may be an input of overlapped dense calls still in flight on the ctx's internal streams)
+    if (ctx->ov_pending[0] || ctx->ov_pending[1]) FP_TRY(overlap_join(ctx, mem == FP_MEM_DEVICE ? (hipStream_t)stream : ctx->stream));
+    FP_TRY(check_params(params));
+    if (batch->B < 0 || batch->F < 1 || batch->NX < 2 || batch->S < 0 || batch->T_obs < 0 || batch->n_obs < 0)
+        return fail(FP_EINVAL, "fp_obstacles_from_plans: bad batch sizes B=%d F=%d NX=%d S=%d T_obs=%d n_obs=%d", batch->B, batch->F, batch->NX, batch->S, batch->T_obs, batch->n_obs);
+    if (batch->NX > FP_MAX_KNOTS) return fail(FP_ELIMIT, "NX=%d exceeds FP_MAX_KNOTS", batch->NX);
+    if (!batch->d_samples || !batch->t_samples || !batch->v_samples || !batch->ego || !batch->frame_of || !batch->scene_of || !batch->t_now || !batch->nx ||
+        !batch->knots || !batch->coef)
+        return fail(FP_EINVAL, "fp_obstacles_from_plans: batch has a NULL array");
+    if ((best_idx == nullptr) == (end_state == nullptr)) return fail(FP_EINVAL, "fp_obstacles_from_plans: exactly one of best_idx / end_state must be given");
+    if (agents->n_rows <= 0) return fail(FP_EINVAL, "fp_obstacles_from_plans: n_rows=%d must be > 0", agents->n_rows);
+    if (agents->tail < FP_TAIL_NONE || agents->tail > FP_TAIL_COAST) return fail(FP_EINVAL, "fp_obstacles_from_plans: tail=%d is not one of FP_TAIL_*", agents->tail);
+    if (agents->G < 0 || agents->n_members < 0) return fail(FP_EINVAL, "fp_obstacles_from_plans: G=%d, n_members=%d must be >= 0", agents->G, agents->n_members);
+    if (agents->G == 0 || agents->n_members == 0) return FP_OK;  // no element to write
+    if (!agents->group_ptr || !agents->members) return fail(FP_EINVAL, "fp_obstacles_from_plans: group_ptr / members must not be NULL");
+    if (agents->col_base < 0) return fail(FP_EINVAL, "fp_obstacles_from_plans: col_base=%d must be >= 0", agents->col_base);
+    HIP_TRY(hipSetDevice(ctx->device));
+    fp::KernelArgs ka;
+    ka.p = *params;
+    ka.r = no_result();
+    fp::AgentArgs a;
+    a.G = agents->G; a.n_members = agents->n_members; a.col_base = agents->col_base; a.n_rows = agents->n_rows; a.tail = agents->tail;
+    if (mem == FP_MEM_DEVICE) {
+        if ((uintptr_t)obs_pose & 15u) return fail(FP_EINVAL, "fp_obstacles_from_plans: obs_pose must be 16-byte aligned");
+        ka.b = *batch;
+        a.group_ptr = agents->group_ptr; a.members = agents->members; a.best_idx = best_idx; a.end_state = end_state;
+        a.obs_pose = obs_pose; a.final_time_step = final_time_step;
+        LAUNCH_TRY(fp::launch_obstacles_from_plans(ka, a, (hipStream_t)stream), "shared-plans kernel");
+        ++ctx->from_plans_launches;
+        return FP_OK;
+    }
+    // host arrays: what the device path decides silently is an error the host path can name
+    const int G = agents->G, B = batch->B;
+    if (agents->group_ptr[0] != 0) return fail(FP_EINVAL, "fp_obstacles_from_plans: group_ptr[0]=%d must be 0", agents->group_ptr[0]);
+    for (int g = 0; g < G; ++g) {
+        const int lo = agents->group_ptr[g], hi = agents->group_ptr[g + 1];
+        if (hi < lo) return fail(FP_EINVAL, "fp_obstacles_from_plans: group_ptr is not ascending at group %d (%d > %d)", g, lo, hi);
+        if ((long)agents->col_base + (hi - lo) > batch->n_obs)
+            return fail(FP_EINVAL, "fp_obstacles_from_plans: group %d: col_base + group size = %d + %d exceeds n_obs = %d", g, agents->col_base, hi - lo, batch->n_obs);
+    }
+    if (agents->group_ptr[G] != agents->n_members)
+        return fail(FP_EINVAL, "fp_obstacles_from_plans: n_members=%d is not group_ptr[G]=%d", agents->n_members, agents->group_ptr[G]);
+    FP_TRY(check_frames_host(batch));
+    {
+        std::vector<int32_t> group_of((size_t)B, -1), member_of((size_t)(batch->S > 0 ? batch->S : 0), -1);
+        for (int g = 0; g < G; ++g)
+            for (int k = agents->group_ptr[g]; k < agents->group_ptr[g + 1]; ++k) {
+                const int e = agents->members[k];
+                if (e < 0 || e >= B) return fail(FP_EINVAL, "fp_obstacles_from_plans: member %d of group %d is ego %d, outside 0 .. B-1 (B=%d)", k - agents->group_ptr[g], g, e, B);
+                if (group_of[e] >= 0) return fail(FP_EINVAL, "fp_obstacles_from_plans: ego %d is a member of group %d and of group %d", e, group_of[e], g);
+                group_of[e] = g;
+                const int sc = batch->scene_of[e];
+                if (sc < 0) return fail(FP_EINVAL, "fp_obstacles_from_plans: member %d of group %d (ego %d) has no scene (scene_of = %d)", k - agents->group_ptr[g], g, e, sc);
+                if (sc >= batch->S) return fail(FP_EINVAL, "scene_of[%d]=%d out of range", e, sc);
+                if (member_of[sc] >= 0) return fail(FP_EINVAL, "fp_obstacles_from_plans: ego %d and ego %d share scene %d (every member needs a scene of its own)", member_of[sc], e, sc);
+                member_of[sc] = e;
+            }
+    }
+    const size_t nB = (size_t)B;
+    if (best_idx) {
+        const long n_cand = (long)params->nd * params->nv * params->nt;
+        for (int i = 0; i < B; ++i)
+            if (best_idx[i] >= n_cand && !(batch->skip && batch->skip[i]))
+                return fail(FP_EINVAL, "fp_obstacles_from_plans: best_idx of ego %d = %d is outside the lattice (nd*nv*nt = %ld)", i, best_idx[i], n_cand);
+        ka.p.points_max = host_points_max(params, batch, nullptr, 0, 0);
+    } else {
+        ka.p.points_max = host_points_max(params, batch, end_state + 2, nB, 3);
+    }
+    const size_t S = (size_t)batch->S, fn = (size_t)batch->F * batch->NX;
+    ka.b = *batch;
+    ka.b.obs_pose = nullptr; ka.b.obs_dims = nullptr; ka.b.final_time_step = nullptr; ka.b.obs_poly = nullptr; ka.b.obs_nvert = nullptr; ka.b.launch_order = nullptr;
+    HostStage hs(ctx);
+    StageList sl;
+    stage_samples(sl, params, batch, &ka.b.d_samples, &ka.b.t_samples, &ka.b.v_samples);
+    sl.in(batch->ego, nB * 6, &ka.b.ego);
+    sl.in(batch->frame_of, nB, &ka.b.frame_of);
+    sl.in(batch->scene_of, nB, &ka.b.scene_of);
+    sl.in(batch->t_now, nB, &ka.b.t_now);
+    sl.in(batch->nx, (size_t)batch->F, &ka.b.nx);
+    sl.in(batch->knots, fn, &ka.b.knots);
+    sl.in(batch->coef, fn * 8, &ka.b.coef);
+    if (batch->skip) sl.in(batch->skip, nB, &ka.b.skip);
+    sl.in(agents->group_ptr, (size_t)G + 1, &a.group_ptr);
+    sl.in(agents->members, (size_t)agents->n_members, &a.members);
+    if (best_idx) sl.in(best_idx, nB, &a.best_idx); else sl.in(end_state, nB * 3, &a.end_state);
+    sl.in_mut(obs_pose, S * (size_t)batch->T_obs * batch->n_obs * 4, &a.obs_pose);
+    if (final_time_step) sl.in_mut(final_time_step, S, &a.final_time_step);
+    FP_TRY(hs.commit(sl));
+    LAUNCH_TRY(fp::launch_obstacles_from_plans(ka, a, ctx->stream), "shared-plans kernel");
+    ++ctx->from_plans_launches;
     return hs.fetch_out();
 }
 

@@ -377,6 +377,19 @@ struct PredictArgs {
     int32_t* final_time_step = nullptr;
 };
 hipError_t launch_obstacles_predict(PredictArgs a, hipStream_t stream);
+// The chosen plans of grouped egos as obstacle columns of each other's scenes (frenet_agents.hip, fp_obstacles_from_plans): one
+// workgroup per destination member.  ka.b.obs_pose and ka.r are not read.  Device addresses; exactly one of best_idx [B] / end_state
+// [B][3] set; final_time_step [S] or nullptr.
+struct AgentArgs {
+    int G = 0, n_members = 0, col_base = 0, n_rows = 0, tail = 0;
+    const int32_t* group_ptr = nullptr;
+    const int32_t* members = nullptr;
+    const int32_t* best_idx = nullptr;
+    const double* end_state = nullptr;
+    double* obs_pose = nullptr;
+    int32_t* final_time_step = nullptr;
+};
+hipError_t launch_obstacles_from_plans(const KernelArgs& ka, const AgentArgs& a, hipStream_t stream);
 // Series of EVERY lattice candidate: ka.r.best_traj [B*C][16][traj_stride], ka.r.best_flags [B*C] (N, M, truncated).
 hipError_t launch_materialize_all(const KernelArgs& ka, hipStream_t stream);
 hipError_t launch_eval_trajs(const KernelArgs& ka, int K, const double* end_states, double* cost, uint32_t* flags, double* traj,

@@ -12,6 +12,8 @@ With audit=(...) a FISS / FISS+ cycle is [plan -> rule verdict of the returned e
 not changed, the violations are counted per ego and rule on the device.
 With enforce=(...) a FISS / FISS+ cycle is ONE fp_plan_fiss_rules call with the loop's hand-over: the walks obey the rules (their validation
 sees the rules' verdicts, the visiting order stays cost-only); audit=(...) may follow it (plan, verdict, advance).
+With agents=AgentGroups(...) the members of a group see each other's plans: fp_obstacles_from_plans writes every member's chosen plan
+into the resident obstacle tables of the others in front of fp_advance.
 """
 from __future__ import annotations
 
@@ -86,7 +88,7 @@ class ClosedLoopRunner:
 
     def __init__(self, engine: FrenetEngine, dbatch: DeviceBatch, goal_xy: np.ndarray, planner: str = "FOP", fused: bool = True,
                  goal_poly: np.ndarray | None = None, goal_nv: np.ndarray | None = None, goal_intervals: np.ndarray | None = None,
-                 rules=(), audit=(), enforce=(), fallback=None):
+                 rules=(), audit=(), enforce=(), fallback=None, agents=None):
         """rules: any subset of the names in rules.TABLE - FOP only, and the batch must carry each rule's data (speed profile / gates /
         corridor / a time gap with a lag above 0).  The cycle then is fp_plan_dense into the runner's own [B][C] tables, the passes asked
         for in the table's order, whatever the caller's, each writing best_idx / best_cost, and fp_advance on the last one's winner;
@@ -113,6 +115,14 @@ class ClosedLoopRunner:
         fp_fallback_stop_rules: the clear stops are ranked by those rules - an ego in front of a closed gate stops before the line.
         self.fallback_rule_counts [B, 5] int32 counts, per ego and FP_RULE_* bit (column log2 of the bit), the cycles whose chosen stop
         violated the rule; run / run_graph return it.
+        agents: an AgentGroups - the members see each other's plans (fp_obstacles_from_plans).  The batch must give every member a scene of
+        its own (AgentGroups.attach).  The cycle then is the plan without a fused hand-over (fp_plan_dense, fp_plan_fiss or
+        fp_plan_fiss_rules with loop = NULL) -> the rule passes (if any) -> the fallback (if any) -> fp_obstacles_from_plans on the
+        RESIDENT table (dbatch.t["obs_pose"] / t["final_time_step"] are rewritten in place, cycle after cycle) -> fp_advance: a linear
+        chain on one stream, eager and from a graph; `fused` has no say.  The plans are FOP's best_idx, or end_state for FISS / FISS+
+        and whenever a fallback is present.  The first cycle plans against whatever the table holds.  The table is what
+        rules=("gaps",) reads, so agents keep a time gap to each other with no further code.  agents= with audit= is not done
+        (ValueError).  agents=None: the calls below, unchanged.
         fused: an FOP cycle is ONE launch (fp_plan_step: the workgroup that finds an ego's argmin advances the ego); False = the two
         calls fp_plan_dense + fp_advance (same results; the A/B of tests and bench).
         goal_poly [B, V, 2] + goal_nv [B] (+ goal_intervals [B, 6] = time_step / velocity / orientation lo, hi; NaN = undefined): the
@@ -122,7 +132,11 @@ class ClosedLoopRunner:
         self.enforce = self._check_enforce(enforce, planner, dbatch.host, self.rules)
         if fallback is not None and self.audit:
             raise ValueError("ClosedLoopRunner: fallback= with audit= is not done (the audit's verdict is taken on the planner's own end state)")
-        self.fallback = fallback
+        if agents is not None and self.audit:
+            raise ValueError("ClosedLoopRunner: agents= with audit= is not done (the audit's verdict is taken on the planner's own end state)")
+        if agents is not None:
+            agents.check(dbatch.host)
+        self.fallback, self.agents = fallback, agents
         self.obey = fallback.rules_for(dbatch.host, "ClosedLoopRunner(fallback=FallbackStop") if fallback is not None and getattr(fallback, "obey", ()) else ()
         torch = dbatch.torch
         self.eng, self.db, self.planner, self.fused = engine, dbatch, planner, fused
@@ -197,6 +211,14 @@ class ClosedLoopRunner:
             self.fb_params = _abi.FpParams.from_buffer_copy(dbatch.params)
             pts = max(fallback.points_max(dbatch.host.tick_t), int(dbatch.params.points_max))
             self.fb_params.points_max = min(pts, _abi.FP_MAX_POINTS) if pts > _abi.FP_FAST_POINTS else 0
+        if agents is not None:  # the groups on device addresses
+            self._ag_arrays = {}
+
+            def ag_addr(name, a):
+                self._ag_arrays[name] = torch.from_numpy(a).to(dbatch.dev)
+                return self._ag_arrays[name].data_ptr()
+
+            self.ag_struct = agents.struct(dbatch.host, ag_addr)
         if self.enforce:  # the enforced set on device addresses, and the per-ego count of rule-rejected refined candidates
             self.rejected = torch.zeros(B, dtype=i32, device=dbatch.dev)
             self.enforce_set, self._enforce_structs = _rules.rule_set(dbatch.host, lambda k: dbatch.t[k].data_ptr(), self.enforce)
@@ -260,7 +282,9 @@ class ClosedLoopRunner:
         _abi.check(eng._lib.fp_advance(eng._ctx, C.byref(db.params), C.byref(self.fb), bi, None, C.byref(self.io), _abi.FP_MEM_DEVICE, stream or None))
 
     def _step_fallback(self, stream: int):
-        """plan (no fused hand-over) -> fp_fallback_stop (with obey: fp_fallback_stop_rules) -> fp_advance(end_state): a linear chain on `stream`."""
+        """plan (no fused hand-over) -> fp_fallback_stop (with obey: fp_fallback_stop_rules) -> fp_advance(end_state): a linear chain on `stream`.
+        With agents: fp_obstacles_from_plans in front of fp_advance; without a fallback the middle call is left out and the hand-over takes
+        the planner's own best_idx (FOP) or end_state."""
         import ctypes as C
 
         db, eng = self.db, self.eng
@@ -278,6 +302,12 @@ class ClosedLoopRunner:
             eng.plan_fiss_rules_device(db.params, self.fb, self.fopts, self.fio, self.enforce_set, None, self.rejected.data_ptr(), stream)
         else:
             eng.plan_fiss_device(db.params, self.fb, self.fopts, self.fio, stream=stream)
+        if self.fallback is None:  # (agents alone)
+            es = 0 if self.planner == "FOP" else self.end_state.data_ptr()
+            eng.share_plans_device(db.params, self.fb, self.ag_struct, 0 if es else bi, es, db.t["obs_pose"].data_ptr(), db.t["final_time_step"].data_ptr(), stream)
+            _abi.check(eng._lib.fp_advance(eng._ctx, C.byref(db.params), C.byref(self.fb), None if es else bi, es or None, C.byref(self.io),
+                                           _abi.FP_MEM_DEVICE, stream or None))
+            return
         if self.obey:
             eng.fallback_stop_rules_device(self.fb_params, self.fb, self.fb_struct, self.obey_set, self.end_state.data_ptr(), self.fb_status.data_ptr(),
                                            self.fb_idx.data_ptr(), self.fb_hit_step.data_ptr(), self.fb_hit_obs.data_ptr(), self.fb_hit_speed.data_ptr(),
@@ -287,6 +317,9 @@ class ClosedLoopRunner:
             eng.fallback_stop_device(self.fb_params, self.fb, self.fb_struct, self.end_state.data_ptr(), self.fb_status.data_ptr(), self.fb_idx.data_ptr(),
                                      self.fb_hit_step.data_ptr(), self.fb_hit_obs.data_ptr(), self.fb_hit_speed.data_ptr(), best_idx=bi,
                                      counts=self.fallback_counts.data_ptr(), stream=stream)
+        if self.agents is not None:
+            eng.share_plans_device(self.fb_params, self.fb, self.ag_struct, 0, self.end_state.data_ptr(), db.t["obs_pose"].data_ptr(),
+                                   db.t["final_time_step"].data_ptr(), stream)
         _abi.check(eng._lib.fp_advance(eng._ctx, C.byref(self.fb_params), C.byref(self.fb), None, self.end_state.data_ptr(), C.byref(self.io),
                                        _abi.FP_MEM_DEVICE, stream or None))
 
@@ -294,7 +327,7 @@ class ClosedLoopRunner:
         """One plan cycle for every running ego + the state hand-over, enqueued on `stream`."""
         import ctypes as C
 
-        if self.fallback is not None:
+        if self.fallback is not None or self.agents is not None:
             return self._step_fallback(stream)
         if self.rules:
             return self._step_rules(stream)

@@ -680,6 +680,54 @@ class FrenetEngine:
         _abi.check(self._lib.fp_obstacles_predict(self._ctx, C.byref(params), C.byref(fb), C.byref(ftracks), obs_pose_ptr or None, fts_ptr or None,
                                                   _abi.FP_MEM_DEVICE, stream or None))
 
+    def share_plans(self, batch: ProblemBatch, agents, best_idx: np.ndarray | None = None, end_state: np.ndarray | None = None,
+                    skip: np.ndarray | None = None):
+        """The chosen plans of grouped egos written into each other's obstacle tables (fp_obstacles_from_plans through FP_MEM_HOST; the
+        definition: include/frenet_gpu.h).  agents: an AgentGroups; best_idx [B] (plan_dense's or a rule pass' argmin) or end_state
+        [B, 3] (plan_fiss' or the fallback's end_state) - exactly one of the two; skip [B] (optional): egos that have no plan.  `batch`
+        holds the plans' START states (the call goes before the hand-over).  Returns (obs_pose, final_time_step): copies of the batch's
+        arrays with the members' columns and clocks rewritten; the batch itself is not modified."""
+        if (best_idx is None) == (end_state is None):
+            raise ValueError("share_plans: exactly one of best_idx / end_state")
+        if not hasattr(self._lib, "fp_obstacles_from_plans"):
+            raise RuntimeError("share_plans: libfrenetgpu.so was built before fp_obstacles_from_plans existed: rebuild")
+        B = batch.B
+        if best_idx is not None:
+            plans = np.ascontiguousarray(best_idx, dtype=np.int32)
+            if plans.shape != (B,):
+                raise ValueError(f"share_plans: best_idx must be [B={B}], got {plans.shape}")
+        else:
+            plans = np.ascontiguousarray(end_state, dtype=np.float64)
+            if plans.shape != (B, 3):
+                raise ValueError(f"share_plans: end_state must be [B={B}, 3], got {plans.shape}")
+        pose = np.array(batch.obs_pose, dtype=np.float64, order="C")
+        fts = np.array(batch.final_time_step, dtype=np.int32, order="C")
+        held = {}
+
+        def addr(name, a):
+            held[name] = a
+            return _ptr(a)
+
+        fa = agents.struct(batch, addr)
+        p, fb = host_structs(batch)
+        if skip is not None:
+            skip = np.ascontiguousarray(skip, dtype=np.int32)
+            assert skip.shape == (B,)
+            fb.skip = _ptr(skip)
+        _abi.check(self._lib.fp_obstacles_from_plans(self._ctx, C.byref(p), C.byref(fb), C.byref(fa), _ptr(plans) if best_idx is not None else None,
+                                                     _ptr(plans) if best_idx is None else None, _ptr(pose) if pose.size else None,
+                                                     _ptr(fts) if fts.size else None, _abi.FP_MEM_HOST, None))
+        return pose, fts
+
+    def share_plans_device(self, params: _abi.FpParams, fb: _abi.FpBatch, fagents: _abi.FpAgents, best_idx: int, end_state: int, obs_pose_ptr: int,
+                           fts_ptr: int = 0, stream: int = 0):
+        """Enqueue the shared-plans kernel between a plan (or its fallback) and fp_advance (device addresses in fb / fagents; best_idx
+        [B] or 0, end_state [B][3] or 0 - exactly one; obs_pose_ptr [S][T_obs][n_obs][4], 16-byte aligned; fts_ptr [S] or 0): one
+        launch, nothing allocated, nothing waited for.  The groups, the plans, ego and t_now are read when the kernel runs, so a
+        captured call replays."""
+        _abi.check(self._lib.fp_obstacles_from_plans(self._ctx, C.byref(params), C.byref(fb), C.byref(fagents), best_idx or None, end_state or None,
+                                                     obs_pose_ptr or None, fts_ptr or None, _abi.FP_MEM_DEVICE, stream or None))
+
     def plan_fopplus(self, batch: ProblemBatch, winner: bool = False, traj_stride: int = TRAJ_STRIDE, traj_sparse: bool = False):
         """FopPlusPlanner.plan() for every ego of the batch (fop_plus_planner.py:16-41) on the device: the cheapest feasible
         candidate + Stats = how many candidates the cost-ordered lazy validation pops before it.  Egos whose outcome hangs on an

@@ -317,7 +317,7 @@ int fp_ctx_set_option(fp_ctx* ctx, const char* name, int value);
 /* Reads an option back, or one of the read-only counters "clearance_launches" (launches of the clearance rescoring kernel,
  * fp_params.w_obstacle > 0, of this ctx so far), "looplog_launches" (launches of fp_loop_record's kernel), "rank_launches" (launches of
  * fp_rank_feasible's kernel), "boundary_launches" (launches of fp_boundary_mask's kernel), "envelope_launches" (launches of fp_speed_envelope's kernel), "gate_launches" (launches of fp_gate_mask's kernel), "margin_launches" (launches of fp_traj_margins' kernel), "fallback_launches" (launches of fp_fallback_stop's kernel), "fallback_rules_launches" (launches of fp_fallback_stop_rules' kernel), "rules_eval_launches" (launches of fp_rules_eval's kernel), "predict_launches" (launches of
- * fp_obstacles_predict's kernel), "from_state_launches" (launches of fp_from_state's kernel), "lattice_launches" (dense lattice launches of this ctx so far) and
+ * fp_obstacles_predict's kernel), "from_plans_launches" (launches of fp_obstacles_from_plans' kernel), "from_state_launches" (launches of fp_from_state's kernel), "lattice_launches" (dense lattice launches of this ctx so far) and
  * "lattice_ordered_launches" (those dispatched in a feedback order or in the order of fp_batch.launch_order) - bench.py reports when an
  * order took effect -, "lattice_launches_2" / "_3" / "_4" (PROCESS-wide: fused lattice launches so far by workgroups per compute unit). */
 int fp_ctx_get_option(fp_ctx* ctx, const char* name, int* value);
@@ -921,6 +921,71 @@ typedef struct {
 
 int fp_obstacles_predict(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, const fp_tracks* tracks,
                          double* obs_pose, int32_t* final_time_step, int mem, void* stream);
+
+/* ---- obstacle pose columns from the egos' own plans (added WITHIN ABI 18: detect it by looking the symbol up, e.g. dlsym) ----
+ * A batch is B egos that cannot see one another: every ego plans against the obstacle table of its scene.  fp_obstacles_from_plans
+ * makes the egos each other's traffic: it writes the plan every member of a group has just chosen into the obstacle tables of the
+ * other members of its group, on the device, so that ego a's committed plan is what ego b avoids in the next cycle.
+ *
+ * The call reads params (lattice sizes, tick_t, points_max) and, from `batch`, the sizes, d_samples, t_samples, v_samples, ego,
+ * frame_of, scene_of, t_now, skip, nx, knots, coef - nothing else; batch->obs_pose is NOT read (a caller normally passes the same
+ * address as `obs_pose`).  obs_dims is the caller's to fill: an agent column has the footprint veh_l x veh_w.
+ *
+ * Definition.  Member k of group g is ego a = members[group_ptr[g] + k]; its column is c = col_base + k.  Every member has a scene of
+ * its own: scene_of[a] >= 0, distinct among all members.
+ *   a has a plan     when skip[a] == 0 (or skip is NULL); its lattice index best_idx[a] lies in 0 .. nd*nv*nt - 1 (decoded as
+ *                    i_v = idx % nv, i_T = (idx / nv) % nt, i_d = idx / (nv * nt): d_samples[i_d], v_samples[a][i_v], t_samples[i_T]) or
+ *                    its end state end_state[a] = (d, v, T) is three finite numbers; N = len(arange(0, T, tick_t)) lies in
+ *                    1 .. the points the call is sized for (fp_params.points_max); and the plan's series has M >= 2 Cartesian points
+ *                    (M = the first point whose s leaves [knots[0], knots[nx - 1]) of frame frame_of[a], else N).
+ *   pose at step i   i < M: the series' own FP_ARR_X / FP_ARR_Y / FP_ARR_YAW element - point i of the plan from ego[a], and
+ *                    yaw[i] = atan2 of the step from point i to point i + 1, the last point repeating yaw[M - 2];
+ *                    i >= M: by `tail` - FP_TAIL_NONE no pose, FP_TAIL_HOLD pose M - 1 again, FP_TAIL_COAST
+ *                    p[i] = p[M-1] + (i - M + 1) * (p[M-1] - p[M-2]) with yaw[M - 1].
+ *   written          for i = 0 .. n_rows - 1 and r = t_now[a] + i with 0 <= r < T_obs: element [scene_of[b']][r][c] of every OTHER
+ *                    member b' of g becomes (x, y, yaw, 1) - or (0, 0, 0, 0) when a has no plan or the tail gives no pose -, and
+ *                    element [scene_of[a]][r][c], a's own column in its own scene, becomes (0, 0, 0, 0): an ego never sees itself.
+ *                    Every other element of the table - other columns, other rows, the scenes of non-members - is neither read
+ *                    nor written.
+ *   final_time_step  [scene_of[a]] = min(T_obs, max(t_now[a] + n_rows, 0)) for every member a, when the pointer is not NULL.
+ * An element is a function of its source ego's state, plan, row and frame alone: two runs, and the two memory spaces, give the same
+ * bits, whatever the order of the members.
+ *
+ * Call order.  The call goes between the plan (fp_plan_dense and its rule passes, fp_plan_fiss, or the fallback behind them) and
+ * fp_advance: `ego` and `t_now` are then still the plan's start, and plan point 1 lands on row t_now + 1 - the row pose 0 of the next
+ * cycle's collision check reads.  n_rows must be at least the longest N + 1 for the next cycle's whole check horizon to be covered by
+ * freshly written rows.  The table is what fp_gap_mask reads, so agents keep a time gap to each other with no further code.
+ *
+ * FP_MEM_DEVICE: one kernel is enqueued - nothing is allocated and nothing waited for.  The groups, the plans, ego and t_now are read
+ * on the device when the kernel runs, so a captured call replays.  obs_pose must be 16-byte aligned.  What a host call reports as an
+ * error is decided silently here: a member outside 0 .. B-1, or one without a scene, writes nothing and gets nothing.
+ * FP_MEM_HOST stages the arrays through the ctx's declared list, obs_pose and final_time_step as in/out arrays, and waits.  All checks
+ * run before any launch, each FP_EINVAL with the group, member or ego named: NULL pointers; both or neither of best_idx / end_state;
+ * n_rows <= 0; tail outside 0 .. 2; a member outside 0 .. B-1; an ego in two groups; a member with scene_of < 0; two members sharing a
+ * scene; col_base < 0 or col_base + group size > n_obs; a non-ascending group_ptr; n_members != group_ptr[G]; a best_idx >= nd*nv*nt
+ * of an ego that is not skipped (as fp_advance).  G == 0 or n_members == 0: nothing is written, FP_OK.
+ * Also read-only in fp_ctx_get_option: "from_plans_launches" = launches of the kernel on this ctx so far (0 for a caller that never
+ * asks: such a caller gets the bits and the launch counts it got before the symbol existed).
+ *
+ * Deliberately not done: fp_shard_call has no slot for it; fp_plan_step / fp_plan_fiss_step do not call it (their hand-over moves the
+ * ego inside the plan launch); no priorities or right-of-way between agents; one footprint (veh_l x veh_w) for every agent. */
+#define FP_TAIL_NONE  0   /* beyond the plan's last point the column has no pose */
+#define FP_TAIL_HOLD  1   /* ... the last pose is repeated */
+#define FP_TAIL_COAST 2   /* ... the last step is repeated: p[i] = p[M-1] + (i-M+1) * (p[M-1] - p[M-2]), yaw = yaw[M-1] */
+
+typedef struct {
+    int32_t G, n_members;        /* groups; n_members = group_ptr[G] (host-known: the grid is a function of sizes alone) */
+    const int32_t* group_ptr;    /* [G+1]        ascending, group_ptr[0] = 0 */
+    const int32_t* members;      /* [n_members]  ego indices; an ego is a member of at most one group */
+    int32_t col_base;            /* member k of a group owns column col_base + k of every scene of its group */
+    int32_t n_rows;              /* rows written per member, from row t_now[a] */
+    int32_t tail;                /* FP_TAIL_* */
+    int32_t reserved0;
+} fp_agents;
+
+int fp_obstacles_from_plans(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, const fp_agents* agents,
+                            const int32_t* best_idx, const double* end_state,   /* exactly one non-NULL, as fp_advance */
+                            double* obs_pose, int32_t* final_time_step, int mem, void* stream);
 
 /* Materialise the whole lattice: the full series of EVERY candidate of every ego, in FOP order
  *   traj [B][C][16][traj_stride] (traj_stride / traj_sparse as in fp_result), flags [B][C] (N << 8 | M << 20 | FP_FLAG_TRUNCATED; the feasibility bits
