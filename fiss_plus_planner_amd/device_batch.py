@@ -17,7 +17,9 @@ into the resident obstacle tables of the others in front of fp_advance.
 """
 from __future__ import annotations
 
+from functools import partial
 from types import SimpleNamespace
+from typing import NamedTuple
 
 import numpy as np
 
@@ -74,6 +76,18 @@ class DeviceBatch:
     def empty(self, shape, dtype):
         return self.torch.empty(shape, dtype=dtype, device=self.dev)
 
+    def addr(self, k: str) -> int:
+        """The device address of the resident array `k` (what rules.Rule.struct / rules.rule_set ask for)."""
+        return self.t[k].data_ptr()
+
+    def uploader(self, held: dict):
+        """addr(name, array) for FallbackStop.struct / AgentGroups.struct: the array goes to the device and stays alive in `held`."""
+        def addr(name, a):
+            held[name] = self.torch.from_numpy(a).to(self.dev)
+            return held[name].data_ptr()
+
+        return addr
+
     @property
     def B(self):
         return self.host.B
@@ -83,48 +97,74 @@ class DeviceBatch:
         return self.host.C
 
 
+STAGES = ("plan", "rules", "audit", "fallback", "share", "advance")  # a cycle is a subset of these, in this order, on one stream
+
+
+class CyclePlan(NamedTuple):
+    stages: tuple           # of STAGES
+    plan_call: str          # the ABI entry point of the plan stage
+    tables: bool            # fp_plan_dense fills the runner's [B][C] cost / flag tables (the rule passes read them)
+    handover_inside: bool   # the plan call hands the egos over itself: no advance stage
+    drives: str             # "best_idx" or "end_state": the plan the hand-over (and the shared plans, the log) follows
+    later_params: str       # "params" or "fb_params": the fp_params of share / advance / record (the fallback's cover its longest stop)
+    fallback_call: str | None
+
+
+def cycle_plan(planner: str, fused, rules, audit, enforce, fallback, obey, agents) -> CyclePlan:
+    """One cycle of ClosedLoopRunner, from its (validated) arguments; the stage arguments count as present / absent.  No device."""
+    between = bool(rules or audit or fallback or agents)  # something stands between the plan and the hand-over
+    inside = not between and bool(enforce or fused)
+    if planner == "FOP":
+        call = "fp_plan_step" if inside else "fp_plan_dense"
+    elif enforce:
+        call = "fp_plan_fiss_rules"  # (loop = the runner's fp_loop_io iff the hand-over is inside, else NULL)
+    else:
+        call = "fp_plan_fiss_step" if inside else "fp_plan_fiss"
+    present = dict(plan=True, rules=rules, audit=audit, fallback=fallback, share=agents, advance=not inside)
+    return CyclePlan(tuple(s for s in STAGES if present[s]), call, bool(rules), inside, "end_state" if planner != "FOP" or fallback else "best_idx",
+                     "fb_params" if fallback else "params", ("fp_fallback_stop_rules" if obey else "fp_fallback_stop") if fallback else None)
+
+
 class ClosedLoopRunner:
     """[plan -> advance] for a whole batch on the device.  planner: "FOP" (fp_plan_dense) or "FISS"/"FISS+" (fp_plan_fiss)."""
 
     def __init__(self, engine: FrenetEngine, dbatch: DeviceBatch, goal_xy: np.ndarray, planner: str = "FOP", fused: bool = True,
                  goal_poly: np.ndarray | None = None, goal_nv: np.ndarray | None = None, goal_intervals: np.ndarray | None = None,
                  rules=(), audit=(), enforce=(), fallback=None, agents=None):
-        """rules: any subset of the names in rules.TABLE - FOP only, and the batch must carry each rule's data (speed profile / gates /
-        corridor / a time gap with a lag above 0).  The cycle then is fp_plan_dense into the runner's own [B][C] tables, the passes asked
-        for in the table's order, whatever the caller's, each writing best_idx / best_cost, and fp_advance on the last one's winner;
-        `fused` has no say.  rules=(): the calls below, unchanged.
+        """The cycle is one linear chain on one stream, eager and from a graph (cycle_plan above):
+            plan -> rule passes -> audit verdict -> fallback stop -> share plans -> advance
+        with the stages the arguments below ask for.  When nothing stands between the plan and the hand-over, and `fused` or enforce= is
+        set, the plan call hands the egos over itself and there is no advance stage (fp_plan_step; fp_plan_fiss_step: FISS+ hands over
+        inside its refinement launch, FISS by the advance kernel behind the pipeline; fp_plan_fiss_rules with the loop's fp_loop_io);
+        fused=False then gives the plan call + fp_advance (same results; the A/B of tests and bench).  In every other cycle the plan call
+        is the one without a hand-over (fp_plan_dense, fp_plan_fiss, fp_plan_fiss_rules with loop = NULL) and `fused` is not looked at.
+        The hand-over follows FOP's best_idx, or end_state for FISS / FISS+ and whenever a fallback is present.
+        rules: any subset of the names in rules.TABLE - FOP only, and the batch must carry each rule's data (speed profile / gates /
+        corridor / a time gap with a lag above 0).  fp_plan_dense then fills the runner's own [B][C] tables and the passes asked for run
+        in the table's order, whatever the caller's, each writing best_idx / best_cost: the hand-over follows the last one's winner.
         audit: any subset of the names in rules.TABLE - FISS / FISS+ only (FOP enforces its rules with rules=), and the batch must carry
-        each rule's data.  The cycle then is fp_plan_fiss (asking for best_flags, which its series writer fills beside best_traj) ->
-        fp_rules_eval (K = 1 on end_state, counts = self.violations) -> fp_advance(end_state): the verdict is taken before the hand-over
-        moves ego / t_now, the plan is the one the loop drives without audit, and `fused` has no say.  self.violations [B, 5] int32 counts,
-        per ego and FP_RULE_* bit (column log2 of the bit), the cycles whose plan violated; run / run_graph return them as
-        `violations` (rule name -> [B]; the envelope's entry adds its two columns) and `violation_counts` [B, 5].  audit=(): the calls
-        below, unchanged.
+        each rule's data.  The plan call is asked for best_flags (its series writer fills them beside best_traj) and fp_rules_eval (K = 1
+        on end_state, counts = self.violations) takes the verdict before the hand-over moves ego / t_now; the plan is the one the loop
+        drives without audit.  self.violations [B, 5] int32 counts, per ego and FP_RULE_* bit (column log2 of the bit), the cycles whose
+        plan violated; run / run_graph return them as `violations` (rule name -> [B]; the envelope's entry adds its two columns) and
+        `violation_counts` [B, 5].
         enforce: any subset of the names in rules.TABLE - FISS / FISS+ only (FOP enforces with rules=), and the batch must carry each
-        rule's data.  Each cycle is one fp_plan_fiss_rules call with the loop's fp_loop_io (FISS+: the refinement's rule instance hands the
-        ego over; FISS: the advance kernel follows); with audit= as well it is fp_plan_fiss_rules (loop = NULL) -> fp_rules_eval ->
-        fp_advance.  self.rejected [B] int32 sums, per ego, the refined candidates a rule alone rejected; run / run_graph return it.
-        fallback: a FallbackStop - FOP (with or without rules=) and FISS / FISS+ (with or without enforce=).  The cycle then is the plan
-        without a fused hand-over (fp_plan_dense + the rule passes, fp_plan_fiss, or fp_plan_fiss_rules with loop = NULL) ->
-        fp_fallback_stop -> fp_advance(end_state): an ego whose plan call found nothing brakes to a stop along the lane instead of ending
-        with FP_DONE_NO_SOLUTION, and plans again in the next cycle; `fused` has no say.  self.fallback_counts [B, 4] int32 counts, per ego,
-        the cycles by fallback status (_abi.FALLBACK_*: column 0 = the ego had a plan or was finished); run / run_graph return it.  With
-        record=True the log is written from end_state for FOP too: its FP_LOG_BEST_IDX column is then -1 in every row.  fallback= with
-        audit= is not done (ValueError).  fallback=None: the calls below, unchanged.  A fallback with obey=(...) (any subset of the
-        names in rules.TABLE; the batch must carry each rule's data, whichever rules= / enforce= name) makes the middle call
-        fp_fallback_stop_rules: the clear stops are ranked by those rules - an ego in front of a closed gate stops before the line.
-        self.fallback_rule_counts [B, 5] int32 counts, per ego and FP_RULE_* bit (column log2 of the bit), the cycles whose chosen stop
-        violated the rule; run / run_graph return it.
-        agents: an AgentGroups - the members see each other's plans (fp_obstacles_from_plans).  The batch must give every member a scene of
-        its own (AgentGroups.attach).  The cycle then is the plan without a fused hand-over (fp_plan_dense, fp_plan_fiss or
-        fp_plan_fiss_rules with loop = NULL) -> the rule passes (if any) -> the fallback (if any) -> fp_obstacles_from_plans on the
-        RESIDENT table (dbatch.t["obs_pose"] / t["final_time_step"] are rewritten in place, cycle after cycle) -> fp_advance: a linear
-        chain on one stream, eager and from a graph; `fused` has no say.  The plans are FOP's best_idx, or end_state for FISS / FISS+
-        and whenever a fallback is present.  The first cycle plans against whatever the table holds.  The table is what
-        rules=("gaps",) reads, so agents keep a time gap to each other with no further code.  agents= with audit= is not done
-        (ValueError).  agents=None: the calls below, unchanged.
-        fused: an FOP cycle is ONE launch (fp_plan_step: the workgroup that finds an ego's argmin advances the ego); False = the two
-        calls fp_plan_dense + fp_advance (same results; the A/B of tests and bench).
+        rule's data.  The plan call is fp_plan_fiss_rules: the walks obey the rules.  self.rejected [B] int32 sums, per ego, the refined
+        candidates a rule alone rejected; run / run_graph return it.
+        fallback: a FallbackStop - FOP (with or without rules=) and FISS / FISS+ (with or without enforce=).  fp_fallback_stop follows the
+        plan and the rule passes: an ego whose plan call found nothing brakes to a stop along the lane instead of ending with
+        FP_DONE_NO_SOLUTION, and plans again in the next cycle.  self.fallback_counts [B, 4] int32 counts, per ego, the cycles by fallback
+        status (_abi.FALLBACK_*: column 0 = the ego had a plan or was finished); run / run_graph return it.  With record=True the log is
+        written from end_state for FOP too: its FP_LOG_BEST_IDX column is then -1 in every row.  fallback= with audit= is not done
+        (ValueError).  A fallback with obey=(...) (any subset of the names in rules.TABLE; the batch must carry each rule's data,
+        whichever rules= / enforce= name) makes the call fp_fallback_stop_rules: the clear stops are ranked by those rules - an ego in
+        front of a closed gate stops before the line.  self.fallback_rule_counts [B, 5] int32 counts, per ego and FP_RULE_* bit (column
+        log2 of the bit), the cycles whose chosen stop violated the rule; run / run_graph return it.
+        agents: an AgentGroups - the members see each other's plans.  The batch must give every member a scene of its own
+        (AgentGroups.attach).  fp_obstacles_from_plans writes the plans the hand-over is about to follow into the RESIDENT table
+        (dbatch.t["obs_pose"] / t["final_time_step"] are rewritten in place, cycle after cycle).  The first cycle plans against whatever
+        the table holds.  The table is what rules=("gaps",) reads, so agents keep a time gap to each other with no further code.
+        agents= with audit= is not done (ValueError).
         goal_poly [B, V, 2] + goal_nv [B] (+ goal_intervals [B, 6] = time_step / velocity / orientation lo, hi; NaN = undefined): the
         goal region of goal_region.is_reached() (planning.py:150-153), see fp_loop_io in include/frenet_gpu.h."""
         self.rules = self._check_rules(rules, planner, dbatch.host)  # (first: the argument errors need no device)
@@ -138,15 +178,16 @@ class ClosedLoopRunner:
             agents.check(dbatch.host)
         self.fallback, self.agents = fallback, agents
         self.obey = fallback.rules_for(dbatch.host, "ClosedLoopRunner(fallback=FallbackStop") if fallback is not None and getattr(fallback, "obey", ()) else ()
+        self.plan = cycle_plan(planner, fused, self.rules, self.audit, self.enforce, fallback is not None, self.obey, agents is not None)
         torch = dbatch.torch
         self.eng, self.db, self.planner, self.fused = engine, dbatch, planner, fused
         B = dbatch.B
         i32, f64 = torch.int32, torch.float64
+        zeros = lambda shape: torch.zeros(shape, dtype=i32, device=dbatch.dev)  # noqa: E731
         self.best_idx = dbatch.empty(B, i32)
         self.best_cost = dbatch.empty(B, f64)
         self.stats = dbatch.empty((B, 4), i32)
-        self.done = torch.zeros(B, dtype=i32, device=dbatch.dev)
-        self.cycles = torch.zeros(B, dtype=i32, device=dbatch.dev)
+        self.done, self.cycles = zeros(B), zeros(B)
         self.goal = torch.from_numpy(np.ascontiguousarray(goal_xy, dtype=np.float64).reshape(B, 2)).to(dbatch.dev)
         self.cart = torch.full((B, 3), float("nan"), dtype=f64, device=dbatch.dev)
         # the runner's OWN view of the resident batch (the shared DeviceBatch keeps its skip mask and its launch-order hint for other callers)
@@ -154,7 +195,7 @@ class ClosedLoopRunner:
         self.fb.skip = self.done.data_ptr()  # finished egos are not planned any more
         self.fb.launch_order = None  # (the egos' states move on: the order the ctx learns from its own launches follows them, the upload's hint would not)
         self.io = _abi.FpLoopIo()
-        self.io.ego, self.io.t_now = dbatch.t["ego"].data_ptr(), dbatch.t["t_now"].data_ptr()
+        self.io.ego, self.io.t_now = dbatch.addr("ego"), dbatch.addr("t_now")
         self.io.done, self.io.cycles = self.done.data_ptr(), self.cycles.data_ptr()
         self.io.goal_xy, self.io.cart_state = self.goal.data_ptr(), self.cart.data_ptr()
         if goal_poly is not None:
@@ -167,10 +208,9 @@ class ClosedLoopRunner:
                 self.io.goal_intervals = self.goal_iv.data_ptr()
         if self.rules:  # the tables the passes mask, and how many candidates each pass flagged in the last cycle
             self.cost_tbl = dbatch.empty((B, dbatch.C), f64)
-            self.flag_tbl = torch.zeros((B, dbatch.C), dtype=i32, device=dbatch.dev)
-            self.n_flagged = {r: torch.zeros(B, dtype=i32, device=dbatch.dev) for r in self.rules}
-            addr = lambda k: dbatch.t[k].data_ptr()  # noqa: E731  (the addresses are fixed: every pass' struct is built once)
-            self.passes = [(p, p.struct(dbatch.host, addr), self.n_flagged[p.name].data_ptr()) for p in map(_rules.by_name.get, self.rules)]
+            self.flag_tbl = zeros((B, dbatch.C))
+            self.n_flagged = {r: zeros(B) for r in self.rules}
+            self.passes = [(p, p.struct(dbatch.host, dbatch.addr), self.n_flagged[p.name].data_ptr()) for p in map(_rules.by_name.get, self.rules)]
         if planner != "FOP":
             self.prev = torch.full((B, 3), -1, dtype=i32, device=dbatch.dev)
             self.ijk = dbatch.empty((B, 3), i32)
@@ -178,55 +218,49 @@ class ClosedLoopRunner:
             self.refined = dbatch.empty(B, i32)
             self.fopts = _abi.FpFissOpts(_abi.FP_FISS_PLUS if planner == "FISS+" else _abi.FP_FISS, 3 if planner == "FISS+" else 0, 10.0, 0.5)
             f = _abi.FpFissIo()
-            f.samp_min, f.samp_max, f.samp_res = (dbatch.t[k].data_ptr() for k in ("samp_min", "samp_max", "samp_res"))
+            f.samp_min, f.samp_max, f.samp_res = (dbatch.addr(k) for k in ("samp_min", "samp_max", "samp_res"))
             f.prev_best_idx, f.best_ijk, f.best_cost, f.end_state = self.prev.data_ptr(), self.ijk.data_ptr(), self.best_cost.data_ptr(), self.end_state.data_ptr()
             f.refined, f.stats, f.trace, f.best_flags, f.best_traj = self.refined.data_ptr(), self.stats.data_ptr(), None, None, None
             self.fio = f
         if self.audit:  # the plan's flag word (fp_plan_fiss writes best_flags with the series), the rule set on device addresses, the counts
             stride = max(_abi.FP_DEFAULT_STRIDE, int(dbatch.params.points_max))
-            self.best_flags = torch.zeros(B, dtype=i32, device=dbatch.dev)
+            self.best_flags = zeros(B)
             self.best_traj = dbatch.empty((B, 16, stride), f64)
             self.fio.best_flags, self.fio.best_traj = self.best_flags.data_ptr(), self.best_traj.data_ptr()
             self.fio.traj_stride, self.fio.traj_sparse = stride, 1
-            self.violations = torch.zeros((B, _abi.FP_RULE_COUNT), dtype=i32, device=dbatch.dev)
-            self.rule_set, self._rule_structs = _rules.rule_set(dbatch.host, lambda k: dbatch.t[k].data_ptr(), self.audit)
+            self.violations = zeros((B, _abi.FP_RULE_COUNT))
+            self.rule_set, self._rule_structs = _rules.rule_set(dbatch.host, dbatch.addr, self.audit)
+        self._uploads = {}  # the fallback's and the agents' own arrays on the device
         if fallback is not None:  # the family on device addresses, the call's outputs, and the per-ego counts by status
             if planner == "FOP":
                 self.end_state = torch.full((B, 3), float("nan"), dtype=f64, device=dbatch.dev)
-            self._fb_arrays = {}
-
-            def fb_addr(name, a):
-                self._fb_arrays[name] = torch.from_numpy(a).to(dbatch.dev)
-                return self._fb_arrays[name].data_ptr()
-
-            self.fb_struct = fallback.struct(dbatch.host, fb_addr)
-            self.fb_status, self.fb_idx, self.fb_hit_step, self.fb_hit_obs = (torch.zeros(B, dtype=i32, device=dbatch.dev) for _ in range(4))
+            self.fb_struct = fallback.struct(dbatch.host, dbatch.uploader(self._uploads))
+            self.fb_status, self.fb_idx, self.fb_hit_step, self.fb_hit_obs = (zeros(B) for _ in range(4))
             self.fb_hit_speed = torch.full((B,), float("nan"), dtype=f64, device=dbatch.dev)
-            self.fallback_counts = torch.zeros((B, 4), dtype=i32, device=dbatch.dev)
+            self.fallback_counts = zeros((B, 4))
             if self.obey:  # the obeyed set on device addresses (DeviceBatch has uploaded the arrays of every rule the batch carries), the verdicts, the counts
-                self.fb_rule_bits = torch.zeros(B, dtype=i32, device=dbatch.dev)
-                self.fallback_rule_counts = torch.zeros((B, _abi.FP_RULE_COUNT), dtype=i32, device=dbatch.dev)
-                self.obey_set, self._obey_structs = _rules.rule_set(dbatch.host, lambda k: dbatch.t[k].data_ptr(), self.obey)
+                self.fb_rule_bits = zeros(B)
+                self.fallback_rule_counts = zeros((B, _abi.FP_RULE_COUNT))
+                self.obey_set, self._obey_structs = _rules.rule_set(dbatch.host, dbatch.addr, self.obey)
             # (the fallback's own calls are sized for its longest stop time; the plan calls keep the batch's params)
             self.fb_params = _abi.FpParams.from_buffer_copy(dbatch.params)
             pts = max(fallback.points_max(dbatch.host.tick_t), int(dbatch.params.points_max))
             self.fb_params.points_max = min(pts, _abi.FP_MAX_POINTS) if pts > _abi.FP_FAST_POINTS else 0
         if agents is not None:  # the groups on device addresses
-            self._ag_arrays = {}
-
-            def ag_addr(name, a):
-                self._ag_arrays[name] = torch.from_numpy(a).to(dbatch.dev)
-                return self._ag_arrays[name].data_ptr()
-
-            self.ag_struct = agents.struct(dbatch.host, ag_addr)
+            self.ag_struct = agents.struct(dbatch.host, dbatch.uploader(self._uploads))
         if self.enforce:  # the enforced set on device addresses, and the per-ego count of rule-rejected refined candidates
-            self.rejected = torch.zeros(B, dtype=i32, device=dbatch.dev)
-            self.enforce_set, self._enforce_structs = _rules.rule_set(dbatch.host, lambda k: dbatch.t[k].data_ptr(), self.enforce)
+            self.rejected = zeros(B)
+            self.enforce_set, self._enforce_structs = _rules.rule_set(dbatch.host, dbatch.addr, self.enforce)
+        self.chain = self._chain()
 
     @staticmethod
-    def _check_rules(rules, planner, batch) -> tuple:
+    def _names(asked) -> tuple:
+        return (asked,) if isinstance(asked, str) else tuple(asked)
+
+    @classmethod
+    def _check_rules(cls, rules, planner, batch) -> tuple:
         """The rules in the order they run; ValueError for an unknown rule, a planner that is not FOP, or a rule without its data."""
-        asked = (rules,) if isinstance(rules, str) else tuple(rules)
+        asked = cls._names(rules)
         for r in asked:
             if r not in _rules.by_name:
                 raise ValueError(f"ClosedLoopRunner: unknown rule {r!r} (rules are a subset of {tuple(_rules.by_name)})")
@@ -237,118 +271,75 @@ class ClosedLoopRunner:
                 raise _rules.missing(_rules.by_name[r], f"ClosedLoopRunner(rules={r!r})")
         return tuple(r for r in _rules.by_name if r in asked)
 
-    @staticmethod
-    def _check_enforce(enforce, planner, batch, rules) -> tuple:
+    @classmethod
+    def _check_enforce(cls, enforce, planner, batch, rules) -> tuple:
         """The enforced rules in the order they run; ValueError for an unknown rule, the FOP planner, rules= beside it, or a rule without
         its data."""
-        asked = (enforce,) if isinstance(enforce, str) else tuple(enforce)
+        asked = cls._names(enforce)
         if asked and rules:
             raise ValueError("ClosedLoopRunner: enforce= (FISS / FISS+) and rules= (FOP) do not combine")
         if asked and planner == "FOP":
             raise ValueError("ClosedLoopRunner: enforce is for the FISS / FISS+ planners (FOP enforces its rules with rules=...)")
         return _rules.check_names(asked, batch, "ClosedLoopRunner(enforce=...)")
 
-    @staticmethod
-    def _check_audit(audit, planner, batch) -> tuple:
+    @classmethod
+    def _check_audit(cls, audit, planner, batch) -> tuple:
         """The audited rules in the order they run; ValueError for an unknown rule, the FOP planner, or a rule without its data."""
-        asked = (audit,) if isinstance(audit, str) else tuple(audit)
+        asked = cls._names(audit)
         names = _rules.check_names(asked, batch, "ClosedLoopRunner(audit=...)")
         if asked and planner == "FOP":
             raise ValueError("ClosedLoopRunner: audit is for the FISS / FISS+ planners (FOP enforces its rules with rules=...)")
         return names
 
-    def _step_audit(self, stream: int):
-        """fp_plan_fiss -> fp_rules_eval (K = 1) -> fp_advance: a linear chain on `stream`."""
-        import ctypes as C
-
-        db, eng = self.db, self.eng
-        if self.enforce:
-            eng.plan_fiss_rules_device(db.params, self.fb, self.fopts, self.fio, self.enforce_set, None, self.rejected.data_ptr(), stream)
-        else:
-            eng.plan_fiss_device(db.params, self.fb, self.fopts, self.fio, stream=stream)
-        eng.rules_eval_device(db.params, self.fb, self.rule_set, 1, self.end_state.data_ptr(), self.best_flags.data_ptr(), 0, self.violations.data_ptr(), stream)
-        _abi.check(eng._lib.fp_advance(eng._ctx, C.byref(db.params), C.byref(self.fb), None, self.end_state.data_ptr(), C.byref(self.io),
-                                       _abi.FP_MEM_DEVICE, stream or None))
-
-    def _step_rules(self, stream: int):
-        """fp_plan_dense -> the rule passes -> fp_advance: a linear chain on `stream`."""
-        import ctypes as C
-
-        db, eng = self.db, self.eng
-        bi, bc, cost, flags = self.best_idx.data_ptr(), self.best_cost.data_ptr(), self.cost_tbl.data_ptr(), self.flag_tbl.data_ptr()
-        eng.plan_dense_device(db.params, self.fb, bi, bc, self.stats.data_ptr(), cost_tbl=cost, flag_tbl=flags, stream=stream)
-        for rule, struct, n in self.passes:
-            eng._table_pass_device(rule, db.params, self.fb, struct, cost, flags, bi, bc, n, stream)
-        _abi.check(eng._lib.fp_advance(eng._ctx, C.byref(db.params), C.byref(self.fb), bi, None, C.byref(self.io), _abi.FP_MEM_DEVICE, stream or None))
-
-    def _step_fallback(self, stream: int):
-        """plan (no fused hand-over) -> fp_fallback_stop (with obey: fp_fallback_stop_rules) -> fp_advance(end_state): a linear chain on `stream`.
-        With agents: fp_obstacles_from_plans in front of fp_advance; without a fallback the middle call is left out and the hand-over takes
-        the planner's own best_idx (FOP) or end_state."""
-        import ctypes as C
-
-        db, eng = self.db, self.eng
-        bi = 0
-        if self.planner == "FOP":
-            bi, bc = self.best_idx.data_ptr(), self.best_cost.data_ptr()
-            if self.rules:
+    def _chain(self) -> list:
+        """The calls of one cycle, stage by stage as self.plan lists them: callables of `stream=`.  Every address is fixed from here on
+        (state lives in HBM and is updated in place), so the arguments are bound once - to the engine's methods, not to the runner:
+        a dropped runner is freed at once, without waiting for the cycle collector."""
+        eng, db, fb, plan = self.eng, self.db, self.fb, self.plan
+        bi, bc, stats = self.best_idx.data_ptr(), self.best_cost.data_ptr(), self.stats.data_ptr()
+        # what the hand-over follows, for share / advance / record: (params, best_idx, end_state), one of the two addresses 0
+        self.driven = (self.fb_params if plan.later_params == "fb_params" else db.params,
+                       bi if plan.drives == "best_idx" else 0, self.end_state.data_ptr() if plan.drives == "end_state" else 0)
+        chain = []
+        for stage in plan.stages:
+            if stage == "plan":
+                loop = self.io if plan.handover_inside else None
+                if plan.plan_call == "fp_plan_step":
+                    chain.append(partial(eng.plan_step_device, db.params, fb, loop, bi, bc, stats))
+                elif plan.plan_call == "fp_plan_dense":
+                    tables = dict(cost_tbl=self.cost_tbl.data_ptr(), flag_tbl=self.flag_tbl.data_ptr()) if plan.tables else {}
+                    chain.append(partial(eng.plan_dense_device, db.params, fb, bi, bc, stats, **tables))
+                elif plan.plan_call == "fp_plan_fiss_rules":  # (with `loop`: the rules' passes, the walks and the hand-over in one call)
+                    chain.append(partial(eng.plan_fiss_rules_device, db.params, fb, self.fopts, self.fio, self.enforce_set, loop, self.rejected.data_ptr()))
+                elif plan.plan_call == "fp_plan_fiss_step":
+                    chain.append(partial(eng.plan_fiss_step_device, db.params, fb, self.fopts, self.fio, loop))
+                else:
+                    chain.append(partial(eng.plan_fiss_device, db.params, fb, self.fopts, self.fio))
+            elif stage == "rules":
                 cost, flags = self.cost_tbl.data_ptr(), self.flag_tbl.data_ptr()
-                eng.plan_dense_device(db.params, self.fb, bi, bc, self.stats.data_ptr(), cost_tbl=cost, flag_tbl=flags, stream=stream)
-                for rule, struct, n in self.passes:
-                    eng._table_pass_device(rule, db.params, self.fb, struct, cost, flags, bi, bc, n, stream)
+                chain += [partial(eng._table_pass_device, rule, db.params, fb, struct, cost, flags, bi, bc, n) for rule, struct, n in self.passes]
+            elif stage == "audit":  # (taken before the hand-over moves ego / t_now)
+                chain.append(partial(eng.rules_eval_device, db.params, fb, self.rule_set, 1, self.end_state.data_ptr(), self.best_flags.data_ptr(), 0,
+                                     self.violations.data_ptr()))
+            elif stage == "fallback":
+                out = [getattr(self, k).data_ptr() for k in ("end_state", "fb_status", "fb_idx", "fb_hit_step", "fb_hit_obs", "fb_hit_speed")]
+                kw = dict(best_idx=bi if self.planner == "FOP" else 0, counts=self.fallback_counts.data_ptr())
+                if plan.fallback_call == "fp_fallback_stop_rules":
+                    chain.append(partial(eng.fallback_stop_rules_device, self.fb_params, fb, self.fb_struct, self.obey_set, *out, self.fb_rule_bits.data_ptr(),
+                                         rule_counts=self.fallback_rule_counts.data_ptr(), **kw))
+                else:
+                    chain.append(partial(eng.fallback_stop_device, self.fb_params, fb, self.fb_struct, *out, **kw))
+            elif stage == "share":
+                params, plan_bi, plan_es = self.driven
+                chain.append(partial(eng.share_plans_device, params, fb, self.ag_struct, plan_bi, plan_es, db.addr("obs_pose"), db.addr("final_time_step")))
             else:
-                eng.plan_dense_device(db.params, self.fb, bi, bc, self.stats.data_ptr(), stream=stream)
-        elif self.enforce:
-            eng.plan_fiss_rules_device(db.params, self.fb, self.fopts, self.fio, self.enforce_set, None, self.rejected.data_ptr(), stream)
-        else:
-            eng.plan_fiss_device(db.params, self.fb, self.fopts, self.fio, stream=stream)
-        if self.fallback is None:  # (agents alone)
-            es = 0 if self.planner == "FOP" else self.end_state.data_ptr()
-            eng.share_plans_device(db.params, self.fb, self.ag_struct, 0 if es else bi, es, db.t["obs_pose"].data_ptr(), db.t["final_time_step"].data_ptr(), stream)
-            _abi.check(eng._lib.fp_advance(eng._ctx, C.byref(db.params), C.byref(self.fb), None if es else bi, es or None, C.byref(self.io),
-                                           _abi.FP_MEM_DEVICE, stream or None))
-            return
-        if self.obey:
-            eng.fallback_stop_rules_device(self.fb_params, self.fb, self.fb_struct, self.obey_set, self.end_state.data_ptr(), self.fb_status.data_ptr(),
-                                           self.fb_idx.data_ptr(), self.fb_hit_step.data_ptr(), self.fb_hit_obs.data_ptr(), self.fb_hit_speed.data_ptr(),
-                                           self.fb_rule_bits.data_ptr(), best_idx=bi, counts=self.fallback_counts.data_ptr(),
-                                           rule_counts=self.fallback_rule_counts.data_ptr(), stream=stream)
-        else:
-            eng.fallback_stop_device(self.fb_params, self.fb, self.fb_struct, self.end_state.data_ptr(), self.fb_status.data_ptr(), self.fb_idx.data_ptr(),
-                                     self.fb_hit_step.data_ptr(), self.fb_hit_obs.data_ptr(), self.fb_hit_speed.data_ptr(), best_idx=bi,
-                                     counts=self.fallback_counts.data_ptr(), stream=stream)
-        if self.agents is not None:
-            eng.share_plans_device(self.fb_params, self.fb, self.ag_struct, 0, self.end_state.data_ptr(), db.t["obs_pose"].data_ptr(),
-                                   db.t["final_time_step"].data_ptr(), stream)
-        _abi.check(eng._lib.fp_advance(eng._ctx, C.byref(self.fb_params), C.byref(self.fb), None, self.end_state.data_ptr(), C.byref(self.io),
-                                       _abi.FP_MEM_DEVICE, stream or None))
+                chain.append(partial(eng.advance_device, self.driven[0], fb, self.io, *self.driven[1:]))
+        return chain
 
     def step(self, stream: int = 0):
         """One plan cycle for every running ego + the state hand-over, enqueued on `stream`."""
-        import ctypes as C
-
-        if self.fallback is not None or self.agents is not None:
-            return self._step_fallback(stream)
-        if self.rules:
-            return self._step_rules(stream)
-        if self.audit:
-            return self._step_audit(stream)
-        if self.enforce:  # one call: the rules' passes, the walks, the hand-over
-            return self.eng.plan_fiss_rules_device(self.db.params, self.fb, self.fopts, self.fio, self.enforce_set, self.io, self.rejected.data_ptr(), stream)
-        lib, ctx = self.eng._lib, self.eng._ctx
-        if self.planner == "FOP" and self.fused:
-            self.eng.plan_step_device(self.db.params, self.fb, self.io, self.best_idx.data_ptr(), self.best_cost.data_ptr(), self.stats.data_ptr(), stream=stream)
-        elif self.planner == "FOP":
-            self.eng.plan_dense_device(self.db.params, self.fb, self.best_idx.data_ptr(), self.best_cost.data_ptr(), self.stats.data_ptr(), stream=stream)
-            _abi.check(lib.fp_advance(ctx, C.byref(self.db.params), C.byref(self.fb), self.best_idx.data_ptr(), None, C.byref(self.io),
-                                      _abi.FP_MEM_DEVICE, stream or None))
-        elif self.fused:  # fp_plan_fiss_step: FISS+ hands the egos over inside its refinement launch, FISS by the advance kernel behind the pipeline
-            _abi.check(lib.fp_plan_fiss_step(ctx, C.byref(self.db.params), C.byref(self.fb), C.byref(self.fopts), C.byref(self.fio), C.byref(self.io),
-                                             _abi.FP_MEM_DEVICE, stream or None))
-        else:
-            self.eng.plan_fiss_device(self.db.params, self.fb, self.fopts, self.fio, stream=stream)
-            _abi.check(lib.fp_advance(ctx, C.byref(self.db.params), C.byref(self.fb), None, self.end_state.data_ptr(), C.byref(self.io),
-                                      _abi.FP_MEM_DEVICE, stream or None))
+        for call in self.chain:
+            call(stream=stream)
 
     def log_reset(self, max_rows: int, poll: bool = True):
         """A fresh device log for the cycles that follow (fp_loop_log): max_rows rows per ego beyond the cycles driven so far, egos that are
@@ -372,12 +363,8 @@ class ClosedLoopRunner:
 
     def record(self, stream: int = 0):
         """fp_loop_record behind the step just enqueued on `stream`: every running ego's new state goes to its next log row."""
-        import ctypes as C
-
-        fop = self.planner == "FOP" and self.fallback is None  # (with a fallback the driven plan is end_state for every planner)
-        _abi.check(self.eng._lib.fp_loop_record(self.eng._ctx, C.byref(self.db.params if self.fallback is None else self.fb_params), C.byref(self.fb), C.byref(self.io),
-                                                self.best_idx.data_ptr() if fop else None, None if fop else self.end_state.data_ptr(),
-                                                self.best_cost.data_ptr(), self.stats.data_ptr(), C.byref(self.flog), _abi.FP_MEM_DEVICE, stream or None))
+        params, bi, es = self.driven  # (with a fallback the driven plan is end_state for every planner)
+        self.eng.loop_record_device(params, self.fb, self.io, bi, es, self.best_cost.data_ptr(), self.stats.data_ptr(), self.flog, stream)
 
     def log_fetch(self) -> LoopLog:
         """The log as numpy arrays (one read-back; synchronises)."""

@@ -972,6 +972,25 @@ class FrenetEngine:
         _abi.check(self._lib.fp_plan_fiss_rules(self._ctx, C.byref(params), C.byref(fb), C.byref(opts), C.byref(io), C.byref(rule_set),
                                                 None if loop is None else C.byref(loop), rejected or None, _abi.FP_MEM_DEVICE, stream or None))
 
+    def plan_fiss_step_device(self, params: _abi.FpParams, fb: _abi.FpBatch, opts: _abi.FpFissOpts, io: _abi.FpFissIo, loop: _abi.FpLoopIo, stream: int = 0):
+        """One cycle of the simulation loop with FISS / FISS+ planning it (fp_plan_fiss_step): plan_fiss_device and the hand-over - FISS+
+        hands the egos over inside its refinement launch, FISS by the advance kernel behind the pipeline.  Device addresses throughout."""
+        _abi.check(self._lib.fp_plan_fiss_step(self._ctx, C.byref(params), C.byref(fb), C.byref(opts), C.byref(io), C.byref(loop), _abi.FP_MEM_DEVICE,
+                                               stream or None))
+
+    def advance_device(self, params: _abi.FpParams, fb: _abi.FpBatch, loop: _abi.FpLoopIo, best_idx: int = 0, end_state: int = 0, stream: int = 0):
+        """Enqueue the hand-over alone behind a plan call (fp_advance; device addresses): every running ego moves on along its plan -
+        best_idx [B] (a lattice candidate) or end_state [B][3], exactly one, the other 0.  One launch, nothing waited for."""
+        _abi.check(self._lib.fp_advance(self._ctx, C.byref(params), C.byref(fb), best_idx or None, end_state or None, C.byref(loop), _abi.FP_MEM_DEVICE,
+                                        stream or None))
+
+    def loop_record_device(self, params: _abi.FpParams, fb: _abi.FpBatch, loop: _abi.FpLoopIo, best_idx: int, end_state: int, best_cost: int, stats: int,
+                           log: _abi.FpLoopLog, stream: int = 0):
+        """Enqueue the record kernel behind a cycle's hand-over (fp_loop_record; device addresses in loop / log): every running ego's new
+        state goes to its next log row.  best_idx [B] or end_state [B][3]: the plan the hand-over drove, the other 0."""
+        _abi.check(self._lib.fp_loop_record(self._ctx, C.byref(params), C.byref(fb), C.byref(loop), best_idx or None, end_state or None, best_cost or None,
+                                            stats or None, C.byref(log), _abi.FP_MEM_DEVICE, stream or None))
+
     def eval_trajs_device(self, params: _abi.FpParams, fb: _abi.FpBatch, K: int, end_states: int, cost: int, flags: int,
                           traj: int = 0, stream: int = 0, traj_stride: int = TRAJ_STRIDE, traj_sparse: bool = False):
         _abi.check(self._lib.fp_eval_trajs(self._ctx, C.byref(params), C.byref(fb), K, end_states, cost or None, flags or None,

@@ -327,7 +327,7 @@ def test_step_with_loop_equals_plan_then_advance(engine, planner):
     for _ in range(3):
         a.step(stream)
         engine.plan_fiss_rules_device(b.db.params, b.fb, b.fopts, b.fio, b.enforce_set, None, b.rejected.data_ptr(), stream)
-        _abi.check(engine._lib.fp_advance(engine._ctx, C.byref(b.db.params), C.byref(b.fb), None, b.end_state.data_ptr(), C.byref(b.io), _abi.FP_MEM_DEVICE, None))
+        engine.advance_device(b.db.params, b.fb, b.io, end_state=b.end_state.data_ptr())
     torch.cuda.synchronize(a.db.dev)
     for x, y in ((a.db.t["ego"], b.db.t["ego"]), (a.db.t["t_now"], b.db.t["t_now"]), (a.done, b.done), (a.cycles, b.cycles), (a.cart, b.cart),
                  (a.end_state, b.end_state), (a.stats, b.stats), (a.best_cost, b.best_cost), (a.rejected, b.rejected), (a.prev, b.prev)):

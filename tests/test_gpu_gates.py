@@ -3,7 +3,6 @@ flag words exact on every candidate the reference decides by more than 1e-9, bit
 untouched, the argmin and the violation count exact, through both memory spaces, with a launch order and a skipped ego; idempotence,
 the ranking and the two other rule passes on its outputs, the waiver, graph capture, a ctx that never asks, the planner class, the error
 codes - and the rule passes in the device-resident closed loop (ClosedLoopRunner(rules=...)) against the reference's loop."""
-import ctypes as C
 import dataclasses
 
 import numpy as np
@@ -258,7 +257,7 @@ def test_closed_loop_with_every_rule_equals_the_calls_made_one_by_one(engine, or
                                 cost.data_ptr(), flags.data_ptr(), bi.data_ptr(), bc.data_ptr())
         engine.boundary_mask_device(db.params, fb, db.t["bound_left"].data_ptr(), db.t["bound_right"].data_ptr(), batch.bound_margin, cost.data_ptr(), flags.data_ptr(),
                                     bi.data_ptr(), bc.data_ptr())
-        _abi.check(engine._lib.fp_advance(engine._ctx, C.byref(db.params), C.byref(fb), bi.data_ptr(), None, C.byref(io), _abi.FP_MEM_DEVICE, None))
+        engine.advance_device(db.params, fb, io, best_idx=bi.data_ptr())
         picked.append(bi.cpu().numpy().copy())
     torch.cuda.synchronize(dev)
     for got in (out, graphed):

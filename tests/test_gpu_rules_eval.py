@@ -300,7 +300,7 @@ def test_closed_loop_audit(engine):
         now = dataclasses.replace(batch, ego=db.t["ego"].cpu().numpy(), t_now=db.t["t_now"].cpu().numpy())
         v = engine.rules_eval(now, r.end_state.cpu().numpy()[:, None, :], rules=("gates",), skip=r.done.cpu().numpy())
         count += (v.rule_bits[:, 0] & R.RULE_GATE) != 0
-        _abi.check(engine._lib.fp_advance(engine._ctx, C.byref(db.params), C.byref(r.fb), None, r.end_state.data_ptr(), C.byref(r.io), _abi.FP_MEM_DEVICE, stream or None))
+        engine.advance_device(db.params, r.fb, r.io, end_state=r.end_state.data_ptr(), stream=stream)
     torch.cuda.synchronize(db.dev)
     assert same_bits(db.t["ego"].cpu().numpy(), base.ego)
     assert np.array_equal(eager.violations["gates"], count) and count.any()  # (the gate is closed when the first cycles' plans arrive)
