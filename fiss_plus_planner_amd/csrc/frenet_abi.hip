@@ -4,6 +4,12 @@
 // strings.  No planning arithmetic happens on the host: if there is no usable GPU every entry point fails with
 // FP_ENODEV / FP_EHIP.
 //
+// One body per entry point, whatever the memory space (CallStage below): the argument checks; under `if (call.host())` the checks that
+// look into the arrays and the points_max a host call derives itself; the arrays, declared once in the call's StageList
+// (frenet_stage_plan.h) - an FP_MEM_DEVICE call's list hands the caller's addresses through, an FP_MEM_HOST call's stages them -;
+// commit; one launch on call.stream(); one counter; `return call.finish()`.  What else differs between the spaces stands at one place
+// each: launch_order_of (the caller's launch order: device calls only), stage_batch's DeviceView, a device call's alignment checks.
+//
 // FP_MEM_HOST staging (latency matters for the B = 1 drop-in planners): small arrays are packed into ONE pinned host
 // block that mirrors the head of the device arena, so a call costs one H2D copy, the kernels, one D2H copy - instead of
 // one transfer per array.  Arrays above kSmallMax bytes are copied directly (no extra host pass over big batches).
@@ -242,27 +248,36 @@ __global__ __launch_bounds__(256) void stage_copy_kernel(uint4* __restrict__ dst
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += gridDim.x * blockDim.x) dst[i] = src[i];
 }
 
-// One FP_MEM_HOST call: the entry point declares its arrays in a StageList (frenet_stage_plan.h), commit() places them, sizes the
-// arena from them and brings the inputs over, the kernels are launched, fetch_out() brings the outputs back.
-class HostStage {
+// One call of an entry point, in either memory space.  The entry point declares its arrays once, in list() (frenet_stage_plan.h);
+// commit() makes the declarations good, the kernels are launched on stream(), finish() ends the call.
+// FP_MEM_HOST: the list stages - commit() places the arrays, sizes the arena from them and brings the inputs over on the ctx's stream,
+// finish() brings the outputs back and waits for them.  FP_MEM_DEVICE: the list passes the caller's addresses through, the stream is the
+// caller's, commit() and finish() have nothing to do: no arena, no pinned block, no copy, no synchronisation.
+// What differs between the two spaces beyond that - checks that look into the arrays, points_max, the launch order - an entry point
+// says under host().
+class CallStage {
   public:
-    explicit HostStage(fp_ctx* ctx) : ctx_(ctx) {}
+    CallStage(fp_ctx* ctx, int mem, void* stream) : ctx_(ctx), host_(mem != FP_MEM_DEVICE), stream_(host_ ? ctx->stream : (hipStream_t)stream), list_(!host_) {}
+
+    bool host() const { return host_; }
+    hipStream_t stream() const { return stream_; }
+    StageList& list() { return list_; }
 
     // The stream sees: the large inputs, one copy each in declaration order; then the window's flush.  Inputs the kernels address in the
-    // pinned block itself need neither.  `list` has to outlive fetch_out().  The default regime is the throughput one: no zero copy.
-    int commit(const StageList& list, const StageRegime& rg = StageRegime())
+    // pinned block itself need neither.  The default regime is the throughput one: no zero copy.
+    int commit(const StageRegime& rg = StageRegime())
     {
-        if (list.overflow()) return fail(FP_EHIP, "internal: a call staged %d arrays, the staging list holds %d", list.n, fp::kStageCap);
-        list_ = &list;
-        plan_ = fp::plan_stage(list, rg);
+        if (!host_) return FP_OK;
+        if (list_.overflow()) return fail(FP_EHIP, "internal: a call staged %d arrays, the staging list holds %d", list_.n, fp::kStageCap);
+        plan_ = fp::plan_stage(list_, rg);
         zero_copy_out_ = rg.zero_copy_out;
-        if (!fp::stage_plan_inside(list, plan_)) return fail(FP_EHIP, "internal: the staging plan places an array outside the arena it sized");
+        if (!fp::stage_plan_inside(list_, plan_)) return fail(FP_EHIP, "internal: the staging plan places an array outside the arena it sized");
         FP_TRY(ctx_->arena.reserve(plan_.arena_bytes));
-        for (int i = 0; i < list.n; ++i) {
-            const fp::StageItem& it = list.item[i];
+        for (int i = 0; i < list_.n; ++i) {
+            const fp::StageItem& it = list_.item[i];
             *it.dev = addr(i);
             if ((it.kind != fp::StageKind::IN && it.kind != fp::StageKind::IN_MUT) || it.bytes == 0) continue;
-            if (plan_.region[i] == fp::StageRegion::LARGE) HIP_TRY(hipMemcpyAsync(*it.dev, it.host, it.bytes, hipMemcpyHostToDevice, ctx_->stream));
+            if (plan_.region[i] == fp::StageRegion::LARGE) HIP_TRY(hipMemcpyAsync(*it.dev, it.host, it.bytes, hipMemcpyHostToDevice, stream_));
             else memcpy(ctx_->pinned + plan_.offset[i], it.host, it.bytes);
         }
         if (plan_.flush) {  // the arena's copy of the window has to be brought up to date
@@ -270,26 +285,27 @@ class HostStage {
             if (zero_copy_out_ && ctx_->stage_kernel) {
                 const int n16 = (int)((plan_.small_in + 15) / 16);  // (both blocks are 256-byte aligned and kSmallRegion long)
                 const int blocks = (n16 + 255) / 256;
-                hipLaunchKernelGGL(stage_copy_kernel, dim3(blocks < 512 ? blocks : 512), dim3(256), 0, ctx_->stream, (uint4*)ctx_->arena.base, (const uint4*)ctx_->pinned, n16);
+                hipLaunchKernelGGL(stage_copy_kernel, dim3(blocks < 512 ? blocks : 512), dim3(256), 0, stream_, (uint4*)ctx_->arena.base, (const uint4*)ctx_->pinned, n16);
                 HIP_TRY(hipGetLastError());
             } else {
-                HIP_TRY(hipMemcpyAsync(ctx_->arena.base, ctx_->pinned, plan_.small_in, hipMemcpyHostToDevice, ctx_->stream));
+                HIP_TRY(hipMemcpyAsync(ctx_->arena.base, ctx_->pinned, plan_.small_in, hipMemcpyHostToDevice, stream_));
             }
         }
         return FP_OK;
     }
     // One D2H copy for the output window (none when the kernels wrote the pinned block itself), one per output outside it, the
     // stream's synchronisation, then the host's copies out of the pinned block.
-    int fetch_out()
+    int finish()
     {
+        if (!host_) return FP_OK;
         if (plan_.small_out_hi > plan_.small_out_lo && !zero_copy_out_)
             HIP_TRY(hipMemcpyAsync(ctx_->pinned + plan_.small_out_lo, ctx_->arena.base + plan_.small_out_lo, plan_.small_out_hi - plan_.small_out_lo,
-                                   hipMemcpyDeviceToHost, ctx_->stream));
-        for (int i = 0; i < list_->n; ++i)
-            if (returns(i) && !via_pinned(i)) HIP_TRY(hipMemcpyAsync(list_->item[i].host, addr(i), list_->item[i].bytes, hipMemcpyDeviceToHost, ctx_->stream));
-        HIP_TRY(hipStreamSynchronize(ctx_->stream));
-        for (int i = 0; i < list_->n; ++i)
-            if (returns(i) && via_pinned(i)) memcpy(list_->item[i].host, ctx_->pinned + plan_.offset[i], list_->item[i].bytes);
+                                   hipMemcpyDeviceToHost, stream_));
+        for (int i = 0; i < list_.n; ++i)
+            if (returns(i) && !via_pinned(i)) HIP_TRY(hipMemcpyAsync(list_.item[i].host, addr(i), list_.item[i].bytes, hipMemcpyDeviceToHost, stream_));
+        HIP_TRY(hipStreamSynchronize(stream_));
+        for (int i = 0; i < list_.n; ++i)
+            if (returns(i) && via_pinned(i)) memcpy(list_.item[i].host, ctx_->pinned + plan_.offset[i], list_.item[i].bytes);
         return FP_OK;
     }
 
@@ -299,12 +315,14 @@ class HostStage {
         if (plan_.region[i] == fp::StageRegion::NONE) return nullptr;
         return (plan_.region[i] == fp::StageRegion::PINNED ? ctx_->pinned : ctx_->arena.base) + plan_.offset[i];
     }
-    bool returns(int i) const { return list_->item[i].kind == fp::StageKind::IN_MUT || (list_->item[i].kind == fp::StageKind::OUT && plan_.region[i] != fp::StageRegion::NONE); }
+    bool returns(int i) const { return list_.item[i].kind == fp::StageKind::IN_MUT || (list_.item[i].kind == fp::StageKind::OUT && plan_.region[i] != fp::StageRegion::NONE); }
     // (an in/out array of the window was copied in with it, but comes back by a copy of its own)
-    bool via_pinned(int i) const { return plan_.region[i] == fp::StageRegion::PINNED || (plan_.region[i] == fp::StageRegion::WINDOW && list_->item[i].kind == fp::StageKind::OUT); }
+    bool via_pinned(int i) const { return plan_.region[i] == fp::StageRegion::PINNED || (plan_.region[i] == fp::StageRegion::WINDOW && list_.item[i].kind == fp::StageKind::OUT); }
 
     fp_ctx* ctx_;
-    const StageList* list_ = nullptr;
+    const bool host_;
+    const hipStream_t stream_;
+    StageList list_;
     fp::StagePlan plan_;
     bool zero_copy_out_ = false;
 };
@@ -520,40 +538,35 @@ fp_batch device_batch(const fp_batch* batch)
     return b;
 }
 
-// The argument block the table passes behind the dense pass share (fp::TablePassArgs), holding the caller's arrays as they were given:
-// all an FP_MEM_DEVICE call needs
-void table_pass_args(fp::TablePassArgs* a, const fp_params* p, const fp_batch* b, const double* cost_tbl, uint32_t* flag_tbl, int32_t* best_idx,
-                     double* best_cost, int32_t* count)
+// What differs between the memory spaces in every call that has a batch.  The launch order: an FP_MEM_DEVICE call hands the caller's
+// fp_batch.launch_order to its kernel, a host call has none.
+const int32_t* launch_order_of(const CallStage& call, const fp_batch* b) { return call.host() ? nullptr : b->launch_order; }
+
+// The argument block the table passes behind the dense pass share (fp::TablePassArgs), declared in the call's list: its scalars, and
+// of the arrays only what the kernels read (the lattice samples, the ego states, the knots, the two tables).  `own` declares the entry
+// point's own arrays where they have always stood in its list, behind the knots: the order of a list decides the arena's layout
+// (plan_stage).  plan_fiss_impl, whose batch and tables are on the device in either space, declares its blocks in a pass-through list.
+template <typename Own>
+void table_pass_declare(StageList& sl, fp::TablePassArgs* a, const fp_params* p, const fp_batch* b, const int32_t* perm, const double* cost_tbl, uint32_t* flag_tbl,
+                        int32_t* best_idx, double* best_cost, int32_t* count, Own own)
 {
+    const size_t B = (size_t)b->B, C = (size_t)p->nd * p->nv * p->nt;
     a->B = b->B; a->NX = b->NX; a->nd = p->nd; a->nv = p->nv; a->nt = p->nt;
     a->tick_t = p->tick_t;
-    a->t_samples = b->t_samples; a->v_samples = b->v_samples; a->ego = b->ego;
-    a->frame_of = b->frame_of; a->nx = b->nx; a->knots = b->knots;
-    a->skip = b->skip; a->perm = b->launch_order;
-    a->cost_tbl = cost_tbl; a->flag_tbl = flag_tbl; a->best_idx = best_idx; a->best_cost = best_cost; a->count = count;
-}
-// FP_MEM_HOST: every array of the block is declared for staging and gets its device address at commit.  Only what the kernels read
-// travels (the lattice samples, the ego states, the knots, the two tables); a host call has no launch order.  `own` declares the
-// entry point's own arrays where they have always stood in its list, behind the knots: the order of a list decides the arena's layout
-// (plan_stage).
-template <typename Own>
-void table_pass_stage(StageList& sl, fp::TablePassArgs* a, int F, Own own)
-{
-    const size_t B = (size_t)a->B, C = (size_t)a->nd * a->nv * a->nt;
-    a->perm = nullptr;
-    sl.in(a->t_samples, (size_t)a->nt, &a->t_samples);
-    sl.in(a->v_samples, B * a->nv, &a->v_samples);
-    sl.in(a->ego, B * 6, &a->ego);
-    sl.in(a->frame_of, B, &a->frame_of);
-    sl.in(a->nx, (size_t)F, &a->nx);
-    sl.in(a->knots, (size_t)F * a->NX, &a->knots);
+    a->perm = perm;
+    sl.in(b->t_samples, (size_t)p->nt, &a->t_samples);
+    sl.in(b->v_samples, B * p->nv, &a->v_samples);
+    sl.in(b->ego, B * 6, &a->ego);
+    sl.in(b->frame_of, B, &a->frame_of);
+    sl.in(b->nx, (size_t)b->F, &a->nx);
+    sl.in(b->knots, (size_t)b->F * b->NX, &a->knots);
     own(sl);
-    if (a->skip) sl.in(a->skip, B, &a->skip);
-    sl.in(a->cost_tbl, B * C, &a->cost_tbl);
-    sl.in_mut(a->flag_tbl, B * C, &a->flag_tbl);
-    sl.out(a->best_idx, B, &a->best_idx);
-    sl.out(a->best_cost, B, &a->best_cost);
-    sl.out(a->count, B, &a->count);
+    if (b->skip) sl.in(b->skip, B, &a->skip);
+    sl.in(cost_tbl, B * C, &a->cost_tbl);
+    sl.in_mut(flag_tbl, B * C, &a->flag_tbl);
+    sl.out(best_idx, B, &a->best_idx);
+    sl.out(best_cost, B, &a->best_cost);
+    sl.out(count, B, &a->count);
 }
 
 // Inline inputs of a multi-kernel call (fp::InlineIn::publish): besides the eight per-ego arrays of the batch the blob carries
@@ -572,7 +585,7 @@ void inline_publish(const fp::InlineIn& inl, fp_batch* dev_pub, const InlineExtr
     for (int i = 0; i < n_extra; ++i) mirror_address(extra[i].dev, mirror);
 }
 
-// Appends the batch's arrays to the call's list (`dev` gets their device addresses at commit).  The tables of a tagged batch do not
+// FP_MEM_HOST: appends the batch's arrays to the call's list (`dev` gets their device addresses at commit).  The tables of a tagged batch do not
 // use the arena: their upload, if one is due, is enqueued here - ahead of the call's other copies.
 int stage_batch(fp_ctx* ctx, StageList& sl, StageRegime& rg, const fp_params* p, const fp_batch* b, fp_batch* dev, fp::InlineIn* inl = nullptr,
                 fp_batch* dev_pub = nullptr, const InlineExtra* extra = nullptr, int n_extra = 0)
@@ -676,6 +689,16 @@ int stage_batch(fp_ctx* ctx, StageList& sl, StageRegime& rg, const fp_params* p,
 #undef PUSH
     if (!has_obs) dev->n_obs = 0;
     if (!has_obs && dev_pub && inlined) dev_pub->n_obs = 0;
+    return FP_OK;
+}
+
+// The batch of a call in either space.  FP_MEM_HOST: stage_batch.  FP_MEM_DEVICE: the caller's struct - as it stands (AS_GIVEN), or as
+// device_batch sees it (NO_OBS_WITHOUT_SCENES) for the kernels that walk obstacle columns; nothing is enqueued.
+enum class DeviceView { AS_GIVEN, NO_OBS_WITHOUT_SCENES };
+int stage_batch(fp_ctx* ctx, CallStage& call, StageRegime& rg, const fp_params* p, const fp_batch* b, fp_batch* dev, DeviceView view)
+{
+    if (call.host()) return stage_batch(ctx, call.list(), rg, p, b, dev);
+    *dev = view == DeviceView::AS_GIVEN ? *b : device_batch(b);
     return FP_OK;
 }
 
@@ -1574,7 +1597,8 @@ static int plan_dense_impl(fp_ctx* ctx, const fp_params* params, const fp_batch*
         return fail(FP_EINVAL, "w_obstacle > 0: the clearance term is defined for FrenetOptimalPlanner's dense pass only - result.fopplus / result.audit must be NULL");
     if (batch->B == 0) return FP_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    const hipStream_t st = mem == FP_MEM_DEVICE ? (hipStream_t)stream : ctx->stream;
+    CallStage call(ctx, mem, stream);
+    const hipStream_t st = call.stream();
     FP_TRY(handover_check(ctx, st));
     const size_t C = (size_t)params->nd * params->nv * params->nt, B = (size_t)batch->B;
     int stride;
@@ -1584,8 +1608,7 @@ static int plan_dense_impl(fp_ctx* ctx, const fp_params* params, const fp_batch*
     ctx_lattice_args(ctx, &ka);
     int32_t* fopplus = result->fopplus;
     uint32_t* audit = result->audit;
-    HostStage hs(ctx);
-    StageList sl;
+    StageList& sl = call.list();
     fp::InlineIn inl;
     if (mem == FP_MEM_DEVICE) {
         ka.b = device_batch(batch);
@@ -1611,7 +1634,7 @@ static int plan_dense_impl(fp_ctx* ctx, const fp_params* params, const fp_batch*
         ka.r.traj_sparse = result->traj_sparse;
         sl.out(result->fopplus, B * 2, &fopplus);
         sl.out(result->audit, B, &audit);
-        FP_TRY(hs.commit(sl, rg));
+        FP_TRY(call.commit(rg));
         // sparse rows are only partly written by the kernels: the host block comes back with the caller's own bytes elsewhere
         if (result->traj_sparse && ka.r.best_traj) HIP_TRY(hipMemcpyAsync(ka.r.best_traj, result->best_traj, traj_doubles * sizeof(double), hipMemcpyDefault, st));
     }
@@ -1638,7 +1661,7 @@ static int plan_dense_impl(fp_ctx* ctx, const fp_params* params, const fp_batch*
         LAUNCH_TRY(fp::launch_fopplus_count((int)B, (int)C, ka.r.cost_tbl, ka.r.flag_tbl, ka.r.best_idx, ka.r.best_cost, fopplus, ka.r.stats, ka.b.skip, st),
                    "FOP+ count kernel");
     if (mem == FP_MEM_DEVICE) return FP_OK;
-    FP_TRY(hs.fetch_out());
+    FP_TRY(call.finish());
     if (handover_failed(ctx)) {  // (the call has synchronised: a timed-out hand-over of ITS launch is known now - run it again without appended workgroups)
         (void)handover_recover(ctx, ctx->stream);
         return fp_plan_dense(ctx, params, batch, result, mem, stream);
@@ -1661,31 +1684,26 @@ int fp_winner_trajs(fp_ctx* ctx, const fp_params* params, const fp_batch* batch,
     ka.r = no_result();
     ka.r.traj_stride = traj_stride;
     ka.r.traj_sparse = traj_sparse;
-    if (mem == FP_MEM_DEVICE) {
-        ka.b = *batch;
-        ka.r.best_idx = const_cast<int32_t*>(best_idx);
-        ka.r.best_flags = best_flags;
-        ka.r.best_traj = best_traj;
-        LAUNCH_TRY(fp::launch_winner_traj(ka, nullptr, (hipStream_t)stream), "winner epilogue");
-        return FP_OK;
+    CallStage call(ctx, mem, stream);
+    if (call.host()) {
+        FP_TRY(check_batch_host(params, batch));
+        FP_TRY(check_stride_host(params, batch, stride));
+        ka.p.points_max = host_points_max(params, batch, nullptr, 0, 0);
+        const int C = params->nd * params->nv * params->nt;
+        for (size_t i = 0; i < B; ++i)
+            if (best_idx[i] >= C) return fail(FP_EINVAL, "best_idx[%zu]=%d out of range", i, best_idx[i]);
     }
-    FP_TRY(check_batch_host(params, batch));
-    FP_TRY(check_stride_host(params, batch, stride));
-    ka.p.points_max = host_points_max(params, batch, nullptr, 0, 0);
-    const int C = params->nd * params->nv * params->nt;
-    for (size_t i = 0; i < B; ++i)
-        if (best_idx[i] >= C) return fail(FP_EINVAL, "best_idx[%zu]=%d out of range", i, best_idx[i]);
-    HostStage hs(ctx);
-    StageList sl;
+    StageList& sl = call.list();
     StageRegime rg;  // (throughput)
-    FP_TRY(stage_batch(ctx, sl, rg, params, batch, &ka.b));
+    FP_TRY(stage_batch(ctx, call, rg, params, batch, &ka.b, DeviceView::AS_GIVEN));
     sl.in(best_idx, B, &ka.r.best_idx);
     sl.out(best_flags, B, &ka.r.best_flags);
     sl.out(best_traj, traj_doubles, &ka.r.best_traj);
-    FP_TRY(hs.commit(sl, rg));
-    if (traj_sparse) HIP_TRY(hipMemcpyAsync(ka.r.best_traj, best_traj, traj_doubles * sizeof(double), hipMemcpyDefault, ctx->stream));
-    LAUNCH_TRY(fp::launch_winner_traj(ka, nullptr, ctx->stream), "winner epilogue");
-    return hs.fetch_out();
+    FP_TRY(call.commit(rg));
+    // (sparse rows are only partly written by the kernels: a host array comes back with the caller's own bytes elsewhere)
+    if (call.host() && traj_sparse) HIP_TRY(hipMemcpyAsync(ka.r.best_traj, best_traj, traj_doubles * sizeof(double), hipMemcpyDefault, call.stream()));
+    LAUNCH_TRY(fp::launch_winner_traj(ka, nullptr, call.stream()), "winner epilogue");
+    return call.finish();
 }
 
 int fp_rank_feasible(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, const double* cost_tbl, const uint32_t* flag_tbl,
@@ -1697,28 +1715,22 @@ int fp_rank_feasible(fp_ctx* ctx, const fp_params* params, const fp_batch* batch
     if (batch->B == 0) return FP_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t B = (size_t)batch->B, C = (size_t)params->nd * params->nv * params->nt;
+    CallStage call(ctx, mem, stream);
     fp::RankArgs a;
     a.B = batch->B; a.C = (int)C; a.K = K;
-    if (mem == FP_MEM_DEVICE) {
-        a.cost_tbl = cost_tbl; a.flag_tbl = flag_tbl; a.skip = batch->skip; a.perm = batch->launch_order;
-        a.rank_idx = rank_idx; a.rank_cost = rank_cost; a.n_feasible = n_feasible;
-        LAUNCH_TRY(fp::launch_rank_feasible(a, (hipStream_t)stream), "ranking kernel");
-        ++ctx->rank_launches;
-        return FP_OK;
-    }
-    // host arrays: only what the kernel reads travels (the two tables and skip)
-    HostStage hs(ctx);
-    StageList sl;
+    a.perm = launch_order_of(call, batch);
+    // only what the kernel reads travels (the two tables and skip)
+    StageList& sl = call.list();
     sl.in(cost_tbl, B * C, &a.cost_tbl);
     sl.in(flag_tbl, B * C, &a.flag_tbl);
     if (batch->skip) sl.in(batch->skip, B, &a.skip);
     sl.out(rank_idx, B * K, &a.rank_idx);
     sl.out(rank_cost, B * K, &a.rank_cost);
     sl.out(n_feasible, B, &a.n_feasible);
-    FP_TRY(hs.commit(sl));
-    LAUNCH_TRY(fp::launch_rank_feasible(a, ctx->stream), "ranking kernel");
+    FP_TRY(call.commit());
+    LAUNCH_TRY(fp::launch_rank_feasible(a, call.stream()), "ranking kernel");
     ++ctx->rank_launches;
-    return hs.fetch_out();
+    return call.finish();
 }
 
 int fp_boundary_mask(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, const fp_corridor* corridor, const double* cost_tbl,
@@ -1730,23 +1742,23 @@ int fp_boundary_mask(fp_ctx* ctx, const fp_params* params, const fp_batch* batch
     FP_TRY(check_corridor(corridor));
     if (batch->B == 0) return FP_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    fp::BoundaryArgs a;
-    table_pass_args(&a, params, batch, cost_tbl, flag_tbl, best_idx, best_cost, n_masked);
-    fp::boundary_args(&a, fp::rule_args(fp_rule_set{nullptr, nullptr, corridor, nullptr}), *params, batch->d_samples);
-    if (mem == FP_MEM_DEVICE) return boundary_pass(ctx, a, (hipStream_t)stream);
-    FP_TRY(check_frames_host(batch));
-    FP_TRY(check_corridor_host(corridor, batch));
+    CallStage call(ctx, mem, stream);
+    if (call.host()) {
+        FP_TRY(check_frames_host(batch));
+        FP_TRY(check_corridor_host(corridor, batch));
+    }
     const size_t fn = (size_t)batch->F * batch->NX;
-    HostStage hs(ctx);
-    StageList sl;
-    sl.in(a.d_samples, (size_t)a.nd, &a.d_samples);
-    table_pass_stage(sl, &a, batch->F, [&](StageList& l) {
+    fp::BoundaryArgs a;
+    fp::boundary_args(&a, fp::rule_args(fp_rule_set{nullptr, nullptr, corridor, nullptr}), *params, batch->d_samples);
+    StageList& sl = call.list();
+    sl.in(a.d_samples, (size_t)params->nd, &a.d_samples);
+    table_pass_declare(sl, &a, params, batch, launch_order_of(call, batch), cost_tbl, flag_tbl, best_idx, best_cost, n_masked, [&](StageList& l) {
         l.in(a.left, fn, &a.left);
         l.in(a.right, fn, &a.right);
     });
-    FP_TRY(hs.commit(sl));
-    FP_TRY(boundary_pass(ctx, a, ctx->stream));
-    return hs.fetch_out();
+    FP_TRY(call.commit());
+    FP_TRY(boundary_pass(ctx, a, call.stream()));
+    return call.finish();
 }
 
 int fp_speed_envelope(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, const fp_speed_profile* profile, const double* cost_tbl,
@@ -1758,22 +1770,21 @@ int fp_speed_envelope(fp_ctx* ctx, const fp_params* params, const fp_batch* batc
     FP_TRY(check_speed_profile(profile, batch));
     if (batch->B == 0) return FP_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    fp::EnvelopeArgs a;
-    table_pass_args(&a, params, batch, cost_tbl, flag_tbl, best_idx, best_cost, n_limited);
-    fp::envelope_args(&a, fp::rule_args(fp_rule_set{profile, nullptr, nullptr, nullptr}), batch->coef);
-    if (mem == FP_MEM_DEVICE) return envelope_pass(ctx, a, (hipStream_t)stream);
-    FP_TRY(check_frames_host(batch));
-    FP_TRY(check_speed_profile_host(profile, batch));
+    CallStage call(ctx, mem, stream);
+    if (call.host()) {
+        FP_TRY(check_frames_host(batch));
+        FP_TRY(check_speed_profile_host(profile, batch));
+    }
     const size_t fn = (size_t)batch->F * batch->NX;
-    HostStage hs(ctx);
-    StageList sl;
-    table_pass_stage(sl, &a, batch->F, [&](StageList& l) {
+    fp::EnvelopeArgs a;
+    fp::envelope_args(&a, fp::rule_args(fp_rule_set{profile, nullptr, nullptr, nullptr}), batch->coef);
+    table_pass_declare(call.list(), &a, params, batch, launch_order_of(call, batch), cost_tbl, flag_tbl, best_idx, best_cost, n_limited, [&](StageList& l) {
         if (a.coef) l.in(a.coef, fn * 8, &a.coef);  // (set when the lateral bound is on: check_speed_profile has seen batch->coef then)
         l.in(a.v_limit, fn, &a.v_limit);
     });
-    FP_TRY(hs.commit(sl));
-    FP_TRY(envelope_pass(ctx, a, ctx->stream));
-    return hs.fetch_out();
+    FP_TRY(call.commit());
+    FP_TRY(envelope_pass(ctx, a, call.stream()));
+    return call.finish();
 }
 
 int fp_gate_mask(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, const fp_gates* gates, const double* cost_tbl, uint32_t* flag_tbl,
@@ -1785,23 +1796,23 @@ int fp_gate_mask(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, co
     FP_TRY(check_gates(gates));
     if (batch->B == 0) return FP_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    fp::GateArgs a;
-    table_pass_args(&a, params, batch, cost_tbl, flag_tbl, best_idx, best_cost, n_gated);
-    fp::gate_args(&a, fp::rule_args(fp_rule_set{nullptr, gates, nullptr, nullptr}), batch->t_now, fp::gate_points_cap(*params, false, 0));
-    if (mem == FP_MEM_DEVICE) return gate_pass(ctx, a, (hipStream_t)stream);
-    FP_TRY(check_frames_host(batch));
-    a.points_cap = fp::gate_points_cap(*params, true, host_points_max(params, batch, nullptr, 0, 0));  // (host calls look at their time samples themselves)
+    CallStage call(ctx, mem, stream);
+    int host_points = 0;  // (a device caller announces its points in fp_params.points_max; host calls look at their time samples themselves)
+    if (call.host()) {
+        FP_TRY(check_frames_host(batch));
+        host_points = host_points_max(params, batch, nullptr, 0, 0);
+    }
     const size_t F = (size_t)batch->F;
-    HostStage hs(ctx);
-    StageList sl;
-    table_pass_stage(sl, &a, batch->F, [&](StageList& l) {
+    fp::GateArgs a;
+    fp::gate_args(&a, fp::rule_args(fp_rule_set{nullptr, gates, nullptr, nullptr}), batch->t_now, fp::gate_points_cap(*params, call.host(), host_points));
+    table_pass_declare(call.list(), &a, params, batch, launch_order_of(call, batch), cost_tbl, flag_tbl, best_idx, best_cost, n_gated, [&](StageList& l) {
         l.in(a.t_now, (size_t)a.B, &a.t_now);
         l.in(a.gate_s, F * a.gate_stride, &a.gate_s);
         l.in(a.closed, F * a.T_gate, &a.closed);
     });
-    FP_TRY(hs.commit(sl));
-    FP_TRY(gate_pass(ctx, a, ctx->stream));
-    return hs.fetch_out();
+    FP_TRY(call.commit());
+    FP_TRY(gate_pass(ctx, a, call.stream()));
+    return call.finish();
 }
 
 int fp_gap_mask(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, const fp_time_gap* gap, const double* cost_tbl, uint32_t* flag_tbl,
@@ -1817,28 +1828,23 @@ int fp_gap_mask(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, con
     fp::KernelArgs ka;
     ka.p = *params;
     ka.r = no_result();
-    const bool host = mem != FP_MEM_DEVICE;  // (a host call has no launch order, and its count is staged)
-    fp::GapArgs g = fp::gap_args(fp::rule_args(fp_rule_set{nullptr, nullptr, nullptr, gap}), host ? nullptr : batch->launch_order, host ? nullptr : n_close);
-    if (!host) {
-        ka.b = device_batch(batch);
-        ka.r.cost_tbl = const_cast<double*>(cost_tbl);  // (read only)
-        ka.r.flag_tbl = flag_tbl; ka.r.best_idx = best_idx; ka.r.best_cost = best_cost;
-        return gap_pass(ctx, ka, g, (hipStream_t)stream);
+    CallStage call(ctx, mem, stream);
+    if (call.host()) {
+        FP_TRY(check_batch_host(params, batch));
+        ka.p.points_max = fp::gap_points_max(*params, true, host_points_max(params, batch, nullptr, 0, 0));  // (host calls look at their time samples themselves)
     }
-    FP_TRY(check_batch_host(params, batch));
-    ka.p.points_max = fp::gap_points_max(*params, true, host_points_max(params, batch, nullptr, 0, 0));  // (host calls look at their time samples themselves)
-    HostStage hs(ctx);
-    StageList sl;
+    fp::GapArgs g = fp::gap_args(fp::rule_args(fp_rule_set{nullptr, nullptr, nullptr, gap}), launch_order_of(call, batch), nullptr);
+    StageList& sl = call.list();
     StageRegime rg;  // (throughput)
-    FP_TRY(stage_batch(ctx, sl, rg, params, batch, &ka.b));
+    FP_TRY(stage_batch(ctx, call, rg, params, batch, &ka.b, DeviceView::NO_OBS_WITHOUT_SCENES));
     sl.in(cost_tbl, B * C, &ka.r.cost_tbl);
     sl.in_mut(flag_tbl, B * C, &ka.r.flag_tbl);
     sl.out(best_idx, B, &ka.r.best_idx);
     sl.out(best_cost, B, &ka.r.best_cost);
     sl.out(n_close, B, &g.count);
-    FP_TRY(hs.commit(sl, rg));
-    FP_TRY(gap_pass(ctx, ka, g, ctx->stream));
-    return hs.fetch_out();
+    FP_TRY(call.commit(rg));
+    FP_TRY(gap_pass(ctx, ka, g, call.stream()));
+    return call.finish();
 }
 
 int fp_rules_eval(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, const fp_rule_set* rules, int32_t K, const double* end_states,
@@ -1854,37 +1860,33 @@ int fp_rules_eval(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, c
     fp::KernelArgs ka;
     ka.p = *params;
     ka.r = no_result();
+    CallStage call(ctx, mem, stream);
     fp::RulesEvalArgs a = fp::rule_args(*rules);
     a.K = K;
-    if (mem == FP_MEM_DEVICE) {
-        ka.b = device_batch(batch);
-        a.end_states = end_states; a.flags = flags; a.rule_bits = rule_bits; a.counts = counts; a.perm = batch->launch_order;
-        LAUNCH_TRY(fp::launch_rules_eval(ka, a, (hipStream_t)stream), "rules kernel");
-        ++ctx->rules_eval_launches;
-        return FP_OK;
+    a.perm = launch_order_of(call, batch);
+    if (call.host()) {
+        FP_TRY(check_batch_host(params, batch, /*past_ok=*/true));  // (a negative t_now reads the gates' first state; no obstacle has a state before step 0)
+        FP_TRY(check_rule_set_host(rules, batch));
+        for (size_t i = 0; i < BK; ++i) {
+            const double n = end_states[3 * i + 2] / params->tick_t;
+            if (n != n || (batch->skip && batch->skip[i / (size_t)K])) continue;  // NaN end state = "no trajectory"
+            if (!(n > 0) || n > FP_MAX_POINTS)
+                return fail(FP_ELIMIT, "fp_rules_eval: end_states of ego %zu, trajectory %zu: T=%g needs 1..FP_MAX_POINTS points", i / (size_t)K, i % (size_t)K, end_states[3 * i + 2]);
+        }
+        ka.p.points_max = host_points_max(params, batch, end_states + 2, BK, 3);
     }
-    FP_TRY(check_batch_host(params, batch, /*past_ok=*/true));  // (a negative t_now reads the gates' first state; no obstacle has a state before step 0)
-    FP_TRY(check_rule_set_host(rules, batch));
-    for (size_t i = 0; i < BK; ++i) {
-        const double n = end_states[3 * i + 2] / params->tick_t;
-        if (n != n || (batch->skip && batch->skip[i / (size_t)K])) continue;  // NaN end state = "no trajectory"
-        if (!(n > 0) || n > FP_MAX_POINTS)
-            return fail(FP_ELIMIT, "fp_rules_eval: end_states of ego %zu, trajectory %zu: T=%g needs 1..FP_MAX_POINTS points", i / (size_t)K, i % (size_t)K, end_states[3 * i + 2]);
-    }
-    ka.p.points_max = host_points_max(params, batch, end_states + 2, BK, 3);
-    HostStage hs(ctx);
-    StageList sl;
+    StageList& sl = call.list();
     StageRegime rg;  // (throughput)
-    FP_TRY(stage_batch(ctx, sl, rg, params, batch, &ka.b));
+    FP_TRY(stage_batch(ctx, call, rg, params, batch, &ka.b, DeviceView::NO_OBS_WITHOUT_SCENES));
     fp::stage_rule_arrays(sl, &a, batch->F, batch->NX);
     sl.in(end_states, BK * 3, &a.end_states);
     sl.in_mut(flags, BK, &a.flags);
     sl.out(rule_bits, BK, &a.rule_bits);
     if (counts) sl.in_mut(counts, B * FP_RULE_COUNT, &a.counts);
-    FP_TRY(hs.commit(sl, rg));
-    LAUNCH_TRY(fp::launch_rules_eval(ka, a, ctx->stream), "rules kernel");
+    FP_TRY(call.commit(rg));
+    LAUNCH_TRY(fp::launch_rules_eval(ka, a, call.stream()), "rules kernel");
     ++ctx->rules_eval_launches;
-    return hs.fetch_out();
+    return call.finish();
 }
 
 int fp_traj_margins(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, int32_t K, const int32_t* best_idx, const double* end_state,
@@ -1902,46 +1904,41 @@ int fp_traj_margins(fp_ctx* ctx, const fp_params* params, const fp_batch* batch,
     ka.p = *params;
     ka.p.check_stride = pose_stride;  // (the kernel's staging and pose set read it there; the caller's own check_stride is not used)
     ka.r = no_result();
+    CallStage call(ctx, mem, stream);
     fp::MarginArgs m;
     m.K = K;
-    if (mem == FP_MEM_DEVICE) {
-        ka.b = device_batch(batch);
-        m.best_idx = best_idx; m.end_state = end_state; m.perm = batch->launch_order;
-        m.min_dist = min_dist; m.min_step = min_step; m.min_obs = min_obs;
-        LAUNCH_TRY(fp::launch_traj_margins(ka, m, (hipStream_t)stream), "plan-margin kernel");
-        ++ctx->margin_launches;
-        return FP_OK;
-    }
-    FP_TRY(check_batch_host(params, batch));
-    if (best_idx) {
-        const int C = params->nd * params->nv * params->nt;
-        for (size_t i = 0; i < KB; ++i) {
-            const size_t b = i % (size_t)batch->B;
-            if (best_idx[i] >= C && !(batch->skip && batch->skip[b]))
-                return fail(FP_EINVAL, "fp_traj_margins: best_idx of ego %zu, plane %zu = %d is outside the lattice (nd*nv*nt = %d)", b, i / (size_t)batch->B, best_idx[i], C);
+    m.perm = launch_order_of(call, batch);
+    if (call.host()) {
+        FP_TRY(check_batch_host(params, batch));
+        if (best_idx) {
+            const int C = params->nd * params->nv * params->nt;
+            for (size_t i = 0; i < KB; ++i) {
+                const size_t b = i % (size_t)batch->B;
+                if (best_idx[i] >= C && !(batch->skip && batch->skip[b]))
+                    return fail(FP_EINVAL, "fp_traj_margins: best_idx of ego %zu, plane %zu = %d is outside the lattice (nd*nv*nt = %d)", b, i / (size_t)batch->B, best_idx[i], C);
+            }
+            ka.p.points_max = host_points_max(params, batch, nullptr, 0, 0);
+        } else {
+            for (size_t i = 0; i < KB; ++i) {
+                const double n = end_state[3 * i + 2] / params->tick_t;
+                if (n != n || (batch->skip && batch->skip[i % (size_t)batch->B])) continue;  // NaN end state = "no trajectory"
+                if (!(n > 0) || n > FP_MAX_POINTS)
+                    return fail(FP_ELIMIT, "fp_traj_margins: end_state of ego %zu, plane %zu: T=%g needs 1..FP_MAX_POINTS points", i % (size_t)batch->B, i / (size_t)batch->B, end_state[3 * i + 2]);
+            }
+            ka.p.points_max = host_points_max(params, batch, end_state + 2, KB, 3);
         }
-        ka.p.points_max = host_points_max(params, batch, nullptr, 0, 0);
-    } else {
-        for (size_t i = 0; i < KB; ++i) {
-            const double n = end_state[3 * i + 2] / params->tick_t;
-            if (n != n || (batch->skip && batch->skip[i % (size_t)batch->B])) continue;  // NaN end state = "no trajectory"
-            if (!(n > 0) || n > FP_MAX_POINTS)
-                return fail(FP_ELIMIT, "fp_traj_margins: end_state of ego %zu, plane %zu: T=%g needs 1..FP_MAX_POINTS points", i % (size_t)batch->B, i / (size_t)batch->B, end_state[3 * i + 2]);
-        }
-        ka.p.points_max = host_points_max(params, batch, end_state + 2, KB, 3);
     }
-    HostStage hs(ctx);
-    StageList sl;
+    StageList& sl = call.list();
     StageRegime rg;  // (throughput)
-    FP_TRY(stage_batch(ctx, sl, rg, params, batch, &ka.b));
+    FP_TRY(stage_batch(ctx, call, rg, params, batch, &ka.b, DeviceView::NO_OBS_WITHOUT_SCENES));
     if (best_idx) sl.in(best_idx, KB, &m.best_idx); else sl.in(end_state, KB * 3, &m.end_state);
     sl.out(min_dist, KB, &m.min_dist);
     sl.out(min_step, KB, &m.min_step);
     sl.out(min_obs, KB, &m.min_obs);
-    FP_TRY(hs.commit(sl, rg));
-    LAUNCH_TRY(fp::launch_traj_margins(ka, m, ctx->stream), "plan-margin kernel");
+    FP_TRY(call.commit(rg));
+    LAUNCH_TRY(fp::launch_traj_margins(ka, m, call.stream()), "plan-margin kernel");
     ++ctx->margin_launches;
-    return hs.fetch_out();
+    return call.finish();
 }
 
 // fp_fallback_stop and fp_fallback_stop_rules: one body.  fn names the entry point in the messages; with_rules: the rule instance
@@ -1969,43 +1966,31 @@ static int fallback_call(const char* fn, bool with_rules, fp_ctx* ctx, const fp_
     fp::KernelArgs ka;
     ka.p = *params;
     ka.r = no_result();
+    CallStage call(ctx, mem, stream);
     fp::FallbackRulesArgs a;  // (fp_fallback_stop launches with its FallbackArgs part)
     a.n_d = fallback->n_d; a.n_stop = fallback->n_stop; a.max_decel = fallback->max_decel;
     if (with_rules) a.rules = fp::rule_args(*rules);
-    if (mem == FP_MEM_DEVICE) {
-        ka.b = device_batch(batch);
-        a.d_targets = fallback->d_targets; a.stop_T = fallback->stop_T; a.best_idx = best_idx; a.end_state = end_state;
-        a.status = status; a.fb_idx = fb_idx; a.hit_step = hit_step; a.hit_obs = hit_obs; a.hit_speed = hit_speed;
-        a.cand = cand; a.counts = counts; a.perm = batch->launch_order;
-        if (with_rules) {
-            a.cand_rules = cand_rules; a.rule_bits = rule_bits; a.rule_counts = rule_counts;
-            LAUNCH_TRY(fp::launch_fallback_stop_rules(ka, a, (hipStream_t)stream), "fallback rules kernel");
-            ++ctx->fallback_rules_launches;
-        } else {
-            LAUNCH_TRY(fp::launch_fallback_stop(ka, a, (hipStream_t)stream), "fallback kernel");
-            ++ctx->fallback_launches;
+    a.perm = launch_order_of(call, batch);
+    if (call.host()) {
+        FP_TRY(check_batch_host(params, batch));
+        if (with_rules) FP_TRY(check_rule_set_host(rules, batch));
+        for (int i = 0; i < fallback->n_stop; ++i) {
+            const double T = fallback->stop_T[i];
+            if (!finite_pos(T) || (i > 0 && !(T > fallback->stop_T[i - 1])))
+                return fail(FP_EINVAL, "%s: stop_T[%d]=%g must be finite, > 0 and above stop_T[%d]", fn, i, T, i - 1);
+            if (ceil(T / params->tick_t) > FP_MAX_POINTS) return fail(FP_ELIMIT, "%s: stop_T[%d]=%g needs more than FP_MAX_POINTS points", fn, i, T);
         }
-        return FP_OK;
+        if (best_idx) {
+            const int C = params->nd * params->nv * params->nt;
+            for (size_t b = 0; b < B; ++b)
+                if (best_idx[b] >= C && !(batch->skip && batch->skip[b]))
+                    return fail(FP_EINVAL, "%s: best_idx of ego %zu = %d is outside the lattice (nd*nv*nt = %d)", fn, b, best_idx[b], C);
+        }
+        ka.p.points_max = host_points_max(params, batch, fallback->stop_T, (size_t)fallback->n_stop, 1);
     }
-    FP_TRY(check_batch_host(params, batch));
-    if (with_rules) FP_TRY(check_rule_set_host(rules, batch));
-    for (int i = 0; i < fallback->n_stop; ++i) {
-        const double T = fallback->stop_T[i];
-        if (!finite_pos(T) || (i > 0 && !(T > fallback->stop_T[i - 1])))
-            return fail(FP_EINVAL, "%s: stop_T[%d]=%g must be finite, > 0 and above stop_T[%d]", fn, i, T, i - 1);
-        if (ceil(T / params->tick_t) > FP_MAX_POINTS) return fail(FP_ELIMIT, "%s: stop_T[%d]=%g needs more than FP_MAX_POINTS points", fn, i, T);
-    }
-    if (best_idx) {
-        const int C = params->nd * params->nv * params->nt;
-        for (size_t b = 0; b < B; ++b)
-            if (best_idx[b] >= C && !(batch->skip && batch->skip[b]))
-                return fail(FP_EINVAL, "%s: best_idx of ego %zu = %d is outside the lattice (nd*nv*nt = %d)", fn, b, best_idx[b], C);
-    }
-    ka.p.points_max = host_points_max(params, batch, fallback->stop_T, (size_t)fallback->n_stop, 1);
-    HostStage hs(ctx);
-    StageList sl;
+    StageList& sl = call.list();
     StageRegime rg;  // (throughput)
-    FP_TRY(stage_batch(ctx, sl, rg, params, batch, &ka.b));
+    FP_TRY(stage_batch(ctx, call, rg, params, batch, &ka.b, DeviceView::NO_OBS_WITHOUT_SCENES));
     if (with_rules) fp::stage_rule_arrays(sl, &a.rules, batch->F, batch->NX);
     sl.in(fallback->d_targets, (size_t)fallback->n_d, &a.d_targets);
     sl.in(fallback->stop_T, (size_t)fallback->n_stop, &a.stop_T);
@@ -2023,15 +2008,15 @@ static int fallback_call(const char* fn, bool with_rules, fp_ctx* ctx, const fp_
         sl.out(rule_bits, B, &a.rule_bits);
         if (rule_counts) sl.in_mut(rule_counts, B * FP_RULE_COUNT, &a.rule_counts);
     }
-    FP_TRY(hs.commit(sl, rg));
+    FP_TRY(call.commit(rg));
     if (with_rules) {
-        LAUNCH_TRY(fp::launch_fallback_stop_rules(ka, a, ctx->stream), "fallback rules kernel");
+        LAUNCH_TRY(fp::launch_fallback_stop_rules(ka, a, call.stream()), "fallback rules kernel");
         ++ctx->fallback_rules_launches;
     } else {
-        LAUNCH_TRY(fp::launch_fallback_stop(ka, a, ctx->stream), "fallback kernel");
+        LAUNCH_TRY(fp::launch_fallback_stop(ka, a, call.stream()), "fallback kernel");
         ++ctx->fallback_launches;
     }
-    return hs.fetch_out();
+    return call.finish();
 }
 
 int fp_fallback_stop(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, const fp_fallback* fallback, const int32_t* best_idx, double* end_state,
@@ -2069,48 +2054,45 @@ int fp_obstacles_predict(fp_ctx* ctx, const fp_params* params, const fp_batch* b
     fp::PredictArgs a;
     a.S = batch->S; a.T_obs = batch->T_obs; a.n_obs = batch->n_obs; a.F = batch->F; a.NX = batch->NX; a.n_rows = tracks->n_rows;
     a.tick_t = params->tick_t;
-    if (mem == FP_MEM_DEVICE) {
-        if ((uintptr_t)obs_pose & 15u) return fail(FP_EINVAL, "fp_obstacles_predict: obs_pose must be 16-byte aligned");
-        a.nx = batch->nx; a.knots = batch->knots; a.coef = batch->coef;
-        a.model = tracks->model; a.state = tracks->state; a.frame_of_scene = tracks->frame_of_scene; a.t0 = tracks->t0;
-        a.obs_pose = obs_pose; a.final_time_step = final_time_step;
-        LAUNCH_TRY(fp::launch_obstacles_predict(a, (hipStream_t)stream), "obstacle prediction kernel");
-        ++ctx->predict_launches;
-        return FP_OK;
-    }
-    // host arrays: what the device path decides silently (such a column has no pose) is an error the host path can name
+    CallStage call(ctx, mem, stream);
     const size_t S = (size_t)batch->S, n = (size_t)batch->n_obs, fn = (size_t)batch->F * batch->NX;
-    bool any_lane = false;
-    for (size_t s = 0; s < S; ++s)
-        for (size_t j = 0; j < n; ++j) {
-            const int32_t m = tracks->model[s * n + j];
-            if (m < FP_TRACK_NONE || m > FP_TRACK_ARC) return fail(FP_EINVAL, "fp_obstacles_predict: model of scene %zu, column %zu is %d, not one of FP_TRACK_*", s, j, m);
-            if (m != FP_TRACK_LANE) continue;
-            any_lane = true;
-            if (!tracks->frame_of_scene || !batch->nx || !batch->knots || !batch->coef)
-                return fail(FP_EINVAL, "fp_obstacles_predict: scene %zu, column %zu is a LANE track but frame_of_scene / nx / knots / coef is NULL", s, j);
-            const int32_t f = tracks->frame_of_scene[s];
-            if (f < 0 || f >= batch->F) return fail(FP_EINVAL, "fp_obstacles_predict: scene %zu, column %zu is a LANE track on frame %d, outside 0 .. F-1 (F=%d)", s, j, f, batch->F);
-            if (batch->nx[f] < 2 || batch->nx[f] > batch->NX) return fail(FP_EINVAL, "fp_obstacles_predict: scene %zu, column %zu: nx[%d]=%d out of range", s, j, f, batch->nx[f]);
-        }
+    bool frames_read = !call.host();  // (a device call hands the frames on as they are; a host call stages them when a LANE track reads them)
+    if (!call.host()) {
+        if ((uintptr_t)obs_pose & 15u) return fail(FP_EINVAL, "fp_obstacles_predict: obs_pose must be 16-byte aligned");
+    } else {
+        // host arrays: what the device path decides silently (such a column has no pose) is an error the host path can name
+        for (size_t s = 0; s < S; ++s)
+            for (size_t j = 0; j < n; ++j) {
+                const int32_t m = tracks->model[s * n + j];
+                if (m < FP_TRACK_NONE || m > FP_TRACK_ARC) return fail(FP_EINVAL, "fp_obstacles_predict: model of scene %zu, column %zu is %d, not one of FP_TRACK_*", s, j, m);
+                if (m != FP_TRACK_LANE) continue;
+                frames_read = true;
+                if (!tracks->frame_of_scene || !batch->nx || !batch->knots || !batch->coef)
+                    return fail(FP_EINVAL, "fp_obstacles_predict: scene %zu, column %zu is a LANE track but frame_of_scene / nx / knots / coef is NULL", s, j);
+                const int32_t f = tracks->frame_of_scene[s];
+                if (f < 0 || f >= batch->F) return fail(FP_EINVAL, "fp_obstacles_predict: scene %zu, column %zu is a LANE track on frame %d, outside 0 .. F-1 (F=%d)", s, j, f, batch->F);
+                if (batch->nx[f] < 2 || batch->nx[f] > batch->NX) return fail(FP_EINVAL, "fp_obstacles_predict: scene %zu, column %zu: nx[%d]=%d out of range", s, j, f, batch->nx[f]);
+            }
+    }
     const size_t span = (size_t)(tracks->n_rows < batch->T_obs ? tracks->n_rows : batch->T_obs);
-    HostStage hs(ctx);
-    StageList sl;
+    StageList& sl = call.list();
     sl.in(tracks->model, S * n, &a.model);
     sl.in(tracks->state, S * n * 6, &a.state);
     sl.in(tracks->t0, S, &a.t0);
-    if (any_lane) {  // (only then are the frames read)
+    if (frames_read) {
         sl.in(tracks->frame_of_scene, S, &a.frame_of_scene);
         sl.in(batch->nx, (size_t)batch->F, &a.nx);
         sl.in(batch->knots, fn, &a.knots);
         sl.in(batch->coef, fn * 8, &a.coef);
     }
     sl.out(final_time_step, S, &a.final_time_step);
-    sl.temp(S * span * n * 4, &a.obs_pose);  // [S][span][n_obs][4]: a scene's written rows from its row 0 on
-    FP_TRY(hs.commit(sl));
-    a.compact = 1;
-    LAUNCH_TRY(fp::launch_obstacles_predict(a, ctx->stream), "obstacle prediction kernel");
+    // a host call predicts into a compact temporary, [S][span][n_obs][4]: a scene's written rows from its row 0 on; a device call into the table
+    if (call.host()) { sl.temp(S * span * n * 4, &a.obs_pose); a.compact = 1; }
+    else a.obs_pose = obs_pose;
+    FP_TRY(call.commit());
+    LAUNCH_TRY(fp::launch_obstacles_predict(a, call.stream()), "obstacle prediction kernel");
     ++ctx->predict_launches;
+    if (!call.host()) return FP_OK;
     // only the written rows travel back; runs that are contiguous on both sides (whole tables) go as one copy
     const double* src = nullptr;
     double* dst = nullptr;
@@ -2128,11 +2110,11 @@ int fp_obstacles_predict(fp_ctx* ctx, const fp_params* params, const fp_batch* b
             run += count;
             continue;
         }
-        if (run) HIP_TRY(hipMemcpyAsync(dst, src, run * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        if (run) HIP_TRY(hipMemcpyAsync(dst, src, run * sizeof(double), hipMemcpyDeviceToHost, call.stream()));
         src = sc_src; dst = sc_dst; run = count;
     }
-    if (run) HIP_TRY(hipMemcpyAsync(dst, src, run * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    return hs.fetch_out();
+    if (run) HIP_TRY(hipMemcpyAsync(dst, src, run * sizeof(double), hipMemcpyDeviceToHost, call.stream()));
+    return call.finish();
 }
 
 int fp_obstacles_from_plans(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, const fp_agents* agents, const int32_t* best_idx,
@@ -2163,57 +2145,52 @@ int fp_obstacles_from_plans(fp_ctx* ctx, const fp_params* params, const fp_batch
     ka.r = no_result();
     fp::AgentArgs a;
     a.G = agents->G; a.n_members = agents->n_members; a.col_base = agents->col_base; a.n_rows = agents->n_rows; a.tail = agents->tail;
-    if (mem == FP_MEM_DEVICE) {
-        if ((uintptr_t)obs_pose & 15u) return fail(FP_EINVAL, "fp_obstacles_from_plans: obs_pose must be 16-byte aligned");
-        ka.b = *batch;
-        a.group_ptr = agents->group_ptr; a.members = agents->members; a.best_idx = best_idx; a.end_state = end_state;
-        a.obs_pose = obs_pose; a.final_time_step = final_time_step;
-        LAUNCH_TRY(fp::launch_obstacles_from_plans(ka, a, (hipStream_t)stream), "shared-plans kernel");
-        ++ctx->from_plans_launches;
-        return FP_OK;
-    }
-    // host arrays: what the device path decides silently is an error the host path can name
+    CallStage call(ctx, mem, stream);
     const int G = agents->G, B = batch->B;
-    if (agents->group_ptr[0] != 0) return fail(FP_EINVAL, "fp_obstacles_from_plans: group_ptr[0]=%d must be 0", agents->group_ptr[0]);
-    for (int g = 0; g < G; ++g) {
-        const int lo = agents->group_ptr[g], hi = agents->group_ptr[g + 1];
-        if (hi < lo) return fail(FP_EINVAL, "fp_obstacles_from_plans: group_ptr is not ascending at group %d (%d > %d)", g, lo, hi);
-        if ((long)agents->col_base + (hi - lo) > batch->n_obs)
-            return fail(FP_EINVAL, "fp_obstacles_from_plans: group %d: col_base + group size = %d + %d exceeds n_obs = %d", g, agents->col_base, hi - lo, batch->n_obs);
-    }
-    if (agents->group_ptr[G] != agents->n_members)
-        return fail(FP_EINVAL, "fp_obstacles_from_plans: n_members=%d is not group_ptr[G]=%d", agents->n_members, agents->group_ptr[G]);
-    FP_TRY(check_frames_host(batch));
-    {
-        std::vector<int32_t> group_of((size_t)B, -1), member_of((size_t)(batch->S > 0 ? batch->S : 0), -1);
-        for (int g = 0; g < G; ++g)
-            for (int k = agents->group_ptr[g]; k < agents->group_ptr[g + 1]; ++k) {
-                const int e = agents->members[k];
-                if (e < 0 || e >= B) return fail(FP_EINVAL, "fp_obstacles_from_plans: member %d of group %d is ego %d, outside 0 .. B-1 (B=%d)", k - agents->group_ptr[g], g, e, B);
-                if (group_of[e] >= 0) return fail(FP_EINVAL, "fp_obstacles_from_plans: ego %d is a member of group %d and of group %d", e, group_of[e], g);
-                group_of[e] = g;
-                const int sc = batch->scene_of[e];
-                if (sc < 0) return fail(FP_EINVAL, "fp_obstacles_from_plans: member %d of group %d (ego %d) has no scene (scene_of = %d)", k - agents->group_ptr[g], g, e, sc);
-                if (sc >= batch->S) return fail(FP_EINVAL, "scene_of[%d]=%d out of range", e, sc);
-                if (member_of[sc] >= 0) return fail(FP_EINVAL, "fp_obstacles_from_plans: ego %d and ego %d share scene %d (every member needs a scene of its own)", member_of[sc], e, sc);
-                member_of[sc] = e;
-            }
-    }
-    const size_t nB = (size_t)B;
-    if (best_idx) {
-        const long n_cand = (long)params->nd * params->nv * params->nt;
-        for (int i = 0; i < B; ++i)
-            if (best_idx[i] >= n_cand && !(batch->skip && batch->skip[i]))
-                return fail(FP_EINVAL, "fp_obstacles_from_plans: best_idx of ego %d = %d is outside the lattice (nd*nv*nt = %ld)", i, best_idx[i], n_cand);
-        ka.p.points_max = host_points_max(params, batch, nullptr, 0, 0);
-    } else {
-        ka.p.points_max = host_points_max(params, batch, end_state + 2, nB, 3);
-    }
-    const size_t S = (size_t)batch->S, fn = (size_t)batch->F * batch->NX;
+    const size_t nB = (size_t)B, S = (size_t)batch->S, fn = (size_t)batch->F * batch->NX;
     ka.b = *batch;
-    ka.b.obs_pose = nullptr; ka.b.obs_dims = nullptr; ka.b.final_time_step = nullptr; ka.b.obs_poly = nullptr; ka.b.obs_nvert = nullptr; ka.b.launch_order = nullptr;
-    HostStage hs(ctx);
-    StageList sl;
+    if (!call.host()) {
+        if ((uintptr_t)obs_pose & 15u) return fail(FP_EINVAL, "fp_obstacles_from_plans: obs_pose must be 16-byte aligned");
+    } else {
+        // host arrays: what the device path decides silently is an error the host path can name
+        if (agents->group_ptr[0] != 0) return fail(FP_EINVAL, "fp_obstacles_from_plans: group_ptr[0]=%d must be 0", agents->group_ptr[0]);
+        for (int g = 0; g < G; ++g) {
+            const int lo = agents->group_ptr[g], hi = agents->group_ptr[g + 1];
+            if (hi < lo) return fail(FP_EINVAL, "fp_obstacles_from_plans: group_ptr is not ascending at group %d (%d > %d)", g, lo, hi);
+            if ((long)agents->col_base + (hi - lo) > batch->n_obs)
+                return fail(FP_EINVAL, "fp_obstacles_from_plans: group %d: col_base + group size = %d + %d exceeds n_obs = %d", g, agents->col_base, hi - lo, batch->n_obs);
+        }
+        if (agents->group_ptr[G] != agents->n_members)
+            return fail(FP_EINVAL, "fp_obstacles_from_plans: n_members=%d is not group_ptr[G]=%d", agents->n_members, agents->group_ptr[G]);
+        FP_TRY(check_frames_host(batch));
+        {
+            std::vector<int32_t> group_of(nB, -1), member_of((size_t)(batch->S > 0 ? batch->S : 0), -1);
+            for (int g = 0; g < G; ++g)
+                for (int k = agents->group_ptr[g]; k < agents->group_ptr[g + 1]; ++k) {
+                    const int e = agents->members[k];
+                    if (e < 0 || e >= B) return fail(FP_EINVAL, "fp_obstacles_from_plans: member %d of group %d is ego %d, outside 0 .. B-1 (B=%d)", k - agents->group_ptr[g], g, e, B);
+                    if (group_of[e] >= 0) return fail(FP_EINVAL, "fp_obstacles_from_plans: ego %d is a member of group %d and of group %d", e, group_of[e], g);
+                    group_of[e] = g;
+                    const int sc = batch->scene_of[e];
+                    if (sc < 0) return fail(FP_EINVAL, "fp_obstacles_from_plans: member %d of group %d (ego %d) has no scene (scene_of = %d)", k - agents->group_ptr[g], g, e, sc);
+                    if (sc >= batch->S) return fail(FP_EINVAL, "scene_of[%d]=%d out of range", e, sc);
+                    if (member_of[sc] >= 0) return fail(FP_EINVAL, "fp_obstacles_from_plans: ego %d and ego %d share scene %d (every member needs a scene of its own)", member_of[sc], e, sc);
+                    member_of[sc] = e;
+                }
+        }
+        if (best_idx) {
+            const long n_cand = (long)params->nd * params->nv * params->nt;
+            for (int i = 0; i < B; ++i)
+                if (best_idx[i] >= n_cand && !(batch->skip && batch->skip[i]))
+                    return fail(FP_EINVAL, "fp_obstacles_from_plans: best_idx of ego %d = %d is outside the lattice (nd*nv*nt = %ld)", i, best_idx[i], n_cand);
+            ka.p.points_max = host_points_max(params, batch, nullptr, 0, 0);
+        } else {
+            ka.p.points_max = host_points_max(params, batch, end_state + 2, nB, 3);
+        }
+        // (of the batch only what the kernel reads travels; the table itself is the call's in / out array)
+        ka.b.obs_pose = nullptr; ka.b.obs_dims = nullptr; ka.b.final_time_step = nullptr; ka.b.obs_poly = nullptr; ka.b.obs_nvert = nullptr; ka.b.launch_order = nullptr;
+    }
+    StageList& sl = call.list();
     stage_samples(sl, params, batch, &ka.b.d_samples, &ka.b.t_samples, &ka.b.v_samples);
     sl.in(batch->ego, nB * 6, &ka.b.ego);
     sl.in(batch->frame_of, nB, &ka.b.frame_of);
@@ -2228,10 +2205,10 @@ int fp_obstacles_from_plans(fp_ctx* ctx, const fp_params* params, const fp_batch
     if (best_idx) sl.in(best_idx, nB, &a.best_idx); else sl.in(end_state, nB * 3, &a.end_state);
     sl.in_mut(obs_pose, S * (size_t)batch->T_obs * batch->n_obs * 4, &a.obs_pose);
     if (final_time_step) sl.in_mut(final_time_step, S, &a.final_time_step);
-    FP_TRY(hs.commit(sl));
-    LAUNCH_TRY(fp::launch_obstacles_from_plans(ka, a, ctx->stream), "shared-plans kernel");
+    FP_TRY(call.commit());
+    LAUNCH_TRY(fp::launch_obstacles_from_plans(ka, a, call.stream()), "shared-plans kernel");
     ++ctx->from_plans_launches;
-    return hs.fetch_out();
+    return call.finish();
 }
 
 int fp_materialize_all(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, uint32_t* flags, double* traj, int32_t traj_stride,
@@ -2250,26 +2227,21 @@ int fp_materialize_all(fp_ctx* ctx, const fp_params* params, const fp_batch* bat
     ka.r = no_result();
     ka.r.traj_stride = traj_stride;
     ka.r.traj_sparse = traj_sparse;
-    if (mem == FP_MEM_DEVICE) {
-        ka.b = *batch;
-        ka.r.best_flags = flags;
-        ka.r.best_traj = traj;
-        LAUNCH_TRY(fp::launch_materialize_all(ka, (hipStream_t)stream), "materialise kernel");
-        return FP_OK;
+    CallStage call(ctx, mem, stream);
+    if (call.host()) {
+        FP_TRY(check_batch_host(params, batch));
+        FP_TRY(check_stride_host(params, batch, stride));
+        ka.p.points_max = host_points_max(params, batch, nullptr, 0, 0);
     }
-    FP_TRY(check_batch_host(params, batch));
-    FP_TRY(check_stride_host(params, batch, stride));
-    ka.p.points_max = host_points_max(params, batch, nullptr, 0, 0);
-    HostStage hs(ctx);
-    StageList sl;
+    StageList& sl = call.list();
     StageRegime rg;  // (throughput)
-    FP_TRY(stage_batch(ctx, sl, rg, params, batch, &ka.b));
+    FP_TRY(stage_batch(ctx, call, rg, params, batch, &ka.b, DeviceView::AS_GIVEN));
     sl.out(flags, BC, &ka.r.best_flags);
     sl.out(traj, traj_doubles, &ka.r.best_traj);
-    FP_TRY(hs.commit(sl, rg));
-    if (traj_sparse) HIP_TRY(hipMemcpyAsync(ka.r.best_traj, traj, traj_doubles * sizeof(double), hipMemcpyDefault, ctx->stream));
-    LAUNCH_TRY(fp::launch_materialize_all(ka, ctx->stream), "materialise kernel");
-    return hs.fetch_out();
+    FP_TRY(call.commit(rg));
+    if (call.host() && traj_sparse) HIP_TRY(hipMemcpyAsync(ka.r.best_traj, traj, traj_doubles * sizeof(double), hipMemcpyDefault, call.stream()));  // (see fp_winner_trajs)
+    LAUNCH_TRY(fp::launch_materialize_all(ka, call.stream()), "materialise kernel");
+    return call.finish();
 }
 
 }  // extern "C"
@@ -2298,7 +2270,8 @@ int plan_fiss_impl(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, 
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t B = (size_t)batch->B, C = (size_t)params->nd * params->nv * params->nt;
     const int R = opts->kind == FP_FISS_PLUS ? opts->max_refine_iters : 0;
-    hipStream_t stream = mem == FP_MEM_DEVICE ? (hipStream_t)stream_v : ctx->stream;
+    CallStage call(ctx, mem, stream_v);
+    hipStream_t stream = call.stream();
     FP_TRY(handover_check(ctx, stream));
     // (host entry: prev_best_idx is in / out - should the appended search of this call time out, the call is repeated from the caller's values)
     std::vector<int32_t> prev_in;
@@ -2355,8 +2328,7 @@ int plan_fiss_impl(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, 
     FP_TRY(traj_stride_of(io->traj_stride, &stride));
     const size_t traj_doubles = io->best_traj ? B * FP_ARR_COUNT * (size_t)stride : 0;
     const size_t trace_doubles = (io->trace && R > 0) ? B * (size_t)R * 7 * 4 : 0;
-    HostStage hs(ctx);
-    StageList sl;
+    StageList& sl = call.list();
     fp::InlineIn inl;   // (host entry, latency regime: see below)
     fp_batch lat_b;     // the batch as the lattice kernel addresses it (byte offsets into inl.bytes when inl.on)
     if (mem == FP_MEM_DEVICE) {
@@ -2406,7 +2378,7 @@ int plan_fiss_impl(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, 
         sl.out(io->trace, trace_doubles, &fa.io.trace);
         sl.out(io->best_flags, B, &fa.io.best_flags);
         sl.out(io->best_traj, traj_doubles, &fa.io.best_traj);
-        FP_TRY(hs.commit(sl, rg));
+        FP_TRY(call.commit(rg));
         if (inl.on) inline_publish(inl, &fa.ka.b, ex, 3);
         else fa.ka.b = lat_b;
         if (io->traj_sparse && fa.io.best_traj) HIP_TRY(hipMemcpyAsync(fa.io.best_traj, io->best_traj, traj_doubles * sizeof(double), hipMemcpyDefault, ctx->stream));
@@ -2422,16 +2394,16 @@ int plan_fiss_impl(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, 
     fp::LatticeResult lr;
     FP_TRY(lattice_step(ctx, params, batch, kl, stream, inl.on ? 2 : ctx->lattice_kernel, mem == FP_MEM_DEVICE ? batch->launch_order : nullptr,
                         inl.on ? &inl : nullptr, ft.flag ? &ft : nullptr, &lr));
-    if (ctx->fiss_stages < 2) return mem == FP_MEM_HOST ? hs.fetch_out() : FP_OK;  // timing diagnostic: outputs are not produced
+    if (ctx->fiss_stages < 2) return call.finish();  // timing diagnostic: outputs are not produced
     fa.walk_jump = ctx->fiss_jump;
     if (rules) {
         // the table passes of the rules that are on, in the order they run (rules.TABLE): the launches a dense call's caller makes behind
         // it, over the same tables - the search reads the words the FOP chain leaves
         const fp_batch& db = fa.ka.b;
         const int32_t* perm = host ? nullptr : batch->launch_order;
+        StageList on_device(/*pass_through=*/true);  // (the call's batch and the scratch tables: device addresses in either space)
         auto pass_args = [&](fp::TablePassArgs* a) {
-            table_pass_args(a, params, &db, fa.cost_tbl, fa.ka.r.flag_tbl, pass_idx, pass_cost, pass_count);
-            a->perm = perm;
+            table_pass_declare(on_device, a, params, &db, perm, fa.cost_tbl, fa.ka.r.flag_tbl, pass_idx, pass_cost, pass_count, [](StageList&) {});
         };
         if (ra.on & FP_RULE_LIMIT) {
             fp::EnvelopeArgs a;
@@ -2489,7 +2461,7 @@ int plan_fiss_impl(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, 
     }
     if (loop && !handed_over) LAUNCH_TRY(fp::launch_advance(fa.ka, nullptr, fa.io.end_state, *loop, stream), "advance kernel");  // (FISS, or no refinement rounds)
     if (mem != FP_MEM_HOST) return FP_OK;
-    FP_TRY(hs.fetch_out());
+    FP_TRY(call.finish());
     if (handover_failed(ctx)) {  // (see fp_plan_dense)
         (void)handover_recover(ctx, ctx->stream);
         if (!prev_in.empty()) memcpy(io->prev_best_idx, prev_in.data(), prev_in.size() * sizeof(int32_t));
@@ -2553,22 +2525,19 @@ int fp_advance(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, cons
     fp::KernelArgs ka;
     ka.p = *params;
     ka.r = no_result();
-    if (mem == FP_MEM_DEVICE) {
-        ka.b = *batch;
-        LAUNCH_TRY(fp::launch_advance(ka, best_idx, end_state, *io, (hipStream_t)stream), "advance kernel");
-        return FP_OK;
+    CallStage call(ctx, mem, stream);
+    if (call.host()) {
+        FP_TRY(check_batch_host(params, batch));
+        if (best_idx) {  // (the kernel decodes the index of every running ego and reads d_samples / t_samples / v_samples with it; negative = no solution)
+            const long n_cand = (long)params->nd * params->nv * params->nt;
+            for (int i = 0; i < batch->B; ++i)
+                if (io->done[i] == FP_RUNNING && best_idx[i] >= n_cand)
+                    return fail(FP_EINVAL, "fp_advance: best_idx[%d]=%d is not below nd*nv*nt=%ld", i, best_idx[i], n_cand);
+        }
     }
-    FP_TRY(check_batch_host(params, batch));
-    if (best_idx) {  // (the kernel decodes the index of every running ego and reads d_samples / t_samples / v_samples with it; negative = no solution)
-        const long n_cand = (long)params->nd * params->nv * params->nt;
-        for (int i = 0; i < batch->B; ++i)
-            if (io->done[i] == FP_RUNNING && best_idx[i] >= n_cand)
-                return fail(FP_EINVAL, "fp_advance: best_idx[%d]=%d is not below nd*nv*nt=%ld", i, best_idx[i], n_cand);
-    }
-    HostStage hs(ctx);
-    StageList sl;
+    StageList& sl = call.list();
     StageRegime rg;  // (throughput)
-    FP_TRY(stage_batch(ctx, sl, rg, params, batch, &ka.b));
+    FP_TRY(stage_batch(ctx, call, rg, params, batch, &ka.b, DeviceView::AS_GIVEN));
     fp_loop_io dio = *io;
     sl.in_mut(io->ego, B * 6, &dio.ego);
     sl.in_mut(io->t_now, B, &dio.t_now);
@@ -2580,17 +2549,17 @@ int fp_advance(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, cons
         sl.in(io->goal_nv, B, &dio.goal_nv);
         if (io->goal_intervals) sl.in(io->goal_intervals, B * 6, &dio.goal_intervals);
     } else {
-        dio.goal_poly = nullptr;
+        dio.goal_poly = nullptr;  // (check_loop_io: a polygon without its counts never gets here)
     }
     const int32_t* d_idx = nullptr;
     const double* d_es = nullptr;
     if (best_idx) sl.in(best_idx, B, &d_idx);
     if (end_state) sl.in(end_state, B * 3, &d_es);
     sl.out(io->cart_state, B * 3, &dio.cart_state);
-    FP_TRY(hs.commit(sl, rg));
-    if (dio.cart_state) HIP_TRY(hipMemsetAsync(dio.cart_state, 0xFF, sizeof(double) * B * 3, ctx->stream));  // NaN for egos that do not move
-    LAUNCH_TRY(fp::launch_advance(ka, d_idx, d_es, dio, ctx->stream), "advance kernel");
-    return hs.fetch_out();
+    FP_TRY(call.commit(rg));
+    if (call.host() && dio.cart_state) HIP_TRY(hipMemsetAsync(dio.cart_state, 0xFF, sizeof(double) * B * 3, call.stream()));  // NaN for egos that do not move
+    LAUNCH_TRY(fp::launch_advance(ka, d_idx, d_es, dio, call.stream()), "advance kernel");
+    return call.finish();
 }
 
 int fp_loop_record(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, const fp_loop_io* io, const int32_t* best_idx,
@@ -2609,21 +2578,13 @@ int fp_loop_record(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, 
     const size_t B = (size_t)batch->B;
     fp::LoopLogArgs a;
     a.B = batch->B; a.nv = params->nv; a.nt = params->nt;
-    if (mem == FP_MEM_DEVICE) {
-        // (a lane stores its row as 16-byte words and moves a Stats row as one)
-        if (((uintptr_t)log->rows | (uintptr_t)stats | (uintptr_t)log->row_stats) & 15u)
-            return fail(FP_EINVAL, "fp_loop_record: rows / stats / row_stats must be 16-byte aligned");
-        a.d_samples = batch->d_samples; a.v_samples = batch->v_samples; a.t_samples = batch->t_samples;
-        a.io = *io; a.best_idx = best_idx; a.end_state = end_state; a.best_cost = best_cost; a.stats = stats; a.log = *log;
-        if (log->n_running) HIP_TRY(hipMemsetAsync(log->n_running, 0, sizeof(int32_t), (hipStream_t)stream));
-        LAUNCH_TRY(fp::launch_loop_record(a, (hipStream_t)stream), "loop-log kernel");
-        ++ctx->looplog_launches;
-        return FP_OK;
-    }
-    // host arrays: only what the kernel reads travels (the three sample arrays of the batch, the loop state, the step's results, the log)
+    CallStage call(ctx, mem, stream);
+    // (a lane stores its row as 16-byte words and moves a Stats row as one: a device caller's arrays have to allow it)
+    if (!call.host() && (((uintptr_t)log->rows | (uintptr_t)stats | (uintptr_t)log->row_stats) & 15u))
+        return fail(FP_EINVAL, "fp_loop_record: rows / stats / row_stats must be 16-byte aligned");
+    // only what the kernel reads travels (the three sample arrays of the batch, the loop state, the step's results, the log)
     const size_t R = (size_t)log->max_rows;
-    HostStage hs(ctx);
-    StageList sl;
+    StageList& sl = call.list();
     stage_samples(sl, params, batch, &a.d_samples, &a.t_samples, &a.v_samples);
     a.io = *io;  // (the kernel only reads the loop state)
     a.log = *log;
@@ -2642,11 +2603,11 @@ int fp_loop_record(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, 
     sl.in_mut(log->sealed, B, &a.log.sealed);
     if (log->stats_sum) sl.in_mut(log->stats_sum, B * 4, &a.log.stats_sum);
     sl.out(log->n_running, 1, &a.log.n_running);
-    FP_TRY(hs.commit(sl));
-    if (a.log.n_running) HIP_TRY(hipMemsetAsync(a.log.n_running, 0, sizeof(int32_t), ctx->stream));
-    LAUNCH_TRY(fp::launch_loop_record(a, ctx->stream), "loop-log kernel");
+    FP_TRY(call.commit());
+    if (a.log.n_running) HIP_TRY(hipMemsetAsync(a.log.n_running, 0, sizeof(int32_t), call.stream()));
+    LAUNCH_TRY(fp::launch_loop_record(a, call.stream()), "loop-log kernel");
     ++ctx->looplog_launches;
-    return hs.fetch_out();
+    return call.finish();
 }
 
 int fp_plan_step(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, const fp_result* result, const fp_loop_io* io, int mem, void* stream)
@@ -2700,15 +2661,12 @@ int fp_frames_build(fp_ctx* ctx, int32_t F, int32_t NX, const int32_t* n, const 
     if (mem != FP_MEM_HOST && mem != FP_MEM_DEVICE) return fail(FP_EINVAL, "mem must be FP_MEM_HOST or FP_MEM_DEVICE");
     if (F == 0) return FP_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    if (mem == FP_MEM_DEVICE) {
-        LAUNCH_TRY(fp::launch_frames_build(F, NX, n, points, knots, coef, (hipStream_t)stream), "frame build");
-        return FP_OK;
-    }
-    for (int f = 0; f < F; ++f)
-        if (n[f] < 2 || n[f] > NX) return fail(FP_EINVAL, "n[%d]=%d out of range", f, n[f]);
+    CallStage call(ctx, mem, stream);
+    if (call.host())
+        for (int f = 0; f < F; ++f)
+            if (n[f] < 2 || n[f] > NX) return fail(FP_EINVAL, "n[%d]=%d out of range", f, n[f]);
     const size_t fn = (size_t)F * NX;
-    HostStage hs(ctx);
-    StageList sl;
+    StageList& sl = call.list();
     const int32_t* d_n = nullptr;
     const double* d_pts = nullptr;
     double* d_k = nullptr;
@@ -2717,9 +2675,9 @@ int fp_frames_build(fp_ctx* ctx, int32_t F, int32_t NX, const int32_t* n, const 
     sl.in(points, fn * 2, &d_pts);
     sl.out(knots, fn, &d_k);
     sl.out(coef, fn * 8, &d_c);
-    FP_TRY(hs.commit(sl));
-    LAUNCH_TRY(fp::launch_frames_build(F, NX, d_n, d_pts, d_k, d_c, ctx->stream), "frame build");
-    return hs.fetch_out();
+    FP_TRY(call.commit());
+    LAUNCH_TRY(fp::launch_frames_build(F, NX, d_n, d_pts, d_k, d_c, call.stream()), "frame build");
+    return call.finish();
 }
 
 int fp_from_state(fp_ctx* ctx, const fp_batch* batch, const double* states, double* ego, int mem, void* stream)
@@ -2731,26 +2689,23 @@ int fp_from_state(fp_ctx* ctx, const fp_batch* batch, const double* states, doub
     if (mem != FP_MEM_HOST && mem != FP_MEM_DEVICE) return fail(FP_EINVAL, "mem must be FP_MEM_HOST or FP_MEM_DEVICE");
     if (batch->B == 0) return FP_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    if (mem == FP_MEM_DEVICE) {
-        LAUNCH_TRY(fp::launch_from_state(*batch, states, ego, (hipStream_t)stream), "from_state");
-        ++ctx->from_state_launches;
-        return FP_OK;
-    }
+    CallStage call(ctx, mem, stream);
     const size_t B = (size_t)batch->B, fn = (size_t)batch->F * batch->NX;
-    FP_TRY(check_frames_host(batch));
-    // host arrays: what the device path answers with a NaN row is an error the host path can name, before anything is launched
-    // (only the frames some ego sits on are looked at, as fp_obstacles_predict does for its LANE tracks)
-    for (size_t b = 0; b < B; ++b) {
-        static const char* const kName[4] = {"x", "y", "yaw", "v"};
-        for (int k = 0; k < 4; ++k)
-            if (!fp::finite_f64(states[b * 4 + k])) return fail(FP_EINVAL, "fp_from_state: ego %zu: %s=%g is not finite", b, kName[k], states[b * 4 + k]);
-        const int32_t f = batch->frame_of[b];
-        const double s_last = batch->knots[(size_t)f * batch->NX + batch->nx[f] - 1];
-        if (fp::project_point_count(s_last) == 0)
-            return fail(FP_EINVAL, "fp_from_state: ego %zu sits on frame %d, whose line of length %g has fewer than two resampled points (0.1 m apart)", b, f, s_last);
+    if (call.host()) {
+        FP_TRY(check_frames_host(batch));
+        // host arrays: what the device path answers with a NaN row is an error the host path can name, before anything is launched
+        // (only the frames some ego sits on are looked at, as fp_obstacles_predict does for its LANE tracks)
+        for (size_t b = 0; b < B; ++b) {
+            static const char* const kName[4] = {"x", "y", "yaw", "v"};
+            for (int k = 0; k < 4; ++k)
+                if (!fp::finite_f64(states[b * 4 + k])) return fail(FP_EINVAL, "fp_from_state: ego %zu: %s=%g is not finite", b, kName[k], states[b * 4 + k]);
+            const int32_t f = batch->frame_of[b];
+            const double s_last = batch->knots[(size_t)f * batch->NX + batch->nx[f] - 1];
+            if (fp::project_point_count(s_last) == 0)
+                return fail(FP_EINVAL, "fp_from_state: ego %zu sits on frame %d, whose line of length %g has fewer than two resampled points (0.1 m apart)", b, f, s_last);
+        }
     }
-    HostStage hs(ctx);
-    StageList sl;
+    StageList& sl = call.list();
     fp_batch db = *batch;
     sl.in(batch->frame_of, B, &db.frame_of);
     sl.in(batch->nx, (size_t)batch->F, &db.nx);
@@ -2760,10 +2715,10 @@ int fp_from_state(fp_ctx* ctx, const fp_batch* batch, const double* states, doub
     double* d_ego = nullptr;
     sl.in(states, B * 4, &d_states);
     sl.out(ego, B * 6, &d_ego);
-    FP_TRY(hs.commit(sl));
-    LAUNCH_TRY(fp::launch_from_state(db, d_states, d_ego, ctx->stream), "from_state");
+    FP_TRY(call.commit());
+    LAUNCH_TRY(fp::launch_from_state(db, d_states, d_ego, call.stream()), "from_state");
     ++ctx->from_state_launches;
-    return hs.fetch_out();
+    return call.finish();
 }
 
 int fp_eval_trajs(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, int32_t K, const double* end_states, double* cost,
@@ -2779,36 +2734,34 @@ int fp_eval_trajs(fp_ctx* ctx, const fp_params* params, const fp_batch* batch, i
     fp::KernelArgs ka;
     ka.p = *params;
     ka.r = no_result();
-    if (mem == FP_MEM_DEVICE) {
-        ka.b = device_batch(batch);
-        LAUNCH_TRY(fp::launch_eval_trajs(ka, K, end_states, cost, flags, traj, stride, traj_sparse, (hipStream_t)stream), "eval kernel");
-        return FP_OK;
+    CallStage call(ctx, mem, stream);
+    if (call.host()) {
+        FP_TRY(check_batch_host(params, batch));
+        for (size_t i = 0; i < BK; ++i) {
+            const double n = end_states[3 * i + 2] / params->tick_t;
+            if (n != n) continue;  // NaN end state = "no trajectory": the kernels emit NaN cost / all-NaN series
+            if (!(n > 0) || n > FP_MAX_POINTS) return fail(FP_ELIMIT, "end_states[%zu].T=%g needs 1..FP_MAX_POINTS points", i, end_states[3 * i + 2]);
+            if (traj && ceil(n) > stride) return fail(FP_EINVAL, "traj_stride=%d is smaller than the %g points of end_states[%zu].T=%g", stride, ceil(n), i, end_states[3 * i + 2]);
+        }
+        ka.p.points_max = host_points_max(params, batch, end_states + 2, BK, 3);
     }
-    FP_TRY(check_batch_host(params, batch));
-    for (size_t i = 0; i < BK; ++i) {
-        const double n = end_states[3 * i + 2] / params->tick_t;
-        if (n != n) continue;  // NaN end state = "no trajectory": the kernels emit NaN cost / all-NaN series
-        if (!(n > 0) || n > FP_MAX_POINTS) return fail(FP_ELIMIT, "end_states[%zu].T=%g needs 1..FP_MAX_POINTS points", i, end_states[3 * i + 2]);
-        if (traj && ceil(n) > stride) return fail(FP_EINVAL, "traj_stride=%d is smaller than the %g points of end_states[%zu].T=%g", stride, ceil(n), i, end_states[3 * i + 2]);
-    }
-    ka.p.points_max = host_points_max(params, batch, end_states + 2, BK, 3);
     const size_t traj_doubles = traj ? BK * FP_ARR_COUNT * (size_t)stride : 0;
-    HostStage hs(ctx);
-    StageList sl;
+    StageList& sl = call.list();
     StageRegime rg;  // (throughput)
-    FP_TRY(stage_batch(ctx, sl, rg, params, batch, &ka.b));
+    FP_TRY(stage_batch(ctx, call, rg, params, batch, &ka.b, DeviceView::NO_OBS_WITHOUT_SCENES));
     const double* d_end = nullptr;
     double* d_cost = nullptr;
     uint32_t* d_flags = nullptr;
     double* d_traj = nullptr;
     sl.in(end_states, BK * 3, &d_end);
-    if (cost) sl.out(cost, BK, &d_cost); else sl.temp(BK, &d_cost);  // (the kernel writes both whether or not the caller wants them)
+    // (the kernel writes both on a host call whether or not the caller wants them; a device call's temporaries are NULL: what the caller passed)
+    if (cost) sl.out(cost, BK, &d_cost); else sl.temp(BK, &d_cost);
     if (flags) sl.out(flags, BK, &d_flags); else sl.temp(BK, &d_flags);
     sl.out(traj, traj_doubles, &d_traj);
-    FP_TRY(hs.commit(sl, rg));
-    if (traj_sparse && d_traj) HIP_TRY(hipMemcpyAsync(d_traj, traj, traj_doubles * sizeof(double), hipMemcpyDefault, ctx->stream));
-    LAUNCH_TRY(fp::launch_eval_trajs(ka, K, d_end, d_cost, d_flags, d_traj, stride, traj_sparse, ctx->stream), "eval kernel");
-    return hs.fetch_out();
+    FP_TRY(call.commit(rg));
+    if (call.host() && traj_sparse && d_traj) HIP_TRY(hipMemcpyAsync(d_traj, traj, traj_doubles * sizeof(double), hipMemcpyDefault, call.stream()));  // (see fp_winner_trajs)
+    LAUNCH_TRY(fp::launch_eval_trajs(ka, K, d_end, d_cost, d_flags, d_traj, stride, traj_sparse, call.stream()), "eval kernel");
+    return call.finish();
 }
 
 }  // extern "C"

@@ -36,8 +36,8 @@ inline RulesEvalArgs rule_args(const fp_rule_set& rules)
     return a;
 }
 
-// FP_MEM_HOST: the arrays of the rules that are on, declared for staging in the passes' order ([F][NX] limits; [F][gate_stride] lines,
-// [F][T_gate] words; [F][NX] edges); each gets its device address at commit
+// The arrays of the rules that are on, declared in the call's list in the passes' order ([F][NX] limits; [F][gate_stride] lines,
+// [F][T_gate] words; [F][NX] edges): a host call's get their device addresses at commit, a device call's keep the caller's
 inline void stage_rule_arrays(StageList& sl, RulesEvalArgs* a, int F, int NX)
 {
     const size_t fn = (size_t)F * NX;
@@ -63,7 +63,7 @@ inline int gate_points_cap(const fp_params& p, bool host, int host_points)
     return n > FP_FAST_POINTS ? n : FP_FAST_POINTS;
 }
 
-// The rule's own fields of each pass block (the TablePassArgs part is table_pass_args', frenet_abi.hip).  coef, t_now, d_samples: the
+// The rule's own fields of each pass block (the TablePassArgs part is table_pass_declare's, frenet_abi.hip).  coef, t_now, d_samples: the
 // batch's arrays as the launch addresses them; coef is read by the lateral check alone.
 inline void envelope_args(EnvelopeArgs* a, const RulesEvalArgs& r, const double* coef)
 {

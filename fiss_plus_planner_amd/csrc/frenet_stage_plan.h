@@ -1,7 +1,8 @@
-// frenet_stage_plan.h - where the arrays of one FP_MEM_HOST call go.  An entry point declares its arrays once, as a StageList;
-// plan_stage decides region and offset of every one of them, the output window and the arena's size; HostStage::commit
-// (frenet_abi.hip) is the one executor.  Host-side arithmetic only: no HIP call, no allocation (tests/test_stage_plan_cpu.py prints
-// plans on a machine without a GPU).
+// frenet_stage_plan.h - where the arrays of one call go.  An entry point declares its arrays once, as a StageList, whatever the call's
+// memory space.  FP_MEM_HOST: the list stages - plan_stage decides region and offset of every array, the output window and the arena's
+// size, and CallStage::commit (frenet_abi.hip) is the one executor.  FP_MEM_DEVICE: the list passes through - every declaration hands the
+// caller's address to the kernel's argument at once and nothing is recorded.  Host-side arithmetic only: no HIP call, no allocation
+// (tests/test_stage_plan_cpu.py prints plans on a machine without a GPU).
 #pragma once
 
 #include <cstddef>
@@ -37,9 +38,15 @@ constexpr int kStageCap = 72;
 struct StageList {
     StageItem item[kStageCap];
     int n = 0;  // items declared; beyond kStageCap nothing is stored and commit refuses the list
+    // Pass-through (an FP_MEM_DEVICE call: the arrays are where the kernels read them): in / in_mut / out store the given address in
+    // *dev - NULL for NULL, what plan_stage gives an output nobody asked for -, temp stores NULL (such a call has no arena), and no
+    // item is recorded: n stays 0.
+    const bool pass_through;
 
+    explicit StageList(bool pass_through_ = false) : pass_through(pass_through_) {}
     void add(StageKind kind, const void* host, size_t bytes, void** dev)
     {
+        if (pass_through) { *dev = const_cast<void*>(host); return; }
         if (n < kStageCap) item[n] = StageItem{kind, const_cast<void*>(host), bytes, dev};
         ++n;
     }
@@ -130,7 +137,7 @@ inline StagePlan plan_stage(const StageList& l, const StageRegime& rg)
     return pl;
 }
 
-// Every placed item inside its region and the arena (HostStage::commit refuses a plan that fails this: a planner bug is an error code,
+// Every placed item inside its region and the arena (CallStage::commit refuses a plan that fails this: a planner bug is an error code,
 // never an overrun).
 inline bool stage_plan_inside(const StageList& l, const StagePlan& pl)
 {

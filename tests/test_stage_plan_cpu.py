@@ -32,7 +32,7 @@ _DENSE_OUT1 = "out:4 out:8 out:16 out:1000 out:500 out:4 out:16384 null:8 null:4
 _FISS_IN1 = "in:24 in:24 in:24 mut:12"
 _FISS_OUT1 = "out:12 out:8 out:24 out:4 out:16 out:672 out:4 out:16384"
 
-# name, "resident" or "-", the declared list: in / mut (IN_MUT) / out / null (OUT with a NULL host pointer) / temp : bytes
+# name, "resident" or "-" ("through": a pass-through list, see the tests at the end), the declared list: in / mut (IN_MUT) / out / null (OUT with a NULL host pointer) / temp : bytes
 CASES = [
     ("small_max", "-", f"in:{SMALL_MAX} in:{SMALL_MAX + 1} out:{SMALL_MAX} out:{SMALL_MAX + 1}"),
     ("latency_in_max", "-", f"in:{ZC_IN_MAX} in:{ZC_IN_MAX + 1} out:8"),
@@ -62,7 +62,7 @@ using namespace fp;
 int main()
 {
     static char line[1 << 16];
-    static unsigned char dummy;
+    static unsigned char dummy[1024], poison;
     static void* dev[1024];
     static const char* kRegime[] = {"thr", "lat0", "lat1", "lat2"};
     static const char kRegion[] = {'-', 'P', 'W', 'L'};
@@ -70,20 +70,28 @@ int main()
         char* save;
         const char* name = strtok_r(line, " \n", &save);
         if (!name) continue;
-        const bool resident = strcmp(strtok_r(nullptr, " \n", &save), "resident") == 0;
-        StageList l;
-        for (char* t; (t = strtok_r(nullptr, " \n", &save));) {
+        const char* flag = strtok_r(nullptr, " \n", &save);
+        const bool resident = strcmp(flag, "resident") == 0, through = strcmp(flag, "through") == 0;
+        StageList l(through);
+        if (through) std::printf("%s through", name);
+        int k = 0;
+        for (char* t; (t = strtok_r(nullptr, " \n", &save)); ++k) {
             char* c = strchr(t, ':');
             *c = 0;
             const size_t bytes = strtoull(c + 1, nullptr, 10);
-            void** d = &dev[l.n % 1024];
-            if (strcmp(t, "in") == 0) l.add(StageKind::IN, &dummy, bytes, d);
-            else if (strcmp(t, "mut") == 0) l.add(StageKind::IN_MUT, &dummy, bytes, d);
-            else if (strcmp(t, "out") == 0) l.add(StageKind::OUT, &dummy, bytes, d);
+            void** d = &dev[k % 1024];
+            void* host = &dummy[k % 1024];  // (every declaration its own address)
+            *d = &poison;
+            if (strcmp(t, "in") == 0) l.add(StageKind::IN, host, bytes, d);
+            else if (strcmp(t, "mut") == 0) l.add(StageKind::IN_MUT, host, bytes, d);
+            else if (strcmp(t, "out") == 0) l.add(StageKind::OUT, host, bytes, d);
             else if (strcmp(t, "null") == 0) l.add(StageKind::OUT, nullptr, bytes, d);
             else if (strcmp(t, "temp") == 0) l.add(StageKind::TEMP, nullptr, bytes, d);
             else return 1;
+            // pass-through: what the declaration stored - the given address, NULL, or nothing / something else
+            if (through) std::printf(" %c", *d == host ? '=' : *d == nullptr ? '0' : '?');
         }
+        if (through) { std::printf(" n=%d overflow=%d\n", l.n, (int)l.overflow()); continue; }
         if (l.overflow()) { std::printf("%s overflow n=%d\n", name, l.n); continue; }
         for (int r = 0; r < 4; ++r) {
             StageRegime rg;
@@ -267,3 +275,20 @@ def test_stage_plan_invariants(driver):
 def test_stage_list_overflow_is_reported(driver):
     rows = _rows(driver, [("fits", "-", " ".join(["in:8"] * STAGE_CAP)), ("too_long", "-", " ".join(["in:8"] * (STAGE_CAP + 1)))])
     assert len(rows) == len(REGIMES) + 1 and rows[0].startswith("fits thr") and rows[-1] == f"too_long overflow n={STAGE_CAP + 1}"
+
+
+_ODDS = next(ops for name, _, ops in CASES if name == "odds_and_ends")
+
+
+def test_pass_through_list_hands_the_addresses_on(driver):
+    """A pass-through list (an FP_MEM_DEVICE call) over the odds_and_ends sequence: every in / mut / out stores the address it was given,
+    whatever its length; the output nobody asked for and every temp store NULL; nothing is recorded."""
+    row, = _rows(driver, [("odds", "through", _ODDS)])
+    want = ["0" if op.split(":")[0] in ("null", "temp") else "=" for op in _ODDS.split()]
+    assert want.count("0") == 3 and row.split() == ["odds", "through"] + want + ["n=0", "overflow=0"]
+
+
+def test_pass_through_list_never_overflows(driver):
+    row, = _rows(driver, [("long", "through", " ".join([_ODDS] * 6))])
+    tok = row.split()
+    assert len(tok) - 4 == 6 * len(_ODDS.split()) > STAGE_CAP and "?" not in tok[2:-2] and tok[-2:] == ["n=0", "overflow=0"]
