@@ -674,6 +674,14 @@ __device__ __forceinline__ double wave_min_f64(double v)
     v = row16_min(v);
     return vmin_f64(vmin_f64(lane_value(v, 0), lane_value(v, 16)), vmin_f64(lane_value(v, 32), lane_value(v, 48)));
 }
+// Orders the LDS accesses of ONE wavefront for the compiler (the hardware executes a wavefront's LDS instructions in program order):
+// what lanes wrote before it, other lanes of the same wavefront read after it.  No instruction is emitted.
+__device__ __forceinline__ void wave_lds_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
 struct Best {
     double cost;
     int idx;

@@ -19,6 +19,8 @@
 //
 // Restated: fiss_planner.py:33-99 (cost_est), :101-138 (generate_trajectory -> table lookup), :140-188, :190-270;
 //           fiss_plus_planner.py:30-59, :80-148.
+#include <type_traits>
+
 #include "frenet_device.h"
 #include "frenet_kernels.h"
 #include "frenet_winner.h"
@@ -48,13 +50,6 @@ struct RankSet {
         return (L << 6) + (lo ? __ffs((int)lo) - 1 : 32 + __ffs((int)hi) - 1);
     }
 };
-
-__device__ __forceinline__ void wave_lds_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // Sort (key[i], idx[i]), i < n (any n <= P, P a power of two), ascending by key, ties by idx, by the W wavefronts of a workgroup.
 // Bitonic network in the form whose compare-exchanges ALL put the smaller element at the lower index (a merge starts with the
@@ -637,9 +632,7 @@ __device__ uint32_t wave_traj_flags(const KernelArgs& ka, int b, const double* e
     if (M < N) flags |= FP_FLAG_TRUNCATED;
     flags |= ((uint32_t)N << FP_FLAG_N_SHIFT) | ((uint32_t)M << FP_FLAG_M_SHIFT);
     if (p.curvature_mask && M >= 2) {  // optional checks (:145-150): they read the points this wavefront just wrote
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
         flags |= wave_curvature_flags<NCH>(p, L.xy, M, lane);
     }
     // collision (frenet_optimal_planner.py:168-195)
@@ -650,9 +643,7 @@ __device__ uint32_t wave_traj_flags(const KernelArgs& ka, int b, const double* e
     const int horizon_cap = L.horizon_cap;
     if (M == 1 && horizon_cap >= 1) return flags | FP_FLAG_COLLISION;  // traj.yaw is empty -> IndexError -> collision (:178-182)
     if (M < 2) return flags;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     const double* scene = bt.obs_pose + (size_t)sc * bt.T_obs * n_obs * 4;
     const double* gd = bt.obs_dims + (size_t)sc * n_obs * 2;
     const double veh_hl = 0.5 * p.veh_l, veh_hw = 0.5 * p.veh_w;
@@ -747,9 +738,7 @@ __device__ uint32_t wave_traj_flags(const KernelArgs& ka, int b, const double* e
             // survivors are tested as soon as a trip leaves any (the table is in time order: a trajectory that collides early is
             // done before the rest of its horizon is scanned)
             if (qn > 0) {
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                wave_lds_sync();
                 bool hit = false;
                 int hit_e = -1;
                 for (int slot = lane; slot < qn; slot += kWave) {  // survivors: exact fp64 test, their pose reads in flight together
@@ -799,151 +788,25 @@ __device__ uint32_t wave_traj_flags(const KernelArgs& ka, int b, const double* e
     return flags;
 }
 
-// ---- fp_plan_fiss_rules: the enforced rules on a popped candidate (fiss_refine_rules_kernel)
-// The rules' tables in LDS, staged once per ego beside the spline as rules_eval_kernel stages them.
-struct RuleLds {
-    double* lim;                // [nx] the limit of the segment that starts at the knot
-    double *l0, *l1, *r0, *r1;  // [NX] each: the corridor's edge and slope per segment and side (stage_corridor)
-    double* line;               // [FP_MAX_GATES] gate lines, NaN for a slot that is unused or waived
-    uint32_t* word;             // [points_cap] closed words of the steps t_now + 1 ..
-    double* dim;                // [n_obs][4] obstacle sizes as stage_ego leaves them (EgoCtx::obs_dim)
-};
-// doubles of those tables (host and device agree on the layout: lim | l0 l1 r0 r1 | line, word | dim)
-__host__ __device__ inline int rule_lds_doubles(uint32_t on, int NX, int cap, int n_obs)
+// ---- fp_plan_fiss_rules: the ego as the rules of frenet_rules.h read it, behind the refinement's layout.  The spline is L's; dim = the
+// obstacle sizes [n_obs][4] as stage_ego leaves them, which the kernel stages behind the rules' tables; no obstacle rows in LDS - the fp32
+// pair table of the refinement holds same-time rows only, so the gaps' rows come from the scene table (obs_row).
+__device__ __forceinline__ EgoCtx refine_ego_ctx(const fp_batch& bt, const RefineLds& L, const double* eg, int nx, const double* dim)
 {
-    int n = 0;
-    if (on & FP_RULE_LIMIT) n += NX;
-    if (on & FP_RULE_BOUNDARY) n += 4 * NX;
-    if (on & FP_RULE_GATE) n += FP_MAX_GATES + (cap + 1) / 2;
-    if (on & FP_RULE_GAP) n += 4 * n_obs;
-    return n;
-}
-__device__ __forceinline__ RuleLds rule_lds(double* base, uint32_t on, int NX, int cap)
-{
-    RuleLds T;
-    T.lim = base;
-    if (on & FP_RULE_LIMIT) base += NX;
-    T.l0 = base; T.l1 = T.l0 + NX; T.r0 = T.l1 + NX; T.r1 = T.r0 + NX;
-    if (on & FP_RULE_BOUNDARY) base += 4 * NX;
-    T.line = base;
-    T.word = (uint32_t*)(T.line + FP_MAX_GATES);
-    if (on & FP_RULE_GATE) base += FP_MAX_GATES + (cap + 1) / 2;
-    T.dim = base;
-    return T;
-}
-
-// The word fp_rules_eval leaves for the end state x whose word on entry is fl (the trajectory's own, without an FP_FLAG_INFEASIBLE bit),
-// computed by the whole wavefront with the predicates of frenet_rules.h: the rules in the order the passes run, lanes on the points
-// 1 + lane, 65 + lane, ... < M, every verdict a ballot, a rule ends on its first hit, the gaps (rows through obs_row from the scene
-// table) only when the word is still feasible after the other three.  All arguments wave-uniform.
-__device__ __forceinline__ uint32_t wave_rule_word(const KernelArgs& ka, const RulesEvalArgs& a, const RuleLds& T, const RefineLds& L, int b, const double* eg, const double* x,
-                                   uint32_t fl, int nx, int lane)
-{
-    const fp_params& p = ka.p;
-    const fp_batch& bt = ka.b;
-    const bool envelope = a.on & FP_RULE_LIMIT, gates = a.on & FP_RULE_GATE, boundary = a.on & FP_RULE_BOUNDARY, gaps = a.on & FP_RULE_GAP;
-    const int lateral = (a.on & FP_RULE_LATERAL) ? 1 : 0;
-    const int cap = points_cap(p), t_last = a.T_gate - 1;
-    const double tick = p.tick_t;
-    const double d_end = x[0], v_end = x[1], T_end = x[2];
-    int M = (int)(fl >> FP_FLAG_M_SHIFT);
-    const int N = (T_end == T_end) ? arange_len(T_end, tick) : 0;
-    if (N <= 0 || N > cap || !(d_end == d_end) || !(v_end == v_end) || M <= 1) return fl;  // no trajectory, or nothing to check
-    if (M > N) M = N;
-    const SplineLds sp{L.knots, L.coef, nx, nx};
-    const double guess_scale = (double)(nx - 1) / (sp.knots[nx - 1] - sp.knots[0]);
-    const Quintic lat = quintic_bvp(eg[3], eg[4], eg[5], d_end, 0.0, 0.0, T_end);
-    const Quartic lon = quartic_bvp(eg[0], eg[1], eg[2], v_end, 0.0, T_end);
-    const double hl = 0.5 * p.veh_l, hw = 0.5 * p.veh_w;
-    uint32_t word_new = fl;
-    if (envelope) {
-        const uint32_t env_want = FP_FLAG_SPEED | (lateral ? FP_FLAG_ACCEL : 0u);
-        uint32_t bits = 0u;
-        for (int i0 = 1; i0 < M; i0 += kWave) {
-            const int i = i0 + lane;
-            bool fast = false, lat_v = false;
-            if (i < M) envelope_point(sp, T.lim, guess_scale, lon, (double)i * tick, a.env_front, a.env_tol, lateral, a.max_lat_accel, fast, lat_v);
-            if (__ballot(fast)) bits |= FP_FLAG_SPEED;
-            if (__ballot(lat_v)) bits |= FP_FLAG_ACCEL;
-            if (bits == env_want) break;  // every bit the rule can give is found
-        }
-        word_new |= bits;
-    }
-    if (gates) {
-        const uint32_t live = (uint32_t)__ballot(lane < FP_MAX_GATES && T.line[lane < FP_MAX_GATES ? lane : 0] == T.line[lane < FP_MAX_GATES ? lane : 0]);
-        const uint32_t* closed = a.closed + (size_t)bt.frame_of[b] * a.T_gate;
-        const double q0 = eg[0] + a.gate_front;
-        const long long tn = L.t_now;
-        for (int i0 = 1; i0 < M && live != 0u; i0 += kWave) {
-            const int i = i0 + lane;
-            bool hit = false;
-            if (i < M) {
-                const uint32_t w = (i <= cap ? T.word[i - 1] : gate_word(closed, tn + i, t_last)) & live;
-                if (w) hit = gate_point(lon, i, tick, a.gate_front, q0, w, T.line);
-            }
-            if (__ballot(hit)) {
-                word_new |= FP_FLAG_SPEED;
-                break;
-            }
-        }
-    }
-    if (boundary) {
-        bool out = false;
-        for (int i0 = 1; i0 < M; i0 += kWave) {
-            const int i = i0 + lane;
-            bool viol = false;
-            if (i < M) viol = boundary_point(sp, T.l0, T.l1, T.r0, T.r1, guess_scale, lon, lat, (double)i * tick, hw, hl, a.margin);
-            if (__ballot(viol)) {  // one violation decides the trajectory
-                out = true;
-                break;
-            }
-        }
-        word_new = (word_new & ~FP_FLAG_BOUNDARY) | (out ? FP_FLAG_BOUNDARY : 0u);
-    }
-    if (gaps && !(word_new & FP_FLAG_INFEASIBLE)) {
-        const int cs = p.check_stride;
-        const int Lf = a.lag_follow / cs, Ll = a.lag_lead / cs;  // the lags in grid steps: only pairs on the grid exist
-        EgoCtx e;
-        e.s0 = eg[0]; e.s_d0 = eg[1]; e.s_dd0 = eg[2]; e.d0 = eg[3]; e.d_d0 = eg[4]; e.d_dd0 = eg[5];
-        e.target_speed = 0.0;
-        e.sp = sp;
-        e.obs_lds = nullptr;  // (the fp32 pair table of the refinement holds same-time rows only: the rows come from the scene table)
-        e.obs_dim = T.dim;
-        e.n_obs = L.scene >= 0 ? bt.n_obs : 0;
-        e.T_obs = bt.T_obs;
-        e.rows = 0;
-        e.t_now = L.t_now;
-        e.horizon_cap = e.n_obs > 0 ? L.horizon_cap : 0;
-        e.col0 = (size_t)(L.scene >= 0 ? L.scene : 0) * bt.n_obs;
-        e.obs_glb = e.n_obs > 0 ? bt.obs_pose + (size_t)L.scene * bt.T_obs * bt.n_obs * 4 : nullptr;
-        const int G = gap_grid_poses(p, e);
-        if (G > 0 && (Lf > 0 || Ll > 0)) {
-            const double r_e = sqrt(fma(hl, hl, hw * hw));
-            const int q_first = (a.first - 1) / cs + 1 < G ? (a.first - 1) / cs + 1 : G;
-            // poses i = 0, cs, 2 cs, ... < min(M, final_time_step - t_now) inside the table: grid poses q < n_pose
-            const int limit = M < e.horizon_cap ? M : e.horizon_cap;
-            int n_pose = limit > 0 ? (limit + cs - 1) / cs : 0;
-            if (G < n_pose) n_pose = G;
-            if (q_first < n_pose) {
-                constexpr int kSplitMax = 8;  // at most this many lanes share one pose's columns (rules_eval_kernel's kRulesSplit)
-                int split = 1;
-                while (split < kSplitMax && (n_pose - q_first) * split * 2 <= kWave) split *= 2;
-                const int per_round = kWave / split, sub = lane & (split - 1);
-                for (int qb = q_first; qb < n_pose; qb += per_round) {
-                    const int q = qb + lane / split, i = q * cs;
-                    bool hit = false;
-                    Obb ego;
-                    if (q < n_pose && i + e.t_now >= 0 && checked_pose(p, e.sp, guess_scale, lon, lat, i, M, ego))
-                        hit = gap_pose_hit(ka, e, ego, q, n_pose, Lf, Ll, sub, split, nullptr, r_e, cs, e.n_obs);
-                    if (__ballot(hit)) {
-                        word_new |= FP_FLAG_COLLISION;
-                        break;  // the one bit the rule can give is found
-                    }
-                }
-            }
-        }
-    }
-    return word_new;
+    EgoCtx e;
+    e.s0 = eg[0]; e.s_d0 = eg[1]; e.s_dd0 = eg[2]; e.d0 = eg[3]; e.d_d0 = eg[4]; e.d_dd0 = eg[5];
+    e.target_speed = 0.0;
+    e.sp = SplineLds{L.knots, L.coef, nx, nx};
+    e.obs_lds = nullptr;
+    e.obs_dim = dim;
+    e.n_obs = L.scene >= 0 ? bt.n_obs : 0;
+    e.T_obs = bt.T_obs;
+    e.rows = 0;
+    e.t_now = L.t_now;
+    e.horizon_cap = e.n_obs > 0 ? L.horizon_cap : 0;
+    e.col0 = (size_t)(L.scene >= 0 ? L.scene : 0) * bt.n_obs;
+    e.obs_glb = e.n_obs > 0 ? bt.obs_pose + (size_t)L.scene * bt.T_obs * bt.n_obs * 4 : nullptr;
+    return e;
 }
 
 }  // namespace
@@ -966,22 +829,414 @@ __host__ __device__ constexpr int refine_lds_bytes(int NX, int pt_entries, int p
 #endif
 // NCH = 2: trajectories of up to 128 points (three workgroups per CU); NCH = 4: up to FP_MAX_POINTS = 256 (tick_t below ~0.04 s at the default
 // horizons: twice the per-wavefront point scratch, two workgroups per CU - the register budget of a loop nest twice as deep).
-template <int NCH>
-__global__ __launch_bounds__(kWave * kRefineWaves, NCH == 2 ? FP_REFINE_OCC : 2) void fiss_refine_kernel(FissArgs fa, int pt_rows_max, const int* perm, int* dur)
+// Args = FissArgs: fp_plan_fiss / fp_plan_fiss_step.  Args = FissRulesArgs (fp_plan_fiss_rules): a popped candidate whose own word is
+// feasible is also checked against the enforced rules (frenet_rules.h) by the wavefront that validated it, and the loop consumes the
+// resulting word - FP_FLAG_BOUNDARY counting as a constraint bit.  The rules' tables are staged beside the spline by the staging
+// wavefronts, behind the refinement's own LDS layout (fa.rules_off).  Two workgroups per CU for those instances: the predicates'
+// registers come on top of a kernel that is at its budget at three.
+template <int NCH, class Args>
+__global__ __launch_bounds__(kWave * kRefineWaves, (std::is_same<Args, FissRulesArgs>::value ? 2 : (NCH == 2 ? FP_REFINE_OCC : 2))) void fiss_refine_kernel(
+    Args fa, int pt_rows_max, const int* perm, int* dur)
 {
-#define FP_REFINE_RULES 0
-#include "frenet_fiss_refine_body.h"
-#undef FP_REFINE_RULES
-}
-
-// The rule instances (fp_plan_fiss_rules).  Two workgroups per CU: the predicates' registers come on top of a kernel that is at its budget
-// at three.
-template <int NCH>
-__global__ __launch_bounds__(kWave * kRefineWaves, 2) void fiss_refine_rules_kernel(FissRulesArgs fa, int pt_rows_max, const int* perm, int* dur)
-{
-#define FP_REFINE_RULES 1
-#include "frenet_fiss_refine_body.h"
-#undef FP_REFINE_RULES
+    constexpr bool kRules = std::is_same<Args, FissRulesArgs>::value;
+    constexpr int kPts = NCH * kWave;  // points per trajectory this instance holds
+#if defined(FP_PHASE_STAMPS)
+    const long long t_begin = wall_clock64();
+#else
+    const long long t_begin = dur ? wall_clock64() : 0;
+#endif
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const KernelArgs& ka = fa.ka;
+    const fp_params& p = ka.p;
+    const fp_batch& bt = ka.b;
+    const int b = perm ? perm[blockIdx.x] : (int)blockIdx.x;  // launch order: longest egos first when the host has one
+    // Timing diagnostic (tools/refine_stamps.py, -DFP_PHASE_STAMPS): thread 0 leaves 10 ns ticks since the workgroup started in
+    // columns 112.. of the last row of the ego's series block (sparse layout, stride 128); column 112 = the absolute start.
+#if defined(FP_PHASE_STAMPS)
+#define FP_RSTAMP(k) do { if (threadIdx.x == 0 && fa.io.best_traj) fa.io.best_traj[((size_t)b * FP_ARR_COUNT + 15) * fa.io.traj_stride + 112 + (k)] = (k) == 0 ? (double)(t_begin & 0xFFFFFFFFFFll) : (double)(wall_clock64() - t_begin); } while (0)
+#else
+#define FP_RSTAMP(k) do { } while (0)
+#endif
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+    constexpr int kThreads = kWave * kRefineWaves;
+    const int32_t* ijk = fa.io.best_ijk + (size_t)b * 3;
+    const int R = fa.opts.max_refine_iters;
+    if (ijk[0] < 0 || R <= 0) {  // nothing found by the coarse search: plan() returns None
+        if (tid == 0 && dur) dur[b] = 0;
+        if (fa.io.best_traj) {   // NaN series, flag word 0
+            KernelArgs kw = ka;
+            kw.r.best_traj = fa.io.best_traj;
+            kw.r.best_flags = fa.io.best_flags;
+            kw.r.traj_stride = fa.io.traj_stride;
+            kw.r.traj_sparse = fa.io.traj_sparse;
+            const double none = __builtin_nan("");
+            if (wave == 0) winner_series_wave(kw, b, b, false, none, none, none, lane, SplineLds{nullptr, nullptr, 0, 0});
+        }
+        // fp_plan_fiss_step: the hand-over of an ego without a trajectory (R > 0: with R == 0 this kernel is not launched) - "no solution"
+        if (ka.has_loop && tid == 0 && R > 0) {
+            int off = (int)offsetof(FissArgs, ka);
+            asm volatile("" : "+s"(off) : : "memory");
+            const KernelArgs& kl = *(const KernelArgs*)((const unsigned char*)__builtin_amdgcn_kernarg_segment_ptr() + off);
+            const double none = __builtin_nan("");
+            advance_ego_to(kl, b, none, none, none, kl.loop);
+        }
+        return;
+    }
+    const int f = bt.frame_of[b];
+    const int nx = bt.nx[f];
+    const int verdict_off = refine_lds_bytes(bt.NX, pt_rows_max * bt.n_obs, kPts) - 32 - kRefineWaves * 2 * kQueue - 4 * (kHot + 4);
+    RefineLds L;
+    L.S = (double*)smem;
+    L.xy = (double2*)(L.S + kRefineS) + wave * kPts;  // one Cartesian scratch row per wavefront
+    L.xyf = (float2*)(L.S + kRefineS + 2 * kPts * kRefineWaves) + wave * kPts;
+    L.knots = L.S + refine_spline_off(kPts);
+    L.queue = (uint16_t*)(smem + verdict_off + 32) + wave * kQueue;
+    L.hot = (int*)(smem + verdict_off + 32 + kRefineWaves * 2 * kQueue);  // [kHot] pairs + [1] count
+    if (tid == 0) L.hot[kHot] = 0;  // (the barrier behind the rounds orders it before the first validation)
+    L.coef = L.knots + nx;
+    // Order of the prologue: wavefront 0 runs the refinement rounds (they only need the ego state: the power sums of a probe's
+    // horizon come in closed form) WHILE wavefronts 1..3 stage the spline and the pair table; then the candidate list goes through
+    // LDS to every wavefront.  The rounds are ~half of the kernel's instructions: running them once instead of
+    // four times is what matters (the kernel is instruction-issue bound), hiding them behind the staging is a bonus.
+    const double* gk = bt.knots + (size_t)f * bt.NX;
+    const double* gc = bt.coef + (size_t)f * 8 * bt.NX;
+    L.pt = nullptr;
+    L.ox = gc[0];                       // x, y of the first knot
+    L.oy = gc[(size_t)4 * bt.NX];
+    const int sc0 = bt.scene_of[b];
+    L.scene = sc0;
+    L.t_now = bt.t_now[b];
+    L.horizon_cap = sc0 >= 0 ? bt.final_time_step[sc0] - L.t_now : 0;
+    int pt_rows = 0;
+    if (sc0 >= 0 && bt.n_obs > 0 && pt_rows_max > 0) {
+        int h = L.horizon_cap;
+        if (h > kPts) h = kPts;
+        if (h > bt.T_obs - L.t_now) h = bt.T_obs - L.t_now;
+        pt_rows = h > 0 ? (h + p.check_stride - 1) / p.check_stride : 0;  // <= pt_rows_max by construction
+        L.pt = (float4*)(L.S + refine_pt_off(bt.NX, kPts));
+    }
+    const double nan = __builtin_nan("");
+    double eg[6];
+#pragma unroll
+    for (int m = 0; m < 6; ++m) eg[m] = bt.ego[(size_t)b * 6 + m];
+    const double target_speed = bt.target_speed[b];
+    double x[3], res[3], lo[3], hi[3];
+#pragma unroll
+    for (int m = 0; m < 3; ++m) {
+        x[m] = fa.io.end_state[(size_t)b * 3 + m];
+        res[m] = fa.io.samp_res[(size_t)b * 3 + m];
+        lo[m] = fa.io.samp_min[(size_t)b * 3 + m];
+        hi[m] = fa.io.samp_max[(size_t)b * 3 + m];
+    }
+    const double coarse_x[3] = {x[0], x[1], x[2]};
+    double* cand = (double*)(smem + verdict_off + 32);  // [64][4] + {ncand, coarse cost}: the queues' bytes, free until validation
+    if (wave > 0) {
+        const int stid = tid - kWave;
+        constexpr int kStagers = kThreads - kWave;
+        for (int i = stid; i < nx; i += kStagers) L.knots[i] = gk[i];
+        for (int i = stid; i < 8 * nx; i += kStagers) {
+            const int r = i / nx, c = i - r * nx;
+            L.coef[r * nx + c] = gc[(size_t)r * bt.NX + c];
+        }
+        // fp32 broad-phase table of every (checked row, obstacle) pair the collision horizon can touch, once per ego: the
+        // validation loop may visit the same pair for up to 21 trajectories
+        if (L.pt) {
+            const int t0 = L.t_now;
+            const double* scene = bt.obs_pose + (size_t)sc0 * bt.T_obs * bt.n_obs * 4;
+            const double* gd = bt.obs_dims + (size_t)sc0 * bt.n_obs * 2;
+            const double veh_hl = 0.5 * p.veh_l, veh_hw = 0.5 * p.veh_w;
+            const double r_ego = sqrt(fma(veh_hl, veh_hl, veh_hw * veh_hw));
+            for (int e = stid; e < pt_rows * bt.n_obs; e += kStagers) {
+                const int r = e / bt.n_obs, j = e - r * bt.n_obs;
+                const double4 ps = *(const double4*)(scene + ((size_t)(r * p.check_stride + t0) * bt.n_obs + j) * 4);
+                const double hl = 0.5 * gd[2 * j], hw = 0.5 * gd[2 * j + 1];
+                const double rx = ps.x - L.ox, ry = ps.y - L.oy;
+                // padding: 1 cm + 2e-6 of the coordinate magnitude dwarfs the fp32 rounding of rx, ry, the pose and the sum
+                const double R = r_ego + sqrt(fma(hl, hl, hw * hw)) + 1e-2 + 2e-6 * (fabs(rx) + fabs(ry));
+                float R2 = (float)(R * R * (1.0 + 1e-5));
+                if (ps.w == 0.0 || !(R2 >= 0.0f)) R2 = -1.0f;  // absent at this step (or NaN size): never passes
+                L.pt[e] = make_float4((float)rx, (float)ry, R2, __int_as_float((r * p.check_stride) | (j << 8)));
+            }
+        }
+        if constexpr (kRules) {
+            // the rules' own tables (stage_rule_tables, the stagers numbered from 0; the mask of the live gates goes to a spare word of the
+            // hot list's block), and behind them the obstacle sizes the gaps read, in the place of stage_ego's table
+            const RulesEvalArgs& a = fa.rules;
+            double* tab = (double*)(smem + fa.rules_off);
+            double* dim = tab + rule_table_doubles(a.on, p, bt.NX);
+            stage_rule_tables(ka, a, b, refine_ego_ctx(bt, L, eg, nx, dim), tab, (uint32_t*)(L.hot + kHot + 1), stid, wave - 1, lane, kStagers);
+            if ((a.on & FP_RULE_GAP) && sc0 >= 0 && bt.n_obs > 0) {
+                const double* gd = bt.obs_dims + (size_t)sc0 * bt.n_obs * 2;
+                for (int j = stid; j < bt.n_obs; j += kStagers) {
+                    const double hl = 0.5 * gd[2 * j], hw = 0.5 * gd[2 * j + 1];
+                    dim[4 * j] = hl;
+                    dim[4 * j + 1] = hw;
+                    dim[4 * j + 2] = sqrt(fma(hl, hl, hw * hw));
+                    dim[4 * j + 3] = 0.0;
+                }
+            }
+        }
+#if defined(FP_RABL) && FP_RABL == 3  // timing ablation: staging only
+    } else if (false) {
+#else
+    } else {
+#endif
+        // The evaluations form a dependent chain (~2.3 us each on a lone wavefront), so the cost of the CURRENT point x rides along
+        // with the six probes around it (lanes >= 6 price x itself): that is the coarse winner's cost in round 0 and the previous
+        // round's step afterwards - R + 1 evaluations in the chain instead of 2 R + 1.
+        double coarse_cost0 = nan;
+        bool have_coarse = false;
+        int pending = -1;  // the lane whose trajectory (= x) still waits for its cost
+        double my_x[3] = {nan, nan, nan}, my_cost = nan;  // lane c = refinement trajectory c (generation order)
+        int ncand = 0;
+        for (int r = 0; r < R; ++r) {
+            // lanes 0..5: the six probes, lane 6: x itself (role 0: longitudinal half + recombination); lanes 8..14: their lateral halves
+            const int pk = lane & 7, dim = pk >> 1;
+            double xp[3] = {x[0], x[1], x[2]};
+            if (pk < 6) {
+                xp[dim] += (pk & 1) ? res[dim] : -res[dim];
+#pragma unroll
+                for (int m = 0; m < 3; ++m) xp[m] = fmin(fmax(xp[m], lo[m]), hi[m]);  // np.clip
+            }
+            const bool bad = lane < 6 && (!(xp[0] == xp[0]) || !(xp[1] == xp[1]) || !(xp[2] == xp[2]));
+            if (__ballot(bad)) break;
+            const double cp = analytic_cost_two_lanes(p, eg, target_speed, xp, (lane >> 3) & 1, kPts);  // valid in lanes 0..6 (6: the cost of x itself)
+            {
+                const double cx0 = __shfl(cp, 6, kWave);
+                if (!have_coarse) { coarse_cost0 = cx0; have_coarse = true; }
+                if (lane == pending) my_cost = cx0;
+                pending = -1;
+            }
+            for (int k = 0; k < 6; ++k) {  // hand probe k to lane ncand + k
+                const double c = __shfl(cp, k, kWave), a0 = __shfl(xp[0], k, kWave), a1 = __shfl(xp[1], k, kWave), a2 = __shfl(xp[2], k, kWave);
+                if (lane == ncand + k) { my_cost = c; my_x[0] = a0; my_x[1] = a1; my_x[2] = a2; }
+            }
+            ncand += 6;
+            double g[3], nrm2 = 0.0;
+#pragma unroll
+            for (int m = 0; m < 3; ++m) {
+                const double Jl = __shfl(cp, 2 * m, kWave), Jr = __shfl(cp, 2 * m + 1, kWave);
+                const double xl = __shfl(xp[m], 2 * m, kWave), xr = __shfl(xp[m], 2 * m + 1, kWave);
+                g[m] = (Jr - Jl) / (xr - xl);
+                nrm2 += g[m] * g[m];
+            }
+            const double nrm = sqrt(nrm2);
+            double xn[3];
+            bool nan_step = false;
+#pragma unroll
+            for (int m = 0; m < 3; ++m) {
+                res[m] *= fa.opts.decaying_factor;  // decays in place, like the reference's aliasing of sampling_res (:282)
+                xn[m] = x[m] - res[m] * g[m] / nrm;
+                xn[m] = fmin(fmax(xn[m], lo[m]), hi[m]);
+                nan_step |= !(xn[m] == xn[m]);
+            }
+            if (nan_step) break;  // zero gradient: the reference raises inside np.arange(nan); refinement stops here
+            if (lane == ncand) { my_x[0] = xn[0]; my_x[1] = xn[1]; my_x[2] = xn[2]; }
+            pending = ncand;  // priced with the next round's probes, or below
+            ncand += 1;
+            x[0] = xn[0]; x[1] = xn[1]; x[2] = xn[2];
+        }
+        if (!have_coarse || pending >= 0) {  // (x is the coarse winner while no round got as far as its evaluation)
+            const double cl = analytic_cost(p, eg, target_speed, x, L.S, kPts);
+            if (!have_coarse) coarse_cost0 = cl;
+            if (lane == pending) my_cost = cl;
+        }
+        cand[lane * 4] = my_x[0]; cand[lane * 4 + 1] = my_x[1]; cand[lane * 4 + 2] = my_x[2]; cand[lane * 4 + 3] = my_cost;
+        if (lane == 0) { cand[4 * kWave] = (double)ncand; cand[4 * kWave + 1] = coarse_cost0; }
+    }
+    if (wave == 0) FP_RSTAMP(1);
+    __syncthreads();
+    FP_RSTAMP(2);
+    double my_x[3] = {cand[lane * 4], cand[lane * 4 + 1], cand[lane * 4 + 2]};  // lane c = refinement trajectory c (generation order)
+    const double my_cost = cand[lane * 4 + 3];
+    const int ncand = (int)cand[4 * kWave];
+    const double coarse_cost = cand[4 * kWave + 1];
+    __syncthreads();  // the queues take their bytes back
+#if defined(FP_RABL) && FP_RABL == 1  // timing ablation: rounds + staging only
+    return;
+#endif
+    // refined_trajs.get() in cost order (ties: generation order), :301-323.  Every wavefront holds the same candidate list;
+    // the next kRefineWaves trajectories in pop order are checked SPECULATIVELY side
+    // by side, one whole wavefront each, and the verdicts are then consumed in pop order exactly like the sequential loop -
+    // validated / checks count only what the reference would have popped before its first collision-free trajectory.
+    uint32_t* verdict = (uint32_t*)(smem + verdict_off);  // [2][kRefineWaves], double-buffered across groups
+    int validated = 0, checks = 0, winner = -1;
+    // The rule instances: [2][kRefineWaves] beside the verdicts, in the 32 bytes in front of the rules' tables: 1 = the rules rejected a
+    // candidate its own word passes; `rejected` counts the consumed ones.  What wave_rules_eval takes beside the trajectory is made
+    // once per ego, here behind the barriers that follow the staging (per popped candidate it costs rules<2> 68 bytes of stack).
+    uint32_t* rule_verdict = nullptr;
+    int rejected = 0;
+    [[maybe_unused]] EgoCtx rule_ego;
+    [[maybe_unused]] RuleTables rule_tabs;
+    [[maybe_unused]] RuleConsts rule_c;
+    if constexpr (kRules) {
+        double* tab = (double*)(smem + fa.rules_off);
+        rule_verdict = (uint32_t*)tab - 2 * kRefineWaves;
+        rule_ego = refine_ego_ctx(bt, L, eg, nx, tab + rule_table_doubles(fa.rules.on, p, bt.NX));
+        rule_tabs = rule_tables(ka, fa.rules, b, tab);
+        rule_c = rule_consts(ka, fa.rules, rule_ego, (const uint32_t*)(L.hot + kHot + 1));
+    }
+    bool alive = lane < ncand;
+    // Pop order = ascending (cost, generation index): a strict total order unless a cost is NaN, so every lane counts the
+    // candidates in front of its own once (register reads, no cross-lane reduction per pop: four 6-step butterflies cost ~1.2 us
+    // of every group).  With a NaN cost in the list the butterfly below decides, as it always did.
+    int rank = kWave;
+    const bool ranked = !__ballot(alive && !(my_cost == my_cost));
+    if (ranked) {
+        rank = 0;
+        for (int j = 0; j < ncand; ++j) {
+            const double cj = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(my_cost), j), __builtin_amdgcn_readlane(__double2loint(my_cost), j));
+            rank += (cj < my_cost || (cj == my_cost && j < lane)) ? 1 : 0;
+        }
+        if (!alive) rank = kWave;
+    }
+    bool open = true;  // (ranked pops) nothing has ended the loop yet
+    for (int grp = 0; winner < 0; ++grp) {
+        int pop[kRefineWaves];
+        if (ranked) {
+#pragma unroll
+            for (int u = 0; u < kRefineWaves; ++u) {
+                const unsigned long long m = __ballot(rank == grp * kRefineWaves + u);
+                int bl = (open && m) ? __ffsll((long long)m) - 1 : -1;
+                if (bl >= 0) {
+                    const double bc = __shfl(my_cost, bl, kWave);
+                    if (bc > coarse_cost) bl = -1;  // `cost > coarse cost` ends the loop (:303-304)
+                }
+                if (bl < 0) open = false;
+                pop[u] = bl;
+            }
+        } else
+#pragma unroll
+        for (int u = 0; u < kRefineWaves; ++u) {
+            double bc = alive ? my_cost : __builtin_inf();
+            int bl = alive ? lane : kWave;
+#pragma unroll
+            for (int off = kWave / 2; off > 0; off >>= 1) {
+                const double oc = __shfl_xor(bc, off, kWave);
+                const int ol = __shfl_xor(bl, off, kWave);
+                if (ol < kWave && (bl >= kWave || oc < bc || (oc == bc && ol < bl))) { bc = oc; bl = ol; }
+            }
+            if (bl >= kWave || bc > coarse_cost) bl = -1;  // queue empty / `cost > coarse cost` ends the loop (:303-304)
+            pop[u] = bl;
+            if (bl < 0) alive = false;  // nothing further is ever popped
+            if (lane == bl) alive = false;
+        }
+        if (pop[0] < 0) break;
+        int mine = pop[0];
+#pragma unroll
+        for (int u = 1; u < kRefineWaves; ++u) mine = (wave == u) ? pop[u] : mine;
+        if (mine >= 0) {
+            const double cx[3] = {__shfl(my_x[0], mine, kWave), __shfl(my_x[1], mine, kWave), __shfl(my_x[2], mine, kWave)};
+#if defined(FP_PHASE_STAMPS)
+            const uint32_t fl = wave_traj_flags<NCH>(ka, b, eg, cx, L, nx, lane, (wave == 0 && grp == 0 && fa.io.best_traj) ? fa.io.best_traj + ((size_t)b * FP_ARR_COUNT + 15) * fa.io.traj_stride + 112 : nullptr, t_begin);
+#else
+            uint32_t fl;
+            // (rule instances: inlined here - as a call the check takes the kernel's argument block through a stack copy - scratch)
+            if constexpr (kRules) [[clang::always_inline]] fl = wave_traj_flags<NCH>(ka, b, eg, cx, L, nx, lane);
+            else fl = wave_traj_flags<NCH>(ka, b, eg, cx, L, nx, lane);
+            if constexpr (kRules) {  // a candidate that is feasible by its own word: the enforced rules decide
+                uint32_t rule_hit = 0u;
+                if (!(fl & FP_FLAG_INFEASIBLE)) {
+                    // the word fp_rules_eval leaves for this end state: rules_eval_kernel's prologue (no trajectory, or nothing to check:
+                    // the word stays), then the rules of frenet_rules.h on the tables staged above
+                    int M = (int)(fl >> FP_FLAG_M_SHIFT);
+                    const int N = (cx[2] == cx[2]) ? arange_len(cx[2], p.tick_t) : 0;
+                    if (N > 0 && N <= points_cap(p) && cx[0] == cx[0] && cx[1] == cx[1] && M > 1) {
+                        if (M > N) M = N;
+                        const Quintic lat = quintic_bvp(eg[3], eg[4], eg[5], cx[0], 0.0, 0.0, cx[2]);
+                        const Quartic lon = quartic_bvp(eg[0], eg[1], eg[2], cx[1], 0.0, cx[2]);
+                        uint32_t spoke;
+                        fl = wave_rules_eval(ka, fa.rules, rule_ego, rule_tabs, rule_c, lon, lat, M, fl, lane, spoke);
+                    }
+                    rule_hit = (fl & FP_FLAG_INFEASIBLE) ? 1u : 0u;
+                }
+                if (lane == 0) rule_verdict[(grp & 1) * kRefineWaves + wave] = rule_hit;
+            }
+#endif
+            if (lane == 0) verdict[(grp & 1) * kRefineWaves + wave] = fl;
+        }
+        __syncthreads();
+        FP_RSTAMP(3 + (grp < 6 ? grp : 6));
+        bool done = false;
+#pragma unroll
+        for (int u = 0; u < kRefineWaves; ++u) {
+            if (done) continue;
+            if (pop[u] < 0) { done = true; continue; }
+            const uint32_t fl = verdict[(grp & 1) * kRefineWaves + u];
+            ++validated;
+            if constexpr (kRules) rejected += (int)rule_verdict[(grp & 1) * kRefineWaves + u];
+            if (fl & (FP_FLAG_CONSTRAINTS | (kRules ? FP_FLAG_BOUNDARY : 0u))) continue;
+            ++checks;
+            if (!(fl & FP_FLAG_COLLISION)) { winner = pop[u]; done = true; }
+        }
+        if (done) break;
+#if defined(FP_RABL) && FP_RABL >= 4  // timing ablation: at most FP_RABL - 3 validation groups
+        if (grp >= FP_RABL - 4) break;
+#endif
+    }
+    if (wave == 0) {
+        if (fa.io.trace && lane < R * 7) {
+            double* tr = fa.io.trace + ((size_t)b * R * 7 + lane) * 4;
+            const bool have = lane < ncand;
+            tr[0] = have ? my_x[0] : nan; tr[1] = have ? my_x[1] : nan; tr[2] = have ? my_x[2] : nan; tr[3] = have ? my_cost : nan;
+        }
+        if (lane == 0) {
+            int32_t* s4 = fa.io.stats + (size_t)b * 4;
+            s4[1] += ncand;
+            s4[2] += validated;
+            s4[3] += checks;
+            if constexpr (kRules)
+                if (fa.rejected && rejected != 0) fa.rejected[b] = fa.rejected[b] + rejected;  // (the ego's entry is this workgroup's alone)
+            fa.io.best_cost[b] = coarse_cost;  // same evaluator as the refined costs
+        }
+        if (winner >= 0 && lane == winner) {
+            fa.io.refined[b] = 1;
+            fa.io.best_cost[b] = my_cost;
+            double* es = fa.io.end_state + (size_t)b * 3;
+            es[0] = my_x[0]; es[1] = my_x[1]; es[2] = my_x[2];
+        }
+    }
+    if (tid == 0 && dur) dur[b] = (int)(wall_clock64() - t_begin);  // 10 ns ticks: feeds the next launches' order
+    // winner epilogue (what plan() returns) on request: the series of the refined trajectory, or of the coarse winner when no
+    // refined one survived.  Every wavefront holds the same candidate list; wavefront 0 writes the series (two time points per
+    // lane, no barrier), the others are done.
+#if defined(FP_RABL) && FP_RABL == 2  // timing ablation: no series
+    return;
+#endif
+    if ((fa.io.best_traj || ka.has_loop) && wave == 0) {
+        double fx[3];
+#pragma unroll
+        for (int m = 0; m < 3; ++m) fx[m] = winner >= 0 ? __shfl(my_x[m], winner, kWave) : coarse_x[m];
+        if (fa.io.best_traj) {
+            KernelArgs kw = ka;
+            kw.r.best_traj = fa.io.best_traj;
+            kw.r.best_flags = fa.io.best_flags;
+            kw.r.traj_stride = fa.io.traj_stride;
+            kw.r.traj_sparse = fa.io.traj_sparse;
+            FP_RSTAMP(10);
+            bool long_series = false;
+            if constexpr (NCH > 2) {  // more points than the one-chunk writer holds: the chunked writer (frenet_winner.h), same arithmetic per element
+                const int n_pts = (fx[2] == fx[2]) ? arange_len(fx[2], p.tick_t) : 0;
+                long_series = n_pts > kSeriesChunk && n_pts <= points_cap(p) && (fx[0] == fx[0]) && (fx[1] == fx[1]);
+                if (long_series) winner_series_wave_long(kw, b, b, fx[0], fx[1], fx[2], lane, SplineLds{L.knots, L.coef, nx, nx});
+            }
+            if (!long_series) winner_series_wave(kw, b, b, true, fx[0], fx[1], fx[2], lane, SplineLds{L.knots, L.coef, nx, nx});
+            FP_RSTAMP(11);
+            FP_RSTAMP(0);
+        }
+        // fp_plan_fiss_step: the workgroup that settled the ego's trajectory hands the ego over to its next state itself (after the
+        // series, which describe the trajectory from the OLD state; every other wavefront of the workgroup is done with the state,
+        // and no other workgroup reads it) - no advance_kernel launch behind the pipeline
+        // (the hand-over's arguments are re-read from the kernel's argument segment HERE, through a laundered pointer: as ordinary kernel
+        // arguments the compiler loads the loop structure's eleven fields at the kernel's start and holds them - 47 more spilled SGPRs
+        // and, through their lanes, two spilled VGPRs in a kernel that is at its register budget)
+        if (ka.has_loop && lane == 0) {
+            int off = (int)offsetof(FissArgs, ka);
+            asm volatile("" : "+s"(off) : : "memory");  // (an offset the compiler cannot see through: the loads below depend on it and stay here)
+            const KernelArgs& kl = *(const KernelArgs*)((const unsigned char*)__builtin_amdgcn_kernarg_segment_ptr() + off);
+            advance_ego_to(kl, b, fx[0], fx[1], fx[2], kl.loop);
+        }
+    }
 }
 
 namespace {
@@ -1007,31 +1262,30 @@ RefineShape refine_shape(const FissArgs& fa, int table_kb)
     return s;
 }
 
+// picks the instance (its LDS attribute: one set of slots per instance, launch_with_lds) and launches it
+template <class Args>
+hipError_t launch_refine_instance(const Args& fa, const RefineShape& s, int bytes, hipStream_t stream, const int* perm, int* dur)
+{
+    const dim3 grid(fa.ka.b.B), block(kWave * kRefineWaves);
+    return s.big ? launch_with_lds<fiss_refine_kernel<4, Args>>(grid, block, bytes, stream, fa, s.pt_rows, perm, dur)
+                 : launch_with_lds<fiss_refine_kernel<2, Args>>(grid, block, bytes, stream, fa, s.pt_rows, perm, dur);
+}
+
 }  // namespace
 
 hipError_t launch_fiss_refine(const FissArgs& fa, hipStream_t stream, int table_kb, const int* perm, int* dur)
 {
     const RefineShape s = refine_shape(fa, table_kb);
-    static LdsSlots configured;
-    static LdsSlots configured_big;
-    if (s.big) {
-        hipError_t e = ensure_dynamic_lds((const void*)fiss_refine_kernel<4>, s.bytes, configured_big);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(fiss_refine_kernel<4>, dim3(fa.ka.b.B), dim3(kWave * kRefineWaves), s.bytes, stream, fa, s.pt_rows, perm, dur);
-        return hipGetLastError();
-    }
-    hipError_t e = ensure_dynamic_lds((const void*)fiss_refine_kernel<2>, s.bytes, configured);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(fiss_refine_kernel<2>, dim3(fa.ka.b.B), dim3(kWave * kRefineWaves), s.bytes, stream, fa, s.pt_rows, perm, dur);
-    return hipGetLastError();
+    return launch_refine_instance(fa, s, s.bytes, stream, perm, dur);
 }
 
-// The rule instances: the refinement's layout, 32 bytes of rule verdicts, the rules' tables.
+// The rule instances: the refinement's layout, 32 bytes of rule verdicts, the rules' tables (frenet_rules.h), the obstacle sizes [n_obs][4]
+// of the gaps.
 void fiss_refine_rules_lds(const FissArgs& fa, uint32_t on, int table_kb, int* base_bytes, int* rule_bytes)
 {
     const RefineShape s = refine_shape(fa, table_kb);
     *base_bytes = (s.bytes + 15) & ~15;
-    *rule_bytes = 32 + 8 * rule_lds_doubles(on, fa.ka.b.NX, points_cap(fa.ka.p), (on & FP_RULE_GAP) ? fa.ka.b.n_obs : 0);
+    *rule_bytes = (int)(32 + 8 * (rule_table_doubles(on, fa.ka.p, fa.ka.b.NX) + ((on & FP_RULE_GAP) ? 4L * fa.ka.b.n_obs : 0L)));
 }
 
 hipError_t launch_fiss_refine_rules(const FissArgs& fa, const RulesEvalArgs& rules, int32_t* rejected, hipStream_t stream, int table_kb, const int* perm, int* dur)
@@ -1046,19 +1300,8 @@ hipError_t launch_fiss_refine_rules(const FissArgs& fa, const RulesEvalArgs& rul
     if (fr.rules.first > FP_MAX_POINTS) fr.rules.first = FP_MAX_POINTS;  // (as launch_rules_eval: beyond every pose either way)
     fr.rejected = rejected;
     fr.rules_off = base + 32;
-    const int bytes = base + own;
-    static LdsSlots configured;
-    static LdsSlots configured_big;
-    if (s.big) {
-        hipError_t e = ensure_dynamic_lds((const void*)fiss_refine_rules_kernel<4>, bytes, configured_big);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(fiss_refine_rules_kernel<4>, dim3(fa.ka.b.B), dim3(kWave * kRefineWaves), bytes, stream, fr, s.pt_rows, perm, dur);
-        return hipGetLastError();
-    }
-    hipError_t e = ensure_dynamic_lds((const void*)fiss_refine_rules_kernel<2>, bytes, configured);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(fiss_refine_rules_kernel<2>, dim3(fa.ka.b.B), dim3(kWave * kRefineWaves), bytes, stream, fr, s.pt_rows, perm, dur);
-    return hipGetLastError();
+    rule_table_offsets(fr.rules, 0, fa.ka.b.NX);  // (relative to smem + rules_off)
+    return launch_refine_instance(fr, s, base + own, stream, perm, dur);
 }
 
 hipError_t launch_fiss_search(const FissArgs& fa, hipStream_t stream)

@@ -40,13 +40,6 @@ constexpr uint32_t kPayCfail = 1u;  // fails check_constraints
 constexpr uint32_t kPayColl = 2u;   // collides
 constexpr uint32_t kPayNan = 4u;    // cost_final is NaN (a NaN centre puts nothing on the frontier)
 
-__device__ __forceinline__ void wave_lds_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // lowest set rank of a bit set over ranks (word k of lane L holds ranks 2048 k + 32 L .. + 31); -1 when empty.  Wave-uniform.
 template <int NW>
 __device__ __forceinline__ int lowest_rank(const uint32_t (&w)[NW])

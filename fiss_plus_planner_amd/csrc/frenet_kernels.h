@@ -299,10 +299,10 @@ struct RulesEvalArgs {
     const int32_t* perm = nullptr;
 };
 hipError_t launch_rules_eval(const KernelArgs& ka, RulesEvalArgs a, hipStream_t stream);
-// fp_plan_fiss_rules: the refinement whose popped candidates are also checked against the enforced rules (fiss_refine_rules_kernel,
-// frenet_fiss.hip).  rules = the rule set as launch_rules_eval takes it (K, end_states, flags, rule_bits, counts, perm
-// and the off_* fields are not read); rejected [B] in/out or nullptr; rules_off = where the rules' tables start in LDS, in bytes
-// (filled in by the launcher).
+// fp_plan_fiss_rules: the refinement whose popped candidates are also checked against the enforced rules (fiss_refine_kernel<NCH, FissRulesArgs>,
+// frenet_fiss.hip).  rules = the rule set as launch_rules_eval takes it (K, end_states, flags, rule_bits, counts and perm
+// are not read); rejected [B] in/out or nullptr; rules_off = where the rules' tables start in LDS, in bytes, the off_* fields relative to
+// it (both filled in by the launcher).
 struct FissRulesArgs : FissArgs {
     RulesEvalArgs rules;
     int32_t* rejected = nullptr;

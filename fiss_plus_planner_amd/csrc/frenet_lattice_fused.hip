@@ -92,15 +92,6 @@ __device__ __forceinline__ int lanes_below(unsigned long long m)
     return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
 }
 
-// Orders the LDS accesses of ONE wavefront for the compiler (the hardware executes a wavefront's LDS instructions in program order):
-// what lanes wrote before it, other lanes of the same wavefront read after it.  No instruction is emitted.
-__device__ __forceinline__ void wave_lds_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // Hand-over wait of the workgroups appended to a launch (winner-series epilogue, FISS+ search): spin on the ego's flag - set by the
 // lattice workgroup that published the ego's results - for at most kHandoverTimeout ticks of the 100 MHz wall clock.  A wait that
 // runs out (only possible if the workgroup distributors did NOT start this XCD's lattice workgroups before this one, see the kernel)

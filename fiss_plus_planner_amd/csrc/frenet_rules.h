@@ -147,17 +147,19 @@ __device__ __forceinline__ bool gap_pose_hit(const KernelArgs& ka, const EgoCtx&
 }
 
 // ---- the four rules on one explicit trajectory, evaluated by a whole wavefront (rules_eval_kernel per end state, the fallback
-// kernel's rule instance per candidate): the tables a workgroup stages once per ego, the call's constants, and the evaluation.
+// kernel's rule instance per candidate, the FISS+ refinement's rule instance per popped candidate): the tables a workgroup stages once
+// per ego, the call's constants, and the evaluation.
 constexpr int kRulesSplit = 8;  // at most this many lanes share one pose's columns (the gaps)
 
 // The rules' own tables in LDS, behind stage_ego's layout at a.off_lim / off_edge / off_gate (doubles): limits [NX] | l0, l1, r0, r1
 // [NX] each | gate lines [FP_MAX_GATES], closed words [points_cap].  closed = the frame's words in global memory (a point beyond the cap).
 struct RuleTables {
-    const double *lim, *l0, *l1, *r0, *r1, *line;
-    const uint32_t *word, *closed;
+    double *lim, *l0, *l1, *r0, *r1, *line;
+    uint32_t* word;
+    const uint32_t* closed;
 };
 // doubles the tables of the rules in `on` take
-inline long rule_table_doubles(uint32_t on, const fp_params& p, int NX)
+__host__ __device__ inline long rule_table_doubles(uint32_t on, const fp_params& p, int NX)
 {
     long own = 0;
     if (on & FP_RULE_LIMIT) own += NX;
@@ -174,43 +176,50 @@ inline void rule_table_offsets(RulesEvalArgs& a, int off, int NX)
     if (a.on & FP_RULE_BOUNDARY) off += 4 * NX;
     a.off_gate = off;
 }
-// Stage them with the workgroup's nth threads (after stage_ego; the caller's barrier follows): the limit of every segment, the
-// corridor (stage_corridor), the gate lines with the waiver folded in - taken from the ego's present state -, the mask of the live
-// slots (*s_live, one LDS word, written by wavefront 0) and the closed words of the steps t_now + 1 .. t_now + points_cap.
+// the tables of ego b in the layout that starts at lds (every wavefront of the workgroup: the addresses alone)
+__device__ __forceinline__ RuleTables rule_tables(const KernelArgs& ka, const RulesEvalArgs& a, int b, double* lds)
+{
+    const int NX = ka.b.NX;
+    RuleTables t;
+    t.lim = lds + a.off_lim;
+    t.l0 = lds + a.off_edge;
+    t.l1 = t.l0 + NX;
+    t.r0 = t.l1 + NX;
+    t.r1 = t.r0 + NX;
+    t.line = lds + a.off_gate;
+    t.word = (uint32_t*)(t.line + FP_MAX_GATES);
+    t.closed = (a.on & FP_RULE_GATE) ? a.closed + (size_t)ka.b.frame_of[b] * a.T_gate : nullptr;
+    return t;
+}
+// Stage them with nth threads of the workgroup, numbered tid = wave * kWave + lane (after stage_ego; the caller's barrier follows): the
+// limit of every segment, the corridor (stage_corridor), the gate lines with the waiver folded in - taken from the ego's present state -,
+// the mask of the live slots (*s_live, one LDS word, written by wavefront 0) and the closed words of the steps t_now + 1 .. t_now + points_cap.
 __device__ __forceinline__ RuleTables stage_rule_tables(const KernelArgs& ka, const RulesEvalArgs& a, int b, const EgoCtx& e, double* lds, uint32_t* s_live,
                                                         int tid, int wave, int lane, int nth)
 {
     const int f = ka.b.frame_of[b], nx = e.sp.nx, NX = ka.b.NX;
     const int cap = points_cap(ka.p), t_last = a.T_gate - 1;
     const long long tn = e.t_now;
-    double* lim = lds + a.off_lim;
-    double* l0 = lds + a.off_edge;
-    double* l1 = l0 + NX;
-    double* r0 = l1 + NX;
-    double* r1 = r0 + NX;
-    double* line = lds + a.off_gate;
-    uint32_t* word = (uint32_t*)(line + FP_MAX_GATES);
-    const bool gates = a.on & FP_RULE_GATE;
-    const uint32_t* closed = gates ? a.closed + (size_t)f * a.T_gate : nullptr;
+    const RuleTables t = rule_tables(ka, a, b, lds);
     if (a.on & FP_RULE_LIMIT) {
         const double* gl = a.v_limit + (size_t)f * NX;
-        for (int i = tid; i < nx; i += nth) lim[i] = i + 1 < nx ? gl[i] : __builtin_inf();  // (the last knot starts no segment)
+        for (int i = tid; i < nx; i += nth) t.lim[i] = i + 1 < nx ? gl[i] : __builtin_inf();  // (the last knot starts no segment)
     }
-    if (a.on & FP_RULE_BOUNDARY) stage_corridor(ka.b.knots + (size_t)f * NX, a.left + (size_t)f * NX, a.right + (size_t)f * NX, nx, nullptr, l0, l1, r0, r1, tid, nth);
-    if (gates) {
+    if (a.on & FP_RULE_BOUNDARY) stage_corridor(ka.b.knots + (size_t)f * NX, a.left + (size_t)f * NX, a.right + (size_t)f * NX, nx, nullptr, t.l0, t.l1, t.r0, t.r1, tid, nth);
+    if (a.on & FP_RULE_GATE) {
         if (wave == 0) {
             double g = __builtin_nan("");
             if (lane < a.gate_stride) {
                 g = a.gate_s[(size_t)f * a.gate_stride + lane];
                 if (gate_waived(a.max_decel, e.s_d0, e.s0 + a.gate_front, g)) g = __builtin_nan("");
             }
-            if (lane < FP_MAX_GATES) line[lane] = g;
+            if (lane < FP_MAX_GATES) t.line[lane] = g;
             const unsigned long long live = __ballot(g == g);
             if (lane == 0) *s_live = (uint32_t)live;
         }
-        for (int i = tid; i < cap; i += nth) word[i] = gate_word(closed, tn + 1 + i, t_last);
+        for (int i = tid; i < cap; i += nth) t.word[i] = gate_word(t.closed, tn + 1 + i, t_last);
     }
-    return RuleTables{lim, l0, l1, r0, r1, line, word, closed};
+    return t;
 }
 
 // What the evaluation needs beside the tables and does not depend on the trajectory (after the barrier behind stage_rule_tables)

@@ -7,16 +7,20 @@ plan_fiss_rules_device, ClosedLoopRunner(enforce=...)).
   3. the refinement, exact, by composition on the device: the call's own trace, eval_trajs' words of its rows, rules_eval's rule bits of
      those words, the pop loop of the contract in numpy;
   4. every case of tests/test_fiss_rules_cpu.py against the CPU reference (tests/fiss_rules_ref.py);
-  5. the winner's series; 6. the closed loop at the red light; 7. a launch order and a second call; 8. the errors of the C ABI.
+  5. the winner's series; 6. the closed loop at the red light; 7. a launch order and a second call; 8. the errors of the C ABI;
+  9. the outputs recorded before the rule instance shared the rules' evaluation, exactly.
 """
 import ctypes as C
 import dataclasses
+import os
 
 import numpy as np
 import pytest
 
+import fiss_rules_parent
 import fiss_rules_ref as FR
 import gates_ref as GR
+from conftest import GOLDEN
 from fiss_plus_planner_amd import _abi, rules, search, synth
 from fiss_plus_planner_amd.engine import host_structs
 
@@ -395,3 +399,14 @@ def test_errors_and_the_call_counter(engine):
     coarse = engine.plan_fiss(big, "FISS+", max_refine_iters=0, enforce=NAMES)
     ijk, stats, _, _, _ = host_walk(big, engine.plan_dense(big, tables=True, **{n: True for n in NAMES}), "FISS+", np.full((big.B, 3), -1, dtype=np.int32))
     assert np.array_equal(coarse.best_ijk, ijk) and np.array_equal(coarse.stats, stats)
+
+
+# ---------------------------------------------------------------- 9. the recorded outputs
+def test_outputs_are_the_recorded_ones(engine):
+    """Every output of the calls of tests/fiss_rules_parent.py, exactly as the library recorded them before the refinement's rule
+    instance took its rule evaluation from frenet_rules.h (tests/golden/fiss_rules_parent.npz)."""
+    want = np.load(os.path.join(GOLDEN, "fiss_rules_parent.npz"))
+    got = fiss_rules_parent.run_all(engine)
+    assert sorted(got) == sorted(want.files)
+    for k in want.files:
+        assert got[k].dtype == want[k].dtype and got[k].shape == want[k].shape and np.array_equal(got[k], want[k], equal_nan=got[k].dtype.kind == "f"), k
