@@ -1027,10 +1027,13 @@ __global__ __launch_bounds__(kWave * kRefineWaves, (std::is_same<Args, FissRules
             for (int m = 0; m < 3; ++m) {
                 res[m] *= fa.opts.decaying_factor;  // decays in place, like the reference's aliasing of sampling_res (:282)
                 xn[m] = x[m] - res[m] * g[m] / nrm;
-                xn[m] = fmin(fmax(xn[m], lo[m]), hi[m]);
                 nan_step |= !(xn[m] == xn[m]);
             }
-            if (nan_step) break;  // zero gradient: the reference raises inside np.arange(nan); refinement stops here
+            // zero gradient or x_r == x_l: the reference raises inside np.arange(nan); refinement stops here, the six probes stay
+            // candidates.  Tested on the UNCLIPPED step: fmin(fmax(NaN, lo), hi) is lo.
+            if (nan_step) break;
+#pragma unroll
+            for (int m = 0; m < 3; ++m) xn[m] = fmin(fmax(xn[m], lo[m]), hi[m]);
             if (lane == ncand) { my_x[0] = xn[0]; my_x[1] = xn[1]; my_x[2] = xn[2]; }
             pending = ncand;  // priced with the next round's probes, or below
             ncand += 1;

@@ -1070,9 +1070,11 @@ int orc_fissplus_plan(const orc_problem* p, double w_heuristic, int32_t max_refi
             for (int m = 0; m < 3; ++m) {
                 res[m] *= decaying_factor;
                 xn[m] = x[m] - res[m] * g[m] / nrm;
-                xn[m] = fmin(fmax(xn[m], p->samp_min[m]), p->samp_max[m]);
             }
-            if (!(xn[0] == xn[0]) || !(xn[1] == xn[1]) || !(xn[2] == xn[2])) break; /* reference raises in np.arange */
+            /* an undefined step (zero gradient, x_r == x_l) ends the rounds: the reference raises in np.arange.  Tested BEFORE the
+               clip: fmin(fmax(NaN, lo), hi) is lo */
+            if (!(xn[0] == xn[0]) || !(xn[1] == xn[1]) || !(xn[2] == xn[2])) break;
+            for (int m = 0; m < 3; ++m) xn[m] = fmin(fmax(xn[m], p->samp_min[m]), p->samp_max[m]);
             double Jn;
             if (orc_eval_traj(p, xn[0], xn[1], xn[2], 0, NULL, 0, NULL, NULL, &Jn, NULL)) break;
             stats[1] += 1;

@@ -55,7 +55,7 @@ def masked_tables(O, batch, b, prob, names):
 def plan(O, batch, b, kind, names, prev=None, max_refine_iters=3, decaying_factor=0.5, w_heuristic=10.0):
     """fp_plan_fiss_rules for ego b -> SimpleNamespace(best_ijk, end_state, best_cost, refined, stats, rejected, prev_best_idx, slack,
     cost_gap, undecided, popped_boundary_only (a sample whose only bit is 128 was popped before the winner), coarse_ijk_free (the coarse
-    winner without rules))."""
+    winner without rules), trace [n, 4] (the refinement's candidates in generation order: end state, cost))."""
     prob = R._problem(O, batch, b)
     nd, nv, nt = batch.nd, batch.nv, batch.nt
     cost, words, lat_slack = masked_tables(O, batch, b, prob, names)
@@ -73,7 +73,7 @@ def plan(O, batch, b, kind, names, prev=None, max_refine_iters=3, decaying_facto
     out = SimpleNamespace(best_ijk=np.full(3, -1, dtype=np.int32), end_state=np.full(3, np.nan), best_cost=np.nan, refined=False,
                           stats=np.array(stats, dtype=np.int32), rejected=0, prev_best_idx=np.full(3, -1, dtype=np.int32) if pv is None else pv.astype(np.int32),
                           slack=np.inf, cost_gap=np.inf, undecided=False, popped_boundary_only=False,
-                          coarse_ijk_free=np.full(3, -1) if free_idx is None else np.asarray(free_idx))
+                          coarse_ijk_free=np.full(3, -1) if free_idx is None else np.asarray(free_idx), trace=np.empty((0, 4)))
     # the pops of the cost-ordered validation: every generated sample that is not behind the winner in (cost, raster) order
     gen = [tuple(i) for i in order]
     key = lambda i: (float(J[i]), (i[0] * nv + i[1]) * nt + i[2])  # noqa: E731
@@ -115,6 +115,7 @@ def plan(O, batch, b, kind, names, prev=None, max_refine_iters=3, decaying_facto
             r = price(x_new)
             cand.append((r.cost, len(cand), x_new.copy(), (int(r.flags) & 0xFF) | (r.N << 8) | (r.M << 20)))
             x = x_new
+        out.trace = np.array([[*es, c] for c, _, es, _ in cand], dtype=np.float64).reshape(-1, 4)
         validated = checks = 0
         consumed = []
         for c, _, es, word in sorted(cand, key=lambda t: (t[0], t[1])):
